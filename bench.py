@@ -12,8 +12,13 @@ vs 3000 GT points, 963-dim features):
     -> (N>1: one RCCL all-reduce of the flat gradient bucket + the 8-byte loss vector)
     -> Adam step.
 All inputs are resident in HBM before the timed region.  Weak scaling: per-GPU work fixed.
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds every other figure: the
+unconditioned timing, the strong-scaling point (N > 1), per-kernel rooflines, component and configuration timings, the
+reference training shape and driver step, the CPU baseline and the parity spot check against the CPU oracle.
+--dump-outputs DIR writes what the last timed step computed (loss, parameters after its Adam step, a fixed row sample of
+the input-feature gradient) as DIR/<name>.npy, float32.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--meshes-per-gpu 8] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--meshes-per-gpu 8] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -1325,6 +1330,27 @@ def self_launch(n, argv):
     return rc
 
 
+DUMP_FEAT_GRAD_ROWS = 4096     # rows of the [meshes x vertices, 963] input-feature gradient written by --dump-outputs
+
+
+def dump_outputs(w, out_dir):
+    """What the timed path hands its caller after the last timed step, as float32 .npy files: the loss, every parameter
+    after that step's Adam update, and the gradient with respect to the input features -- a fixed, seeded sample of
+    DUMP_FEAT_GRAD_ROWS of its rows (all rows when there are no more; the whole tensor is ~79 MB at the default shard)."""
+    w.finish()         # N > 1: the Adam step the last timed step's all-reduce feeds
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(out_dir, name + ".npy"), np.array(a, dtype=np.float32, order="C"))
+    save("loss", np.float32(w.mean_loss()))
+    for name, p in w.stack.named_parameters():
+        save("param." + name, p.detach().cpu().numpy())
+    grad = w.feat.grad.detach().reshape(-1, w.feat.shape[-1])
+    if grad.shape[0] > DUMP_FEAT_GRAD_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(grad.shape[0], DUMP_FEAT_GRAD_ROWS, replace=False))
+        grad = grad[torch.from_numpy(rows).to(grad.device)]
+    save("feat_grad_rows", grad.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1334,7 +1360,13 @@ def main():
     ap.add_argument("--global-batch", type=int, default=0,
                     help="STRONG scaling: this many meshes in total, split evenly over the ranks (64 = BASELINE config 5's batch); "
                          "the line then says scaling: strong.  Default 0: weak scaling, --meshes-per-gpu on every rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the unconditioned timing, the strong-scaling point, per-kernel rooflines, component / "
+                         "configuration / training-shape / driver-step timings, the CPU baseline and the parity spot check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, parameters after its Adam step, a seeded row sample of the "
+                         "input-feature gradient) to DIR/<name>.npy in float32; same arguments, same inputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline and no parity spot check")
     ap.add_argument("--clock-warmup-ms", type=float, default=250.0,
                     help="neutral GEMM load in front of the warm-up steps so that short runs are not timed on the clock ramp (0: off)")
     ap.add_argument("--gt-index", action="store_true", help="culled Chamfer tiles on an index of the ground-truth clouds built OUTSIDE the "
@@ -1402,13 +1434,15 @@ def main():
             _lib.clear_hip_error()
     gdist.barrier()          # ranks finish their setup at different times: condition the devices together, so that
     # the same K steps behind the same W warm-up steps WITHOUT the conditioning load first (what --clock-warmup-ms 0 prints):
-    # reported beside the headline as ms_per_step_unconditioned
-    unconditioned = time_steps(w.run, args.steps, args.warmup) if args.clock_warmup_ms > 0 else None
+    # reported beside the headline as ms_per_step_unconditioned (--full only)
+    unconditioned = time_steps(w.run, args.steps, args.warmup) if args.clock_warmup_ms > 0 and args.full else None
     settle_clocks(dev, args.clock_warmup_ms)   # nobody idles at the barrier in front of the timed region and cools down again
     elapsed = time_steps(w.run, args.steps, args.warmup)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(w, args.dump_outputs)
     if unconditioned is None:
         unconditioned = elapsed
-    if world > 1:
+    if world > 1 and args.full:
         tu = torch.tensor([unconditioned], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tu, op=torch.distributed.ReduceOp.MAX)
         unconditioned = float(tu.item())
@@ -1423,7 +1457,7 @@ def main():
     elapsed, fastest = float(t[0].item()), -float(t[1].item())
     ranks_seen = int(round(float(seen.item())))
     strong = None
-    if (world > 1 or force_dp) and not args.global_batch and 64 % world == 0 and not args.steps_only:
+    if args.full and (world > 1 or force_dp) and not args.global_batch and 64 % world == 0 and not args.steps_only:
         try:
             strong = strong_scaling_point(dev, rank, world, force_dp, args.steps, args.warmup)
         except Exception as exc:          # every rank fails or none does (same code, same sizes): the headline still goes out
@@ -1438,7 +1472,6 @@ def main():
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
             "scaling": "strong" if args.global_batch else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "ranks_seen": ranks_seen,
-            "ms_per_step_unconditioned": round(unconditioned / args.steps * 1e3, 4),
             "ms_per_step_ranks": {"max": round(elapsed / args.steps * 1e3, 4), "min": round(fastest / args.steps * 1e3, 4),
                                   "rank0": round(own / args.steps * 1e3, 4)},
             "config": {"workload": "BASELINE config 5 shard: %d independent 2562-vert/5120-face meshes per GPU, full "
@@ -1458,11 +1491,13 @@ def main():
                         "gradient] ; the launch stream waits for the collective")},
             "final_loss": round(w.mean_loss(), 6),
         }
+        if args.full:
+            line["ms_per_step_unconditioned"] = round(unconditioned / args.steps * 1e3, 4)
         if strong is not None:
             line["strong_scaling"] = strong
         if per_gpu == 8:
             line["step_level"] = step_level_roofline(total_meshes / elapsed / world)     # per GPU
-        if not args.steps_only:
+        if args.full and not args.steps_only:
             try:
                 roofline, others = kernel_rooflines(w)
                 line["roofline"] = roofline
@@ -1480,7 +1515,7 @@ def main():
             except Exception as exc:
                 print("bench.py: %s failed (%s: %s)" % (key, type(exc).__name__, exc), file=sys.stderr)
                 line[key] = {"error": "%s: %s" % (type(exc).__name__, str(exc)[:300])}
-        if world == 1 and not force_dp and not args.steps_only:
+        if args.full and world == 1 and not force_dp and not args.steps_only:
             extra("components_us", lambda: component_times(w))
             extra("configs", lambda: baseline_configs(dev))
             extra("split_bf16_experiment", lambda: split_bf16_experiment(dev))
@@ -1492,7 +1527,7 @@ def main():
                 wb = line["whole_batch_single_gpu"]        # N = 1: the strong-scaling point IS the whole batch on this GPU
                 line["strong_scaling"] = {"global_batch": 64, "meshes_per_gpu": 64, "scaling": "strong", "ms_per_step": wb["ms_per_step"],
                                           "meshes_per_s": wb["meshes_per_s"], "final_loss": wb["final_loss"]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             extra("cpu_baseline", cpu_baseline)
             extra("parity_spot_check", lambda: parity_spot_check(w))
         if force_dp:

@@ -202,6 +202,10 @@ def run_sync_bn_capture(port, total, out):
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     eager = [t.clone() for t in keep["out"]] + [f.grad.clone(), p.grad.clone()] + [q.grad.clone() for q in block.parameters() if q.grad is not None]
+    # RCCL's watchdog thread polls the end events of the eager all-reduces until it retires them; a poll that lands after the
+    # capture has pulled RCCL's stream in fails (hipErrorCapturedEvent) and terminates the process.  Capture only once the
+    # watchdog holds no work.
+    dist.group.WORLD._wait_for_pending_works()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=side, capture_error_mode="relaxed"):
         step()

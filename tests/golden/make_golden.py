@@ -176,6 +176,54 @@ def make_nn_fma():
     save("nnfma_outputs", **out)
 
 
+def make_refbin():
+    """The reference's nnsearch binaries (plain build, seeds 0-3; FMA build, seeds 40-43) on seeded random clouds, inputs
+    and outputs stored: tests/test_oracle_pin.py pins the oracle to them wherever the binaries cannot be built."""
+    assert oracle.have_ref_fma(), "needs oracle/_ref/libref_nnsearch_fma.so and an FMA-capable host"
+    out = {}
+    for kind, seeds, fn in (("plain", range(4), oracle.ref_nnsearch), ("fma", range(40, 44), oracle.ref_nnsearch_fma)):
+        for seed in seeds:
+            rng = np.random.default_rng(seed)
+            n, m = int(rng.integers(1, 700)), int(rng.integers(1, 700))
+            a = rng.standard_normal((2, n, 3)).astype(np.float32)
+            b = (rng.integers(-2, 3, (2, m, 3)) if seed % 2 else rng.standard_normal((2, m, 3))).astype(np.float32)
+            d, i = fn(a, b)
+            key = "%s%d." % (kind, seed)
+            out.update({key + "xyz1": a, key + "xyz2": b, key + "dist": d, key + "idx": i})
+    save("refbin_nnsearch", **out)
+
+
+def make_overlay_names():
+    """What tests/test_overlay.py needs of the reference checkout, as data: the public names of the reference's utils.py
+    and models.py as the overlay executes them, the names utils.py imports from chamfer_distance / tri_distance, and the
+    names each driver (GEOMetrics.py, auto_encoder.py) loads without binding them itself (its star-imports' share)."""
+    import ast
+    import json
+    import subprocess
+    tests = os.path.dirname(HERE)
+    sys.path.insert(0, tests)
+    import test_overlay
+    probe = ("OVERLAY=%r; ROOT=%r; REF=%r\n" % (os.path.join(ROOT, "overlay"), ROOT, REF) + test_overlay.PROBE.split("import utils,")[0]
+             + "import json, utils, models\n"
+             + "pub = lambda m: sorted(k for k in vars(m) if not k.startswith('__'))\n"
+             + "print('JSON', json.dumps({'utils': pub(utils._reference_utils), 'models': pub(models._reference_models)}))\n")
+    out = subprocess.run([sys.executable, "-c", probe], env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"), cwd=REF,
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    names = json.loads([l for l in out.stdout.splitlines() if l.startswith("JSON ")][0][5:])
+    imports = {}
+    for node in ast.walk(ast.parse(open(os.path.join(REF, "utils.py")).read())):
+        if isinstance(node, ast.ImportFrom) and node.module in ("chamfer_distance", "tri_distance"):
+            imports.setdefault(node.module, []).extend(a.name for a in node.names)
+    fixture = {"modules": names, "utils_imports": imports,
+               "drivers": {d: sorted(test_overlay._free_names(os.path.join(REF, d))) for d in ("GEOMetrics.py", "auto_encoder.py")}}
+    path = os.path.join(HERE, "overlay_names.json")
+    with open(path, "w") as f:
+        json.dump(fixture, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("%-28s %6.1f KB" % ("overlay_names.json", os.path.getsize(path) / 1024))
+
+
 # -------------------------------------------------------- sampling + losses ----
 def make_sampling_and_losses():
     V2, F2 = meshgen.icosphere(2)
@@ -448,11 +496,17 @@ if __name__ == "__main__":
     if "--tri-true" in sys.argv:
         make_tri_true()
         sys.exit(0)
+    if "--refbin" in sys.argv:
+        make_refbin()
+        make_overlay_names()
+        sys.exit(0)
     make_regularisers()
     if "--only-new" in sys.argv:
         sys.exit(0)
     make_nn()
     make_nn_fma()
+    make_refbin()
+    make_overlay_names()
     make_sampling_and_losses()
     make_adjacency()
     make_layers()

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -65,6 +66,29 @@ def test_bench_single_gpu_line_has_the_contract_fields(gpu):
         assert key in line
 
 
+@pytest.mark.timeout(600)
+def test_plain_line_is_lean_and_dumps_the_last_step(gpu, tmp_path):
+    """A plain run times its steps and prints the headline alone (everything else is --full); --dump-outputs writes what
+    the last timed step computed as float32 arrays, 64 MB at most, the same from run to run with the same arguments."""
+    args = ["--steps", "3", "--warmup", "1"]
+    a = _run(args + ["--dump-outputs", str(tmp_path / "a")])
+    b = _run(args + ["--dump-outputs", str(tmp_path / "b")])
+    for key in ("roofline", "cpu_baseline", "parity_spot_check", "driver_step", "configs", "ms_per_step_unconditioned"):
+        assert key not in a, key
+    assert a["steps"] == 3 and a["warmup"] == 1 and a["ms_per_step"] > 0 and a["final_loss"] == b["final_loss"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"loss.npy", "feat_grad_rows.npy", "param.0.weight1.npy", "param.2.bias.npy"} <= set(names)
+    total = 0
+    for name in names:
+        x, y = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert x.dtype == np.float32 and np.isfinite(x).all(), name
+        np.testing.assert_array_equal(x, y, err_msg=name)
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")) - a["final_loss"]) <= 1e-6 * (1 + abs(a["final_loss"]))
+
+
 def test_more_ranks_than_devices_is_refused_loudly(gpu):
     import torch
     n = torch.cuda.device_count() + 1
@@ -80,7 +104,7 @@ def test_bench_whole_n_gt_1_path_with_rccl_on_one_gpu(gpu):
     asynchronous all-reduce, the timed loop AND the per-kernel probes that follow it with RCCL's watchdog thread alive -- in
     a 1-rank group on this GPU.  What an 8-GPU node will run, minus the other seven ranks; the line must come out complete
     (the probes capture thread-locally, so that the watchdog's event polling cannot invalidate their captures)."""
-    line = _run(["--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--clock-warmup-ms", "0"], {"GEOM_BENCH_FORCE_DP": "1"})
+    line = _run(["--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline", "--clock-warmup-ms", "0"], {"GEOM_BENCH_FORCE_DP": "1"})
     assert line["n_gpus"] == 1 and line["ranks_seen"] == 1 and "forced_dp" in line["config"]
     assert line["config"]["dp_sequence"].startswith("per step ONE graph")     # the collective was captured into the step graph
     assert line["config"]["launch"] == "hipgraph" and line["value"] > 0

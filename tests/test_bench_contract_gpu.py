@@ -1,4 +1,4 @@
-"""-m gpu: `python bench.py` end to end with a handful of steps -- the JSON line must carry the driver's contract
+"""-m gpu: `python bench.py --full` end to end with a handful of steps -- the JSON line must carry the driver's contract
 (metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data /
 config.workload) plus the `roofline` and `cpu_baseline` objects, with a roofline fraction that is a fraction."""
 import json
@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.timeout(600)
 def test_bench_line_carries_the_contract(gpu):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2"], cwd=ROOT,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full"], cwd=ROOT,
                          capture_output=True, text=True, timeout=560)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

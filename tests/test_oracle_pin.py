@@ -1,6 +1,6 @@
 """CPU: pin the oracle against the golden vectors the REFERENCE produced
-(tests/golden/make_golden.py) and, when it is present, against the reference's own
-nnsearch binary (oracle/_ref)."""
+(tests/golden/make_golden.py), among them the outputs of the reference's own nnsearch
+binary (oracle/_ref), and against that binary itself when it is present."""
 
 import numpy as np
 import pytest
@@ -39,17 +39,24 @@ def test_nn_scan_config2_reference_outputs():
     np.testing.assert_array_equal(bits(d1), bits(g["dist1"]))
 
 
-@pytest.mark.skipif(not oracle.have_ref(), reason="oracle/_ref (reference nnsearch) not built here")
+def _refbin_case(kind, seed):
+    """Seeded random clouds and what the reference's nnsearch binary (`kind` "plain" or "fma" build) returned on them
+    (tests/golden/refbin_nnsearch.npz, written by make_golden.py from oracle/_ref)."""
+    g = golden("refbin_nnsearch")
+    key = "%s%d." % (kind, seed)
+    return g[key + "xyz1"], g[key + "xyz2"], g[key + "dist"], g[key + "idx"]
+
+
 @pytest.mark.parametrize("seed", range(4))
 def test_nn_scan_equals_live_reference_binary(seed):
-    rng = np.random.default_rng(seed)
-    n, m = int(rng.integers(1, 700)), int(rng.integers(1, 700))
-    a = rng.standard_normal((2, n, 3)).astype(np.float32)
-    b = (rng.integers(-2, 3, (2, m, 3)) if seed % 2 else rng.standard_normal((2, m, 3))).astype(np.float32)
+    a, b, d_ref, i_ref = _refbin_case("plain", seed)
     d, i = oracle.nn_scan(a, b)
-    dr, ir = oracle.ref_nnsearch(a, b)
-    np.testing.assert_array_equal(i, ir)
-    np.testing.assert_array_equal(bits(d), bits(dr))
+    np.testing.assert_array_equal(i, i_ref)
+    np.testing.assert_array_equal(bits(d), bits(d_ref))
+    if oracle.have_ref():                   # and the binary itself, where build() could compile it
+        dr, ir = oracle.ref_nnsearch(a, b)
+        np.testing.assert_array_equal(i, ir)
+        np.testing.assert_array_equal(bits(d), bits(dr))
 
 
 def _nn_case_inputs(name):
@@ -77,17 +84,16 @@ def test_nn_fma_arithmetic_matches_the_fma_built_reference_vectors(name):
     np.testing.assert_allclose(d1, g["dist1"], rtol=1e-6, atol=1e-12)
 
 
-@pytest.mark.skipif(not oracle.have_ref_fma(), reason="oracle/_ref FMA build (or an FMA-capable host) not available")
 @pytest.mark.parametrize("seed", range(4))
 def test_nn_fma_scan_equals_live_fma_built_reference_binary(seed):
-    rng = np.random.default_rng(40 + seed)
-    n, m = int(rng.integers(1, 700)), int(rng.integers(1, 700))
-    a = rng.standard_normal((2, n, 3)).astype(np.float32)
-    b = (rng.integers(-2, 3, (2, m, 3)) if seed % 2 else rng.standard_normal((2, m, 3))).astype(np.float32)
+    a, b, d_ref, i_ref = _refbin_case("fma", 40 + seed)
     d, i = oracle.nn_scan_fma(a, b)
-    dr, ir = oracle.ref_nnsearch_fma(a, b)
-    np.testing.assert_array_equal(i, ir)
-    np.testing.assert_array_equal(bits(d), bits(dr))
+    np.testing.assert_array_equal(i, i_ref)
+    np.testing.assert_array_equal(bits(d), bits(d_ref))
+    if oracle.have_ref_fma():               # and the binary itself, where build() could compile it and the host has FMA
+        dr, ir = oracle.ref_nnsearch_fma(a, b)
+        np.testing.assert_array_equal(i, ir)
+        np.testing.assert_array_equal(bits(d), bits(dr))
 
 
 def test_tail_truncation_quirks():

@@ -13,6 +13,6 @@ python tools/dense_pmc_json.py gpurun_out $OUT/r04_dense_pmc.json
 python tools/shorten_stats.py $(ls /tmp/ts/*/t_kernel_stats.csv /tmp/ts/t_kernel_stats.csv 2>/dev/null | head -1) $OUT/r04_training_shape_kernel_stats.csv
 bash tools/probe/dp_trace.sh > $OUT/r04_dp_step_timeline.txt 2>&1
 python tools/time_force_dp.py 2>&1 | grep force_dp > $OUT/time_force_dp.txt
-python bench.py > $OUT/r04_bench_default_run.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/r04_bench_default_run.json 2> $OUT/bench_default.err
 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_form.json 2>/dev/null
 ls -la $OUT

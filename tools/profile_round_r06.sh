@@ -16,6 +16,6 @@ python tools/time_driver_step.py --zero-edit 2>&1 | grep -v amdgpu.ids > $OUT/r0
 python tools/time_split_bf16.py 2>&1 | grep -v amdgpu.ids > $OUT/r06_split_bf16_experiment.txt
 python tools/time_force_dp.py 2>&1 | grep -v amdgpu.ids > $OUT/r06_dp_fixed_cost.txt
 cp $OUT/r06_pmc_counters.json $OUT/r06_step_kernel_stats.csv profiles/     # (on the box: the bench line reads its counter-derived fields from the profiles of THESE sources)
-python bench.py > $OUT/r06_bench_default_run.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/r06_bench_default_run.json 2> $OUT/bench_default.err
 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_form.json 2>/dev/null
 ls -la $OUT
