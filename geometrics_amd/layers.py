@@ -8,7 +8,6 @@ the tensor's identity + version) and replaces the reference's dense `adj @ suppo
 `torch.cat` and bias add by one fused HIP kernel (csrc/zn_gcn.hip); the dense feature GEMM
 `input @ W` stays a library GEMM (rocBLAS/hipBLASLt through torch.matmul).
 """
-import ctypes
 import math
 import os
 import threading
@@ -21,8 +20,12 @@ from torch.nn import Module
 from torch.nn.parameter import Parameter
 
 from . import _lib
+from . import backward_pass as _pass
 from . import dense as _dense_kernels
 from . import fused as _fused
+# (re-exported: bench.py and dist.py use the public names, models, ops, deform and the tests the private ones)
+from .backward_pass import (_alias, _gradient_buffer, bind_gradient_targets, deferred_parameter_gradients,  # noqa: F401
+                            late_input_gradients)
 
 _ACT_NONE, _ACT_RELU, _ACT_ELU = 0, 1, 2
 
@@ -168,357 +171,19 @@ def aggregate_forward(s, bias_c, csr, k, act, out, want_mask=False):
     return mask
 
 
-# ---- bias gradients of a whole backward pass finished in ONE launch -----------------------------------------------
-# The aggregation backward leaves per-workgroup partial column sums; reducing them is a launch-floor kernel (4.7 us) per
-# layer -- 14 of them in a deformation block.  Inside an autograd backward pass the reduction is postponed instead: the
-# partials are queued, and a callback at the END of the pass (the engine's queue_callback, what DDP uses for its own
-# finalisation) reduces all of them with one geom_colsum_batch_f32 launch on the stream they were produced on.  The
-# bias gradient handed to autograd is therefore complete when backward() returns, but not while the pass is running;
-# a pass in which something could read it earlier -- an existing .grad to accumulate into, a hook on the bias, a bias that
-# receives gradients from more than one node (the engine adds them on arrival) -- takes the immediate reduction, and so
-# does every call outside an engine-run pass.
-# Deferral is OPT-IN (round-2 advice): what cannot be seen from here -- C++ hooks on the AccumulateGrad node (torch DDP's
-# Reducer copies the gradient into its bucket on arrival), a second consumer of the parameter that is a plain torch op --
-# would read the placeholder before the flush.  bench.py and the deformation block's own training step switch it on
-# (`with layers.deferred_parameter_gradients():`), nothing else does; a placeholder is zero-filled when
-# `_zero_fill_deferred` is set (debugging aid: detect_anomaly trips over uninitialised memory otherwise).
-defer_parameter_gradients = False     # False: every bias / weight gradient is reduced where it is produced
-_zero_fill_deferred = False
-
-# Gradient targets (data-parallel steps: geometrics_amd.dist.GradBucket(bind=True)): a parameter bound to a tensor of its
-# shape gets its gradient WRITTEN THERE by the launches of this module -- the reduction launch at the end of the pass writes
-# straight into the flat all-reduce bucket, autograd adopts the tensor as `.grad` (a fresh, contiguous tensor object of
-# the parameter's layout is taken as is, not copied), and the bucket's pack launch has nothing left to gather.
-_gradient_targets = {}
-
-
-def bind_gradient_targets(params, tensors):
-    """`tensors[i]` (same shape / dtype / device as `params[i]`, contiguous) receives the gradient of `params[i]` from now on;
-    None unbinds.  Only gradients this module produces itself land there (a library-product fallback returns its own tensor)."""
-    for p, t in zip(params, tensors):
-        key = id(p)
-        if t is None:
-            _gradient_targets.pop(key, None)
-            continue
-        if t.shape != p.shape or t.dtype != p.dtype or t.device != p.device or not t.is_contiguous():
-            raise ValueError("a gradient target must match its parameter's shape, dtype and device and be contiguous")
-        _gradient_targets[key] = (weakref.ref(p, lambda _r, k=key: _gradient_targets.pop(k, None)), t)
-
-
-def _gradient_buffer(param, like):
-    """Where the gradient of `param` (may be None: unknown) goes: its bound target, else a new tensor like `like`."""
-    hit = _gradient_targets.get(id(param)) if param is not None else None
-    # (a parameter that already holds a gradient is being ACCUMULATED into: the new gradient must not overwrite the old one's
-    # memory, which is what the target is by then)
-    # (a parameter fed by more than one live autograd node -- a shared weight or bias, a layer applied twice -- has its
-    # gradients ADDED by the engine: each node needs memory of its own, or the second would overwrite the first's before the
-    # sum is formed; GradBucket.pack() gathers a gradient that did not land in its view by copy)
-    if (hit is not None and hit[0]() is param and hit[1].shape == like.shape and param.grad is None
-            and _bias_user_count(param) <= 1):
-        return hit[1].detach()           # a fresh tensor object over the target's memory (autograd adopts it as .grad)
-    return torch.zeros_like(like) if _zero_fill_deferred else torch.empty_like(like)
 use_matrix_core_products = True       # the layers' dense gradients on csrc/dense_gemm.hip where dense.plan says so
 use_any_shape_products = True         # every other width: csrc/dense_any.hip (False: the library's products)
-
-
-class deferred_parameter_gradients:
-    """Context manager: inside it, bias / weight gradients of a backward pass are finished by batched launches at the end
-    of the pass (the caller guarantees that nothing reads a parameter gradient before backward() returns)."""
-
-    def __init__(self, enabled=True):
-        self.enabled = enabled
-
-    def __enter__(self):
-        global defer_parameter_gradients
-        self.prev = defer_parameter_gradients
-        defer_parameter_gradients = self.enabled
-        return self
-
-    def __exit__(self, *exc):
-        global defer_parameter_gradients
-        defer_parameter_gradients = self.prev
-        return False
-# ---- the input gradient of a layer whose input is a LEAF, issued AFTER the parameter gradients of the pass are final ------
-# Data-parallel steps (bench.py, N > 1): the only thing the gradient all-reduce has to wait for is the end-of-pass reduction
-# launch; the first layer's input gradient dX = G . W^T (65 us at the BASELINE shard, a third of the all-reduce window an
-# 8-GPU ring needs) is needed by nobody before backward() returns -- its consumer is the leaf's .grad.  Inside
-# `late_input_gradients()` such a product is therefore postponed like the parameter-gradient reductions: the node hands
-# autograd the (not yet written) gradient buffer, and the end-of-pass callback launches the product AFTER the reduction
-# launch and after `parameter_gradients_ready` callbacks have run -- which is where a data-parallel step records the event
-# its collective waits for, so that the all-reduce travels while the product runs.  Same safeguards as the other deferrals
-# (leaf without hooks or an existing .grad, a single consumer, an engine-run pass); opt-in, nothing else uses it.
-late_input_gradient_products = False
-_pending_late = {}        # autograd graph-task id -> [(g2, w2, product buffer, stream, input ref)]
-parameter_gradients_ready = []   # callables run by the end-of-pass callback right after the reduction launch(es)
-
-
-class late_input_gradients:
-    """Context manager around forward + backward (see above); `on_parameter_gradients` = a callable run inside the
-    end-of-pass callback once every parameter gradient of the pass has been launched, before the postponed products."""
-
-    def __init__(self, on_parameter_gradients=None, enabled=True, collect=None):
-        """collect: a list -- the postponed products are NOT launched by the callback but appended to it as callables
-        (each launches one product into the gradient buffer autograd already holds); the caller launches them, e.g. after
-        issuing a collective.  They stay valid for as long as their tensors do (a captured step replays them every step)."""
-        self.enabled, self.hook, self.collect = enabled, on_parameter_gradients, collect
-
-    def __enter__(self):
-        global late_input_gradient_products
-        self.prev = late_input_gradient_products
-        late_input_gradient_products = self.enabled
-        if self.hook is not None:
-            parameter_gradients_ready.append(self.hook)
-        self.prev_collect = _late_collect[0]
-        _late_collect[0] = self.collect
-        return self
-
-    def __exit__(self, *exc):
-        global late_input_gradient_products
-        late_input_gradient_products = self.prev
-        if self.hook is not None:
-            parameter_gradients_ready.remove(self.hook)
-        _late_collect[0] = self.prev_collect
-        return False
-
-
-def _may_postpone_input_gradient(x):
-    """A leaf whose gradient nobody observes before backward() returns: no tensor hooks (they would not see the postponed
-    part), an engine-run first-order pass, deferral of the parameter gradients active (the flush this rides on).  The
-    postponing node returns NO gradient for the leaf to the engine; the end-of-pass callback launches the product into a
-    buffer of its own and then SETS the leaf's .grad to it -- or adds it to what is there: whatever other consumers of the
-    leaf contributed through the engine during the pass (or an earlier pass left behind) is kept, so any number of
-    consumers is correct.  (Round 4 handed the engine the not-yet-written buffer instead; a second consumer's gradient was
-    added to uninitialised memory and then overwritten: round-4 advice.)  Only under .backward(): torch.autograd.grad(...,
-    inputs=[leaf]) collects what the ENGINE carries and fails loudly ("not used in the graph") for such a leaf."""
-    if not (late_input_gradient_products and defer_parameter_gradients) or not hasattr(torch._C, "_current_graph_task_id"):
-        return False
-    if torch._C._current_graph_task_id() < 0 or torch.is_grad_enabled():
-        return False
-    return (x.is_leaf and not x._backward_hooks and not getattr(x, "_post_accumulate_grad_hooks", None))
-
-
-_late_collect = [None]
-
-
-def _late_product(g2, w2, out, stream):
-    def launch():
-        with torch.cuda.stream(stream), torch.no_grad():
-            if (_own_products_preferred() and use_matrix_core_products and w2.is_contiguous() and g2.is_contiguous() and g2.shape[0] >= 512
-                    and w2.shape[1] % 16 == 0 and _dense_kernels.supported(w2.shape[0], w2.shape[1], g2.shape[0])):
-                _dense_kernels.backward_input(g2, w2, out=out)
-            else:
-                torch.mm(g2, w2.t(), out=out)
-    return launch
-
-
-def _flush_late(task):
-    for hook in list(parameter_gradients_ready):
-        hook()
-    for g2, w2, out, stream, x_ref in _pending_late.pop(task, []):
-        jobs = [_late_product(g2, w2, out, stream)]
-        x = x_ref()
-        if x is not None:
-            if x.grad is None:
-                x.grad = out.view(x.shape)       # the product's own buffer becomes the leaf's gradient: no copy
-            else:                                # other consumers of the leaf (or an earlier pass) were there first: add
-                def add(x=x, out=out, stream=stream):
-                    with torch.cuda.stream(stream), torch.no_grad():
-                        x.grad.add_(out.view_as(x.grad))
-                jobs.append(add)
-        if _late_collect[0] is None:
-            for job in jobs:
-                job()
-        else:
-            _late_collect[0].extend(jobs)
-
-
-_pending_colsums = {}     # autograd graph-task id -> [(partials, rows, cols, out alias, stream)]
-_pending_reduce = {}      # autograd graph-task id -> [(rows, cin, c, workspace, dW alias, stream, param ref)]: weight-gradient partials
-# bias parameter -> the live autograd nodes that produce a gradient for it.  A bias shared by two layers (or a layer applied
-# twice) gets its gradients ADDED by the engine inside the pass, which reads them on arrival: more than one live node means
-# immediate reduction for all of them.  Nodes leave the set when their graph is freed.
-_bias_users = {}          # id(bias) -> (weak reference to the bias, WeakSet of nodes); keyed by identity, tensors do not compare
-
-
-def _register_bias_user(bias, node):
-    key = id(bias)
-    entry = _bias_users.get(key)
-    if entry is None or entry[0]() is not bias:
-        entry = _bias_users[key] = (weakref.ref(bias, lambda _ref, k=key: _bias_users.pop(k, None)), weakref.WeakSet())
-    entry[1].add(node)
-
-
-def _bias_user_count(bias):
-    entry = _bias_users.get(id(bias))
-    return len(entry[1]) if entry is not None and entry[0]() is bias else 0
-
-
-def _alias(t):
-    """A second tensor object over t's memory (no view relation): keeps the storage alive without being a reference to
-    the tensor itself, so that autograd still finds the gradient unshared and stores it instead of cloning it."""
-    return torch.empty(0, dtype=t.dtype, device=t.device).set_(t.untyped_storage(), t.storage_offset(), t.size(), t.stride())
-
-
-def _may_defer(bias, opted_in=False):
-    """opted_in: the forward ran inside weight_gradient_batching() -- that context is the caller's explicit request."""
-    if not (defer_parameter_gradients or opted_in) or bias is None or not hasattr(torch._C, "_current_graph_task_id"):
-        return False
-    if torch._C._current_graph_task_id() < 0 or torch.is_grad_enabled():      # not an engine pass / double backward
-        return False
-    acc = getattr(bias, "grad_fn", None)
-    if acc is not None:      # not a leaf
-        return False
-    if _bias_user_count(bias) > 1:      # another node of a live graph feeds the same parameter
-        return False
-    return (bias.grad is None and not bias._backward_hooks and not getattr(bias, "_post_accumulate_grad_hooks", None)
-            and bias.is_leaf)
-
-
-def _check_landed(param_ref, out):
-    """After a deferred reduction: the gradient autograd stored for the parameter must BE the buffer the flush wrote.  If
-    the engine kept a copy instead (it clones a gradient it does not hold the only reference to), the finished values are
-    copied into it -- never leave a placeholder behind silently."""
-    param = param_ref() if param_ref is not None else None
-    if param is None or param.grad is None or param.grad.data_ptr() == out.data_ptr():
-        return
-    if param.grad.shape == out.shape or param.grad.numel() == out.numel():
-        param.grad.copy_(out.view_as(param.grad))
-    else:
-        raise RuntimeError("geometrics_amd: a deferred parameter gradient did not reach its parameter (shape %s vs %s)"
-                           % (tuple(param.grad.shape), tuple(out.shape)))
-
-
-_flush_registered = set()     # graph tasks whose end-of-pass callback is queued
-_backward_optimizer = None     # optim.FusedAdam.fuse_into_backward(): its step rides in the end-of-pass launch when that launch covers it
-
-
-def _register_flush(task):
-    """ONE end-of-pass callback per backward pass: it finishes the pending bias-gradient column sums AND the pending
-    weight-gradient partial sums, in one launch where their shapes allow."""
-    if task in _flush_registered:
-        return
-    for stale in [t for t in _flush_registered if t < task - 64]:      # passes that died of an exception
-        _flush_registered.discard(stale)
-        _pending_colsums.pop(stale, None)
-        _pending_reduce.pop(stale, None)
-        _pending_late.pop(stale, None)
-    _flush_registered.add(task)
-    torch.autograd.Variable._execution_engine.queue_callback(lambda: _flush_pass(task))
-
-
-def _flush_pass(task):
-    try:
-        _flush_parameter_gradients(task)
-    finally:
-        _flush_late(task)      # the postponed input-gradient products: behind the reduction launch(es) and the ready-callbacks
-
-
-def _flush_parameter_gradients(task):
-    _flush_registered.discard(task)
-    _flush_pending_gradients(task)
-
-
-def _flush_pending_gradients(task):
-    red = _pending_reduce.get(task, [])
-    cs = list(_pending_colsums.get(task, []))
-    streams = {j[5] for j in red} | {j[4] for j in cs}
-    joint = (red and cs and len(streams) == 1 and all(j[2] % 4 == 0 for j in cs)
-             and 2 * len(red) + len(cs) <= _lib.DENSE_MAX_REDUCE_JOBS)
-    if not joint:
-        _flush_colsums(task)
-        _flush_reduce(task)
-        return
-    _pending_reduce.pop(task, None)
-    _pending_colsums.pop(task, None)
-    stream = next(iter(streams))
-    n, m = len(red), len(cs)
-    ints = lambda seq: (ctypes.c_int * len(seq))(*seq)
-    ptrs = lambda seq: (ctypes.c_void_p * len(seq))(*[t.data_ptr() for t in seq])
-    opt = _backward_optimizer
-    slots = None
-    if opt is not None:     # the optimiser's step rides along when this launch finishes the gradient of every one of its parameters
-        owners = [j[6]() if j[6] is not None else None for j in red] + [j[5]() if j[5] is not None else None for j in cs]
-        index = {id(p): k for k, p in enumerate(opt.params)}
-        slots = [index.get(id(p)) if p is not None else None for p in owners]
-        if None in slots or sorted(slots) != list(range(len(opt.params))) or opt.params[0].device != stream.device:
-            slots = None
-    with torch.cuda.device(stream.device):
-        if slots is None:
-            _lib.check(_lib.lib().geom_dense_reduce2_f32(
-                n, ints([j[0] for j in red]), ints([j[1] for j in red]), ints([j[2] for j in red]), ptrs([j[3] for j in red]),
-                ptrs([j[4] for j in red]), None, m, ptrs([j[0] for j in cs]), ints([j[1] for j in cs]), ints([j[2] for j in cs]),
-                ptrs([j[3] for j in cs]), stream.cuda_stream), "geom_dense_reduce2_f32")
-        else:
-            pick = lambda seq, ks: ptrs([seq[k] for k in ks])
-            wk, bk = slots[:n], slots[n:]
-            params = [p.data for p in opt.params]
-            _lib.check(_lib.lib().geom_dense_reduce_adam_f32(
-                n, ints([j[0] for j in red]), ints([j[1] for j in red]), ints([j[2] for j in red]), ptrs([j[3] for j in red]),
-                ptrs([j[4] for j in red]), pick(params, wk), pick(opt.exp_avg, wk), pick(opt.exp_avg_sq, wk),
-                m, ptrs([j[0] for j in cs]), ints([j[1] for j in cs]), ints([j[2] for j in cs]), ptrs([j[3] for j in cs]),
-                pick(params, bk), pick(opt.exp_avg, bk), pick(opt.exp_avg_sq, bk), float(opt.lr), float(opt.betas[0]),
-                float(opt.betas[1]), float(opt.eps), opt.state.data_ptr(), stream.cuda_stream), "geom_dense_reduce_adam_f32")
-            opt._stepped_in_backward = True
-    for job in red:
-        _check_landed(job[6], job[4])
-    for job in cs:
-        _check_landed(job[5], job[3])
-
-
-def _flush_colsums(task):
-    jobs = _pending_colsums.pop(task, [])
-    by_stream = {}
-    for job in jobs:
-        by_stream.setdefault(job[4], []).append(job)
-    for stream, group in by_stream.items():
-        with torch.cuda.device(stream.device):
-            for c0 in range(0, len(group), _lib.COLSUM_MAX_JOBS):
-                chunk = group[c0:c0 + _lib.COLSUM_MAX_JOBS]
-                n = len(chunk)
-                _lib.check(_lib.lib().geom_colsum_batch_f32(
-                    n, (ctypes.c_void_p * n)(*[j[0].data_ptr() for j in chunk]), (ctypes.c_int * n)(*[j[1] for j in chunk]),
-                    (ctypes.c_int * n)(*[j[2] for j in chunk]), (ctypes.c_void_p * n)(*[j[3].data_ptr() for j in chunk]),
-                    stream.cuda_stream), "geom_colsum_batch_f32")
-    for job in jobs:
-        _check_landed(job[5], job[3])
-
-
-def _queue_colsum(partials, rows, cols, out, param=None):
-    task = torch._C._current_graph_task_id()
-    jobs = _pending_colsums.get(task)
-    if jobs is None:
-        jobs = _pending_colsums[task] = []
-    _register_flush(task)
-    jobs.append((partials, rows, cols, _alias(out), torch.cuda.current_stream(out.device),
-                 None if param is None else weakref.ref(param)))
-
-
-def _finish_colsum(partials, rows, cols, grad_bias, bias, defer):
-    """Per-workgroup column sums -> the bias gradient: queued for the end-of-pass launch, or one launch now."""
-    if defer:
-        _queue_colsum(partials, rows, cols, grad_bias, bias)
-        return
-    with torch.cuda.device(partials.device):
-        _lib.check(_lib.lib().geom_colsum_batch_f32(
-            1, (ctypes.c_void_p * 1)(partials.data_ptr()), (ctypes.c_int * 1)(rows), (ctypes.c_int * 1)(cols),
-            (ctypes.c_void_p * 1)(grad_bias.data_ptr()), _lib.stream_ptr()), "geom_colsum_batch_f32")
 
 
 def aggregate_backward(g, csr, k, act, out, mask, want_bias, bias=None, arena=None):
     """grad_support = [A^T . g'[..., :k] | g'[..., k:]] with g' = g * act'(out) (relu' from the sign mask when there is
     one), and the bias gradient = column sums of g' out of the same launch (+ a fixed-order reduction: at once, or -- given
-    the bias parameter, inside a backward pass -- batched at the end of the pass, see above)."""
+    the bias parameter, inside a backward pass -- batched at the end of the pass: geometrics_amd.backward_pass)."""
     b, nv, c = g.shape
     grad_support = _new_like(g, "grad_support", arena, descending=True)
-    grad_bias = scratch = None
-    defer = False
-    if want_bias:   # column sums of g come out of the same kernel (per-block partials + fixed-order reduce)
-        grad_bias = _gradient_buffer(bias, bias) if bias is not None and bias.shape == (c,) and bias.dtype == torch.float32 \
-            else torch.empty(c, dtype=torch.float32, device=g.device)
-        scratch = torch.empty(_lib.lib().geom_zn_gcn_bwd_scratch_floats(b, nv, c), dtype=torch.float32,
-                              device=g.device)
-        defer = _may_defer(bias, opted_in=arena is not None)
-    now = None if defer else grad_bias
+    # column sums of g come out of the same kernel (per-block partials + fixed-order reduce)
+    bg = _pass.bias_gradient(bias, c, g.device, _lib.lib().geom_zn_gcn_bwd_scratch_floats(b, nv, c),
+                             opted_in=arena is not None) if want_bias else _pass.NO_BIAS_GRADIENT
     with torch.cuda.device(g.device):
         code = _lib.EUNSUPPORTED
         ell_w = csr.ell_w
@@ -527,18 +192,18 @@ def aggregate_backward(g, csr, k, act, out, mask, want_bias, bias=None, arena=No
             code = _lib.lib().geom_zn_gcn_aggregate_ell_bwd_f32(
                 b, nv, c, k, ell_w, csr.ell_col_t.data_ptr(), csr.ell_val_t.data_ptr(), _lib.ptr(over[0]),
                 _lib.ptr(over[1]), _lib.ptr(over[2]), g.data_ptr(),
-                _lib.ptr(out), _lib.ptr(mask), act, grad_support.data_ptr(), _lib.ptr(now), _lib.ptr(scratch),
+                _lib.ptr(out), _lib.ptr(mask), act, grad_support.data_ptr(), _lib.ptr(bg.now), _lib.ptr(bg.scratch),
                 _lib.stream_ptr())
         if code == _lib.EUNSUPPORTED:
             ell_w = 0
             _lib.call("geom_zn_gcn_aggregate_bwd_f32", b, nv, c, k, csr.rowptr_t.data_ptr(),
                       csr.col_t.data_ptr(), csr.val_t.data_ptr(), g.data_ptr(), _lib.ptr(out), act,
-                      grad_support.data_ptr(), _lib.ptr(now), _lib.ptr(scratch))
+                      grad_support.data_ptr(), _lib.ptr(bg.now), _lib.ptr(bg.scratch))
         else:
             _lib.check(code, "geom_zn_gcn_aggregate_ell_bwd_f32")
-    if defer:
-        _queue_colsum(scratch, int(_lib.lib().geom_zn_gcn_bwd_partial_rows(b, nv, c, k, ell_w)), c, grad_bias, bias)
-    return grad_support, grad_bias
+    if bg.defer:
+        bg.finish(int(_lib.lib().geom_zn_gcn_bwd_partial_rows(b, nv, c, k, ell_w)))
+    return grad_support, bg.out
 
 
 class _ZeroNAggregate(torch.autograd.Function):
@@ -555,9 +220,7 @@ class _ZeroNAggregate(torch.autograd.Function):
         out = _new_like(s, "aggregated", ctx.arena)
         mask = aggregate_forward(s, bias_c, csr, k, act, out, want_mask=support.requires_grad)
         ctx.csr, ctx.k, ctx.act, ctx.has_bias = csr, k, act, bias is not None
-        ctx.bias_ref = None if bias is None else weakref.ref(bias)
-        if bias is not None and ctx.needs_input_grad[1]:
-            _register_bias_user(bias, ctx)
+        ctx.bias_ref = _pass.parameter_ref(bias, ctx, ctx.needs_input_grad[1])
         ctx.masked = mask is not None
         if mask is not None:
             ctx.save_for_backward(mask)
@@ -602,9 +265,7 @@ class _ZeroNAggregateHead(torch.autograd.Function):
                       csr.ell_val.data_ptr(), _lib.ptr(over[0]), _lib.ptr(over[1]), _lib.ptr(over[2]), s.data_ptr(),
                       _lib.ptr(bias_c), act, out.data_ptr(), _lib.ptr(mask), base_c.data_ptr(), float(scale), pos.data_ptr())
         ctx.csr, ctx.k, ctx.act, ctx.scale, ctx.shape = csr, k, act, float(scale), (b, nv, c)
-        ctx.bias_ref = None if bias is None else weakref.ref(bias)
-        if bias is not None and ctx.needs_input_grad[1]:
-            _register_bias_user(bias, ctx)
+        ctx.bias_ref = _pass.parameter_ref(bias, ctx, ctx.needs_input_grad[1])
         if mask is not None:
             ctx.save_for_backward(mask)
         return pos
@@ -616,39 +277,33 @@ class _ZeroNAggregateHead(torch.autograd.Function):
         csr, k = ctx.csr, ctx.k
         mask = ctx.saved_tensors[0] if ctx.saved_tensors else None
         grad_support = torch.empty(b, nv, c, dtype=torch.float32, device=gp.device)
-        grad_bias = scratch = None
-        defer = False
-        bias = ctx.bias_ref() if ctx.bias_ref is not None else None
-        if ctx.needs_input_grad[1] and ctx.bias_ref is not None:
-            grad_bias = _gradient_buffer(bias, bias) if bias is not None and bias.shape == (c,) and bias.dtype == torch.float32 \
-                else torch.empty(c, dtype=torch.float32, device=gp.device)
-            scratch = torch.empty(_lib.lib().geom_zn_gcn_bwd_scratch_floats(b, nv, c), dtype=torch.float32, device=gp.device)
-            defer = _may_defer(bias)
         down = ctx.down
         # (the launch below takes THIS layer's aggregation backward: it must be a shape the boundary kernel serves -- 192 wide,
         # k = 64, table width 8 without long rows -- and `wt` the transposed weight of a 192-row product; else: the separate operators)
-        if (down is not None and down.wt is not None and down.wanted and ctx.needs_input_grad[0]
-                and _fused.plan(b * nv)["bwd"] and down.wt.dim() == 2 and down.wt.shape[0] == c
-                and _fused.supported(csr, c, k, down.wt.shape[1])):
+        fused = (down is not None and down.wt is not None and down.wanted and ctx.needs_input_grad[0]
+                 and _fused.plan(b * nv)["bwd"] and down.wt.dim() == 2 and down.wt.shape[0] == c
+                 and _fused.supported(csr, c, k, down.wt.shape[1]))
+        rows = _fused.partial_rows(b, nv) if fused else None
+        bg = _pass.NO_BIAS_GRADIENT
+        if ctx.needs_input_grad[1] and ctx.bias_ref is not None:
+            scratch = (rows, c) if fused else _lib.lib().geom_zn_gcn_bwd_scratch_floats(b, nv, c)
+            bg = _pass.bias_gradient(ctx.bias_ref(), c, gp.device, scratch)
+        if fused:
             # this aggregation backward AND the input gradient of the product below it in one launch (csrc/zn_stack.hip);
             # the boundary below picks its input gradient up from the link instead of computing it
-            rows = _fused.partial_rows(b, nv)
-            partial = torch.empty(rows, c, dtype=torch.float32, device=gp.device) if grad_bias is not None else None
             _fused.layer_backward(None, None, mask, csr, k, ctx.act, down.wt, g_out=grad_support, grad_in=down.take_dx(b, nv),
-                                  colsum_partial=partial, grad_pos=gp, head_scale=ctx.scale, shape=(b, nv, c))
+                                  colsum_partial=bg.scratch, grad_pos=gp, head_scale=ctx.scale, shape=(b, nv, c))
             down.stamp(grad_support)
-            if grad_bias is not None:
-                _finish_colsum(partial, rows, c, grad_bias, bias, defer)
-            return grad_support, grad_bias, (gp if ctx.needs_input_grad[2] else None), None, None, None, None, None
+            bg.finish(rows)
+            return grad_support, bg.out, (gp if ctx.needs_input_grad[2] else None), None, None, None, None, None
         over = csr.over_t or (None, None, None)
         with torch.cuda.device(gp.device):
             _lib.call("geom_zn_gcn_aggregate_ell_head_bwd_f32", b, nv, c, k, csr.ell_w, csr.ell_col_t.data_ptr(),
                       csr.ell_val_t.data_ptr(), _lib.ptr(over[0]), _lib.ptr(over[1]), _lib.ptr(over[2]), gp.data_ptr(),
-                      ctx.scale, _lib.ptr(mask), ctx.act, grad_support.data_ptr(), _lib.ptr(None if defer else grad_bias),
-                      _lib.ptr(scratch))
-        if defer:
-            _queue_colsum(scratch, int(_lib.lib().geom_zn_gcn_bwd_partial_rows(b, nv, c, k, csr.ell_w)), c, grad_bias, bias)
-        return (grad_support if ctx.needs_input_grad[0] else None), grad_bias, (gp if ctx.needs_input_grad[2] else None), \
+                      ctx.scale, _lib.ptr(mask), ctx.act, grad_support.data_ptr(), _lib.ptr(bg.now), _lib.ptr(bg.scratch))
+        if bg.defer:
+            bg.finish(int(_lib.lib().geom_zn_gcn_bwd_partial_rows(b, nv, c, k, csr.ell_w)))
+        return (grad_support if ctx.needs_input_grad[0] else None), bg.out, (gp if ctx.needs_input_grad[2] else None), \
             None, None, None, None, None
 
 
@@ -693,9 +348,9 @@ def zero_n_aggregate(support, adj, bias, k, activation=None):
 # dW = X^T . G of a hidden layer (K = b*V rows against a 192 x 192 output) is the library's least efficient product: 22 us at
 # the reference's training shape for 0.57 GFLOP, and a deformation block issues twelve of them, one per layer.  The
 # gradients are independent of each other, so inside `weight_gradient_batching()` they are postponed to the end of the
-# backward pass (same mechanism and same safeguards as the bias gradients above) and issued as one strided-batched
-# product per run of equal layers: 242 -> 72 us for the twelve.  A strided-batched product wants its operands at a
-# regular pitch, so while the context is active the layers' activations and gradients are carved out of stacked buffers
+# backward pass (geometrics_amd.backward_pass: same mechanism and safeguards as the bias gradients) and issued as one
+# strided-batched product per run of equal layers: 242 -> 72 us for the twelve.  A strided-batched product wants its operands
+# at a regular pitch, so while the context is active the layers' activations and gradients are carved out of stacked buffers
 # (`_Slabs`): consecutive equal-shape allocations sit one pitch apart, forward ones ascending, backward ones descending
 # (the backward pass meets the layers in reverse), which makes X_l, G_l and dW_l all ascending in l.
 class _Slabs:
@@ -723,9 +378,6 @@ _active = threading.local()    # .slabs = the arena of the forward pass running 
 
 def current_slabs():
     return getattr(_active, "slabs", None)
-
-
-_pending_dense = {}       # autograd graph-task id -> [(x2d, g2d, dW slot alias, stream)] in backward order
 
 
 class weight_gradient_batching:
@@ -769,35 +421,27 @@ def _regular_run(tensors):
     return first, step
 
 
-def _flush_dense(task):
-    jobs = _pending_dense.pop(task, [])
-    jobs.reverse()                                   # layer order: every operand ascending
-    _flush_dense_products([job[:4] for job in jobs])
-    for job in jobs:
-        _check_landed(job[4], job[2])
-
-
-def _flush_dense_products(jobs):
+def _launch_weight_products(jobs):
+    """A pass's postponed weight-gradient products in layer order: batched over runs of equal layers at a regular pitch."""
     i = 0
     while i < len(jobs):
-        x, g, out, stream = jobs[i]
+        first = jobs[i]
         j = i + 1
-        while j < len(jobs) and jobs[j][0].shape == x.shape and jobs[j][1].shape == g.shape and jobs[j][3] == stream:
+        while (j < len(jobs) and jobs[j].x.shape == first.x.shape and jobs[j].g.shape == first.g.shape
+               and jobs[j].stream == first.stream):
             j += 1
         group = jobs[i:j]
-        with torch.cuda.stream(stream), torch.no_grad():
-            runs = [_regular_run([job[k] for job in group]) for k in range(3)] if len(group) > 1 else None
+        with torch.cuda.stream(first.stream), torch.no_grad():
+            runs = [_regular_run([getattr(job, name) for job in group]) for name in ("x", "g", "out")] if len(group) > 1 else None
             if runs and all(runs):
-                n = len(group)
-                xb = torch.as_strided(runs[0][0], (n,) + tuple(x.shape), (runs[0][1],) + tuple(x.stride()))
-                gb = torch.as_strided(runs[1][0], (n,) + tuple(g.shape), (runs[1][1],) + tuple(g.stride()))
-                ob = torch.as_strided(runs[2][0], (n,) + tuple(out.shape), (runs[2][1],) + tuple(out.stride()))
+                xb, gb, ob = (torch.as_strided(run[0], (len(group),) + tuple(t.shape), (run[1],) + tuple(t.stride()))
+                              for run, t in zip(runs, (first.x, first.g, first.out)))
                 torch.bmm(xb.transpose(1, 2), gb, out=ob)
             else:
-                for xx, gg, oo, _ in group:
+                for job in group:
                     # (a layer of its own width -- the block's 192 -> 3 coordinate head: 7712 summed rows against a 192 x 3 output
                     # is 75 us in the library, which runs it without a split; the any-shape kernel splits the sum)
-                    _weight_gradient_product(xx, gg, out=oo)
+                    _weight_gradient_product(job.x, job.g, out=job.out)
         i = j
 
 
@@ -841,13 +485,13 @@ def _library_or_own_forward(x, w2):
     return torch.matmul(x, w2)
 
 
-def _library_or_own_input_gradient(g2, w2):
+def _library_or_own_input_gradient(g2, w2, out=None):
     """g2 @ w2^T ([rows, c] x [cin, c]^T) by the library, or by geom_dense_bwd_input_f32 when the library runs untuned."""
     if (_own_products_preferred() and use_matrix_core_products and g2.is_cuda and g2.dtype == torch.float32 and g2.dim() == 2
             and g2.is_contiguous() and w2.is_contiguous() and w2.dim() == 2 and g2.shape[1] == w2.shape[1] and g2.shape[0] >= 512
             and w2.shape[1] % 16 == 0 and _dense_kernels.supported(w2.shape[0], w2.shape[1], g2.shape[0])):
-        return _dense_kernels.backward_input(g2, w2)
-    return torch.matmul(g2, w2.t())
+        return _dense_kernels.backward_input(g2, w2, out=out)
+    return torch.matmul(g2, w2.t()) if out is None else torch.mm(g2, w2.t(), out=out)
 
 
 def _forward_product(x, w2):
@@ -880,9 +524,7 @@ class _Dense(torch.autograd.Function):
     def forward(ctx, x, w, arena):
         ctx.save_for_backward(x, w)
         ctx.arena = arena
-        ctx.w_ref = weakref.ref(w)
-        if ctx.needs_input_grad[1]:
-            _register_bias_user(w, ctx)
+        ctx.w_ref = _pass.parameter_ref(w, ctx, ctx.needs_input_grad[1])
         return _forward_product(x, w.reshape(w.shape[-2:]))
 
     @staticmethod
@@ -895,16 +537,9 @@ class _Dense(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             x2, g2 = x.reshape(-1, x.shape[-1]), g.reshape(-1, g.shape[-1])
             param = ctx.w_ref()
-            if param is not None and x2.is_contiguous() and _may_defer(param, opted_in=True):
+            if param is not None and x2.is_contiguous() and _pass.may_defer(param, opted_in=True):
                 grad_w = ctx.arena.take("dW", w.shape, w.device, descending=True)
-                task = torch._C._current_graph_task_id()
-                jobs = _pending_dense.get(task)
-                if jobs is None:
-                    for stale in [t for t in _pending_dense if t < task - 64]:
-                        del _pending_dense[stale]
-                    jobs = _pending_dense[task] = []
-                    torch.autograd.Variable._execution_engine.queue_callback(lambda: _flush_dense(task))
-                jobs.append((x2, g2, _alias(grad_w).view(w2.shape), torch.cuda.current_stream(w.device), ctx.w_ref))
+                _pass.postpone_weight_product(x2, g2, grad_w, ctx.w_ref, _launch_weight_products)
             else:
                 grad_w = _weight_gradient_product(x2, g2).view(w.shape)
         return grad_x, grad_w, None
@@ -913,47 +548,17 @@ class _Dense(torch.autograd.Function):
 # ---- the layer's dense products on the fp32 matrix cores (csrc/dense_gemm.hip) -----------------------------------------
 
 
-def _flush_reduce(task):
-    jobs = _pending_reduce.pop(task, [])
-    by_stream = {}
-    for job in jobs:
-        by_stream.setdefault(job[5], []).append(job[:5] + (None,))
-    for stream, group in by_stream.items():
-        _dense_kernels.reduce(group, stream.cuda_stream)
-    for job in jobs:
-        _check_landed(job[6], job[4])
-
-
-def _finish_weight_gradient(w_ref, w, rows, cin, c, ws):
-    """The weight gradient whose split partial sums are in `ws`: queued for the reduction launch at the end of the pass where
-    deferral is allowed (its buffer handed to autograd now), reduced at once otherwise."""
-    param = w_ref()
-    grad_w = _gradient_buffer(param, w)
-    if param is not None and _may_defer(param):
-        task = torch._C._current_graph_task_id()
-        jobs = _pending_reduce.get(task)
-        if jobs is None:
-            jobs = _pending_reduce[task] = []
-        _register_flush(task)
-        jobs.append((rows, cin, c, ws, _alias(grad_w).view(cin, c), torch.cuda.current_stream(w.device), w_ref))
-    else:
-        _dense_kernels.reduce([(rows, cin, c, ws, grad_w.view(cin, c), None)])
-    return grad_w
-
-
 class _DenseMM(torch.autograd.Function):
     """support = input @ W with both gradients on the matrix-core kernels where `dense.plan` puts them: the input
     gradient and the split partial sums of the weight gradient in ONE launch (two workgroups per CU) for the 192-wide
     layers, the partial sums alone for the 963-wide one; the partials of all layers of a backward pass are added up by one
-    reduction launch at its end when parameter-gradient deferral is on (see `defer_parameter_gradients`), at once
+    reduction launch at its end inside `deferred_parameter_gradients()` (geometrics_amd.backward_pass), at once
     otherwise.  Same values either way: the reduction order is fixed by the shape."""
 
     @staticmethod
     def forward(ctx, x, w):
         ctx.save_for_backward(x, w)
-        ctx.w_ref = weakref.ref(w)
-        if ctx.needs_input_grad[1]:
-            _register_bias_user(w, ctx)
+        ctx.w_ref = _pass.parameter_ref(w, ctx, ctx.needs_input_grad[1])
         return _library_or_own_forward(x, w.reshape(w.shape[-2:]))
 
     @staticmethod
@@ -972,24 +577,19 @@ class _DenseMM(torch.autograd.Function):
             return grad_x, grad_w
         ws = _dense_kernels.weight_workspace(rows, cin, c, x.device)
         grad_x = None
-        late = None
         if need_x and plan["pair"]:
             grad_x = torch.empty_like(x)
             _dense_kernels.backward_pair(x2, g2, w2, grad_x.view(rows, cin), ws)
         else:
-            if need_x and _may_postpone_input_gradient(x):
+            if need_x and _pass.may_postpone_input_gradient(x):
                 # no gradient for x through the engine: the end-of-pass callback launches the product behind the reduction
-                # launch and makes its buffer the leaf's .grad (_flush_late)
-                late = (g2, w2, torch.empty(rows, cin, dtype=x.dtype, device=x.device), torch.cuda.current_stream(x.device),
-                        weakref.ref(x))
+                # launch and makes its buffer the leaf's .grad
+                late = torch.empty(rows, cin, dtype=x.dtype, device=x.device)
+                _pass.postpone_input_gradient(lambda: _library_or_own_input_gradient(g2, w2, out=late), late, x)
             elif need_x:
                 grad_x = _library_or_own_input_gradient(g2, w2).view(x.shape)
             _dense_kernels.backward_weight_partials(x2, g2, ws)
-        if late is not None:
-            task = torch._C._current_graph_task_id()
-            _pending_late.setdefault(task, []).append(late)
-            _register_flush(task)
-        return grad_x, _finish_weight_gradient(ctx.w_ref, w, rows, cin, c, ws)
+        return grad_x, _pass.weight_gradient(ctx.w_ref, w, rows, cin, c, ws)
 
 
 class _DenseAny(torch.autograd.Function):
@@ -1098,12 +698,8 @@ class _FusedBoundary(torch.autograd.Function):
             up.wanted = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         x, s_next = _fused.layer_forward(s, bias_c, csr, k, act, w2, mask=mask, wt_out=up.wt)
         ctx.csr, ctx.k, ctx.act, ctx.up, ctx.down = csr, k, act, up, down
-        ctx.bias_ref = None if bias is None else weakref.ref(bias)
-        ctx.w_ref = weakref.ref(w_next)
-        if bias is not None and ctx.needs_input_grad[1]:
-            _register_bias_user(bias, ctx)
-        if ctx.needs_input_grad[2]:
-            _register_bias_user(w_next, ctx)
+        ctx.bias_ref = _pass.parameter_ref(bias, ctx, ctx.needs_input_grad[1])
+        ctx.w_ref = _pass.parameter_ref(w_next, ctx, ctx.needs_input_grad[2])
         ctx.masked = mask is not None
         ctx.save_for_backward(x, w_next, *([mask] if mask is not None else []))
         return s_next
@@ -1139,7 +735,7 @@ class _FusedBoundary(torch.autograd.Function):
         elif split:
             _dense_kernels.backward_weight_partials(x2, g2, ws)
         if split:
-            grad_w = _finish_weight_gradient(ctx.w_ref, w, rows, c, n_out, ws)
+            grad_w = _pass.weight_gradient(ctx.w_ref, w, rows, c, n_out, ws)
         elif need_w:
             grad_w = _weight_gradient_product(x2, g2).view(w.shape)
         if not (need_s or need_b):
@@ -1148,17 +744,13 @@ class _FusedBoundary(torch.autograd.Function):
         bias = ctx.bias_ref() if ctx.bias_ref is not None else None
         out = x if (act != _ACT_NONE and mask is None) else None
         if down is not None and down.wt is not None and down.wanted and _fused.plan(rows)["bwd"]:
-            grad_bias = partial = None
             prows = _fused.partial_rows(b, nv)
-            if need_b:
-                grad_bias = _gradient_buffer(bias, bias) if bias is not None and bias.shape == (c,) \
-                    else torch.empty(c, dtype=torch.float32, device=x.device)
-                partial = torch.empty(prows, c, dtype=torch.float32, device=x.device)
+            bg = _pass.bias_gradient(bias, c, x.device, (prows, c)) if need_b else _pass.NO_BIAS_GRADIENT
             grad_support, _ = _fused.layer_backward(dx, out, mask, csr, k, act, down.wt, grad_in=down.take_dx(b, nv),
-                                                    colsum_partial=partial)
+                                                    colsum_partial=bg.scratch)
             down.stamp(grad_support)
-            if need_b:
-                _finish_colsum(partial, prows, c, grad_bias, bias, _may_defer(bias))
+            bg.finish(prows)
+            grad_bias = bg.out
         else:
             grad_support, grad_bias = aggregate_backward(dx, csr, k, act, out, mask, need_b, bias)
         return (grad_support if need_s else None), grad_bias, grad_w, None, None, None, None, None

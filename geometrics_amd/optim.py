@@ -7,7 +7,7 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, backward_pass
 
 
 class _InBackward:
@@ -15,20 +15,17 @@ class _InBackward:
         self.opt = opt
 
     def __enter__(self):
-        from . import layers
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise RuntimeError("FusedAdam.in_backward() would step on the LOCAL gradients, before the all-reduce across the "
                                "%d ranks; data-parallel steps call step(bucket.views, grad_scale=1/world) after the exchange"
                                % dist.get_world_size())
-        self.prev = layers._backward_optimizer
-        layers._backward_optimizer = self.opt
+        self.prev = backward_pass.set_optimizer(self.opt)
         self.opt._stepped_in_backward = False
         return self.opt
 
     def __exit__(self, *exc):
-        from . import layers
-        layers._backward_optimizer = self.prev
+        backward_pass.set_optimizer(self.prev)
         return False
 
 
@@ -56,7 +53,7 @@ class FusedAdam:
 
     def in_backward(self):
         """Context manager around forward + backward of ONE iteration: the step is applied INSIDE the backward pass, in the
-        launch that finishes the gradients (layers' end-of-pass reduction, geom_dense_reduce_adam_f32) -- no optimiser
+        launch that finishes the gradients (the end-of-pass reduction, geom_dense_reduce_adam_f32) -- no optimiser
         launch of its own, no second read of the gradients.  It happens only if (a) parameter-gradient deferral is on
         (`layers.deferred_parameter_gradients()`) and (b) that one launch finishes the gradient of EVERY parameter of this
         optimiser, each exactly once; the following `step()` (no arguments, grad_scale 1) is then a no-op.  Otherwise

@@ -1,14 +1,15 @@
-"""-m gpu: two backward passes in flight at once.  layers.py keeps the work it postpones to the end of a backward pass (bias /
-weight-gradient reductions, the first layer's late input gradient) in process-wide tables keyed by the autograd graph-task id;
-two python threads, each with its own model, stream and input, run forward + backward concurrently under
-deferred_parameter_gradients() + late_input_gradients() -- every gradient must be the one the same model gives alone."""
+"""-m gpu: two backward passes in flight at once.  geometrics_amd.backward_pass keeps the work the layers postpone to the end of
+a backward pass (bias / weight-gradient reductions, the first layer's late input gradient) in one record per pass, in a
+process-wide registry keyed by the autograd graph-task id; two python threads, each with its own model, stream and input, run
+forward + backward concurrently under deferred_parameter_gradients() + late_input_gradients() -- every gradient must be the
+one the same model gives alone."""
 import threading
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from geometrics_amd import layers, meshgen, utils
+from geometrics_amd import backward_pass, layers, meshgen, utils
 
 pytestmark = pytest.mark.gpu
 
@@ -70,5 +71,5 @@ def test_two_backward_passes_in_flight(gpu, rows):
             assert torch.isfinite(got).all()
             # the routes (deferred / immediate reduction) give the same values: fixed reduction orders
             assert torch.equal(got, want) or float((got - want).abs().max()) <= 1e-5 * float(want.abs().max())
-    # nothing was left behind in the process-wide tables
-    assert not layers._pending_late and not layers._pending_colsums and not layers._pending_reduce and not layers._pending_dense
+    # nothing was left behind in the process-wide registry
+    assert not backward_pass.pending()

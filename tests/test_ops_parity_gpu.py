@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from helpers import bits, fp64_surface_gradient, golden, rows_close
-from geometrics_amd import layers, meshgen, ops, utils
+from geometrics_amd import backward_pass, layers, meshgen, ops, utils
 from oracle import ref_ops
 
 pytestmark = pytest.mark.gpu
@@ -717,7 +717,7 @@ def test_tapped_layer_output_sums_its_two_gradients_in_the_batchnorm_backward(gp
 
 def test_bias_gradients_of_a_backward_pass_are_finished_in_one_batched_launch(gpu):
     """Inside an autograd pass the per-layer bias-gradient reductions are queued and finished by ONE
-    geom_colsum_batch_f32 launch at the end of the pass (layers.defer_parameter_gradients): same bits as the immediate
+    geom_colsum_batch_f32 launch at the end of the pass (layers.deferred_parameter_gradients()): same bits as the immediate
     reduction, complete when backward() returns, nothing left pending; a bias with an existing .grad (accumulation) or a
     hook takes the immediate path; torch.autograd.grad sees finished values; and a captured pass replays."""
     from geometrics_amd import meshgen
@@ -730,8 +730,7 @@ def test_bias_gradients_of_a_backward_pass_are_finished_in_one_batched_launch(gp
     g_out = torch.randn(5, V.shape[0], 40, device=gpu)
 
     def run(defer, prepare=None):
-        layers.defer_parameter_gradients = defer
-        try:
+        with layers.deferred_parameter_gradients(defer):
             for p in stack.parameters():
                 p.grad = None
             if prepare:
@@ -740,10 +739,8 @@ def test_bias_gradients_of_a_backward_pass_are_finished_in_one_batched_launch(gp
             for i, layer in enumerate(stack):
                 h = layer(h, adj, F.relu if i < 2 else None)
             h.backward(g_out)
-            assert not layers._pending_colsums
+            assert not backward_pass.pending()
             return [layer.bias.grad.clone() for layer in stack], [layer._weight().grad.clone() for layer in stack]
-        finally:
-            layers.defer_parameter_gradients = False
 
     now_b, now_w = run(False)
     later_b, later_w = run(True)
@@ -771,28 +768,25 @@ def test_bias_gradients_of_a_backward_pass_are_finished_in_one_batched_launch(gp
     tied = layers.Batch_Image_ZERON_GCNGCN(48, 48).to(gpu)
     tied.bias = stack[1].bias
     def tied_pass(defer):
-        layers.defer_parameter_gradients = defer
-        try:
+        with layers.deferred_parameter_gradients(defer):
             for p_ in list(stack.parameters()) + [tied.weight1]:
                 p_.grad = None
             h = stack[0](x, adj, F.relu)
             h = tied(stack[1](h, adj, F.relu), adj, F.relu)
             stack[2](h, adj, None).backward(g_out)
-            assert not layers._pending_colsums
+            assert not backward_pass.pending()
             return stack[1].bias.grad.clone()
-        finally:
-            layers.defer_parameter_gradients = False
     assert torch.equal(tied_pass(False), tied_pass(True))      # a shared bias is never postponed: same launches either way
     del tied
     # deferral is opt-in: by default nothing is pending at any time and the values are the same
-    assert layers.defer_parameter_gradients is False
+    assert backward_pass.switches.defer is False
     # torch.autograd.grad: captured gradients are finished when the call returns
     with layers.deferred_parameter_gradients():
         h = x
         for i, layer in enumerate(stack):
             h = layer(h, adj, F.relu if i < 2 else None)
         got = torch.autograd.grad(h, [layer.bias for layer in stack], g_out)
-    assert not layers._pending_colsums
+    assert not backward_pass.pending()
     for a, b in zip(got, now_b):
         close(a.cpu().numpy(), b.cpu().numpy(), 2e-6)
     # HIP-graph capture of forward + backward: the batched launch is part of the graph
@@ -882,10 +876,10 @@ def test_late_input_gradient_is_the_same_product_issued_behind_the_reduction_lau
         calls.clear()
         if prepare:
             prepare()
-        hook = lambda: calls.append(len(layers._pending_reduce) + len(layers._pending_colsums))
+        hook = lambda: calls.append(backward_pass.pending("reduces", "colsums"))
         with layers.deferred_parameter_gradients(), layers.late_input_gradients(hook, enabled=late):
             stack[1](stack[0](x, adj, F.relu), adj, F.relu).backward(g_out)
-        assert not layers._pending_late and not layers._pending_reduce
+        assert not backward_pass.pending()
         return x.grad.clone(), [p_.grad.clone() for p_ in stack.parameters()]
 
     now_x, now_p = run(False)
@@ -921,7 +915,7 @@ def test_late_input_gradient_is_the_same_product_issued_behind_the_reduction_lau
             ((stack[0](x, adj, F.relu) * g_out).sum() + (x * 2.0).sum()).backward()
         return x.grad.clone()
     close(with_torch_op(True).cpu().numpy(), with_torch_op(False).cpu().numpy(), 1e-6)
-    assert float((with_torch_op(True) - 2.0).abs().max()) > 0.0 and not layers._pending_late
+    assert float((with_torch_op(True) - 2.0).abs().max()) > 0.0 and not backward_pass.pending()
 
 
 def test_weight_gradients_of_equal_layers_come_from_one_batched_product(gpu):
@@ -951,7 +945,7 @@ def test_weight_gradients_of_equal_layers_come_from_one_batched_product(gpu):
             for i, layer in enumerate(stack):
                 h = layer(h, adj, F.relu if i < 4 else None)
         h.backward(g_out)
-        assert not layers._pending_dense and not layers._pending_colsums
+        assert not backward_pass.pending()
         return (h.detach().clone(), x.grad.clone(), [l.weight1.grad.clone() for l in stack], [l.bias.grad.clone() for l in stack])
 
     import contextlib
