@@ -17,7 +17,9 @@ Where every workgroup of a launch is resident at once (482 vertices on an MI355X
 are ONE (`chain`): a vertex's workgroup runs layer after layer and waits for its neighbours' rows inside the launch.
 
 `serves()` says when the launches apply (192-wide block, k = 64, b <= 16, bounded-degree table of width 8, training mode,
-local BatchNorm statistics, fp32 on a HIP device); everything else takes the separate operators (models.py).
+local BatchNorm statistics over the input's vertices, fp32 on a HIP device); everything else takes the separate operators
+(models.py).  The one-launch chain also needs a structurally symmetric adjacency (`csr.symmetric_structure`); a directed one
+takes the launches per layer.
 """
 import ctypes
 import os
@@ -52,6 +54,10 @@ def serves(block, features, pooled, csr):
     for i in range(1, LAYERS + 1):
         gc, bn = getattr(block, "gc%d" % i), getattr(block, "bn%d" % i)
         if gc.bias is None or gc.weight1.shape[-1] != 192 or (i > 1 and gc.weight1.shape[-2] != 192) or bn._synchronised():
+            return False
+        # (the launches index the BatchNorm's per-vertex tensors by the input's vertex; each layer takes its own momentum / eps)
+        if bn.num_features != features.shape[1] or bn.momentum is None or any(
+                t is None or t.dtype != torch.float32 for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
             return False
     return True
 
@@ -219,7 +225,8 @@ def chain_backward(layers, done, device, ds_first=None):
 
 class _HiddenChain(torch.autograd.Function):
     """X_14 = the thirteen hidden layers applied to S_1 (see the module docstring).  apply(s1, lead, csr, stats, momentum,
-    eps, *biases[13], *weights[12] (gc2..gc13), *bn_weights[13], *bn_biases[13]); stats = [(running_mean, running_var)] * 13.
+    eps, *biases[13], *weights[12] (gc2..gc13), *bn_weights[13], *bn_biases[13]); stats = [(running_mean, running_var)] * 13,
+    momentum / eps = the 13 BatchNorms' own values (sequences of 13).
     Returns the final features TWICE (two tensor objects over one memory: one for the coordinate head, one for the caller;
     their gradients meet inside the first backward launch instead of in an add pass)."""
 
@@ -241,7 +248,9 @@ class _HiddenChain(torch.autograd.Function):
         means, invstds = torch.empty(L, nv, **f32), torch.empty(L, nv, **f32)
         s_buf = (torch.empty(b, nv, c, **f32), torch.empty(b, nv, c, **f32))
         s_cur = s1
-        as_chain = chain_fits(nv, dev)
+        # (a chain launch needs a symmetric pattern: vertex v rewrites its support row once the vertices of ITS row are done
+        # with the previous layer, and those must be all the vertices that gather v's row -- A[u][v] != 0 => A[v][u] != 0)
+        as_chain = csr.symmetric_structure and chain_fits(nv, dev)
         # (counters of the forward and of the backward chain launch, cleared by the packing launch)
         counters = torch.empty(2, nv * CTR_STRIDE, dtype=torch.int32, device=dev) if as_chain else None
         w2, wts = pack_weights(weights, counters)     # w2[i - 1] / wts[i - 1] = W_{i+1} / its transpose, in register-slice order
@@ -255,8 +264,8 @@ class _HiddenChain(torch.autograd.Function):
                 wh = w_head.reshape(c, 3)
                 wh = wh if wh.is_contiguous() else wh.contiguous()
                 s_head = torch.empty(b, nv, 3, **f32)
-            call = ((s_cur, biases[i - 1], csr, bn_w[i - 1], bn_b[i - 1], stats[i - 1][0], stats[i - 1][1], True, momentum, eps,
-                     relu, res, 0.5, zs[i - 1], xs[i - 1], means[i - 1], invstds[i - 1]),
+            call = ((s_cur, biases[i - 1], csr, bn_w[i - 1], bn_b[i - 1], stats[i - 1][0], stats[i - 1][1], True, momentum[i - 1],
+                     eps[i - 1], relu, res, 0.5, zs[i - 1], xs[i - 1], means[i - 1], invstds[i - 1]),
                     dict(w_next=w2[i - 1] if nxt else None, s_out=s_buf[i & 1] if nxt else None,
                          w_head=wh if head else None, s_head=s_head if head else None))
             if as_chain:
@@ -380,4 +389,5 @@ def hidden_chain(block, s1, lead, csr, head=None):
     w_head = None
     if head is not None and tuple(head.weight1.shape[-2:]) == (192, 3):
         w_head = head.weight1
-    return _HiddenChain.apply(s1, lead, csr, stats, bns[0].momentum, bns[0].eps, w_head, *params)
+    momentum, eps = tuple(float(bn.momentum) for bn in bns), tuple(float(bn.eps) for bn in bns)
+    return _HiddenChain.apply(s1, lead, csr, stats, momentum, eps, w_head, *params)

@@ -34,6 +34,7 @@ _ACT_NONE, _ACT_RELU, _ACT_ELU = 0, 1, 2
 class _Csr:
     __slots__ = ("rowptr", "col", "val", "rowptr_t", "col_t", "val_t", "nv", "nnz",
                  "ell_w", "ell_col", "ell_val", "ell_col_t", "ell_val_t", "inv_deg", "over", "over_t",
+                 "symmetric_structure",
                  "_deform_tail")      # (geometrics_amd.deform: the rows' entries beyond the table as a second fixed-width table)
 
 
@@ -88,6 +89,10 @@ def _finish_csr(c):
     # 1 / (neighbours without the self loop): what batch_get_lap_info divides by on the binary adjacency
     c.inv_deg = (1.0 / ((c.rowptr[1:] - c.rowptr[:-1]).float() - 1.0)).contiguous()
     c.ell_w = _ell_width(c.rowptr[1:] - c.rowptr[:-1], c.rowptr_t[1:] - c.rowptr_t[:-1]) if c.nv else 0
+    # A[u][v] != 0 exactly where A[v][u] != 0 (values may differ): every route builds rows with their columns in ascending
+    # order, so the pattern is symmetric iff CSR and CSR^T have the same (rowptr, col).  The chain launches of
+    # geometrics_amd.deform rely on it (a vertex waits only on the vertices of its own row before it overwrites its row).
+    c.symmetric_structure = bool(torch.equal(c.rowptr, c.rowptr_t) and torch.equal(c.col, c.col_t))
     c.ell_col = c.ell_val = c.ell_col_t = c.ell_val_t = c.over = c.over_t = None
     if c.ell_w:
         c.ell_col, c.ell_val, c.over = _to_ell(c.rowptr, c.col, c.val, c.ell_w)

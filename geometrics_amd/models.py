@@ -244,6 +244,11 @@ class VertexBatchNorm(nn.Module):
     def forward(self, x, relu=False, residual=None, scale=0.5, tap=False):
         """tap=True returns the result twice: on the HIP kernel two tensor objects over the same memory whose gradients
         are added inside the backward kernel (give one to each consumer); on the library routes the same tensor twice."""
+        if x.dim() < 2 or x.shape[1] != self.num_features:
+            # (as nn.BatchNorm1d does; checked on the host before anything is enqueued: the kernels index the per-vertex
+            # parameters and statistics by the input's vertex)
+            raise RuntimeError("running_mean should contain %d elements not %d"
+                               % (x.shape[1] if x.dim() >= 2 else 0, self.num_features))
         if self._synchronised() or not self.fused_kernel_serves(x):
             if self.training:
                 self._pending_batches += 1      # nn.BatchNorm1d's num_batches_tracked, folded in when the state is saved

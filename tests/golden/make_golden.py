@@ -413,6 +413,141 @@ def make_block():
     save("deformation_block_v162", **arrays)
 
 
+# ------------------------------------------------- deformation block at width 192 ----
+# case -> (mesh, batch, ReLU, eval-mode forward after the step, seed, {layer: (BatchNorm setting, value)}); every input and
+# parameter is regenerated from the seed (tests/helpers.py), the fixture stores checksums of them and the reference's results
+BLOCK192_CASES = {
+    "train482": ("uv_sphere_482", 16, True, True, 1920, {}),
+    "smooth482": ("uv_sphere_482", 16, False, False, 1920, {}),
+    "ico162_bn": ("icosphere_162", 5, True, False, 1921, {5: ("eps", 1e-3), 9: ("momentum", 0.3), 13: ("eps", 1e-4)}),
+    "ico162_b24": ("icosphere_162", 24, True, True, 1922, {}),
+}
+BLOCK192_ROWS = 24          # sampled (mesh, vertex) rows of the 192-wide tensors (the [B,V,3] ones: two whole meshes)
+BLOCK192_WROWS = 16         # sampled rows of the weight gradients of gc1, gc2, gc7, gc13
+
+
+BLOCK192_KINK = 2e-5        # every float64 pre-activation of a ReLU case lies at least this far from the ReLU's kink
+
+
+def _off_the_kink(block, g, inp, adj):
+    """BatchNorm biases of the ReLU cases moved off the kink: an fp32 evaluation of the block may put a pre-activation that
+    lies within its rounding of zero on either side, and ONE such switched unit (one mesh, vertex, column) moves the
+    parameter gradients of its layer and of every layer before it by up to 5e-3 of their scale (its BatchNorm backward
+    couples the vertex's whole row, the aggregations spread it) -- what the 482-vertex training case showed: a unit of
+    layer 6 at 4.2e-7 from zero.  Layer by layer, every vertex with a pre-activation within BLOCK192_KINK of zero gets its
+    BatchNorm bias (which shifts the vertex's pre-activations of that layer and nothing before) moved by a few
+    BLOCK192_KINK until none is; later layers are examined after the shift.  Returns the moves as fixture arrays."""
+    import helpers                                   # (tests/, on the path: make_block192)
+    helpers.block192_parameters(block, g)
+    feats, pooled = (torch.from_numpy(inp[k]).double() for k in ("features", "pooled"))
+    A = torch.from_numpy(adj)
+    moves = []
+    for layer in range(1, 14):
+        pre = []
+        with torch.no_grad():
+            helpers.block64(block, feats, pooled, A, relu=True, pre=pre)
+        y = pre[layer - 1]
+        bias = getattr(block, "bn%d" % layer).bias
+        for v in torch.nonzero((y.abs() < BLOCK192_KINK).any(dim=2).any(dim=0)).flatten().tolist():
+            b0 = float(bias[v])
+            for k in (3, -3, 6, -6, 9, -9, 12, -12, 15, -15):
+                moved = float(np.float32(b0 + k * BLOCK192_KINK))
+                if bool(((y[:, v, :] + (moved - b0)).abs() >= BLOCK192_KINK).all()):
+                    break
+            else:
+                raise RuntimeError("no bias of layer %d vertex %d clears the kink" % (layer, v))
+            with torch.no_grad():
+                bias[v] = moved
+            moves.append((layer, v, moved))
+    pre = []
+    with torch.no_grad():
+        helpers.block64(block, feats, pooled, A, relu=True, pre=pre)
+    assert all(float(y.abs().min()) >= BLOCK192_KINK for y in pre)
+    return dict(bn_fix_layer=np.array([m[0] for m in moves], np.int8), bn_fix_vertex=np.array([m[1] for m in moves], np.int16),
+                bn_fix_value=np.array([m[2] for m in moves], np.float32), kink=np.float64(BLOCK192_KINK))
+
+
+def make_block192():
+    """The reference's BatchMeshDeformationBlock(195, V) (hidden 192) in FLOAT64 on fp32-exact inputs: one training step
+    (forward, backward with seeded upstream gradients), then, where the case says so, the eval-mode forward under no_grad
+    with the updated running statistics.  Stored as fp32 (3e-8 relative: far below every bar of the fp32 kernels) with a
+    float64 seeded-weight checksum of every full output and gradient (tests/helpers.weighted_checksum)."""
+    import models as ref_models                      # the reference's models.py
+    assert ref_models.__file__.startswith(REF)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import helpers
+    arrays = {}
+    for mesh in ("uv_sphere_482", "icosphere_162"):
+        V, Fc = meshgen.uv_sphere() if mesh == "uv_sphere_482" else meshgen.icosphere(2)
+        adj = ref_utils.adj_init(t(Fc))["adj"].numpy()
+        r, c = np.nonzero(adj)
+        arrays.update({"%s.adj_rows" % mesh: r.astype(np.int16), "%s.adj_cols" % mesh: c.astype(np.int16),
+                       "%s.adj_vals" % mesh: adj[r, c].astype(np.float32)})
+    for case, (mesh, batch, relu, with_eval, seed, settings) in BLOCK192_CASES.items():
+        nv = 482 if mesh == "uv_sphere_482" else 162
+        r, c = arrays["%s.adj_rows" % mesh].astype(np.int64), arrays["%s.adj_cols" % mesh].astype(np.int64)
+        adj = np.zeros((nv, nv), np.float32)
+        adj[r, c] = arrays["%s.adj_vals" % mesh]
+        out = dict(mesh=np.array(mesh), batch=np.int64(batch), nv=np.int64(nv), seed=np.int64(seed), relu=np.bool_(relu))
+        eps, momentum = np.full(14, 1e-5), np.full(14, 0.1)
+        for i, (what, value) in settings.items():
+            (eps if what == "eps" else momentum)[i - 1] = value
+        out.update(bn_eps=eps, bn_momentum=momentum)
+        inp = helpers.block192_case(out)
+        if relu:
+            out.update(_off_the_kink(ref_models.BatchMeshDeformationBlock(195, nv), out, inp, adj))
+        block = helpers.block192_parameters(ref_models.BatchMeshDeformationBlock(195, nv), out)
+        names = sorted(n for n, _ in block.named_parameters())
+        out["param_names"] = np.array(names)
+        out["in_ck.params"] = np.array([float(dict(block.named_parameters())[n].detach().double().sum()) for n in names])
+        block.double().train()
+        for name, a in inp.items():
+            out["in_ck." + name] = np.float64(a.astype(np.float64).sum())
+        feats, pooled = (torch.from_numpy(inp[k]).double().requires_grad_(True) for k in ("features", "pooled"))
+        g_f, g_c = (torch.from_numpy(inp[k]).double() for k in ("g_features", "g_coords"))
+        A = torch.from_numpy(adj).double()
+        relu_fn = torch.nn.functional.relu
+        if not relu:                                 # the smooth chain: F.relu of the reference's forward is the identity
+            torch.nn.functional.relu = lambda x, inplace=False: x
+        try:
+            out_f, coords = block(feats, pooled, A)
+            ((out_f * g_f).sum() + (coords * g_c).sum()).backward()
+        finally:
+            torch.nn.functional.relu = relu_fn
+        rng = np.random.default_rng([seed, 7])
+        ends = [0, nv - 1]
+        rings = [np.array([j for j in np.nonzero(adj[e])[0] if j != e]) for e in ends]
+        rows_v = ends + [int(ring[k * len(ring) // 3]) for ring in rings for k in range(3)]
+        rest = np.setdiff1d(np.arange(nv), rows_v)
+        rows_v += [int(v) for v in rng.choice(rest, BLOCK192_ROWS - len(rows_v), replace=False)]
+        rows_b = rng.integers(0, batch, BLOCK192_ROWS)
+        rows_b[0], rows_b[1] = 0, batch - 1
+        rows_v, rows_b = np.array(rows_v, np.int32), rows_b.astype(np.int32)
+        meshes = np.array([0, batch - 1], np.int32)      # the [B,V,3] tensors: every vertex of the first and the last mesh
+        out.update(rows_v=rows_v, rows_b=rows_b, meshes=meshes)
+        full = {"features": out_f, "coords": coords, "grad.features": feats.grad, "grad.pooled": pooled.grad}
+        params = dict(block.named_parameters())
+        for name, p in params.items():
+            if not name.startswith("bn14"):
+                full["grad." + name] = p.grad
+        full["running_mean"] = torch.stack([getattr(block, "bn%d" % i).running_mean for i in range(1, 14)])
+        full["running_var"] = torch.stack([getattr(block, "bn%d" % i).running_var for i in range(1, 14)])
+        if with_eval:
+            block.eval()
+            with torch.no_grad():
+                full["eval.features"], full["eval.coords"] = block(feats.detach(), pooled.detach(), A)
+        for i in (1, 2, 7, 13):
+            n_in = params["gc%d.weight1" % i].shape[1]
+            out["wrows.gc%d" % i] = np.concatenate(([0, 1, 2, n_in - 1], rng.choice(np.arange(3, n_in - 1), BLOCK192_WROWS - 4,
+                                                                                     replace=False))).astype(np.int32)
+        full = {k: v.detach().numpy() for k, v in full.items()}
+        out.update({k: v.astype(np.float32) for k, v in helpers.block192_stored(out, full).items()})
+        out["ck_names"] = np.array(sorted(full))
+        out["ck"] = np.stack([helpers.weighted_checksum(name, full[name]) for name in sorted(full)])
+        arrays.update({"%s.%s" % (case, k): v for k, v in out.items()})
+    save("block192", **arrays)
+
+
 # --------------------------------------------------------------- image pooling ----
 def make_pooling():
     torch.cuda.LongTensor = torch.LongTensor          # the reference casts indices with .type(torch.cuda.LongTensor)
@@ -489,6 +624,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--block" in sys.argv:
         make_block()
+        sys.exit(0)
+    if "--block192" in sys.argv:
+        make_block192()
         sys.exit(0)
     if "--nn-fma" in sys.argv:
         make_nn_fma()

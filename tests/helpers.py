@@ -32,6 +32,174 @@ def fill_parameters(module, seed, gain=2.0):
     return module
 
 
+def fill_block_parameters(block, seed):
+    """fill_parameters for a mesh deformation block (reference models.py:203-235) at the reference's own init scale
+    (layers.py:99-105: weight1 [1, in, out] ~ U(+-0.3 * 6 / sqrt(in + 1)), bias ~ U(+-0.1)) and with non-trivial
+    BatchNorm affine parameters: weight ~ U(0.5, 1.5), bias ~ U(-0.3, 0.3).  Same seed-per-name scheme: the block of the
+    reference (nn.BatchNorm1d) and the project's get the same values whatever their dtype."""
+    import zlib
+
+    import torch
+    with torch.no_grad():
+        for name, p in sorted(block.named_parameters()):
+            rng = np.random.default_rng([seed, zlib.crc32(name.encode())])
+            if name.endswith("weight1"):
+                lo, hi = -1.8 / np.sqrt(p.shape[1] + p.shape[0]), 1.8 / np.sqrt(p.shape[1] + p.shape[0])
+            elif name.startswith("bn"):
+                lo, hi = (0.5, 1.5) if name.endswith("weight") else (-0.3, 0.3)
+            else:
+                lo, hi = -0.1, 0.1
+            p.copy_(torch.from_numpy(rng.uniform(lo, hi, tuple(p.shape)).astype(np.float32)))
+    return block
+
+
+def seeded_input(seed, shape, scale=1.0):
+    """A deterministic fp32 array ~ scale * N(0, 1) (numpy's generator, independent of torch's stream)."""
+    return (np.random.default_rng(seed).standard_normal(tuple(shape)) * scale).astype(np.float32)
+
+
+def checksum_weights(name, shape):
+    """Seeded float64 weights in U(-1, 1) for the checksum of a tensor called `name`."""
+    import zlib
+    return np.random.default_rng([1920, zlib.crc32(name.encode())]).uniform(-1.0, 1.0, tuple(shape))
+
+
+def weighted_checksum(name, t):
+    """(sum(t * w), sum(|t| * |w|)) in float64, w = checksum_weights(name, t.shape): a change anywhere in t moves the first
+    by its size times a weight of order one; the second is the scale the first is compared at."""
+    t = np.asarray(t, np.float64)
+    w = checksum_weights(name, t.shape)
+    return np.array([(t * w).sum(), (np.abs(t) * np.abs(w)).sum()])
+
+
+# ---- the mesh deformation block restated in float64 (reference models.py:237-297 on layers.py:107-116) --------------------
+def bn64(z, gamma, beta, eps):
+    """nn.BatchNorm1d(verts) on [B,V,C] in training mode, float64: one statistic per vertex over (B, C)."""
+    mean = z.mean(dim=(0, 2), keepdim=True)
+    var = ((z - mean) ** 2).mean(dim=(0, 2), keepdim=True)
+    return (z - mean) / (var + eps).sqrt() * gamma.view(1, -1, 1) + beta.view(1, -1, 1), mean.flatten(), var.flatten()
+
+
+def block64(block, feats, pooled, adj, relu=True, stats=None, running=None, pre=None):
+    """models.py:237-297 restated in float64 on the host (dense adjacency, torch ops): returns (features, coords, parameters)
+    -- the parameters as float64 leaves, whose .grad a backward pass fills.  Each layer normalises with ITS BatchNorm's eps.
+    stats (a list): receives every layer's batch statistics (mean, biased variance) in order.  running ({layer: (mean, var)}):
+    eval mode -- those statistics normalise instead of the batch's.  pre (a list): receives every layer's pre-activation (what
+    the ReLU is applied to)."""
+    import torch
+    p = {k: v.detach().double().cpu().requires_grad_(v.requires_grad) for k, v in block.named_parameters()}
+    adj = adj.double().cpu()
+
+    def gc(i, x):
+        sup = x @ p["gc%d.weight1" % i][0]
+        k = sup.shape[-1] // 3
+        return torch.cat((adj @ sup[..., :k], sup[..., k:]), dim=-1) + p["gc%d.bias" % i]
+
+    def layer(i, x):
+        gamma, beta, eps = p["bn%d.weight" % i], p["bn%d.bias" % i], float(getattr(block, "bn%d" % i).eps)
+        if running is not None:
+            mean, var = (torch.as_tensor(t, dtype=torch.float64).view(1, -1, 1) for t in running[i])
+            y = (gc(i, x) - mean) / (var + eps).sqrt() * gamma.view(1, -1, 1) + beta.view(1, -1, 1)
+        else:
+            y, mean, var = bn64(gc(i, x), gamma, beta, eps)
+            if stats is not None:
+                stats.append((mean.detach(), var.detach()))
+        if pre is not None:
+            pre.append(y.detach())
+        return torch.relu(y) if relu else y
+    f = torch.cat((feats, pooled), dim=-1)
+    x = layer(1, f)
+    x = layer(2, x)
+    f = (f[..., :block.hidden] + x) / 2
+    for i in (3, 5, 7, 9, 11):
+        x = layer(i, f)
+        x = layer(i + 1, x)
+        f = (f + x) / 2
+    x = layer(13, f)
+    f = (f + x) / 2
+    return f, gc(15, f), p
+
+
+def block192_parameters(block, g):
+    """A case's parameters on `block` (the reference's or the project's, any dtype): fill_block_parameters(seed), then the
+    case's BatchNorm biases moved off the ReLU kink (bn_fix_layer / bn_fix_vertex / bn_fix_value: see make_golden.py
+    make_block192) and its per-layer BatchNorm eps / momentum; checked against the fixture's checksums where it has them."""
+    import torch
+    fill_block_parameters(block, int(g["seed"]))
+    with torch.no_grad():
+        for layer, v, value in zip(g.get("bn_fix_layer", ()), g.get("bn_fix_vertex", ()), g.get("bn_fix_value", ())):
+            getattr(block, "bn%d" % int(layer)).bias[int(v)] = float(value)
+    for i in range(1, 15):
+        bn = getattr(block, "bn%d" % i)
+        bn.eps, bn.momentum = float(g["bn_eps"][i - 1]), float(g["bn_momentum"][i - 1])
+    if "in_ck.params" in g:
+        named = dict(block.named_parameters())
+        assert sorted(named) == list(g["param_names"])
+        assert [float(named[n].detach().double().sum()) for n in g["param_names"]] == list(g["in_ck.params"])
+    return block
+
+
+def block192_case(g):
+    """Inputs of a case of tests/golden/block192.npz regenerated from its seeds, each checked against the fixture's float64
+    checksum (a change in numpy's random stream fails here instead of comparing different inputs): dict of fp32 arrays
+    features [B,V,3], pooled [B,V,192], g_features [B,V,192], g_coords [B,V,3]."""
+    b, nv, seed = int(g["batch"]), int(g["nv"]), int(g["seed"])
+    shapes = dict(features=(b, nv, 3), pooled=(b, nv, 192), g_features=(b, nv, 192), g_coords=(b, nv, 3))
+    out = {}
+    for k, (name, shape) in enumerate(sorted(shapes.items())):
+        out[name] = seeded_input([seed, k], shape)
+        if "in_ck." + name in g:
+            assert float(out[name].astype(np.float64).sum()) == float(g["in_ck." + name]), name
+    return out
+
+
+BLOCK192_CASES = ("train482", "smooth482", "ico162_bn", "ico162_b24")
+
+
+def block192_fixture(case):
+    """One case of tests/golden/block192.npz as a dict without the case prefix, with its mesh's COO adjacency (adj_rows,
+    adj_cols, adj_vals) and `adj` (the dense fp32 [V,V] matrix)."""
+    g = golden("block192")
+    out = {k[len(case) + 1:]: v for k, v in g.items() if k.startswith(case + ".")}
+    mesh = str(out["mesh"])
+    out.update({k[len(mesh) + 1:]: v for k, v in g.items() if k.startswith(mesh + ".")})
+    nv = int(out["nv"])
+    adj = np.zeros((nv, nv), np.float32)
+    adj[out["adj_rows"].astype(np.int64), out["adj_cols"].astype(np.int64)] = out["adj_vals"]
+    out["adj"] = adj
+    return out
+
+
+def block192_stored(g, full):
+    """The arrays block192.npz stores, taken out of a case's FULL results (numpy; keyed like the fixture's checksums:
+    features, coords, grad.features, grad.pooled, grad.<parameter>, running_mean / running_var [13,V], eval.*) exactly as
+    the fixture's maker takes them: (mesh, vertex) rows of the 192-wide tensors, two whole meshes of the [B,V,3] ones,
+    sampled rows of four weight gradients, the rest in full; the 13 layers' vectors stacked."""
+    rb, rv, m = g["rows_b"].astype(np.int64), g["rows_v"].astype(np.int64), g["meshes"].astype(np.int64)
+    out = {"features_rows": full["features"][rb, rv], "coords": full["coords"][m], "grad.features": full["grad.features"][m],
+           "grad.pooled_rows": full["grad.pooled"][rb, rv],
+           "grad.gc_bias": np.stack([full["grad.gc%d.bias" % i] for i in range(1, 14)]),
+           "grad.gc15.bias": full["grad.gc15.bias"], "grad.gc15.weight1": full["grad.gc15.weight1"],
+           "grad.bn_weight": np.stack([full["grad.bn%d.weight" % i] for i in range(1, 14)]),
+           "grad.bn_bias": np.stack([full["grad.bn%d.bias" % i] for i in range(1, 14)]),
+           "running_mean": full["running_mean"], "running_var": full["running_var"]}
+    for i in (1, 2, 7, 13):
+        out["grad.gc%d.weight1_rows" % i] = full["grad.gc%d.weight1" % i][0][g["wrows.gc%d" % i].astype(np.int64)]
+    if "eval.features" in full:
+        out["eval.features_rows"] = full["eval.features"][rb, rv]
+        out["eval.coords"] = full["eval.coords"][m]
+    return out
+
+
+def log_margin(what, err, bar):
+    """err against its bar (both relative); appended to $GEOM_MARGIN_LOG when set (margins of a run, for the bounds)."""
+    log = os.environ.get("GEOM_MARGIN_LOG")
+    if log:
+        with open(log, "a") as f:
+            f.write("%s: %.3g (bar %g, %.3f of it)\n" % (what, err, bar, err / bar))
+    return err <= bar
+
+
 def tri_true_case(name):
     """Inputs of a tests/golden/tri_true_*.npz fixture, regenerated from their seeds (the fixture stores the expected
     per-point true squared distances + a checksum of the inputs): (verts [B,V,3], faces [F,3], points [B,N,3], true [B,N])."""

@@ -10,12 +10,18 @@ geometrics_amd/deform.py; reference models.py:237-297 on layers.py:107-116).
 * the step inside a HIP graph; shapes the launches do not serve fall back to the separate operators;
 * the thirteen launches of a direction as ONE (a vertex's workgroup waits for its neighbours' rows inside the launch): bit for
   bit the layer-by-layer launches; only the stream that owns a device's chain launches issues them; a mesh whose workgroups are
-  not all resident at once takes the layer-by-layer launches."""
+  not all resident at once takes the layer-by-layer launches;
+* the block at width 192 against the reference's own block run in float64 (tests/golden/block192.npz): the chain launch,
+  the smooth chain, per-layer BatchNorm settings, the batch > 16 fall-back and the eval-mode forward;
+* a directed adjacency takes the launches per layer (never the chain), a block for another vertex count raises on the host."""
 import numpy as np
 import pytest
 import torch
 
 from geometrics_amd import deform, layers, meshgen, models, utils
+from helpers import (BLOCK192_CASES, bits, block192_case, block192_fixture, block192_parameters, block192_stored, log_margin,
+                     weighted_checksum)
+from helpers import bn64 as _bn64, block64 as _block64
 
 pytestmark = pytest.mark.gpu
 
@@ -29,13 +35,6 @@ def _mesh(name, gpu):
 def _maxrel(a, b):
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return float((a - b).abs().max()) / max(float(b.abs().max()), 1e-30)
-
-
-def _bn64(z, gamma, beta, eps):
-    """nn.BatchNorm1d(verts) on [B,V,C] in training mode, float64: one statistic per vertex over (B, C)."""
-    mean = z.mean(dim=(0, 2), keepdim=True)
-    var = ((z - mean) ** 2).mean(dim=(0, 2), keepdim=True)
-    return (z - mean) / torch.sqrt(var + eps) * gamma.view(1, -1, 1) + beta.view(1, -1, 1), mean.flatten(), var.flatten()
 
 
 @pytest.mark.parametrize("mesh,batch", [("uv_sphere_482", 16), ("icosphere_162", 5)])
@@ -116,32 +115,6 @@ def test_one_backward_launch_against_the_separate_operators(gpu, mesh, batch):
     gy = torch.where(on, (g + g2).double().cpu(), torch.zeros_like(gx))
     sg, sgx = gy.sum(dim=(0, 2)), (gy * xh).sum(dim=(0, 2))
     assert _maxrel(dz2, ga * i * (gy - sg.view(1, -1, 1) / n - xh * sgx.view(1, -1, 1) / n)) <= 1e-4
-
-
-def _block64(block, feats, pooled, adj, relu=True):
-    """models.py:237-297 restated in float64 on the host (dense adjacency, torch ops): returns (features, coords, parameters)."""
-    p = {k: v.detach().double().cpu().requires_grad_(v.requires_grad) for k, v in block.named_parameters()}
-    adj = adj.double().cpu()
-
-    def gc(i, x):
-        sup = x @ p["gc%d.weight1" % i][0]
-        k = sup.shape[-1] // 3
-        return torch.cat((adj @ sup[..., :k], sup[..., k:]), dim=-1) + p["gc%d.bias" % i]
-
-    def layer(i, x):
-        y, _, _ = _bn64(gc(i, x), p["bn%d.weight" % i], p["bn%d.bias" % i], 1e-5)
-        return torch.relu(y) if relu else y
-    f = torch.cat((feats, pooled), dim=-1)
-    x = layer(1, f)
-    x = layer(2, x)
-    f = (f[..., :block.hidden] + x) / 2
-    for i in (3, 5, 7, 9, 11):
-        x = layer(i, f)
-        x = layer(i + 1, x)
-        f = (f + x) / 2
-    x = layer(13, f)
-    f = (f + x) / 2
-    return f, gc(15, f), p
 
 
 def _l2rel(a, b):
@@ -460,3 +433,188 @@ def test_chain_launches_under_a_busy_neighbour_stream(gpu):
         for x, y in zip(got, ref):
             assert torch.equal(x, y), "step %d" % step
     torch.cuda.synchronize()
+
+
+def _spy_chain(monkeypatch, forbid=False):
+    """The names of the chain launches asked for from here on: deform.chain_forward / chain_backward still run, or with
+    forbid = True fail the test instead of launching."""
+    calls = []
+    for name in ("chain_forward", "chain_backward"):
+        real = getattr(deform, name)
+
+        def spy(*a, _real=real, _name=name, **k):
+            calls.append(_name)
+            if forbid:
+                raise AssertionError("%s asked for on a directed adjacency" % _name)
+            return _real(*a, **k)
+        monkeypatch.setattr(deform, name, spy)
+    return calls
+
+
+# case -> (deform.serves at the case's shape, chain launches taken)
+_BLOCK192_ROUTES = {"train482": (True, True), "smooth482": (True, True), "ico162_bn": (True, True), "ico162_b24": (False, False)}
+
+
+@pytest.mark.parametrize("case", BLOCK192_CASES)
+def test_block192_against_the_reference_fixture(gpu, case, monkeypatch):
+    """The block at the width that ships (192) against the REFERENCE's BatchMeshDeformationBlock(195, V) run in float64
+    (tests/golden/block192.npz): train482 = the reference's training shape on the fused chain launches (482 vertices, two
+    33-entry poles: table + tail); smooth482 = the same without the ReLUs (deform.relu = False; the reference's F.relu made the
+    identity); ico162_bn = batch 5 (rows beyond the batch are zero rows of the tile) with per-layer BatchNorm settings that
+    differ from bn1's; ico162_b24 = batch 24 on the separate operators and the library BatchNorm (24 x 192 > 4096 values per
+    vertex).  After the step, where stored, the eval-mode forward under no_grad with the updated running statistics (the
+    reference driver's validation loop).  Every stored gradient ELEMENT is held to 5e-5 of its tensor's scale, in the ReLU
+    cases too: their fixture keeps every float64 pre-activation at least 2e-5 from the ReLU's kink (make_golden.py
+    _off_the_kink), so no fp32 evaluation switches a unit (one switched unit of layer 6 moved the parameter gradients of
+    layers 1-6 by up to 6e-3 of their scale)."""
+    g = block192_fixture(case)
+    inp = block192_case(g)                    # (checksums of the regenerated inputs asserted)
+    b, nv = int(g["batch"]), int(g["nv"])
+    relu = bool(g["relu"])
+    V, Fc = meshgen.uv_sphere() if str(g["mesh"]) == "uv_sphere_482" else meshgen.icosphere(2)
+    adj = utils.adj_init(torch.from_numpy(Fc).to(gpu))["adj"]
+    a = adj.cpu().numpy()
+    r, c = np.nonzero(a)
+    assert np.array_equal(r, g["adj_rows"]) and np.array_equal(c, g["adj_cols"]) and np.array_equal(bits(a[r, c]), bits(g["adj_vals"]))
+    csr = layers.adjacency_csr(adj)
+    block = block192_parameters(models.BatchMeshDeformationBlock(195, nv), g).to(gpu).train()     # (checksums asserted)
+    named = dict(block.named_parameters())
+    to = lambda k: torch.from_numpy(inp[k]).to(gpu)          # noqa: E731
+    feats, pooled = to("features").requires_grad_(True), to("pooled").requires_grad_(True)
+    serves, chained = _BLOCK192_ROUTES[case]
+    assert deform.serves(block, feats, pooled, csr) == serves
+    if not serves:
+        assert not block.bn1.fused_kernel_serves(torch.empty(b, nv, 192, device=gpu))      # the library BatchNorm
+    calls = _spy_chain(monkeypatch)
+    monkeypatch.setattr(deform, "relu", relu)
+    out_f, coords = block(feats, pooled, adj)
+    ((out_f * to("g_features")).sum() + (coords * to("g_coords")).sum()).backward()
+    assert calls == (["chain_forward", "chain_backward"] if chained else [])
+    monkeypatch.setattr(deform, "relu", True)
+    sd = block.state_dict()
+    assert all(int(sd["bn%d.num_batches_tracked" % i]) == 1 for i in range(1, 14)) and int(sd["bn14.num_batches_tracked"]) == 0
+    assert all(named[k].grad is None for k in named if k.startswith("bn14"))
+    np64 = lambda t: t.detach().double().cpu().numpy()         # noqa: E731
+    full = {"features": np64(out_f), "coords": np64(coords), "grad.features": np64(feats.grad), "grad.pooled": np64(pooled.grad),
+            "running_mean": np.stack([np64(getattr(block, "bn%d" % i).running_mean) for i in range(1, 14)]),
+            "running_var": np.stack([np64(getattr(block, "bn%d" % i).running_var) for i in range(1, 14)])}
+    full.update({"grad." + k: np64(p.grad) for k, p in named.items() if not k.startswith("bn14")})
+    if "eval.coords" in g:
+        block.eval()
+        with torch.no_grad():
+            e_f, e_c = block(feats.detach(), pooled.detach(), adj)
+        full.update({"eval.features": np64(e_f), "eval.coords": np64(e_c)})
+    assert sorted(full) == list(g["ck_names"])
+    stored = block192_stored(g, full)
+    assert set(stored) == {k for k in g if k in stored}
+
+    def maxrel(x, y):
+        return float(np.abs(x - y).max()) / max(float(np.abs(y).max()), 1e-30)
+
+    def tensors(key, x):          # (the 13 layers' stacked vectors are 13 tensors)
+        if key in ("grad.gc_bias", "grad.bn_weight", "grad.bn_bias", "running_mean", "running_var"):
+            return [("%s %s[layer %d]" % (case, key, i + 1), t) for i, t in enumerate(x)]
+        return [("%s %s" % (case, key), x)]
+    bad = []
+    for key, got in stored.items():
+        for (what, x), (_, y) in zip(tensors(key, got), tensors(key, g[key].astype(np.float64))):
+            if not key.startswith("grad."):          # forward, eval forward, running statistics
+                bar = 1e-5 if key.startswith("running") else 2e-5
+                if not log_margin(what + " max-norm", maxrel(x, y), bar):
+                    bad.append("%s: %.2e of scale (bar %g)" % (what, maxrel(x, y), bar))
+            elif not log_margin(what + " max-norm", maxrel(x, y), 5e-5):     # every gradient element
+                bad.append("%s: %.2e of scale (bar 5e-5)" % (what, maxrel(x, y)))
+    for name, (want, scale) in zip(g["ck_names"], g["ck"]):
+        name = str(name)
+        bar = 1e-5 if name.startswith("running") else 2e-5 if not name.startswith("grad.") else 5e-5
+        err = abs(weighted_checksum(name, full[name])[0] - want) / scale
+        if not log_margin("%s checksum %s" % (case, name), err, bar):
+            bad.append("checksum of %s: %.2e of its scale (bar %g)" % (name, err, bar))
+    assert not bad, "; ".join(bad)
+
+
+def _directed_482():
+    """The 482-vertex template's normalised adjacency made DIRECTED (host tensor): A[u][v] deleted for every third edge
+    u < v (A[v][u] kept), and one-way entries between vertices far apart in the numbering -- different XCD runs of the
+    launches' vertex order (db_vertex: runs of 61 vertices).  Rows stay within the 8-wide table + the tail."""
+    V, Fc = meshgen.uv_sphere()
+    a = utils.adj_init(torch.from_numpy(Fc))["adj"].clone()
+    u, v = np.nonzero(np.triu(a.numpy(), 1))
+    a[u[::3], v[::3]] = 0.0
+    for p, q in ((10, 400), (100, 300), (200, 470), (300, 30), (450, 60), (130, 250)):
+        assert a[p, q] == 0 and a[q, p] == 0
+        a[p, q] = 0.125
+    return a
+
+
+@pytest.mark.parametrize("relu", [False, True])
+def test_block_on_a_directed_adjacency(gpu, relu, monkeypatch):
+    """A directed adjacency (A[u][v] != 0 where A[v][u] == 0) may not take the chain launch: there vertex v rewrites its support
+    row once the vertices of ITS row are past the previous layer, and u, which gathers v's row, is not among them.  The block
+    takes the fused launches per layer instead (and, deform.enabled = False, the separate operators): both against the
+    float64 restatement on the same dense adjacency, at the bars of test_the_fused_block_against_float64... (relu=False:
+    deform.relu applies to the fused launches only, so the separate operators are compared under ReLU).  A symmetric
+    pattern with asymmetric values -- the row-normalised mesh adjacency itself -- still takes the chain."""
+    import copy
+    adj = _directed_482().to(gpu)
+    nv = adj.shape[0]
+    csr = layers.adjacency_csr(adj)
+    assert not csr.symmetric_structure and csr.ell_w == 8 and csr.over is not None
+    assert not torch.equal(adj != 0, (adj != 0).t())
+    torch.manual_seed(20)
+    block = models.BatchMeshDeformationBlock(3 + 200, nv).to(gpu).train()
+    with torch.no_grad():
+        for i in range(1, 14):
+            getattr(block, "bn%d" % i).weight.uniform_(0.5, 1.5)
+            getattr(block, "bn%d" % i).bias.uniform_(-0.3, 0.3)
+    feats = torch.randn(16, nv, 3, device=gpu)
+    pooled = torch.randn(16, nv, 200, device=gpu)
+    g_f, g_c = torch.randn(16, nv, 192, device=gpu), torch.randn(16, nv, 3, device=gpu)
+    f64, p64 = feats.double().cpu().requires_grad_(True), pooled.double().cpu().requires_grad_(True)
+    e_f, e_c, params64 = _block64(block, f64, p64, adj, relu)
+    ((e_f * g_f.double().cpu()).sum() + (e_c * g_c.double().cpu()).sum()).backward()
+    calls = _spy_chain(monkeypatch, forbid=True)
+    for fused in ((True, False) if relu else (True,)):
+        blk = copy.deepcopy(block)
+        monkeypatch.setattr(deform, "enabled", fused)
+        monkeypatch.setattr(deform, "relu", relu)
+        f, p = feats.clone().requires_grad_(True), pooled.clone().requires_grad_(True)
+        assert deform.serves(blk, f, p, csr) == fused
+        out_f, coords = blk(f, p, adj)
+        ((out_f * g_f).sum() + (coords * g_c).sum()).backward()
+        assert calls == []
+        assert _maxrel(out_f, e_f) <= 2e-5 and _maxrel(coords, e_c) <= 2e-5
+        named = dict(blk.named_parameters())
+        pairs = [(n, q.grad, params64[n].grad) for n, q in named.items() if not n.startswith("bn14")]
+        pairs += [("features", f.grad, f64.grad), ("pooled", p.grad, p64.grad)]
+        for name, got, want in pairs:
+            if relu:
+                assert _l2rel(got, want) <= 5e-3, "%s (fused %s): %.2e from float64 in the L2 norm" % (name, fused, _l2rel(got, want))
+            else:
+                assert _maxrel(got, want) <= 5e-5, "%s: %.2e of scale from float64" % (name, _maxrel(got, want))
+    monkeypatch.undo()              # (deform.enabled / relu back to True, the launches unwrapped)
+    calls = _spy_chain(monkeypatch)
+    nv, sym, csr = _mesh("uv_sphere_482", gpu)
+    assert csr.symmetric_structure and not torch.equal(sym, sym.t())
+    out_f, coords = block(feats.clone().requires_grad_(True), pooled, sym)
+    (out_f.sum() + coords.sum()).backward()
+    assert calls == ["chain_forward", "chain_backward"]
+
+
+def test_a_block_for_another_vertex_count_raises_before_any_launch(gpu):
+    """A block built for 162 vertices given 482-vertex inputs raises as the reference's nn.BatchNorm1d does, on the fused
+    route and on the separate operators, before any BatchNorm launch (which would index the 162-entry parameters and
+    statistics by vertices up to 481): the launches never serve the call, and VertexBatchNorm checks on the host."""
+    nv, adj, csr = _mesh("uv_sphere_482", gpu)
+    block = models.BatchMeshDeformationBlock(3 + 197, 162).to(gpu).train()
+    f, p = torch.randn(16, nv, 3, device=gpu), torch.randn(16, nv, 197, device=gpu)
+    assert not deform.serves(block, f, p, csr)
+    try:
+        for fused in (True, False):
+            deform.enabled = fused
+            with pytest.raises(RuntimeError, match="running_mean should contain 482 elements not 162"):
+                block(f, p, adj)
+    finally:
+        deform.enabled = True
+    torch.cuda.synchronize()
+    assert all(bool((getattr(block, "bn%d" % i).running_mean == 0).all()) for i in range(1, 15))
