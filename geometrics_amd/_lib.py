@@ -138,6 +138,7 @@ _SIGNATURES = {
     "geom_deform_chain_bwd_f32": [_i, _vp, _vp, _vp, _vp],
     "geom_deform_chain_fits": [_i],
     "geom_deform_layer_bwd_f32": [_vp, _vp],
+    "geom_deform_infer_fwd_f32": [_vp, _vp],
 }
 
 
@@ -163,6 +164,17 @@ class DeformBwd(ctypes.Structure):
                 ("relu", _i), ("has_res", _i), ("scale", _f),
                 ("grad_res", _vp), ("dz", _vp), ("grad_bn_w", _vp), ("grad_bn_b", _vp), ("colsum", _vp),
                 ("ds_head", _vp), ("w_head", _vp), ("x_top", _vp), ("dw_head", _vp), ("vpx", _i)]
+
+
+class DeformInfer(ctypes.Structure):
+    """struct geom_deform_infer (include/geom_hip.h): a hidden layer of the deformation block, eval-mode forward."""
+    _fields_ = [("b", _i), ("nv", _i), ("c", _i), ("k", _i), ("ell_w", _i),
+                ("s_in", _vp), ("bias", _vp), ("ell_col", _vp), ("ell_val", _vp),
+                ("tail_col", _vp), ("tail_val", _vp),
+                ("bn_w", _vp), ("bn_b", _vp), ("run_mean", _vp), ("run_var", _vp),
+                ("eps", _f), ("relu", _i),
+                ("res", _vp), ("res_ld", _i), ("scale", _f),
+                ("x_out", _vp), ("w_next", _vp), ("s_out", _vp), ("w_head", _vp), ("s_head", _vp)]
 
 
 class SurfaceCull(ctypes.Structure):

@@ -724,6 +724,186 @@ __global__ __launch_bounds__(DB_THREADS, 2) void db_bwd_chain_kernel(DbBwdChain 
     }
 }
 
+// ---- the eval-mode forward (geom_deform_infer_fwd_f32): one launch per hidden layer, BatchNorm on the running statistics
+//
+//   Z   = [A . S[:, :64] | S[:, 64:]] + bias          zn_gcn.hip's order and arithmetic (table slots, then the tail, in CSR order)
+//   X'  = ReLU((Z - rm_v) * (1 / sqrtf(rv_v + eps)) * gamma_v + beta_v) (+ residual, * scale)   vertex_bn.hip's eval branch
+//   S'  = X' . W_next                                  exact fp32 on v_mfma_f32_16x16x4_f32 (db_product)
+//
+// Tiling: in eval mode BatchNorm1d(verts) is a fixed per-vertex affine map -- no reduction over the batch is left -- so the rows
+// are independent apart from the gather, and the tile is 16 CONSECUTIVE rows of the flattened [b * nv] row space (a row-block;
+// it may span two meshes: every row gathers inside its own mesh).  At the driver's validation batch of 1 that fills the MFMA
+// rows the training tiling (one vertex = one tile, its batch rows = the tile's rows) leaves 15/16 empty, and any batch works.
+// The table, the BatchNorm parameters and the statistics are per ROW here (vector loads; the training kernel has one vertex
+// per workgroup and reads them with scalar loads); a pole's tail is walked four entries per round trip by its own 16 lanes
+// (the wave's weight slice is live across it: there are no registers for more).
+//
+// Work per workgroup: a workgroup keeps the wave's 192 x 48 weight slice in registers (36 KB per wave, 147 KB per workgroup)
+// and runs q or q + 1 consecutive row-blocks (zn_stack.hip's q / rem dealing) over at most DI_WGS = 512 workgroups -- two per
+// CU of an MI355X, the residency of __launch_bounds__(256, 2).  Batch 1 (31 row-blocks) and batch 16 (482) get one row-block
+// per workgroup: the launch is one latency chain (table -> gathers -> product), and more workgroups are more chains in flight.
+// Above 512 row-blocks a workgroup takes two or more in turn instead of a new workgroup re-reading the 147 KB slice from L2:
+// at batch 40 (1 205 row-blocks) 512 slices are read instead of 1 205.  Logical workgroup order follows db_vertex: contiguous
+// row-block runs per XCD, so the neighbour rows a run gathers stay in one L2.
+// No workgroup waits for another: a launch depends only on the one before it in stream order.
+constexpr int DI_WGS = 512;
+
+template <bool PRODUCT, bool LOAD_SLICE>
+__device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const int rb, float *lds, DbSlice &bw)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = lane & 15, g = lane >> 4; // matrix-core coordinates
+    const int rl = tid >> 4, j = tid & 15;  // row of the block and float4 group of the gather / BatchNorm thread
+    const int c0 = 4 * j;
+    const int rows = a.b * a.nv;
+    const int r = rb * 16 + rl;
+    const bool on = r < rows;
+    const int mesh = on ? r / a.nv : 0, v = on ? r - mesh * a.nv : 0;
+    const int64_t op_bytes = (int64_t)rows * DB_C * 4;
+    const __amdgpu_buffer_rsrc_t r_src = db_rsrc(a.s_in, op_bytes);
+    const unsigned rowbase = (unsigned)mesh * (unsigned)a.nv * (DB_C * 4);
+    const unsigned own_off = on ? (unsigned)r * (DB_C * 4) + 4 * c0 : DB_OOB;
+    // round trip 1: the row's table, the first entry of its tail row, the vertex's BatchNorm parameters and running
+    // statistics, the bias and the residual
+    int nb[DB_W];
+    float wv[DB_W];
+    {
+        const int4 ci0 = *reinterpret_cast<const int4 *>(a.ell_col + (size_t)v * DB_W), ci1 = *reinterpret_cast<const int4 *>(a.ell_col + (size_t)v * DB_W + 4);
+        const float4 wi0 = *reinterpret_cast<const float4 *>(a.ell_val + (size_t)v * DB_W), wi1 = *reinterpret_cast<const float4 *>(a.ell_val + (size_t)v * DB_W + 4);
+        nb[0] = ci0.x, nb[1] = ci0.y, nb[2] = ci0.z, nb[3] = ci0.w, nb[4] = ci1.x, nb[5] = ci1.y, nb[6] = ci1.z, nb[7] = ci1.w;
+        wv[0] = wi0.x, wv[1] = wi0.y, wv[2] = wi0.z, wv[3] = wi0.w, wv[4] = wi1.x, wv[5] = wi1.y, wv[6] = wi1.z, wv[7] = wi1.w;
+    }
+    const int tail0 = a.tail_col ? a.tail_col[(size_t)v * DB_TAIL] : -1;
+    const float gamma = a.bn_w ? a.bn_w[v] : 1.f, beta = a.bn_b ? a.bn_b[v] : 0.f;
+    const float mean = a.run_mean[v], invstd = 1.f / sqrtf(a.run_var[v] + a.eps);
+    float4 bias4[3], rv[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        bias4[i] = a.bias ? *reinterpret_cast<const float4 *>(a.bias + c0 + DB_K * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (a.res) {
+        const __amdgpu_buffer_rsrc_t r_res = db_rsrc(a.res, ((int64_t)rows - 1) * a.res_ld * 4 + DB_C * 4);
+        const unsigned roff = (unsigned)r * (unsigned)a.res_ld * 4u + 4 * c0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) rv[i] = db_ld4(r_res, on ? roff + 4 * DB_K * i : DB_OOB);
+    }
+    // round trip 2: the neighbour rows + the thread's own pass-through elements; the weight slice behind them (the
+    // vector-memory counter retires in order: asked for first, it would hold up every gather).  A later row-block of the
+    // workgroup holds the slice already: its gathers go in two rounds of four (no registers for eight rows in flight;
+    // hipcc -Rpass-analysis=kernel-resource-usage: 246 VGPRs, 0 bytes of scratch)
+    constexpr int ROUND = LOAD_SLICE || !PRODUCT ? DB_W : DB_W / 2;
+    float4 z[3];
+#pragma unroll
+    for (int i = 1; i < 3; ++i) z[i] = db_ld4(r_src, on ? own_off + 4 * DB_K * i : DB_OOB);
+    float4 facc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int n0 = 0; n0 < DB_W; n0 += ROUND) {
+        float4 sv[ROUND];
+#pragma unroll
+        for (int n = 0; n < ROUND; ++n)
+            sv[n] = db_ld4(r_src, on ? rowbase + (unsigned)(nb[n0 + n] >= 0 ? nb[n0 + n] : v) * (DB_C * 4) + 4 * c0 : DB_OOB);
+        if (LOAD_SLICE) db_load_slice(bw, a.w_next, wave, lane);
+#pragma unroll
+        for (int n = 0; n < ROUND; ++n) {
+            if (nb[n0 + n] >= 0) { // ELL order == CSR order of the row
+                facc.x += wv[n0 + n] * sv[n].x, facc.y += wv[n0 + n] * sv[n].y, facc.z += wv[n0 + n] * sv[n].z, facc.w += wv[n0 + n] * sv[n].w;
+            }
+        }
+    }
+    if (tail0 >= 0) { // (the 33-entry poles of 482.obj: entries 8, 9, ... of the row, still in CSR order; -1 pads the end)
+        for (int n0 = 0; n0 < DB_TAIL; n0 += 4) {
+            const int4 tc4 = *reinterpret_cast<const int4 *>(a.tail_col + (size_t)v * DB_TAIL + n0);
+            const float4 tw4 = *reinterpret_cast<const float4 *>(a.tail_val + (size_t)v * DB_TAIL + n0);
+            const int tc[4] = {tc4.x, tc4.y, tc4.z, tc4.w};
+            const float tw[4] = {tw4.x, tw4.y, tw4.z, tw4.w};
+            if (tc[0] < 0) break;
+            float4 tv[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) tv[t] = db_ld4(r_src, (on && tc[t] >= 0) ? rowbase + (unsigned)tc[t] * (DB_C * 4) + 4 * c0 : DB_OOB);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if (tc[t] >= 0) {
+                    facc.x += tw[t] * tv[t].x, facc.y += tw[t] * tv[t].y, facc.z += tw[t] * tv[t].z, facc.w += tw[t] * tv[t].w;
+                }
+            }
+        }
+    }
+    z[0] = facc;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) z[i].x += bias4[i].x, z[i].y += bias4[i].y, z[i].z += bias4[i].z, z[i].w += bias4[i].w;
+    // BatchNorm on the running statistics: the operations and order of geom_vertex_bn_fwd_f32 (no folded scale / shift)
+    auto finish = [&](float zz, float res) {
+        float y = (zz - mean) * invstd * gamma + beta;
+        if (a.relu) y = y > 0.f ? y : 0.f;
+        if (a.res) y = (res + y) * a.scale;
+        return on ? y : 0.f;
+    };
+    float4 xo[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        xo[i] = make_float4(finish(z[i].x, rv[i].x), finish(z[i].y, rv[i].y), finish(z[i].z, rv[i].z), finish(z[i].w, rv[i].w));
+    if (a.x_out) {
+        const __amdgpu_buffer_rsrc_t r_x = db_rsrc(a.x_out, op_bytes);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) db_st4(r_x, own_off == DB_OOB ? DB_OOB : own_off + 4 * DB_K * i, xo[i]);
+    }
+    if (!PRODUCT) {
+        // the coordinate head's raw support s_head[row] = X'[row] . W_head (as db_fwd_body: a row's 192 columns sit in the 16
+        // lanes of its group)
+        if (a.w_head) {
+            float h[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const float xv[4] = {xo[i].x, xo[i].y, xo[i].z, xo[i].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float *wr = a.w_head + (size_t)(c0 + DB_K * i + e) * 3;
+                    h[0] += xv[e] * wr[0], h[1] += xv[e] * wr[1], h[2] += xv[e] * wr[2];
+                }
+            }
+#pragma unroll
+            for (int m = 8; m > 0; m >>= 1) {
+                h[0] += __shfl_xor(h[0], m, GEOM_WAVE), h[1] += __shfl_xor(h[1], m, GEOM_WAVE), h[2] += __shfl_xor(h[2], m, GEOM_WAVE);
+            }
+            if (j == 0 && on) {
+                float *dst = a.s_head + (size_t)r * 3;
+                dst[0] = h[0], dst[1] = h[1], dst[2] = h[2];
+            }
+        }
+        return;
+    }
+    // the next layer's product on the tile (rows beyond the last are zero rows of the panel)
+    db_to_panel(lds, rl, c0, xo);
+    __syncthreads();
+    float *stage = lds + DB_PANEL;
+    db_product(bw, lds, stage, wave, x, g);
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t r_s = db_rsrc(a.s_out, op_bytes);
+#pragma unroll
+    for (int t = 0; t < 3; ++t) { // the tile leaves in memory order: 16 consecutive rows = 12 KB contiguous
+        const int idx = tid + DB_THREADS * t, rr = idx / 48, c4 = idx % 48;
+        const f32x4 val = *reinterpret_cast<const f32x4 *>(stage + rr * DB_LDC + 4 * c4);
+        const int row = rb * 16 + rr;
+        db_st4(r_s, row < rows ? (unsigned)row * (DB_C * 4) + 16u * c4 : DB_OOB, make_float4(val[0], val[1], val[2], val[3]));
+    }
+    // (the next row-block writes the panel, which nobody reads any more; the staging tile only after its first barrier)
+}
+
+template <bool PRODUCT>
+__global__ __launch_bounds__(DB_THREADS, 2) void di_fwd_kernel(geom_deform_infer a, int nrb, int nwg, int per_xcd)
+{
+    __shared__ __attribute__((aligned(16))) float lds[DB_PANEL + DB_CST];
+    const int w = blockIdx.x;
+    const int lw = (w & 7) * per_xcd + (w >> 3); // logical workgroup: contiguous runs per XCD (workgroup w runs on XCD w % 8)
+    if (lw >= nwg) return;
+    const int q = nrb / nwg, rem = nrb - q * nwg;
+    const int first = lw * q + (lw < rem ? lw : rem), count = q + (lw < rem ? 1 : 0);
+    DbSlice bw;
+    di_row_block<PRODUCT, PRODUCT>(a, first, lds, bw);
+    for (int i = 1; i < count; ++i) di_row_block<PRODUCT, false>(a, first + i, lds, bw);
+}
+
 inline bool db_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 int db_check_shape(int b, int nv, int c, int k, int ell_w)
@@ -836,6 +1016,35 @@ extern "C" int geom_deform_chain_bwd_f32(int count, const geom_deform_bwd *layer
     if (!geom_deform_chain_fits(layers[0].nv)) return GEOM_EUNSUPPORTED;
     c.count = count, c.done = done, c.ds_first = ds_first;
     hipLaunchKernelGGL(db_bwd_chain_kernel, dim3(8 * c.layer[0].vpx), dim3(DB_THREADS), 0, static_cast<hipStream_t>(stream), c);
+    return geom::launch_status();
+}
+
+// One eval-mode hidden layer over b >= 1 meshes (see di_row_block).  Every invalid argument is GEOM_EINVAL, decided on the host
+// before anything is enqueued.
+extern "C" int geom_deform_infer_fwd_f32(const geom_deform_infer *args, void *stream)
+{
+    if (!args) return GEOM_EINVAL;
+    const geom_deform_infer a = *args;
+    if (a.b < 1 || a.nv < 1 || a.c != DB_C || a.k != DB_K || a.ell_w != DB_W) return GEOM_EINVAL;
+    if ((int64_t)a.b * a.nv * DB_C >= (1LL << 29)) return GEOM_EINVAL; // 32-bit byte offsets
+    if (!a.s_in || !a.ell_col || !a.ell_val || !a.run_mean || !a.run_var) return GEOM_EINVAL;
+    if (a.w_next ? !a.s_out : (a.s_out != nullptr)) return GEOM_EINVAL;
+    if ((a.w_head != nullptr) != (a.s_head != nullptr) || (a.w_head && a.w_next)) return GEOM_EINVAL; // the head rides without a product
+    if (!a.w_next && !a.x_out && !a.s_head) return GEOM_EINVAL;                                      // nothing to write
+    if ((a.tail_col != nullptr) != (a.tail_val != nullptr)) return GEOM_EINVAL;
+    if (a.res && (a.res_ld < DB_C || (int64_t)a.b * a.nv * a.res_ld >= (1LL << 29))) return GEOM_EINVAL;
+    if (!db_aligned16(a.s_in) || !db_aligned16(a.ell_col) || !db_aligned16(a.ell_val) || !db_aligned16(a.tail_col) ||
+        !db_aligned16(a.tail_val) || !db_aligned16(a.bias) || !db_aligned16(a.x_out) || !db_aligned16(a.s_out) ||
+        !db_aligned16(a.w_next) || ((uintptr_t)a.res & 3))
+        return GEOM_EINVAL;
+    geom_deform_infer l = a;
+    if (!l.res) l.scale = 1.f;
+    const int nrb = (a.b * a.nv + 15) / 16;
+    const int nwg = nrb < DI_WGS ? nrb : DI_WGS, per_xcd = (nwg + 7) / 8;
+    const dim3 grid(8 * per_xcd), block(DB_THREADS);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (l.w_next) hipLaunchKernelGGL((di_fwd_kernel<true>), grid, block, 0, s, l, nrb, nwg, per_xcd);
+    else hipLaunchKernelGGL((di_fwd_kernel<false>), grid, block, 0, s, l, nrb, nwg, per_xcd);
     return geom::launch_status();
 }
 

@@ -20,6 +20,10 @@ are ONE (`chain`): a vertex's workgroup runs layer after layer and waits for its
 local BatchNorm statistics over the input's vertices, fp32 on a HIP device); everything else takes the separate operators
 (models.py).  The one-launch chain also needs a structurally symmetric adjacency (`csr.symmetric_structure`); a directed one
 takes the launches per layer.
+
+Eval mode under no_grad (`serves_inference`, `inference_chain`): BatchNorm on the running statistics is a per-vertex affine map,
+so the layer launch (geom_deform_infer_fwd_f32) tiles 16 consecutive rows of the flattened [B * V] rows instead of a vertex's
+batch rows -- any batch, no cross-workgroup waits, nothing written to the BatchNorm state.
 """
 import ctypes
 import os
@@ -374,6 +378,92 @@ class _HiddenChain(torch.autograd.Function):
         if g_head is not None:
             g_wh = g_head.view(ctx.head_shape)
         return (g_s1, g_lead, None, None, None, None, g_wh, *grads)
+
+
+def serves_inference(block, features, pooled, csr):
+    """Whether the eval-mode launches (geom_deform_infer_fwd_f32) serve this call of `block`: eval() under no_grad, a
+    192-wide block, fp32 on a HIP device, the bounded-degree table, and biases / BatchNorm parameters and running statistics
+    in fp32 over the input's vertices.  No limit on the batch but b * nv * 192 < 2^29 (the 32-bit byte offsets of the
+    launches' [b, nv, 192] operands; infer_layer_forward copies a wider residual to that pitch where it would pass them), no
+    symmetry requirement on the adjacency (no workgroup waits for another) and no BatchNorm synchronisation (eval mode has no
+    batch statistics)."""
+    if not enabled or block.training or torch.is_grad_enabled() or block.hidden != 192:
+        return False
+    if not (features.is_cuda and features.dtype == torch.float32 and pooled.is_cuda and pooled.dtype == torch.float32
+            and features.dim() == 3):
+        return False
+    if features.shape[0] < 1 or features.shape[0] * features.shape[1] * 192 >= 2 ** 29:
+        return False
+    if csr.ell_w != 8 or _tail_tables(csr) is False:
+        return False
+    for i in range(1, LAYERS + 1):
+        gc, bn = getattr(block, "gc%d" % i), getattr(block, "bn%d" % i)
+        if gc.bias is None or gc.weight1.shape[-1] != 192 or (i > 1 and gc.weight1.shape[-2] != 192):
+            return False
+        if bn.num_features != features.shape[1] or any(
+                t is None or t.dtype != torch.float32 for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
+            return False
+    return True
+
+
+def infer_layer_forward(s_in, bias, csr, bn_w, bn_b, run_mean, run_var, eps, relu, res, scale, x_out, w_next=None, s_out=None,
+                        w_head=None, s_head=None):
+    """One eval-mode launch (geom_deform_infer_fwd_f32): x_out (may be None) = relu?(BN_eval(aggregate(s_in) + bias))
+    (+ res, * scale); s_out = x_out . W_next (w_next PACKED: pack_weights()[0][l]) or, on the last layer, s_head = x_out . w_head."""
+    b, nv, c = s_in.shape
+    tail = _tail_tables(csr)
+    res, res_ld = _rows192(res, (b, nv, c))
+    if res is not None and b * nv * res_ld >= 2 ** 29:
+        # a residual read in place at a wide pitch (the leading columns of a 963 / 1155-wide block input) whose byte offsets
+        # would pass 32 bits: a contiguous copy (pitch 192, within the limit serves_inference checks)
+        res = res.contiguous()
+        res_ld = res.stride(1)
+    a = _lib.DeformInfer(b, nv, c, 64, csr.ell_w, _p(s_in), _p(bias), _p(csr.ell_col), _p(csr.ell_val), _p(tail[0]), _p(tail[1]),
+                         _p(bn_w), _p(bn_b), _p(run_mean), _p(run_var), float(eps), int(relu), _p(res), res_ld, float(scale),
+                         _p(x_out), _p(w_next), _p(s_out), _p(w_head), _p(s_head))
+    with torch.cuda.device(s_in.device):
+        _lib.call("geom_deform_infer_fwd_f32", ctypes.addressof(a))
+
+
+def inference_chain(block, s1, lead, csr, head=None):
+    """The thirteen hidden layers of `block` in eval mode applied to the first layer's raw support s1 [B,V,192]: one packing
+    launch and thirteen geom_deform_infer_fwd_f32 launches.  Returns (features, head_support): head_support = the raw support
+    [B,V,3] of `head` (the block's 192 -> 3 coordinate layer) when it is given, else None.  Writes nothing to the BatchNorms'
+    running statistics; only the activations a residual or the caller reads are stored."""
+    L = LAYERS
+    s1 = _lib.require(s1, "s1", torch.float32, 3, 192)
+    b, nv, c = s1.shape
+    dev = s1.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    gcs = [getattr(block, "gc%d" % i) for i in range(1, L + 1)]
+    bns = [getattr(block, "bn%d" % i) for i in range(1, L + 1)]
+    w2, _ = pack_weights([g.weight1 for g in gcs[1:]])
+    # outputs a residual reads: layer 2k's output is the residual of layer 2k + 2 (and layer 12's of layer 13, RESIDUALS), so
+    # two buffers in turn; the last layer writes the caller's tensor
+    keep = {j - 1 for j in RESIDUALS.values() if j != "lead"}
+    x_bufs = (torch.empty(b, nv, c, **f32), torch.empty(b, nv, c, **f32))
+    s_bufs = (torch.empty(b, nv, c, **f32), torch.empty(b, nv, c, **f32))
+    out = torch.empty(b, nv, c, **f32)
+    wh = s_head = None
+    if head is not None:
+        wh = head.weight1.reshape(c, 3)
+        wh = wh if wh.is_contiguous() else wh.contiguous()
+        s_head = torch.empty(b, nv, 3, **f32)
+    xs = {}
+    s_cur = s1
+    for i in range(1, L + 1):
+        src = RESIDUALS.get(i)
+        res = None if src is None else (lead if src == "lead" else xs[src - 1])
+        last = i == L
+        x_out = out if last else (x_bufs[(i // 2) & 1] if i in keep else None)
+        bn = bns[i - 1]
+        infer_layer_forward(s_cur, gcs[i - 1].bias, csr, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu, res,
+                            0.5, x_out, w_next=None if last else w2[i - 1], s_out=None if last else s_bufs[i & 1],
+                            w_head=wh if last else None, s_head=s_head if last else None)
+        if x_out is not None:
+            xs[i] = x_out
+        s_cur = s_bufs[i & 1]
+    return out, s_head
 
 
 def hidden_chain(block, s1, lead, csr, head=None):

@@ -315,6 +315,18 @@ class BatchMeshDeformationBlock(nn.Module):
                     feats, feats_out = _deform.hidden_chain(self, s1, lead, csr)
                     coords = self.gc15(feats, adj, _identity)
             return feats_out, coords
+        if csr is not None and _deform.serves_inference(self, features, pooled, csr):
+            # eval() under no_grad (validation, evaluation): one launch per hidden layer on the running statistics, 16
+            # consecutive (mesh, vertex) rows per tile at any batch size (geom_deform_infer_fwd_f32)
+            full, lead = _InputTap.apply(features, pooled, self.hidden, True)
+            s1 = _layers._dense(full, self.gc1.weight1)
+            if tuple(self.gc15.weight1.shape[-2:]) == (192, 3) and self.gc15.bias is not None:
+                feats, s15 = _deform.inference_chain(self, s1, lead, csr, head=self.gc15)
+                coords = _layers.zero_n_aggregate(s15, adj, self.gc15.bias, 3 // self.gc15.split, None)
+            else:
+                feats, _ = _deform.inference_chain(self, s1, lead, csr)
+                coords = self.gc15(feats, adj, _identity)
+            return feats, coords
         with batching:
             full, lead = _InputTap.apply(features, pooled, self.hidden)
             x = self._layer(1, full, adj)

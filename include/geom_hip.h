@@ -443,6 +443,32 @@ int geom_deform_chain_fwd_f32(int count, const geom_deform_fwd *layers, int *don
 int geom_deform_chain_bwd_f32(int count, const geom_deform_bwd *layers, int *done, float *ds_first, void *stream);
 int geom_deform_pack_weights_zero_f32(int count, const float *const *w, float *fwd, float *bwd, int *zero, int zero_words,
                                       void *stream);
+/* The eval-mode forward of a hidden layer (BatchNorm on the running statistics, nothing written to them) at ANY batch size
+ * b >= 1, b * nv * 192 < 2^29: the tile is 16 consecutive rows of the flattened [b * nv] rows (a row's gather stays inside
+ * its mesh), one launch per layer, no workgroup waits for another.
+ *     Z     = [A . s_in[:, :k] | s_in[:, k:]] + bias           (the bits of geom_zn_gcn_aggregate_ell_fwd_f32, act 0; not stored)
+ *     x_out = relu?((Z - run_mean_v) * (1 / sqrtf(run_var_v + eps)) * bn_w_v + bn_b_v) ; with res: (res + .) * scale
+ *             (the bits of geom_vertex_bn_fwd_f32 in eval mode); x_out may be NULL (not stored)
+ *     s_out = x_out . w_next  (w_next packed as geom_deform_pack_weights_f32's fwd[l]); NULL: the last hidden layer, which may
+ *             write the coordinate head's raw support s_head [b,nv,3] = x_out . w_head (w_head [192,3] row-major)
+ * c == 192, k == 64, ell_w == 8 (tail tables as for geom_deform_fwd); with a residual also b * nv * res_ld < 2^29 (callers
+ * copy a wider residual to pitch 192 first).  s_in, ell_col, ell_val, tail_col, tail_val, bias, x_out, s_out and w_next
+ * 16-byte aligned, res 4-byte aligned.  Anything else, a null required pointer or a size over a limit: GEOM_EINVAL. */
+typedef struct geom_deform_infer {
+    int b, nv, c, k, ell_w;
+    const float *s_in, *bias;                                   /* bias [192] or NULL */
+    const int *ell_col; const float *ell_val;
+    const int *tail_col; const float *tail_val;                 /* [nv, GEOM_DEFORM_TAIL] or NULL */
+    const float *bn_w, *bn_b;                                   /* [nv] or NULL (1 / 0) */
+    const float *run_mean, *run_var;                            /* [nv] */
+    float eps;
+    int relu;
+    const float *res; int res_ld; float scale;                  /* optional residual [b,nv,res_ld >= 192] */
+    float *x_out;
+    const float *w_next; float *s_out;
+    const float *w_head; float *s_head;
+} geom_deform_infer;
+int geom_deform_infer_fwd_f32(const geom_deform_infer *args, void *stream);
 /* EXPERIMENT (csrc/dense_split_bf16.hip; on no default route): c [m, 192] = a [m, k] . w [k, 192] on the BF16 matrix cores with
  * exact fp32 products -- every fp32 operand is the exact sum of three bf16 numbers, the products a_i b_j are exact in fp32,
  * terms = 6 keeps those with i + j <= 2 (the rest is below 2^-24 of |a b|), 9 keeps all; fp32 accumulation, the leading
