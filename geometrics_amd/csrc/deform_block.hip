@@ -914,47 +914,32 @@ int db_check_shape(int b, int nv, int c, int k, int ell_w)
     return 0;
 }
 
-} // namespace
-
-#ifdef DB_PROBE_STAMPS
-extern "C" int geom_db_probe_read(unsigned long long *dst, int n)
+// What geom_deform_fwd and geom_deform_infer ask alike of the operands they have in common; every failure is GEOM_EINVAL.
+template <typename Args>
+bool db_fwd_operands_ok(const Args &a)
 {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(db_stamps), sizeof(unsigned long long) * n, 0, hipMemcpyDeviceToHost);
+    if (!a.s_in || !a.ell_col || !a.ell_val) return false;
+    if (a.w_next && !a.s_out) return false;
+    if ((a.w_head != nullptr) != (a.s_head != nullptr) || (a.w_head && a.w_next)) return false; // the head rides in the launch without a product
+    if (a.tail_col && !a.tail_val) return false;
+    if (a.res && a.res_ld < DB_C) return false; // (any pitch: a column slice of the block's 1155-wide input is read in place)
+    return db_aligned16(a.s_in) && db_aligned16(a.ell_col) && db_aligned16(a.ell_val) && db_aligned16(a.x_out) && db_aligned16(a.s_out) &&
+           db_aligned16(a.bias) && !((uintptr_t)a.res & 3) && db_aligned16(a.w_next);
 }
-#endif
 
-extern "C" int geom_deform_layer_fwd_f32(const geom_deform_fwd *args, void *stream)
+// The operands of ONE forward layer of a non-empty shape that passed db_check_shape; fills in what the kernels read beside them.
+int db_check_fwd(geom_deform_fwd &a)
 {
-    if (!args) return GEOM_EINVAL;
-    geom_deform_fwd a = *args;
-    const int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w);
-    if (code) return code;
-    if (a.b == 0 || a.nv == 0) return 0;
-    if (!a.s_in || !a.ell_col || !a.ell_val || !a.x_out) return GEOM_EINVAL;
+    if (!db_fwd_operands_ok(a) || !a.x_out || !db_aligned16(a.z_out)) return GEOM_EINVAL;
     if (a.training ? (!a.save_mean || !a.save_invstd) : (!a.run_mean || !a.run_var)) return GEOM_EINVAL;
-    if (a.w_next && !a.s_out) return GEOM_EINVAL;
-    if ((a.w_head != nullptr) != (a.s_head != nullptr) || (a.w_head && a.w_next)) return GEOM_EINVAL; // the head rides in the launch without a product
-    if (a.tail_col && !a.tail_val) return GEOM_EINVAL;
-    if (a.res && a.res_ld < DB_C) return GEOM_EINVAL; // (any pitch: a column slice of the block's 1155-wide input is read in place)
-    if (!db_aligned16(a.s_in) || !db_aligned16(a.ell_col) || !db_aligned16(a.ell_val) || !db_aligned16(a.x_out) || !db_aligned16(a.z_out) ||
-        !db_aligned16(a.s_out) || !db_aligned16(a.bias) || ((uintptr_t)a.res & 3) || !db_aligned16(a.w_next))
-        return GEOM_EINVAL;
     if (!a.res) a.scale = 1.f;
     a.vpx = (a.nv + 7) / 8;
-    const dim3 grid(8 * a.vpx), block(DB_THREADS);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (a.w_next) hipLaunchKernelGGL((db_fwd_kernel<true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((db_fwd_kernel<false>), grid, block, 0, s, a);
-    return geom::launch_status();
+    return 0;
 }
 
-extern "C" int geom_deform_layer_bwd_f32(const geom_deform_bwd *args, void *stream)
+// ... and of one backward layer.  The first failing check decides the code.
+int db_check_bwd(geom_deform_bwd &a)
 {
-    if (!args) return GEOM_EINVAL;
-    geom_deform_bwd a = *args;
-    const int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w);
-    if (code) return code;
-    if (a.b == 0 || a.nv == 0) return 0;
     if (!a.z || !a.save_mean || !a.save_invstd || !a.dz) return GEOM_EINVAL;
     const bool product = a.dz_up != nullptr;
     if (product ? (!a.ell_col_t || !a.ell_val_t || !a.ds_up || !a.wt_up) : (!a.g && !a.ds_head)) return GEOM_EINVAL;
@@ -968,9 +953,44 @@ extern "C" int geom_deform_layer_bwd_f32(const geom_deform_bwd *args, void *stre
         return GEOM_EINVAL;
     if (!a.has_res) a.scale = 1.f;
     a.vpx = (a.nv + 7) / 8;
+    return 0;
+}
+
+} // namespace
+
+#ifdef DB_PROBE_STAMPS
+extern "C" int geom_db_probe_read(unsigned long long *dst, int n)
+{
+    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(db_stamps), sizeof(unsigned long long) * n, 0, hipMemcpyDeviceToHost);
+}
+#endif
+
+extern "C" int geom_deform_layer_fwd_f32(const geom_deform_fwd *args, void *stream)
+{
+    if (!args) return GEOM_EINVAL;
+    geom_deform_fwd a = *args;
+    int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w);
+    if (code) return code;
+    if (a.b == 0 || a.nv == 0) return 0;
+    if ((code = db_check_fwd(a))) return code;
     const dim3 grid(8 * a.vpx), block(DB_THREADS);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (product) hipLaunchKernelGGL((db_bwd_kernel<true>), grid, block, 0, s, a);
+    if (a.w_next) hipLaunchKernelGGL((db_fwd_kernel<true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((db_fwd_kernel<false>), grid, block, 0, s, a);
+    return geom::launch_status();
+}
+
+extern "C" int geom_deform_layer_bwd_f32(const geom_deform_bwd *args, void *stream)
+{
+    if (!args) return GEOM_EINVAL;
+    geom_deform_bwd a = *args;
+    int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w);
+    if (code) return code;
+    if (a.b == 0 || a.nv == 0) return 0;
+    if ((code = db_check_bwd(a))) return code;
+    const dim3 grid(8 * a.vpx), block(DB_THREADS);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (a.dz_up) hipLaunchKernelGGL((db_bwd_kernel<true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((db_bwd_kernel<false>), grid, block, 0, s, a);
     return geom::launch_status();
 }
@@ -987,29 +1007,18 @@ extern "C" int geom_deform_chain_bwd_f32(int count, const geom_deform_bwd *layer
     DbBwdChain c{};
     for (int l = 0; l < count; ++l) {
         geom_deform_bwd a = layers[l];
-        const int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w);
+        int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w);
         if (code) return code;
         if (a.b != layers[0].b || a.nv != layers[0].nv) return GEOM_EINVAL;
-        if (!a.z || !a.save_mean || !a.save_invstd || !a.dz) return GEOM_EINVAL;
         const bool product = a.dz_up != nullptr;
         if (product != (l > 0)) return GEOM_EINVAL;                                   // only the top layer reads its gradient from memory
         if (product && a.dz_up != layers[l - 1].dz) return GEOM_EINVAL;               // a chain
         if (product && l > 1 && (a.ell_col_t != layers[1].ell_col_t || a.ell_val_t != layers[1].ell_val_t ||
                                  a.tail_col_t != layers[1].tail_col_t || a.tail_val_t != layers[1].tail_val_t))
             return GEOM_EINVAL;
-        if (product ? (!a.ell_col_t || !a.ell_val_t || !a.ds_up || !a.wt_up) : (!a.g && !a.ds_head)) return GEOM_EINVAL;
-        if (a.ds_head && (product || !a.w_head || (a.dw_head && !a.x_top) || !db_aligned16(a.x_top))) return GEOM_EINVAL;
-        if (a.tail_col_t && !a.tail_val_t) return GEOM_EINVAL;
-        if ((a.g_ld && a.g_ld < DB_C) || (a.g2_ld && a.g2_ld < DB_C)) return GEOM_EINVAL;
-        if ((int64_t)a.b * a.nv * (a.g_ld > a.g2_ld ? a.g_ld : a.g2_ld) >= (1LL << 29)) return GEOM_EUNSUPPORTED;
-        if (!db_aligned16(a.dz_up) || !db_aligned16(a.ell_col_t) || !db_aligned16(a.ell_val_t) || !db_aligned16(a.ds_up) || ((uintptr_t)a.g & 3) ||
-            ((uintptr_t)a.g2 & 3) || !db_aligned16(a.z) || !db_aligned16(a.grad_res) || !db_aligned16(a.dz) || !db_aligned16(a.colsum) ||
-            !db_aligned16(a.wt_up))
-            return GEOM_EINVAL;
+        if ((code = db_check_bwd(a))) return code;                                    // (its 2^29 limit answers before the next check)
         for (int e = 0; e < l; ++e)
             if (layers[e].dz == a.dz) return GEOM_EINVAL;                              // (every step its own dZ: neighbours read it a step later)
-        if (!a.has_res) a.scale = 1.f;
-        a.vpx = (a.nv + 7) / 8;
         c.layer[l] = a;
     }
     if (layers[0].b == 0 || layers[0].nv == 0) return 0;
@@ -1027,16 +1036,11 @@ extern "C" int geom_deform_infer_fwd_f32(const geom_deform_infer *args, void *st
     const geom_deform_infer a = *args;
     if (a.b < 1 || a.nv < 1 || a.c != DB_C || a.k != DB_K || a.ell_w != DB_W) return GEOM_EINVAL;
     if ((int64_t)a.b * a.nv * DB_C >= (1LL << 29)) return GEOM_EINVAL; // 32-bit byte offsets
-    if (!a.s_in || !a.ell_col || !a.ell_val || !a.run_mean || !a.run_var) return GEOM_EINVAL;
-    if (a.w_next ? !a.s_out : (a.s_out != nullptr)) return GEOM_EINVAL;
-    if ((a.w_head != nullptr) != (a.s_head != nullptr) || (a.w_head && a.w_next)) return GEOM_EINVAL; // the head rides without a product
-    if (!a.w_next && !a.x_out && !a.s_head) return GEOM_EINVAL;                                      // nothing to write
-    if ((a.tail_col != nullptr) != (a.tail_val != nullptr)) return GEOM_EINVAL;
-    if (a.res && (a.res_ld < DB_C || (int64_t)a.b * a.nv * a.res_ld >= (1LL << 29))) return GEOM_EINVAL;
-    if (!db_aligned16(a.s_in) || !db_aligned16(a.ell_col) || !db_aligned16(a.ell_val) || !db_aligned16(a.tail_col) ||
-        !db_aligned16(a.tail_val) || !db_aligned16(a.bias) || !db_aligned16(a.x_out) || !db_aligned16(a.s_out) ||
-        !db_aligned16(a.w_next) || ((uintptr_t)a.res & 3))
-        return GEOM_EINVAL;
+    if (!db_fwd_operands_ok(a) || !a.run_mean || !a.run_var) return GEOM_EINVAL;
+    if (!a.w_next && (a.s_out || (!a.x_out && !a.s_head))) return GEOM_EINVAL;                       // no product: no s_out, and something to write
+    if (a.tail_val && !a.tail_col) return GEOM_EINVAL;
+    if (a.res && (int64_t)a.b * a.nv * a.res_ld >= (1LL << 29)) return GEOM_EINVAL;
+    if (!db_aligned16(a.tail_col) || !db_aligned16(a.tail_val)) return GEOM_EINVAL;
     geom_deform_infer l = a;
     if (!l.res) l.scale = 1.f;
     const int nrb = (a.b * a.nv + 15) / 16;
@@ -1108,24 +1112,15 @@ extern "C" int geom_deform_chain_fwd_f32(int count, const geom_deform_fwd *layer
     DbFwdChain c{};
     for (int l = 0; l < count; ++l) {
         geom_deform_fwd a = layers[l];
-        const int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w);
+        int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w);
         if (code) return code;
         if (a.b != layers[0].b || a.nv != layers[0].nv || a.ell_col != layers[0].ell_col || a.ell_val != layers[0].ell_val ||
             a.tail_col != layers[0].tail_col || a.tail_val != layers[0].tail_val)
             return GEOM_EINVAL;
-        if (!a.s_in || !a.ell_col || !a.ell_val || !a.x_out) return GEOM_EINVAL;
-        if (a.training ? (!a.save_mean || !a.save_invstd) : (!a.run_mean || !a.run_var)) return GEOM_EINVAL;
-        if (a.w_next ? !a.s_out : l + 1 < count) return GEOM_EINVAL;                 // only the last layer may lack a product
+        if (!a.w_next && l + 1 < count) return GEOM_EINVAL;                          // only the last layer may lack a product
         if (l > 0 && a.s_in != layers[l - 1].s_out) return GEOM_EINVAL;              // a chain
         if (l > 1 && a.s_out && a.s_out == layers[l - 1].s_out) return GEOM_EINVAL; // (ping-pong at least)
-        if ((a.w_head != nullptr) != (a.s_head != nullptr) || (a.w_head && a.w_next)) return GEOM_EINVAL;
-        if (a.tail_col && !a.tail_val) return GEOM_EINVAL;
-        if (a.res && a.res_ld < DB_C) return GEOM_EINVAL;
-        if (!db_aligned16(a.s_in) || !db_aligned16(a.ell_col) || !db_aligned16(a.ell_val) || !db_aligned16(a.x_out) || !db_aligned16(a.z_out) ||
-            !db_aligned16(a.s_out) || !db_aligned16(a.bias) || ((uintptr_t)a.res & 3) || !db_aligned16(a.w_next))
-            return GEOM_EINVAL;
-        if (!a.res) a.scale = 1.f;
-        a.vpx = (a.nv + 7) / 8;
+        if ((code = db_check_fwd(a))) return code;
         c.layer[l] = a;
     }
     if (layers[0].b == 0 || layers[0].nv == 0) return 0;

@@ -16,15 +16,17 @@ support gradients; bias gradients: per-vertex column sums out of the backward la
 Where every workgroup of a launch is resident at once (482 vertices on an MI355X: yes) the thirteen launches of a direction
 are ONE (`chain`): a vertex's workgroup runs layer after layer and waits for its neighbours' rows inside the launch.
 
-`serves()` says when the launches apply (192-wide block, k = 64, b <= 16, bounded-degree table of width 8, training mode,
-local BatchNorm statistics over the input's vertices, fp32 on a HIP device); everything else takes the separate operators
-(models.py).  The one-launch chain also needs a structurally symmetric adjacency (`csr.symmetric_structure`); a directed one
+`SCHEDULE` is the block's layer plan (which layer averages with which earlier output, where a product follows, which outputs are
+kept): every route walks it.  `serves()` says when the launches apply (`_servable`: 192-wide block, k = 64, bounded-degree table
+of width 8, fp32 on a HIP device, BatchNorm over the input's vertices; and b <= 16, training mode, local BatchNorm
+statistics); everything else takes the separate operators (models.py).  The one-launch chain also needs a structurally symmetric adjacency (`csr.symmetric_structure`); a directed one
 takes the launches per layer.
 
 Eval mode under no_grad (`serves_inference`, `inference_chain`): BatchNorm on the running statistics is a per-vertex affine map,
 so the layer launch (geom_deform_infer_fwd_f32) tiles 16 consecutive rows of the flattened [B * V] rows instead of a vertex's
 batch rows -- any batch, no cross-workgroup waits, nothing written to the BatchNorm state.
 """
+import collections
 import ctypes
 import os
 import threading
@@ -39,31 +41,55 @@ from . import layers as _layers
 RESIDUALS = {2: "lead", 4: 3, 6: 5, 8: 7, 10: 9, 12: 11, 13: 13}
 LAYERS = 13
 
+# The block's hidden layers, one record per layer, in order -- what every route walks (the chain's forward and backward,
+# inference_chain, the separate operators of models.py).  index: 1-based; residual: None, "lead" (the leading 192 columns of the
+# block input) or j = the OUTPUT of layer j; product: the next layer's product follows in the layer's launch; head: the coordinate
+# head may ride in it instead (the last layer); tap: a later layer reads the output as its residual, so it has to be kept.
+Layer = collections.namedtuple("Layer", "index residual product head tap")
+_SOURCE = {i: src if src == "lead" else src - 1 for i, src in RESIDUALS.items()}      # (X_j is the output of layer j - 1)
+SCHEDULE = tuple(Layer(i, _SOURCE.get(i), i < LAYERS, i == LAYERS, i in _SOURCE.values()) for i in range(1, LAYERS + 1))
+
 enabled = True      # tests / A-B timing: False keeps the separate operators
 relu = True         # tests only: False drops the ReLU of every hidden layer (a smooth chain: every launch of the backward can then
 #                     be held to a tight float64 bound -- under ReLU a pre-activation within rounding of zero may fall on either
 #                     side in any two fp32 evaluations and switch a whole unit's term)
 
 
-def serves(block, features, pooled, csr):
-    """Whether the fused launches serve this call of `block` (a models.BatchMeshDeformationBlock)."""
-    if not enabled or block.hidden != 192 or not block.training or not torch.is_grad_enabled():
+def hidden_layers(block):
+    """(gc1..gc13, bn1..bn13) of a models.BatchMeshDeformationBlock."""
+    return ([getattr(block, "gc%d" % i) for i in range(1, LAYERS + 1)], [getattr(block, "bn%d" % i) for i in range(1, LAYERS + 1)])
+
+
+def _servable(block, features, pooled, csr):
+    """What the training and the eval launches ask alike of a call of `block`, the cheap questions first: the package switch, a
+    192-wide block, fp32 [B,V,*] inputs on a HIP device with b * nv * 192 < 2^29 (32-bit byte offsets), the bounded-degree table
+    of width 8 (+ tail tables), and per layer a bias, the widths and fp32 BatchNorm tensors over the input's vertices (the
+    launches index them by the input's vertex)."""
+    if not enabled or block.hidden != 192:
         return False
-    if not (features.is_cuda and features.dtype == torch.float32 and pooled.dtype == torch.float32 and features.dim() == 3):
+    if not (features.is_cuda and features.dtype == torch.float32 and pooled.is_cuda and pooled.dtype == torch.float32
+            and features.dim() == 3):
         return False
-    if features.shape[0] > 16 or features.shape[0] * features.shape[1] * 192 >= 2 ** 29:
+    if features.shape[0] * features.shape[1] * 192 >= 2 ** 29:
         return False
     if csr.ell_w != 8 or _tail_tables(csr) is False:
         return False
-    for i in range(1, LAYERS + 1):
-        gc, bn = getattr(block, "gc%d" % i), getattr(block, "bn%d" % i)
-        if gc.bias is None or gc.weight1.shape[-1] != 192 or (i > 1 and gc.weight1.shape[-2] != 192) or bn._synchronised():
+    for i, (gc, bn) in enumerate(zip(*hidden_layers(block))):
+        if gc.bias is None or gc.weight1.shape[-1] != 192 or (i > 0 and gc.weight1.shape[-2] != 192):
             return False
-        # (the launches index the BatchNorm's per-vertex tensors by the input's vertex; each layer takes its own momentum / eps)
-        if bn.num_features != features.shape[1] or bn.momentum is None or any(
+        if bn.num_features != features.shape[1] or any(
                 t is None or t.dtype != torch.float32 for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
             return False
     return True
+
+
+def serves(block, features, pooled, csr):
+    """Whether the fused training launches serve this call of `block` (a models.BatchMeshDeformationBlock): _servable, in
+    training mode with gradients, at most 16 meshes, local BatchNorm statistics with a momentum (each layer takes its own)."""
+    if not block.training or not torch.is_grad_enabled() or (features.dim() == 3 and features.shape[0] > 16):
+        return False
+    return _servable(block, features, pooled, csr) and not any(
+        bn._synchronised() or bn.momentum is None for bn in hidden_layers(block)[1])
 
 
 def _p(t):
@@ -182,9 +208,10 @@ def chain_forward(layers, done, device):
         _lib.call("geom_deform_chain_fwd_f32", len(layers), ctypes.addressof(structs), done.data_ptr())
 
 
-def _rows192(t, shape):
-    """(tensor, row pitch in floats) of a [B,V,192] gradient as the backward launch reads it: in place when it is row-major
-    with contiguous rows at any pitch (a column slice of a wider buffer), a contiguous copy otherwise."""
+def rows_operand(t, shape):
+    """(tensor, row pitch in floats) of a [B,V,C] operand (a residual, a gradient) as the kernels read it: in place when it is
+    fp32 on the device, row-major with contiguous rows at any pitch (a column slice of a wider buffer), a contiguous copy
+    otherwise.  None -> (None, 0)."""
     if t is None:
         return None, 0
     b, nv, c = shape
@@ -195,14 +222,19 @@ def _rows192(t, shape):
     return t, t.stride(1)
 
 
+def head_weight(head):
+    """The coordinate head's weight ([1,192,3] / [192,3]: models.py:219 gc15) as the launches read it: [192, 3] contiguous."""
+    return head.reshape(192, 3).contiguous()
+
+
 def _backward_args(shape, csr, z, bn_w, bn_b, save_mean, save_invstd, relu, has_res, scale, dz, grad_bn_w, grad_bn_b,
                    dz_up=None, ds_up=None, wt_up=None, g=None, g2=None, grad_res=None, colsum=None, ds_head=None, w_head=None,
                    x_top=None, dw_head=None):
     """(struct, tensors it points into that were made here: the caller keeps them alive until the launch is issued)"""
     b, nv, c = shape
     tail = _tail_tables(csr)
-    g, g_ld = _rows192(g, shape)
-    g2, g2_ld = _rows192(g2, shape)
+    g, g_ld = rows_operand(g, shape)
+    g2, g2_ld = rows_operand(g2, shape)
     a = _lib.DeformBwd(b, nv, c, 64, csr.ell_w, _p(dz_up), _p(csr.ell_col_t), _p(csr.ell_val_t), _p(tail[2]), _p(tail[3]),
                        _p(ds_up), _p(wt_up), _p(g), _p(g2), g_ld, g2_ld, _p(z), _p(bn_w), _p(bn_b), _p(save_mean),
                        _p(save_invstd), int(relu), int(has_res), float(scale), _p(grad_res), _p(dz), _p(grad_bn_w),
@@ -243,7 +275,7 @@ class _HiddenChain(torch.autograd.Function):
         biases, weights = params[:L], params[L:2 * L - 1]
         bn_w, bn_b = params[2 * L - 1:3 * L - 1], params[3 * L - 1:4 * L - 1]
         s1 = _lib.require(s1, "s1", torch.float32, 3, 192)
-        lead, _ = _rows192(lead, tuple(s1.shape))       # in place when it is the leading columns of the block's wide input
+        lead, _ = rows_operand(lead, tuple(s1.shape))       # in place when it is the leading columns of the block's wide input
         b, nv, c = s1.shape
         dev = s1.device
         f32 = dict(dtype=torch.float32, device=dev)
@@ -259,15 +291,11 @@ class _HiddenChain(torch.autograd.Function):
         counters = torch.empty(2, nv * CTR_STRIDE, dtype=torch.int32, device=dev) if as_chain else None
         w2, wts = pack_weights(weights, counters)     # w2[i - 1] / wts[i - 1] = W_{i+1} / its transpose, in register-slice order
         calls = []
-        for i in range(1, L + 1):
-            src = RESIDUALS.get(i)
-            res = None if src is None else (lead if src == "lead" else xs[src - 2])
-            nxt = i < L
-            head = w_head is not None and not nxt
-            if head:
-                wh = w_head.reshape(c, 3)
-                wh = wh if wh.is_contiguous() else wh.contiguous()
-                s_head = torch.empty(b, nv, 3, **f32)
+        wh = s_head = None
+        if w_head is not None:
+            wh, s_head = head_weight(w_head), torch.empty(b, nv, 3, **f32)
+        for i, src, nxt, head, _ in SCHEDULE:
+            res = None if src is None else (lead if src == "lead" else xs[src - 1])
             call = ((s_cur, biases[i - 1], csr, bn_w[i - 1], bn_b[i - 1], stats[i - 1][0], stats[i - 1][1], True, momentum[i - 1],
                      eps[i - 1], relu, res, 0.5, zs[i - 1], xs[i - 1], means[i - 1], invstds[i - 1]),
                     dict(w_next=w2[i - 1] if nxt else None, s_out=s_buf[i & 1] if nxt else None,
@@ -315,7 +343,7 @@ class _HiddenChain(torch.autograd.Function):
         dss = torch.empty(L - 1, b, nv, c, **f32)     # dss[i - 2] = dS_i = gradient of layer i's raw support, i = 2..L
         g_bnw, g_bnb = torch.empty(L, nv, **f32), torch.empty(L, nv, **f32)
         colsum = torch.empty(L, nv, c, **f32)
-        pending = {}                                   # j -> gradient that reaches X_j through a residual average
+        pending = {}                                   # j -> gradient that reaches layer j's output through a residual average
         g_lead = None
         # (the forward ran as one launch: so does the backward, if this stream still owns the device's chain launches)
         counters = ctx.counters
@@ -323,17 +351,16 @@ class _HiddenChain(torch.autograd.Function):
         calls = [] if ctx.counters is not None and chain_fits(nv, dev) else None
         if calls is not None:
             ctx.counters = None
-        for i in range(L, 0, -1):
-            src = RESIDUALS.get(i)
+        for i, src, _, top, _ in reversed(SCHEDULE):
             grad_res = torch.empty(b, nv, c, **f32) if src is not None else None
             common = dict(relu=ctx.relu, has_res=src is not None, scale=0.5, dz=dzs[i - 1], grad_bn_w=g_bnw[i - 1], grad_bn_b=g_bnb[i - 1],
                           grad_res=grad_res, colsum=colsum[i - 1])
             where = ((b, nv, c), csr, zs[i - 1], bn_w[i - 1], bn_b[i - 1], means[i - 1], invstds[i - 1])
-            if i == L:
+            if top:
                 what = dict(g=g_top, g2=g_top2, ds_head=ds_head, w_head=w_head if ds_head is not None else None,
                             x_top=xs[L - 1] if dw_head is not None else None, dw_head=dw_head, **common)
             else:
-                what = dict(dz_up=dzs[i], ds_up=dss[i - 1], wt_up=wts[i - 1], g2=pending.pop(i + 1, None), **common)
+                what = dict(dz_up=dzs[i], ds_up=dss[i - 1], wt_up=wts[i - 1], g2=pending.pop(i, None), **common)
             if calls is None:
                 layer_backward(*where, **what)
             else:
@@ -387,23 +414,9 @@ def serves_inference(block, features, pooled, csr):
     launches' [b, nv, 192] operands; infer_layer_forward copies a wider residual to that pitch where it would pass them), no
     symmetry requirement on the adjacency (no workgroup waits for another) and no BatchNorm synchronisation (eval mode has no
     batch statistics)."""
-    if not enabled or block.training or torch.is_grad_enabled() or block.hidden != 192:
+    if block.training or torch.is_grad_enabled() or (features.dim() == 3 and features.shape[0] < 1):
         return False
-    if not (features.is_cuda and features.dtype == torch.float32 and pooled.is_cuda and pooled.dtype == torch.float32
-            and features.dim() == 3):
-        return False
-    if features.shape[0] < 1 or features.shape[0] * features.shape[1] * 192 >= 2 ** 29:
-        return False
-    if csr.ell_w != 8 or _tail_tables(csr) is False:
-        return False
-    for i in range(1, LAYERS + 1):
-        gc, bn = getattr(block, "gc%d" % i), getattr(block, "bn%d" % i)
-        if gc.bias is None or gc.weight1.shape[-1] != 192 or (i > 1 and gc.weight1.shape[-2] != 192):
-            return False
-        if bn.num_features != features.shape[1] or any(
-                t is None or t.dtype != torch.float32 for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
-            return False
-    return True
+    return _servable(block, features, pooled, csr)
 
 
 def infer_layer_forward(s_in, bias, csr, bn_w, bn_b, run_mean, run_var, eps, relu, res, scale, x_out, w_next=None, s_out=None,
@@ -412,7 +425,7 @@ def infer_layer_forward(s_in, bias, csr, bn_w, bn_b, run_mean, run_var, eps, rel
     (+ res, * scale); s_out = x_out . W_next (w_next PACKED: pack_weights()[0][l]) or, on the last layer, s_head = x_out . w_head."""
     b, nv, c = s_in.shape
     tail = _tail_tables(csr)
-    res, res_ld = _rows192(res, (b, nv, c))
+    res, res_ld = rows_operand(res, (b, nv, c))
     if res is not None and b * nv * res_ld >= 2 ** 29:
         # a residual read in place at a wide pitch (the leading columns of a 963 / 1155-wide block input) whose byte offsets
         # would pass 32 bits: a contiguous copy (pitch 192, within the limit serves_inference checks)
@@ -427,35 +440,28 @@ def infer_layer_forward(s_in, bias, csr, bn_w, bn_b, run_mean, run_var, eps, rel
 
 def inference_chain(block, s1, lead, csr, head=None):
     """The thirteen hidden layers of `block` in eval mode applied to the first layer's raw support s1 [B,V,192]: one packing
-    launch and thirteen geom_deform_infer_fwd_f32 launches.  Returns (features, head_support): head_support = the raw support
-    [B,V,3] of `head` (the block's 192 -> 3 coordinate layer) when it is given, else None.  Writes nothing to the BatchNorms'
-    running statistics; only the activations a residual or the caller reads are stored."""
-    L = LAYERS
+    launch and thirteen geom_deform_infer_fwd_f32 launches.  Returns (features, features, head_support) as hidden_chain does:
+    head_support = the raw support [B,V,3] of `head` (the block's 192 -> 3 coordinate layer) when it is given, else None.
+    Writes nothing to the BatchNorms' running statistics; only the activations a residual or the caller reads are stored."""
     s1 = _lib.require(s1, "s1", torch.float32, 3, 192)
     b, nv, c = s1.shape
     dev = s1.device
     f32 = dict(dtype=torch.float32, device=dev)
-    gcs = [getattr(block, "gc%d" % i) for i in range(1, L + 1)]
-    bns = [getattr(block, "bn%d" % i) for i in range(1, L + 1)]
+    gcs, bns = hidden_layers(block)
     w2, _ = pack_weights([g.weight1 for g in gcs[1:]])
-    # outputs a residual reads: layer 2k's output is the residual of layer 2k + 2 (and layer 12's of layer 13, RESIDUALS), so
-    # two buffers in turn; the last layer writes the caller's tensor
-    keep = {j - 1 for j in RESIDUALS.values() if j != "lead"}
+    # outputs a residual reads (SCHEDULE's tap): layer 2k's output is the residual of layer 2k + 2 (and layer 12's of layer 13),
+    # so two buffers in turn; the last layer writes the caller's tensor
     x_bufs = (torch.empty(b, nv, c, **f32), torch.empty(b, nv, c, **f32))
     s_bufs = (torch.empty(b, nv, c, **f32), torch.empty(b, nv, c, **f32))
     out = torch.empty(b, nv, c, **f32)
     wh = s_head = None
     if head is not None:
-        wh = head.weight1.reshape(c, 3)
-        wh = wh if wh.is_contiguous() else wh.contiguous()
-        s_head = torch.empty(b, nv, 3, **f32)
+        wh, s_head = head_weight(head.weight1), torch.empty(b, nv, 3, **f32)
     xs = {}
     s_cur = s1
-    for i in range(1, L + 1):
-        src = RESIDUALS.get(i)
-        res = None if src is None else (lead if src == "lead" else xs[src - 1])
-        last = i == L
-        x_out = out if last else (x_bufs[(i // 2) & 1] if i in keep else None)
+    for i, src, _, last, keep in SCHEDULE:
+        res = None if src is None else (lead if src == "lead" else xs[src])
+        x_out = out if last else (x_bufs[(i // 2) & 1] if keep else None)
         bn = bns[i - 1]
         infer_layer_forward(s_cur, gcs[i - 1].bias, csr, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu, res,
                             0.5, x_out, w_next=None if last else w2[i - 1], s_out=None if last else s_bufs[i & 1],
@@ -463,21 +469,20 @@ def inference_chain(block, s1, lead, csr, head=None):
         if x_out is not None:
             xs[i] = x_out
         s_cur = s_bufs[i & 1]
-    return out, s_head
+    return out, out, s_head
 
 
 def hidden_chain(block, s1, lead, csr, head=None):
-    """The thirteen hidden layers of `block` applied to the first layer's raw support; returns (features, features) -- see
-    _HiddenChain -- or, with head = the block's coordinate layer (192 -> 3), (features, raw support of the head)."""
-    L = LAYERS
-    gcs = [getattr(block, "gc%d" % i) for i in range(1, L + 1)]
-    bns = [getattr(block, "bn%d" % i) for i in range(1, L + 1)]
+    """The thirteen hidden layers of `block` applied to the first layer's raw support; returns (features for the coordinate
+    layer, features for the caller, None) -- two handles, see _HiddenChain -- or, with head = the block's coordinate layer
+    (192 -> 3 with a bias: the caller's decision), (features, the same, raw support of the head)."""
+    gcs, bns = hidden_layers(block)
     for bn in bns:
         bn._pending_batches += 1
     stats = [(bn.running_mean, bn.running_var) for bn in bns]
     params = [g.bias for g in gcs] + [g.weight1 for g in gcs[1:]] + [bn.weight for bn in bns] + [bn.bias for bn in bns]
-    w_head = None
-    if head is not None and tuple(head.weight1.shape[-2:]) == (192, 3):
-        w_head = head.weight1
     momentum, eps = tuple(float(bn.momentum) for bn in bns), tuple(float(bn.eps) for bn in bns)
-    return _HiddenChain.apply(s1, lead, csr, stats, momentum, eps, w_head, *params)
+    if head is None:
+        return _HiddenChain.apply(s1, lead, csr, stats, momentum, eps, None, *params) + (None,)
+    feats, s_head = _HiddenChain.apply(s1, lead, csr, stats, momentum, eps, head.weight1, *params)
+    return feats, feats, s_head

@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
+from . import deform as _deform
 from . import layers as _layers
 from .layers import Batch_Image_ZERON_GCNGCN, GCNMax, ZERON_GCN, _alias
 
@@ -36,14 +37,14 @@ class _VertexBN(torch.autograd.Function):
         xc = _lib.require(x, "x", torch.float32, 3)
         b, nv, c = xc.shape
         dev = xc.device
-        res, res_ld = _residual_operand(residual, xc)   # a column slice of a wider row-major tensor is read in place
+        res, res_ld = _deform.rows_operand(residual, xc.shape)   # a column slice of a wider row-major tensor is read in place
         out = _layers._new_like(xc, "normalised", _layers.current_slabs())   # a slot of the pass's stacked buffers when batching is on
         mean = torch.empty(nv, dtype=torch.float32, device=dev)
         invstd = torch.empty(nv, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _lib.call("geom_vertex_bn_fwd_f32", b, nv, c, xc.data_ptr(), _lib.ptr(weight), _lib.ptr(bias),
                       _lib.ptr(running_mean), _lib.ptr(running_var), int(training), float(momentum), float(eps),
-                      int(relu), _lib.ptr(res), res_ld, float(scale), out.data_ptr(), mean.data_ptr(),
+                      int(relu), _lib.ptr(res), res_ld or c, float(scale), out.data_ptr(), mean.data_ptr(),
                       invstd.data_ptr())
         if training:
             ctx.save_for_backward(xc, weight, bias, mean, invstd)
@@ -72,20 +73,6 @@ class _VertexBN(torch.autograd.Function):
                       mean.data_ptr(), invstd.data_ptr(), int(ctx.relu), int(ctx.has_res), float(ctx.scale),
                       grad_x.data_ptr(), _lib.ptr(grad_res), _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(g2))
         return grad_x, gw, gb, None, None, grad_res, None, None, None, None, None, None
-
-
-def _residual_operand(residual, like):
-    """The residual as the kernels read it: in place when it is a [B,V,C] fp32 tensor or a column slice of a wider
-    row-major one (row stride = its leading dimension), a contiguous copy otherwise.  Returns (tensor, row stride)."""
-    if residual is None:
-        return None, like.shape[2]
-    res = residual
-    nv, c = like.shape[1], like.shape[2]
-    ok = (res.dim() == 3 and res.shape == like.shape and res.stride(2) == 1 and res.stride(1) >= c
-          and res.stride(0) == nv * res.stride(1) and res.dtype == torch.float32 and res.is_cuda)
-    if not ok:
-        res = res.contiguous()
-    return res, res.stride(1)
 
 
 class _InputTap(torch.autograd.Function):
@@ -298,45 +285,39 @@ class BatchMeshDeformationBlock(nn.Module):
 
     def forward(self, features, pooled, adj):
         import contextlib
-        from . import deform as _deform
         batching = _layers.weight_gradient_batching(depth=14) if self.batch_weight_gradients else contextlib.nullcontext()
         csr = _layers.adjacency_csr(adj) if (torch.is_tensor(adj) and adj.dim() == 2 and features.is_cuda) else None
+        chain = None
         if csr is not None and _deform.serves(self, features, pooled, csr):
             # ONE launch per hidden layer and direction (csrc/deform_block.hip): aggregation + BatchNorm1d(verts) + ReLU +
             # residual average + the next layer's product; the first layer's product and the coordinate head stay the layers'
+            chain = _deform.hidden_chain
+        elif csr is not None and _deform.serves_inference(self, features, pooled, csr):
+            # eval() under no_grad (validation, evaluation): one launch per hidden layer on the running statistics, 16
+            # consecutive (mesh, vertex) rows per tile at any batch size (geom_deform_infer_fwd_f32); no gradients to batch
+            chain, batching = _deform.inference_chain, contextlib.nullcontext()
+        if chain is not None:
+            # a 192 -> 3 head with a bias: its product (and its two gradients) ride in the last / first layer launch
+            head = self.gc15 if tuple(self.gc15.weight1.shape[-2:]) == (192, 3) and self.gc15.bias is not None else None
             with batching:
                 full, lead = _InputTap.apply(features, pooled, self.hidden, True)
                 s1 = _layers._dense(full, self.gc1.weight1)
-                if tuple(self.gc15.weight1.shape[-2:]) == (192, 3) and self.gc15.bias is not None:
-                    # the coordinate head's product (and its two gradients) ride in the last / first layer launch
-                    feats_out, s15 = _deform.hidden_chain(self, s1, lead, csr, head=self.gc15)
-                    coords = _layers.zero_n_aggregate(s15, adj, self.gc15.bias, 3 // self.gc15.split, None)
+                feats, feats_out, s15 = chain(self, s1, lead, csr, head=head)
+                if head is not None:
+                    coords = _layers.zero_n_aggregate(s15, adj, head.bias, 3 // head.split, None)
                 else:
-                    feats, feats_out = _deform.hidden_chain(self, s1, lead, csr)
                     coords = self.gc15(feats, adj, _identity)
             return feats_out, coords
-        if csr is not None and _deform.serves_inference(self, features, pooled, csr):
-            # eval() under no_grad (validation, evaluation): one launch per hidden layer on the running statistics, 16
-            # consecutive (mesh, vertex) rows per tile at any batch size (geom_deform_infer_fwd_f32)
-            full, lead = _InputTap.apply(features, pooled, self.hidden, True)
-            s1 = _layers._dense(full, self.gc1.weight1)
-            if tuple(self.gc15.weight1.shape[-2:]) == (192, 3) and self.gc15.bias is not None:
-                feats, s15 = _deform.inference_chain(self, s1, lead, csr, head=self.gc15)
-                coords = _layers.zero_n_aggregate(s15, adj, self.gc15.bias, 3 // self.gc15.split, None)
-            else:
-                feats, _ = _deform.inference_chain(self, s1, lead, csr)
-                coords = self.gc15(feats, adj, _identity)
-            return feats, coords
         with batching:
             full, lead = _InputTap.apply(features, pooled, self.hidden)
-            x = self._layer(1, full, adj)
-            feats, feats_r = self._layer(2, x, adj, residual=lead, tap=True)
-            for i in (3, 5, 7, 9, 11):
-                x = self._layer(i, feats, adj)
-                feats, feats_r = self._layer(i + 1, x, adj, residual=feats_r, tap=True)
-            feats, feats_r = self._layer(13, feats, adj, residual=feats_r, tap=True)
-            coords = self.gc15(feats, adj, _identity)
-        return feats_r, coords
+            x, taps = full, {"lead": lead}
+            for i, src, _, last, tap in _deform.SCHEDULE:
+                # (the last layer's output has two readers as well: the coordinate layer and the caller)
+                x = self._layer(i, x, adj, residual=None if src is None else taps.pop(src), tap=tap or last)
+                if tap or last:
+                    x, taps[i] = x
+            coords = self.gc15(x, adj, _identity)
+        return taps[_deform.LAYERS], coords
 
 
 class MeshEncoder(nn.Module):

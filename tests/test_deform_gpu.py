@@ -234,6 +234,78 @@ def test_shapes_the_launches_do_not_serve_take_the_separate_operators(gpu):
     assert torch.isfinite(big.grad).all()
 
 
+# What a training forward + backward of the block issues on the separate operators (`deform.enabled = False`): the library entry
+# points that go through _lib.call, in order; every entry point whose status goes through _lib.check (those, and the launches the
+# layers issue themselves); and per VertexBatchNorm call (layer, residual given, tap).  Recorded ONCE, from the block as it was when
+# its layer pairs were written out by hand; the loop over deform.SCHEDULE has to reproduce all three exactly.
+SEPARATE_OPERATOR_CALLS = """
+geom_vertex_bn_fwd_f32 geom_vertex_bn_fwd_f32 geom_vertex_bn_fwd_f32 geom_vertex_bn_fwd_f32 geom_vertex_bn_fwd_f32
+geom_vertex_bn_fwd_f32 geom_vertex_bn_fwd_f32 geom_vertex_bn_fwd_f32 geom_vertex_bn_fwd_f32 geom_vertex_bn_fwd_f32
+geom_vertex_bn_fwd_f32 geom_vertex_bn_fwd_f32 geom_vertex_bn_fwd_f32 geom_gemm_f32 geom_gemm_f32 geom_vertex_bn_bwd_f32
+geom_vertex_bn_bwd_f32 geom_vertex_bn_bwd_f32 geom_vertex_bn_bwd_f32 geom_vertex_bn_bwd_f32 geom_vertex_bn_bwd_f32
+geom_vertex_bn_bwd_f32 geom_vertex_bn_bwd_f32 geom_vertex_bn_bwd_f32 geom_vertex_bn_bwd_f32 geom_vertex_bn_bwd_f32
+geom_vertex_bn_bwd_f32 geom_vertex_bn_bwd_f32
+""".split()
+SEPARATE_OPERATOR_CHECKS = """
+geom_zn_gcn_aggregate_ell_fwd_f32 geom_vertex_bn_fwd_f32 geom_zn_gcn_aggregate_ell_fwd_f32 geom_vertex_bn_fwd_f32
+geom_zn_gcn_aggregate_ell_fwd_f32 geom_vertex_bn_fwd_f32 geom_zn_gcn_aggregate_ell_fwd_f32 geom_vertex_bn_fwd_f32
+geom_zn_gcn_aggregate_ell_fwd_f32 geom_vertex_bn_fwd_f32 geom_zn_gcn_aggregate_ell_fwd_f32 geom_vertex_bn_fwd_f32
+geom_zn_gcn_aggregate_ell_fwd_f32 geom_vertex_bn_fwd_f32 geom_zn_gcn_aggregate_ell_fwd_f32 geom_vertex_bn_fwd_f32
+geom_zn_gcn_aggregate_ell_fwd_f32 geom_vertex_bn_fwd_f32 geom_zn_gcn_aggregate_ell_fwd_f32 geom_vertex_bn_fwd_f32
+geom_zn_gcn_aggregate_ell_fwd_f32 geom_vertex_bn_fwd_f32 geom_zn_gcn_aggregate_ell_fwd_f32 geom_vertex_bn_fwd_f32
+geom_zn_gcn_aggregate_ell_fwd_f32 geom_vertex_bn_fwd_f32 geom_gemm_f32 geom_zn_gcn_aggregate_ell_fwd_f32
+geom_zn_gcn_aggregate_ell_bwd_f32 geom_gemm_f32 geom_vertex_bn_bwd_f32 geom_zn_gcn_aggregate_ell_bwd_f32
+geom_vertex_bn_bwd_f32 geom_zn_gcn_aggregate_ell_bwd_f32 geom_vertex_bn_bwd_f32 geom_zn_gcn_aggregate_ell_bwd_f32
+geom_vertex_bn_bwd_f32 geom_zn_gcn_aggregate_ell_bwd_f32 geom_vertex_bn_bwd_f32 geom_zn_gcn_aggregate_ell_bwd_f32
+geom_vertex_bn_bwd_f32 geom_zn_gcn_aggregate_ell_bwd_f32 geom_vertex_bn_bwd_f32 geom_zn_gcn_aggregate_ell_bwd_f32
+geom_vertex_bn_bwd_f32 geom_zn_gcn_aggregate_ell_bwd_f32 geom_vertex_bn_bwd_f32 geom_zn_gcn_aggregate_ell_bwd_f32
+geom_vertex_bn_bwd_f32 geom_zn_gcn_aggregate_ell_bwd_f32 geom_vertex_bn_bwd_f32 geom_zn_gcn_aggregate_ell_bwd_f32
+geom_vertex_bn_bwd_f32 geom_zn_gcn_aggregate_ell_bwd_f32 geom_vertex_bn_bwd_f32 geom_zn_gcn_aggregate_ell_bwd_f32
+""".split()
+SEPARATE_OPERATOR_BATCHNORMS = [(1, False, False), (2, True, True), (3, False, False), (4, True, True), (5, False, False),
+                                (6, True, True), (7, False, False), (8, True, True), (9, False, False), (10, True, True),
+                                (11, False, False), (12, True, True), (13, True, True)]
+
+
+def test_the_separate_operators_issue_what_they_issued(gpu, monkeypatch):
+    from geometrics_amd import _lib
+    nv, adj, csr = _mesh("icosphere_162", gpu)
+    torch.manual_seed(11)
+    block = models.BatchMeshDeformationBlock(200, nv).to(gpu).train()
+    f = torch.randn(4, nv, 3, device=gpu, requires_grad=True)
+    p = torch.randn(4, nv, 197, device=gpu, requires_grad=True)
+    monkeypatch.setattr(deform, "enabled", False)
+
+    def step():
+        out_f, coords = block(f, p, adj)
+        (out_f.sum() + coords.sum()).backward()
+        torch.cuda.synchronize()
+    step()                                   # (whatever is set up on a first call is not part of the sequence)
+    calls, checks, norms = [], [], []
+    real_call, real_check, real_bn = _lib.call, _lib.check, models.VertexBatchNorm.forward
+    layer_of = {getattr(block, "bn%d" % i): i for i in range(1, 15)}
+
+    def call_spy(name, *args):
+        calls.append(name)
+        return real_call(name, *args)
+
+    def check_spy(code, what):
+        checks.append(what)
+        return real_check(code, what)
+
+    def bn_spy(self, x, relu=False, residual=None, scale=0.5, tap=False):
+        norms.append((layer_of[self], residual is not None, bool(tap)))
+        return real_bn(self, x, relu=relu, residual=residual, scale=scale, tap=tap)
+    monkeypatch.setattr(_lib, "call", call_spy)
+    monkeypatch.setattr(_lib, "check", check_spy)
+    monkeypatch.setattr(models.VertexBatchNorm, "forward", bn_spy)
+    step()
+    monkeypatch.undo()
+    assert norms == SEPARATE_OPERATOR_BATCHNORMS
+    assert checks == SEPARATE_OPERATOR_CHECKS
+    assert calls == SEPARATE_OPERATOR_CALLS
+
+
 def test_packed_weight_slices_hold_the_matrix_and_its_transpose(gpu):
     """geom_deform_pack_weights_f32: [wave][e / 4][lane][e % 4] with element e = (4 jp + c) * 3 + u of lane (x, g) =
     W[48 g + 4 jp + c][48 wave + 3 x + u] (and the same of W^T): a permutation of the matrix, checked index by index."""
