@@ -9,8 +9,6 @@ the tensor's identity + version) and replaces the reference's dense `adj @ suppo
 `input @ W` stays a library GEMM (rocBLAS/hipBLASLt through torch.matmul).
 """
 import math
-import os
-import threading
 import weakref
 
 import torch
@@ -21,11 +19,13 @@ from torch.nn.parameter import Parameter
 
 from . import _lib
 from . import backward_pass as _pass
-from . import dense as _dense_kernels
 from . import fused as _fused
+from . import products as _products
 # (re-exported: bench.py and dist.py use the public names, models, ops, deform and the tests the private ones)
 from .backward_pass import (_alias, _gradient_buffer, bind_gradient_targets, deferred_parameter_gradients,  # noqa: F401
                             late_input_gradients)
+# (the layers' dense products; the flags that steer them are set on geometrics_amd.products, not here)
+from .products import _dense, _new_like, current_slabs, weight_gradient_batching  # noqa: F401
 
 _ACT_NONE, _ACT_RELU, _ACT_ELU = 0, 1, 2
 
@@ -175,9 +175,6 @@ def aggregate_forward(s, bias_c, csr, k, act, out, want_mask=False):
             _lib.check(code, "geom_zn_gcn_aggregate_ell_fwd_f32")
     return mask
 
-
-use_matrix_core_products = True       # the layers' dense gradients on csrc/dense_gemm.hip where dense.plan says so
-use_any_shape_products = True         # every other width: csrc/dense_any.hip (False: the library's products)
 
 
 def aggregate_backward(g, csr, k, act, out, mask, want_bias, bias=None, arena=None):
@@ -349,302 +346,6 @@ def zero_n_aggregate(support, adj, bias, k, activation=None):
     return out
 
 
-# ---- weight gradients of a stack of equal layers as ONE batched product --------------------------------------------------
-# dW = X^T . G of a hidden layer (K = b*V rows against a 192 x 192 output) is the library's least efficient product: 22 us at
-# the reference's training shape for 0.57 GFLOP, and a deformation block issues twelve of them, one per layer.  The
-# gradients are independent of each other, so inside `weight_gradient_batching()` they are postponed to the end of the
-# backward pass (geometrics_amd.backward_pass: same mechanism and safeguards as the bias gradients) and issued as one
-# strided-batched product per run of equal layers: 242 -> 72 us for the twelve.  A strided-batched product wants its operands
-# at a regular pitch, so while the context is active the layers' activations and gradients are carved out of stacked buffers
-# (`_Slabs`): consecutive equal-shape allocations sit one pitch apart, forward ones ascending, backward ones descending
-# (the backward pass meets the layers in reverse), which makes X_l, G_l and dW_l all ascending in l.
-class _Slabs:
-    """Stacked buffers for the tensors of one forward/backward pass: take(kind, shape) returns the next [shape] slot of a
-    [slots, *shape] buffer of that kind and shape (a fresh buffer when the current one is used up: the run of equal
-    layers is then split there).  slots = the depth of the stack (untaken slots cost address space only)."""
-    def __init__(self, slots):
-        self.open = {}
-        self.slots = max(2, int(slots))
-
-    def take(self, kind, shape, device, descending=False):
-        shape = tuple(shape)
-        key = (kind, shape, device, descending)
-        slots = self.slots
-        cur = self.open.get(key)
-        if cur is None or cur[1] == slots:
-            cur = self.open[key] = [torch.empty((slots,) + shape, dtype=torch.float32, device=device), 0]
-        index = slots - 1 - cur[1] if descending else cur[1]
-        cur[1] += 1
-        return cur[0][index]
-
-
-_active = threading.local()    # .slabs = the arena of the forward pass running on this thread (weight_gradient_batching)
-
-
-def current_slabs():
-    return getattr(_active, "slabs", None)
-
-
-class weight_gradient_batching:
-    """Context manager for the FORWARD pass of a stack of layers: their weight gradients are computed at the end of the
-    backward pass, batched over runs of equal layers (see above).  Results differ from the per-layer products only by the
-    library kernel's summation order (1e-6 relative)."""
-
-    def __init__(self, depth=4):
-        """depth: how many equal layers follow each other at most (the slots of one stacked buffer)."""
-        self.depth = depth
-
-    def __enter__(self):
-        self.outer = current_slabs()
-        # nothing to batch without a backward pass: an inference forward keeps its plain, progressively freed allocations
-        _active.slabs = _Slabs(self.depth) if torch.is_grad_enabled() else None
-        return self
-
-    def __exit__(self, *exc):
-        _active.slabs = self.outer
-        return False
-
-
-def _new_like(t, kind, arena, descending=False):
-    """Allocation of an activation / gradient: a slot of the pass's stacked buffers when batching is on."""
-    if arena is None:
-        return torch.empty_like(t)
-    return arena.take(kind, t.shape, t.device, descending)
-
-
-def _regular_run(tensors):
-    """(first tensor, pitch in elements) when the tensors sit at one constant positive pitch inside one storage."""
-    first = tensors[0]
-    if len(tensors) == 1:
-        return first, 0
-    base = first.untyped_storage().data_ptr()
-    if any(t.untyped_storage().data_ptr() != base or t.stride() != first.stride() for t in tensors):
-        return None
-    step = tensors[1].storage_offset() - first.storage_offset()
-    if step <= 0 or any(tensors[i + 1].storage_offset() - tensors[i].storage_offset() != step for i in range(len(tensors) - 1)):
-        return None
-    return first, step
-
-
-def _launch_weight_products(jobs):
-    """A pass's postponed weight-gradient products in layer order: batched over runs of equal layers at a regular pitch."""
-    i = 0
-    while i < len(jobs):
-        first = jobs[i]
-        j = i + 1
-        while (j < len(jobs) and jobs[j].x.shape == first.x.shape and jobs[j].g.shape == first.g.shape
-               and jobs[j].stream == first.stream):
-            j += 1
-        group = jobs[i:j]
-        with torch.cuda.stream(first.stream), torch.no_grad():
-            runs = [_regular_run([getattr(job, name) for job in group]) for name in ("x", "g", "out")] if len(group) > 1 else None
-            if runs and all(runs):
-                xb, gb, ob = (torch.as_strided(run[0], (len(group),) + tuple(t.shape), (run[1],) + tuple(t.stride()))
-                              for run, t in zip(runs, (first.x, first.g, first.out)))
-                torch.bmm(xb.transpose(1, 2), gb, out=ob)
-            else:
-                for job in group:
-                    # (a layer of its own width -- the block's 192 -> 3 coordinate head: 7712 summed rows against a 192 x 3 output
-                    # is 75 us in the library, which runs it without a split; the any-shape kernel splits the sum)
-                    _weight_gradient_product(job.x, job.g, out=job.out)
-        i = j
-
-
-def _takes_any_shape_kernel(rows, cin, c):
-    """Shapes whose products run on csrc/dense_any.hip: whatever the 192-column kernels (dense.plan) do not take."""
-    return (use_any_shape_products and use_matrix_core_products and _dense_kernels.plan(rows, cin, c)["dw"] != "mfma"
-            and _dense_kernels.any_supported(rows, cin, c))
-
-
-# The library's products of this path are fast only with the recorded selections of geometrics_amd/tuning (TunableOp: validated
-# against the PyTorch / hipBLASLt build, so a library update REJECTS the file and the default heuristic runs the 963-wide
-# products at 85 us instead of 62).  When gemm_tuning.enable() was called and the file was rejected, the forward products and
-# the wide input gradient of the 192-column layers take this package's own matrix-core kernels instead (csrc/dense_gemm.hip:
-# within a few per cent of the tuned library, measured by tools/time_dense.py and bench.py --own-products): the headline does
-# not hang on a version-locked file.  None = that rule; True / False force it (tests, A/B).
-own_dense_products = None
-
-
-def _own_products_preferred():
-    if own_dense_products is not None:
-        return bool(own_dense_products)
-    env = os.environ.get("GEOM_OWN_PRODUCTS")
-    if env is not None:
-        return env not in ("", "0")
-    from . import gemm_tuning
-    return gemm_tuning.status == "library default (tuning file rejected)"      # (not: "tuned at start-up", gemm_tuning.tune_products)
-
-
-def _own_kernel_takes(x, w2):
-    return (use_matrix_core_products and x.is_cuda and x.dtype == torch.float32 and w2.dtype == torch.float32 and w2.dim() == 2
-            and w2.is_contiguous() and x.shape[-1] == w2.shape[0] and w2.shape[1] % 16 == 0
-            and _dense_kernels.supported(w2.shape[0], w2.shape[1], x.numel() // max(x.shape[-1], 1))
-            and x.numel() // max(x.shape[-1], 1) >= 512)
-
-
-def _library_or_own_forward(x, w2):
-    """x @ w2 by the library, or by geom_dense_fwd_f32 when the library runs untuned (see above)."""
-    if _own_products_preferred() and _own_kernel_takes(x, w2):
-        x2 = x.reshape(-1, x.shape[-1])
-        return _dense_kernels.forward(x2 if x2.is_contiguous() else x2.contiguous(), w2).view(x.shape[:-1] + (w2.shape[1],))
-    return torch.matmul(x, w2)
-
-
-def _library_or_own_input_gradient(g2, w2, out=None):
-    """g2 @ w2^T ([rows, c] x [cin, c]^T) by the library, or by geom_dense_bwd_input_f32 when the library runs untuned."""
-    if (_own_products_preferred() and use_matrix_core_products and g2.is_cuda and g2.dtype == torch.float32 and g2.dim() == 2
-            and g2.is_contiguous() and w2.is_contiguous() and w2.dim() == 2 and g2.shape[1] == w2.shape[1] and g2.shape[0] >= 512
-            and w2.shape[1] % 16 == 0 and _dense_kernels.supported(w2.shape[0], w2.shape[1], g2.shape[0])):
-        return _dense_kernels.backward_input(g2, w2, out=out)
-    return torch.matmul(g2, w2.t()) if out is None else torch.mm(g2, w2.t(), out=out)
-
-
-def _forward_product(x, w2):
-    """x [..., cin] @ w2 [cin, c]: ONE rule for which kernel computes it, whichever autograd node wraps it (the routes of a
-    layer must agree bit for bit in the forward: tests compare them)."""
-    rows = x.numel() // x.shape[-1] if x.shape[-1] else 0
-    if (x.is_cuda and x.dtype == torch.float32 and w2.dtype == torch.float32 and w2.dim() == 2 and w2.is_contiguous()
-            and x.shape[-1] == w2.shape[0] and _takes_any_shape_kernel(rows, x.shape[-1], w2.shape[-1])):
-        x2 = x.reshape(-1, x.shape[-1])
-        return _dense_kernels.gemm(x2 if x2.is_contiguous() else x2.contiguous(), w2).view(x.shape[:-1] + (w2.shape[1],))
-    return _library_or_own_forward(x, w2)
-
-
-def _weight_gradient_product(x2, g2, out=None):
-    """x2^T @ g2 ([rows, cin]^T x [rows, c]): the any-shape kernel's split product where _takes_any_shape_kernel says so (the
-    library runs a long sum against a small output without a split: 75 us for the 192 -> 3 head at 7712 rows), else the library."""
-    if (x2.is_cuda and x2.dtype == torch.float32 and g2.dtype == torch.float32 and x2.dim() == 2 and g2.dim() == 2
-            and x2.stride(1) == 1 and g2.stride(1) == 1 and (out is None or (out.dim() == 2 and out.stride(1) == 1))
-            and _takes_any_shape_kernel(x2.shape[0], x2.shape[1], g2.shape[1])):
-        return _dense_kernels.gemm(x2, g2, trans_a=True, out=out)
-    return torch.mm(x2.t(), g2) if out is None else torch.mm(x2.t(), g2, out=out)
-
-
-class _Dense(torch.autograd.Function):
-    """support = input @ W for [.., Cin] x [Cin, Cout] (W may carry the reference's leading 1: [1, Cin, Cout]) with the
-    weight gradient postponed to the end of the backward pass (used only inside weight_gradient_batching();
-    torch.matmul otherwise).  Takes the PARAMETER itself, so that its gradient goes straight to the leaf."""
-
-    @staticmethod
-    def forward(ctx, x, w, arena):
-        ctx.save_for_backward(x, w)
-        ctx.arena = arena
-        ctx.w_ref = _pass.parameter_ref(w, ctx, ctx.needs_input_grad[1])
-        return _forward_product(x, w.reshape(w.shape[-2:]))
-
-    @staticmethod
-    def backward(ctx, grad):
-        x, w = ctx.saved_tensors
-        g = grad.contiguous()
-        w2 = w.reshape(w.shape[-2:])
-        grad_x = torch.matmul(g, w2.t()) if ctx.needs_input_grad[0] else None
-        grad_w = None
-        if ctx.needs_input_grad[1]:
-            x2, g2 = x.reshape(-1, x.shape[-1]), g.reshape(-1, g.shape[-1])
-            param = ctx.w_ref()
-            if param is not None and x2.is_contiguous() and _pass.may_defer(param, opted_in=True):
-                grad_w = ctx.arena.take("dW", w.shape, w.device, descending=True)
-                _pass.postpone_weight_product(x2, g2, grad_w, ctx.w_ref, _launch_weight_products)
-            else:
-                grad_w = _weight_gradient_product(x2, g2).view(w.shape)
-        return grad_x, grad_w, None
-
-
-# ---- the layer's dense products on the fp32 matrix cores (csrc/dense_gemm.hip) -----------------------------------------
-
-
-class _DenseMM(torch.autograd.Function):
-    """support = input @ W with both gradients on the matrix-core kernels where `dense.plan` puts them: the input
-    gradient and the split partial sums of the weight gradient in ONE launch (two workgroups per CU) for the 192-wide
-    layers, the partial sums alone for the 963-wide one; the partials of all layers of a backward pass are added up by one
-    reduction launch at its end inside `deferred_parameter_gradients()` (geometrics_amd.backward_pass), at once
-    otherwise.  Same values either way: the reduction order is fixed by the shape."""
-
-    @staticmethod
-    def forward(ctx, x, w):
-        ctx.save_for_backward(x, w)
-        ctx.w_ref = _pass.parameter_ref(w, ctx, ctx.needs_input_grad[1])
-        return _library_or_own_forward(x, w.reshape(w.shape[-2:]))
-
-    @staticmethod
-    def backward(ctx, grad):
-        x, w = ctx.saved_tensors
-        g2 = grad.reshape(-1, grad.shape[-1]).contiguous()
-        x2 = x.reshape(-1, x.shape[-1])
-        w2 = w.reshape(w.shape[-2:])
-        rows, cin = x2.shape
-        c = g2.shape[1]
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        plan = _dense_kernels.plan(rows, cin, c)
-        if not x2.is_contiguous() or not w2.is_contiguous() or not (need_w and plan["dw"] == "mfma"):
-            grad_x = _library_or_own_input_gradient(g2, w2).view(x.shape) if need_x else None
-            grad_w = _weight_gradient_product(x2, g2).view(w.shape) if need_w else None
-            return grad_x, grad_w
-        ws = _dense_kernels.weight_workspace(rows, cin, c, x.device)
-        grad_x = None
-        if need_x and plan["pair"]:
-            grad_x = torch.empty_like(x)
-            _dense_kernels.backward_pair(x2, g2, w2, grad_x.view(rows, cin), ws)
-        else:
-            if need_x and _pass.may_postpone_input_gradient(x):
-                # no gradient for x through the engine: the end-of-pass callback launches the product behind the reduction
-                # launch and makes its buffer the leaf's .grad
-                late = torch.empty(rows, cin, dtype=x.dtype, device=x.device)
-                _pass.postpone_input_gradient(lambda: _library_or_own_input_gradient(g2, w2, out=late), late, x)
-            elif need_x:
-                grad_x = _library_or_own_input_gradient(g2, w2).view(x.shape)
-            _dense_kernels.backward_weight_partials(x2, g2, ws)
-        return grad_x, _pass.weight_gradient(ctx.w_ref, w, rows, cin, c, ws)
-
-
-class _DenseAny(torch.autograd.Function):
-    """support = input @ W and both gradients on the any-shape matrix-core kernel (csrc/dense_any.hip): the layers whose
-    widths the 192-column kernels do not take -- the mesh encoder's 3 / 60 / ... / 300-wide ZERON_GCN layers, whose weight
-    gradients (18 432 summed rows against a 300 x 300 output) the library runs without a split, 73-97 us each."""
-
-    @staticmethod
-    def forward(ctx, x, w):
-        x2 = x.reshape(-1, x.shape[-1])
-        w2 = w.reshape(w.shape[-2:])
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        ctx.save_for_backward(x2, w)
-        ctx.x_shape = x.shape
-        return _forward_product(x2, w2).view(x.shape[:-1] + (w2.shape[1],))
-
-    @staticmethod
-    def backward(ctx, grad):
-        x2, w = ctx.saved_tensors
-        w2 = w.reshape(w.shape[-2:])
-        g2 = grad.reshape(-1, grad.shape[-1])
-        if not g2.is_contiguous():
-            g2 = g2.contiguous()
-        grad_x = grad_w = None
-        if ctx.needs_input_grad[0]:
-            grad_x = _dense_kernels.gemm(g2, w2, trans_b=True).view(ctx.x_shape)
-        if ctx.needs_input_grad[1]:
-            grad_w = _dense_kernels.gemm(x2, g2, trans_a=True).view(w.shape)
-        return grad_x, grad_w
-
-
-def _dense(x, w):
-    """input @ weight of a 0N-GCN layer; w = the layer's weight parameter ([Cin, Cout] or [1, Cin, Cout])."""
-    arena = current_slabs()
-    plain = (not x.is_cuda or x.dtype != torch.float32 or w.dtype != torch.float32
-             or not (w.dim() == 2 or (w.dim() == 3 and w.shape[0] == 1))
-             or not (x.requires_grad or w.requires_grad) or not torch.is_grad_enabled())
-    if not plain and arena is None and use_matrix_core_products:
-        rows = x.numel() // x.shape[-1]
-        if w.requires_grad and _dense_kernels.plan(rows, x.shape[-1], w.shape[-1])["dw"] == "mfma":
-            return _DenseMM.apply(x, w)
-        if w.is_contiguous() and _takes_any_shape_kernel(rows, x.shape[-1], w.shape[-1]):
-            return _DenseAny.apply(x, w)
-    if plain or arena is None:
-        # ([1,Cin,Cout]: one GEMM, not B broadcast bmm's; the same kernel as the differentiable routes pick for the shape)
-        return _forward_product(x, w.squeeze(0) if w.dim() == 3 else w)
-    return _Dense.apply(x, w, arena)
-
-
 # ---- a stack of layers with its layer BOUNDARIES as single launches (csrc/zn_stack.hip) -----------------------------------
 # Between two consecutive 192-wide layers the aggregation of the first is the operand load of the second's product, and in the
 # backward pass the aggregation backward of a layer is the operand load of its own input-gradient product.  The boundary
@@ -718,31 +419,17 @@ class _FusedBoundary(torch.autograd.Function):
         w2 = w.reshape(w.shape[-2:])
         n_out = w2.shape[1]
         g2 = grad_next.reshape(rows, n_out).contiguous()
-        x2 = x.view(rows, c)
         need_s, need_b, need_w = ctx.needs_input_grad[:3]
         need_b = need_b and ctx.bias_ref is not None
         up, down, csr, k, act = ctx.up, ctx.down, ctx.csr, ctx.k, ctx.act
-        # ---- layer L+1's product: dW partials, and dX unless the launch above left it in the link
-        dx = up.claim_dx(g2)
-        plan = _dense_kernels.plan(rows, c, n_out)
-        grad_w = ws = None
-        split = need_w and plan["dw"] == "mfma" and w2.is_contiguous()
-        if split:
-            ws = _dense_kernels.weight_workspace(rows, c, n_out, x.device)
-        if dx is None and (need_s or need_b):
-            if split and plan["pair"]:
-                dx = torch.empty_like(x)
-                _dense_kernels.backward_pair(x2, g2, w2, dx.view(rows, c), ws)
-            else:
-                dx = torch.matmul(g2, w2.t()).view(x.shape)
-                if split:
-                    _dense_kernels.backward_weight_partials(x2, g2, ws)
-        elif split:
-            _dense_kernels.backward_weight_partials(x2, g2, ws)
-        if split:
-            grad_w = _pass.weight_gradient(ctx.w_ref, w, rows, c, n_out, ws)
-        elif need_w:
-            grad_w = _weight_gradient_product(x2, g2).view(w.shape)
+        # ---- layer L+1's product: its gradients as after _dense (x is contiguous: saved by this node's forward), with dX taken from
+        # the link when the launch above left it there, never postponed, and never on the any-shape kernel (the library, since
+        # this product's forward was not that kernel's either)
+        route = _products.route(rows, c, n_out, need_w, w2.is_contiguous(), True, False, _products._own_products_preferred(),
+                                _products.use_any_shape_products)
+        if route.dx == "any":
+            route = route._replace(dx="lib")
+        dx, grad_w = _products.product_gradients(x, g2, w, ctx.w_ref, route, need_s or need_b, need_w, dx=up.claim_dx(g2))
         if not (need_s or need_b):
             return None, None, grad_w, None, None, None, None, None
         # ---- layer L's aggregation: with the input gradient of ITS product in the same launch when the boundary below wants it
@@ -763,7 +450,7 @@ class _FusedBoundary(torch.autograd.Function):
 
 def _boundary_fuses(x, csr, prev, layer, act, activation):
     """Whether the boundary between `prev` and `layer` takes the single launch."""
-    if not (use_matrix_core_products and current_slabs() is None and isinstance(csr, _Csr)):
+    if not (current_slabs() is None and isinstance(csr, _Csr)):
         return False
     if activation is not None and act == _ACT_NONE:          # a foreign callable: applied by the caller between the operators
         return False

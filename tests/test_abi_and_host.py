@@ -333,25 +333,67 @@ def test_fused_plan_thresholds_and_overrides(monkeypatch):
     assert not fused.supported(Csr, 192, 64, 192)                           # long rows: the table kernel with its CSR tail
 
 
+def _takes_any_shape_kernel(rows, cin, c):
+    """Whether products.route() puts a trainable layer's product of this shape (contiguous operands, default flags apart from
+    use_any_shape_products, which is read where it is set) on csrc/dense_any.hip."""
+    from geometrics_amd import products
+    r = products.route(rows, cin, c, True, True, True, False, False, products.use_any_shape_products)
+    return (r.forward, r.dx, r.dw) == ("any", "any", "any")
+
+
 def test_which_kernel_takes_a_product():
     import torch
-    from geometrics_amd import dense, layers
+    from geometrics_amd import dense, layers, products
     # the 192-column kernels where they apply, the any-shape kernel for every other width, the library for tiny inputs
     assert dense.plan(20496, 963, 192)["dw"] == "mfma" and not dense.plan(20496, 963, 192)["pair"]
     assert dense.plan(20496, 192, 192)["pair"]
     assert dense.plan(18432, 300, 300)["dw"] == "lib" and dense.any_supported(18432, 300, 300)
-    assert layers._takes_any_shape_kernel(18432, 300, 300) and layers._takes_any_shape_kernel(7712, 192, 3)
-    assert not layers._takes_any_shape_kernel(20496, 192, 192)              # dense_gemm.hip's pair launch
-    assert not layers._takes_any_shape_kernel(100, 60, 60)                  # launch-bound: the library
-    keep = layers.use_any_shape_products
-    layers.use_any_shape_products = False
+    assert _takes_any_shape_kernel(18432, 300, 300) and _takes_any_shape_kernel(7712, 192, 3)
+    assert not _takes_any_shape_kernel(20496, 192, 192)              # dense_gemm.hip's pair launch
+    assert not _takes_any_shape_kernel(100, 60, 60)                  # launch-bound: the library
+    keep = products.use_any_shape_products
+    products.use_any_shape_products = False
     try:
-        assert not layers._takes_any_shape_kernel(18432, 300, 300)
+        assert not _takes_any_shape_kernel(18432, 300, 300)
     finally:
-        layers.use_any_shape_products = keep
+        products.use_any_shape_products = keep
     with pytest.raises(ValueError):
         dense.gemm(torch.zeros(4, 3), torch.zeros(5, 2))                    # summed extents differ: refused before any launch
     with pytest.raises(ValueError):
         dense.gemm(torch.zeros(4, 6)[:, ::2], torch.zeros(3, 2))            # rows must have unit stride
     link = layers._StackLink()
     assert link.wt is None and link.dx is None and link.g_ref is None and not link.wanted
+
+
+def test_the_route_of_every_product_is_the_one_it_had():
+    """products.route() over rows x cin x c x its six booleans against tests/golden/product_routes.json: what the three autograd
+    nodes and six predicates it replaced answered at each point (recorded from them: which kernel ran the forward, dX and dW,
+    whether a node of this package wrapped the product, and what their library-or-own choice for an input gradient was).
+    Three differences are deliberate and spelled out below; everything else is equal."""
+    import itertools
+    import json
+    import os
+    from geometrics_amd import products
+    with open(os.path.join(os.path.dirname(__file__), "golden", "product_routes.json")) as f:
+        golden = json.load(f)
+    assert golden["flags"] == ["w_requires_grad", "w_contiguous", "x_contiguous", "batched", "own", "any_allowed"]
+    assert golden["columns"] == ["forward", "dx", "dw", "node", "lib_or_own"]
+    assert (golden["rows"], golden["cin"], golden["c"]) == ([100, 256, 511, 512, 648, 20496], [3, 40, 48, 99, 192, 196, 963],
+                                                            [3, 16, 40, 48, 96, 192, 208])
+    checked = 0
+    for rows, cin, c in itertools.product(golden["rows"], golden["cin"], golden["c"]):
+        line = golden["table"]["%d,%d,%d" % (rows, cin, c)]
+        for letter, flags in zip(line, itertools.product((False, True), repeat=6)):
+            forward, dx, dw, node, lib_or_own = golden["records"][letter]
+            batched = flags[3]
+            if dx == "lib":
+                # an input gradient that was the library's whatever the preference for own products said (inside
+                # weight_gradient_batching(); behind a product torch's autograd differentiated) follows that preference now
+                dx = lib_or_own
+            if not batched:
+                # a node exactly when one of the three is not the library's: a product whose forward is a kernel of this package had
+                # none and lost its gradients; one whose three products were the library's anyway had one and needs none
+                node = (forward, dx, dw) != ("lib", "lib", "lib")
+            assert tuple(products.route(rows, cin, c, *flags)) == (forward, dx, dw, node), (rows, cin, c, flags)
+            checked += 1
+    assert checked == 6 * 7 * 7 * 64

@@ -104,7 +104,7 @@ def test_layer_through_autograd_matches_the_library_route(gpu):
     products (torch.matmul + autograd) -- the same values within fp32 summation order."""
     import numpy as np
     import torch.nn.functional as F
-    from geometrics_amd import layers, meshgen, utils
+    from geometrics_amd import layers, meshgen, products, utils
     V, Fc = meshgen.icosphere(3)
     adj = utils.normalize_adj(utils.calc_adj(torch.from_numpy(np.ascontiguousarray(Fc)).cuda()))
     torch.manual_seed(3)
@@ -113,7 +113,7 @@ def test_layer_through_autograd_matches_the_library_route(gpu):
     seed = torch.randn(V.shape[0], 250, device="cuda")
     res = {}
     for mode in (True, False):
-        layers.use_any_shape_products = mode
+        products.use_any_shape_products = mode
         try:
             layer.zero_grad()
             x.grad = None
@@ -121,7 +121,7 @@ def test_layer_through_autograd_matches_the_library_route(gpu):
             out.backward(seed)
             res[mode] = [out.detach().clone(), x.grad.clone(), layer.weight.grad.clone(), layer.bias.grad.clone()]
         finally:
-            layers.use_any_shape_products = True
+            products.use_any_shape_products = True
     for a, b in zip(res[True], res[False]):
         assert (a - b).abs().max().item() <= 2e-5 * b.abs().max().item()
 
