@@ -16,7 +16,7 @@ FLAG_FIX_REGION6 = 2
 FLAG_TRI_BRUTE_FORCE = 4
 FLAG_NN_FMA = 8
 FLAG_TRI_WS_READY = 16
-ABI_VERSION = 14
+ABI_VERSION = 15
 EUNSUPPORTED = -3
 ADAM_MAX_TENSORS = 64
 COLSUM_MAX_JOBS = 32
@@ -70,8 +70,6 @@ _SIGNATURES = {
     "geom_face_areas_f32": [_i, _i, _vp, _i, _vp, _vp, _vp],
     "geom_draw_samples_f32": [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "geom_draw_samples_rng_f32": [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "geom_surface_loss_bwd_gather_f32": [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                         _f, _f, _vp, _vp, _vp, _vp],
     "geom_surface_loss_bwd_f32": [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp],
     "geom_surface_finalize_f32": [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i,
                                   _i, _vp, _vp, _vp],
@@ -93,15 +91,12 @@ _SIGNATURES = {
     "geom_segment_max_fwd_f32": [_i, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp],
     "geom_segment_max_bwd_f32": [_i, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp],
     "geom_sum_f32": [ctypes.c_int64, _vp, _f, _vp, _vp],
-    "geom_sum2_f32": [ctypes.c_int64, _vp, _f, ctypes.c_int64, _vp, _f, _vp, _vp, ctypes.c_int64, _vp],
     "geom_sample_chamfer_bwd_f32": [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _f, _vp, _vp],
     "geom_laplacian_f32": [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp],
     "geom_edge_sqlen_fwd_f32": [_i, _i, _vp, _i, _vp, _vp, _vp],
     "geom_edge_sqlen_bwd_f32": [_i, _i, _vp, _i, _vp, _vp, _f, _vp, _vp],
     "geom_vertex_bn_fwd_f32": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp, _i, _f, _vp, _vp, _vp, _vp],
     "geom_vertex_bn_bwd_f32": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
-    "geom_pool_features_fwd_f32": [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
-    "geom_pool_features_bwd_f32": [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
     "geom_pool_features_fwd_ld_f32": [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp],
     "geom_pool_features_fwd_fronts_f32": [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _vp],
     "geom_pool_features_bwd_ld_f32": [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_size_t, _vp],
@@ -246,10 +241,6 @@ def lib():
         L.geom_segment_max_workspace_bytes.restype = ctypes.c_int64
         L.geom_segment_max_workspace_bytes.argtypes = [_i, _i, ctypes.c_int64]
         L.geom_zn_gcn_bwd_scratch_floats.restype = ctypes.c_int64
-        L.geom_surface_bin_count_words.restype = ctypes.c_int64
-        L.geom_surface_bin_count_words.argtypes = [_i, _i]
-        L.geom_surface_bin_list_words.restype = ctypes.c_int64
-        L.geom_surface_bin_list_words.argtypes = [_i, _i, _i, _i]
         L.geom_surface_order_words.restype = ctypes.c_int64
         L.geom_surface_order_words.argtypes = [_i, _i, _i, _i]
         L.geom_zn_gcn_relu_mask_words.restype = ctypes.c_int64
@@ -287,7 +278,7 @@ def declared_symbols():
     return sorted(["geom_abi_version", "geom_strerror", "geom_tri_distance_workspace_bytes",
                    "geom_zn_gcn_bwd_scratch_floats", "geom_zn_gcn_bwd_partial_rows", "geom_pool_features_bwd_workspace_bytes",
                    "geom_segment_max_workspace_bytes", "geom_zn_gcn_relu_mask_words",
-                   "geom_surface_bin_count_words", "geom_surface_bin_list_words", "geom_surface_order_words",
+                   "geom_surface_order_words",
                    "geom_dense_bwd_weight_workspace_floats", "geom_chamfer_nn_culled_workspace_floats",
                    "geom_nn_cull_index_floats", "geom_surface_tail_counters_offset", "geom_zn_layer_partial_rows",
                    "geom_gemm_workspace_floats", "geom_stage_regularisers_blocks", "geom_split_bf16_kpad"] + list(_SIGNATURES))

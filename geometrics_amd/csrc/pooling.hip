@@ -700,13 +700,6 @@ extern "C" int geom_pool_features_fwd_fronts_f32(int b, int nv, const float *ver
     return pool_fwd_launch(a, b, nv, out, out_ld, n_fronts, fronts, widths, cols, buf, stream);
 }
 
-extern "C" int geom_pool_features_fwd_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
-                                          int levels, const float *const *blocks, const int *channels, const int *dims,
-                                          float *out, void *stream)
-{
-    return geom_pool_features_fwd_ld_f32(b, nv, verts, cam_mat, cam_pos, levels, blocks, channels, dims, out, 0, stream);
-}
-
 static size_t pool_ws_layout(int b, int nv, int levels, const int *dims, BinSpace *ws, void *base)
 {
     int per_mesh = 0;
@@ -733,19 +726,6 @@ extern "C" size_t geom_pool_features_bwd_workspace_bytes(int b, int nv, int leve
 {
     if (b <= 0 || nv <= 0 || levels <= 0 || levels > GEOM_POOL_MAX_LEVELS || !dims) return 0;
     return pool_ws_layout(b, nv, levels, dims, nullptr, nullptr);
-}
-
-extern "C" int geom_pool_features_bwd_ld_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
-                                             int levels, const float *const *blocks, const int *channels, const int *dims,
-                                             const float *grad_out, int64_t grad_ld, float *const *grad_blocks, float *grad_verts,
-                                             void *workspace, size_t workspace_bytes, void *stream);
-extern "C" int geom_pool_features_bwd_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
-                                          int levels, const float *const *blocks, const int *channels, const int *dims,
-                                          const float *grad_out, float *const *grad_blocks, float *grad_verts,
-                                          void *workspace, size_t workspace_bytes, void *stream)
-{
-    return geom_pool_features_bwd_ld_f32(b, nv, verts, cam_mat, cam_pos, levels, blocks, channels, dims, grad_out, 0, grad_blocks,
-                                         grad_verts, workspace, workspace_bytes, stream);
 }
 
 // grad_ld: floats between two vertex rows of `grad_out` (0 = the pooled width; larger: the gradient is read in place out of a

@@ -293,61 +293,6 @@ __global__ __launch_bounds__(SUM_THREADS) void sum_kernel(int64_t n, const float
     }
 }
 
-constexpr int SUM_BATCH = 8;
-__device__ __forceinline__ float thread_sum(int64_t n, const float *x)
-{
-    float acc = 0.f;
-    const bool vec = (((uintptr_t)x) & 15) == 0;
-    const int64_t n4 = vec ? n / 4 : 0;
-    const float4 *x4 = reinterpret_cast<const float4 *>(x);
-    for (int64_t base = 0; base < n4; base += (int64_t)SUM_BATCH * SUM_THREADS) {
-        float4 v[SUM_BATCH];
-#pragma unroll
-        for (int j = 0; j < SUM_BATCH; ++j) {
-            const int64_t i = base + threadIdx.x + (int64_t)j * SUM_THREADS;
-            v[j] = i < n4 ? x4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int j = 0; j < SUM_BATCH; ++j) acc += (v[j].x + v[j].y) + (v[j].z + v[j].w);
-    }
-    for (int64_t i = 4 * n4 + threadIdx.x; i < n; i += SUM_THREADS) acc += x[i]; // tail / unaligned input
-    return acc;
-}
-
-// out[0] = s1 * sum(x1) + s2 * sum(x2): the whole  (dist_1 + dist_2) * 3000  of utils.py:420/484
-// in one launch, same fixed reduction tree per segment.
-__global__ __launch_bounds__(SUM_THREADS) void sum2_kernel(int64_t n1, const float *x1, float s1, int64_t n2,
-                                                            const float *x2, float s2, float *out, float *clear,
-                                                            int64_t clear_count)
-{
-    __shared__ float partial[2][SUM_THREADS / GEOM_WAVE];
-    // optional side job: zero the buffer the backward will accumulate into (saves the backward a fill launch --
-    // about 5 us inside a captured graph, where this workgroup's stores are free)
-    for (int64_t i = threadIdx.x; i < clear_count; i += SUM_THREADS) clear[i] = 0.f;
-    // One workgroup: the sum is a latency chain unless many loads are in flight.  Each thread issues up to
-    // SUM_BATCH float4 loads per segment back to back (48 000 floats = 12 per thread: one round trip), then
-    // adds them in a fixed order -- the association is static, so the result stays bit-reproducible.
-    float a1 = thread_sum(n1, x1), a2 = thread_sum(n2, x2);
-    for (int off = GEOM_WAVE / 2; off > 0; off >>= 1) {
-        a1 += __shfl_down(a1, off, GEOM_WAVE);
-        a2 += __shfl_down(a2, off, GEOM_WAVE);
-    }
-    if ((threadIdx.x & (GEOM_WAVE - 1)) == 0) {
-        partial[0][threadIdx.x >> 6] = a1;
-        partial[1][threadIdx.x >> 6] = a2;
-    }
-    __syncthreads();
-    if (threadIdx.x < GEOM_WAVE) {
-        float v1 = threadIdx.x < SUM_THREADS / GEOM_WAVE ? partial[0][threadIdx.x] : 0.f;
-        float v2 = threadIdx.x < SUM_THREADS / GEOM_WAVE ? partial[1][threadIdx.x] : 0.f;
-        for (int off = GEOM_WAVE / 2; off > 0; off >>= 1) {
-            v1 += __shfl_down(v1, off, GEOM_WAVE);
-            v2 += __shfl_down(v2, off, GEOM_WAVE);
-        }
-        if (threadIdx.x == 0) out[0] = v1 * s1 + v2 * s2;
-    }
-}
-
 inline dim3 pt_grid(int64_t count) { return dim3((unsigned)((count + PT_THREADS - 1) / PT_THREADS)); }
 
 } // namespace
@@ -470,16 +415,6 @@ extern "C" int geom_surface_loss_bwd_f32(int b, int nv, int nf, const int64_t *f
                      coef_sample, coef_tri, grad_verts, n_gt, (unsigned)blocks_s};
     hipLaunchKernelGGL(surface_bwd_kernel, dim3((unsigned)(blocks_s + blocks_t)), dim3(PT_THREADS), 0,
                        static_cast<hipStream_t>(stream), a);
-    return geom::launch_status();
-}
-
-extern "C" int geom_sum2_f32(int64_t n1, const float *x1, float scale1, int64_t n2, const float *x2, float scale2,
-                             float *out, float *clear, int64_t clear_count, void *stream)
-{
-    if (n1 < 0 || n2 < 0 || !out || (n1 > 0 && !x1) || (n2 > 0 && !x2)) return GEOM_EINVAL;
-    if (clear_count < 0 || (clear_count > 0 && !clear)) return GEOM_EINVAL;
-    hipLaunchKernelGGL(sum2_kernel, dim3(1), dim3(SUM_THREADS), 0, static_cast<hipStream_t>(stream), n1, x1, scale1, n2,
-                       x2, scale2, out, clear, clear_count);
     return geom::launch_status();
 }
 

@@ -14,3 +14,17 @@ static inline int64_t geom_surface_order_ints(int b, int nf, int64_t cap)
 }
 static inline int64_t geom_surface_status_ints(int b) { return ((int64_t)b + 1 + 3) & ~3ll; }
 static inline int64_t geom_surface_status_offset(int b, int nf, int64_t cap) { return geom_surface_order_ints(b, nf, cap) + (int64_t)b * cap * 8; }
+
+// The scratch carved up (float4: the including file has the HIP headers); a null `order` gives null members.
+struct SurfaceScratch {
+    int *off, *seg, *pface, *slot; // [b,nf+1], then [b,cap] each
+    float4 *rec;                   // [b,cap,2]
+    int *status;                   // [b+1]
+};
+static inline SurfaceScratch geom_surface_scratch(int *order, int b, int nf, int64_t cap)
+{
+    if (!order) return SurfaceScratch{};
+    int *seg = order + (int64_t)b * (nf + 1), *pface = seg + (int64_t)b * cap;
+    return SurfaceScratch{order, seg, pface, pface + (int64_t)b * cap, reinterpret_cast<float4 *>(order + geom_surface_order_ints(b, nf, cap)),
+                          order + geom_surface_status_offset(b, nf, cap)};
+}

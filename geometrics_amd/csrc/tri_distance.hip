@@ -1337,6 +1337,20 @@ __global__ __launch_bounds__(8 * GEOM_WAVE, CULL ? 5 : 1) void surface_scan_kern
     }
 }
 
+// Runtime flags -> template arguments: with_flags(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...),
+// so a launch names its kernel once (template argument `A()` for the parameter `auto A`), not once per combination of flags.
+template <class F>
+auto with_flags(F &&f)
+{
+    return f();
+}
+template <class F, class... Flags>
+auto with_flags(F &&f, bool first, Flags... rest)
+{
+    auto bound = [&](auto c) { return with_flags([&](auto... cs) { return f(c, cs...); }, rest...); };
+    return first ? bound(std::true_type{}) : bound(std::false_type{});
+}
+
 template <bool INDEXED, bool TRUNC, bool FIX6>
 int launch_grouped_variant(const TriJob &job, const TriGws &ws, const int *order, hipStream_t s, const SurfaceOut &surf)
 {
@@ -1358,6 +1372,9 @@ int launch_grouped_variant(const TriJob &job, const TriGws &ws, const int *order
     return geom::launch_status();
 }
 
+inline int64_t query_tiles(int b, int n) { return (int64_t)b * ((n + TRI_QUERIES - 1) / TRI_QUERIES); }
+constexpr int FILL_TILES = 256; // query tiles from which one workgroup per tile fills the chip
+
 // How many workgroups share a query tile.  A workgroup holds 16 waves and at most two fit a CU.  With
 // fewer query tiles than CUs (1-5 meshes of 3000 points) most of the chip would idle, so the triangle
 // range of a tile is split over up to 4 workgroups (measured: 1 mesh 51 -> 26 us, 3 meshes 72 -> 50 us).
@@ -1365,19 +1382,46 @@ int launch_grouped_variant(const TriJob &job, const TriGws &ws, const int *order
 // balance returns (8 meshes: 73 us unsplit, 86 us at split 3) and parts stay >= 1024 triangles.
 inline int ws_split(int b, int n, int m_pad)
 {
-    const int64_t tiles = (int64_t)b * ((n + TRI_QUERIES - 1) / TRI_QUERIES);
-    if (tiles <= 0 || tiles >= 256) return 1;
+    const int64_t tiles = query_tiles(b, n);
+    if (tiles <= 0 || tiles >= FILL_TILES) return 1;
     int split = (int)((512 + tiles - 1) / tiles);
     if (split > m_pad / 1024) split = m_pad / 1024;
     if (split > 4) split = 4;
     return split < 1 ? 1 : split;
 }
 
-inline size_t ws_bytes_needed(int b, int n, int m_pad)
+// THE fused-launch rule of the surface step: geom_surface_prepare_f32 writes the triangle records of the scan, and
+// geom_surface_scan_f32 runs both scans as one launch on them, exactly when this holds -- a coherent triangle order, neither
+// the truncation nor the brute-force flag, one workgroup per query tile and enough tiles of the n_gt query points to fill
+// the chip.  (The two must agree: records the scan does not read, or a scan of records nobody wrote, would pass silently.)
+inline bool surface_step_fuses(int b, int n_gt, int nf, bool have_order, unsigned flags)
 {
-    // member spheres + corners, group spheres, triangle-0 corners, merged keys
-    return (size_t)b * m_pad * 4 * sizeof(float4) + (size_t)b * (m_pad / GRP) * sizeof(float4) + (size_t)b * 3 * sizeof(float4) +
-           (size_t)b * n * 8;
+    return have_order && !(flags & (GEOM_FLAG_REF_TAIL_TRUNC | GEOM_FLAG_TRI_BRUTE_FORCE)) &&
+           ws_split(b, n_gt, ws_pad(nf)) == 1 && query_tiles(b, n_gt) >= FILL_TILES;
+}
+
+// The grouped workspace, in float4 units from its start: member spheres at 0 | corners | group spheres | triangle-0 corners |
+// b * n merged keys of 8 bytes (split > 1) or, in their place, the finalize tail's counters.  The flat form (TriWs) keeps its
+// spheres and corners in the same places and its keys where the group spheres start; it fits the same byte count.
+struct GwsLayout {
+    size_t cor, grp, first, keys;
+};
+inline GwsLayout gws_layout(int b, int m_pad)
+{
+    GwsLayout l;
+    l.cor = (size_t)b * m_pad, l.grp = 4 * l.cor, l.first = l.grp + (size_t)b * (m_pad / GRP), l.keys = l.first + (size_t)b * 3;
+    return l;
+}
+inline size_t ws_bytes_needed(int b, int n, int m_pad) { return gws_layout(b, m_pad).keys * sizeof(float4) + (size_t)b * n * 8; }
+inline bool ws_usable(const void *workspace, size_t bytes, int b, int n, int m_pad)
+{
+    return workspace && bytes >= ws_bytes_needed(b, n, m_pad) && !((uintptr_t)workspace & 15);
+}
+inline TriGws carve_gws(void *workspace, int b, int m_pad, int split)
+{
+    const GwsLayout l = gws_layout(b, m_pad);
+    float4 *base = static_cast<float4 *>(workspace);
+    return TriGws{base, base + l.cor, base + l.grp, base + l.first, reinterpret_cast<unsigned long long *>(base + l.keys), m_pad, split};
 }
 
 // *fused = whether the scan wrote the point-to-surface outputs itself (else the caller launches the separate kernel)
@@ -1386,59 +1430,49 @@ int launch_tri_ws(const TriJob &job, const int *order, unsigned flags, void *wor
                   const SurfaceOut &surf = NO_SURFACE, bool *fused = nullptr)
 {
     if (fused) *fused = false;
-    const int m_pad = ws_pad(job.m);
-    if (!workspace || ws_bytes < ws_bytes_needed(job.b, job.n, m_pad) || ((uintptr_t)workspace & 15)) return GEOM_EINVAL;
-    float4 *base = static_cast<float4 *>(workspace);
-    if (order) { // coherent order supplied: two-level scan
-        float4 *grp = base + (size_t)job.b * m_pad * 4;
-        float4 *first = grp + (size_t)job.b * (m_pad / GRP);
-        TriGws gws{base, base + (size_t)job.b * m_pad, grp, first, reinterpret_cast<unsigned long long *>(first + (size_t)job.b * 3),
-                   m_pad, ws_split(job.b, job.n, m_pad)};
-        hipStream_t gs = static_cast<hipStream_t>(stream);
-        const bool gtrunc = flags & GEOM_FLAG_REF_TAIL_TRUNC, gfix6 = flags & GEOM_FLAG_FIX_REGION6;
-        if (fused) *fused = gws.split == 1 && surf.sqdist != nullptr;
-        if (gtrunc && gfix6) return launch_grouped_variant<INDEXED, true, true>(job, gws, order, gs, surf);
-        if (gtrunc) return launch_grouped_variant<INDEXED, true, false>(job, gws, order, gs, surf);
-        if (gfix6) return launch_grouped_variant<INDEXED, false, true>(job, gws, order, gs, surf);
-        return launch_grouped_variant<INDEXED, false, false>(job, gws, order, gs, surf);
-    }
-    TriWs ws{base, base + (size_t)job.b * m_pad, reinterpret_cast<unsigned long long *>(base + (size_t)job.b * m_pad * 4),
-             m_pad, ws_split(job.b, job.n, m_pad)};
+    const int m_pad = ws_pad(job.m), split = ws_split(job.b, job.n, m_pad);
+    if (!ws_usable(workspace, ws_bytes, job.b, job.n, m_pad)) return GEOM_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool trunc = flags & GEOM_FLAG_REF_TAIL_TRUNC, fix6 = flags & GEOM_FLAG_FIX_REGION6;
-    if (trunc && fix6) return launch_ws_variant<INDEXED, true, true>(job, ws, s);
-    if (trunc) return launch_ws_variant<INDEXED, true, false>(job, ws, s);
-    if (fix6) return launch_ws_variant<INDEXED, false, true>(job, ws, s);
-    return launch_ws_variant<INDEXED, false, false>(job, ws, s);
+    if (order) { // coherent order supplied: two-level scan
+        const TriGws gws = carve_gws(workspace, job.b, m_pad, split);
+        if (fused) *fused = split == 1 && surf.sqdist != nullptr;
+        return with_flags([&](auto T, auto F6) { return launch_grouped_variant<INDEXED, T(), F6()>(job, gws, order, s, surf); },
+                          trunc, fix6);
+    }
+    float4 *base = static_cast<float4 *>(workspace);
+    const TriWs ws{base, base + (size_t)job.b * m_pad, reinterpret_cast<unsigned long long *>(base + (size_t)job.b * m_pad * 4),
+                   m_pad, split};
+    return with_flags([&](auto T, auto F6) { return launch_ws_variant<INDEXED, T(), F6()>(job, ws, s); }, trunc, fix6);
 }
 
 template <bool INDEXED>
 int launch_tri(const TriJob &job, unsigned flags, void *stream)
 {
-    dim3 grid((job.n + TRI_QUERIES - 1) / TRI_QUERIES, job.b, 1);
-    dim3 block(TRI_THREADS);
+    const dim3 grid((job.n + TRI_QUERIES - 1) / TRI_QUERIES, job.b, 1), block(TRI_THREADS);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool trunc = flags & GEOM_FLAG_REF_TAIL_TRUNC, fix6 = flags & GEOM_FLAG_FIX_REGION6;
-    if (!(flags & GEOM_FLAG_TRI_BRUTE_FORCE)) {
-        if (trunc && fix6)
-            hipLaunchKernelGGL((tri_distance_culled_kernel<INDEXED, true, true>), grid, block, 0, s, job);
-        else if (trunc)
-            hipLaunchKernelGGL((tri_distance_culled_kernel<INDEXED, true, false>), grid, block, 0, s, job);
-        else if (fix6)
-            hipLaunchKernelGGL((tri_distance_culled_kernel<INDEXED, false, true>), grid, block, 0, s, job);
-        else
-            hipLaunchKernelGGL((tri_distance_culled_kernel<INDEXED, false, false>), grid, block, 0, s, job);
-        return geom::launch_status();
-    }
-    if (trunc && fix6)
-        hipLaunchKernelGGL((tri_distance_kernel<INDEXED, true, true>), grid, block, 0, s, job);
-    else if (trunc)
-        hipLaunchKernelGGL((tri_distance_kernel<INDEXED, true, false>), grid, block, 0, s, job);
-    else if (fix6)
-        hipLaunchKernelGGL((tri_distance_kernel<INDEXED, false, true>), grid, block, 0, s, job);
-    else
-        hipLaunchKernelGGL((tri_distance_kernel<INDEXED, false, false>), grid, block, 0, s, job);
+    const bool brute = flags & GEOM_FLAG_TRI_BRUTE_FORCE, trunc = flags & GEOM_FLAG_REF_TAIL_TRUNC, fix6 = flags & GEOM_FLAG_FIX_REGION6;
+    with_flags([&](auto BRUTE, auto T, auto F6) {
+        if constexpr (BRUTE()) hipLaunchKernelGGL((tri_distance_kernel<INDEXED, T(), F6()>), grid, block, 0, s, job);
+        else hipLaunchKernelGGL((tri_distance_culled_kernel<INDEXED, T(), F6()>), grid, block, 0, s, job);
+    }, brute, trunc, fix6);
     return geom::launch_status();
+}
+
+// The argument checks every tri entry point opens with (INDEXED: verts + faces, else the three corner arrays); the first
+// failing check decides the code.  TRI_EMPTY: nothing to do, the entry point returns 0.  more_missing: a further required
+// pointer of the entry point's own is null.
+constexpr int TRI_EMPTY = 1;
+template <bool INDEXED>
+int tri_check(const TriJob &j, bool more_missing = false)
+{
+    if (j.b < 0 || j.n < 0 || j.m < 0 || j.nv < 0) return GEOM_EINVAL;
+    if (j.b == 0 || j.n == 0) return TRI_EMPTY;
+    if (j.m == 0 || (INDEXED && j.nv == 0)) return GEOM_EINVAL;
+    if (!j.xyz || (INDEXED ? !j.verts || !j.faces : !j.tri1 || !j.tri2 || !j.tri3) || !j.dist || !j.point || !j.index || more_missing)
+        return GEOM_EINVAL;
+    if (j.b > 65535 || j.m >= (1 << 26)) return GEOM_ETOOBIG;
+    return 0;
 }
 
 } // namespace
@@ -1447,12 +1481,8 @@ extern "C" int geom_tri_distance_f32(int b, int n, const float *xyz, int m,
                                      const float *tri1, const float *tri2, const float *tri3,
                                      float *dist, int *point, int *index, unsigned flags, void *stream)
 {
-    if (b < 0 || n < 0 || m < 0) return GEOM_EINVAL;
-    if (b == 0 || n == 0) return 0;
-    if (m == 0) return GEOM_EINVAL;
-    if (!xyz || !tri1 || !tri2 || !tri3 || !dist || !point || !index) return GEOM_EINVAL;
-    if (b > 65535 || m >= (1 << 26)) return GEOM_ETOOBIG;
-    TriJob job{xyz, tri1, tri2, tri3, nullptr, nullptr, dist, point, index, b, n, m, 0};
+    const TriJob job{xyz, tri1, tri2, tri3, nullptr, nullptr, dist, point, index, b, n, m, 0};
+    if (const int code = tri_check<false>(job)) return code == TRI_EMPTY ? 0 : code;
     return launch_tri<false>(job, flags, stream);
 }
 
@@ -1460,12 +1490,8 @@ extern "C" int geom_tri_distance_indexed_f32(int b, int n, const float *xyz, int
                                              int nf, const int64_t *faces,
                                              float *dist, int *point, int *index, unsigned flags, void *stream)
 {
-    if (b < 0 || n < 0 || nf < 0 || nv < 0) return GEOM_EINVAL;
-    if (b == 0 || n == 0) return 0;
-    if (nf == 0 || nv == 0) return GEOM_EINVAL;
-    if (!xyz || !verts || !faces || !dist || !point || !index) return GEOM_EINVAL;
-    if (b > 65535 || nf >= (1 << 26)) return GEOM_ETOOBIG;
-    TriJob job{xyz, nullptr, nullptr, nullptr, verts, faces, dist, point, index, b, n, nf, nv};
+    const TriJob job{xyz, nullptr, nullptr, nullptr, verts, faces, dist, point, index, b, n, nf, nv};
+    if (const int code = tri_check<true>(job)) return code == TRI_EMPTY ? 0 : code;
     return launch_tri<true>(job, flags, stream);
 }
 
@@ -1475,8 +1501,7 @@ extern "C" int geom_tri_distance_indexed_f32(int b, int n, const float *xyz, int
 extern "C" size_t geom_surface_tail_counters_offset(int b, int n, int m)
 {
     if (b <= 0 || n <= 0 || m <= 0 || !tail_counters_fit(b, n)) return 0;
-    const int m_pad = ws_pad(m);
-    return ((size_t)b * m_pad * 4 + (size_t)b * (m_pad / GRP) + (size_t)b * 3) * sizeof(float4);
+    return gws_layout(b, ws_pad(m)).keys * sizeof(float4);
 }
 
 extern "C" size_t geom_tri_distance_workspace_bytes(int b, int n, int m)
@@ -1490,12 +1515,8 @@ extern "C" int geom_tri_distance_ws_f32(int b, int n, const float *xyz, int m,
                                         float *dist, int *point, int *index, unsigned flags,
                                         void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (b < 0 || n < 0 || m < 0) return GEOM_EINVAL;
-    if (b == 0 || n == 0) return 0;
-    if (m == 0) return GEOM_EINVAL;
-    if (!xyz || !tri1 || !tri2 || !tri3 || !dist || !point || !index) return GEOM_EINVAL;
-    if (b > 65535 || m >= (1 << 26)) return GEOM_ETOOBIG;
-    TriJob job{xyz, tri1, tri2, tri3, nullptr, nullptr, dist, point, index, b, n, m, 0};
+    const TriJob job{xyz, tri1, tri2, tri3, nullptr, nullptr, dist, point, index, b, n, m, 0};
+    if (const int code = tri_check<false>(job)) return code == TRI_EMPTY ? 0 : code;
     if (flags & GEOM_FLAG_TRI_BRUTE_FORCE) return launch_tri<false>(job, flags, stream);
     return launch_tri_ws<false>(job, order, flags, workspace, workspace_bytes, stream);
 }
@@ -1505,12 +1526,8 @@ extern "C" int geom_tri_distance_indexed_ws_f32(int b, int n, const float *xyz, 
                                                 float *dist, int *point, int *index, unsigned flags,
                                                 void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (b < 0 || n < 0 || nf < 0 || nv < 0) return GEOM_EINVAL;
-    if (b == 0 || n == 0) return 0;
-    if (nf == 0 || nv == 0) return GEOM_EINVAL;
-    if (!xyz || !verts || !faces || !dist || !point || !index) return GEOM_EINVAL;
-    if (b > 65535 || nf >= (1 << 26)) return GEOM_ETOOBIG;
-    TriJob job{xyz, nullptr, nullptr, nullptr, verts, faces, dist, point, index, b, n, nf, nv};
+    const TriJob job{xyz, nullptr, nullptr, nullptr, verts, faces, dist, point, index, b, n, nf, nv};
+    if (const int code = tri_check<true>(job)) return code == TRI_EMPTY ? 0 : code;
     if (flags & GEOM_FLAG_TRI_BRUTE_FORCE) return launch_tri<true>(job, flags, stream);
     return launch_tri_ws<true>(job, order, flags, workspace, workspace_bytes, stream);
 }
@@ -1522,12 +1539,8 @@ extern "C" int geom_tri_surface_fwd_f32(int b, int n, const float *xyz, int nv, 
                                         float *sqdist, float *closest, float *weights, unsigned flags, void *workspace,
                                         size_t workspace_bytes, void *stream)
 {
-    if (b < 0 || n < 0 || nf < 0 || nv < 0) return GEOM_EINVAL;
-    if (b == 0 || n == 0) return 0;
-    if (nf == 0 || nv == 0) return GEOM_EINVAL;
-    if (!xyz || !verts || !faces || !dist || !point || !index || !sqdist || !closest || !weights) return GEOM_EINVAL;
-    if (b > 65535 || nf >= (1 << 26)) return GEOM_ETOOBIG;
-    TriJob job{xyz, nullptr, nullptr, nullptr, verts, faces, dist, point, index, b, n, nf, nv};
+    const TriJob job{xyz, nullptr, nullptr, nullptr, verts, faces, dist, point, index, b, n, nf, nv};
+    if (const int code = tri_check<true>(job, !sqdist || !closest || !weights)) return code == TRI_EMPTY ? 0 : code;
     bool fused = false;
     int rc;
     if (flags & GEOM_FLAG_TRI_BRUTE_FORCE) rc = launch_tri<true>(job, flags, stream);
@@ -1546,11 +1559,11 @@ __global__ __launch_bounds__(NNS_THREADS) void nn_records_kernel(NNJob job, NNRe
 // corners).  gt [b,n_gt,3] against the sampled points [b,num,3]: NN both ways (sq_gt / idx_p for the gt points, sq_pred /
 // idx_g for the sampled points, as geom_chamfer_nn_f32(gt, points)); and, when verts != NULL, gt against the mesh
 // (tri_dist / option / index + the point-to-surface quantities sq / closest / weights, as geom_tri_surface_fwd_f32).
-// With a coherent triangle order, the default arithmetic flags and enough query tiles to fill the chip both scans run
-// as ONE heterogeneous launch after the triangle-record prep; otherwise as the separate launches.  order_scratch (may be
-// NULL): the finalize scratch of geom_surface_finalize_f32 -- the scans then also write every point's gradient record
-// into it (u, v: the sampled points' draws; coef_*: the two gradient coefficients); *records_written tells the caller
-// whether they did (the split / brute-force / truncation variants leave them to the finalize pass).
+// Where the step fuses (surface_step_fuses) both scans run as ONE heterogeneous launch after the triangle-record prep;
+// otherwise as the separate launches.  order_scratch (may be NULL): the finalize scratch of geom_surface_finalize_f32 --
+// the scans then also write every point's gradient record into it (u, v: the sampled points' draws; coef_*: the two
+// gradient coefficients); *records_written tells the caller whether they did (the split / brute-force / truncation
+// variants leave them to the finalize pass).
 extern "C" int geom_surface_scan_f32(int b, int n_gt, const float *gt, int num, const float *points, float *sq_gt,
                                      int *idx_p, float *sq_pred, int *idx_g, int nv, const float *verts, int nf,
                                      const int64_t *faces, const int *tri_order, float *tri_dist, int *option, int *index,
@@ -1574,7 +1587,8 @@ extern "C" int geom_surface_scan_f32(int b, int n_gt, const float *gt, int num, 
     if ((nn_flags & GEOM_FLAG_REF_TAIL_TRUNC) && (nn_flags & GEOM_FLAG_NN_FMA)) return GEOM_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t cap = (int64_t)num + n_gt;
-    float4 *rec = order_scratch ? reinterpret_cast<float4 *>(order_scratch + geom_surface_order_ints(b, nf, cap)) : nullptr;
+    const SurfaceScratch scr = geom_surface_scratch(order_scratch, b, nf, cap);
+    float4 *rec = scr.rec;
     NNJob job{gt, points, sq_gt, sq_pred, idx_p, idx_g, b, n_gt, num};
     const int longer = n_gt > num ? n_gt : num;
     const int nn_tiles = (longer + NN_QUERIES - 1) / NN_QUERIES;
@@ -1582,25 +1596,20 @@ extern "C" int geom_surface_scan_f32(int b, int n_gt, const float *gt, int num, 
     const unsigned nn_blocks = geom::xcd_grid(2 * b, nn_tiles);
     const bool fma = nn_flags & GEOM_FLAG_NN_FMA;
     // records of the NN side: the sampled points always; the gt points through their nearest sample only without a tri scan
-    NNRecords rr{rec, u, v, coef_sample, coef_other, (int)(tri ? cap : cap), tri ? 0 : 1};
+    NNRecords rr{rec, u, v, coef_sample, coef_other, (int)cap, tri ? 0 : 1};
 
     if (tri) {
-        const int m_pad = ws_pad(nf);
-        const int split = ws_split(b, n_gt, m_pad);
-        const bool fusable = tri_order && !(tri_flags & (GEOM_FLAG_REF_TAIL_TRUNC | GEOM_FLAG_TRI_BRUTE_FORCE)) &&
-                             !(nn_flags & GEOM_FLAG_REF_TAIL_TRUNC) && split == 1 &&
-                             (int64_t)b * ((n_gt + TRI_QUERIES - 1) / TRI_QUERIES) >= 256;
-        if (fusable) {
-            if (!workspace || workspace_bytes < ws_bytes_needed(b, n_gt, m_pad) || ((uintptr_t)workspace & 15)) return GEOM_EINVAL;
-            float4 *base = static_cast<float4 *>(workspace);
-            float4 *grp = base + (size_t)b * m_pad * 4;
-            float4 *first = grp + (size_t)b * (m_pad / GRP);
-            TriGws gws{base, base + (size_t)b * m_pad, grp, first, reinterpret_cast<unsigned long long *>(first + (size_t)b * 3), m_pad, 1};
+        if (surface_step_fuses(b, n_gt, nf, tri_order != nullptr, flags)) {
+            const int m_pad = ws_pad(nf);
+            if (!ws_usable(workspace, workspace_bytes, b, n_gt, m_pad)) return GEOM_EINVAL;
+            const TriGws gws = carve_gws(workspace, b, m_pad, 1);
             TriJob tj{gt, nullptr, nullptr, nullptr, verts, faces, tri_dist, option, index, b, n_gt, nf, nv};
             const bool fix6 = tri_flags & GEOM_FLAG_FIX_REGION6;
-            if (flags & GEOM_FLAG_TRI_WS_READY) {} // records of an earlier call on the same mesh: no prep launch
-            else if (fix6) hipLaunchKernelGGL((tri_prep_grouped_kernel<true, false, true>), dim3((m_pad + 255) / 256, b), dim3(256), 0, s, tj, gws, tri_order);
-            else hipLaunchKernelGGL((tri_prep_grouped_kernel<true, false, false>), dim3((m_pad + 255) / 256, b), dim3(256), 0, s, tj, gws, tri_order);
+            if (!(flags & GEOM_FLAG_TRI_WS_READY)) // (else: records of an earlier call on the same mesh, no prep launch)
+                with_flags([&](auto F6) {
+                    hipLaunchKernelGGL((tri_prep_grouped_kernel<true, false, F6()>), dim3((m_pad + 255) / 256, b), dim3(256), 0, s, tj,
+                                       gws, tri_order);
+                }, fix6);
             const int qtiles = (n_gt + TRI_QUERIES - 1) / TRI_QUERIES;
             const unsigned tri_blocks = geom::xcd_grid(b, qtiles);
             SurfaceOut so{verts, faces, nv, sq, closest, weights, rec, coef_other, (int)cap, num};
@@ -1613,18 +1622,14 @@ extern "C" int geom_surface_scan_f32(int b, int n_gt, const float *gt, int num, 
             ScanTail st{};
             if (tail && (!tail->loss || !tail->choices || (tail->want_order && !rec))) return GEOM_EINVAL;
             if (tail && culled) { // the launch with the culled Chamfer tiles only (three workgroups per CU, latency-bound tiles)
-                const int64_t per64 = (int64_t)num + n_gt;
                 // (b <= scan_tail_max_meshes(): the roles wait from the start of the launch on slots the tiles need too -- a few
                 // dozen of 768 cost nothing, hundreds would crowd the tiles out; larger batches finalize in a launch of their own)
-                if (per64 <= 0x3fffffff && b <= scan_tail_max_meshes() && tail_counters_fit(b, n_gt) &&
-                    geom_finalize::finalize_lds_ints(nf, (int)per64, 8 * GEOM_WAVE, tail->want_order != 0) < (size_t)SCAN_TAIL_LDS_INTS) {
-                    int *off = order_scratch, *seg = off ? off + (int64_t)b * (nf + 1) : nullptr;
-                    int *pface = seg ? seg + (int64_t)b * cap : nullptr, *slot = pface ? pface + (int64_t)b * cap : nullptr;
+                if (cap <= 0x3fffffff && b <= scan_tail_max_meshes() && tail_counters_fit(b, n_gt) &&
+                    geom_finalize::finalize_lds_ints(nf, (int)cap, 8 * GEOM_WAVE, tail->want_order != 0) < (size_t)SCAN_TAIL_LDS_INTS) {
                     st.fin = geom_finalize::FinalizeArgs{tail->choices, u, v, points, gt, idx_g, nullptr, index, closest, weights, sq_pred, sq,
                                                          tail->scale_sample, tail->scale_other, coef_sample, coef_other, b, nf, num, n_gt,
-                                                         geom_finalize::OTHER_TRI, (int)per64, tail->want_order ? 1 : 0, rec ? 1 : 0,
-                                                         off, seg, pface, slot, rec, tail->loss,
-                                                         order_scratch ? order_scratch + geom_surface_status_offset(b, nf, cap) : nullptr};
+                                                         geom_finalize::OTHER_TRI, (int)cap, tail->want_order ? 1 : 0, rec ? 1 : 0,
+                                                         scr.off, scr.seg, scr.pface, scr.slot, rec, tail->loss, scr.status};
                     st.done = reinterpret_cast<int *>(gws.keys);
                     st.tiles = (int)(tri_blocks + nn_blocks);
                     st.roles = tail->want_order ? b + 1 : 1;
@@ -1641,20 +1646,10 @@ extern "C" int geom_surface_scan_f32(int b, int n_gt, const float *gt, int num, 
                 nc = NNCull{reinterpret_cast<const float *>(s1 + (size_t)b * (n_gt / NNS_GROUP)),
                             reinterpret_cast<const float *>(s2 + (size_t)b * (num / NNS_GROUP)), cull->gt_order, nullptr, s1, s2}; // samples: identity order
             }
-#define GEOM_LAUNCH_SCAN(F6, FM, CU)                                                                                            \
-    hipLaunchKernelGGL((surface_scan_kernel<F6, FM, CU>), grid, block, 0, s, gt, b, n_gt, nf, gws, tri_dist, option, index, so, job, \
-                       rr, (int)tri_blocks, nc, st)
-#define GEOM_LAUNCH_SCAN2(F6, FM)                                                                                               \
-    do {                                                                                                                        \
-        if (culled) GEOM_LAUNCH_SCAN(F6, FM, true);                                                                             \
-        else GEOM_LAUNCH_SCAN(F6, FM, false);                                                                                   \
-    } while (0)
-            if (fix6 && fma) GEOM_LAUNCH_SCAN2(true, true);
-            else if (fix6) GEOM_LAUNCH_SCAN2(true, false);
-            else if (fma) GEOM_LAUNCH_SCAN2(false, true);
-            else GEOM_LAUNCH_SCAN2(false, false);
-#undef GEOM_LAUNCH_SCAN2
-#undef GEOM_LAUNCH_SCAN
+            with_flags([&](auto F6, auto FMA, auto CULL) {
+                hipLaunchKernelGGL((surface_scan_kernel<F6(), FMA(), CULL()>), grid, block, 0, s, gt, b, n_gt, nf, gws, tri_dist, option,
+                                   index, so, job, rr, (int)tri_blocks, nc, st);
+            }, fix6, fma, culled);
             if (records_written) *records_written = rec != nullptr;
             return geom::launch_status();
         }
@@ -1666,16 +1661,15 @@ extern "C" int geom_surface_scan_f32(int b, int n_gt, const float *gt, int num, 
     }
     // no tri scan (batch_point_to_point): the NN launch writes both kinds of records
     if (nn_flags & GEOM_FLAG_REF_TAIL_TRUNC) return geom_chamfer_nn_f32(b, n_gt, gt, num, points, sq_gt, idx_p, sq_pred, idx_g, nn_flags, stream);
-    if (fma) hipLaunchKernelGGL(nn_records_kernel<true>, dim3(nn_blocks), dim3(NNS_THREADS), 0, s, job, rr);
-    else hipLaunchKernelGGL(nn_records_kernel<false>, dim3(nn_blocks), dim3(NNS_THREADS), 0, s, job, rr);
+    with_flags([&](auto FMA) { hipLaunchKernelGGL(nn_records_kernel<FMA()>, dim3(nn_blocks), dim3(NNS_THREADS), 0, s, job, rr); }, fma);
     if (records_written) *records_written = rec != nullptr;
     return geom::launch_status();
 }
 
 // Draws + sampled points of batch_sample (exactly geom_draw_samples_rng_f32) and, when the surface scan of the same
-// step will run fused (same conditions as in geom_surface_scan_f32: coherent tri_order, no truncation / brute-force
-// flags, >= 256 query tiles of n_gt points), the triangle records of that scan -- in ONE launch; *prepared = 1 then and
-// the scan is called with GEOM_FLAG_TRI_WS_READY.  Otherwise only the draws are made (*prepared = 0).
+// step will run fused (surface_step_fuses for its n_gt query points, and a workspace to write to), the triangle records of
+// that scan -- in ONE launch; *prepared = 1 then and the scan is called with GEOM_FLAG_TRI_WS_READY.  Otherwise only the
+// draws are made (*prepared = 0).
 extern "C" int geom_surface_prepare_f32(int b, int nv, const float *verts, int nf, const int64_t *faces, int num,
                                         uint64_t *rng_state, int64_t *choices, float *u, float *v, float *points, int n_gt,
                                         const int *tri_order, unsigned flags, void *workspace, size_t workspace_bytes,
@@ -1687,46 +1681,29 @@ extern "C" int geom_surface_prepare_f32(int b, int nv, const float *verts, int n
     if (b == 0 || num == 0) return 0;
     if (nf == 0 || !verts || !faces || !rng_state || !choices || !u || !v) return GEOM_EINVAL;
     if (b > 65535) return GEOM_ETOOBIG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int draw_chunks = (num + DRAW_THREADS - 1) / DRAW_THREADS;
+    if (!workspace || n_gt <= 0 || !surface_step_fuses(b, n_gt, nf, tri_order != nullptr, flags))
+        return geom_draw_samples_rng_f32(b, nv, verts, nf, faces, num, rng_state, choices, u, v, points, stream);
     const int m_pad = ws_pad(nf);
-    const bool fusable = tri_order && workspace && n_gt > 0 &&
-                         !(flags & (GEOM_FLAG_REF_TAIL_TRUNC | GEOM_FLAG_TRI_BRUTE_FORCE)) && ws_split(b, n_gt, m_pad) == 1 &&
-                         (int64_t)b * ((n_gt + TRI_QUERIES - 1) / TRI_QUERIES) >= 256;
-    if (!fusable) return geom_draw_samples_rng_f32(b, nv, verts, nf, faces, num, rng_state, choices, u, v, points, stream);
-    if (workspace_bytes < ws_bytes_needed(b, n_gt, m_pad) || ((uintptr_t)workspace & 15)) return GEOM_EINVAL;
-    float4 *base = static_cast<float4 *>(workspace);
-    float4 *grp = base + (size_t)b * m_pad * 4;
-    float4 *first = grp + (size_t)b * (m_pad / GRP);
-    TriGws gws{base, base + (size_t)b * m_pad, grp, first, reinterpret_cast<unsigned long long *>(first + (size_t)b * 3), m_pad, 1};
+    if (!ws_usable(workspace, workspace_bytes, b, n_gt, m_pad)) return GEOM_EINVAL;
+    const TriGws gws = carve_gws(workspace, b, m_pad, 1);
     TriJob tj{nullptr, nullptr, nullptr, nullptr, verts, faces, nullptr, nullptr, nullptr, b, n_gt, nf, nv};
-    const int prep_chunks = (m_pad + DRAW_THREADS - 1) / DRAW_THREADS;
-    unsigned long long *st = reinterpret_cast<unsigned long long *>(rng_state);
+    const int draw_chunks = (num + DRAW_THREADS - 1) / DRAW_THREADS, prep_chunks = (m_pad + DRAW_THREADS - 1) / DRAW_THREADS;
     // the culled Chamfer scan of the same step wants the samples in a visiting order: the draw workgroups then generate them
     // in the order of their faces' positions in tri_order (sorted uniforms from exponential spacings: draw_body.h) and write
     // the samples' index -- run spheres + visiting-order copy
     const bool sorted = cull && cull->sample_index && num >= NN_QUERIES && num < DRAW_SORT_CHUNKS * DRAW_THREADS;
     if (sorted && ((uintptr_t)cull->sample_index & 15)) return GEOM_EINVAL;
-    const int draw_blocks = draw_chunks * b;
-    const dim3 grid(draw_blocks + prep_chunks * b), block(DRAW_THREADS);
+    DrawSort srt{};
     if (sorted) {
         float4 *sph = reinterpret_cast<float4 *>(cull->sample_index);
-        DrawSort srt{tri_order, cull->faces_in_order, reinterpret_cast<float *>(sph + (size_t)b * (num / NNS_GROUP)), sph};
-        if (flags & GEOM_FLAG_FIX_REGION6)
-            hipLaunchKernelGGL((surface_prepare_kernel<true, true>), grid, block, 0, s, draw_blocks, draw_chunks, nv, verts, nf, faces,
-                               num, st, choices, u, v, points, tj, gws, tri_order, prep_chunks, srt);
-        else
-            hipLaunchKernelGGL((surface_prepare_kernel<false, true>), grid, block, 0, s, draw_blocks, draw_chunks, nv, verts, nf, faces,
-                               num, st, choices, u, v, points, tj, gws, tri_order, prep_chunks, srt);
-        if (prepared) *prepared = 3; // bit 0: triangle records; bit 1: the sampled points' index
-        return geom::launch_status();
+        srt = DrawSort{tri_order, cull->faces_in_order, reinterpret_cast<float *>(sph + (size_t)b * (num / NNS_GROUP)), sph};
     }
-    if (flags & GEOM_FLAG_FIX_REGION6)
-        hipLaunchKernelGGL((surface_prepare_kernel<true, false>), grid, block, 0, s, draw_blocks, draw_chunks, nv, verts, nf, faces, num,
-                           st, choices, u, v, points, tj, gws, tri_order, prep_chunks, DrawSort{});
-    else
-        hipLaunchKernelGGL((surface_prepare_kernel<false, false>), grid, block, 0, s, draw_blocks, draw_chunks, nv, verts, nf, faces, num,
-                           st, choices, u, v, points, tj, gws, tri_order, prep_chunks, DrawSort{});
-    if (prepared) *prepared = 1;
+    const int draw_blocks = draw_chunks * b;
+    with_flags([&](auto F6, auto SORTED) {
+        hipLaunchKernelGGL((surface_prepare_kernel<F6(), SORTED()>), dim3(draw_blocks + prep_chunks * b), dim3(DRAW_THREADS), 0,
+                           static_cast<hipStream_t>(stream), draw_blocks, draw_chunks, nv, verts, nf, faces, num,
+                           reinterpret_cast<unsigned long long *>(rng_state), choices, u, v, points, tj, gws, tri_order, prep_chunks, srt);
+    }, (flags & GEOM_FLAG_FIX_REGION6) != 0, sorted);
+    if (prepared) *prepared = sorted ? 3 : 1; // bit 0: triangle records; bit 1: the sampled points' index
     return geom::launch_status();
 }

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GEOM_ABI_VERSION 14
+#define GEOM_ABI_VERSION 15
 
 /* argument errors */
 #define GEOM_EINVAL   (-1) /* bad size / null pointer */
@@ -184,11 +184,6 @@ int geom_p2tri_loss_bwd_f32(int b, int n, const float *xyz, int nv, int nf, cons
 
 /* out[0] = scale * sum(x[0..n)) with a fixed reduction tree (bit-reproducible run to run). */
 int geom_sum_f32(int64_t n, const float *x, float scale, float *out, void *stream);
-/* out[0] = scale1*sum(x1) + scale2*sum(x2): the whole (dist_1 + dist_2) * 3000 of utils.py:420/484.
- * clear/clear_count (may be NULL/0): floats the same launch sets to zero -- the buffer the backward scatters
- * into, so that it needs no fill launch of its own (one workgroup: meant for a few hundred KB). */
-int geom_sum2_f32(int64_t n1, const float *x1, float scale1, int64_t n2, const float *x2, float scale2,
-                  float *out, float *clear, int64_t clear_count, void *stream);
 
 /* Fused backward of the Chamfer term THROUGH the sampling (utils.py:454-462 + 615-631 under autograd):
  * the gradient 2*coef*(point - other) of a sampled point is scattered straight into grad_verts with
@@ -210,24 +205,6 @@ int geom_surface_loss_bwd_f32(int b, int nv, int nf, const int64_t *faces, int n
                               const int *idx_g, const int *index, const float *closest, const float *weights,
                               const float *coef_dev, float coef_sample, float coef_tri, float *grad_verts,
                               void *stream);
-/* The same backward (and that of batch_point_to_point) as a GATHER: no float atomics, no zero-fill of grad_verts,
- * bit-reproducible.  vf_ptr [nv+1] / vf_item [3*nf] = static CSR vertex -> incident (face << 2 | corner), ascending
- * per vertex.  Exactly one of idx_p ([b,n_gt] nearest sampled point of each gt point: the two-sided Chamfer term)
- * and index (+ closest, weights: the point-to-triangle term) may be given, or neither (sampled-point term only).
- * counts: geom_surface_bin_count_words(b, nf) int32, MUST BE ZERO on entry and is left zero again;
- * lists: geom_surface_bin_list_words(b, nf, num, n_gt) int32 scratch, 16-byte aligned (face offsets, per-point slot /
- * face / ordered id lists and two float4 records per point: the points are counting-sorted by face and every
- * face's points summed in ascending id order -- exact for any distribution of points over faces).  Returns
- * GEOM_EUNSUPPORTED when nf + num + n_gt exceeds what one workgroup can order in LDS (~38 000): use the scatter
- * entry points then.  Every element of grad_verts [b,nv,3] is written. */
-int64_t geom_surface_bin_count_words(int b, int nf);
-int64_t geom_surface_bin_list_words(int b, int nf, int num, int n_gt);
-int geom_surface_loss_bwd_gather_f32(int b, int nv, int nf, const int *vf_ptr, const int *vf_item, int num,
-                                     const int64_t *choices, const float *u, const float *v, const float *points,
-                                     int n_gt, const float *gt, const int *idx_g, const int *idx_p, const int *index,
-                                     const float *closest, const float *weights, const float *coef_dev,
-                                     float coef_sample, float coef_other, int *counts, int *lists, float *grad_verts,
-                                     void *stream);
 
 /* ---- 0N-GCN aggregation (layers.py:34-41, 107-116, 143-152) -----------------------------------
  * out[r,:k] = sum_j val[j]*support[col[j],:k] over CSR row r (rowptr int32 [nv+1], col int32, val f32),
@@ -590,15 +567,8 @@ int geom_vertex_bn_bwd_f32(int b, int nv, int c, const float *x, const float *gr
  * gradient is requested (ABI 9; GEOM_EINVAL otherwise); dims[l] <= 64, else GEOM_EUNSUPPORTED. */
 size_t geom_pool_features_bwd_workspace_bytes(int b, int nv, int levels, const int *dims);
 #define GEOM_POOL_MAX_LEVELS 8
-int geom_pool_features_fwd_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
-                               int levels, const float *const *blocks, const int *channels, const int *dims,
-                               float *out, void *stream);
-int geom_pool_features_bwd_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
-                               int levels, const float *const *blocks, const int *channels, const int *dims,
-                               const float *grad_out, float *const *grad_blocks, float *grad_verts,
-                               void *workspace, size_t workspace_bytes, void *stream);
-/* The same two with a ROW PITCH: out_ld / grad_ld = floats between two vertex rows (0 = the pooled width, i.e. the calls
- * above).  Larger: the features are written into / their gradient is read out of a column slice of a wider row-major buffer --
+/* Forward and backward take a ROW PITCH: out_ld / grad_ld = floats between two vertex rows (0 = the pooled width).
+ * Larger: the features are written into / their gradient is read out of a column slice of a wider row-major buffer --
  * the deformation block's concatenated input [positions | previous features | pooled] and the input gradient of its first
  * product -- so that neither `torch.cat` (utils.py / models.py:241) nor the slicing copies of its backward are launched. */
 int geom_pool_features_fwd_ld_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos, int levels,
@@ -640,8 +610,8 @@ int geom_nn_cull_index_f32(int b, int n, const float *xyz, const int *order, flo
 
 /* ---- per-step preparation of the surface loss in one launch ------------------------------------------------------
  * Everything that depends only on the vertex positions: the random face draws (+ sampled points) of batch_sample,
- * exactly geom_draw_samples_rng_f32, AND -- when the scan of the same step will take the fused route (coherent
- * tri_order, no truncation / brute-force flag, >= 256 query tiles of n_gt points) -- the triangle records of
+ * exactly geom_draw_samples_rng_f32, AND -- when the scan of the same step will take the fused route (THE FUSED ROUTE
+ * under geom_surface_scan_f32 below; a NULL workspace or n_gt = 0 also means "draws only") -- the triangle records of
  * geom_surface_scan_f32 in `workspace` (geom_tri_distance_workspace_bytes(b, n_gt, nf)).  *prepared = 1 then: pass
  * GEOM_FLAG_TRI_WS_READY and the same workspace to the scan.  Otherwise only the draws are made (*prepared = 0). */
 int geom_surface_prepare_f32(int b, int nv, const float *verts, int nf, const int64_t *faces, int num,
@@ -652,10 +622,12 @@ int geom_surface_prepare_f32(int b, int nv, const float *verts, int nf, const in
 /* ---- the two arg-min scans of the surface loss in one call (utils.py:451 + 470) ----------------------------------
  * gt [b,n_gt,3] against the sampled points [b,num,3]: nearest neighbours both ways, exactly geom_chamfer_nn_f32(gt,
  * points) -> (sq_gt, idx_p) for the gt points, (sq_pred, idx_g) for the sampled points; and, when verts != NULL, gt
- * against the mesh, exactly geom_tri_surface_fwd_f32 -> tri_dist / option / index + sq / closest / weights.  With a
- * coherent tri_order, default tri flags and at least 256 query tiles both scans run as ONE heterogeneous launch
- * (workgroups [0, tri tiles) scan triangles, the rest scan points) behind the triangle-record prep; otherwise as the
- * separate launches -- same results either way.  flags: GEOM_FLAG_FIX_REGION6 / _TRI_BRUTE_FORCE / _REF_TAIL_TRUNC /
+ * against the mesh, exactly geom_tri_surface_fwd_f32 -> tri_dist / option / index + sq / closest / weights.
+ * THE FUSED ROUTE: with a coherent tri_order, neither GEOM_FLAG_REF_TAIL_TRUNC nor _TRI_BRUTE_FORCE, and at least 256
+ * query tiles (b * ceil(n_gt / 64)) both scans run as ONE heterogeneous launch (workgroups [0, tri tiles) scan
+ * triangles, the rest scan points) behind the triangle-record prep; otherwise as the separate launches -- same results
+ * either way.  (One rule in the library decides this for geom_surface_prepare_f32 and for this call.)
+ * flags: GEOM_FLAG_FIX_REGION6 / _TRI_BRUTE_FORCE / _REF_TAIL_TRUNC /
  * _NN_FMA as for the separate entry points.  workspace: as geom_tri_distance_workspace_bytes(b, n_gt, nf).
  * order_scratch (may be NULL): the `order` buffer of geom_surface_finalize_f32; the scans then also write every
  * point's gradient record into it (u, v [b,num]: the draws of the sampled points; coef_sample / coef_other as for the
