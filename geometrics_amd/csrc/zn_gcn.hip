@@ -262,6 +262,27 @@ inline GcnGeometry gcn_geometry(int b, int nv, int c, int vec, bool backward)
 
 inline bool gcn_vec4(int c, int /*k*/) { return c % 4 == 0; } // any k: the group straddling column k is mixed
 
+// ---- what the dispatchers below share -----------------------------------------------------------------------------------------
+inline int check_sizes(int b, int nv, int c, int k) { return (b < 0 || nv < 0 || c < 0 || k < 0 || k > c) ? GEOM_EINVAL : 0; }
+
+// What a backward needs beyond its operands: the forward output wherever an activation's derivative is read from it
+// (has_saved: `saved`, or the sign mask on the route that has one), and scratch for the bias gradient's partials.
+template <bool BACKWARD>
+int check_gradient_operands(int act, bool has_saved, const float *grad_bias, const float *scratch)
+{
+    return ((BACKWARD && act != ACT_NONE && !has_saved) || (grad_bias && !scratch)) ? GEOM_EINVAL : 0;
+}
+
+// After an aggregation launch: a backward that left `blocks` rows of column-sum partials reduces them into grad_bias in fixed
+// order.  grad_bias == null: the partials stay un-reduced (geom_colsum_batch_f32 finishes them at the end of the pass).
+inline int finish_launch(bool backward, int64_t blocks, int c, const float *partial, float *grad_bias, hipStream_t s)
+{
+    if (backward && partial && grad_bias)
+        hipLaunchKernelGGL(colsum_final_kernel, dim3((c + CS_COLS - 1) / CS_COLS), dim3(CS_COLS * CS_LANES), 0, s, (int)blocks, c,
+                           partial, grad_bias);
+    return geom::launch_status();
+}
+
 template <int VEC, bool BACKWARD>
 int launch(const GcnArgs &a, int act, float *colsum_partial, float *grad_bias, void *stream)
 {
@@ -278,10 +299,7 @@ int launch(const GcnArgs &a, int act, float *colsum_partial, float *grad_bias, v
     case ACT_ELU: hipLaunchKernelGGL((zn_aggregate_kernel<VEC, ACT_ELU, BACKWARD>), grid, block, lds, s, a, geo.groups, geo.rows_in_flight, geo.rows_per_block, colsum_partial); break;
     default: return GEOM_EINVAL;
     }
-    if (BACKWARD && colsum_partial && grad_bias) // grad_bias == null: partials only (geom_colsum_batch_f32 finishes them)
-        hipLaunchKernelGGL(colsum_final_kernel, dim3((a.c + CS_COLS - 1) / CS_COLS), dim3(CS_COLS * CS_LANES), 0, s,
-                           (int)geo.blocks, a.c, colsum_partial, grad_bias);
-    return geom::launch_status();
+    return finish_launch(BACKWARD, geo.blocks, a.c, colsum_partial, grad_bias, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -538,40 +556,56 @@ __global__ __launch_bounds__(GCN_THREADS) void zn_aggregate_ell_kernel(EllArgs a
     }
 }
 
-inline int ell_rows_per_block(int k) { return GCN_THREADS / (k >> 2); }
-inline int ell_nc(int c, int k) { return (k > 0 && k % 4 == 0 && c % k == 0) ? c / k - 1 : -1; }
-inline bool ell_supported(int c, int k, int w)
+// Which table kernel takes a shape (asked by the dispatcher and the two size functions): none = the CSR kernel at the top; the
+// kernel above at split 3 (the one with the sign mask and the head) / split 10; zn_aggregate_ell_any_kernel below, any width.
+enum EllRoute { ELL_NONE, ELL_FAST3, ELL_FAST10, ELL_ANY };
+
+inline int ell_any_vec(int c) { return c % 4 == 0 ? 4 : c % 2 == 0 ? 2 : 1; }
+inline int ell_nc(int c, int k) { return (k > 0 && k % 4 == 0 && c % k == 0) ? c / k - 1 : -1; } // pass-through float4s per aggregated one
+
+inline EllRoute ell_route(int c, int k, int w)
 {
+    if (w != 8 && w != 16) return ELL_NONE;
     const int nc = ell_nc(c, k);
-    return (nc == 2 || nc == 9) && (w == 8 || w == 16) && (k >> 2) <= GCN_THREADS;
+    if ((nc == 2 || nc == 9) && (k >> 2) <= GCN_THREADS) return nc == 2 ? ELL_FAST3 : ELL_FAST10;
+    return (c > 0 && c / ell_any_vec(c) <= GCN_THREADS) ? ELL_ANY : ELL_NONE;
+}
+
+// rows of one tile (a thread per aggregated float4 of a row), row tiles per workgroup, workgroups per mesh, chunks * meshes
+struct EllGeometry { int rows_per_block, iters, chunks; int64_t blocks; };
+
+inline EllGeometry ell_geometry(int b, int nv, int k, bool backward)
+{
+    EllGeometry g;
+    g.rows_per_block = GCN_THREADS / (k >> 2);
+    // row tiles per workgroup (measured at the BASELINE shard, us: forward 8.1 / 8.4 / 9.2 / 11.1 for 1-4 tiles --
+    // one row per thread keeps the most loads in flight; backward incl. the bias reduction 14.6 / 12.8 / 13.7 / 14.8)
+    g.iters = backward ? 2 : 1;
+    g.chunks = (nv + g.rows_per_block * g.iters - 1) / (g.rows_per_block * g.iters);
+    g.blocks = (int64_t)g.chunks * b;
+    return g;
+}
+
+template <int ACT, bool BACKWARD, int NC, bool MASK = false, bool HEAD = false> // the table width as a template argument
+void launch_ell_w(const EllArgs &a, int w, const EllGeometry &geo, dim3 grid, size_t lds, hipStream_t s, float *partial)
+{
+    if (w == 8) hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 8, NC, MASK, HEAD>), grid, dim3(GCN_THREADS), lds, s, a, geo.rows_per_block, geo.iters, partial);
+    else hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 16, NC, MASK, HEAD>), grid, dim3(GCN_THREADS), lds, s, a, geo.rows_per_block, geo.iters, partial);
 }
 
 template <int ACT, bool BACKWARD>
-void launch_ell_shape(const EllArgs &a, int w, dim3 grid, size_t lds, hipStream_t s, int rpb, int iters, float *partial)
+void launch_ell_shape(const EllArgs &a, int w, int nc, const EllGeometry &geo, dim3 grid, size_t lds, hipStream_t s, float *partial)
 {
-    const dim3 block(GCN_THREADS);
-    const int nc = ell_nc(a.c, a.k);
     if (a.head_in) { // dispatch_ell admits it for split 3 with ReLU + mask or without activation only
-        if constexpr (ACT == ACT_RELU) {
-            if (w == 8) hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 8, 2, true, true>), grid, block, lds, s, a, rpb, iters, partial);
-            else hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 16, 2, true, true>), grid, block, lds, s, a, rpb, iters, partial);
-        } else if constexpr (ACT == ACT_NONE) {
-            if (w == 8) hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 8, 2, false, true>), grid, block, lds, s, a, rpb, iters, partial);
-            else hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 16, 2, false, true>), grid, block, lds, s, a, rpb, iters, partial);
-        }
+        if constexpr (ACT == ACT_RELU) launch_ell_w<ACT, BACKWARD, 2, true, true>(a, w, geo, grid, lds, s, partial);
+        else if constexpr (ACT == ACT_NONE) launch_ell_w<ACT, BACKWARD, 2, false, true>(a, w, geo, grid, lds, s, partial);
         return;
     }
     if constexpr (ACT == ACT_RELU) {
-        if (a.mask && nc == 2) {
-            if (w == 8) hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 8, 2, true>), grid, block, lds, s, a, rpb, iters, partial);
-            else hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 16, 2, true>), grid, block, lds, s, a, rpb, iters, partial);
-            return;
-        }
+        if (a.mask && nc == 2) return launch_ell_w<ACT, BACKWARD, 2, true>(a, w, geo, grid, lds, s, partial);
     }
-    if (w == 8 && nc == 2) hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 8, 2>), grid, block, lds, s, a, rpb, iters, partial);
-    else if (w == 16 && nc == 2) hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 16, 2>), grid, block, lds, s, a, rpb, iters, partial);
-    else if (w == 8 && nc == 9) hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 8, 9>), grid, block, lds, s, a, rpb, iters, partial);
-    else hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 16, 9>), grid, block, lds, s, a, rpb, iters, partial);
+    if (nc == 2) launch_ell_w<ACT, BACKWARD, 2>(a, w, geo, grid, lds, s, partial);
+    else launch_ell_w<ACT, BACKWARD, 9>(a, w, geo, grid, lds, s, partial);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -739,9 +773,6 @@ __global__ __launch_bounds__(GCN_THREADS) void zn_aggregate_ell_any_kernel(EllAr
     }
 }
 
-inline int ell_any_vec(int c) { return c % 4 == 0 ? 4 : c % 2 == 0 ? 2 : 1; }
-inline bool ell_any_supported(int c, int w) { return (w == 8 || w == 16) && c > 0 && c / ell_any_vec(c) <= GCN_THREADS; }
-
 inline GcnGeometry ell_any_geometry(int b, int nv, int c, bool backward)
 {
     GcnGeometry g;
@@ -776,92 +807,71 @@ void launch_ell_any_vec(const EllArgs &a, int w, const GcnGeometry &geo, dim3 gr
     }
 }
 
-template <bool BACKWARD>
-int dispatch_ell_any(EllArgs a, int b, int w, int act, float *grad_bias, float *scratch, void *stream)
-{
-    if (!ell_any_supported(a.c, w) || a.head_in || a.mask) return GEOM_EUNSUPPORTED;
-    if (b == 0 || a.nv == 0) return 0;
-    if (!a.col || !a.val || !a.y || !a.x) return GEOM_EINVAL;
-    if (BACKWARD && act != ACT_NONE && !a.saved) return GEOM_EINVAL;
-    if (grad_bias && !scratch) return GEOM_EINVAL;
-    if (a.over_ptr && (!a.over_col || !a.over_val)) return GEOM_EINVAL;
-    // the table rows are read 16 bytes at a time; the operands VEC floats at a time (rows of c floats: VEC divides c)
-    if ((((uintptr_t)a.col | (uintptr_t)a.val) % 16) != 0) return GEOM_EINVAL;
-    if ((((uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)a.saved) % (4 * ell_any_vec(a.c))) != 0) return GEOM_EINVAL;
-    if (b > 65535) return GEOM_ETOOBIG;
-    const GcnGeometry geo = ell_any_geometry(b, a.nv, a.c, BACKWARD);
-    float *partial = scratch;
-    const size_t lds = (BACKWARD && partial) ? (size_t)geo.rows_in_flight * a.c * sizeof(float) : 0;
-    const dim3 grid((unsigned)geo.chunks, (unsigned)b);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (act) {
-    case ACT_NONE: launch_ell_any_vec<ACT_NONE, BACKWARD>(a, w, geo, grid, lds, s, partial); break;
-    case ACT_RELU: launch_ell_any_vec<ACT_RELU, BACKWARD>(a, w, geo, grid, lds, s, partial); break;
-    case ACT_ELU: launch_ell_any_vec<ACT_ELU, BACKWARD>(a, w, geo, grid, lds, s, partial); break;
-    default: return GEOM_EINVAL;
-    }
-    if (BACKWARD && partial && grad_bias)
-        hipLaunchKernelGGL(colsum_final_kernel, dim3((a.c + CS_COLS - 1) / CS_COLS), dim3(CS_COLS * CS_LANES), 0, s, (int)geo.blocks, a.c,
-                           partial, grad_bias);
-    return geom::launch_status();
-}
-
+// The table kernels' dispatcher.  Its checks are the CSR dispatcher's with the table's own in between; where the two differ:
+// c == 0 has no route here (only the CSR dispatcher calls that shape empty), relu' comes from the sign mask where there is one,
+// the fast kernel reads its bias as float4s too, and the mesh axis is checked before the geometry (it does not depend on it).
 template <bool BACKWARD>
 int dispatch_ell(EllArgs a, int b, int w, int act, float *grad_bias, float *scratch, void *stream)
 {
-    if (b < 0 || a.nv < 0 || a.c < 0 || a.k < 0 || a.k > a.c) return GEOM_EINVAL;
-    if (!ell_supported(a.c, a.k, w)) return dispatch_ell_any<BACKWARD>(a, b, w, act, grad_bias, scratch, stream); // any width / split
+    if (const int code = check_sizes(b, a.nv, a.c, a.k)) return code;
+    const EllRoute route = ell_route(a.c, a.k, w);
+    const bool fast = route == ELL_FAST3 || route == ELL_FAST10;
+    if (route == ELL_NONE || (!fast && (a.head_in || a.mask))) return GEOM_EUNSUPPORTED; // head and sign mask: the fast kernel's
     if (b == 0 || a.nv == 0) return 0;
     if (!a.col || !a.val || !a.y || (!a.x && !(BACKWARD && a.head_in))) return GEOM_EINVAL;
-    if (a.head_in) { // head mode: split 3, ReLU with the sign mask or no activation; the forward also needs head_out
-        if (ell_nc(a.c, a.k) != 2 || !((act == ACT_RELU && a.mask) || act == ACT_NONE) || (!BACKWARD && !a.head_out))
-            return GEOM_EUNSUPPORTED;
-    }
-    if (a.mask && !(act == ACT_RELU && ell_nc(a.c, a.k) == 2)) return GEOM_EINVAL; // sign mask: ReLU, split 3 only
-    if (BACKWARD && act != ACT_NONE && !a.saved && !a.mask) return GEOM_EINVAL;
-    if (grad_bias && !scratch) return GEOM_EINVAL;
+    // head mode: split 3, ReLU with the sign mask or no activation; the forward also needs head_out
+    if (a.head_in && (route != ELL_FAST3 || !((act == ACT_RELU && a.mask) || act == ACT_NONE) || (!BACKWARD && !a.head_out)))
+        return GEOM_EUNSUPPORTED;
+    if (a.mask && !(act == ACT_RELU && route == ELL_FAST3)) return GEOM_EINVAL; // sign mask: ReLU, split 3 only
+    if (const int code = check_gradient_operands<BACKWARD>(act, a.saved || a.mask, grad_bias, scratch)) return code;
     if (a.over_ptr && (!a.over_col || !a.over_val)) return GEOM_EINVAL;
-    if ((((uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)a.saved | (uintptr_t)a.bias | (uintptr_t)a.col | (uintptr_t)a.val) % 16) != 0)
+    // the table rows are read 16 bytes at a time; the operands as float4s, or (any width) VEC floats at a time: VEC divides c
+    if ((((uintptr_t)a.col | (uintptr_t)a.val) % 16) != 0) return GEOM_EINVAL;
+    if ((((uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)a.saved | (uintptr_t)(fast ? a.bias : nullptr)) % (fast ? 16 : 4 * ell_any_vec(a.c))) != 0)
         return GEOM_EINVAL;
     if (b > 65535) return GEOM_ETOOBIG;
-    const int rpb = ell_rows_per_block(a.k);
-    // row tiles per workgroup (measured at the BASELINE shard, us: forward 8.1 / 8.4 / 9.2 / 11.1 for 1-4 tiles --
-    // one row per thread keeps the most loads in flight; backward incl. the bias reduction 14.6 / 12.8 / 13.7 / 14.8)
-    const int iters = BACKWARD ? 2 : 1;
-    const int chunks = (a.nv + rpb * iters - 1) / (rpb * iters);
     float *partial = scratch; // with grad_bias == null the partials stay un-reduced (geom_colsum_batch_f32 finishes them)
-    const size_t lds = (BACKWARD && partial) ? (size_t)rpb * a.c * sizeof(float) : 0;
-    a.b = b;
-    a.chunks = chunks;
-    dim3 grid(geom::xcd_grid(b, chunks));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!fast) {
+        const GcnGeometry geo = ell_any_geometry(b, a.nv, a.c, BACKWARD);
+        const size_t lds = (BACKWARD && partial) ? (size_t)geo.rows_in_flight * a.c * sizeof(float) : 0;
+        const dim3 grid((unsigned)geo.chunks, (unsigned)b);
+        switch (act) {
+        case ACT_NONE: launch_ell_any_vec<ACT_NONE, BACKWARD>(a, w, geo, grid, lds, s, partial); break;
+        case ACT_RELU: launch_ell_any_vec<ACT_RELU, BACKWARD>(a, w, geo, grid, lds, s, partial); break;
+        case ACT_ELU: launch_ell_any_vec<ACT_ELU, BACKWARD>(a, w, geo, grid, lds, s, partial); break;
+        default: return GEOM_EINVAL;
+        }
+        return finish_launch(BACKWARD, geo.blocks, a.c, partial, grad_bias, s);
+    }
+    const EllGeometry geo = ell_geometry(b, a.nv, a.k, BACKWARD);
+    const size_t lds = (BACKWARD && partial) ? (size_t)geo.rows_per_block * a.c * sizeof(float) : 0;
+    a.b = b, a.chunks = geo.chunks;
+    const dim3 grid(geom::xcd_grid(b, geo.chunks));
+    const int nc = route == ELL_FAST3 ? 2 : 9;
     switch (act) {
-    case ACT_NONE: launch_ell_shape<ACT_NONE, BACKWARD>(a, w, grid, lds, s, rpb, iters, partial); break;
-    case ACT_RELU: launch_ell_shape<ACT_RELU, BACKWARD>(a, w, grid, lds, s, rpb, iters, partial); break;
-    case ACT_ELU: launch_ell_shape<ACT_ELU, BACKWARD>(a, w, grid, lds, s, rpb, iters, partial); break;
+    case ACT_NONE: launch_ell_shape<ACT_NONE, BACKWARD>(a, w, nc, geo, grid, lds, s, partial); break;
+    case ACT_RELU: launch_ell_shape<ACT_RELU, BACKWARD>(a, w, nc, geo, grid, lds, s, partial); break;
+    case ACT_ELU: launch_ell_shape<ACT_ELU, BACKWARD>(a, w, nc, geo, grid, lds, s, partial); break;
     default: return GEOM_EINVAL;
     }
-    if (BACKWARD && partial && grad_bias)
-        hipLaunchKernelGGL(colsum_final_kernel, dim3((a.c + CS_COLS - 1) / CS_COLS), dim3(CS_COLS * CS_LANES), 0, s,
-                           chunks * b, a.c, partial, grad_bias);
-    return geom::launch_status();
+    return finish_launch(BACKWARD, geo.blocks, a.c, partial, grad_bias, s);
 }
 
 template <bool BACKWARD>
 int dispatch(GcnArgs a, int b, int act, float *grad_bias, float *scratch, void *stream)
 {
-    if (b < 0 || a.nv < 0 || a.c < 0 || a.k < 0 || a.k > a.c) return GEOM_EINVAL;
+    if (const int code = check_sizes(b, a.nv, a.c, a.k)) return code;
     if (b == 0 || a.nv == 0 || a.c == 0) return 0;
     if (!a.rowptr || !a.x || !a.y || (a.k > 0 && (!a.col || !a.val))) return GEOM_EINVAL;
-    if (BACKWARD && act != ACT_NONE && !a.saved) return GEOM_EINVAL;
-    if (grad_bias && !scratch) return GEOM_EINVAL;
+    if (const int code = check_gradient_operands<BACKWARD>(act, a.saved != nullptr, grad_bias, scratch)) return code;
     a.rows = (int64_t)b * a.nv;
-    if (gcn_vec4(a.c, a.k) && (((uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)a.saved) % 16 != 0))
-        return GEOM_EINVAL; // row-major fp32 tensors from any allocator are 16-byte aligned; refuse odd views
     const bool vec4 = gcn_vec4(a.c, a.k);
-    float *partial = scratch;
+    if (vec4 && (((uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)a.saved) % 16 != 0))
+        return GEOM_EINVAL; // row-major fp32 tensors from any allocator are 16-byte aligned; refuse odd views
     if (!vec4 && a.c > GCN_THREADS) return GEOM_ETOOBIG;
-    return vec4 ? launch<4, BACKWARD>(a, act, partial, grad_bias, stream) : launch<1, BACKWARD>(a, act, partial, grad_bias, stream);
+    // (the mesh axis is checked in launch(), next to the block count)
+    return vec4 ? launch<4, BACKWARD>(a, act, scratch, grad_bias, stream) : launch<1, BACKWARD>(a, act, scratch, grad_bias, stream);
 }
 
 } // namespace
@@ -888,12 +898,10 @@ extern "C" int64_t geom_zn_gcn_bwd_scratch_floats(int b, int nv, int c)
 extern "C" int64_t geom_zn_gcn_bwd_partial_rows(int b, int nv, int c, int k, int ell_w)
 {
     if (b <= 0 || nv <= 0 || c <= 0 || k < 0 || k > c) return 0;
-    if (ell_w) {
-        if (!ell_supported(c, k, ell_w)) return ell_any_supported(c, ell_w) ? ell_any_geometry(b, nv, c, true).blocks : 0;
-        const int per = ell_rows_per_block(k) * 2; // two row tiles per workgroup in the backward
-        return (int64_t)((nv + per - 1) / per) * b;
-    }
-    return gcn_geometry(b, nv, c, gcn_vec4(c, k) ? 4 : 1, true).blocks;
+    if (!ell_w) return gcn_geometry(b, nv, c, gcn_vec4(c, k) ? 4 : 1, true).blocks;
+    const EllRoute route = ell_route(c, k, ell_w);
+    if (route == ELL_ANY) return ell_any_geometry(b, nv, c, true).blocks;
+    return route == ELL_NONE ? 0 : ell_geometry(b, nv, k, true).blocks;
 }
 
 extern "C" int geom_colsum_batch_f32(int count, const float *const *partials, const int *rows, const int *cols,
@@ -928,7 +936,8 @@ extern "C" int geom_zn_gcn_aggregate_ell_fwd_f32(int b, int nv, int c, int k, in
                                                  const float *over_val, const float *support, const float *bias,
                                                  int act, float *out, uint16_t *relu_mask, void *stream)
 {
-    EllArgs a{ell_col, ell_val, support, bias, nullptr, out, nv, c, k, relu_mask, over_ptr, over_col, over_val};
+    EllArgs a{.col = ell_col, .val = ell_val, .x = support, .bias = bias, .y = out, .nv = nv, .c = c, .k = k, .mask = relu_mask,
+              .over_ptr = over_ptr, .over_col = over_col, .over_val = over_val};
     return dispatch_ell<false>(a, b, w, act, nullptr, nullptr, stream);
 }
 
@@ -939,13 +948,16 @@ extern "C" int geom_zn_gcn_aggregate_ell_head_fwd_f32(int b, int nv, int c, int 
                                                       float scale, float *pos, void *stream)
 {
     if (!base || !pos) return GEOM_EINVAL;
-    EllArgs a{ell_col, ell_val, support, bias, nullptr, out, nv, c, k, relu_mask, over_ptr, over_col, over_val, 0, 0, base, pos, scale};
+    EllArgs a{.col = ell_col, .val = ell_val, .x = support, .bias = bias, .y = out, .nv = nv, .c = c, .k = k, .mask = relu_mask,
+              .over_ptr = over_ptr, .over_col = over_col, .over_val = over_val, .head_in = base, .head_out = pos, .head_scale = scale};
     return dispatch_ell<false>(a, b, w, act, nullptr, nullptr, stream);
 }
 
+// Words of the ReLU sign mask: a property of the split alone, not of the route (either table width has the mask; beyond the fast
+// kernel's 1024 aggregated columns the words are still counted, and the dispatcher refuses the mask).  0: no mask at this split.
 extern "C" int64_t geom_zn_gcn_relu_mask_words(int b, int nv, int c, int k)
 {
-    if (b <= 0 || nv <= 0 || ell_nc(c, k) != 2) return 0; // 0: this shape has no mask path
+    if (b <= 0 || nv <= 0 || ell_nc(c, k) != 2) return 0;
     return (int64_t)b * nv * (k >> 2);
 }
 
@@ -955,8 +967,8 @@ extern "C" int geom_zn_gcn_aggregate_ell_bwd_f32(int b, int nv, int c, int k, in
                                                  const uint16_t *relu_mask, int act, float *grad_support,
                                                  float *grad_bias, float *scratch, void *stream)
 {
-    EllArgs a{ell_colT, ell_valT, grad_out, nullptr, out, grad_support, nv, c, k, const_cast<uint16_t *>(relu_mask),
-              over_ptrT, over_colT, over_valT};
+    EllArgs a{.col = ell_colT, .val = ell_valT, .x = grad_out, .saved = out, .y = grad_support, .nv = nv, .c = c, .k = k,
+              .mask = const_cast<uint16_t *>(relu_mask), .over_ptr = over_ptrT, .over_col = over_colT, .over_val = over_valT};
     return dispatch_ell<true>(a, b, w, act, grad_bias, scratch, stream);
 }
 
@@ -967,7 +979,7 @@ extern "C" int geom_zn_gcn_aggregate_ell_head_bwd_f32(int b, int nv, int c, int 
                                                       float *grad_bias, float *scratch, void *stream)
 {
     if (!grad_pos) return GEOM_EINVAL;
-    EllArgs a{ell_colT, ell_valT, nullptr, nullptr, nullptr, grad_support, nv, c, k, const_cast<uint16_t *>(relu_mask),
-              over_ptrT, over_colT, over_valT, 0, 0, grad_pos, nullptr, scale};
+    EllArgs a{.col = ell_colT, .val = ell_valT, .y = grad_support, .nv = nv, .c = c, .k = k, .mask = const_cast<uint16_t *>(relu_mask),
+              .over_ptr = over_ptrT, .over_col = over_colT, .over_val = over_valT, .head_in = grad_pos, .head_scale = scale};
     return dispatch_ell<true>(a, b, w, act, grad_bias, scratch, stream);
 }

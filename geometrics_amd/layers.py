@@ -5,8 +5,8 @@ and initialisers (reference layers.py:14-189), so `models.py` and pretrained sta
 `forward(input, adj, activation)` still receives the DENSE [V,V] adjacency the callers pass
 (models.py:241, GEOMetrics.py:120).  The layer derives CSR and CSR^T from it once (cached on
 the tensor's identity + version) and replaces the reference's dense `adj @ support[..., :k]`,
-`torch.cat` and bias add by one fused HIP kernel (csrc/zn_gcn.hip); the dense feature GEMM
-`input @ W` stays a library GEMM (rocBLAS/hipBLASLt through torch.matmul).
+`torch.cat` and bias add by one fused HIP kernel (csrc/zn_gcn.hip, launched by `aggregation.py`); which
+kernel computes the feature product `input @ W` and its gradients is `products.route()`'s decision.
 """
 import math
 import weakref
@@ -18,6 +18,7 @@ from torch.nn import Module
 from torch.nn.parameter import Parameter
 
 from . import _lib
+from . import aggregation as _agg
 from . import backward_pass as _pass
 from . import fused as _fused
 from . import products as _products
@@ -26,8 +27,9 @@ from .backward_pass import (_alias, _gradient_buffer, bind_gradient_targets, def
                             late_input_gradients)
 # (the layers' dense products; the flags that steer them are set on geometrics_amd.products, not here)
 from .products import _dense, _new_like, current_slabs, weight_gradient_batching  # noqa: F401
-
-_ACT_NONE, _ACT_RELU, _ACT_ELU = 0, 1, 2
+# (the aggregation's launches; tools and tests call the two launchers under these names)
+from .aggregation import ACT_ELU as _ACT_ELU, ACT_NONE as _ACT_NONE, ACT_RELU as _ACT_RELU  # noqa: F401
+from .aggregation import activation_code as _activation_code, backward as aggregate_backward, forward as aggregate_forward  # noqa: F401
 
 
 # --------------------------------------------------------------- CSR cache ----
@@ -137,75 +139,26 @@ def adjacency_csr(adj):
 
 
 # ------------------------------------------------------- fused aggregation ----
-def _activation_code(activation):
-    """ReLU / ELU(alpha=1) are folded into the kernel epilogue (and their derivative into the
-    backward read); any other callable is applied by the caller after an un-activated kernel."""
-    if activation is F.relu or activation is torch.relu:
-        return _ACT_RELU
-    if activation is F.elu:
-        return _ACT_ELU
-    return _ACT_NONE
+def _route(activation, t, adj, any_input=False):
+    """(activation, the tensor an entry below is given, adj) -> the kernel's activation code; `foreign`: a callable the kernels do
+    not know, applied by the caller afterwards; `batched`: an fp32 [B,V,C] device tensor with ONE adjacency, what the head and the
+    boundary launches take; the CSR, built for a batched input only unless `any_input` (zero_n_aggregate: everything but a dense
+    adjacency per mesh, [B,V,V], which has none and takes the torch path)."""
+    act = _ACT_NONE if activation is None else _activation_code(activation)
+    per_mesh = torch.is_tensor(adj) and adj.dim() == 3
+    batched = torch.is_tensor(t) and t.dim() == 3 and t.is_cuda and t.dtype == torch.float32 and not per_mesh
+    csr = adjacency_csr(adj) if batched or (any_input and not per_mesh) else None
+    return act, activation is not None and act == _ACT_NONE, batched, csr
 
 
-def aggregate_forward(s, bias_c, csr, k, act, out, want_mask=False):
-    """Launch out = act([A . s[..., :k] | s[..., k:]] + bias) on contiguous fp32 [B,V,C] tensors: the fixed-stride table
-    kernel when the adjacency has one (bounded degrees; long rows continue in its CSR tail), the generic CSR kernel
-    otherwise.  Returns the ReLU sign mask when one was asked for and written."""
-    b, nv, c = s.shape
-    mask = None
-    with torch.cuda.device(s.device):
-        code = _lib.EUNSUPPORTED
-        if csr.ell_w:   # bounded-degree mesh: fixed-stride neighbour table, no rowptr round trip
-            if want_mask and act == _ACT_RELU:
-                # one sign bit per output element: the backward takes relu' from it instead of re-reading `out`
-                words = _lib.lib().geom_zn_gcn_relu_mask_words(b, nv, c, k)
-                if words:
-                    mask = torch.empty(words, dtype=torch.int16, device=s.device)
-            over = csr.over or (None, None, None)
-            code = _lib.lib().geom_zn_gcn_aggregate_ell_fwd_f32(
-                b, nv, c, k, csr.ell_w, csr.ell_col.data_ptr(), csr.ell_val.data_ptr(), _lib.ptr(over[0]),
-                _lib.ptr(over[1]), _lib.ptr(over[2]), s.data_ptr(),
-                _lib.ptr(bias_c), act, out.data_ptr(), _lib.ptr(mask), _lib.stream_ptr())
-            if code == _lib.EUNSUPPORTED:
-                mask = None
-        if code == _lib.EUNSUPPORTED:
-            _lib.call("geom_zn_gcn_aggregate_fwd_f32", b, nv, c, k, csr.rowptr.data_ptr(), csr.col.data_ptr(),
-                      csr.val.data_ptr(), s.data_ptr(), _lib.ptr(bias_c), act, out.data_ptr())
-        else:
-            _lib.check(code, "geom_zn_gcn_aggregate_ell_fwd_f32")
-    return mask
+def _split_k(support, layer):
+    return support.shape[-1] // layer.split        # the leading columns of a layer's support that are aggregated
 
 
-
-def aggregate_backward(g, csr, k, act, out, mask, want_bias, bias=None, arena=None):
-    """grad_support = [A^T . g'[..., :k] | g'[..., k:]] with g' = g * act'(out) (relu' from the sign mask when there is
-    one), and the bias gradient = column sums of g' out of the same launch (+ a fixed-order reduction: at once, or -- given
-    the bias parameter, inside a backward pass -- batched at the end of the pass: geometrics_amd.backward_pass)."""
-    b, nv, c = g.shape
-    grad_support = _new_like(g, "grad_support", arena, descending=True)
-    # column sums of g come out of the same kernel (per-block partials + fixed-order reduce)
-    bg = _pass.bias_gradient(bias, c, g.device, _lib.lib().geom_zn_gcn_bwd_scratch_floats(b, nv, c),
-                             opted_in=arena is not None) if want_bias else _pass.NO_BIAS_GRADIENT
-    with torch.cuda.device(g.device):
-        code = _lib.EUNSUPPORTED
-        ell_w = csr.ell_w
-        if ell_w:
-            over = csr.over_t or (None, None, None)
-            code = _lib.lib().geom_zn_gcn_aggregate_ell_bwd_f32(
-                b, nv, c, k, ell_w, csr.ell_col_t.data_ptr(), csr.ell_val_t.data_ptr(), _lib.ptr(over[0]),
-                _lib.ptr(over[1]), _lib.ptr(over[2]), g.data_ptr(),
-                _lib.ptr(out), _lib.ptr(mask), act, grad_support.data_ptr(), _lib.ptr(bg.now), _lib.ptr(bg.scratch),
-                _lib.stream_ptr())
-        if code == _lib.EUNSUPPORTED:
-            ell_w = 0
-            _lib.call("geom_zn_gcn_aggregate_bwd_f32", b, nv, c, k, csr.rowptr_t.data_ptr(),
-                      csr.col_t.data_ptr(), csr.val_t.data_ptr(), g.data_ptr(), _lib.ptr(out), act,
-                      grad_support.data_ptr(), _lib.ptr(bg.now), _lib.ptr(bg.scratch))
-        else:
-            _lib.check(code, "geom_zn_gcn_aggregate_ell_bwd_f32")
-    if bg.defer:
-        bg.finish(int(_lib.lib().geom_zn_gcn_bwd_partial_rows(b, nv, c, k, ell_w)))
-    return grad_support, bg.out
+def _bias_for(ctx):
+    """(a bias gradient is wanted, the bias parameter) of a node that kept `bias_ref` in its forward."""
+    wanted = ctx.needs_input_grad[1] and ctx.bias_ref is not None
+    return wanted, (ctx.bias_ref() if wanted else None)
 
 
 class _ZeroNAggregate(torch.autograd.Function):
@@ -220,8 +173,8 @@ class _ZeroNAggregate(torch.autograd.Function):
         bias_c = None if bias is None else _lib.require(bias, "bias", torch.float32, 1)
         ctx.arena = current_slabs()
         out = _new_like(s, "aggregated", ctx.arena)
-        mask = aggregate_forward(s, bias_c, csr, k, act, out, want_mask=support.requires_grad)
-        ctx.csr, ctx.k, ctx.act, ctx.has_bias = csr, k, act, bias is not None
+        mask = _agg.forward(s, bias_c, csr, k, act, out, want_mask=support.requires_grad)
+        ctx.csr, ctx.k, ctx.act = csr, k, act
         ctx.bias_ref = _pass.parameter_ref(bias, ctx, ctx.needs_input_grad[1])
         ctx.masked = mask is not None
         if mask is not None:
@@ -232,13 +185,10 @@ class _ZeroNAggregate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        g = grad_out.contiguous()
-        act = ctx.act
         mask = ctx.saved_tensors[0] if ctx.masked else None
-        out = ctx.saved_tensors[0] if (act != _ACT_NONE and not ctx.masked) else None
-        grad_support, grad_bias = aggregate_backward(g, ctx.csr, ctx.k, act, out, mask,
-                                                     ctx.has_bias and ctx.needs_input_grad[1],
-                                                     ctx.bias_ref() if ctx.bias_ref is not None else None, ctx.arena)
+        out = ctx.saved_tensors[0] if (ctx.act != _ACT_NONE and not ctx.masked) else None
+        grad_support, grad_bias = _agg.backward(grad_out.contiguous(), ctx.csr, ctx.k, ctx.act, out, mask, *_bias_for(ctx),
+                                                arena=ctx.arena)
         return (grad_support if ctx.needs_input_grad[0] else None), grad_bias, None, None, None
 
 
@@ -254,19 +204,10 @@ class _ZeroNAggregateHead(torch.autograd.Function):
         s = _lib.require(support, "support", torch.float32, 3)
         base_c = _lib.require(base, "base", torch.float32, 3, 3)
         ctx.down = down        # a _StackLink: the boundary launch that produced `support` (zero_n_stack_positions)
-        b, nv, c = s.shape
         bias_c = None if bias is None else _lib.require(bias, "bias", torch.float32, 1)
-        out = torch.empty_like(s)
         pos = torch.empty_like(base_c)
-        mask = None
-        if act == _ACT_RELU:
-            mask = torch.empty(_lib.lib().geom_zn_gcn_relu_mask_words(b, nv, c, k), dtype=torch.int16, device=s.device)
-        over = csr.over or (None, None, None)
-        with torch.cuda.device(s.device):
-            _lib.call("geom_zn_gcn_aggregate_ell_head_fwd_f32", b, nv, c, k, csr.ell_w, csr.ell_col.data_ptr(),
-                      csr.ell_val.data_ptr(), _lib.ptr(over[0]), _lib.ptr(over[1]), _lib.ptr(over[2]), s.data_ptr(),
-                      _lib.ptr(bias_c), act, out.data_ptr(), _lib.ptr(mask), base_c.data_ptr(), float(scale), pos.data_ptr())
-        ctx.csr, ctx.k, ctx.act, ctx.scale, ctx.shape = csr, k, act, float(scale), (b, nv, c)
+        mask = _agg.forward(s, bias_c, csr, k, act, torch.empty_like(s), want_mask=True, head=(base_c, scale, pos))
+        ctx.csr, ctx.k, ctx.act, ctx.scale, ctx.shape = csr, k, act, float(scale), tuple(s.shape)
         ctx.bias_ref = _pass.parameter_ref(bias, ctx, ctx.needs_input_grad[1])
         if mask is not None:
             ctx.save_for_backward(mask)
@@ -276,74 +217,40 @@ class _ZeroNAggregateHead(torch.autograd.Function):
     def backward(ctx, grad_pos):
         gp = grad_pos.contiguous()
         b, nv, c = ctx.shape
-        csr, k = ctx.csr, ctx.k
         mask = ctx.saved_tensors[0] if ctx.saved_tensors else None
-        grad_support = torch.empty(b, nv, c, dtype=torch.float32, device=gp.device)
-        down = ctx.down
-        # (the launch below takes THIS layer's aggregation backward: it must be a shape the boundary kernel serves -- 192 wide,
-        # k = 64, table width 8 without long rows -- and `wt` the transposed weight of a 192-row product; else: the separate operators)
-        fused = (down is not None and down.wt is not None and down.wanted and ctx.needs_input_grad[0]
-                 and _fused.plan(b * nv)["bwd"] and down.wt.dim() == 2 and down.wt.shape[0] == c
-                 and _fused.supported(csr, c, k, down.wt.shape[1]))
-        rows = _fused.partial_rows(b, nv) if fused else None
-        bg = _pass.NO_BIAS_GRADIENT
-        if ctx.needs_input_grad[1] and ctx.bias_ref is not None:
-            scratch = (rows, c) if fused else _lib.lib().geom_zn_gcn_bwd_scratch_floats(b, nv, c)
-            bg = _pass.bias_gradient(ctx.bias_ref(), c, gp.device, scratch)
-        if fused:
-            # this aggregation backward AND the input gradient of the product below it in one launch (csrc/zn_stack.hip);
-            # the boundary below picks its input gradient up from the link instead of computing it
-            _fused.layer_backward(None, None, mask, csr, k, ctx.act, down.wt, g_out=grad_support, grad_in=down.take_dx(b, nv),
-                                  colsum_partial=bg.scratch, grad_pos=gp, head_scale=ctx.scale, shape=(b, nv, c))
-            down.stamp(grad_support)
-            bg.finish(rows)
-            return grad_support, bg.out, (gp if ctx.needs_input_grad[2] else None), None, None, None, None, None
-        over = csr.over_t or (None, None, None)
-        with torch.cuda.device(gp.device):
-            _lib.call("geom_zn_gcn_aggregate_ell_head_bwd_f32", b, nv, c, k, csr.ell_w, csr.ell_col_t.data_ptr(),
-                      csr.ell_val_t.data_ptr(), _lib.ptr(over[0]), _lib.ptr(over[1]), _lib.ptr(over[2]), gp.data_ptr(),
-                      ctx.scale, _lib.ptr(mask), ctx.act, grad_support.data_ptr(), _lib.ptr(bg.now), _lib.ptr(bg.scratch))
-        if bg.defer:
-            bg.finish(int(_lib.lib().geom_zn_gcn_bwd_partial_rows(b, nv, c, k, csr.ell_w)))
-        return (grad_support if ctx.needs_input_grad[0] else None), bg.out, (gp if ctx.needs_input_grad[2] else None), \
-            None, None, None, None, None
+        below = ctx.down if _agg.takes_product_below(ctx.down, ctx.csr, c, ctx.k, b * nv, ctx.needs_input_grad[0]) else None
+        grad_support, grad_bias = _agg.backward(None, ctx.csr, ctx.k, ctx.act, None, mask, *_bias_for(ctx),
+                                                head=(gp, ctx.scale, ctx.shape), below=below)
+        return (grad_support if ctx.needs_input_grad[0] else None), grad_bias, \
+            (gp if ctx.needs_input_grad[2] else None), None, None, None, None, None
 
 
 def zero_n_aggregate_head(support, adj, bias, k, activation, base, scale, down=None):
     """base + scale * zero_n_aggregate(...)[..., :3] for a [B,V,C] support: fused (see _ZeroNAggregateHead) for split-3
     layers on a bounded-degree mesh with ReLU or no activation, the two separate operators otherwise."""
-    act = _ACT_NONE if activation is None else _activation_code(activation)
-    fused = (torch.is_tensor(support) and support.dim() == 3 and support.is_cuda and support.dtype == torch.float32
-             and not (torch.is_tensor(adj) and adj.dim() == 3) and (activation is None or act == _ACT_RELU))
-    if fused:
-        csr = adjacency_csr(adj)
-        c = support.shape[-1]
-        fused = bool(csr.ell_w) and k > 0 and k % 4 == 0 and c == 3 * k
-    if not fused:
-        from .ops import VertexHead
-        return VertexHead.apply(base, zero_n_aggregate(support, adj, bias, k, activation), scale)
-    return _ZeroNAggregateHead.apply(support, bias, base, csr, k, act, scale, down)
+    act, foreign, batched, csr = _route(activation, support, adj)
+    if batched and not foreign and act != _ACT_ELU and csr.ell_w and k > 0 and k % 4 == 0 and support.shape[-1] == 3 * k:
+        return _ZeroNAggregateHead.apply(support, bias, base, csr, k, act, scale, down)
+    from .ops import VertexHead
+    return VertexHead.apply(base, zero_n_aggregate(support, adj, bias, k, activation), scale)
 
 
 def zero_n_aggregate(support, adj, bias, k, activation=None):
     """Shared tail of every 0N-GCN layer; accepts [V,C] or [B,V,C] support.  Returns the
     ACTIVATED output when `activation` is given (fused for relu / elu)."""
-    if torch.is_tensor(adj) and adj.dim() == 3:
+    act, foreign, _, csr = _route(activation, support, adj, any_input=True)
+    if csr is None:
         # one dense adjacency PER MESH ([B,V,V]): what the reference's torch.matmul(adj, support[..., :k]) also accepts
         # (layers.py:111, 146).  Not a shape the reference drivers produce; served by the same dense product.
         out = torch.cat((torch.matmul(adj, support[..., :k]), support[..., k:]), dim=-1)
         if bias is not None:
             out = out + bias
         return out if activation is None else activation(out)
-    csr = adjacency_csr(adj)
-    act = _ACT_NONE if activation is None else _activation_code(activation)
     s3 = support.unsqueeze(0) if support.dim() == 2 else support
     out = _ZeroNAggregate.apply(s3, bias, csr, k, act)
     if support.dim() == 2:
         out = out.squeeze(0)
-    if activation is not None and act == _ACT_NONE:
-        out = activation(out)
-    return out
+    return activation(out) if foreign else out
 
 
 # ---- a stack of layers with its layer BOUNDARIES as single launches (csrc/zn_stack.hip) -----------------------------------
@@ -392,13 +299,11 @@ class _FusedBoundary(torch.autograd.Function):
     @staticmethod
     def forward(ctx, support, bias, w_next, csr, k, act, up, down):
         s = _lib.require(support, "support", torch.float32, 3)
-        b, nv, c = s.shape
+        c = s.shape[-1]
         bias_c = None if bias is None else _lib.require(bias, "bias", torch.float32, 1)
         w2 = w_next.reshape(w_next.shape[-2:])
         need = any(ctx.needs_input_grad[:3])
-        mask = None
-        if need and act == _ACT_RELU:
-            mask = torch.empty(_lib.lib().geom_zn_gcn_relu_mask_words(b, nv, c, k), dtype=torch.int16, device=s.device)
+        mask = _agg.relu_mask(s, k) if need and act == _ACT_RELU else None
         if need:
             up.wt = torch.empty(w2.shape[1], c, dtype=torch.float32, device=s.device)
             up.wanted = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
@@ -419,9 +324,8 @@ class _FusedBoundary(torch.autograd.Function):
         w2 = w.reshape(w.shape[-2:])
         n_out = w2.shape[1]
         g2 = grad_next.reshape(rows, n_out).contiguous()
-        need_s, need_b, need_w = ctx.needs_input_grad[:3]
-        need_b = need_b and ctx.bias_ref is not None
-        up, down, csr, k, act = ctx.up, ctx.down, ctx.csr, ctx.k, ctx.act
+        need_s, _, need_w = ctx.needs_input_grad[:3]
+        need_b, bias = _bias_for(ctx)
         # ---- layer L+1's product: its gradients as after _dense (x is contiguous: saved by this node's forward), with dX taken from
         # the link when the launch above left it there, never postponed, and never on the any-shape kernel (the library, since
         # this product's forward was not that kernel's either)
@@ -429,56 +333,42 @@ class _FusedBoundary(torch.autograd.Function):
                                 _products.use_any_shape_products)
         if route.dx == "any":
             route = route._replace(dx="lib")
-        dx, grad_w = _products.product_gradients(x, g2, w, ctx.w_ref, route, need_s or need_b, need_w, dx=up.claim_dx(g2))
+        dx, grad_w = _products.product_gradients(x, g2, w, ctx.w_ref, route, need_s or need_b, need_w, dx=ctx.up.claim_dx(g2))
         if not (need_s or need_b):
             return None, None, grad_w, None, None, None, None, None
         # ---- layer L's aggregation: with the input gradient of ITS product in the same launch when the boundary below wants it
-        bias = ctx.bias_ref() if ctx.bias_ref is not None else None
-        out = x if (act != _ACT_NONE and mask is None) else None
-        if down is not None and down.wt is not None and down.wanted and _fused.plan(rows)["bwd"]:
-            prows = _fused.partial_rows(b, nv)
-            bg = _pass.bias_gradient(bias, c, x.device, (prows, c)) if need_b else _pass.NO_BIAS_GRADIENT
-            grad_support, _ = _fused.layer_backward(dx, out, mask, csr, k, act, down.wt, grad_in=down.take_dx(b, nv),
-                                                    colsum_partial=bg.scratch)
-            down.stamp(grad_support)
-            bg.finish(prows)
-            grad_bias = bg.out
-        else:
-            grad_support, grad_bias = aggregate_backward(dx, csr, k, act, out, mask, need_b, bias)
+        below = ctx.down if _agg.takes_product_below(ctx.down, ctx.csr, c, ctx.k, rows, need_s) else None
+        out = x if (ctx.act != _ACT_NONE and mask is None) else None
+        grad_support, grad_bias = _agg.backward(dx, ctx.csr, ctx.k, ctx.act, out, mask, need_b, bias, below=below)
         return (grad_support if need_s else None), grad_bias, grad_w, None, None, None, None, None
 
 
-def _boundary_fuses(x, csr, prev, layer, act, activation):
-    """Whether the boundary between `prev` and `layer` takes the single launch."""
+def _boundary_fuses(rows, csr, prev, layer):
+    """Whether the boundary between `prev` and `layer` takes the single launch (csr: None unless the stack's input is batched
+    and its activation one the kernels know)."""
     if not (current_slabs() is None and isinstance(csr, _Csr)):
-        return False
-    if activation is not None and act == _ACT_NONE:          # a foreign callable: applied by the caller between the operators
         return False
     w = layer._weight()
     c = prev._weight().shape[-1]
     if w.dtype != torch.float32 or w.shape[-2] != c or not w.is_contiguous() or prev.split != 3 or c % 3:
         return False
-    rows = x.numel() // x.shape[-1]
     return _fused.supported(csr, c, c // 3, w.shape[-1]) and _fused.plan(rows)["fwd"]
 
 
-def _stack_supports(x, adj, stack, head):
-    """The front of a stack up to the support of its last layer: (support, link of the last boundary, csr)."""
-    act = _ACT_NONE if head["activation"] is None else _activation_code(head["activation"])
-    activation = head["activation"]
-    batched = torch.is_tensor(x) and x.dim() == 3 and x.is_cuda and x.dtype == torch.float32 \
-        and not (torch.is_tensor(adj) and adj.dim() == 3)
-    csr = adjacency_csr(adj) if batched else None
+def _stack_supports(x, adj, stack, activation):
+    """The front of a stack up to the support of its last layer: (support, link of the last boundary)."""
+    act, foreign, _, csr = _route(activation, x, adj)
+    if foreign:          # (a foreign callable is applied between the operators)
+        csr = None
     s = _dense(x, stack[0]._weight())
     link = None
     for prev, layer in zip(stack[:-1], stack[1:]):
-        if batched and _boundary_fuses(x, csr, prev, layer, act, activation):
+        if _boundary_fuses(x.numel() // x.shape[-1], csr, prev, layer):
             up = _StackLink()
-            s = _FusedBoundary.apply(s, prev.bias, layer._weight(), csr, s.shape[-1] // prev.split, act, up, link)
+            s = _FusedBoundary.apply(s, prev.bias, layer._weight(), csr, _split_k(s, prev), act, up, link)
             link = up
         else:
-            h = zero_n_aggregate(s, adj, prev.bias, s.shape[-1] // prev.split, activation)
-            s = _dense(h, layer._weight())
+            s = _dense(zero_n_aggregate(s, adj, prev.bias, _split_k(s, prev), activation), layer._weight())
             link = None
     return s, link
 
@@ -487,14 +377,14 @@ def zero_n_stack(x, adj, stack, activation):
     """stack[-1](... stack[1](stack[0](x, adj, activation), adj, activation) ...): consecutive 0N-GCN layers applied to one
     adjacency (GEOMetrics.py:117-131 runs such runs per deformation stage), their boundaries as single launches where
     `fused.plan` says so.  Same values as calling the layers one by one."""
-    s, _ = _stack_supports(x, adj, stack, {"activation": activation})
-    return zero_n_aggregate(s, adj, stack[-1].bias, s.shape[-1] // stack[-1].split, activation)
+    s, _ = _stack_supports(x, adj, stack, activation)
+    return zero_n_aggregate(s, adj, stack[-1].bias, _split_k(s, stack[-1]), activation)
 
 
 def zero_n_stack_positions(x, adj, stack, activation, base, scale):
     """base + scale * zero_n_stack(x, adj, stack, activation)[..., :3] -- the coordinate update of a deformation stage."""
-    s, link = _stack_supports(x, adj, stack, {"activation": activation})
-    return zero_n_aggregate_head(s, adj, stack[-1].bias, s.shape[-1] // stack[-1].split, activation, base, scale, down=link)
+    s, link = _stack_supports(x, adj, stack, activation)
+    return zero_n_aggregate_head(s, adj, stack[-1].bias, _split_k(s, stack[-1]), activation, base, scale, down=link)
 
 
 def _uniform(t, bound):
@@ -511,13 +401,13 @@ class _ZeroNBase(Module):
 
     def forward(self, input, adj, activation):
         support = _dense(input, self._weight())
-        return zero_n_aggregate(support, adj, self.bias, support.shape[-1] // self.split, activation)
+        return zero_n_aggregate(support, adj, self.bias, _split_k(support, self), activation)
 
     def forward_positions(self, input, adj, activation, base, scale):
         """base + scale * self(input, adj, activation)[..., :3] -- the coordinate update of a deformation stage
         (GEOMetrics.py:121,126,131) without materialising the layer output's gradient (see zero_n_aggregate_head)."""
         support = _dense(input, self._weight())
-        return zero_n_aggregate_head(support, adj, self.bias, support.shape[-1] // self.split, activation, base, scale)
+        return zero_n_aggregate_head(support, adj, self.bias, _split_k(support, self), activation, base, scale)
 
 
 class ZERON_GCN(_ZeroNBase):
@@ -572,6 +462,7 @@ class Batch_Image_ZERON_GCNGCN(_ZeroNBase):
 
 class _MaxPoolBase(Module):
     """Aggregate like a 0N-GCN layer (split 10), then max over the vertex axis."""
+    split = 10
 
     def __init__(self, in_features, print_length):
         super().__init__()
@@ -586,7 +477,7 @@ class _MaxPoolBase(Module):
 
     def _pre_activation(self, r_s, adj):
         support = _dense(r_s, self.weight_Ws[0])
-        return zero_n_aggregate(support, adj, self.weight_Bs[0], support.shape[-1] // 10)
+        return zero_n_aggregate(support, adj, self.weight_Bs[0], _split_k(support, self))
 
 
 class GCNMax(_MaxPoolBase):
@@ -595,7 +486,7 @@ class GCNMax(_MaxPoolBase):
 
     def forward(self, r_s, adj, activation):
         support = _dense(r_s, self.weight_Ws[0])
-        acted = zero_n_aggregate(support, adj, self.weight_Bs[0], support.shape[-1] // 10, activation)
+        acted = zero_n_aggregate(support, adj, self.weight_Bs[0], _split_k(support, self), activation)
         if hasattr(adj, "offsets"):
             from .ops import SegmentMax
             return SegmentMax.apply(acted, adj.offsets, adj.max_len)

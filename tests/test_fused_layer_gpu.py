@@ -167,10 +167,10 @@ def test_the_stack_operator_uses_the_boundary_launch(gpu):
     x = torch.randn(2, nv, 48, device="cuda")
     fused.force = {"fwd": True, "bwd": True}
     try:
-        s, link = layers._stack_supports(x, csr, list(stack), {"activation": F.relu})
+        s, link = layers._stack_supports(x, csr, list(stack), F.relu)
         assert link is not None and torch.equal(link.wt, stack[-1].weight1[0].t())
         fused.force = {"fwd": False, "bwd": False}
-        s2, link2 = layers._stack_supports(x, csr, list(stack), {"activation": F.relu})
+        s2, link2 = layers._stack_supports(x, csr, list(stack), F.relu)
         assert link2 is None
     finally:
         fused.force = None
@@ -193,7 +193,7 @@ def test_the_plan_switches_the_boundary_launches_on_by_itself_at_a_large_shard(g
     from geometrics_amd import layers
     torch.manual_seed(5)
     stack = torch.nn.ModuleList([layers.Batch_Image_ZERON_GCNGCN(i, o) for i, o in ((99, C), (C, C), (C, C))]).cuda()
-    s, link = layers._stack_supports(torch.randn(b, nv, 99, device="cuda"), csr, list(stack), {"activation": F.relu})
+    s, link = layers._stack_supports(torch.randn(b, nv, 99, device="cuda"), csr, list(stack), F.relu)
     assert link is not None and link.wt is not None                         # the un-forced plan took the boundary launch
     del s, link, stack
     got_pos, got = _stack_auto(b, level, act_fn)
