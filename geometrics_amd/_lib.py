@@ -16,7 +16,7 @@ FLAG_FIX_REGION6 = 2
 FLAG_TRI_BRUTE_FORCE = 4
 FLAG_NN_FMA = 8
 FLAG_TRI_WS_READY = 16
-ABI_VERSION = 15
+ABI_VERSION = 16
 EUNSUPPORTED = -3
 ADAM_MAX_TENSORS = 64
 COLSUM_MAX_JOBS = 32
@@ -133,6 +133,8 @@ _SIGNATURES = {
     "geom_deform_chain_bwd_f32": [_i, _vp, _vp, _vp, _vp],
     "geom_deform_chain_fits": [_i],
     "geom_deform_layer_bwd_f32": [_vp, _vp],
+    "geom_deform_layer_wide_fwd_f32": [_vp, _vp],
+    "geom_deform_layer_wide_bwd_f32": [_vp, _vp],
     "geom_deform_infer_fwd_f32": [_vp, _vp],
 }
 

@@ -904,12 +904,395 @@ __global__ __launch_bounds__(DB_THREADS, 2) void di_fwd_kernel(geom_deform_infer
     for (int i = 1; i < count; ++i) di_row_block<PRODUCT, false>(a, first + i, lds, bw);
 }
 
+// ---- training batches of 17 .. GEOM_DEFORM_WIDE_MAX_B meshes (geom_deform_layer_wide_{fwd,bwd}_f32): one launch per hidden
+// layer and direction, still one workgroup per VERTEX; the vertex's b rows are T = ceil(b / 16) <= 4 row tiles of the matrix
+// core (tile t, tile row rl = mesh 16 t + rl; rows at or beyond b are zero rows of the panel and store nothing).
+//
+// Schedule of a workgroup (forward; the backward mirrors it):
+//   1. the T tiles' gathers one after the other through db_aggregate (the plain launch's order: same bits), no weight slice
+//      live yet -- a pole's 32 tail rows per tile need the registers; Z leaves for z_out and STAYS in registers (12 floats per
+//      tile, 48 at most) for both statistics passes;
+//   2. the wave's weight slice (144 registers) is requested ONCE, in front of the statistics, and serves all T products;
+//   3. the vertex's statistics over all b * 192 values: per thread over its tiles in tile order, then db_sum2 (mean; then the
+//      centred second moment) -- the tiles meet inside the workgroup, in a fixed order, no atomics;
+//   4. per tile: BatchNorm + ReLU + residual -> x_out, the panel, the product, s_out (the residual of tile t + 1 is requested
+//      before the product of tile t).
+// Backward: 1. the T tiles' gathers of dZ_up -> G (ds_up), kept in registers; 2. the slice; 3. per tile G . W_up^T through the
+// panel, the product's rows replace G in the registers (the slice is dead from here on); 4. Z and the second gradient per tile,
+// mask + the two sums over all tiles (db_sum2); 5. dZ per tile, the column sums over tiles, then lanes, then waves.
+constexpr int DBW_TILES = GEOM_DEFORM_WIDE_MAX_B / 16;
+
+template <bool PRODUCT>
+__global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd a)
+{
+    __shared__ __attribute__((aligned(16))) float lds[DB_PANEL + DB_CST + DB_RED];
+    const int v = db_vertex(blockIdx.x, a.vpx, a.nv);
+    if (v < 0) return;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = lane & 15, g = lane >> 4;
+    const int rl = tid >> 4, j = tid & 15;
+    const int c0 = 4 * j;
+    const int tiles = (a.b + 15) >> 4;
+    const int64_t op_bytes = (int64_t)a.b * a.nv * DB_C * 4;
+    const __amdgpu_buffer_rsrc_t r_src = db_rsrc(a.s_in, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_z = db_rsrc(a.z_out, op_bytes), r_x = db_rsrc(a.x_out, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_res = db_rsrc(a.res, ((int64_t)a.b * a.nv - 1) * a.res_ld * 4 + DB_C * 4);
+    // byte offset of the thread's first float4 of tile t in a [b, nv, 192] operand (DB_OOB: a row at or beyond b)
+    auto own = [&](int t) {
+        const int mesh = 16 * t + rl;
+        return mesh < a.b ? ((unsigned)mesh * (unsigned)a.nv + (unsigned)v) * (DB_C * 4) + 4 * c0 : DB_OOB;
+    };
+    auto residual = [&](int t, float4 (&rv)[3]) {
+        const int mesh = 16 * t + rl;
+        const unsigned roff = ((unsigned)mesh * (unsigned)a.nv + (unsigned)v) * (unsigned)a.res_ld * 4u + 4 * c0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) rv[i] = a.res ? db_ld4(r_res, mesh < a.b ? roff + 4 * DB_K * i : DB_OOB) : make_float4(0.f, 0.f, 0.f, 0.f);
+    };
+    const float gamma = a.bn_w ? a.bn_w[v] : 1.f, beta = a.bn_b ? a.bn_b[v] : 0.f;
+    const bool updates = a.training && tid == 0;
+    const float old_mean = (updates && a.run_mean) ? a.run_mean[v] : 0.f, old_var = (updates && a.run_var) ? a.run_var[v] : 0.f;
+    float4 bias4[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) bias4[i] = a.bias ? *reinterpret_cast<const float4 *>(a.bias + c0 + DB_K * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const DbTable tb = db_table(v, a.ell_col, a.ell_val, a.tail_col, a.tail_val, lane);
+
+    // ---- 1. the tiles' aggregations
+    float4 z[DBW_TILES][3];
+    DbSlice bw;
+#pragma unroll
+    for (int t = 0; t < DBW_TILES; ++t) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) z[t][i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t < tiles) {
+            const int mesh = 16 * t + rl;
+            const unsigned rowbase = (unsigned)mesh * (unsigned)a.nv * (DB_C * 4);
+            z[t][0] = db_aggregate<false, false>(r_src, mesh < a.b, rowbase, v, c0, tb, &z[t][1], bw, nullptr, wave, lane);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                z[t][i].x += bias4[i].x, z[t][i].y += bias4[i].y, z[t][i].z += bias4[i].z, z[t][i].w += bias4[i].w;
+                if (a.z_out) db_st4(r_z, own(t) == DB_OOB ? DB_OOB : own(t) + 4 * DB_K * i, z[t][i]);
+            }
+        }
+    }
+    // ---- 2. the weight slice for all tiles, and the first tile's residual, under the statistics
+    __builtin_amdgcn_sched_barrier(0);
+    if (PRODUCT) db_load_slice(bw, a.w_next, wave, lane);
+    float4 rvn[3];
+    residual(0, rvn);
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---- 3. BatchNorm1d(verts): one statistic per vertex over its b * 192 values (two-pass: mean, then the centred second moment)
+    float *red = lds + DB_PANEL + DB_CST;
+    const int n = a.b * DB_C;
+    float mean, invstd;
+    if (a.training) {
+        float s = 0.f, dummy = 0.f;
+#pragma unroll
+        for (int t = 0; t < DBW_TILES; ++t) {
+            const float4 *zt = z[t];
+            const float st = (((zt[0].x + zt[0].y) + (zt[0].z + zt[0].w)) + ((zt[1].x + zt[1].y) + (zt[1].z + zt[1].w))) + ((zt[2].x + zt[2].y) + (zt[2].z + zt[2].w));
+            if (16 * t + rl < a.b) s += st;
+        }
+        db_sum2(s, dummy, red);
+        mean = s / n;
+        float q = 0.f;
+#pragma unroll
+        for (int t = 0; t < DBW_TILES; ++t) {
+            float qt = 0.f;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const float d0 = z[t][i].x - mean, d1 = z[t][i].y - mean, d2 = z[t][i].z - mean, d3 = z[t][i].w - mean;
+                qt += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+            }
+            if (16 * t + rl < a.b) q += qt;
+        }
+        dummy = 0.f;
+        db_sum2(q, dummy, red);
+        const float var = q / n; // biased, as used for normalisation
+        invstd = 1.f / sqrtf(var + a.eps);
+        if (tid == 0) {
+            a.save_mean[v] = mean, a.save_invstd[v] = invstd;
+            if (a.run_mean) a.run_mean[v] = (1.f - a.momentum) * old_mean + a.momentum * mean;
+            if (a.run_var) a.run_var[v] = (1.f - a.momentum) * old_var + a.momentum * (n > 1 ? q / (n - 1) : var);
+        }
+    } else {
+        mean = a.run_mean[v];
+        invstd = 1.f / sqrtf(a.run_var[v] + a.eps);
+    }
+
+    // ---- 4. the tiles' outputs and products
+    float *stage = lds + DB_PANEL;
+    const __amdgpu_buffer_rsrc_t r_s = db_rsrc(a.s_out, op_bytes);
+#pragma unroll
+    for (int t = 0; t < DBW_TILES; ++t) {
+        if (t < tiles) {
+            const bool mesh_on = 16 * t + rl < a.b;
+            float4 rv[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) rv[i] = rvn[i];
+            if (t + 1 < tiles) residual(t + 1, rvn);
+            auto finish = [&](float zz, float r) {
+                float y = (zz - mean) * invstd * gamma + beta;
+                if (a.relu) y = y > 0.f ? y : 0.f;
+                if (a.res) y = (r + y) * a.scale;
+                return mesh_on ? y : 0.f;
+            };
+            float4 xo[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                xo[i] = make_float4(finish(z[t][i].x, rv[i].x), finish(z[t][i].y, rv[i].y), finish(z[t][i].z, rv[i].z), finish(z[t][i].w, rv[i].w));
+                db_st4(r_x, own(t) == DB_OOB ? DB_OOB : own(t) + 4 * DB_K * i, xo[i]);
+            }
+            if (!PRODUCT) {
+                // the coordinate head's product inside the last hidden layer's launch (as db_fwd_body)
+                if (a.w_head && a.s_head) {
+                    float h[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        const float xv[4] = {xo[i].x, xo[i].y, xo[i].z, xo[i].w};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float *wr = a.w_head + (size_t)(c0 + DB_K * i + e) * 3;
+                            h[0] += xv[e] * wr[0], h[1] += xv[e] * wr[1], h[2] += xv[e] * wr[2];
+                        }
+                    }
+#pragma unroll
+                    for (int m = 8; m > 0; m >>= 1) {
+                        h[0] += __shfl_xor(h[0], m, GEOM_WAVE), h[1] += __shfl_xor(h[1], m, GEOM_WAVE), h[2] += __shfl_xor(h[2], m, GEOM_WAVE);
+                    }
+                    if (j == 0 && mesh_on) {
+                        float *dst = a.s_head + ((size_t)(16 * t + rl) * a.nv + v) * 3;
+                        dst[0] = h[0], dst[1] = h[1], dst[2] = h[2];
+                    }
+                }
+            } else {
+                // (the panel's readers and the staging tile's are behind the previous tile's two barriers)
+                db_to_panel(lds, rl, c0, xo);
+                __syncthreads();
+                db_product(bw, lds, stage, wave, x, g);
+                __syncthreads();
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { // the tile leaves in memory order: 768 contiguous bytes per mesh row
+                    const int idx = tid + DB_THREADS * k, r = idx / 48, c4 = idx % 48, mesh = 16 * t + r;
+                    const f32x4 val = *reinterpret_cast<const f32x4 *>(stage + r * DB_LDC + 4 * c4);
+                    const unsigned off = mesh < a.b ? ((unsigned)mesh * (unsigned)a.nv + (unsigned)v) * (DB_C * 4) + 16u * c4 : DB_OOB;
+                    db_st4(r_s, off, make_float4(val[0], val[1], val[2], val[3]));
+                }
+                __syncthreads(); // (the staging tile is free for the next tile's product)
+            }
+        }
+    }
+}
+
+template <bool PRODUCT>
+__global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd a)
+{
+    __shared__ __attribute__((aligned(16))) float lds[DB_PANEL + DB_CST + DB_RED];
+    const int v = db_vertex(blockIdx.x, a.vpx, a.nv);
+    if (v < 0) return;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = lane & 15, g = lane >> 4;
+    const int rl = tid >> 4, j = tid & 15;
+    const int c0 = 4 * j;
+    const int tiles = (a.b + 15) >> 4;
+    const int64_t op_bytes = (int64_t)a.b * a.nv * DB_C * 4;
+    const int g_ld = a.g_ld ? a.g_ld : DB_C, g2_ld = a.g2_ld ? a.g2_ld : DB_C;
+    const __amdgpu_buffer_rsrc_t r_z = db_rsrc(a.z, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_g2 = db_rsrc(a.g2, ((int64_t)a.b * a.nv - 1) * g2_ld * 4 + DB_C * 4);
+    const __amdgpu_buffer_rsrc_t r_g = db_rsrc(a.g, ((int64_t)a.b * a.nv - 1) * g_ld * 4 + DB_C * 4);
+    const __amdgpu_buffer_rsrc_t r_gr = db_rsrc(a.grad_res, op_bytes), r_dz = db_rsrc(a.dz, op_bytes);
+    // byte offset of the thread's float4 i of tile t in a [b, nv, ld] operand (DB_OOB: a row at or beyond b)
+    auto at = [&](int t, int i, int ld) {
+        const int mesh = 16 * t + rl;
+        return mesh < a.b ? (((unsigned)mesh * (unsigned)a.nv + (unsigned)v) * (unsigned)ld + (unsigned)(c0 + DB_K * i)) * 4u : DB_OOB;
+    };
+    const float mean = a.save_mean[v], invstd = a.save_invstd[v];
+    const float gamma = a.bn_w ? a.bn_w[v] : 1.f, beta = a.bn_b ? a.bn_b[v] : 0.f;
+    float *stage = lds + DB_PANEL;
+    float4 go[DBW_TILES][3];
+#pragma unroll
+    for (int t = 0; t < DBW_TILES; ++t)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) go[t][i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (PRODUCT) {
+        // ---- 1. aggregation backward of the layer above, tile by tile: G = [A^T . dZ_up[:, :64] | dZ_up[:, 64:]]
+        const __amdgpu_buffer_rsrc_t r_src = db_rsrc(a.dz_up, op_bytes), r_ds = db_rsrc(a.ds_up, op_bytes);
+        const DbTable tb = db_table(v, a.ell_col_t, a.ell_val_t, a.tail_col_t, a.tail_val_t, lane);
+        DbSlice bw;
+#pragma unroll
+        for (int t = 0; t < DBW_TILES; ++t) {
+            if (t < tiles) {
+                const int mesh = 16 * t + rl;
+                const unsigned rowbase = (unsigned)mesh * (unsigned)a.nv * (DB_C * 4);
+                go[t][0] = db_aggregate<false, false>(r_src, mesh < a.b, rowbase, v, c0, tb, &go[t][1], bw, nullptr, wave, lane);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) db_st4(r_ds, at(t, i, DB_C), go[t][i]); // the layer above's weight gradient reads it
+            }
+        }
+        // ---- 2. the slice of W_up^T, once for all tiles; 3. dX = G . W_up^T
+        __builtin_amdgcn_sched_barrier(0);
+        db_load_slice(bw, a.wt_up, wave, lane);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < DBW_TILES; ++t) {
+            if (t < tiles) {
+                db_to_panel(lds, rl, c0, go[t]); // (rows beyond the batch read zeros: zero rows of the tile)
+                __syncthreads();
+                db_product(bw, lds, stage, wave, x, g);
+                __syncthreads();
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const f32x4 r = *reinterpret_cast<const f32x4 *>(stage + rl * DB_LDC + c0 + DB_K * i);
+                    go[t][i] = make_float4(r[0], r[1], r[2], r[3]);
+                }
+                __syncthreads(); // (the staging tile is free for the next tile's product)
+            }
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < DBW_TILES; ++t)
+            if (t < tiles && a.g) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) go[t][i] = db_ld4(r_g, at(t, i, g_ld));
+            }
+        if (a.ds_head) {
+            // ---- the coordinate head inside the first backward launch (as db_bwd_body): its input gradient joins g; the vertex's
+            // partial of its weight gradient: per thread over its tiles in tile order, then the wave's rows, then the waves
+            const __amdgpu_buffer_rsrc_t r_xt = db_rsrc(a.x_top, op_bytes);
+            float *wsum = lds + DB_PANEL; // [4 waves][192 * 3]
+            float part[3][4][3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int o = 0; o < 3; ++o) part[i][e][o] = 0.f;
+#pragma unroll
+            for (int t = 0; t < DBW_TILES; ++t) {
+                if (t < tiles) {
+                    const int mesh = 16 * t + rl;
+                    float dsh[3] = {0.f, 0.f, 0.f};
+                    if (mesh < a.b) {
+                        const float *src = a.ds_head + ((size_t)mesh * a.nv + v) * 3;
+                        dsh[0] = src[0], dsh[1] = src[1], dsh[2] = src[2];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        const float4 xt = a.dw_head ? db_ld4(r_xt, at(t, i, DB_C)) : make_float4(0.f, 0.f, 0.f, 0.f);
+                        const float xv[4] = {xt.x, xt.y, xt.z, xt.w};
+                        float add[4];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float *wr = a.w_head + (size_t)(c0 + DB_K * i + e) * 3;
+                            add[e] = (dsh[0] * wr[0] + dsh[1] * wr[1]) + dsh[2] * wr[2];
+#pragma unroll
+                            for (int o = 0; o < 3; ++o) part[i][e][o] += xv[e] * dsh[o];
+                        }
+                        go[t][i].x += add[0], go[t][i].y += add[1], go[t][i].z += add[2], go[t][i].w += add[3];
+                    }
+                }
+            }
+            if (a.dw_head) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+#pragma unroll
+                        for (int o = 0; o < 3; ++o) {
+                            const float p = part[i][e][o];
+                            float acc = p;
+#pragma unroll
+                            for (int k = 1; k < 4; ++k) acc += __shfl(p, (lane & 15) + 16 * k, GEOM_WAVE);
+                            if ((lane >> 4) == 0) wsum[wave * (DB_C * 3) + (c0 + DB_K * i + e) * 3 + o] = acc;
+                        }
+                __syncthreads();
+                for (int k = tid; k < DB_C * 3; k += DB_THREADS)
+                    a.dw_head[(size_t)v * (DB_C * 3) + k] = ((wsum[k] + wsum[DB_C * 3 + k]) + wsum[2 * DB_C * 3 + k]) + wsum[3 * DB_C * 3 + k];
+                __syncthreads();
+            }
+        }
+    }
+    // ---- 4. this layer: residual scale, ReLU mask, the two sums of the BatchNorm backward over all tiles
+    float sum_g = 0.f, sum_gx = 0.f;
+    float4 zv[DBW_TILES][3];
+#pragma unroll
+    for (int t = 0; t < DBW_TILES; ++t) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) zv[t][i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t < tiles) {
+            const bool mesh_on = 16 * t + rl < a.b;
+            auto one = [&](float zz, float &gg, float second) {
+                const float xhat = (zz - mean) * invstd;
+                gg += second;
+                if (a.has_res) gg *= a.scale;
+                const float pass = gg;
+                if (a.relu && !(xhat * gamma + beta > 0.f)) gg = 0.f;
+                if (!mesh_on) gg = 0.f;
+                sum_g += gg;
+                sum_gx += gg * xhat;
+                return pass;
+            };
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                zv[t][i] = db_ld4(r_z, at(t, i, DB_C));
+                const float4 s = a.g2 ? db_ld4(r_g2, at(t, i, g2_ld)) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 r = make_float4(one(zv[t][i].x, go[t][i].x, s.x), one(zv[t][i].y, go[t][i].y, s.y),
+                                             one(zv[t][i].z, go[t][i].z, s.z), one(zv[t][i].w, go[t][i].w, s.w));
+                if (a.has_res && a.grad_res) db_st4(r_gr, at(t, i, DB_C), r);
+            }
+        }
+    }
+    float *red = lds + DB_PANEL + DB_CST;
+    db_sum2(sum_g, sum_gx, red);
+    if (tid == 0) {
+        if (a.grad_bn_b) a.grad_bn_b[v] = sum_g;
+        if (a.grad_bn_w) a.grad_bn_w[v] = sum_gx;
+    }
+    // ---- 5. dZ, and the vertex's column sums of dZ over its meshes (per thread over its tiles, the wave's rows, the waves)
+    const int n = a.b * DB_C;
+    const float kk = gamma * invstd, mg = sum_g / n, mgx = sum_gx / n;
+    float4 cs[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) cs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int t = 0; t < DBW_TILES; ++t) {
+        if (t < tiles) {
+            const bool mesh_on = 16 * t + rl < a.b;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const float4 zz = zv[t][i], gg = go[t][i];
+                float4 dz = make_float4(kk * (gg.x - mg - (zz.x - mean) * invstd * mgx), kk * (gg.y - mg - (zz.y - mean) * invstd * mgx),
+                                        kk * (gg.z - mg - (zz.z - mean) * invstd * mgx), kk * (gg.w - mg - (zz.w - mean) * invstd * mgx));
+                if (!mesh_on) dz = make_float4(0.f, 0.f, 0.f, 0.f);
+                db_st4(r_dz, at(t, i, DB_C), dz);
+                cs[i].x += dz.x, cs[i].y += dz.y, cs[i].z += dz.z, cs[i].w += dz.w;
+            }
+        }
+    }
+    if (a.colsum) {
+        __syncthreads(); // (the staging tile may still be read above)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            float4 t = cs[i];
+#pragma unroll
+            for (int k = 1; k < 4; ++k) {
+                const int src = (lane & 15) + 16 * k;
+                t.x += __shfl(cs[i].x, src), t.y += __shfl(cs[i].y, src), t.z += __shfl(cs[i].z, src), t.w += __shfl(cs[i].w, src);
+            }
+            if ((lane >> 4) == 0) *reinterpret_cast<float4 *>(stage + wave * DB_C + c0 + DB_K * i) = t;
+        }
+        __syncthreads();
+        if (tid < DB_C) a.colsum[(size_t)v * DB_C + tid] = ((stage[tid] + stage[DB_C + tid]) + stage[2 * DB_C + tid]) + stage[3 * DB_C + tid];
+    }
+}
+
 inline bool db_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
-int db_check_shape(int b, int nv, int c, int k, int ell_w)
+// max_b: 16 for the launches of one row tile per vertex, GEOM_DEFORM_WIDE_MAX_B for the wide ones
+int db_check_shape(int b, int nv, int c, int k, int ell_w, int max_b = 16)
 {
     if (b < 0 || nv < 0 || c <= 0 || k < 0) return GEOM_EINVAL;
-    if (c != DB_C || k != DB_K || ell_w != DB_W || b > 16) return GEOM_EUNSUPPORTED;
+    if (c != DB_C || k != DB_K || ell_w != DB_W || b > max_b) return GEOM_EUNSUPPORTED;
     if ((int64_t)b * nv * DB_C >= (1LL << 29)) return GEOM_EUNSUPPORTED; // 32-bit byte offsets
     return 0;
 }
@@ -992,6 +1375,41 @@ extern "C" int geom_deform_layer_bwd_f32(const geom_deform_bwd *args, void *stre
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (a.dz_up) hipLaunchKernelGGL((db_bwd_kernel<true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((db_bwd_kernel<false>), grid, block, 0, s, a);
+    return geom::launch_status();
+}
+
+// The same layers at 17 <= b <= GEOM_DEFORM_WIDE_MAX_B meshes: ceil(b / 16) row tiles per vertex (dbw_fwd_kernel /
+// dbw_bwd_kernel).  Checks and codes of the plain entry points; b <= 16 belongs to those: GEOM_EUNSUPPORTED here.
+extern "C" int geom_deform_layer_wide_fwd_f32(const geom_deform_fwd *args, void *stream)
+{
+    if (!args) return GEOM_EINVAL;
+    geom_deform_fwd a = *args;
+    int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w, GEOM_DEFORM_WIDE_MAX_B);
+    if (code) return code;
+    if (a.b == 0 || a.nv == 0) return 0;
+    if (a.b <= 16) return GEOM_EUNSUPPORTED;
+    if ((code = db_check_fwd(a))) return code;
+    if (a.res && (int64_t)a.b * a.nv * a.res_ld >= (1LL << 29)) return GEOM_EUNSUPPORTED; // 32-bit byte offsets of the residual
+    const dim3 grid(8 * a.vpx), block(DB_THREADS);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (a.w_next) hipLaunchKernelGGL((dbw_fwd_kernel<true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((dbw_fwd_kernel<false>), grid, block, 0, s, a);
+    return geom::launch_status();
+}
+
+extern "C" int geom_deform_layer_wide_bwd_f32(const geom_deform_bwd *args, void *stream)
+{
+    if (!args) return GEOM_EINVAL;
+    geom_deform_bwd a = *args;
+    int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w, GEOM_DEFORM_WIDE_MAX_B);
+    if (code) return code;
+    if (a.b == 0 || a.nv == 0) return 0;
+    if (a.b <= 16) return GEOM_EUNSUPPORTED;
+    if ((code = db_check_bwd(a))) return code;
+    const dim3 grid(8 * a.vpx), block(DB_THREADS);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (a.dz_up) hipLaunchKernelGGL((dbw_bwd_kernel<true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((dbw_bwd_kernel<false>), grid, block, 0, s, a);
     return geom::launch_status();
 }
 

@@ -22,6 +22,12 @@ of width 8, fp32 on a HIP device, BatchNorm over the input's vertices; and b <= 
 statistics); everything else takes the separate operators (models.py).  The one-launch chain also needs a structurally symmetric adjacency (`csr.symmetric_structure`); a directed one
 takes the launches per layer.
 
+Training batches of 17 .. 64 meshes (`serves_wide`, `wide_layer_forward` / `wide_layer_backward`): the same launch per layer and
+direction with the vertex's batch rows as ceil(b / 16) <= 4 row tiles behind ONE register-resident weight slice
+(geom_deform_layer_wide_{fwd,bwd}_f32); the vertex's statistics are combined across the tiles inside the workgroup.  Launches
+per layer only -- never the one-launch chain, no counters.  Opt-in: `wide = True` (GEOM_DEFORM_WIDE=1); the default keeps the
+separate operators above 16 meshes until the route has been timed against them.
+
 Eval mode under no_grad (`serves_inference`, `inference_chain`): BatchNorm on the running statistics is a per-vertex affine map,
 so the layer launch (geom_deform_infer_fwd_f32) tiles 16 consecutive rows of the flattened [B * V] rows instead of a vertex's
 batch rows -- any batch, no cross-workgroup waits, nothing written to the BatchNorm state.
@@ -87,6 +93,25 @@ def serves(block, features, pooled, csr):
     """Whether the fused training launches serve this call of `block` (a models.BatchMeshDeformationBlock): _servable, in
     training mode with gradients, at most 16 meshes, local BatchNorm statistics with a momentum (each layer takes its own)."""
     if not block.training or not torch.is_grad_enabled() or (features.dim() == 3 and features.shape[0] > 16):
+        return False
+    return _servable(block, features, pooled, csr) and not any(
+        bn._synchronised() or bn.momentum is None for bn in hidden_layers(block)[1])
+
+
+# Training batches of 17 .. WIDE_MAX_BATCH meshes on the launches with ceil(b / 16) row tiles per vertex
+# (geom_deform_layer_wide_*); False keeps the separate operators there.  OFF unless GEOM_DEFORM_WIDE=1: the route has not been
+# timed against the separate operators yet (tools/time_deform_wide.py), and it goes on per batch only where that comparison
+# shows a win beyond its spread.
+wide = os.environ.get("GEOM_DEFORM_WIDE", "0") == "1"
+WIDE_MAX_BATCH = 64      # GEOM_DEFORM_WIDE_MAX_B
+
+
+def serves_wide(block, features, pooled, csr):
+    """Whether the wide training launches serve this call of `block`: the clauses of serves() with 17 <= b <= WIDE_MAX_BATCH
+    meshes, and the `wide` switch."""
+    if not wide or not block.training or not torch.is_grad_enabled() or features.dim() != 3:
+        return False
+    if not 16 < features.shape[0] <= WIDE_MAX_BATCH:
         return False
     return _servable(block, features, pooled, csr) and not any(
         bn._synchronised() or bn.momentum is None for bn in hidden_layers(block)[1])
@@ -200,6 +225,13 @@ def layer_forward(s_in, *args, **kwargs):
         _lib.call("geom_deform_layer_fwd_f32", ctypes.addressof(a))
 
 
+def wide_layer_forward(s_in, *args, **kwargs):
+    """layer_forward for 17 .. WIDE_MAX_BATCH meshes (geom_deform_layer_wide_fwd_f32): same arguments, same results."""
+    a = _forward_args(s_in, *args, **kwargs)
+    with torch.cuda.device(s_in.device):
+        _lib.call("geom_deform_layer_wide_fwd_f32", ctypes.addressof(a))
+
+
 def chain_forward(layers, done, device):
     """`layers` (lists of layer_forward's arguments) as ONE launch (geom_deform_chain_fwd_f32); done: int32 [nv * CTR_STRIDE],
     zero."""
@@ -250,6 +282,13 @@ def layer_backward(shape, csr, z, *args, **kwargs):
         _lib.call("geom_deform_layer_bwd_f32", ctypes.addressof(a))
 
 
+def wide_layer_backward(shape, csr, z, *args, **kwargs):
+    """layer_backward for 17 .. WIDE_MAX_BATCH meshes (geom_deform_layer_wide_bwd_f32): same arguments, same results."""
+    a, _keep = _backward_args(shape, csr, z, *args, **kwargs)
+    with torch.cuda.device(z.device):
+        _lib.call("geom_deform_layer_wide_bwd_f32", ctypes.addressof(a))
+
+
 def chain_backward(layers, done, device, ds_first=None):
     """`layers` (lists of layer_backward's arguments, the top layer first) as ONE launch (geom_deform_chain_bwd_f32); ds_first:
     receives the aggregation backward of the last layer's dZ (the chain's first layer has no activation behind its support)."""
@@ -286,7 +325,9 @@ class _HiddenChain(torch.autograd.Function):
         s_cur = s1
         # (a chain launch needs a symmetric pattern: vertex v rewrites its support row once the vertices of ITS row are done
         # with the previous layer, and those must be all the vertices that gather v's row -- A[u][v] != 0 => A[v][u] != 0)
-        as_chain = csr.symmetric_structure and chain_fits(nv, dev)
+        # (above 16 meshes: the wide launches, layer by layer -- never a chain, no counters)
+        as_chain = b <= 16 and csr.symmetric_structure and chain_fits(nv, dev)
+        forward_launch = layer_forward if b <= 16 else wide_layer_forward
         # (counters of the forward and of the backward chain launch, cleared by the packing launch)
         counters = torch.empty(2, nv * CTR_STRIDE, dtype=torch.int32, device=dev) if as_chain else None
         w2, wts = pack_weights(weights, counters)     # w2[i - 1] / wts[i - 1] = W_{i+1} / its transpose, in register-slice order
@@ -303,7 +344,7 @@ class _HiddenChain(torch.autograd.Function):
             if as_chain:
                 calls.append(call)
             else:
-                layer_forward(*call[0], **call[1])
+                forward_launch(*call[0], **call[1])
             s_cur = s_buf[i & 1]
         if as_chain:
             chain_forward(calls, counters[0], dev)
@@ -351,6 +392,7 @@ class _HiddenChain(torch.autograd.Function):
         calls = [] if ctx.counters is not None and chain_fits(nv, dev) else None
         if calls is not None:
             ctx.counters = None
+        backward_launch = layer_backward if b <= 16 else wide_layer_backward
         for i, src, _, top, _ in reversed(SCHEDULE):
             grad_res = torch.empty(b, nv, c, **f32) if src is not None else None
             common = dict(relu=ctx.relu, has_res=src is not None, scale=0.5, dz=dzs[i - 1], grad_bn_w=g_bnw[i - 1], grad_bn_b=g_bnb[i - 1],
@@ -362,7 +404,7 @@ class _HiddenChain(torch.autograd.Function):
             else:
                 what = dict(dz_up=dzs[i], ds_up=dss[i - 1], wt_up=wts[i - 1], g2=pending.pop(i, None), **common)
             if calls is None:
-                layer_backward(*where, **what)
+                backward_launch(*where, **what)
             else:
                 calls.append((where, what))
             if src == "lead":

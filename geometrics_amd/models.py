@@ -288,9 +288,10 @@ class BatchMeshDeformationBlock(nn.Module):
         batching = _layers.weight_gradient_batching(depth=14) if self.batch_weight_gradients else contextlib.nullcontext()
         csr = _layers.adjacency_csr(adj) if (torch.is_tensor(adj) and adj.dim() == 2 and features.is_cuda) else None
         chain = None
-        if csr is not None and _deform.serves(self, features, pooled, csr):
+        if csr is not None and (_deform.serves(self, features, pooled, csr) or _deform.serves_wide(self, features, pooled, csr)):
             # ONE launch per hidden layer and direction (csrc/deform_block.hip): aggregation + BatchNorm1d(verts) + ReLU +
             # residual average + the next layer's product; the first layer's product and the coordinate head stay the layers'
+            # (17 .. 64 meshes: the launches with several row tiles per vertex)
             chain = _deform.hidden_chain
         elif csr is not None and _deform.serves_inference(self, features, pooled, csr):
             # eval() under no_grad (validation, evaluation): one launch per hidden layer on the running statistics, 16

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GEOM_ABI_VERSION 15
+#define GEOM_ABI_VERSION 16
 
 /* argument errors */
 #define GEOM_EINVAL   (-1) /* bad size / null pointer */
@@ -496,6 +496,22 @@ int geom_camera_info_f32(int b, const float *param, float *cam_mat, float *cam_p
 int geom_deform_pack_weights_f32(int count, const float *const *w, float *fwd, float *bwd, void *stream);
 int geom_deform_layer_fwd_f32(const geom_deform_fwd *args, void *stream);
 int geom_deform_layer_bwd_f32(const geom_deform_bwd *args, void *stream);
+/* The same two launches for training batches of 17 <= b <= GEOM_DEFORM_WIDE_MAX_B meshes: still one workgroup per vertex, its b
+ * rows as ceil(b / 16) <= 4 row tiles of the matrix core behind ONE register-resident weight slice (the 147 KB a workgroup
+ * reads serve up to four tiles); rows at or beyond b in the last tile are zero rows of the panel and store nothing.  Same
+ * argument structs, operands and semantics as geom_deform_layer_fwd_f32 / geom_deform_layer_bwd_f32 (residual, g and g2 at any
+ * pitch, the coordinate head in the last forward / first backward launch, colsum, grad_res, the running statistics):
+ *   - z_out / ds_up: the bits of geom_zn_gcn_aggregate_ell_fwd_f32 / _bwd_f32 (table slots, then the tail, in CSR order);
+ *   - the vertex's statistics run over all b * 192 values: mean, then the centred second moment (biased variance for the
+ *     normalisation, unbiased for the running variance); the backward's two sums likewise -- per thread over its tiles in tile
+ *     order, then the wave, then the four waves: fixed order, no atomics, a repeated launch gives the same bits;
+ *   - products exact fp32 on v_mfma_f32_16x16x4_f32 from the packed weights of geom_deform_pack_weights_f32.
+ * Codes: b <= 16 (the plain entry points' ground) or b > GEOM_DEFORM_WIDE_MAX_B: GEOM_EUNSUPPORTED; b == 0 or nv == 0: 0;
+ * every other shape, pointer and alignment check answers as the plain entry points do; a residual pitch with
+ * b * nv * res_ld >= 2^29: GEOM_EUNSUPPORTED. */
+#define GEOM_DEFORM_WIDE_MAX_B 64
+int geom_deform_layer_wide_fwd_f32(const geom_deform_fwd *args, void *stream);
+int geom_deform_layer_wide_bwd_f32(const geom_deform_bwd *args, void *stream);
 
 /* Any-shape product on the fp32 matrix cores (csrc/dense_any.hip): c [m, n] (row pitch ldc) = op(a) . op(b), exact fp32
  * (v_mfma_f32_16x16x4_f32), any sizes / pitches / 4-byte alignments -- `torch.mm(input, weight)` of the layers whose widths
