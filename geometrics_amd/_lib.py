@@ -136,6 +136,12 @@ _SIGNATURES = {
     "geom_deform_layer_wide_fwd_f32": [_vp, _vp],
     "geom_deform_layer_wide_bwd_f32": [_vp, _vp],
     "geom_deform_infer_fwd_f32": [_vp, _vp],
+    "geom_encoder_layer_fwd_f32": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _i, _vp, ctypes.c_int64,
+                                   _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp],
+    "geom_encoder_layer_bwd_f32": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i, _vp,
+                                   ctypes.c_int64, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp],
+    "geom_latent_l1_fwd_f32": [_i, _i, _vp, _vp, _vp, _f, _vp, _vp],
+    "geom_latent_l1_bwd_f32": [_i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp],
 }
 
 

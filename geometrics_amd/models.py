@@ -23,8 +23,9 @@ from torch import nn
 
 from . import _lib
 from . import deform as _deform
+from . import encoder as _encoder
 from . import layers as _layers
-from .layers import Batch_Image_ZERON_GCNGCN, GCNMax, ZERON_GCN, _alias
+from .layers import Batch_Image_ZERON_GCNGCN, BatchGCNMax, BatchZERON_GCN, GCNMax, ZERON_GCN, _alias
 
 
 def _identity(x):
@@ -371,3 +372,41 @@ class MeshEncoder(nn.Module):
 
         sample = batch.verts.detach().clone().requires_grad_(batch.verts.requires_grad)
         return torch.cuda.make_graphed_callables(_Encode(), (sample,), num_warmup_iters=warmup)
+
+
+class BatchMeshEncoder(nn.Module):
+    """Reference models.py:386-435: the mesh encoder for a batch of meshes that share ONE adjacency -- sixteen BatchZERON_GCN
+    layers (3 -> 60 ... -> 300, ELU) and a BatchGCNMax head (max over the vertices of the un-activated values).  Layer names,
+    widths and state_dict keys are the reference's.  `forward(positions [B,V,3], adj [V,V]) -> [B, latent]`.
+
+    With FROZEN parameters (`encoder.requires_grad_(False)`, what the latent loss of GEOMetrics.py:165-171 needs: only the
+    positions receive a gradient) and `geometrics_amd.encoder.enabled` the pass is one launch per layer and direction
+    (geometrics_amd/encoder.py); otherwise it is the plain composition of the layers, parameter gradients included.
+    `last_route` tells which one the last call took: "fused" or "separate"."""
+
+    _WIDTHS = MeshEncoder._WIDTHS
+
+    def __init__(self, latent_length):
+        super().__init__()
+        for name, cin, cout in self._WIDTHS:
+            setattr(self, name, BatchZERON_GCN(cin, cout))
+        self.reduce = BatchGCNMax(300, latent_length)
+        self.last_route = None
+
+    def pre_max(self, positions, adj):
+        """The values the head takes its max of, [B,V,latent] (the reference computes them inside BatchGCNMax, layers.py:186)."""
+        if _encoder.serves(self, positions, adj):
+            csr = _layers.adjacency_csr(adj)       # (built before the first launch: a captured forward never syncs)
+            self.last_route = "fused"
+            return _encoder.pre_max(self, positions, csr)
+        self.last_route = "separate"
+        features = positions
+        for name, _, _ in self._WIDTHS:
+            features = getattr(self, name)(features, adj, F.elu)
+        return self.reduce._pre_activation(features, adj)
+
+    def forward(self, positions, adj, play=False):
+        v = self.pre_max(positions, adj)
+        if self.last_route == "fused":
+            return _encoder.vertex_max(v)
+        return torch.max(v, dim=1)[0]

@@ -730,6 +730,31 @@ int geom_segment_max_fwd_f32(int nseg, const int64_t *offsets, int64_t max_len, 
 int geom_segment_max_bwd_f32(int nseg, const int64_t *offsets, int64_t total_rows, int c,
                              const float *grad_out, const int *arg, float *grad_x, void *stream);
 
+/* ---- the frozen mesh encoder, one launch per layer and direction (models.py:386-435; csrc/encoder_stack.hip) -----------
+ * forward : out[b*nv][n] = T(s) . w,        T(s) = act([A . s[:, :k] | s[:, k:]] + bias), s [b*nv][c], w [c][n]
+ * backward: out[b*nv][n] = T(g, x) . w^T,   T = [A^T . g'[:, :k] | g'[:, k:]], g' = g * act'(x_saved), g [b*nv][c], w [n][c]
+ * (rowptr, col, val) is the CSR (forward) / CSR^T (backward) of the ONE [nv, nv] adjacency the b meshes share (may be NULL
+ * when k == 0); bias may be NULL; act as geom_zn_gcn_aggregate_*; x_saved may be NULL when act == 0.  k == 0, no bias, act
+ * == 0: the plain product.  Every matrix has its own row pitch in floats (>= its width), any alignment.  x_out / t_out (may be
+ * NULL, [b*nv][c]) receives T, which equals geom_zn_gcn_aggregate_fwd_f32 / _bwd_f32 on the same input bit for bit; the product
+ * is exact fp32 (as geom_gemm_f32).  No weight or bias gradients: the entry points serve frozen parameters.
+ * Codes: a negative size, k > c, an unknown act, a null required pointer or a pitch below its width: GEOM_EINVAL (checked
+ * before any launch); k > 32: GEOM_EUNSUPPORTED; b * nv beyond 2^31 - 65: GEOM_ETOOBIG. */
+int geom_encoder_layer_fwd_f32(int b, int nv, int c, int k, int n, const int *rowptr, const int *col, const float *val,
+                               const float *s, int64_t lds, const float *bias, int act, const float *w, int64_t ldw,
+                               float *out, int64_t ldo, float *x_out, int64_t ldx, void *stream);
+int geom_encoder_layer_bwd_f32(int b, int nv, int c, int k, int n, const int *rowptrT, const int *colT, const float *valT,
+                               const float *g, int64_t ldg, const float *x_saved, int64_t ldx, int act, const float *w,
+                               int64_t ldw, float *out, int64_t ldo, float *t_out, int64_t ldt, void *stream);
+/* The latent loss of the training step (GEOMetrics.py:165-171): loss[0] = weight * sum_b [ mean_j |pred[b][j] - target[b][j]|
+ * * on[b] / sum(on) ] for pred, target [b][l] and on [b] (device floats), and grad_pred = grad_loss[0] * d loss / d pred.
+ * sum(on) == 0 gives loss 0 and a zero gradient, decided on the device (the reference reads the sum on the host).  One
+ * workgroup, fixed summation order: bit-reproducible.  A negative size or a null pointer: GEOM_EINVAL. */
+int geom_latent_l1_fwd_f32(int b, int l, const float *pred, const float *target, const float *on, float weight, float *loss,
+                           void *stream);
+int geom_latent_l1_bwd_f32(int b, int l, const float *pred, const float *target, const float *on, float weight,
+                           const float *grad_loss, float *grad_pred, void *stream);
+
 /* ---- optimiser step for the replicated layer parameters (GEOMetrics.py:73: Adam, lr 1e-4) -----------
  * torch.optim.Adam's update (no weight decay / amsgrad) for up to GEOM_ADAM_MAX_TENSORS tensors in ONE
  * launch.  params/grads/exp_avg/exp_avg_sq/sizes are HOST arrays of `count` device pointers / lengths;
