@@ -23,6 +23,17 @@
 // kernel start so that it lands under the gather round trips; the activation tile goes through the same conflict-free
 // [k-quarter][row][52] LDS panel, one ds_read_b128 per 12 MFMAs.  482 workgroups of 4 waves, two resident per CU: while one
 // waits for its gathers the other runs its 144 MFMAs per wave.
+//
+// Three forward bodies (db_fwd_body: plain and chain launches, one row tile per vertex; dbw_fwd_kernel: up to four tiles per
+// vertex; di_row_block: eval, 16 consecutive rows of [b * nv]) and two backward ones (db_bwd_body, dbw_bwd_kernel) run the SAME
+// layer.  Its steps -- bias, BatchNorm + ReLU + residual, the statistics and their publication, the coordinate head both ways,
+// the staging tile's way out, the BatchNorm backward, the column sums -- are stated once, as the db_* helpers behind
+// db_to_panel, and every body calls them: the wide route must give the plain route's bits, the eval route vertex_bn's.
+// The bodies themselves stay apart, because their SCHEDULES differ on purpose: the plain body requests the weight slice inside
+// db_aggregate<SLICE>, behind its gathers; the wide body once, behind the gathers of ALL tiles (a pole's 32 tail rows per tile
+// need the slice's registers); the eval body walks a per-row table and, once the slice is live, gathers in two rounds of four.
+// The chain kernels sit at 256 VGPRs already (tools/kernel_resources.sh): one body templated over the tile count, or the eval
+// table walk folded into db_aggregate, would trade these orders for one that fits none of them.
 #include "geom_common.h"
 
 namespace {
@@ -323,6 +334,222 @@ __device__ __forceinline__ void db_to_panel(float *panel, int rl, int c0, const 
     }
 }
 
+// ---- the steps every body of this file shares.  Each is stated ONCE: the wide launches must give the bits of the plain ones
+// and the eval launch those of vertex_bn's eval branch, so a body calls these and keeps only its own schedule (the top of the
+// file).  Values and fixed-size array references only: the bodies sit at the register ceiling, nothing here may reach scratch.
+
+// byte offset of the thread's float4 i (columns c0 + 64 i ..) of its own row, from that of float4 0 (DB_OOB: no row)
+__device__ __forceinline__ unsigned db_own(unsigned own_off, int i) { return own_off == DB_OOB ? DB_OOB : own_off + 4 * DB_K * i; }
+
+template <typename Args> // geom_deform_fwd or geom_deform_infer
+__device__ __forceinline__ float4 db_bias4(const Args &a, int c0, int i)
+{
+    return a.bias ? *reinterpret_cast<const float4 *>(a.bias + c0 + DB_K * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+__device__ __forceinline__ void db_add_bias(float4 (&z)[3], const float4 (&bias4)[3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i) z[i].x += bias4[i].x, z[i].y += bias4[i].y, z[i].z += bias4[i].z, z[i].w += bias4[i].w;
+}
+
+// BatchNorm + ReLU + residual of a thread's 12 values: the operations and order of geom_vertex_bn_fwd_f32 (no folded scale /
+// shift).  `on` = false: a row beyond the batch, zeros.
+struct DbNorm {
+    float mean, invstd, gamma, beta;
+};
+template <typename Args> // (relu, res and scale are the layer's: geom_deform_fwd or geom_deform_infer)
+__device__ __forceinline__ float db_norm_one(const Args &a, const DbNorm &bn, float zz, float r, bool on)
+{
+    float y = (zz - bn.mean) * bn.invstd * bn.gamma + bn.beta;
+    if (a.relu) y = y > 0.f ? y : 0.f;
+    if (a.res) y = (r + y) * a.scale;
+    return on ? y : 0.f;
+}
+template <typename Args>
+__device__ __forceinline__ void db_norm_apply(const Args &a, const DbNorm &bn, const float4 (&z)[3], const float4 (&r)[3], bool on, float4 (&xo)[3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        xo[i] = make_float4(db_norm_one(a, bn, z[i].x, r[i].x, on), db_norm_one(a, bn, z[i].y, r[i].y, on),
+                            db_norm_one(a, bn, z[i].z, r[i].z, on), db_norm_one(a, bn, z[i].w, r[i].w, on));
+}
+
+// batch statistics: a thread's 12 values of one tile row, in this order
+__device__ __forceinline__ float db_row_sum(const float4 (&z)[3])
+{
+    return (((z[0].x + z[0].y) + (z[0].z + z[0].w)) + ((z[1].x + z[1].y) + (z[1].z + z[1].w))) + ((z[2].x + z[2].y) + (z[2].z + z[2].w));
+}
+__device__ __forceinline__ float db_row_centred_sq(const float4 (&z)[3], float mean)
+{
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float d0 = z[i].x - mean, d1 = z[i].y - mean, d2 = z[i].z - mean, d3 = z[i].w - mean;
+        q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    }
+    return q;
+}
+// ... and what follows the two reductions: q = the vertex's centred sum of squares over its n values.  Returns invstd; thread 0
+// writes the saved statistics and moves the running ones (nn.BatchNorm1d: with the unbiased variance).
+__device__ __forceinline__ float db_publish_stats(const geom_deform_fwd &a, int v, int n, float mean, float q, float old_mean, float old_var)
+{
+    const float var = q / n; // biased, as used for normalisation
+    const float invstd = 1.f / sqrtf(var + a.eps);
+    if (threadIdx.x == 0) {
+        a.save_mean[v] = mean, a.save_invstd[v] = invstd;
+        if (a.run_mean) a.run_mean[v] = (1.f - a.momentum) * old_mean + a.momentum * mean;
+        if (a.run_var) a.run_var[v] = (1.f - a.momentum) * old_var + a.momentum * (n > 1 ? q / (n - 1) : var);
+    }
+    return invstd;
+}
+
+// The coordinate head's product (models.py:219,295: gc15 = 192 -> 3) inside the last hidden layer's launch:
+// h[o] = sum_c X[row][c] W_head[c][o]; a row's 192 columns sit in the 16 lanes of its group, every one of which gets the sums
+__device__ __forceinline__ void db_head_fwd(const float4 (&xo)[3], const float *w_head, int c0, float (&h)[3])
+{
+    h[0] = 0.f, h[1] = 0.f, h[2] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float xv[4] = {xo[i].x, xo[i].y, xo[i].z, xo[i].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float *wr = w_head + (size_t)(c0 + DB_K * i + e) * 3;
+            h[0] += xv[e] * wr[0], h[1] += xv[e] * wr[1], h[2] += xv[e] * wr[2];
+        }
+    }
+#pragma unroll
+    for (int m = 8; m > 0; m >>= 1) {
+        h[0] += __shfl_xor(h[0], m, GEOM_WAVE), h[1] += __shfl_xor(h[1], m, GEOM_WAVE), h[2] += __shfl_xor(h[2], m, GEOM_WAVE);
+    }
+}
+
+// The staging tile leaves in memory order (a row's 768 bytes are contiguous); row_offset(r) = byte offset of staging row r, or
+// DB_OOB.  AGENT: rows another workgroup of the same launch gathers.
+template <bool AGENT, typename RowOffset>
+__device__ __forceinline__ void db_store_tile(const float *stage, __amdgpu_buffer_rsrc_t r_s, RowOffset row_offset)
+{
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        const int idx = (int)threadIdx.x + DB_THREADS * t, r = idx / 48, c4 = idx % 48;
+        const f32x4 val = *reinterpret_cast<const f32x4 *>(stage + r * DB_LDC + 4 * c4);
+        const unsigned row = row_offset(r);
+        db_st4<AGENT>(r_s, row == DB_OOB ? DB_OOB : row + 16u * c4, make_float4(val[0], val[1], val[2], val[3]));
+    }
+}
+// ... or returns to the thread's registers (its row rl, columns c0 + 64 i ..)
+__device__ __forceinline__ void db_load_tile(const float *stage, int rl, int c0, float4 (&go)[3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const f32x4 t = *reinterpret_cast<const f32x4 *>(stage + rl * DB_LDC + c0 + DB_K * i);
+        go[i] = make_float4(t[0], t[1], t[2], t[3]);
+    }
+}
+
+// BatchNorm backward of one element: gg = the upstream gradient (+ the second one, * the residual's scale: returned, the
+// residual's gradient), then masked by the ReLU and the batch; xhat and the two sums of the reduction
+__device__ __forceinline__ float db_bn_bwd_elem(const geom_deform_bwd &a, float mean, float invstd, float gamma, float beta, bool mesh_on,
+                                                float zz, float &gg, float second, float &xhat, float &sum_g, float &sum_gx)
+{
+    xhat = (zz - mean) * invstd;
+    gg += second;
+    if (a.has_res) gg *= a.scale;
+    const float pass = gg;
+    if (a.relu && !(xhat * gamma + beta > 0.f)) gg = 0.f;
+    if (!mesh_on) gg = 0.f;
+    sum_g += gg;
+    sum_gx += gg * xhat;
+    return pass;
+}
+// ... a float4 of them; the residual's gradient leaves for grad_res at `off`
+__device__ __forceinline__ void db_bn_bwd_elems(const geom_deform_bwd &a, float mean, float invstd, float gamma, float beta, bool mesh_on,
+                                                const float4 &zv, float4 &go, const float4 &second, float4 &xh, float &sum_g, float &sum_gx,
+                                                __amdgpu_buffer_rsrc_t r_gr, unsigned off)
+{
+    const float4 r = make_float4(db_bn_bwd_elem(a, mean, invstd, gamma, beta, mesh_on, zv.x, go.x, second.x, xh.x, sum_g, sum_gx),
+                                 db_bn_bwd_elem(a, mean, invstd, gamma, beta, mesh_on, zv.y, go.y, second.y, xh.y, sum_g, sum_gx),
+                                 db_bn_bwd_elem(a, mean, invstd, gamma, beta, mesh_on, zv.z, go.z, second.z, xh.z, sum_g, sum_gx),
+                                 db_bn_bwd_elem(a, mean, invstd, gamma, beta, mesh_on, zv.w, go.w, second.w, xh.w, sum_g, sum_gx));
+    if (a.has_res && a.grad_res) db_st4(r_gr, off, r);
+}
+// after the reduction: the BatchNorm parameter gradients of vertex v
+__device__ __forceinline__ void db_publish_bn_grads(const geom_deform_bwd &a, int v, float sum_g, float sum_gx)
+{
+    if (threadIdx.x == 0) {
+        if (a.grad_bn_b) a.grad_bn_b[v] = sum_g;
+        if (a.grad_bn_w) a.grad_bn_w[v] = sum_gx;
+    }
+}
+__device__ __forceinline__ float db_bn_bwd_dz(float kk, float g, float xhat, float mg, float mgx) { return kk * (g - mg - xhat * mgx); }
+__device__ __forceinline__ float4 db_bn_bwd_dz4(float kk, const float4 &g, const float4 &xh, float mg, float mgx, bool mesh_on)
+{
+    float4 dz = make_float4(db_bn_bwd_dz(kk, g.x, xh.x, mg, mgx), db_bn_bwd_dz(kk, g.y, xh.y, mg, mgx), db_bn_bwd_dz(kk, g.z, xh.z, mg, mgx),
+                            db_bn_bwd_dz(kk, g.w, xh.w, mg, mgx));
+    if (!mesh_on) dz = make_float4(0.f, 0.f, 0.f, 0.f);
+    return dz;
+}
+
+// Bias gradient of a layer: the vertex's column sums of `src` (a thread's dZ, summed over its tiles) over its meshes, in mesh
+// order -- lanes 16 apart hold the wave's four rows, the four waves' sums through the staging tile; the host adds the vertices up
+__device__ __forceinline__ void db_colsum(const float4 (&src)[3], float *stage, float *colsum, int v, int c0)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    __syncthreads(); // (the staging tile may still be read above)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        float4 t = src[i];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) {
+            const int from = (lane & 15) + 16 * k;
+            t.x += __shfl(src[i].x, from), t.y += __shfl(src[i].y, from), t.z += __shfl(src[i].z, from), t.w += __shfl(src[i].w, from);
+        }
+        if ((lane >> 4) == 0) *reinterpret_cast<float4 *>(stage + wave * DB_C + c0 + DB_K * i) = t;
+    }
+    __syncthreads();
+    if (tid < DB_C) colsum[(size_t)v * DB_C + tid] = ((stage[tid] + stage[DB_C + tid]) + stage[2 * DB_C + tid]) + stage[3 * DB_C + tid];
+}
+
+// The coordinate head's backward (gc15, 192 -> 3) inside the first backward launch: dS_head . W_head^T of column `col` joins g ...
+__device__ __forceinline__ float db_head_bwd_input(const float (&dsh)[3], const float *w_head, int col)
+{
+    const float *wr = w_head + (size_t)col * 3;
+    return (dsh[0] * wr[0] + dsh[1] * wr[1]) + dsh[2] * wr[2];
+}
+// ... and the vertex's partial of its weight gradient X^T . dS_head goes out with the column sums.  p = the thread's product
+// (summed over its tiles) for (col, o): the rows of a wave (lanes 16 apart, in mesh order) into wsum [4 waves][192 * 3],
+__device__ __forceinline__ void db_head_bwd_weight_rows(float p, float *wsum, int col, int o)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float acc = p;
+#pragma unroll
+    for (int k = 1; k < 4; ++k) acc += __shfl(p, (lane & 15) + 16 * k, GEOM_WAVE);
+    if ((lane >> 4) == 0) wsum[wave * (DB_C * 3) + col * 3 + o] = acc;
+}
+// then the four waves in order
+__device__ __forceinline__ void db_head_bwd_weight_reduce(const float *wsum, float *dw_head, int v)
+{
+    __syncthreads();
+    for (int t = threadIdx.x; t < DB_C * 3; t += DB_THREADS)
+        dw_head[(size_t)v * (DB_C * 3) + t] = ((wsum[t] + wsum[DB_C * 3 + t]) + wsum[2 * DB_C * 3 + t]) + wsum[3 * DB_C * 3 + t];
+    __syncthreads();
+}
+
+// G = [A^T . dZ[:, :64] | dZ[:, 64:]] of the thread's row (an aggregation backward: db_aggregate on the transposed tables),
+// kept in gs and stored at its own place of r_dst.  CHAIN and the wait gave up: NaN, loudly.
+template <bool SLICE, bool CHAIN>
+__device__ __forceinline__ void db_aggregate_and_store_own_row(__amdgpu_buffer_rsrc_t r_src, __amdgpu_buffer_rsrc_t r_dst, bool mesh_on,
+                                                               unsigned rowbase, int v, int c0, const DbTable &tb, float4 (&gs)[3], DbSlice &bw,
+                                                               const float *packed, int wave, int lane, const int *done = nullptr,
+                                                               int need = 0)
+{
+    bool arrived = true;
+    gs[0] = db_aggregate<SLICE, CHAIN>(r_src, mesh_on, rowbase, v, c0, tb, &gs[1], bw, packed, wave, lane, done, need, &arrived);
+    if (CHAIN && !arrived) gs[0].x = __builtin_nanf("");
+    const unsigned own_off = mesh_on ? rowbase + (unsigned)v * (DB_C * 4) + 4 * c0 : DB_OOB;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) db_st4(r_dst, db_own(own_off, i), gs[i]);
+}
+
 // One layer of vertex v.  CHAIN: layer `layer` (0-based) of a chain launch -- layer > 0 reads the previous layer's support
 // rows from the neighbours' workgroups (wait + agent-scope loads), a layer with a product publishes its rows.
 template <bool PRODUCT, bool CHAIN>
@@ -345,10 +572,7 @@ __device__ __forceinline__ void db_fwd_body(const geom_deform_fwd &a, const int 
     const float old_mean = (updates && a.run_mean) ? a.run_mean[v] : 0.f, old_var = (updates && a.run_var) ? a.run_var[v] : 0.f;
     float4 bias4[3], rv[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        bias4[i] = a.bias ? *reinterpret_cast<const float4 *>(a.bias + c0 + DB_K * i) : make_float4(0.f, 0.f, 0.f, 0.f);
-        rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    for (int i = 0; i < 3; ++i) bias4[i] = db_bias4(a, c0, i), rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (a.res) {
         const __amdgpu_buffer_rsrc_t r_res = db_rsrc(a.res, ((int64_t)a.b * a.nv - 1) * a.res_ld * 4 + DB_C * 4);
         const unsigned roff = ((unsigned)rl * (unsigned)a.nv + (unsigned)v) * (unsigned)a.res_ld * 4u + 4 * c0;
@@ -368,75 +592,42 @@ __device__ __forceinline__ void db_fwd_body(const geom_deform_fwd &a, const int 
         z[0] = db_aggregate<PRODUCT, false>(r_src, mesh_on, rowbase, v, c0, tb, &z[1], bw, a.w_next, wave, lane);
     }
     if (CHAIN && !arrived) z[0].x = __builtin_nanf(""); // poisons the vertex's statistics: every output of the layer is NaN
-#pragma unroll
-    for (int i = 0; i < 3; ++i) z[i].x += bias4[i].x, z[i].y += bias4[i].y, z[i].z += bias4[i].z, z[i].w += bias4[i].w;
+    db_add_bias(z, bias4);
 
     DB_STAMP(1); // gathers arrived (z holds the aggregated row)
     // ---- BatchNorm1d(verts): one statistic per vertex over its b * 192 values (two-pass: mean, then the centred second moment)
     float *red = lds + DB_PANEL + DB_CST;
     const int n = a.b * DB_C;
-    float mean, invstd;
+    DbNorm bn;
     if (a.training) {
         float s = 0.f, dummy = 0.f;
-        if (mesh_on) s = (((z[0].x + z[0].y) + (z[0].z + z[0].w)) + ((z[1].x + z[1].y) + (z[1].z + z[1].w))) + ((z[2].x + z[2].y) + (z[2].z + z[2].w));
+        if (mesh_on) s = db_row_sum(z);
         db_sum2(s, dummy, red);
-        mean = s / n;
+        bn.mean = s / n;
         float q = 0.f;
-        if (mesh_on) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const float d0 = z[i].x - mean, d1 = z[i].y - mean, d2 = z[i].z - mean, d3 = z[i].w - mean;
-                q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-            }
-        }
+        if (mesh_on) q = db_row_centred_sq(z, bn.mean);
         dummy = 0.f;
         db_sum2(q, dummy, red);
-        const float var = q / n; // biased, as used for normalisation
-        invstd = 1.f / sqrtf(var + a.eps);
-        if (tid == 0) {
-            a.save_mean[v] = mean, a.save_invstd[v] = invstd;
-            if (a.run_mean) a.run_mean[v] = (1.f - a.momentum) * old_mean + a.momentum * mean;
-            if (a.run_var) a.run_var[v] = (1.f - a.momentum) * old_var + a.momentum * (n > 1 ? q / (n - 1) : var);
-        }
+        bn.invstd = db_publish_stats(a, v, n, bn.mean, q, old_mean, old_var);
     } else {
-        mean = a.run_mean[v];
-        invstd = 1.f / sqrtf(a.run_var[v] + a.eps);
+        bn.mean = a.run_mean[v];
+        bn.invstd = 1.f / sqrtf(a.run_var[v] + a.eps);
     }
+    bn.gamma = gamma, bn.beta = beta;
     DB_STAMP(2); // statistics done
-    auto finish = [&](float zz, float r) {
-        float y = (zz - mean) * invstd * gamma + beta;
-        if (a.relu) y = y > 0.f ? y : 0.f;
-        if (a.res) y = (r + y) * a.scale;
-        return mesh_on ? y : 0.f;
-    };
     float4 xo[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        xo[i] = make_float4(finish(z[i].x, rv[i].x), finish(z[i].y, rv[i].y), finish(z[i].z, rv[i].z), finish(z[i].w, rv[i].w));
+    db_norm_apply(a, bn, z, rv, mesh_on, xo);
     const __amdgpu_buffer_rsrc_t r_z = db_rsrc(a.z_out, op_bytes), r_x = db_rsrc(a.x_out, op_bytes);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        if (a.z_out) db_st4(r_z, own_off == DB_OOB ? DB_OOB : own_off + 4 * DB_K * i, z[i]);
-        db_st4(r_x, own_off == DB_OOB ? DB_OOB : own_off + 4 * DB_K * i, xo[i]);
+        if (a.z_out) db_st4(r_z, db_own(own_off, i), z[i]);
+        db_st4(r_x, db_own(own_off, i), xo[i]);
     }
     if (!PRODUCT) {
-        // ---- the coordinate head's product (models.py:219,295: gc15 = 192 -> 3) inside the last hidden layer's launch:
-        // s_head[row][o] = sum_c X[row][c] W_head[c][o]; a row's 192 columns sit in the 16 lanes of its group
+        // ---- the coordinate head's product inside the last hidden layer's launch
         if (a.w_head && a.s_head) {
-            float h[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const float xv[4] = {xo[i].x, xo[i].y, xo[i].z, xo[i].w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float *wr = a.w_head + (size_t)(c0 + DB_K * i + e) * 3;
-                    h[0] += xv[e] * wr[0], h[1] += xv[e] * wr[1], h[2] += xv[e] * wr[2];
-                }
-            }
-#pragma unroll
-            for (int m = 8; m > 0; m >>= 1) {
-                h[0] += __shfl_xor(h[0], m, GEOM_WAVE), h[1] += __shfl_xor(h[1], m, GEOM_WAVE), h[2] += __shfl_xor(h[2], m, GEOM_WAVE);
-            }
+            float h[3];
+            db_head_fwd(xo, a.w_head, c0, h);
             if (j == 0 && mesh_on) {
                 float *dst = a.s_head + ((size_t)rl * a.nv + v) * 3;
                 dst[0] = h[0], dst[1] = h[1], dst[2] = h[2];
@@ -460,13 +651,7 @@ __device__ __forceinline__ void db_fwd_body(const geom_deform_fwd &a, const int 
     __syncthreads();
     DB_STAMP(7);
     const __amdgpu_buffer_rsrc_t r_s = db_rsrc(a.s_out, op_bytes);
-#pragma unroll
-    for (int t = 0; t < 3; ++t) { // the tile leaves in memory order: 768 contiguous bytes per mesh row
-        const int idx = tid + DB_THREADS * t, r = idx / 48, c4 = idx % 48;
-        const f32x4 val = *reinterpret_cast<const f32x4 *>(stage + r * DB_LDC + 4 * c4);
-        const unsigned off = r < a.b ? ((unsigned)r * (unsigned)a.nv + (unsigned)v) * (DB_C * 4) + 16u * c4 : DB_OOB;
-        db_st4<CHAIN>(r_s, off, make_float4(val[0], val[1], val[2], val[3]));
-    }
+    db_store_tile<CHAIN>(stage, r_s, [&](int r) { return r < a.b ? ((unsigned)r * (unsigned)a.nv + (unsigned)v) * (DB_C * 4) : DB_OOB; });
     DB_STAMP(8);
     if (CHAIN) { // publish: every wave's stores are acknowledged (written through), then the vertex's count moves
         __builtin_amdgcn_s_waitcnt(0);
@@ -518,7 +703,6 @@ __device__ __forceinline__ void db_bwd_body(const geom_deform_bwd &a, const int 
     const int64_t op_bytes = (int64_t)a.b * a.nv * DB_C * 4;
     const unsigned rowbase = (unsigned)rl * (unsigned)a.nv * (DB_C * 4);
     const unsigned own_off = mesh_on ? rowbase + (unsigned)v * (DB_C * 4) + 4 * c0 : DB_OOB;
-    auto at = [&](int i) { return own_off == DB_OOB ? DB_OOB : own_off + 4 * DB_K * i; };
     // everything this layer's BatchNorm backward reads is requested with the gathers
     // g / g2 may be column slices of wider row-major buffers (row pitch g_ld / g2_ld floats; dword-aligned 16-byte buffer loads):
     // the next block's input gradient is read in place instead of through a slicing copy
@@ -533,13 +717,12 @@ __device__ __forceinline__ void db_bwd_body(const geom_deform_bwd &a, const int 
     float4 zv[3], g2v[3], go[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        zv[i] = db_ld4(r_z, at(i));
-        g2v[i] = a.g2 ? db_ld4(r_g2, g2_off == DB_OOB ? DB_OOB : g2_off + 4 * DB_K * i) : make_float4(0.f, 0.f, 0.f, 0.f);
-        if (!PRODUCT) go[i] = a.g ? db_ld4(r_g, g_off == DB_OOB ? DB_OOB : g_off + 4 * DB_K * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        zv[i] = db_ld4(r_z, db_own(own_off, i));
+        g2v[i] = a.g2 ? db_ld4(r_g2, db_own(g2_off, i)) : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!PRODUCT) go[i] = a.g ? db_ld4(r_g, db_own(g_off, i)) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     if (!PRODUCT && a.ds_head) {
-        // ---- the coordinate head (gc15, 192 -> 3) inside the first backward launch: its input gradient dS_head . W_head^T is
-        // added to g, and the vertex's partial of its weight gradient X^T . dS_head goes out with the column sums
+        // ---- the coordinate head inside the first backward launch (db_head_bwd_*)
         float dsh[3] = {0.f, 0.f, 0.f};
         if (mesh_on) {
             const float *src = a.ds_head + ((size_t)rl * a.nv + v) * 3;
@@ -549,50 +732,34 @@ __device__ __forceinline__ void db_bwd_body(const geom_deform_bwd &a, const int 
         float *wsum = lds + DB_PANEL; // [4 waves][192 * 3]
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            const float4 xt = a.dw_head ? db_ld4(r_xt, at(i)) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 xt = a.dw_head ? db_ld4(r_xt, db_own(own_off, i)) : make_float4(0.f, 0.f, 0.f, 0.f);
             const float xv[4] = {xt.x, xt.y, xt.z, xt.w};
             float add[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int col = c0 + DB_K * i + e;
-                const float *wr = a.w_head + (size_t)col * 3;
-                add[e] = (dsh[0] * wr[0] + dsh[1] * wr[1]) + dsh[2] * wr[2];
-                if (a.dw_head) { // rows of a wave: lanes 16 apart, in mesh order; the four waves through LDS
+                add[e] = db_head_bwd_input(dsh, a.w_head, col);
+                if (a.dw_head) {
 #pragma unroll
-                    for (int o = 0; o < 3; ++o) {
-                        const float t = xv[e] * dsh[o];
-                        float acc = t;
-#pragma unroll
-                        for (int k = 1; k < 4; ++k) acc += __shfl(t, (lane & 15) + 16 * k, GEOM_WAVE);
-                        if ((lane >> 4) == 0) wsum[wave * (DB_C * 3) + col * 3 + o] = acc;
-                    }
+                    for (int o = 0; o < 3; ++o) db_head_bwd_weight_rows(xv[e] * dsh[o], wsum, col, o);
                 }
             }
             go[i].x += add[0], go[i].y += add[1], go[i].z += add[2], go[i].w += add[3];
         }
-        if (a.dw_head) {
-            __syncthreads();
-            for (int t = tid; t < DB_C * 3; t += DB_THREADS)
-                a.dw_head[(size_t)v * (DB_C * 3) + t] = ((wsum[t] + wsum[DB_C * 3 + t]) + wsum[2 * DB_C * 3 + t]) + wsum[3 * DB_C * 3 + t];
-            __syncthreads();
-        }
+        if (a.dw_head) db_head_bwd_weight_reduce(wsum, a.dw_head, v);
     }
     float *stage = lds + DB_PANEL;
     if (PRODUCT) {
         // ---- aggregation backward of the layer above: G = [A^T . dZ_up[:, :64] | dZ_up[:, 64:]]
         const __amdgpu_buffer_rsrc_t r_src = db_rsrc(a.dz_up, op_bytes), r_ds = db_rsrc(a.ds_up, op_bytes);
-        float4 gs[3];
+        float4 gs[3]; // (stored: the layer above's weight gradient reads it, X^T . G)
         DbSlice bw;
         if (CHAIN) {
-            bool arrived = true;
-            gs[0] = db_aggregate<true, true>(r_src, mesh_on, rowbase, v, c0, *table, &gs[1], bw, a.wt_up, wave, lane, done, step, &arrived);
-            if (!arrived) gs[0].x = __builtin_nanf(""); // (the wait gave up: the layer's gradients are NaN, loudly)
+            db_aggregate_and_store_own_row<true, true>(r_src, r_ds, mesh_on, rowbase, v, c0, *table, gs, bw, a.wt_up, wave, lane, done, step);
         } else {
             const DbTable tb = db_table(v, a.ell_col_t, a.ell_val_t, a.tail_col_t, a.tail_val_t, lane);
-            gs[0] = db_aggregate<true, false>(r_src, mesh_on, rowbase, v, c0, tb, &gs[1], bw, a.wt_up, wave, lane);
+            db_aggregate_and_store_own_row<true, false>(r_src, r_ds, mesh_on, rowbase, v, c0, tb, gs, bw, a.wt_up, wave, lane);
         }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) db_st4(r_ds, at(i), gs[i]); // the layer above's weight gradient reads it (X^T . G)
         db_to_panel(lds, rl, c0, gs);                           // (rows beyond the batch read zeros: zero rows of the tile)
         DB_STAMP(1); // gathers arrived, G stored + in the panel
         __syncthreads();
@@ -605,68 +772,29 @@ __device__ __forceinline__ void db_bwd_body(const geom_deform_bwd &a, const int 
         DB_STAMP(4);
         __syncthreads();
         DB_STAMP(5);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const f32x4 t = *reinterpret_cast<const f32x4 *>(stage + rl * DB_LDC + c0 + DB_K * i);
-            go[i] = make_float4(t[0], t[1], t[2], t[3]);
-        }
+        db_load_tile(stage, rl, c0, go);
     }
     // ---- this layer: residual scale, ReLU mask, BatchNorm backward
     float sum_g = 0.f, sum_gx = 0.f;
     float4 xh[3];
     const __amdgpu_buffer_rsrc_t r_gr = db_rsrc(a.grad_res, op_bytes), r_dz = db_rsrc(a.dz, op_bytes);
-    auto one = [&](float zz, float &gg, float second, float &xhat) {
-        xhat = (zz - mean) * invstd;
-        gg += second;
-        if (a.has_res) gg *= a.scale;
-        const float pass = gg;
-        if (a.relu && !(xhat * gamma + beta > 0.f)) gg = 0.f;
-        if (!mesh_on) gg = 0.f;
-        sum_g += gg;
-        sum_gx += gg * xhat;
-        return pass;
-    };
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float4 r = make_float4(one(zv[i].x, go[i].x, g2v[i].x, xh[i].x), one(zv[i].y, go[i].y, g2v[i].y, xh[i].y),
-                                     one(zv[i].z, go[i].z, g2v[i].z, xh[i].z), one(zv[i].w, go[i].w, g2v[i].w, xh[i].w));
-        if (a.has_res && a.grad_res) db_st4(r_gr, at(i), r);
-    }
+    for (int i = 0; i < 3; ++i)
+        db_bn_bwd_elems(a, mean, invstd, gamma, beta, mesh_on, zv[i], go[i], g2v[i], xh[i], sum_g, sum_gx, r_gr, db_own(own_off, i));
     float *red = lds + DB_PANEL + DB_CST;
     DB_STAMP(6);
     db_sum2(sum_g, sum_gx, red);
     DB_STAMP(7);
-    if (tid == 0) {
-        if (a.grad_bn_b) a.grad_bn_b[v] = sum_g;
-        if (a.grad_bn_w) a.grad_bn_w[v] = sum_gx;
-    }
+    db_publish_bn_grads(a, v, sum_g, sum_gx);
     const int n = a.b * DB_C;
     const float kk = gamma * invstd, mg = sum_g / n, mgx = sum_gx / n;
     float4 dz[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        dz[i] = make_float4(kk * (go[i].x - mg - xh[i].x * mgx), kk * (go[i].y - mg - xh[i].y * mgx),
-                            kk * (go[i].z - mg - xh[i].z * mgx), kk * (go[i].w - mg - xh[i].w * mgx));
-        if (!mesh_on) dz[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        db_st4<CHAIN>(r_dz, at(i), dz[i]);
+        dz[i] = db_bn_bwd_dz4(kk, go[i], xh[i], mg, mgx, mesh_on);
+        db_st4<CHAIN>(r_dz, db_own(own_off, i), dz[i]);
     }
-    // ---- bias gradient of this layer: the vertex's column sums of dZ over its meshes, in mesh order (lanes 16 apart hold the
-    // wave's four meshes, the four waves' sums through LDS); the host adds the vertices up
-    if (a.colsum) {
-        __syncthreads(); // (the staging tile may still be read above)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            float4 t = dz[i];
-#pragma unroll
-            for (int k = 1; k < 4; ++k) {
-                const int src = (lane & 15) + 16 * k;
-                t.x += __shfl(dz[i].x, src), t.y += __shfl(dz[i].y, src), t.z += __shfl(dz[i].z, src), t.w += __shfl(dz[i].w, src);
-            }
-            if ((lane >> 4) == 0) *reinterpret_cast<float4 *>(stage + wave * DB_C + c0 + DB_K * i) = t;
-        }
-        __syncthreads();
-        if (tid < DB_C) a.colsum[(size_t)v * DB_C + tid] = ((stage[tid] + stage[DB_C + tid]) + stage[2 * DB_C + tid]) + stage[3 * DB_C + tid];
-    }
+    if (a.colsum) db_colsum(dz, stage, a.colsum, v, c0); // the bias gradient of this layer
     DB_STAMP(8);
     if (CHAIN) { // publish the vertex's dZ rows (every wave's stores acknowledged first)
         __builtin_amdgcn_s_waitcnt(0);
@@ -715,12 +843,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void db_bwd_chain_kernel(DbBwdChain 
         const __amdgpu_buffer_rsrc_t r_src = db_rsrc(a.dz, op_bytes), r_ds = db_rsrc(c.ds_first, op_bytes);
         float4 gs[3];
         DbSlice none;
-        bool arrived = true;
-        gs[0] = db_aggregate<false, true>(r_src, mesh_on, rowbase, v, c0, tb, &gs[1], none, nullptr, wave, lane, c.done, c.count, &arrived);
-        if (!arrived) gs[0].x = __builtin_nanf("");
-        const unsigned own_off = mesh_on ? rowbase + (unsigned)v * (DB_C * 4) + 4 * c0 : DB_OOB;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) db_st4(r_ds, own_off == DB_OOB ? DB_OOB : own_off + 4 * DB_K * i, gs[i]);
+        db_aggregate_and_store_own_row<false, true>(r_src, r_ds, mesh_on, rowbase, v, c0, tb, gs, none, nullptr, wave, lane, c.done, c.count);
     }
 }
 
@@ -776,12 +899,10 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
     const int tail0 = a.tail_col ? a.tail_col[(size_t)v * DB_TAIL] : -1;
     const float gamma = a.bn_w ? a.bn_w[v] : 1.f, beta = a.bn_b ? a.bn_b[v] : 0.f;
     const float mean = a.run_mean[v], invstd = 1.f / sqrtf(a.run_var[v] + a.eps);
+    const DbNorm bn = {mean, invstd, gamma, beta};
     float4 bias4[3], rv[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        bias4[i] = a.bias ? *reinterpret_cast<const float4 *>(a.bias + c0 + DB_K * i) : make_float4(0.f, 0.f, 0.f, 0.f);
-        rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    for (int i = 0; i < 3; ++i) bias4[i] = db_bias4(a, c0, i), rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (a.res) {
         const __amdgpu_buffer_rsrc_t r_res = db_rsrc(a.res, ((int64_t)rows - 1) * a.res_ld * 4 + DB_C * 4);
         const unsigned roff = (unsigned)r * (unsigned)a.res_ld * 4u + 4 * c0;
@@ -795,7 +916,7 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
     constexpr int ROUND = LOAD_SLICE || !PRODUCT ? DB_W : DB_W / 2;
     float4 z[3];
 #pragma unroll
-    for (int i = 1; i < 3; ++i) z[i] = db_ld4(r_src, on ? own_off + 4 * DB_K * i : DB_OOB);
+    for (int i = 1; i < 3; ++i) z[i] = db_ld4(r_src, db_own(own_off, i));
     float4 facc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int n0 = 0; n0 < DB_W; n0 += ROUND) {
@@ -830,42 +951,19 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
         }
     }
     z[0] = facc;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) z[i].x += bias4[i].x, z[i].y += bias4[i].y, z[i].z += bias4[i].z, z[i].w += bias4[i].w;
-    // BatchNorm on the running statistics: the operations and order of geom_vertex_bn_fwd_f32 (no folded scale / shift)
-    auto finish = [&](float zz, float res) {
-        float y = (zz - mean) * invstd * gamma + beta;
-        if (a.relu) y = y > 0.f ? y : 0.f;
-        if (a.res) y = (res + y) * a.scale;
-        return on ? y : 0.f;
-    };
+    db_add_bias(z, bias4);
     float4 xo[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        xo[i] = make_float4(finish(z[i].x, rv[i].x), finish(z[i].y, rv[i].y), finish(z[i].z, rv[i].z), finish(z[i].w, rv[i].w));
+    db_norm_apply(a, bn, z, rv, on, xo); // BatchNorm on the running statistics
     if (a.x_out) {
         const __amdgpu_buffer_rsrc_t r_x = db_rsrc(a.x_out, op_bytes);
 #pragma unroll
-        for (int i = 0; i < 3; ++i) db_st4(r_x, own_off == DB_OOB ? DB_OOB : own_off + 4 * DB_K * i, xo[i]);
+        for (int i = 0; i < 3; ++i) db_st4(r_x, db_own(own_off, i), xo[i]);
     }
     if (!PRODUCT) {
-        // the coordinate head's raw support s_head[row] = X'[row] . W_head (as db_fwd_body: a row's 192 columns sit in the 16
-        // lanes of its group)
+        // the coordinate head's raw support s_head[row] = X'[row] . W_head
         if (a.w_head) {
-            float h[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const float xv[4] = {xo[i].x, xo[i].y, xo[i].z, xo[i].w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float *wr = a.w_head + (size_t)(c0 + DB_K * i + e) * 3;
-                    h[0] += xv[e] * wr[0], h[1] += xv[e] * wr[1], h[2] += xv[e] * wr[2];
-                }
-            }
-#pragma unroll
-            for (int m = 8; m > 0; m >>= 1) {
-                h[0] += __shfl_xor(h[0], m, GEOM_WAVE), h[1] += __shfl_xor(h[1], m, GEOM_WAVE), h[2] += __shfl_xor(h[2], m, GEOM_WAVE);
-            }
+            float h[3];
+            db_head_fwd(xo, a.w_head, c0, h);
             if (j == 0 && on) {
                 float *dst = a.s_head + (size_t)r * 3;
                 dst[0] = h[0], dst[1] = h[1], dst[2] = h[2];
@@ -880,13 +978,10 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
     db_product(bw, lds, stage, wave, x, g);
     __syncthreads();
     const __amdgpu_buffer_rsrc_t r_s = db_rsrc(a.s_out, op_bytes);
-#pragma unroll
-    for (int t = 0; t < 3; ++t) { // the tile leaves in memory order: 16 consecutive rows = 12 KB contiguous
-        const int idx = tid + DB_THREADS * t, rr = idx / 48, c4 = idx % 48;
-        const f32x4 val = *reinterpret_cast<const f32x4 *>(stage + rr * DB_LDC + 4 * c4);
+    db_store_tile<false>(stage, r_s, [&](int rr) { // (16 consecutive rows = 12 KB contiguous)
         const int row = rb * 16 + rr;
-        db_st4(r_s, row < rows ? (unsigned)row * (DB_C * 4) + 16u * c4 : DB_OOB, make_float4(val[0], val[1], val[2], val[3]));
-    }
+        return row < rows ? (unsigned)row * (DB_C * 4) : DB_OOB;
+    });
     // (the next row-block writes the panel, which nobody reads any more; the staging tile only after its first barrier)
 }
 
@@ -953,7 +1048,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd 
     const float old_mean = (updates && a.run_mean) ? a.run_mean[v] : 0.f, old_var = (updates && a.run_var) ? a.run_var[v] : 0.f;
     float4 bias4[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) bias4[i] = a.bias ? *reinterpret_cast<const float4 *>(a.bias + c0 + DB_K * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = 0; i < 3; ++i) bias4[i] = db_bias4(a, c0, i);
     const DbTable tb = db_table(v, a.ell_col, a.ell_val, a.tail_col, a.tail_val, lane);
 
     // ---- 1. the tiles' aggregations
@@ -967,11 +1062,10 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd 
             const int mesh = 16 * t + rl;
             const unsigned rowbase = (unsigned)mesh * (unsigned)a.nv * (DB_C * 4);
             z[t][0] = db_aggregate<false, false>(r_src, mesh < a.b, rowbase, v, c0, tb, &z[t][1], bw, nullptr, wave, lane);
+            db_add_bias(z[t], bias4);
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                z[t][i].x += bias4[i].x, z[t][i].y += bias4[i].y, z[t][i].z += bias4[i].z, z[t][i].w += bias4[i].w;
-                if (a.z_out) db_st4(r_z, own(t) == DB_OOB ? DB_OOB : own(t) + 4 * DB_K * i, z[t][i]);
-            }
+            for (int i = 0; i < 3; ++i)
+                if (a.z_out) db_st4(r_z, db_own(own(t), i), z[t][i]);
         }
     }
     // ---- 2. the weight slice for all tiles, and the first tile's residual, under the statistics
@@ -984,41 +1078,30 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd 
     // ---- 3. BatchNorm1d(verts): one statistic per vertex over its b * 192 values (two-pass: mean, then the centred second moment)
     float *red = lds + DB_PANEL + DB_CST;
     const int n = a.b * DB_C;
-    float mean, invstd;
+    DbNorm bn;
     if (a.training) {
         float s = 0.f, dummy = 0.f;
 #pragma unroll
         for (int t = 0; t < DBW_TILES; ++t) {
-            const float4 *zt = z[t];
-            const float st = (((zt[0].x + zt[0].y) + (zt[0].z + zt[0].w)) + ((zt[1].x + zt[1].y) + (zt[1].z + zt[1].w))) + ((zt[2].x + zt[2].y) + (zt[2].z + zt[2].w));
+            const float st = db_row_sum(z[t]);
             if (16 * t + rl < a.b) s += st;
         }
         db_sum2(s, dummy, red);
-        mean = s / n;
+        bn.mean = s / n;
         float q = 0.f;
 #pragma unroll
         for (int t = 0; t < DBW_TILES; ++t) {
-            float qt = 0.f;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const float d0 = z[t][i].x - mean, d1 = z[t][i].y - mean, d2 = z[t][i].z - mean, d3 = z[t][i].w - mean;
-                qt += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-            }
+            const float qt = db_row_centred_sq(z[t], bn.mean);
             if (16 * t + rl < a.b) q += qt;
         }
         dummy = 0.f;
         db_sum2(q, dummy, red);
-        const float var = q / n; // biased, as used for normalisation
-        invstd = 1.f / sqrtf(var + a.eps);
-        if (tid == 0) {
-            a.save_mean[v] = mean, a.save_invstd[v] = invstd;
-            if (a.run_mean) a.run_mean[v] = (1.f - a.momentum) * old_mean + a.momentum * mean;
-            if (a.run_var) a.run_var[v] = (1.f - a.momentum) * old_var + a.momentum * (n > 1 ? q / (n - 1) : var);
-        }
+        bn.invstd = db_publish_stats(a, v, n, bn.mean, q, old_mean, old_var);
     } else {
-        mean = a.run_mean[v];
-        invstd = 1.f / sqrtf(a.run_var[v] + a.eps);
+        bn.mean = a.run_mean[v];
+        bn.invstd = 1.f / sqrtf(a.run_var[v] + a.eps);
     }
+    bn.gamma = gamma, bn.beta = beta;
 
     // ---- 4. the tiles' outputs and products
     float *stage = lds + DB_PANEL;
@@ -1031,35 +1114,15 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd 
 #pragma unroll
             for (int i = 0; i < 3; ++i) rv[i] = rvn[i];
             if (t + 1 < tiles) residual(t + 1, rvn);
-            auto finish = [&](float zz, float r) {
-                float y = (zz - mean) * invstd * gamma + beta;
-                if (a.relu) y = y > 0.f ? y : 0.f;
-                if (a.res) y = (r + y) * a.scale;
-                return mesh_on ? y : 0.f;
-            };
             float4 xo[3];
+            db_norm_apply(a, bn, z[t], rv, mesh_on, xo);
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                xo[i] = make_float4(finish(z[t][i].x, rv[i].x), finish(z[t][i].y, rv[i].y), finish(z[t][i].z, rv[i].z), finish(z[t][i].w, rv[i].w));
-                db_st4(r_x, own(t) == DB_OOB ? DB_OOB : own(t) + 4 * DB_K * i, xo[i]);
-            }
+            for (int i = 0; i < 3; ++i) db_st4(r_x, db_own(own(t), i), xo[i]);
             if (!PRODUCT) {
-                // the coordinate head's product inside the last hidden layer's launch (as db_fwd_body)
+                // the coordinate head's product inside the last hidden layer's launch
                 if (a.w_head && a.s_head) {
-                    float h[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-                        const float xv[4] = {xo[i].x, xo[i].y, xo[i].z, xo[i].w};
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float *wr = a.w_head + (size_t)(c0 + DB_K * i + e) * 3;
-                            h[0] += xv[e] * wr[0], h[1] += xv[e] * wr[1], h[2] += xv[e] * wr[2];
-                        }
-                    }
-#pragma unroll
-                    for (int m = 8; m > 0; m >>= 1) {
-                        h[0] += __shfl_xor(h[0], m, GEOM_WAVE), h[1] += __shfl_xor(h[1], m, GEOM_WAVE), h[2] += __shfl_xor(h[2], m, GEOM_WAVE);
-                    }
+                    float h[3];
+                    db_head_fwd(xo, a.w_head, c0, h);
                     if (j == 0 && mesh_on) {
                         float *dst = a.s_head + ((size_t)(16 * t + rl) * a.nv + v) * 3;
                         dst[0] = h[0], dst[1] = h[1], dst[2] = h[2];
@@ -1071,13 +1134,10 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd 
                 __syncthreads();
                 db_product(bw, lds, stage, wave, x, g);
                 __syncthreads();
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { // the tile leaves in memory order: 768 contiguous bytes per mesh row
-                    const int idx = tid + DB_THREADS * k, r = idx / 48, c4 = idx % 48, mesh = 16 * t + r;
-                    const f32x4 val = *reinterpret_cast<const f32x4 *>(stage + r * DB_LDC + 4 * c4);
-                    const unsigned off = mesh < a.b ? ((unsigned)mesh * (unsigned)a.nv + (unsigned)v) * (DB_C * 4) + 16u * c4 : DB_OOB;
-                    db_st4(r_s, off, make_float4(val[0], val[1], val[2], val[3]));
-                }
+                db_store_tile<false>(stage, r_s, [&](int r) {
+                    const int mesh = 16 * t + r;
+                    return mesh < a.b ? ((unsigned)mesh * (unsigned)a.nv + (unsigned)v) * (DB_C * 4) : DB_OOB;
+                });
                 __syncthreads(); // (the staging tile is free for the next tile's product)
             }
         }
@@ -1140,11 +1200,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd 
                 __syncthreads();
                 db_product(bw, lds, stage, wave, x, g);
                 __syncthreads();
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const f32x4 r = *reinterpret_cast<const f32x4 *>(stage + rl * DB_LDC + c0 + DB_K * i);
-                    go[t][i] = make_float4(r[0], r[1], r[2], r[3]);
-                }
+                db_load_tile(stage, rl, c0, go[t]);
                 __syncthreads(); // (the staging tile is free for the next tile's product)
             }
         }
@@ -1156,7 +1212,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd 
                 for (int i = 0; i < 3; ++i) go[t][i] = db_ld4(r_g, at(t, i, g_ld));
             }
         if (a.ds_head) {
-            // ---- the coordinate head inside the first backward launch (as db_bwd_body): its input gradient joins g; the vertex's
+            // ---- the coordinate head inside the first backward launch (db_head_bwd_*): its input gradient joins g; the vertex's
             // partial of its weight gradient: per thread over its tiles in tile order, then the wave's rows, then the waves
             const __amdgpu_buffer_rsrc_t r_xt = db_rsrc(a.x_top, op_bytes);
             float *wsum = lds + DB_PANEL; // [4 waves][192 * 3]
@@ -1183,8 +1239,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd 
                         float add[4];
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const float *wr = a.w_head + (size_t)(c0 + DB_K * i + e) * 3;
-                            add[e] = (dsh[0] * wr[0] + dsh[1] * wr[1]) + dsh[2] * wr[2];
+                            add[e] = db_head_bwd_input(dsh, a.w_head, c0 + DB_K * i + e);
 #pragma unroll
                             for (int o = 0; o < 3; ++o) part[i][e][o] += xv[e] * dsh[o];
                         }
@@ -1198,56 +1253,31 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd 
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
 #pragma unroll
-                        for (int o = 0; o < 3; ++o) {
-                            const float p = part[i][e][o];
-                            float acc = p;
-#pragma unroll
-                            for (int k = 1; k < 4; ++k) acc += __shfl(p, (lane & 15) + 16 * k, GEOM_WAVE);
-                            if ((lane >> 4) == 0) wsum[wave * (DB_C * 3) + (c0 + DB_K * i + e) * 3 + o] = acc;
-                        }
-                __syncthreads();
-                for (int k = tid; k < DB_C * 3; k += DB_THREADS)
-                    a.dw_head[(size_t)v * (DB_C * 3) + k] = ((wsum[k] + wsum[DB_C * 3 + k]) + wsum[2 * DB_C * 3 + k]) + wsum[3 * DB_C * 3 + k];
-                __syncthreads();
+                        for (int o = 0; o < 3; ++o) db_head_bwd_weight_rows(part[i][e][o], wsum, c0 + DB_K * i + e, o);
+                db_head_bwd_weight_reduce(wsum, a.dw_head, v);
             }
         }
     }
     // ---- 4. this layer: residual scale, ReLU mask, the two sums of the BatchNorm backward over all tiles
     float sum_g = 0.f, sum_gx = 0.f;
-    float4 zv[DBW_TILES][3];
+    float4 xh[DBW_TILES][3];
 #pragma unroll
     for (int t = 0; t < DBW_TILES; ++t) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) zv[t][i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int i = 0; i < 3; ++i) xh[t][i] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (t < tiles) {
             const bool mesh_on = 16 * t + rl < a.b;
-            auto one = [&](float zz, float &gg, float second) {
-                const float xhat = (zz - mean) * invstd;
-                gg += second;
-                if (a.has_res) gg *= a.scale;
-                const float pass = gg;
-                if (a.relu && !(xhat * gamma + beta > 0.f)) gg = 0.f;
-                if (!mesh_on) gg = 0.f;
-                sum_g += gg;
-                sum_gx += gg * xhat;
-                return pass;
-            };
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                zv[t][i] = db_ld4(r_z, at(t, i, DB_C));
+                const float4 zv = db_ld4(r_z, at(t, i, DB_C));
                 const float4 s = a.g2 ? db_ld4(r_g2, at(t, i, g2_ld)) : make_float4(0.f, 0.f, 0.f, 0.f);
-                const float4 r = make_float4(one(zv[t][i].x, go[t][i].x, s.x), one(zv[t][i].y, go[t][i].y, s.y),
-                                             one(zv[t][i].z, go[t][i].z, s.z), one(zv[t][i].w, go[t][i].w, s.w));
-                if (a.has_res && a.grad_res) db_st4(r_gr, at(t, i, DB_C), r);
+                db_bn_bwd_elems(a, mean, invstd, gamma, beta, mesh_on, zv, go[t][i], s, xh[t][i], sum_g, sum_gx, r_gr, at(t, i, DB_C));
             }
         }
     }
     float *red = lds + DB_PANEL + DB_CST;
     db_sum2(sum_g, sum_gx, red);
-    if (tid == 0) {
-        if (a.grad_bn_b) a.grad_bn_b[v] = sum_g;
-        if (a.grad_bn_w) a.grad_bn_w[v] = sum_gx;
-    }
+    db_publish_bn_grads(a, v, sum_g, sum_gx);
     // ---- 5. dZ, and the vertex's column sums of dZ over its meshes (per thread over its tiles, the wave's rows, the waves)
     const int n = a.b * DB_C;
     const float kk = gamma * invstd, mg = sum_g / n, mgx = sum_gx / n;
@@ -1260,30 +1290,13 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd 
             const bool mesh_on = 16 * t + rl < a.b;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                const float4 zz = zv[t][i], gg = go[t][i];
-                float4 dz = make_float4(kk * (gg.x - mg - (zz.x - mean) * invstd * mgx), kk * (gg.y - mg - (zz.y - mean) * invstd * mgx),
-                                        kk * (gg.z - mg - (zz.z - mean) * invstd * mgx), kk * (gg.w - mg - (zz.w - mean) * invstd * mgx));
-                if (!mesh_on) dz = make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 dz = db_bn_bwd_dz4(kk, go[t][i], xh[t][i], mg, mgx, mesh_on);
                 db_st4(r_dz, at(t, i, DB_C), dz);
                 cs[i].x += dz.x, cs[i].y += dz.y, cs[i].z += dz.z, cs[i].w += dz.w;
             }
         }
     }
-    if (a.colsum) {
-        __syncthreads(); // (the staging tile may still be read above)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            float4 t = cs[i];
-#pragma unroll
-            for (int k = 1; k < 4; ++k) {
-                const int src = (lane & 15) + 16 * k;
-                t.x += __shfl(cs[i].x, src), t.y += __shfl(cs[i].y, src), t.z += __shfl(cs[i].z, src), t.w += __shfl(cs[i].w, src);
-            }
-            if ((lane >> 4) == 0) *reinterpret_cast<float4 *>(stage + wave * DB_C + c0 + DB_K * i) = t;
-        }
-        __syncthreads();
-        if (tid < DB_C) a.colsum[(size_t)v * DB_C + tid] = ((stage[tid] + stage[DB_C + tid]) + stage[2 * DB_C + tid]) + stage[3 * DB_C + tid];
-    }
+    if (a.colsum) db_colsum(cs, stage, a.colsum, v, c0);
 }
 
 inline bool db_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
@@ -1315,6 +1328,7 @@ int db_check_fwd(geom_deform_fwd &a)
 {
     if (!db_fwd_operands_ok(a) || !a.x_out || !db_aligned16(a.z_out)) return GEOM_EINVAL;
     if (a.training ? (!a.save_mean || !a.save_invstd) : (!a.run_mean || !a.run_var)) return GEOM_EINVAL;
+    if (a.res && (int64_t)a.b * a.nv * a.res_ld >= (1LL << 29)) return GEOM_EUNSUPPORTED; // 32-bit byte offsets of the residual
     if (!a.res) a.scale = 1.f;
     a.vpx = (a.nv + 7) / 8;
     return 0;
@@ -1339,6 +1353,29 @@ int db_check_bwd(geom_deform_bwd &a)
     return 0;
 }
 
+// whether the layer's launch carries a product (forward: the next layer's; backward: the input gradient of the layer above)
+inline bool db_has_product(const geom_deform_fwd &a) { return a.w_next != nullptr; }
+inline bool db_has_product(const geom_deform_bwd &a) { return a.dz_up != nullptr; }
+inline int db_check_layer(geom_deform_fwd &a) { return db_check_fwd(a); }
+inline int db_check_layer(geom_deform_bwd &a) { return db_check_bwd(a); }
+
+template <typename Args, void (*WITH_PRODUCT)(Args), void (*WITHOUT)(Args)>
+int db_launch_layer(const Args *args, void *stream, int min_b, int max_b)
+{
+    if (!args) return GEOM_EINVAL;
+    Args a = *args;
+    int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w, max_b);
+    if (code) return code;
+    if (a.b == 0 || a.nv == 0) return 0;
+    if (a.b <= min_b) return GEOM_EUNSUPPORTED;
+    if ((code = db_check_layer(a))) return code;
+    const dim3 grid(8 * a.vpx), block(DB_THREADS);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (db_has_product(a)) hipLaunchKernelGGL(WITH_PRODUCT, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(WITHOUT, grid, block, 0, s, a);
+    return geom::launch_status();
+}
+
 } // namespace
 
 #ifdef DB_PROBE_STAMPS
@@ -1348,69 +1385,28 @@ extern "C" int geom_db_probe_read(unsigned long long *dst, int n)
 }
 #endif
 
+// The four launches of ONE layer: plain (a vertex's 1 <= b <= 16 rows are one row tile) and wide (17 <= b <=
+// GEOM_DEFORM_WIDE_MAX_B: ceil(b / 16) tiles), forward and backward, have one set of checks in one order -- the first failing
+// one decides the code -- and one launch shape.  A batch outside the entry's window (min_b, max_b] belongs to the other entry
+// point: GEOM_EUNSUPPORTED.
 extern "C" int geom_deform_layer_fwd_f32(const geom_deform_fwd *args, void *stream)
 {
-    if (!args) return GEOM_EINVAL;
-    geom_deform_fwd a = *args;
-    int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w);
-    if (code) return code;
-    if (a.b == 0 || a.nv == 0) return 0;
-    if ((code = db_check_fwd(a))) return code;
-    const dim3 grid(8 * a.vpx), block(DB_THREADS);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (a.w_next) hipLaunchKernelGGL((db_fwd_kernel<true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((db_fwd_kernel<false>), grid, block, 0, s, a);
-    return geom::launch_status();
+    return db_launch_layer<geom_deform_fwd, db_fwd_kernel<true>, db_fwd_kernel<false>>(args, stream, 0, 16);
 }
 
 extern "C" int geom_deform_layer_bwd_f32(const geom_deform_bwd *args, void *stream)
 {
-    if (!args) return GEOM_EINVAL;
-    geom_deform_bwd a = *args;
-    int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w);
-    if (code) return code;
-    if (a.b == 0 || a.nv == 0) return 0;
-    if ((code = db_check_bwd(a))) return code;
-    const dim3 grid(8 * a.vpx), block(DB_THREADS);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (a.dz_up) hipLaunchKernelGGL((db_bwd_kernel<true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((db_bwd_kernel<false>), grid, block, 0, s, a);
-    return geom::launch_status();
+    return db_launch_layer<geom_deform_bwd, db_bwd_kernel<true>, db_bwd_kernel<false>>(args, stream, 0, 16);
 }
 
-// The same layers at 17 <= b <= GEOM_DEFORM_WIDE_MAX_B meshes: ceil(b / 16) row tiles per vertex (dbw_fwd_kernel /
-// dbw_bwd_kernel).  Checks and codes of the plain entry points; b <= 16 belongs to those: GEOM_EUNSUPPORTED here.
 extern "C" int geom_deform_layer_wide_fwd_f32(const geom_deform_fwd *args, void *stream)
 {
-    if (!args) return GEOM_EINVAL;
-    geom_deform_fwd a = *args;
-    int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w, GEOM_DEFORM_WIDE_MAX_B);
-    if (code) return code;
-    if (a.b == 0 || a.nv == 0) return 0;
-    if (a.b <= 16) return GEOM_EUNSUPPORTED;
-    if ((code = db_check_fwd(a))) return code;
-    if (a.res && (int64_t)a.b * a.nv * a.res_ld >= (1LL << 29)) return GEOM_EUNSUPPORTED; // 32-bit byte offsets of the residual
-    const dim3 grid(8 * a.vpx), block(DB_THREADS);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (a.w_next) hipLaunchKernelGGL((dbw_fwd_kernel<true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((dbw_fwd_kernel<false>), grid, block, 0, s, a);
-    return geom::launch_status();
+    return db_launch_layer<geom_deform_fwd, dbw_fwd_kernel<true>, dbw_fwd_kernel<false>>(args, stream, 16, GEOM_DEFORM_WIDE_MAX_B);
 }
 
 extern "C" int geom_deform_layer_wide_bwd_f32(const geom_deform_bwd *args, void *stream)
 {
-    if (!args) return GEOM_EINVAL;
-    geom_deform_bwd a = *args;
-    int code = db_check_shape(a.b, a.nv, a.c, a.k, a.ell_w, GEOM_DEFORM_WIDE_MAX_B);
-    if (code) return code;
-    if (a.b == 0 || a.nv == 0) return 0;
-    if (a.b <= 16) return GEOM_EUNSUPPORTED;
-    if ((code = db_check_bwd(a))) return code;
-    const dim3 grid(8 * a.vpx), block(DB_THREADS);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (a.dz_up) hipLaunchKernelGGL((dbw_bwd_kernel<true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((dbw_bwd_kernel<false>), grid, block, 0, s, a);
-    return geom::launch_status();
+    return db_launch_layer<geom_deform_bwd, dbw_bwd_kernel<true>, dbw_bwd_kernel<false>>(args, stream, 16, GEOM_DEFORM_WIDE_MAX_B);
 }
 
 // `count` backward layers in execution order (layers[0] = the top layer, read from memory: dz_up == NULL; layers[t].dz_up ==

@@ -61,6 +61,10 @@ relu = True         # tests only: False drops the ReLU of every hidden layer (a 
 #                     side in any two fp32 evaluations and switch a whole unit's term)
 
 
+# rows * pitch (floats) of an operand the launches address with 32-bit byte offsets must stay below this
+OFFSET_LIMIT = 2 ** 29
+
+
 def hidden_layers(block):
     """(gc1..gc13, bn1..bn13) of a models.BatchMeshDeformationBlock."""
     return ([getattr(block, "gc%d" % i) for i in range(1, LAYERS + 1)], [getattr(block, "bn%d" % i) for i in range(1, LAYERS + 1)])
@@ -76,7 +80,7 @@ def _servable(block, features, pooled, csr):
     if not (features.is_cuda and features.dtype == torch.float32 and pooled.is_cuda and pooled.dtype == torch.float32
             and features.dim() == 3):
         return False
-    if features.shape[0] * features.shape[1] * 192 >= 2 ** 29:
+    if features.shape[0] * features.shape[1] * 192 >= OFFSET_LIMIT:
         return False
     if csr.ell_w != 8 or _tail_tables(csr) is False:
         return False
@@ -240,15 +244,19 @@ def chain_forward(layers, done, device):
         _lib.call("geom_deform_chain_fwd_f32", len(layers), ctypes.addressof(structs), done.data_ptr())
 
 
-def rows_operand(t, shape):
+def rows_operand(t, shape, limit=None):
     """(tensor, row pitch in floats) of a [B,V,C] operand (a residual, a gradient) as the kernels read it: in place when it is
     fp32 on the device, row-major with contiguous rows at any pitch (a column slice of a wider buffer), a contiguous copy
-    otherwise.  None -> (None, 0)."""
+    otherwise.  limit: the launch's bound on b * nv * pitch (OFFSET_LIMIT for a residual: its 32-bit byte offsets) -- a wider
+    pitch that would reach it (the leading columns of a 963 / 1155-wide block input) is copied to pitch C, which the bound on
+    b * nv * 192 that _servable checks keeps below it.  None -> (None, 0)."""
     if t is None:
         return None, 0
     b, nv, c = shape
     ok = (t.dim() == 3 and tuple(t.shape) == (b, nv, c) and t.is_cuda and t.dtype == torch.float32 and t.stride(2) == 1
           and t.stride(1) >= c and t.stride(0) == nv * t.stride(1) and t.data_ptr() % 4 == 0)
+    if ok and limit is not None and b * nv * t.stride(1) >= limit:
+        ok = False
     if not ok:
         t = t.contiguous()
     return t, t.stride(1)
@@ -314,7 +322,8 @@ class _HiddenChain(torch.autograd.Function):
         biases, weights = params[:L], params[L:2 * L - 1]
         bn_w, bn_b = params[2 * L - 1:3 * L - 1], params[3 * L - 1:4 * L - 1]
         s1 = _lib.require(s1, "s1", torch.float32, 3, 192)
-        lead, _ = rows_operand(lead, tuple(s1.shape))       # in place when it is the leading columns of the block's wide input
+        # in place when it is the leading columns of the block's wide input (a copy where its byte offsets would pass 32 bits)
+        lead, _ = rows_operand(lead, tuple(s1.shape), OFFSET_LIMIT)
         b, nv, c = s1.shape
         dev = s1.device
         f32 = dict(dtype=torch.float32, device=dev)
@@ -467,12 +476,7 @@ def infer_layer_forward(s_in, bias, csr, bn_w, bn_b, run_mean, run_var, eps, rel
     (+ res, * scale); s_out = x_out . W_next (w_next PACKED: pack_weights()[0][l]) or, on the last layer, s_head = x_out . w_head."""
     b, nv, c = s_in.shape
     tail = _tail_tables(csr)
-    res, res_ld = rows_operand(res, (b, nv, c))
-    if res is not None and b * nv * res_ld >= 2 ** 29:
-        # a residual read in place at a wide pitch (the leading columns of a 963 / 1155-wide block input) whose byte offsets
-        # would pass 32 bits: a contiguous copy (pitch 192, within the limit serves_inference checks)
-        res = res.contiguous()
-        res_ld = res.stride(1)
+    res, res_ld = rows_operand(res, (b, nv, c), OFFSET_LIMIT)
     a = _lib.DeformInfer(b, nv, c, 64, csr.ell_w, _p(s_in), _p(bias), _p(csr.ell_col), _p(csr.ell_val), _p(tail[0]), _p(tail[1]),
                          _p(bn_w), _p(bn_b), _p(run_mean), _p(run_var), float(eps), int(relu), _p(res), res_ld, float(scale),
                          _p(x_out), _p(w_next), _p(s_out), _p(w_head), _p(s_head))

@@ -78,6 +78,8 @@ FWD_ROWS = [
     (dict(tail_col="p17"), -1, -1),
     (dict(res="p18", res_ld=191), -1, -1),
     (dict(res="p18", res_ld=0), -1, -1),
+    (dict(res="p18", res_ld=70000), -3, -3),              # 16 * 482 * 70000 >= 2^29: the residual's 32-bit byte offsets
+    (dict(res="p18", res_ld=70000, s_in=None), -1, -1),   # (the operand checks answer first)
     (dict(s_in="p0+4"), -1, -1),
     (dict(ell_col="p2+4"), -1, -1),
     (dict(ell_val="p3+4"), -1, -1),
@@ -246,6 +248,10 @@ FWD_CHAIN_ROWS = [
     (dict(done="p30+64"), dict(c=191), 0, -1),
     ({}, dict(s_in="p23", c=191), 1, -3),
     ({}, dict(s_in="p23", x_out=None), 1, -1),
+    ({}, dict(res="p18", res_ld=70000), 1, -3),
+    ({}, dict(res="p18", res_ld=70000), 2, -3),
+    ({}, dict(res="p18", res_ld=70000, x_out=None), 1, -1),
+    ({}, dict(s_in="p23", res="p18", res_ld=70000), 1, -1),   # (the chain's links are checked in front of a layer's operands)
 ]
 BWD_CHAIN_ROWS = [
     (dict(count=0), {}, 0, -1),
