@@ -172,3 +172,107 @@ def mesh_encoder(params, positions, adj):
 def segment_max(x, sizes):
     """Per-mesh column max of rows concatenated along dim 0 (layers.py:78 applied mesh by mesh)."""
     return torch.stack([part.max(dim=0)[0] for part in torch.split(x, list(sizes), dim=0)])
+
+
+# ---- image-feature pooling (utils.py:286-389) -------------------------------------------------------------------------------
+POOL_SCALE, POOL_FOCAL, POOL_HALF, POOL_NORM = 0.57, 248.0, 224.0 / 2.0, 223.0
+
+
+def camera_info(param):
+    """utils.py:286-313: rotation rows [B,3,3] (the camera's x, y, z axes, normalised) and position [B,3] from
+    (azimuth deg, elevation deg, distance); the `%` is torch.remainder."""
+    theta = (np.pi * param[:, 0] / 180.0) % 360.0
+    phi = (np.pi * param[:, 1] / 180.0) % 360.0
+    flat = param[:, 2] * torch.cos(phi)
+    pos = torch.stack((flat * torch.cos(theta), param[:, 2] * torch.sin(phi), flat * torch.sin(theta)), dim=1)
+    up = torch.zeros_like(pos)
+    up[:, 1] = 1.0
+    x = torch.cross(up, pos, dim=1)
+    y = torch.cross(pos, x, dim=1)
+    return torch.stack([a / torch.sqrt((a ** 2).sum(1, keepdim=True)) for a in (x, y, pos)], dim=1), pos
+
+
+def _pool_project(verts, cam_mat, cam_pos):
+    """utils.py:321-333: camera-space (X, Y, Z) [B,V] each and the image fractions (xs, ys) [B,V] of every vertex."""
+    a = verts * POOL_SCALE - cam_pos.unsqueeze(1)
+    X, Y, Z = ((a[..., 0] * cam_mat[:, None, r, 0] + a[..., 1] * cam_mat[:, None, r, 1]) + a[..., 2] * cam_mat[:, None, r, 2]
+               for r in range(3))
+    xs = ((-Y) / (-Z) * POOL_FOCAL + POOL_HALF) / POOL_NORM
+    ys = (X / (-Z) * POOL_FOCAL + POOL_HALF) / POOL_NORM
+    return X, Y, Z, xs, ys
+
+
+def _pool_texels(block, xs, ys):
+    """utils.py:339-371 for one map [B,C,d,d]: the unclamped texel coordinates (rx, ry), the weights A = x2 - x, B = x - x1,
+    G = y2 - y, H = y - y1 of the CLAMPED coordinate ([B,V] each; all zero where it is integral) and the four texels' values
+    c11, c12, c21, c22 [B,V,C] (first index x1 / x2, second y1 / y2)."""
+    b, c, dim = block.shape[0], block.shape[1], block.shape[-1]
+    rx, ry = xs * dim, ys * dim
+    cx, cy = torch.clamp(rx, 0, dim - 1), torch.clamp(ry, 0, dim - 1)
+    x1, x2, y1, y2 = torch.floor(cx), torch.ceil(cx), torch.floor(cy), torch.ceil(cy)
+    planes = block.reshape(b, c, dim * dim)
+
+    def take(x, y):
+        index = (x.long() * dim + y.long()).unsqueeze(1).expand(-1, c, -1)
+        return torch.gather(planes, 2, index).transpose(1, 2)
+
+    return (rx, ry), (x2 - cx, cx - x1, y2 - cy, cy - y1), (take(x1, y1), take(x1, y2), take(x2, y1), take(x2, y2))
+
+
+def pool_features(blocks, verts, cam_mat, cam_pos):
+    """utils.py:316-389 with the camera of batch_camera_info handed in: [B,V,sum C] features of the maps `blocks` (each
+    [B,C,d,d]) at the pixels the vertices [B,V,3] project to.  Any float dtype (of all arguments alike); differentiable
+    in the maps and the vertices by autograd."""
+    _, _, _, xs, ys = _pool_project(verts, cam_mat, cam_pos)
+    out = []
+    for block in blocks:
+        _, (A, B, G, H), (c11, c12, c21, c22) = _pool_texels(block, xs, ys)
+        A, B, G, H = (w.unsqueeze(-1) for w in (A, B, G, H))
+        out.append(((A * c11 * G + H * c12 * A) + G * c21 * B) + B * c22 * H)
+    return torch.cat(out, dim=-1)
+
+
+def pool_vertex_gradient(blocks, verts, cam_mat, cam_pos, grad_out):
+    """d (sum grad_out * pool_features) / d verts in FLOAT64 from the closed form, TERM BY TERM -- one term per (vertex, map,
+    channel).  With f_c = A c11 G + H c12 A + G c21 B + B c22 H and floor / ceil piecewise constant,
+        d f_c / d x = (-c11 G - H c12) + (G c21 + c22 H),     d f_c / d y = (-A c11 + c12 A) + (-c21 B + B c22)
+    per texel; a texel coordinate is xs * dim, the clamp to [0, dim - 1] passes the gradient only inside (bounds included), and
+    J = d (xs, ys) / d vertex [B,V,2,3] chains through the perspective divide, the camera matrix and the 0.57.  Returns float64
+    numpy arrays in the sense of helpers.fp64_surface_gradient / helpers.rows_close:
+      grad  [B,V,3]  sum_c g_c * d f_c / d (x, y) * dim * [inside the clamp] * J;
+      mass  [B,V,3]  the same sum with every factor's absolute value, the four texel terms of d f_c taken separately: the scale an
+                     fp32 evaluation's round-off is proportional to, whatever cancels;
+      floor [B,V,3]  one fp32 ulp of a texel coordinate (eps * dim) through every term: the weights are differences of the fp32
+                     xs * dim and a whole number, so their ABSOLUTE rounding does not shrink with the weight --
+                     eps * dim^2 * sum_c |g_c| (|c11| + |c12| + |c21| + |c22|) |J| on the axes the clamp lets through;
+      near  [B,V]    the smallest distance, over the maps and both axes, of the unclamped texel coordinate to the nearest texel
+                     line 0 ... dim - 1: the gradient is discontinuous across a line, a comparison with an fp32 evaluation
+                     leaves out the vertices that sit on one."""
+    eps = float(np.finfo(np.float32).eps)
+    verts, cam_mat, cam_pos, grad_out = (t.detach().double().cpu() for t in (verts, cam_mat, cam_pos, grad_out))
+    X, Y, Z, xs, ys = _pool_project(verts, cam_mat, cam_pos)
+    # xs = (Y / Z * F + 112) / 223,  ys = (-X / Z * F + 112) / 223;  d (X, Y, Z) / d vertex = 0.57 * the camera's rows
+    k = POOL_FOCAL / POOL_NORM
+    rows = POOL_SCALE * cam_mat[:, None]                                                       # [B,1,3 (X,Y,Z),3]
+    J = torch.stack(((k / Z).unsqueeze(-1) * rows[:, :, 1] + (-k * Y / Z ** 2).unsqueeze(-1) * rows[:, :, 2],
+                     (-k / Z).unsqueeze(-1) * rows[:, :, 0] + (k * X / Z ** 2).unsqueeze(-1) * rows[:, :, 2]), dim=2)
+    grad, mass, floor = (torch.zeros_like(verts) for _ in range(3))
+    near = torch.full(verts.shape[:2], float("inf"), dtype=torch.float64)
+    col = 0
+    for block in blocks:
+        c, dim = block.shape[1], block.shape[-1]
+        (rx, ry), (A, B, G, H), (c11, c12, c21, c22) = _pool_texels(block.detach().double().cpu(), xs, ys)
+        A, B, G, H = (w.unsqueeze(-1) for w in (A, B, G, H))
+        g = grad_out[..., col:col + c]
+        col += c
+        inside = torch.stack(((rx >= 0) & (rx <= dim - 1), (ry >= 0) & (ry <= dim - 1)), dim=-1).double() * dim  # [B,V,2]
+        terms = (torch.stack((-c11 * G, -H * c12, G * c21, c22 * H)), torch.stack((-A * c11, c12 * A, -c21 * B, B * c22)))
+        d = torch.stack([(g * t.sum(0)).sum(-1) for t in terms], dim=-1) * inside                              # [B,V,2]
+        d_abs = torch.stack([(g.abs() * t.abs().sum(0)).sum(-1) for t in terms], dim=-1) * inside
+        ulp = (eps * dim * (g.abs() * (c11.abs() + c12.abs() + c21.abs() + c22.abs())).sum(-1)).unsqueeze(-1) * inside
+        grad += (d.unsqueeze(-1) * J).sum(2)
+        mass += (d_abs.unsqueeze(-1) * J.abs()).sum(2)
+        floor += (ulp.unsqueeze(-1) * J.abs()).sum(2)
+        for r in (rx, ry):
+            near = torch.minimum(near, (r - torch.clamp(torch.round(r), 0, dim - 1)).abs())
+    return grad.numpy(), mass.numpy(), floor.numpy(), near.numpy()

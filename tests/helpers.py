@@ -298,3 +298,36 @@ def rows_close(actual, exact, mass, rtol, what="", floor=None, floor_ulps=0.0):
     assert worst <= 1.0, "%s: worst element is %.2fx its bound (rtol %g of the row's term mass + %g coordinate ulps per term); " \
                          "max err %g" % (what, worst, rtol, floor_ulps, err.max())
     return worst
+
+
+# ---- the pooling's vertex-position gradient per element (oracle/ref_ops.py pool_vertex_gradient) -------------------------------
+POOL_NEAR = 1e-3          # texels: vertices closer than this to a texel line are left out (the gradient jumps across the line;
+#                           the fp32 texel coordinate is within 1e-5 of the float64 one: 100 times the rounding)
+POOL_MAX_LEFT_OUT = 0.02  # share of a case's vertices that may be left out
+POOL_ROW_RTOL = 8 * float(np.finfo(np.float32).eps)   # the project's bar for a short fp32 product chain
+POOL_FLOOR_ULPS = 1.0     # texel-coordinate ulps through every term
+
+
+def pool_vertex_gradient_close(got, blocks, verts, cam_mat, cam_pos, grad_out, what):
+    """`got` [B,V,3] -- an fp32 evaluation of d (sum grad_out * pooled features) / d verts -- against the float64 closed form
+    (ref_ops.pool_vertex_gradient, given the SAME fp32 cameras), element by element: rows_close(POOL_ROW_RTOL of the element's
+    term mass + POOL_FLOOR_ULPS texel-coordinate ulps through every term) on the vertices at least POOL_NEAR from every texel
+    line -- at most POOL_MAX_LEFT_OUT of the case's vertices may sit closer --, and exactly zero wherever the float64 gradient
+    is exactly zero (the clamp lets nothing through).  Arguments are torch tensors (any device) or numpy arrays.  Returns
+    {"keep": [B,V] bool, "zero_rows": all-zero rows of the float64 gradient, "zero_checked": those of them that are kept,
+    "live_rows": kept rows with a gradient, "worst": the worst element as a share of its bound}."""
+    import torch
+    from oracle import ref_ops
+    cpu = lambda t: torch.as_tensor(t).detach().cpu()
+    grad, mass, floor, near = ref_ops.pool_vertex_gradient([cpu(m) for m in blocks], cpu(verts), cpu(cam_mat), cpu(cam_pos),
+                                                           cpu(grad_out))
+    keep = near >= POOL_NEAR
+    assert (~keep).mean() <= POOL_MAX_LEFT_OUT, "%s: %d of %d vertices within %g of a texel line" % (what, (~keep).sum(), keep.size,
+                                                                                                 POOL_NEAR)
+    got = cpu(got).numpy()
+    zero = keep & (grad == 0).all(-1)
+    assert (got[zero] == 0).all(), "%s: a vertex the clamp holds on both axes has a gradient" % what
+    live = keep & ~zero
+    worst = rows_close(got[live], grad[live], mass[live], POOL_ROW_RTOL, what, floor=floor[live], floor_ulps=POOL_FLOOR_ULPS)
+    return {"keep": keep, "zero_rows": int((grad == 0).all(-1).sum()), "zero_checked": int(zero.sum()), "live_rows": int(live.sum()),
+            "worst": worst}

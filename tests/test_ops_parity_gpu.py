@@ -10,7 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import bits, fp64_surface_gradient, golden, rows_close
+from helpers import bits, fp64_surface_gradient, golden, pool_vertex_gradient_close, rows_close
 from geometrics_amd import backward_pass, layers, meshgen, ops, utils
 from oracle import ref_ops
 
@@ -1084,7 +1084,7 @@ def test_pooling_with_more_channel_chunks_than_grid_slices(gpu):
     """The pooling launches give every workgroup one 64-channel chunk up to 32 chunks; beyond that a workgroup walks several
     (and sums their shares of the vertex gradient).  Two maps of 1280 channels = 40 chunks against the same maps pooled in
     halves of 640 (10 + 10 chunks per call): features per channel bit for bit, map gradients and the vertex gradient (= the sum
-    of the halves') within fp32 round-off."""
+    of the halves') within fp32 round-off -- and the vertex gradient element by element against the float64 closed form."""
     torch.manual_seed(12)
     V, _ = meshgen.icosphere(2)
     b, nv = 2, V.shape[0]
@@ -1110,6 +1110,8 @@ def test_pooling_with_more_channel_chunks_than_grid_slices(gpu):
         gv_sum += verts.grad
         verts.grad = None
     close(gv_big.cpu().numpy(), gv_sum.cpu().numpy(), 2e-5)
+    cam_mat, cam_pos = utils.batch_camera_info(img_info.clone())
+    pool_vertex_gradient_close(gv_big, big, verts, cam_mat, cam_pos, grad_out, "pooling verts.grad 40 chunks (device-drawn maps)")
 
 
 def test_surface_loss_with_per_mesh_weights_equals_the_weighted_stages(gpu):
@@ -1157,9 +1159,10 @@ def test_surface_loss_with_per_mesh_weights_equals_the_weighted_stages(gpu):
 
 
 def _pooling_against_float64(gpu, verts, img_info, chans, dims, headrooms=(0,)):
-    """forward, map gradient and vertex gradient of batched_pooling against float64 built from the pooling operator itself:
-    pooling identity maps (channel t = the one-hot map of texel t) returns P [b, nv, texels] with the weights as the kernel
-    forms them, so feats = P maps and d maps = P^T g in float64, per element, bound 8 eps * sum |P||g| (|maps|)."""
+    """forward and map gradient of batched_pooling against float64 built from the pooling operator itself: pooling identity
+    maps (channel t = the one-hot map of texel t) returns P [b, nv, texels] with the weights as the kernel forms them, so
+    feats = P maps and d maps = P^T g in float64, per element, bound 8 eps * sum |P||g| (|maps|).  (P itself and the vertex
+    gradient against the float64 restatement of the reference: test_pooling_vertex_gradient_gpu.py.)"""
     b = verts.shape[0]
     maps = [torch.randn(b, c, d, d, device=gpu, requires_grad=True) for c, d in zip(chans, dims)]
     eps = np.finfo(np.float32).eps

@@ -8,7 +8,7 @@ import torch
 
 import oracle
 from oracle import ref_ops
-from helpers import bits, golden, golden_names, tri_true_case
+from helpers import bits, golden, golden_names, rows_close, tri_true_case
 from geometrics_amd import meshgen
 
 NN_CASES = [n for n in golden_names("nn_") if n != "nn_config2_outputs"]
@@ -246,6 +246,45 @@ def test_regulariser_restatements():
     edge.backward()
     np.testing.assert_allclose(edge.item(), g["edge"], rtol=1e-6)
     np.testing.assert_allclose(v2.grad.numpy(), g["grad_verts_edge"], rtol=1e-4, atol=1e-8)
+
+
+def test_pooling_restatement_matches_reference_fixture():
+    """ref_ops.camera_info / pool_features / pool_vertex_gradient (utils.py:286-389) on the reference's own fp32 run
+    (pooling_v162): camera, features and map gradients at the bars of the device test of the same fixture; the closed-form
+    vertex gradient equals float64 autograd of the forward; and the reference's fp32 vertex gradient meets the closed form
+    ELEMENT BY ELEMENT at the bound the kernel is held to (8 eps of the term mass + 1 texel-coordinate ulp per term: worst
+    element at 0.49 of it; without the floor it would sit at 31 eps of its mass)."""
+    g = golden("pooling_v162")
+    t = lambda a: torch.from_numpy(a)
+
+    def close(actual, expected, rtol):                                     # (max-norm, as test_ops_parity_gpu.close)
+        assert np.abs(np.asarray(actual, np.float64) - expected).max() <= rtol * np.abs(expected).max()
+
+    cam_mat, cam_pos = ref_ops.camera_info(t(g["img_info"]))
+    close(cam_mat.numpy(), g["cam_mat"], 1e-6)
+    close(cam_pos.numpy(), g["cam_pos"], 1e-6)
+    blocks32 = [t(g["block%d" % i]) for i in range(4)]
+    close(ref_ops.pool_features(blocks32, t(g["verts"]), cam_mat, cam_pos).numpy(), g["features"], 3e-5)     # its fp32 run
+    # the whole operation in float64, the camera included
+    cam_mat, cam_pos = ref_ops.camera_info(t(g["img_info"]).double())
+    blocks = [b.double().requires_grad_(True) for b in blocks32]
+    verts = t(g["verts"]).double().requires_grad_(True)
+    feats = ref_ops.pool_features(blocks, verts, cam_mat, cam_pos)
+    assert feats.shape == (2, 162, 36)
+    close(feats.detach().numpy(), g["features"], 3e-5)
+    feats.backward(t(g["grad_out"]).double())
+    for i, blk in enumerate(blocks):
+        close(blk.grad.numpy(), g["grad_block%d" % i], 3e-5)
+    close(verts.grad.numpy(), g["grad_verts"], 2e-4)
+    grad, mass, floor, near = ref_ops.pool_vertex_gradient(blocks32, t(g["verts"]), cam_mat, cam_pos, t(g["grad_out"]))
+    assert np.abs(grad - verts.grad.numpy()).max() <= 1e-14 * np.abs(grad).max()          # (4e-16 of it)
+    assert mass.min() >= 0 and (np.abs(grad) <= mass * (1 + 1e-12)).all() and near.shape == (2, 162)
+    # no vertex is left out here: the reference's fp32 run took every vertex's texels as float64 does
+    eps = float(np.finfo(np.float32).eps)
+    rows_close(g["grad_verts"], grad, mass, 8 * eps, "pooling_v162 grad_verts (reference fp32)", floor=floor, floor_ulps=1.0)
+    clamped = (grad == 0).all(-1)
+    assert clamped.sum() == 17 and (g["grad_verts"][clamped] == 0).all() and (np.abs(g["grad_verts"]).sum(-1) == 0).sum() == 17
+    assert (near < 1e-3).mean() <= 0.02                                               # (5 of 324)
 
 
 def test_nn_grad_restatement_equals_autograd_of_the_distance_form():
