@@ -102,6 +102,7 @@ _SIGNATURES = {
     "geom_pool_features_bwd_ld_f32": [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_size_t, _vp],
     "geom_colsum_batch_f32": [_i, _vp, _vp, _vp, _vp, _vp],
     "geom_adam_step_f32": [_i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _i, _vp],
+    "geom_adam_table_step_f32": [_i, _vp, ctypes.c_int64, _vp, _f, _f, _f, _f, _vp, _i, _vp],
     "geom_dense_fwd_f32": [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "geom_dense_bwd_input_f32": [_i, _i, _i, _vp, _vp, _vp, _vp],
     "geom_dense_bwd_weight_f32": [_i, _i, _i, _vp, _vp, _vp, _i, _vp],
@@ -272,6 +273,8 @@ def lib():
         L.geom_zn_layer_partial_rows.argtypes = [_i, _i]
         L.geom_gemm_workspace_floats.restype = ctypes.c_int64
         L.geom_gemm_workspace_floats.argtypes = [_i, _i, _i]
+        L.geom_adam_table_bytes.restype = ctypes.c_int64
+        L.geom_adam_table_bytes.argtypes = [_i, ctypes.c_int64]
         L.geom_surface_tail_counters_offset.restype = ctypes.c_size_t
         L.geom_surface_tail_counters_offset.argtypes = [_i, _i, _i]
         for name, args in _SIGNATURES.items():
@@ -289,7 +292,8 @@ def declared_symbols():
                    "geom_surface_order_words",
                    "geom_dense_bwd_weight_workspace_floats", "geom_chamfer_nn_culled_workspace_floats",
                    "geom_nn_cull_index_floats", "geom_surface_tail_counters_offset", "geom_zn_layer_partial_rows",
-                   "geom_gemm_workspace_floats", "geom_stage_regularisers_blocks", "geom_split_bf16_kpad"] + list(_SIGNATURES))
+                   "geom_gemm_workspace_floats", "geom_stage_regularisers_blocks", "geom_split_bf16_kpad",
+                   "geom_adam_table_bytes"] + list(_SIGNATURES))
 
 
 def check(code, what):

@@ -771,6 +771,19 @@ int geom_latent_l1_bwd_f32(int b, int l, const float *pred, const float *target,
 int geom_adam_step_f32(int count, float *const *params, const float *const *grads, float *const *exp_avg,
                        float *const *exp_avg_sq, const int64_t *sizes, float lr, float beta1, float beta2,
                        float eps, float grad_scale, float *state, int advance, void *stream);
+/* The same step (same state words, same arithmetic, same bits) as ONE launch for ANY number of tensors, with the learning rate
+ * read on the device.  `table` is a DEVICE buffer of geom_adam_table_bytes(count, total_blocks) bytes, 8-byte aligned, that the
+ * caller fills (on the host, then copies): p[count], g[count], m[count], v[count] (device pointers), n[count] (int64_t lengths),
+ * first_block[count], group[count] (int): first_block[0] = 0, first_block[i + 1] = first_block[i] + (n[i] + 1023) / 1024, and
+ * total_blocks = that sum over all tensors (an empty tensor owns no workgroup).  Tensor i steps with lr[group[i]] (`lr`: device
+ * floats, one per group; a replayed HIP graph follows a value written there); beta1, beta2, eps and grad_scale are shared -- the
+ * state holds ONE pair of beta powers.  advance as above.  count == 0: 0 without a launch; only empty tensors: one workgroup
+ * still advances the state.  A negative count or total_blocks, a null or misaligned pointer: GEOM_EINVAL; total_blocks above
+ * 0x3fffffff: GEOM_ETOOBIG (geom_adam_table_bytes returns the same codes, negative, in place of a size).  The kernel trusts
+ * the table: what it names must be valid device memory of the stated lengths. */
+int64_t geom_adam_table_bytes(int count, int64_t total_blocks);
+int geom_adam_table_step_f32(int count, const void *table, int64_t total_blocks, const float *lr, float beta1, float beta2,
+                             float eps, float grad_scale, float *state, int advance, void *stream);
 
 #ifdef __cplusplus
 }

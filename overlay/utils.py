@@ -8,12 +8,16 @@ overlay (1) finds the reference's own utils.py further down sys.path, (2) execut
 lines resolve to the overlay packages, so nothing is JIT-compiled with nvcc -- (3) re-exports
 all of its public names, and (4) overrides the hot-path ones with the HIP implementations.
 No reference source is shipped in this repository.
+
+`optim` stays the reference's `torch.optim` unless GEOM_OVERLAY_ADAM=fused is set in the environment: then `optim.Adam(params,
+lr=...)` (GEOMetrics.py:73) builds a geometrics_amd.optim.FusedAdam and every other attribute of `optim` is torch.optim's.
 """
 import importlib.util
 import os
 import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+_ADAM = os.environ.get("GEOM_OVERLAY_ADAM", "torch") or "torch"       # read here: the reference's names replace `os` below
 
 
 def _find_reference_utils():
@@ -36,3 +40,9 @@ from geometrics_amd.utils import (Plane, adj_init, batch_calc_edge, batch_camera
                                   batch_get_lap_info, batch_point_to_point, batch_point_to_surface, batch_sample,
                                   batched_pooling, calc_adj, calc_point_to_line, chamfer_dist, edge, normalize_adj,
                                   tri_dist)
+
+if _ADAM == "fused":
+    from geometrics_amd.optim import overlay_namespace as _overlay_namespace  # noqa: E402
+    optim = _overlay_namespace()
+elif _ADAM != "torch":
+    raise ImportError("overlay/utils.py: GEOM_OVERLAY_ADAM=%r; 'fused' or 'torch' (the default)" % _ADAM)
