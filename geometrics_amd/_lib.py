@@ -1,28 +1,43 @@
 """ctypes binding of libgeom_hip.so (the C ABI declared in include/geom_hip.h).
 
-torch is used only for device memory and the current HIP stream; the signatures below are
-plain pointers and sizes.  Loading fails loudly -- there is no fallback implementation.
+torch is used only for device memory and the current HIP stream; the signatures, argument structs and limits are read
+from the header (_header.py): plain pointers and sizes.  Loading fails loudly -- there is no fallback implementation.
 """
 import ctypes
 import os
 
 import torch
 
+from . import _header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgeom_hip.so")
 
-FLAG_REF_TAIL_TRUNC = 1
-FLAG_FIX_REGION6 = 2
-FLAG_TRI_BRUTE_FORCE = 4
-FLAG_NN_FMA = 8
-FLAG_TRI_WS_READY = 16
-ABI_VERSION = 16
-EUNSUPPORTED = -3
-ADAM_MAX_TENSORS = 64
-COLSUM_MAX_JOBS = 32
-DENSE_MAX_LAYERS = 8
-DENSE_MAX_REDUCE_JOBS = 32
-ADAM_STATE_WORDS = 2112
+# the limits, flags and codes of the header under the names the operators use (GEOM_X -> X)
+_C = _header.CONSTANTS
+ABI_VERSION = _C["ABI_VERSION"]
+EUNSUPPORTED = _C["EUNSUPPORTED"]
+FLAG_REF_TAIL_TRUNC = _C["FLAG_REF_TAIL_TRUNC"]
+FLAG_FIX_REGION6 = _C["FLAG_FIX_REGION6"]
+FLAG_TRI_BRUTE_FORCE = _C["FLAG_TRI_BRUTE_FORCE"]
+FLAG_NN_FMA = _C["FLAG_NN_FMA"]
+FLAG_TRI_WS_READY = _C["FLAG_TRI_WS_READY"]
+ADAM_MAX_TENSORS = _C["ADAM_MAX_TENSORS"]
+ADAM_STATE_WORDS = _C["ADAM_STATE_WORDS"]
+COLSUM_MAX_JOBS = _C["COLSUM_MAX_JOBS"]
+DENSE_MAX_LAYERS = _C["DENSE_MAX_LAYERS"]
+DENSE_MAX_REDUCE_JOBS = _C["DENSE_MAX_REDUCE_JOBS"]
+SUM_MAX_TENSORS = _C["SUM_MAX_TENSORS"]
+DEFORM_CHAIN_MAX = _C["DEFORM_CHAIN_MAX"]
+DEFORM_TAIL = _C["DEFORM_TAIL"]
+DEFORM_WIDE_MAX_B = _C["DEFORM_WIDE_MAX_B"]
+
+# the argument structs, fields as the header orders them
+DeformFwd = _header.STRUCTS["geom_deform_fwd"]
+DeformBwd = _header.STRUCTS["geom_deform_bwd"]
+DeformInfer = _header.STRUCTS["geom_deform_infer"]
+SurfaceCull = _header.STRUCTS["geom_surface_cull"]
+SurfaceTail = _header.STRUCTS["geom_surface_tail"]
 
 # ---- package-wide reference-quirk mode (SURVEY quirk register Q1 / Q3) ------------------------------------------------
 # The shipped CUDA kernels drop the tail of every 512-wide tile of targets / triangles (chamfer_distance.cu:31-33,
@@ -53,150 +68,15 @@ def quirk_flags():
     return FLAG_REF_TAIL_TRUNC if _reference_quirks else 0
 
 
-_vp = ctypes.c_void_p
-_i = ctypes.c_int
-_u = ctypes.c_uint
-_f = ctypes.c_float
-
-# name -> argtypes; every function returns int (0 ok / hipError_t / negative GEOM_E*)
-_SIGNATURES = {
-    "geom_chamfer_nn_f32": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _u, _vp],
-    "geom_chamfer_nn_culled_f32": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u, _vp, _vp],
-    "geom_tri_distance_f32": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _u, _vp],
-    "geom_tri_distance_indexed_f32": [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _u, _vp],
-    "geom_tri_distance_ws_f32": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u, _vp, ctypes.c_size_t, _vp],
-    "geom_tri_surface_fwd_f32": [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u, _vp, ctypes.c_size_t, _vp],
-    "geom_tri_distance_indexed_ws_f32": [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _u, _vp, ctypes.c_size_t, _vp],
-    "geom_face_areas_f32": [_i, _i, _vp, _i, _vp, _vp, _vp],
-    "geom_draw_samples_f32": [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
-    "geom_draw_samples_rng_f32": [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "geom_surface_loss_bwd_f32": [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp],
-    "geom_surface_finalize_f32": [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i,
-                                  _i, _vp, _vp, _vp],
-    "geom_surface_prepare_f32": [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _u, _vp, ctypes.c_size_t, _vp, _vp, _vp],
-    "geom_nn_cull_index_f32": [_i, _i, _vp, _vp, _vp, _vp],
-    "geom_surface_scan_f32": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                              _vp, _vp, _f, _f, _vp, _u, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp],
-    "geom_surface_gather_f32": [_i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "geom_surface_finalize_w_f32": [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i,
-                                    _i, _vp, _vp, _vp, _vp],
-    "geom_surface_gather_w_f32": [_i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "geom_vertex_head_fwd_f32": [ctypes.c_int64, _i, _vp, _vp, _f, _vp, _vp],
-    "geom_vertex_head_bwd_f32": [ctypes.c_int64, _i, _vp, _f, _vp, _vp],
-    "geom_sample_faces_fwd_f32": [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
-    "geom_sample_faces_bwd_f32": [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "geom_chamfer_grad_f32": [_i, _i, _vp, _i, _vp, _vp, _vp, _f, _vp, _i, _vp, _vp],
-    "geom_p2tri_loss_fwd_f32": [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "geom_p2tri_loss_bwd_f32": [_i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp],
-    "geom_segment_max_fwd_f32": [_i, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp],
-    "geom_segment_max_bwd_f32": [_i, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp],
-    "geom_sum_f32": [ctypes.c_int64, _vp, _f, _vp, _vp],
-    "geom_sample_chamfer_bwd_f32": [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _f, _vp, _vp],
-    "geom_laplacian_f32": [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp],
-    "geom_edge_sqlen_fwd_f32": [_i, _i, _vp, _i, _vp, _vp, _vp],
-    "geom_edge_sqlen_bwd_f32": [_i, _i, _vp, _i, _vp, _vp, _f, _vp, _vp],
-    "geom_vertex_bn_fwd_f32": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp, _i, _f, _vp, _vp, _vp, _vp],
-    "geom_vertex_bn_bwd_f32": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
-    "geom_pool_features_fwd_ld_f32": [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp],
-    "geom_pool_features_fwd_fronts_f32": [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _vp],
-    "geom_pool_features_bwd_ld_f32": [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_size_t, _vp],
-    "geom_colsum_batch_f32": [_i, _vp, _vp, _vp, _vp, _vp],
-    "geom_adam_step_f32": [_i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _i, _vp],
-    "geom_adam_table_step_f32": [_i, _vp, ctypes.c_int64, _vp, _f, _f, _f, _f, _vp, _i, _vp],
-    "geom_dense_fwd_f32": [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
-    "geom_dense_bwd_input_f32": [_i, _i, _i, _vp, _vp, _vp, _vp],
-    "geom_dense_bwd_weight_f32": [_i, _i, _i, _vp, _vp, _vp, _i, _vp],
-    "geom_dense_bwd_f32": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
-    "geom_dense_reduce2_f32": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
-    "geom_dense_reduce_adam_f32": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f,
-                                   _vp, _vp],
-    "geom_dense_reduce_f32": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "geom_zn_gcn_aggregate_fwd_f32": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
-    "geom_zn_gcn_aggregate_ell_fwd_f32": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
-    "geom_zn_gcn_aggregate_ell_bwd_f32": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
-    "geom_zn_gcn_aggregate_ell_head_fwd_f32": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp],
-    "geom_zn_gcn_aggregate_ell_head_bwd_f32": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _vp, _vp, _vp],
-    "geom_zn_gcn_aggregate_bwd_f32": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
-    "geom_gemm_f32": [_i, _i, _i, _vp, ctypes.c_int64, _i, _vp, ctypes.c_int64, _i, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp],
-    "geom_zn_layer_fwd_f32": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
-    "geom_zn_layer_bwd_f32": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _i, _vp, _vp, _vp, _vp],
-    "geom_camera_info_f32": [_i, _vp, _vp, _vp, _vp],
-    "geom_sum_tensors_f32": [_i, _vp, ctypes.c_int64, _vp, _vp],
-    "geom_sum_tensors_rows_f32": [_i, _vp, _vp, ctypes.c_int64, _i, _vp, _vp],
-    "geom_split_bf16_planes_f32": [_i, _i, _vp, _vp, _vp],
-    "geom_gemm_split_bf16_f32": [_i, _i, _i, _vp, _vp, _vp, _i, _vp],
-    "geom_stage_regularisers_fwd_f32": [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp],
-    "geom_stage_regularisers_bwd_f32": [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp],
-    "geom_deform_layer_fwd_f32": [_vp, _vp],
-    "geom_deform_pack_weights_f32": [_i, _vp, _vp, _vp, _vp],
-    "geom_deform_pack_weights_zero_f32": [_i, _vp, _vp, _vp, _vp, _i, _vp],
-    "geom_deform_chain_fwd_f32": [_i, _vp, _vp, _vp],
-    "geom_deform_chain_bwd_f32": [_i, _vp, _vp, _vp, _vp],
-    "geom_deform_chain_fits": [_i],
-    "geom_deform_layer_bwd_f32": [_vp, _vp],
-    "geom_deform_layer_wide_fwd_f32": [_vp, _vp],
-    "geom_deform_layer_wide_bwd_f32": [_vp, _vp],
-    "geom_deform_infer_fwd_f32": [_vp, _vp],
-    "geom_encoder_layer_fwd_f32": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _i, _vp, ctypes.c_int64,
-                                   _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp],
-    "geom_encoder_layer_bwd_f32": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i, _vp,
-                                   ctypes.c_int64, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp],
-    "geom_latent_l1_fwd_f32": [_i, _i, _vp, _vp, _vp, _f, _vp, _vp],
-    "geom_latent_l1_bwd_f32": [_i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp],
-}
-
-
-class DeformFwd(ctypes.Structure):
-    """struct geom_deform_fwd (include/geom_hip.h): a hidden layer of the deformation block, forward."""
-    _fields_ = [("b", _i), ("nv", _i), ("c", _i), ("k", _i), ("ell_w", _i),
-                ("s_in", _vp), ("bias", _vp), ("ell_col", _vp), ("ell_val", _vp),
-                ("tail_col", _vp), ("tail_val", _vp),
-                ("bn_w", _vp), ("bn_b", _vp), ("run_mean", _vp), ("run_var", _vp),
-                ("training", _i), ("momentum", _f), ("eps", _f), ("relu", _i),
-                ("res", _vp), ("res_ld", _i), ("scale", _f),
-                ("z_out", _vp), ("x_out", _vp), ("save_mean", _vp), ("save_invstd", _vp),
-                ("w_next", _vp), ("s_out", _vp), ("w_head", _vp), ("s_head", _vp), ("vpx", _i)]
-
-
-class DeformBwd(ctypes.Structure):
-    """struct geom_deform_bwd (include/geom_hip.h): a hidden layer of the deformation block, backward."""
-    _fields_ = [("b", _i), ("nv", _i), ("c", _i), ("k", _i), ("ell_w", _i),
-                ("dz_up", _vp), ("ell_col_t", _vp), ("ell_val_t", _vp),
-                ("tail_col_t", _vp), ("tail_val_t", _vp),
-                ("ds_up", _vp), ("wt_up", _vp), ("g", _vp), ("g2", _vp), ("g_ld", _i), ("g2_ld", _i),
-                ("z", _vp), ("bn_w", _vp), ("bn_b", _vp), ("save_mean", _vp), ("save_invstd", _vp),
-                ("relu", _i), ("has_res", _i), ("scale", _f),
-                ("grad_res", _vp), ("dz", _vp), ("grad_bn_w", _vp), ("grad_bn_b", _vp), ("colsum", _vp),
-                ("ds_head", _vp), ("w_head", _vp), ("x_top", _vp), ("dw_head", _vp), ("vpx", _i)]
-
-
-class DeformInfer(ctypes.Structure):
-    """struct geom_deform_infer (include/geom_hip.h): a hidden layer of the deformation block, eval-mode forward."""
-    _fields_ = [("b", _i), ("nv", _i), ("c", _i), ("k", _i), ("ell_w", _i),
-                ("s_in", _vp), ("bias", _vp), ("ell_col", _vp), ("ell_val", _vp),
-                ("tail_col", _vp), ("tail_val", _vp),
-                ("bn_w", _vp), ("bn_b", _vp), ("run_mean", _vp), ("run_var", _vp),
-                ("eps", _f), ("relu", _i),
-                ("res", _vp), ("res_ld", _i), ("scale", _f),
-                ("x_out", _vp), ("w_next", _vp), ("s_out", _vp), ("w_head", _vp), ("s_head", _vp)]
-
-
-class SurfaceCull(ctypes.Structure):
-    """struct geom_surface_cull (include/geom_hip.h): the buffers of the culled Chamfer scan inside the surface step."""
-    _fields_ = [("gt_order", ctypes.c_void_p), ("gt_index", ctypes.c_void_p), ("sample_index", ctypes.c_void_p),
-                ("faces_in_order", ctypes.c_void_p)]
-
-
-class SurfaceTail(ctypes.Structure):
-    """struct geom_surface_tail (include/geom_hip.h): the finalize pass as extra (role) workgroups of the fused scan launch."""
-    _fields_ = [("choices", ctypes.c_void_p), ("scale_sample", ctypes.c_float), ("scale_other", ctypes.c_float),
-                ("want_order", ctypes.c_int), ("loss", ctypes.c_void_p), ("finalized", ctypes.c_int)]
+def status(name, *args, stream=None):
+    """Invoke an entry point on the current stream of the current device (or on `stream`, a raw hipStream_t) and return its
+    code: 0, a hipError_t or a negative GEOM_E* -- for callers that look at GEOM_EUNSUPPORTED before they check()."""
+    return getattr(lib(), name)(*args, stream_ptr() if stream is None else stream)
 
 
 def call(name, *args):
     """Invoke an entry point on the current stream of the current device and raise on failure."""
-    code = getattr(lib(), name)(*args, stream_ptr())
-    check(code, name)
+    check(status(name, *args), name)
 
 
 def ptr(t):
@@ -239,61 +119,18 @@ def lib():
             print("geometrics_amd: GEOM_LIB_OVERRIDE is set -- loading %s instead of the product library (probe builds only; "
                   "its ABI version is checked, its sources are not)" % override, file=sys.stderr)
         L = ctypes.CDLL(override or LIB_PATH)
-        L.geom_abi_version.restype = _i
-        L.geom_strerror.restype = ctypes.c_char_p
-        L.geom_strerror.argtypes = [_i]
-        if L.geom_abi_version() != ABI_VERSION:
+        if L.geom_abi_version() != ABI_VERSION:       # a stale library, before any of its symbols is looked up
             raise RuntimeError("geometrics_amd: libgeom_hip.so ABI %d != binding ABI %d; rebuild"
                                % (L.geom_abi_version(), ABI_VERSION))
-        L.geom_pool_features_bwd_workspace_bytes.restype = ctypes.c_size_t
-        L.geom_pool_features_bwd_workspace_bytes.argtypes = [_i, _i, _i, _vp]
-        L.geom_segment_max_workspace_bytes.restype = ctypes.c_int64
-        L.geom_segment_max_workspace_bytes.argtypes = [_i, _i, ctypes.c_int64]
-        L.geom_zn_gcn_bwd_scratch_floats.restype = ctypes.c_int64
-        L.geom_surface_order_words.restype = ctypes.c_int64
-        L.geom_surface_order_words.argtypes = [_i, _i, _i, _i]
-        L.geom_zn_gcn_relu_mask_words.restype = ctypes.c_int64
-        L.geom_zn_gcn_relu_mask_words.argtypes = [_i, _i, _i, _i]
-        L.geom_zn_gcn_bwd_scratch_floats.argtypes = [_i, _i, _i]
-        L.geom_zn_gcn_bwd_partial_rows.restype = ctypes.c_int64
-        L.geom_zn_gcn_bwd_partial_rows.argtypes = [_i, _i, _i, _i, _i]
-        L.geom_dense_bwd_weight_workspace_floats.restype = ctypes.c_int64
-        L.geom_dense_bwd_weight_workspace_floats.argtypes = [_i, _i, _i]
-        L.geom_chamfer_nn_culled_workspace_floats.restype = ctypes.c_int64
-        L.geom_chamfer_nn_culled_workspace_floats.argtypes = [_i, _i, _i]
-        L.geom_nn_cull_index_floats.restype = ctypes.c_int64
-        L.geom_nn_cull_index_floats.argtypes = [_i, _i]
-        L.geom_tri_distance_workspace_bytes.restype = ctypes.c_size_t
-        L.geom_tri_distance_workspace_bytes.argtypes = [_i, _i, _i]
-        L.geom_split_bf16_kpad.restype = _i
-        L.geom_split_bf16_kpad.argtypes = [_i]
-        L.geom_stage_regularisers_blocks.restype = ctypes.c_int64
-        L.geom_stage_regularisers_blocks.argtypes = [_i, _i, _i]
-        L.geom_zn_layer_partial_rows.restype = ctypes.c_int64
-        L.geom_zn_layer_partial_rows.argtypes = [_i, _i]
-        L.geom_gemm_workspace_floats.restype = ctypes.c_int64
-        L.geom_gemm_workspace_floats.argtypes = [_i, _i, _i]
-        L.geom_adam_table_bytes.restype = ctypes.c_int64
-        L.geom_adam_table_bytes.argtypes = [_i, ctypes.c_int64]
-        L.geom_surface_tail_counters_offset.restype = ctypes.c_size_t
-        L.geom_surface_tail_counters_offset.argtypes = [_i, _i, _i]
-        for name, args in _SIGNATURES.items():
+        for name, (restype, argtypes) in _header.PROTOTYPES.items():
             fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = _i
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
 
 def declared_symbols():
-    return sorted(["geom_abi_version", "geom_strerror", "geom_tri_distance_workspace_bytes",
-                   "geom_zn_gcn_bwd_scratch_floats", "geom_zn_gcn_bwd_partial_rows", "geom_pool_features_bwd_workspace_bytes",
-                   "geom_segment_max_workspace_bytes", "geom_zn_gcn_relu_mask_words",
-                   "geom_surface_order_words",
-                   "geom_dense_bwd_weight_workspace_floats", "geom_chamfer_nn_culled_workspace_floats",
-                   "geom_nn_cull_index_floats", "geom_surface_tail_counters_offset", "geom_zn_layer_partial_rows",
-                   "geom_gemm_workspace_floats", "geom_stage_regularisers_blocks", "geom_split_bf16_kpad",
-                   "geom_adam_table_bytes"] + list(_SIGNATURES))
+    return sorted(_header.PROTOTYPES)
 
 
 def check(code, what):
@@ -309,7 +146,7 @@ def clear_hip_error():
         hip = ctypes.CDLL("libamdhip64.so")
     except OSError:
         return 0
-    hip.hipGetLastError.restype = _i
+    hip.hipGetLastError.restype = ctypes.c_int
     return hip.hipGetLastError()
 
 

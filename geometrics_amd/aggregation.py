@@ -36,7 +36,7 @@ def _table(csr, transposed):
 
 def _table_took(csr, name, *args):
     """Launch a table entry point that has a CSR counterpart; False: there is no table, or the library's route refuses the shape."""
-    code = getattr(_lib.lib(), name)(*args, _lib.stream_ptr()) if csr.ell_w else _lib.EUNSUPPORTED
+    code = _lib.status(name, *args) if csr.ell_w else _lib.EUNSUPPORTED
     if code != _lib.EUNSUPPORTED:
         _lib.check(code, name)
     return code != _lib.EUNSUPPORTED

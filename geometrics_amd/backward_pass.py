@@ -285,8 +285,8 @@ def _launch_colsums(jobs):
     for stream, group in _by_stream(jobs):
         with torch.cuda.device(stream.device):
             for c0 in range(0, len(group), _lib.COLSUM_MAX_JOBS):
-                _lib.check(_lib.lib().geom_colsum_batch_f32(*_colsum_args(group[c0:c0 + _lib.COLSUM_MAX_JOBS]),
-                                                            stream.cuda_stream), "geom_colsum_batch_f32")
+                _lib.check(_lib.status("geom_colsum_batch_f32", *_colsum_args(group[c0:c0 + _lib.COLSUM_MAX_JOBS]),
+                                       stream=stream.cuda_stream), "geom_colsum_batch_f32")
 
 
 def _launch_reduces(jobs):
@@ -309,15 +309,17 @@ def _launch_joint(reduces, colsums, stream):
             slots = None
     with torch.cuda.device(stream.device):
         if slots is None:
-            _lib.check(_lib.lib().geom_dense_reduce2_f32(*weights, None, *biases, stream.cuda_stream), "geom_dense_reduce2_f32")
+            _lib.check(_lib.status("geom_dense_reduce2_f32", *weights, None, *biases, stream=stream.cuda_stream),
+                       "geom_dense_reduce2_f32")
         else:
             pick = lambda seq, ks: _ptrs([seq[k] for k in ks])
             wk, bk = slots[:len(reduces)], slots[len(reduces):]
             params = [p.data for p in opt.params]
-            _lib.check(_lib.lib().geom_dense_reduce_adam_f32(
+            _lib.check(_lib.status(
+                "geom_dense_reduce_adam_f32",
                 *weights, pick(params, wk), pick(opt.exp_avg, wk), pick(opt.exp_avg_sq, wk),
                 *biases, pick(params, bk), pick(opt.exp_avg, bk), pick(opt.exp_avg_sq, bk), float(opt.lr), float(opt.betas[0]),
-                float(opt.betas[1]), float(opt.eps), opt.state.data_ptr(), stream.cuda_stream), "geom_dense_reduce_adam_f32")
+                float(opt.betas[1]), float(opt.eps), opt.state.data_ptr(), stream=stream.cuda_stream), "geom_dense_reduce_adam_f32")
             opt._stepped_in_backward = True
 
 

@@ -125,10 +125,8 @@ def forward_cuda(xyz1, xyz2, dist1, dist2, idx1, idx2, flags=None):
     b, n, _ = xyz1.shape
     m = xyz2.shape[1]
     with torch.cuda.device(xyz1.device):
-        code = _lib.lib().geom_chamfer_nn_f32(
-            b, n, xyz1.data_ptr(), m, xyz2.data_ptr(),
-            dist1.data_ptr(), idx1.data_ptr(), dist2.data_ptr(), idx2.data_ptr(),
-            flags, _lib.stream_ptr())
+        code = _lib.status("geom_chamfer_nn_f32", b, n, xyz1.data_ptr(), m, xyz2.data_ptr(),
+                           dist1.data_ptr(), idx1.data_ptr(), dist2.data_ptr(), idx2.data_ptr(), flags)
     _lib.check(code, "geom_chamfer_nn_f32")
 
 

@@ -46,6 +46,7 @@ from . import layers as _layers
 # columns of the block input) or j = X_j, the INPUT of layer j (X_{j} = output of layer j - 1).
 RESIDUALS = {2: "lead", 4: 3, 6: 5, 8: 7, 10: 9, 12: 11, 13: 13}
 LAYERS = 13
+assert LAYERS <= _lib.DEFORM_CHAIN_MAX      # the chain launches take the whole block
 
 # The block's hidden layers, one record per layer, in order -- what every route walks (the chain's forward and backward,
 # inference_chain, the separate operators of models.py).  index: 1-based; residual: None, "lead" (the leading 192 columns of the
@@ -107,7 +108,7 @@ def serves(block, features, pooled, csr):
 # timed against the separate operators yet (tools/time_deform_wide.py), and it goes on per batch only where that comparison
 # shows a win beyond its spread.
 wide = os.environ.get("GEOM_DEFORM_WIDE", "0") == "1"
-WIDE_MAX_BATCH = 64      # GEOM_DEFORM_WIDE_MAX_B
+WIDE_MAX_BATCH = _lib.DEFORM_WIDE_MAX_B
 
 
 def serves_wide(block, features, pooled, csr):
@@ -125,7 +126,7 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
-TAIL = 32      # GEOM_DEFORM_TAIL: entries of an adjacency row beyond the 8-wide neighbour table that the launches take
+TAIL = _lib.DEFORM_TAIL      # entries of an adjacency row beyond the 8-wide neighbour table that the launches take
 
 
 def _tail_tables(csr):
@@ -446,10 +447,11 @@ class _HiddenChain(torch.autograd.Function):
             jobs.append((dw_head, c * 3, g_head))
         n = len(jobs)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().geom_colsum_batch_f32(
+            _lib.check(_lib.status(
+                "geom_colsum_batch_f32",
                 n, (ctypes.c_void_p * n)(*[j[0].data_ptr() for j in jobs]), (ctypes.c_int * n)(*([nv] * n)),
-                (ctypes.c_int * n)(*[j[1] for j in jobs]), (ctypes.c_void_p * n)(*[j[2].data_ptr() for j in jobs]),
-                _lib.stream_ptr()), "geom_colsum_batch_f32")
+                (ctypes.c_int * n)(*[j[1] for j in jobs]), (ctypes.c_void_p * n)(*[j[2].data_ptr() for j in jobs])),
+                "geom_colsum_batch_f32")
         grads = [g_bias[i] for i in range(L)] + [g_w[i].view(1, c, c) for i in range(L - 1)] \
             + [g_bnw[i] for i in range(L)] + [g_bnb[i] for i in range(L)]
         g_wh = None

@@ -111,8 +111,7 @@ def reduce(jobs, stream=None):
     ptrs = lambda k: (ctypes.c_void_p * n)(*[None if j[k] is None else j[k].data_ptr() for j in jobs])
     dev = jobs[0][3].device
     with torch.cuda.device(dev):
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        _lib.check(_lib.lib().geom_dense_reduce_f32(n, ints(0), ints(1), ints(2), ptrs(3), ptrs(4), ptrs(5), s),
+        _lib.check(_lib.status("geom_dense_reduce_f32", n, ints(0), ints(1), ints(2), ptrs(3), ptrs(4), ptrs(5), stream=stream),
                    "geom_dense_reduce_f32")
 
 

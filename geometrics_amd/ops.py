@@ -342,11 +342,12 @@ class SurfaceLoss(torch.autograd.Function):
             tail = None
             if not two_sided and scan_finalize_tail and mesh_weight is None:    # (the in-launch roles know no per-mesh factors)
                 tail = _lib.SurfaceTail(choices.data_ptr(), scale / sq_pred.numel(), scale / sq.numel(), int(want), out.data_ptr(), 0)
-            _lib.check(L.geom_surface_scan_f32(
+            _lib.check(_lib.status(
+                "geom_surface_scan_f32",
                 b, n_gt, gt_c.data_ptr(), num, points.data_ptr(), sq_gt.data_ptr(), idx_p.data_ptr(), sq_pred.data_ptr(),
                 idx_g.data_ptr(), *tri_args, u.data_ptr(), v.data_ptr(), coef_s, coef_o, order.data_ptr() if want else None,
                 flags, ws_ptr, ws_len, ctypes.byref(wrote), ctypes.byref(cull) if cull is not None else None,
-                ctypes.byref(tail) if tail is not None else None, _lib.stream_ptr()), "geom_surface_scan_f32")
+                ctypes.byref(tail) if tail is not None else None), "geom_surface_scan_f32")
             # finalize: the loss reduction AND, when a gradient is wanted, the backward's preparation (points counting-sorted
             # by face in ascending id order; the records too when the scans could not write them) in one launch; the
             # backward is then a single gather launch
@@ -357,13 +358,12 @@ class SurfaceLoss(torch.autograd.Function):
                     sq_pred.data_ptr(), other_sq.data_ptr(), scale / sq_pred.numel(), scale / other_sq.numel(), coef_s, coef_o)
             if tail is None or not tail.finalized:
                 wptr = _lib.ptr(mesh_weight)
-                code = L.geom_surface_finalize_w_f32(*args, int(want), wrote.value, order.data_ptr(), out.data_ptr(), wptr,
-                                                     _lib.stream_ptr())
+                code = _lib.status("geom_surface_finalize_w_f32", *args, int(want), wrote.value, order.data_ptr(), out.data_ptr(), wptr)
                 if code == _lib.EUNSUPPORTED:       # too many faces + points for the in-LDS ordering: loss only, scatter backward
                     if mesh_weight is not None and want:
                         raise RuntimeError("per-mesh weights need the ordered backward (faces + points of a mesh within ~38 000)")
                     want = False
-                    code = L.geom_surface_finalize_w_f32(*args, 0, 0, order.data_ptr(), out.data_ptr(), wptr, _lib.stream_ptr())
+                    code = _lib.status("geom_surface_finalize_w_f32", *args, 0, 0, order.data_ptr(), out.data_ptr(), wptr)
                 _lib.check(code, "geom_surface_finalize_w_f32")
             ctx.order = order if want else None
             if tail is not None and tail.finalized and want:
@@ -485,8 +485,6 @@ class FanOut(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        import ctypes
-
         def rows(g):      # a [.., width] column slice of a wider row-major buffer is read in place
             if g.is_contiguous():
                 return g, g.shape[-1]
@@ -498,7 +496,7 @@ class FanOut(torch.autograd.Function):
         if not given:
             return None, None
         first = given[0][0]
-        fast = first.is_cuda and first.dtype == torch.float32 and len(given) <= 8 and first.dim() >= 1
+        fast = first.is_cuda and first.dtype == torch.float32 and len(given) <= _lib.SUM_MAX_TENSORS and first.dim() >= 1
         if len(given) == 1 or not fast:
             total = first.contiguous()
             for g, _ in given[1:]:
@@ -523,11 +521,10 @@ class SumScalars(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, *terms):
-        import ctypes
         ts = [t.reshape(()) for t in terms]
         out = torch.empty((), dtype=torch.float32, device=ts[0].device)
         ctx.n = len(ts)
-        if not all(t.is_cuda and t.dtype == torch.float32 for t in ts) or len(ts) > 8:
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in ts) or len(ts) > _lib.SUM_MAX_TENSORS:
             total = ts[0]
             for t in ts[1:]:
                 total = total + t
@@ -676,7 +673,6 @@ class PoolFeatures(torch.autograd.Function):
         if isinstance(headroom, (tuple, list)):
             headroom, fronts = headroom
         headroom = int(headroom or 0)
-        import ctypes
         v = _f32(verts, "verts_pos", 3, 3)
         cam_mat = _f32(cam_mat, "cam_mat", 3, 3)
         cam_pos = _f32(cam_pos, "cam_pos", 2, 3)
@@ -725,7 +721,6 @@ class PoolFeatures(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        import ctypes
         v, cam_mat, cam_pos = ctx.saved_tensors[:3]
         blks = ctx.saved_tensors[3:]
         ptrs, chans, dims, n = ctx.meta
@@ -857,24 +852,22 @@ def draw_samples(verts, faces, num, generator=None, with_points=False, prepare_s
                 if gt_index is not None:
                     s_index = torch.empty(max(int(_lib.lib().geom_nn_cull_index_floats(b, num)), 4), dtype=torch.float32, device=dev)
                     cull = _lib.SurfaceCull(None, None, s_index.data_ptr(), _lib.ptr(faces_in_order(verts_c, faces)))
-                code = _lib.lib().geom_surface_prepare_f32(
+                code = _lib.status(
+                    "geom_surface_prepare_f32",
                     b, nv, verts_c.data_ptr(), nf, faces.data_ptr(), num, _rng_state(dev).data_ptr(), choices.data_ptr(),
                     u.data_ptr(), v.data_ptr(), points.data_ptr(), n_gt, _lib.ptr(face_order(verts_c, faces)), 0,
-                    tri_ws.data_ptr(), ws_bytes, ctypes.byref(prepared), ctypes.byref(cull) if cull is not None else None,
-                    _lib.stream_ptr())
+                    tri_ws.data_ptr(), ws_bytes, ctypes.byref(prepared), ctypes.byref(cull) if cull is not None else None)
                 if code == 0:
                     if prepared.value & 2:
                         return choices, u, v, points, ScanPrep(tri_ws, s_index)
                     return choices, u, v, points, (tri_ws if prepared.value else None)
             else:
-                code = _lib.lib().geom_draw_samples_rng_f32(b, nv, verts_c.data_ptr(), faces.shape[0], faces.data_ptr(), num,
-                                                            _rng_state(dev).data_ptr(), choices.data_ptr(), u.data_ptr(),
-                                                            v.data_ptr(), _lib.ptr(points), _lib.stream_ptr())
+                code = _lib.status("geom_draw_samples_rng_f32", b, nv, verts_c.data_ptr(), faces.shape[0], faces.data_ptr(), num,
+                                   _rng_state(dev).data_ptr(), choices.data_ptr(), u.data_ptr(), v.data_ptr(), _lib.ptr(points))
         else:
             uniforms = torch.rand(3, b, num, device=dev, generator=generator)
-            code = _lib.lib().geom_draw_samples_f32(b, nv, verts_c.data_ptr(), faces.shape[0], faces.data_ptr(), num,
-                                                    uniforms.data_ptr(), choices.data_ptr(), u.data_ptr(),
-                                                    v.data_ptr(), _lib.stream_ptr())
+            code = _lib.status("geom_draw_samples_f32", b, nv, verts_c.data_ptr(), faces.shape[0], faces.data_ptr(), num,
+                               uniforms.data_ptr(), choices.data_ptr(), u.data_ptr(), v.data_ptr())
     if code == _lib.EUNSUPPORTED:
         if uniforms is None:
             uniforms = torch.rand(3, b, num, device=dev)

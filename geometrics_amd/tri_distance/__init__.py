@@ -157,14 +157,15 @@ def forward_cuda(xyz1, tri1, tri2, tri3, dist, point, index, flags=None, use_wor
         if use_workspace:
             ws, nbytes = _workspace(b, n, m, xyz1.device)
             order, order_ptr = _order_ptr(order, m, xyz1.device)
-            code = _lib.lib().geom_tri_distance_ws_f32(
+            code = _lib.status(
+                "geom_tri_distance_ws_f32",
                 b, n, xyz1.data_ptr(), m, tri1.data_ptr(), tri2.data_ptr(), tri3.data_ptr(), order_ptr,
-                dist.data_ptr(), point.data_ptr(), index.data_ptr(), flags, ws.data_ptr(), nbytes,
-                _lib.stream_ptr())
+                dist.data_ptr(), point.data_ptr(), index.data_ptr(), flags, ws.data_ptr(), nbytes)
         else:
-            code = _lib.lib().geom_tri_distance_f32(
+            code = _lib.status(
+                "geom_tri_distance_f32",
                 b, n, xyz1.data_ptr(), m, tri1.data_ptr(), tri2.data_ptr(), tri3.data_ptr(),
-                dist.data_ptr(), point.data_ptr(), index.data_ptr(), flags, _lib.stream_ptr())
+                dist.data_ptr(), point.data_ptr(), index.data_ptr(), flags)
     _lib.check(code, "geom_tri_distance_f32")
 
 
@@ -209,14 +210,15 @@ def tri_distance_indexed(xyz1, verts, faces, flags=None, use_workspace=True, ord
             if isinstance(order, str):
                 order = face_order(verts, faces)
             order, order_ptr = _order_ptr(order, faces.shape[0], dev)
-            code = _lib.lib().geom_tri_distance_indexed_ws_f32(
+            code = _lib.status(
+                "geom_tri_distance_indexed_ws_f32",
                 b, n, xyz1.data_ptr(), verts.shape[1], verts.data_ptr(), faces.shape[0], faces.data_ptr(), order_ptr,
-                dist.data_ptr(), point.data_ptr(), index.data_ptr(), flags, ws.data_ptr(), nbytes,
-                _lib.stream_ptr())
+                dist.data_ptr(), point.data_ptr(), index.data_ptr(), flags, ws.data_ptr(), nbytes)
         else:
-            code = _lib.lib().geom_tri_distance_indexed_f32(
+            code = _lib.status(
+                "geom_tri_distance_indexed_f32",
                 b, n, xyz1.data_ptr(), verts.shape[1], verts.data_ptr(), faces.shape[0], faces.data_ptr(),
-                dist.data_ptr(), point.data_ptr(), index.data_ptr(), flags, _lib.stream_ptr())
+                dist.data_ptr(), point.data_ptr(), index.data_ptr(), flags)
     _lib.check(code, "geom_tri_distance_indexed_f32")
     return dist, point, index
 

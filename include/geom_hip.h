@@ -14,6 +14,14 @@
  *      chamfer_distance/chamfer_distance.cu:70-72, tri_distance/tri_distance.cu:225-227.)
  *   - layouts are the reference's: contiguous AoS float32 [B,N,3], int32 index
  *     outputs (chamfer_distance/chamfer_distance.py:16-26, tri_distance/tri_distance.py:22-30).
+ *   - the python binding (geometrics_amd/_header.py) is READ from this file when the package is imported: argument types,
+ *     return types, argument structs and limits are stated here and nowhere else.  The reader accepts, outside comments,
+ *       `#define GEOM_X <integer>`                 written 16, 16u or (-3)
+ *       `typedef struct name { ... } name;`        fields `type a, *b;` (several declarators per type)
+ *       `type geom_name(type name, ...);`          or `(void)`; every parameter named, every name declared once
+ *     with type = int, unsigned, float, int64_t or size_t, or anything with a `*` (bound as an untyped pointer); a
+ *     function may also return `const char *`.  Everything else -- a struct by value, a function pointer, another
+ *     scalar type, a `geom_name(` in a macro -- makes the import fail rather than bind a guessed type.
  *
  * Paths in the comments are relative to the reference checkout (EdwardSmith1884/GEOMetrics).
  */

@@ -3,6 +3,7 @@ logic (mesh generator, adjacency, CSR, argument validation) -- no compute calls 
 import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -28,6 +29,11 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), "libgeom_hip.so does not export %s" % n
     assert sorted(_lib.declared_symbols()) == names, "ctypes table and header disagree"
     assert _lib.lib().geom_abi_version() == _lib.ABI_VERSION
+    # ... and nothing else: an exported geom_* function the header does not declare has no checked binding
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, stdout=subprocess.PIPE, text=True, timeout=60).stdout
+    exported = sorted(line.split()[2] for line in out.splitlines() if len(line.split()) == 3 and line.split()[1] in "Tt"
+                      and line.split()[2].startswith("geom_"))
+    assert exported == names, "libgeom_hip.so exports geom_* functions that include/geom_hip.h does not declare"
 
 
 def test_error_strings_and_argument_rejection_without_a_gpu():
