@@ -147,26 +147,29 @@ def _workspace(b, n, m, dev):
     return torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=dev), nbytes
 
 
+def _scan(names, xyz1, m, geometry, outputs, flags, use_workspace, order):
+    """One launch of a tri scan.  names: (workspace entry point, workspace-free one); geometry: the entry point's arguments
+    between xyz and order (the three corner arrays, or nv / verts / nf / faces); outputs: (dist, point, index)."""
+    b, n, _ = xyz1.shape
+    dev = xyz1.device
+    out = tuple(t.data_ptr() for t in outputs) + (flags,)
+    with torch.cuda.device(dev):
+        if use_workspace:
+            ws, nbytes = _workspace(b, n, m, dev)
+            order, order_ptr = _order_ptr(order, m, dev)
+            code = _lib.status(names[0], b, n, xyz1.data_ptr(), *geometry, order_ptr, *out, ws.data_ptr(), nbytes)
+        else:
+            code = _lib.status(names[1], b, n, xyz1.data_ptr(), *geometry, *out)
+    _lib.check(code, names[1])
+
+
 def forward_cuda(xyz1, tri1, tri2, tri3, dist, point, index, flags=None, use_workspace=True, order=None):
     """Same call shape as the reference's pybind `tri.forward_cuda` (tri_distance.cpp:16-30,34-36)."""
     if flags is None:
         flags = _lib.quirk_flags()
-    b, n, _ = xyz1.shape
     m = tri1.shape[1]
-    with torch.cuda.device(xyz1.device):
-        if use_workspace:
-            ws, nbytes = _workspace(b, n, m, xyz1.device)
-            order, order_ptr = _order_ptr(order, m, xyz1.device)
-            code = _lib.status(
-                "geom_tri_distance_ws_f32",
-                b, n, xyz1.data_ptr(), m, tri1.data_ptr(), tri2.data_ptr(), tri3.data_ptr(), order_ptr,
-                dist.data_ptr(), point.data_ptr(), index.data_ptr(), flags, ws.data_ptr(), nbytes)
-        else:
-            code = _lib.status(
-                "geom_tri_distance_f32",
-                b, n, xyz1.data_ptr(), m, tri1.data_ptr(), tri2.data_ptr(), tri3.data_ptr(),
-                dist.data_ptr(), point.data_ptr(), index.data_ptr(), flags)
-    _lib.check(code, "geom_tri_distance_f32")
+    _scan(("geom_tri_distance_ws_f32", "geom_tri_distance_f32"), xyz1, m,
+          (m, tri1.data_ptr(), tri2.data_ptr(), tri3.data_ptr()), (dist, point, index), flags, use_workspace, order)
 
 
 def tri_distance(xyz1, tri1, tri2, tri3, flags=None, use_workspace=True, order="auto"):
@@ -181,13 +184,11 @@ def tri_distance(xyz1, tri1, tri2, tri3, flags=None, use_workspace=True, order="
     for t in tris:
         if t.shape != tris[0].shape or t.shape[0] != b:
             raise RuntimeError("tri1/tri2/tri3 must share one [B,M,3] shape with xyz1's batch")
-    dist, point, index = _outputs(b, n, dev)
-    if flags is None:
-        flags = _lib.quirk_flags()
+    outputs = _outputs(b, n, dev)
     if isinstance(order, str):
         order = soup_order(*tris) if use_workspace else None
-    forward_cuda(xyz1, tris[0], tris[1], tris[2], dist, point, index, flags, use_workspace, order)
-    return dist, point, index
+    forward_cuda(xyz1, tris[0], tris[1], tris[2], *outputs, flags, use_workspace, order)
+    return outputs
 
 
 def tri_distance_indexed(xyz1, verts, faces, flags=None, use_workspace=True, order="auto"):
@@ -203,24 +204,12 @@ def tri_distance_indexed(xyz1, verts, faces, flags=None, use_workspace=True, ord
         raise RuntimeError("verts and xyz1 batch sizes differ")
     if flags is None:
         flags = _lib.quirk_flags()
-    dist, point, index = _outputs(b, n, dev)
-    with torch.cuda.device(dev):
-        if use_workspace:
-            ws, nbytes = _workspace(b, n, faces.shape[0], dev)
-            if isinstance(order, str):
-                order = face_order(verts, faces)
-            order, order_ptr = _order_ptr(order, faces.shape[0], dev)
-            code = _lib.status(
-                "geom_tri_distance_indexed_ws_f32",
-                b, n, xyz1.data_ptr(), verts.shape[1], verts.data_ptr(), faces.shape[0], faces.data_ptr(), order_ptr,
-                dist.data_ptr(), point.data_ptr(), index.data_ptr(), flags, ws.data_ptr(), nbytes)
-        else:
-            code = _lib.status(
-                "geom_tri_distance_indexed_f32",
-                b, n, xyz1.data_ptr(), verts.shape[1], verts.data_ptr(), faces.shape[0], faces.data_ptr(),
-                dist.data_ptr(), point.data_ptr(), index.data_ptr(), flags)
-    _lib.check(code, "geom_tri_distance_indexed_f32")
-    return dist, point, index
+    outputs = _outputs(b, n, dev)
+    if use_workspace and isinstance(order, str):
+        order = face_order(verts, faces)
+    _scan(("geom_tri_distance_indexed_ws_f32", "geom_tri_distance_indexed_f32"), xyz1, faces.shape[0],
+          (verts.shape[1], verts.data_ptr(), faces.shape[0], faces.data_ptr()), outputs, flags, use_workspace, order)
+    return outputs
 
 
 class TriDistanceFunction(torch.autograd.Function):

@@ -410,6 +410,50 @@ def test_tri_degenerate_triangles(oracle_mod, gpu):
         np.testing.assert_array_equal(np.isnan(d.cpu().numpy()), np.isnan(ed))
 
 
+def _split_case(nf):
+    """The smallest shape whose workspace scans split a query tile over two workgroups (2 meshes x 130 points = 6 tiles,
+    m_pad = ws_pad(nf) >= 2048 -> split = 2), so the merged keys go through tri_finalize_kernel: the first nf faces of the
+    level-4 icosphere; the second half of the points is moved out to radius 150, squared distance above 10000."""
+    verts, F, pts = _mesh_case(2, 4, 130, seed=nf)
+    pts = pts.copy()
+    far = pts[:, 65:]
+    pts[:, 65:] = far / np.maximum(np.linalg.norm(far, axis=-1, keepdims=True), 1e-6) * 150.0
+    return verts, np.ascontiguousarray(F[:nf]), np.ascontiguousarray(pts, np.float32)
+
+
+@pytest.mark.parametrize("nf", [2051, 2052, 2560])   # last reference tile of 3 (rule Q3 applies), of 4 (it does not), whole
+@pytest.mark.parametrize("flags", [0, FLAG_REF_TAIL_TRUNC, FLAG_FIX_REGION6, FLAG_REF_TAIL_TRUNC | FLAG_FIX_REGION6])
+def test_tri_split_tiles_finish_rule(oracle_mod, gpu, nf, flags):
+    """split > 1 under every flag: the finish rule (first-triangle seed, short-last-tile rule Q3) applied from merged keys,
+    with the first triangle at stride 3 * m_pad (flat scan) and in the `first` record (grouped scan).  Q3's
+    `acc_d > 10000` branch is taken for the far half of the queries and not for the near half."""
+    verts, F, pts = _split_case(nf)
+    t1, t2, t3 = (np.ascontiguousarray(verts[:, F[:, k]]) for k in range(3))
+    ed, _, ei = oracle_mod.tri_scan(pts, t1, t2, t3, flags)
+    full = oracle_mod.tri_scan(pts, t1, t2, t3, flags & ~FLAG_REF_TAIL_TRUNC)[0]
+    assert (full > 10000.0).sum() > 0 and (full <= 10000.0).sum() > 0
+    if (flags & FLAG_REF_TAIL_TRUNC) and nf == 2051:
+        replaced = (ed == 10000.0) & (ei == 0)
+        assert replaced.sum() > 0 and (~replaced).sum() > 0
+    _check_tri(oracle_mod, gpu, pts, verts, F, flags)
+
+
+def test_tri_split_tiles_degenerate_first_triangle(oracle_mod, gpu):
+    """split > 1 with a degenerate FIRST triangle: the NaN seed must stick in tri_finalize_kernel too."""
+    verts, F, pts = _split_case(2051)
+    F = F.copy()
+    F[0] = [3, 3, 3]
+    t1, t2, t3 = (np.ascontiguousarray(verts[:, F[:, k]]) for k in range(3))
+    ed, ep, ei = oracle_mod.tri_scan(pts, t1, t2, t3)
+    assert np.isnan(ed).any()
+    for order in (None, morton_order(_dev(verts[0][F].mean(1), gpu))):
+        for d, p, i in (tri_distance(_dev(pts, gpu), _dev(t1, gpu), _dev(t2, gpu), _dev(t3, gpu), 0, order=order),
+                        tri_distance_indexed(_dev(pts, gpu), _dev(verts, gpu), _dev(F, gpu), 0, order=order)):
+            np.testing.assert_array_equal(i.cpu().numpy(), ei)
+            np.testing.assert_array_equal(p.cpu().numpy(), ep)
+            np.testing.assert_array_equal(np.isnan(d.cpu().numpy()), np.isnan(ed))
+
+
 @pytest.mark.parametrize("case", ["on_vertices", "far_away", "offset_1000", "tiny_scale", "huge_scale", "slivers",
                                   "duplicate_faces", "points_on_surface", "batch8_baseline"])
 def test_tri_culling_is_exact_under_stress(oracle_mod, gpu, case):
