@@ -31,7 +31,8 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 EXTRA_FLAGS = {"dense_gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "zn_stack.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "deform_block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-               "encoder_stack.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+               "encoder_stack.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               "dense_dx_split_bf16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def sources():

@@ -6,6 +6,7 @@ products, exact fp32, with the layer's own epilogue / prologue folded in (see th
 Everything here takes 2-D row-major views: x [rows, cin] (rows = b*V), w [cin, c].
 """
 import ctypes
+import os
 
 import torch
 
@@ -31,6 +32,86 @@ def plan(rows, cin, c):
     ok = ok and c % 48 == 0        # the weight-gradient kernel: every wave owns whole 12-column groups of the output
     pair = pair and ok
     return {"fwd": "lib", "dx": "mfma" if pair else "lib", "dw": "mfma" if ok and rows >= 512 else "lib", "pair": pair}
+
+
+# A product whose input gradient plan() leaves with the library ("dx": "lib") runs it on the bf16 matrix cores instead
+# (backward_input_split) where wide_dx_plan() says so -- the 963-wide first layer at the training shape, 20 496 rows: 48 us
+# with its planes launch against the library's 85 launch against launch (tools/time_wide_dx.py, profiles/r07_wide_dx.txt).
+# The kernel keeps a workgroup's rows of G in LDS and every workgroup pulls all weight planes through L2 once, whatever its
+# row count, so it wants several 16-row blocks per compute unit: at the driver step's 7712 rows (482 row-blocks, under 2 per
+# CU) it is level with the library (31.1 against 32.9 us: inside the noise), and that shape stays where it was.  The
+# threshold is 4 row-blocks for each of 256 CUs.  (A rule of its own, not a key of plan(): plan()'s dictionary is what it was.)
+WIDE_DX_MIN_ROWS = 16384
+
+
+def wide_dx_plan(rows, cin, c):
+    return c == 192 and cin > 192 and rows >= WIDE_DX_MIN_ROWS
+
+
+# None: the rule above, or the environment's GEOM_WIDE_DX = lib | split;  "lib" / "split": force the library's product / the
+# kernel wherever it takes the operands, whatever the row count (tests, A/B measurements of one tree)
+wide_dx = None
+
+
+def wide_dx_takes(g, w, out=None):
+    """Whether g [.., 192] @ w [cin, 192]^T, a product the route leaves with the library, runs on backward_input_split."""
+    mode = wide_dx if wide_dx is not None else (os.environ.get("GEOM_WIDE_DX") or None)
+    if mode not in (None, "lib", "split"):
+        raise ValueError("GEOM_WIDE_DX / dense.wide_dx must be 'lib' or 'split' (got %r)" % (mode,))
+    if mode == "lib" or w.dim() != 2 or g.dim() < 2:
+        return False
+    cin, c = w.shape
+    rows = g.numel() // max(c, 1)
+    if not (c == 192 and g.shape[-1] == c and cin > 192 and rows >= 1 and rows * max(cin, c) < 2 ** 29):
+        return False
+    for t in (g, w) + (() if out is None else (out,)):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == g.device):
+            return False
+    if g.data_ptr() % 16 or w.data_ptr() % 16 or (out is not None and tuple(out.shape) != (rows, cin)):      # (out: contiguous, above)
+        return False
+    return mode == "split" or wide_dx_plan(rows, cin, c)
+
+
+def wide_dx_planes(w):
+    """w [cin, 192] fp32 -> its three bf16 planes (bit patterns as int16) in the order the kernel's waves read them (csrc/
+    dense_dx_split_bf16.hip, dx_frag_index); wide_dx_planes_matrix() puts them back into [3, cinpad, 192]."""
+    if not (w.is_cuda and w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous()):
+        raise ValueError("wide_dx_planes: a contiguous 2-D float32 tensor on a HIP device")
+    cin, c = w.shape
+    planes = torch.empty(3 * int(_lib.lib().geom_dense_dx_split_cinpad(cin)) * c, dtype=torch.int16, device=w.device)
+    with torch.cuda.device(w.device):
+        _lib.call("geom_dense_dx_split_planes_f32", cin, c, w.data_ptr(), planes.data_ptr())
+    return planes
+
+
+def wide_dx_planes_matrix(planes):
+    """The planes of wide_dx_planes as [3, cinpad, 192]: w == plane 0 + plane 1 + plane 2 exactly, rows cin .. cinpad - 1 zero."""
+    nt = int(_lib.lib().geom_dense_dx_split_cinpad(1)) // 16                 # column tiles of a wave's group
+    # [group][k-block][tile][plane][k group of 8][column in tile][k in group] -> [plane][group, tile, column][k-block, k group, k]
+    return planes.view(-1, 6, nt, 3, 4, 16, 8).permute(3, 0, 2, 5, 1, 4, 6).reshape(3, -1, 192)
+
+
+def backward_input_split(g, w, out=None):
+    """grad_x = g @ w.T (g [rows, 192], w [cin, 192], both contiguous fp32) with exact fp32 products on the bf16 matrix cores
+    (csrc/dense_dx_split_bf16.hip).  Two launches on the current stream on EVERY call: the split of w into three bf16 planes,
+    then the product -- nothing is cached, so a captured graph follows the weights it is replayed on.
+    Finite inputs: every product is exact (six terms g_i w_j, i + j <= 2; what is dropped is below 2^-24 of |g w|), the sum is
+    a fixed-order fp32 sum (the leading term in one accumulator, the five small ones in a second, k ascending), so the result
+    is bit-reproducible and a row's result does not depend on which other rows the call holds: a shard computes what the
+    whole batch would.  Non-finite inputs: an inf or NaN in a row of g makes that output row non-finite (an inf splits into
+    inf + NaN, so the class -- inf or NaN -- may differ from the library's) and leaves every other row alone.  Range edges:
+    a value within one bf16 ulp of FLT_MAX may round to inf; values below 2^-110 lose low bits (negligible in absolute terms)."""
+    rows, c = g.shape
+    cin = w.shape[0]
+    if not (g.is_cuda and g.dtype == torch.float32 and g.dim() == 2 and g.is_contiguous()):
+        raise ValueError("backward_input_split: g must be a contiguous float32 tensor on a HIP device")
+    planes = wide_dx_planes(w)
+    out = torch.empty(rows, cin, dtype=torch.float32, device=g.device) if out is None else out
+    if not (_row_major(out) and out.dtype == torch.float32 and out.device == g.device and tuple(out.shape) == (rows, cin)):
+        raise ValueError("backward_input_split: out must be a float32 [%d, %d] tensor with contiguous rows on g's device" % (rows, cin))
+    with torch.cuda.device(g.device):
+        _lib.call("geom_dense_dx_split_f32", rows, cin, c, g.data_ptr(), planes.data_ptr(), out.data_ptr(), out.stride(0) if rows > 1 else cin)
+    return out
 
 
 def forward(x, w, out=None):

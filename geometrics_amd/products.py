@@ -173,6 +173,12 @@ def _input_gradient(kind, g, w2, out=None):
         return _dense_kernels.gemm(g, w2, trans_b=True, out=out)
     if kind == "own":
         return _dense_kernels.backward_input(g, w2, out=out)
+    # "lib": the library's product -- or, where dense.wide_dx_plan says so (the 963-wide first layer at training size), the
+    # same product on the bf16 matrix cores.  route() does not know the difference: the kind names who owns the product's
+    # values (exact fp32 products, an fp32 sum), not which launch computes them
+    if _dense_kernels.wide_dx_takes(g, w2, out):
+        dx = _dense_kernels.backward_input_split(g.view(-1, g.shape[-1]), w2, out=out)
+        return dx if out is not None else dx.view(g.shape[:-1] + (w2.shape[0],))
     return torch.matmul(g, w2.t()) if out is None else torch.mm(g, w2.t(), out=out)
 
 

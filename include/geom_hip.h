@@ -462,6 +462,17 @@ int geom_deform_infer_fwd_f32(const geom_deform_infer *args, void *stream);
 int geom_split_bf16_kpad(int k);
 int geom_split_bf16_planes_f32(int k, int n, const float *w, uint16_t *planes, void *stream);
 int geom_gemm_split_bf16_f32(int m, int k, int n, const float *a, const uint16_t *planes, float *c, int terms, void *stream);
+/* The same arithmetic for the wide first layer's INPUT GRADIENT (csrc/dense_dx_split_bf16.hip): dx [rows, cin] = g [rows, 192] .
+ * w^T for w [cin, 192] row-major, any rows >= 0 and cin >= 1, c == 192 only (else GEOM_EUNSUPPORTED); dx row-major with a pitch
+ * of ldx >= cin floats (4-byte aligned rows), g 16-byte aligned.  Six terms, two fp32 accumulators per element (g0 w0 | the five small terms),
+ * k ascending, no split over k: an element depends on its own row of g and row of w only, so the result is bit-reproducible and
+ * the same whichever tile or launch computes the row.  A non-finite value in a row of g makes that output row non-finite (an
+ * infinity splits into inf + NaN) and touches no other row.  w comes as planes [3][cinpad][192] bf16 (cinpad =
+ * geom_dense_dx_split_cinpad(cin), padding rows zero) from geom_dense_dx_split_planes_f32, which the caller launches in front
+ * of EVERY product on the same stream: nothing is cached on the host, so a captured graph re-splits the weights it replays on. */
+int geom_dense_dx_split_cinpad(int cin);
+int geom_dense_dx_split_planes_f32(int cin, int c, const float *w, uint16_t *planes, void *stream);
+int geom_dense_dx_split_f32(int rows, int cin, int c, const float *g, const uint16_t *planes, float *dx, int ldx, void *stream);
 
 /* The regularisers of ONE deformation stage (GEOMetrics.py:147-161: edge term of the new positions + squared difference of
  * the Laplacian coordinates of the previous and the new positions + their squared displacement) in one launch per direction
