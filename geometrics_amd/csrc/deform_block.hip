@@ -19,9 +19,9 @@
 // Why this tiling: BatchNorm1d(verts) normalises a vertex over (batch, channel), so the natural tile is "all batch rows of one
 // vertex" -- exactly M = 16 of the fp32 MFMA -- and the only cross-tile dependencies of a layer are the two gathers
 // (neighbours' support rows forward, neighbours' dZ rows backward), which is where the launch boundaries sit.  The weight
-// operand follows zn_stack.hip: a wave owns 48 output columns and holds its 192 x 48 slice in 144 registers, requested at
-// kernel start so that it lands under the gather round trips; the activation tile goes through the same conflict-free
-// [k-quarter][row][52] LDS panel, one ds_read_b128 per 12 MFMAs.  482 workgroups of 4 waves, two resident per CU: while one
+// operand is the row-block product's of mfma_tiles.h (zn_stack.hip runs the same one): a wave owns 48 output columns and holds
+// its 192 x 48 slice in 144 registers, requested at kernel start so that it lands under the gather round trips; the activation
+// tile goes through that product's LDS panel, one ds_read_b128 per 12 MFMAs.  482 workgroups of 4 waves, two resident per CU: while one
 // waits for its gathers the other runs its 144 MFMAs per wave.
 //
 // Three forward bodies (db_fwd_body: plain and chain launches, one row tile per vertex; dbw_fwd_kernel: up to four tiles per
@@ -34,27 +34,23 @@
 // need the slice's registers); the eval body walks a per-row table and, once the slice is live, gathers in two rounds of four.
 // The chain kernels sit at 256 VGPRs already (tools/kernel_resources.sh): one body templated over the tile count, or the eval
 // table walk folded into db_aggregate, would trade these orders for one that fits none of them.
-#include "geom_common.h"
+#include "mfma_tiles.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-struct __attribute__((packed, aligned(4))) f3u { float x, y, z; };
+using namespace geom;
 
 constexpr int DB_THREADS = 256;
-constexpr int DB_C = 192;            // layer width
+constexpr int DB_C = RB_C;           // layer width
 constexpr int DB_K = 64;             // aggregated columns (split 3)
 constexpr int DB_W = 8;              // neighbour-table width
 constexpr int DB_TAIL = GEOM_DEFORM_TAIL; // width of the tail table (entries of a row beyond the neighbour table)
-constexpr int DB_LDR = 52;           // floats per (quarter, row) line of the operand panel: 48 used, pitch 13 x 16 B
-constexpr int DB_SUB = 16 * DB_LDR;  // one k-quarter of the panel
-constexpr int DB_PANEL = 4 * DB_SUB;
-constexpr int DB_LDC = DB_C + 4;     // row pitch of the output staging tile
-constexpr int DB_CST = 16 * DB_LDC;
 constexpr int DB_RED = 16;           // floats of reduction scratch
-constexpr unsigned DB_OOB = 0x80000000u;
+#ifdef DB_PROBE_FEW_MFMA // probe build: a sixth of the MFMAs (wrong results)
+constexpr int DB_PROBE = TILE_PROBE_FEW_MFMA;
+#else
+constexpr int DB_PROBE = TILE_PROBE_NONE;
+#endif
 
 #ifdef DB_PROBE_STAMPS
 // probe build (tools/probe/db_stamps.sh): shader-clock stamps of wave 0 of every workgroup at the phase boundaries
@@ -69,26 +65,6 @@ __device__ unsigned long long db_stamps[1024 * DB_STAMP_SLOTS];
 #else
 #define DB_STAMP(i) do { } while (0)
 #endif
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t db_rsrc(const void *p, int64_t bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, p ? (int)bytes : 0, 0x00020000);
-}
-// AGENT: the access of a chain launch that another workgroup of the SAME launch produces / consumes (sc1: through the XCD's L2
-// to the memory side, what an agent-scope atomic compiles to -- the eight L2s do not snoop each other)
-constexpr int DB_SC1 = 16;
-template <bool AGENT = false>
-__device__ __forceinline__ float4 db_ld4(__amdgpu_buffer_rsrc_t r, unsigned off)
-{
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, AGENT ? DB_SC1 : 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-template <bool AGENT = false>
-__device__ __forceinline__ void db_st4(__amdgpu_buffer_rsrc_t r, unsigned off, float4 v)
-{
-    __builtin_amdgcn_raw_buffer_store_b128((u32x4){__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)},
-                                           r, off, 0, AGENT ? DB_SC1 : 0);
-}
 
 // ---- the layers of a block as ONE launch (db_fwd_chain_kernel): a vertex's workgroup runs layer after layer and waits, in front
 // of a layer's gathers, until the workgroups of its NEIGHBOURS have published the previous layer's support rows -- the only
@@ -134,7 +110,7 @@ __device__ __forceinline__ void db_sum2(float &a, float &b, float *red)
 }
 
 // The wave's 192 x 48 slice of a weight, from the PACKED copy geom_deform_pack_weights_f32 makes once per step: element
-// e = (4 jp + c) * 3 + u of lane (x, g) of wave w is W[k = 48 g + 4 jp + c][48 w + 3 x + u] (zn_stack.hip's operand layout),
+// e = (4 jp + c) * 3 + u of lane (x, g) of wave w is W[k = 48 g + 4 jp + c][48 w + 3 x + u] (the row-block product's slice, mfma_tiles.h),
 // stored [wave][e / 4][lane][e % 4] -- every load instruction of a wave reads 1 KB of consecutive bytes (36 b128 loads per
 // lane instead of 48 12-byte loads whose 192-byte runs straddle cache lines: 1.67 x fewer L2 bytes -- all 482 workgroups
 // read the same 147 KB, the L2 of an XCD is what they queue at).
@@ -144,7 +120,7 @@ struct DbSlice {
 };
 __device__ __forceinline__ void db_load_slice(DbSlice &bw, const float *packed, int wave, int lane)
 {
-    const __amdgpu_buffer_rsrc_t r_b = db_rsrc(packed, (int64_t)DB_C * DB_C * 4);
+    const __amdgpu_buffer_rsrc_t r_b = rsrc(packed, (int64_t)DB_C * DB_C * 4);
     const unsigned b0 = ((unsigned)(wave * 36) * 64u + (unsigned)lane) * 16u;
 #pragma unroll
     for (int i = 0; i < 36; ++i) {
@@ -157,40 +133,12 @@ __device__ __forceinline__ void db_load_slice(DbSlice &bw, const float *packed, 
     }
 }
 
-// C tile [16 rows][192] = panel [16][192] . slice, into the staging tile (natural [row][col] layout, pitch DB_LDC)
+// C tile [16 rows][192] = panel [16][192] . slice, into the staging tile (natural [row][col] layout, pitch RB_LDC)
 __device__ __forceinline__ void db_product(const DbSlice &bw, const float *panel, float *stage, int wave, int x, int g)
 {
-    const float *pa = panel + g * DB_SUB + x * DB_LDR;
     f32x4 acc[3];
-#pragma unroll
-    for (int u = 0; u < 3; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x4 af = *reinterpret_cast<const f32x4 *>(pa);
-#pragma unroll
-    for (int jp = 0; jp < 12; ++jp) {
-        f32x4 an = af;
-        if (jp + 1 < 12) an = *reinterpret_cast<const f32x4 *>(pa + 4 * (jp + 1));
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-#ifdef DB_PROBE_FEW_MFMA
-            if (jp >= 2) continue; // probe: a sixth of the MFMAs (wrong results)
-#endif
-            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw.at(jp, c, 0), af[c], acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw.at(jp, c, 1), af[c], acc[1], 0, 0, 0);
-            acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw.at(jp, c, 2), af[c], acc[2], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        af = an;
-    }
-    // accumulator u of lane (x, g) holds C[row x][48 wave + 12 g + 3 r + u], r = 0..3: twelve consecutive columns
-    float e[12];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int u = 0; u < 3; ++u) e[3 * r + u] = acc[u][r];
-    float *dst = stage + x * DB_LDC + wave * 48 + 12 * g;
-#pragma unroll
-    for (int v = 0; v < 3; ++v) *reinterpret_cast<f32x4 *>(dst + 4 * v) = (f32x4){e[4 * v], e[4 * v + 1], e[4 * v + 2], e[4 * v + 3]};
+    rowblock_product<DB_PROBE>([&](int jp, int c, int u) { return bw.at(jp, c, u); }, panel + panel_offset(48 * g, x), acc);
+    rowblock_to_stage(acc, stage, wave, x, g);
 }
 
 // geom_deform_pack_weights_f32: thread = one element of one packed copy (2 * count copies of 36 864 floats)
@@ -282,11 +230,11 @@ __device__ __forceinline__ float4 db_aggregate(__amdgpu_buffer_rsrc_t r_src, boo
 #pragma unroll
     for (int n = 0; n < DB_W; ++n) {
         const unsigned off = rowbase + (unsigned)(nb[n] >= 0 ? nb[n] : v) * (DB_C * 4) + 4 * c0;
-        sv[n] = db_ld4<CHAIN>(r_src, mesh_on ? off : DB_OOB);
+        sv[n] = ld4<CHAIN>(r_src, mesh_on ? off : OOB);
     }
     const unsigned own_off = rowbase + (unsigned)v * (DB_C * 4) + 4 * c0;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) own[i] = db_ld4<CHAIN>(r_src, mesh_on ? own_off + 4 * DB_K * (i + 1) : DB_OOB);
+    for (int i = 0; i < 2; ++i) own[i] = ld4<CHAIN>(r_src, mesh_on ? own_off + 4 * DB_K * (i + 1) : OOB);
     float4 facc = make_float4(0.f, 0.f, 0.f, 0.f);
     auto table_terms = [&]() {
 #pragma unroll
@@ -309,7 +257,7 @@ __device__ __forceinline__ float4 db_aggregate(__amdgpu_buffer_rsrc_t r_src, boo
 #pragma unroll
     for (int n = 0; n < DB_TAIL; ++n) {
         const int col = __builtin_amdgcn_readlane(tcol, n);
-        tv[n] = db_ld4<CHAIN>(r_src, (mesh_on && col >= 0) ? rowbase + (unsigned)col * (DB_C * 4) + 4 * c0 : DB_OOB);
+        tv[n] = ld4<CHAIN>(r_src, (mesh_on && col >= 0) ? rowbase + (unsigned)col * (DB_C * 4) + 4 * c0 : OOB);
     }
     table_terms(); // summation order: the table's slots, then the tail, in CSR order
 #pragma unroll
@@ -329,8 +277,7 @@ __device__ __forceinline__ void db_to_panel(float *panel, int rl, int c0, const 
 {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        const int col = c0 + DB_K * i;
-        *reinterpret_cast<float4 *>(panel + (col / 48) * DB_SUB + rl * DB_LDR + col % 48) = x[i];
+        *reinterpret_cast<float4 *>(panel + panel_offset(c0 + DB_K * i, rl)) = x[i];
     }
 }
 
@@ -338,8 +285,8 @@ __device__ __forceinline__ void db_to_panel(float *panel, int rl, int c0, const 
 // and the eval launch those of vertex_bn's eval branch, so a body calls these and keeps only its own schedule (the top of the
 // file).  Values and fixed-size array references only: the bodies sit at the register ceiling, nothing here may reach scratch.
 
-// byte offset of the thread's float4 i (columns c0 + 64 i ..) of its own row, from that of float4 0 (DB_OOB: no row)
-__device__ __forceinline__ unsigned db_own(unsigned own_off, int i) { return own_off == DB_OOB ? DB_OOB : own_off + 4 * DB_K * i; }
+// byte offset of the thread's float4 i (columns c0 + 64 i ..) of its own row, from that of float4 0 (OOB: no row)
+__device__ __forceinline__ unsigned db_own(unsigned own_off, int i) { return own_off == OOB ? OOB : own_off + 4 * DB_K * i; }
 
 template <typename Args> // geom_deform_fwd or geom_deform_infer
 __device__ __forceinline__ float4 db_bias4(const Args &a, int c0, int i)
@@ -424,16 +371,16 @@ __device__ __forceinline__ void db_head_fwd(const float4 (&xo)[3], const float *
 }
 
 // The staging tile leaves in memory order (a row's 768 bytes are contiguous); row_offset(r) = byte offset of staging row r, or
-// DB_OOB.  AGENT: rows another workgroup of the same launch gathers.
+// OOB.  AGENT: rows another workgroup of the same launch gathers.
 template <bool AGENT, typename RowOffset>
 __device__ __forceinline__ void db_store_tile(const float *stage, __amdgpu_buffer_rsrc_t r_s, RowOffset row_offset)
 {
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
         const int idx = (int)threadIdx.x + DB_THREADS * t, r = idx / 48, c4 = idx % 48;
-        const f32x4 val = *reinterpret_cast<const f32x4 *>(stage + r * DB_LDC + 4 * c4);
+        const f32x4 val = *reinterpret_cast<const f32x4 *>(stage + r * RB_LDC + 4 * c4);
         const unsigned row = row_offset(r);
-        db_st4<AGENT>(r_s, row == DB_OOB ? DB_OOB : row + 16u * c4, make_float4(val[0], val[1], val[2], val[3]));
+        st4<AGENT>(r_s, row == OOB ? OOB : row + 16u * c4, make_float4(val[0], val[1], val[2], val[3]));
     }
 }
 // ... or returns to the thread's registers (its row rl, columns c0 + 64 i ..)
@@ -441,7 +388,7 @@ __device__ __forceinline__ void db_load_tile(const float *stage, int rl, int c0,
 {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        const f32x4 t = *reinterpret_cast<const f32x4 *>(stage + rl * DB_LDC + c0 + DB_K * i);
+        const f32x4 t = *reinterpret_cast<const f32x4 *>(stage + rl * RB_LDC + c0 + DB_K * i);
         go[i] = make_float4(t[0], t[1], t[2], t[3]);
     }
 }
@@ -470,7 +417,7 @@ __device__ __forceinline__ void db_bn_bwd_elems(const geom_deform_bwd &a, float 
                                  db_bn_bwd_elem(a, mean, invstd, gamma, beta, mesh_on, zv.y, go.y, second.y, xh.y, sum_g, sum_gx),
                                  db_bn_bwd_elem(a, mean, invstd, gamma, beta, mesh_on, zv.z, go.z, second.z, xh.z, sum_g, sum_gx),
                                  db_bn_bwd_elem(a, mean, invstd, gamma, beta, mesh_on, zv.w, go.w, second.w, xh.w, sum_g, sum_gx));
-    if (a.has_res && a.grad_res) db_st4(r_gr, off, r);
+    if (a.has_res && a.grad_res) st4(r_gr, off, r);
 }
 // after the reduction: the BatchNorm parameter gradients of vertex v
 __device__ __forceinline__ void db_publish_bn_grads(const geom_deform_bwd &a, int v, float sum_g, float sum_gx)
@@ -545,9 +492,9 @@ __device__ __forceinline__ void db_aggregate_and_store_own_row(__amdgpu_buffer_r
     bool arrived = true;
     gs[0] = db_aggregate<SLICE, CHAIN>(r_src, mesh_on, rowbase, v, c0, tb, &gs[1], bw, packed, wave, lane, done, need, &arrived);
     if (CHAIN && !arrived) gs[0].x = __builtin_nanf("");
-    const unsigned own_off = mesh_on ? rowbase + (unsigned)v * (DB_C * 4) + 4 * c0 : DB_OOB;
+    const unsigned own_off = mesh_on ? rowbase + (unsigned)v * (DB_C * 4) + 4 * c0 : OOB;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) db_st4(r_dst, db_own(own_off, i), gs[i]);
+    for (int i = 0; i < 3; ++i) st4(r_dst, db_own(own_off, i), gs[i]);
 }
 
 // One layer of vertex v.  CHAIN: layer `layer` (0-based) of a chain launch -- layer > 0 reads the previous layer's support
@@ -563,9 +510,9 @@ __device__ __forceinline__ void db_fwd_body(const geom_deform_fwd &a, const int 
     DB_STAMP(0);
     const bool mesh_on = rl < a.b;
     const int64_t op_bytes = (int64_t)a.b * a.nv * DB_C * 4;
-    const __amdgpu_buffer_rsrc_t r_src = db_rsrc(a.s_in, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_src = rsrc(a.s_in, op_bytes);
     const unsigned rowbase = (unsigned)rl * (unsigned)a.nv * (DB_C * 4);
-    const unsigned own_off = mesh_on ? rowbase + (unsigned)v * (DB_C * 4) + 4 * c0 : DB_OOB;
+    const unsigned own_off = mesh_on ? rowbase + (unsigned)v * (DB_C * 4) + 4 * c0 : OOB;
     // the vertex's BatchNorm parameters, the bias and the residual travel with the gathers
     const float gamma = a.bn_w ? a.bn_w[v] : 1.f, beta = a.bn_b ? a.bn_b[v] : 0.f;
     const bool updates = a.training && tid == 0;
@@ -574,10 +521,10 @@ __device__ __forceinline__ void db_fwd_body(const geom_deform_fwd &a, const int 
 #pragma unroll
     for (int i = 0; i < 3; ++i) bias4[i] = db_bias4(a, c0, i), rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (a.res) {
-        const __amdgpu_buffer_rsrc_t r_res = db_rsrc(a.res, ((int64_t)a.b * a.nv - 1) * a.res_ld * 4 + DB_C * 4);
+        const __amdgpu_buffer_rsrc_t r_res = rsrc(a.res, ((int64_t)a.b * a.nv - 1) * a.res_ld * 4 + DB_C * 4);
         const unsigned roff = ((unsigned)rl * (unsigned)a.nv + (unsigned)v) * (unsigned)a.res_ld * 4u + 4 * c0;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) rv[i] = db_ld4(r_res, mesh_on ? roff + 4 * DB_K * i : DB_OOB);
+        for (int i = 0; i < 3; ++i) rv[i] = ld4(r_res, mesh_on ? roff + 4 * DB_K * i : OOB);
     }
     // The weight slice is requested BEHIND the gathers: the vector-memory counter retires in order, so a wave that asked for
     // its 36 KB of weights first would wait for them in front of every gather (the table entries come by scalar loads, which
@@ -596,7 +543,7 @@ __device__ __forceinline__ void db_fwd_body(const geom_deform_fwd &a, const int 
 
     DB_STAMP(1); // gathers arrived (z holds the aggregated row)
     // ---- BatchNorm1d(verts): one statistic per vertex over its b * 192 values (two-pass: mean, then the centred second moment)
-    float *red = lds + DB_PANEL + DB_CST;
+    float *red = lds + RB_PANEL + RB_CST;
     const int n = a.b * DB_C;
     DbNorm bn;
     if (a.training) {
@@ -617,11 +564,11 @@ __device__ __forceinline__ void db_fwd_body(const geom_deform_fwd &a, const int 
     DB_STAMP(2); // statistics done
     float4 xo[3];
     db_norm_apply(a, bn, z, rv, mesh_on, xo);
-    const __amdgpu_buffer_rsrc_t r_z = db_rsrc(a.z_out, op_bytes), r_x = db_rsrc(a.x_out, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_z = rsrc(a.z_out, op_bytes), r_x = rsrc(a.x_out, op_bytes);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        if (a.z_out) db_st4(r_z, db_own(own_off, i), z[i]);
-        db_st4(r_x, db_own(own_off, i), xo[i]);
+        if (a.z_out) st4(r_z, db_own(own_off, i), z[i]);
+        st4(r_x, db_own(own_off, i), xo[i]);
     }
     if (!PRODUCT) {
         // ---- the coordinate head's product inside the last hidden layer's launch
@@ -641,7 +588,7 @@ __device__ __forceinline__ void db_fwd_body(const geom_deform_fwd &a, const int 
     DB_STAMP(3); // outputs requested, panel written
     __syncthreads();
     DB_STAMP(4);
-    float *stage = lds + DB_PANEL;
+    float *stage = lds + RB_PANEL;
 #ifdef DB_PROBE_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // probe: separate the wait for the weight slice from the MFMAs
     DB_STAMP(5);
@@ -650,8 +597,8 @@ __device__ __forceinline__ void db_fwd_body(const geom_deform_fwd &a, const int 
     DB_STAMP(6); // MFMAs issued + staged
     __syncthreads();
     DB_STAMP(7);
-    const __amdgpu_buffer_rsrc_t r_s = db_rsrc(a.s_out, op_bytes);
-    db_store_tile<CHAIN>(stage, r_s, [&](int r) { return r < a.b ? ((unsigned)r * (unsigned)a.nv + (unsigned)v) * (DB_C * 4) : DB_OOB; });
+    const __amdgpu_buffer_rsrc_t r_s = rsrc(a.s_out, op_bytes);
+    db_store_tile<CHAIN>(stage, r_s, [&](int r) { return r < a.b ? ((unsigned)r * (unsigned)a.nv + (unsigned)v) * (DB_C * 4) : OOB; });
     DB_STAMP(8);
     if (CHAIN) { // publish: every wave's stores are acknowledged (written through), then the vertex's count moves
         __builtin_amdgcn_s_waitcnt(0);
@@ -663,7 +610,7 @@ __device__ __forceinline__ void db_fwd_body(const geom_deform_fwd &a, const int 
 template <bool PRODUCT>
 __global__ __launch_bounds__(DB_THREADS, 2) void db_fwd_kernel(geom_deform_fwd a)
 {
-    __shared__ __attribute__((aligned(16))) float lds[DB_PANEL + DB_CST + DB_RED];
+    __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST + DB_RED];
     const int v = db_vertex(blockIdx.x, a.vpx, a.nv);
     if (v < 0) return;
     db_fwd_body<PRODUCT, false>(a, v, lds, nullptr, 0, nullptr);
@@ -677,7 +624,7 @@ struct DbFwdChain {
 
 __global__ __launch_bounds__(DB_THREADS, 2) void db_fwd_chain_kernel(DbFwdChain c)
 {
-    __shared__ __attribute__((aligned(16))) float lds[DB_PANEL + DB_CST + DB_RED];
+    __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST + DB_RED];
     const int v = db_vertex(blockIdx.x, c.layer[0].vpx, c.layer[0].nv);
     if (v < 0) return;
     const DbTable tb = db_table(v, c.layer[0].ell_col, c.layer[0].ell_val, c.layer[0].tail_col, c.layer[0].tail_val, threadIdx.x & 63);
@@ -702,24 +649,24 @@ __device__ __forceinline__ void db_bwd_body(const geom_deform_bwd &a, const int 
     const bool mesh_on = rl < a.b;
     const int64_t op_bytes = (int64_t)a.b * a.nv * DB_C * 4;
     const unsigned rowbase = (unsigned)rl * (unsigned)a.nv * (DB_C * 4);
-    const unsigned own_off = mesh_on ? rowbase + (unsigned)v * (DB_C * 4) + 4 * c0 : DB_OOB;
+    const unsigned own_off = mesh_on ? rowbase + (unsigned)v * (DB_C * 4) + 4 * c0 : OOB;
     // everything this layer's BatchNorm backward reads is requested with the gathers
     // g / g2 may be column slices of wider row-major buffers (row pitch g_ld / g2_ld floats; dword-aligned 16-byte buffer loads):
     // the next block's input gradient is read in place instead of through a slicing copy
     const int g_ld = a.g_ld ? a.g_ld : DB_C, g2_ld = a.g2_ld ? a.g2_ld : DB_C;
-    const __amdgpu_buffer_rsrc_t r_z = db_rsrc(a.z, op_bytes);
-    const __amdgpu_buffer_rsrc_t r_g2 = db_rsrc(a.g2, ((int64_t)a.b * a.nv - 1) * g2_ld * 4 + DB_C * 4);
-    const __amdgpu_buffer_rsrc_t r_g = db_rsrc(a.g, ((int64_t)a.b * a.nv - 1) * g_ld * 4 + DB_C * 4);
-    const unsigned g_off = mesh_on ? (((unsigned)rl * (unsigned)a.nv + (unsigned)v) * (unsigned)g_ld + (unsigned)c0) * 4u : DB_OOB;
-    const unsigned g2_off = mesh_on ? (((unsigned)rl * (unsigned)a.nv + (unsigned)v) * (unsigned)g2_ld + (unsigned)c0) * 4u : DB_OOB;
+    const __amdgpu_buffer_rsrc_t r_z = rsrc(a.z, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_g2 = rsrc(a.g2, ((int64_t)a.b * a.nv - 1) * g2_ld * 4 + DB_C * 4);
+    const __amdgpu_buffer_rsrc_t r_g = rsrc(a.g, ((int64_t)a.b * a.nv - 1) * g_ld * 4 + DB_C * 4);
+    const unsigned g_off = mesh_on ? (((unsigned)rl * (unsigned)a.nv + (unsigned)v) * (unsigned)g_ld + (unsigned)c0) * 4u : OOB;
+    const unsigned g2_off = mesh_on ? (((unsigned)rl * (unsigned)a.nv + (unsigned)v) * (unsigned)g2_ld + (unsigned)c0) * 4u : OOB;
     const float mean = a.save_mean[v], invstd = a.save_invstd[v];
     const float gamma = a.bn_w ? a.bn_w[v] : 1.f, beta = a.bn_b ? a.bn_b[v] : 0.f;
     float4 zv[3], g2v[3], go[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        zv[i] = db_ld4(r_z, db_own(own_off, i));
-        g2v[i] = a.g2 ? db_ld4(r_g2, db_own(g2_off, i)) : make_float4(0.f, 0.f, 0.f, 0.f);
-        if (!PRODUCT) go[i] = a.g ? db_ld4(r_g, db_own(g_off, i)) : make_float4(0.f, 0.f, 0.f, 0.f);
+        zv[i] = ld4(r_z, db_own(own_off, i));
+        g2v[i] = a.g2 ? ld4(r_g2, db_own(g2_off, i)) : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!PRODUCT) go[i] = a.g ? ld4(r_g, db_own(g_off, i)) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     if (!PRODUCT && a.ds_head) {
         // ---- the coordinate head inside the first backward launch (db_head_bwd_*)
@@ -728,11 +675,11 @@ __device__ __forceinline__ void db_bwd_body(const geom_deform_bwd &a, const int 
             const float *src = a.ds_head + ((size_t)rl * a.nv + v) * 3;
             dsh[0] = src[0], dsh[1] = src[1], dsh[2] = src[2];
         }
-        const __amdgpu_buffer_rsrc_t r_xt = db_rsrc(a.x_top, op_bytes);
-        float *wsum = lds + DB_PANEL; // [4 waves][192 * 3]
+        const __amdgpu_buffer_rsrc_t r_xt = rsrc(a.x_top, op_bytes);
+        float *wsum = lds + RB_PANEL; // [4 waves][192 * 3]
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            const float4 xt = a.dw_head ? db_ld4(r_xt, db_own(own_off, i)) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 xt = a.dw_head ? ld4(r_xt, db_own(own_off, i)) : make_float4(0.f, 0.f, 0.f, 0.f);
             const float xv[4] = {xt.x, xt.y, xt.z, xt.w};
             float add[4];
 #pragma unroll
@@ -748,10 +695,10 @@ __device__ __forceinline__ void db_bwd_body(const geom_deform_bwd &a, const int 
         }
         if (a.dw_head) db_head_bwd_weight_reduce(wsum, a.dw_head, v);
     }
-    float *stage = lds + DB_PANEL;
+    float *stage = lds + RB_PANEL;
     if (PRODUCT) {
         // ---- aggregation backward of the layer above: G = [A^T . dZ_up[:, :64] | dZ_up[:, 64:]]
-        const __amdgpu_buffer_rsrc_t r_src = db_rsrc(a.dz_up, op_bytes), r_ds = db_rsrc(a.ds_up, op_bytes);
+        const __amdgpu_buffer_rsrc_t r_src = rsrc(a.dz_up, op_bytes), r_ds = rsrc(a.ds_up, op_bytes);
         float4 gs[3]; // (stored: the layer above's weight gradient reads it, X^T . G)
         DbSlice bw;
         if (CHAIN) {
@@ -777,11 +724,11 @@ __device__ __forceinline__ void db_bwd_body(const geom_deform_bwd &a, const int 
     // ---- this layer: residual scale, ReLU mask, BatchNorm backward
     float sum_g = 0.f, sum_gx = 0.f;
     float4 xh[3];
-    const __amdgpu_buffer_rsrc_t r_gr = db_rsrc(a.grad_res, op_bytes), r_dz = db_rsrc(a.dz, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_gr = rsrc(a.grad_res, op_bytes), r_dz = rsrc(a.dz, op_bytes);
 #pragma unroll
     for (int i = 0; i < 3; ++i)
         db_bn_bwd_elems(a, mean, invstd, gamma, beta, mesh_on, zv[i], go[i], g2v[i], xh[i], sum_g, sum_gx, r_gr, db_own(own_off, i));
-    float *red = lds + DB_PANEL + DB_CST;
+    float *red = lds + RB_PANEL + RB_CST;
     DB_STAMP(6);
     db_sum2(sum_g, sum_gx, red);
     DB_STAMP(7);
@@ -792,7 +739,7 @@ __device__ __forceinline__ void db_bwd_body(const geom_deform_bwd &a, const int 
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         dz[i] = db_bn_bwd_dz4(kk, go[i], xh[i], mg, mgx, mesh_on);
-        db_st4<CHAIN>(r_dz, db_own(own_off, i), dz[i]);
+        st4<CHAIN>(r_dz, db_own(own_off, i), dz[i]);
     }
     if (a.colsum) db_colsum(dz, stage, a.colsum, v, c0); // the bias gradient of this layer
     DB_STAMP(8);
@@ -806,7 +753,7 @@ __device__ __forceinline__ void db_bwd_body(const geom_deform_bwd &a, const int 
 template <bool PRODUCT>
 __global__ __launch_bounds__(DB_THREADS, 2) void db_bwd_kernel(geom_deform_bwd a)
 {
-    __shared__ __attribute__((aligned(16))) float lds[DB_PANEL + DB_CST + DB_RED];
+    __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST + DB_RED];
     const int v = db_vertex(blockIdx.x, a.vpx, a.nv);
     if (v < 0) return;
     db_bwd_body<PRODUCT, false>(a, v, lds, nullptr, 0, nullptr);
@@ -821,7 +768,7 @@ struct DbBwdChain {
 
 __global__ __launch_bounds__(DB_THREADS, 2) void db_bwd_chain_kernel(DbBwdChain c)
 {
-    __shared__ __attribute__((aligned(16))) float lds[DB_PANEL + DB_CST + DB_RED];
+    __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST + DB_RED];
     const int v = db_vertex(blockIdx.x, c.layer[0].vpx, c.layer[0].nv);
     if (v < 0) return;
     const geom_deform_bwd &t = c.layer[c.count > 1 ? 1 : 0]; // (the top layer may come without tables)
@@ -840,7 +787,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void db_bwd_chain_kernel(DbBwdChain 
         const bool mesh_on = rl < a.b;
         const int64_t op_bytes = (int64_t)a.b * a.nv * DB_C * 4;
         const unsigned rowbase = (unsigned)rl * (unsigned)a.nv * (DB_C * 4);
-        const __amdgpu_buffer_rsrc_t r_src = db_rsrc(a.dz, op_bytes), r_ds = db_rsrc(c.ds_first, op_bytes);
+        const __amdgpu_buffer_rsrc_t r_src = rsrc(a.dz, op_bytes), r_ds = rsrc(c.ds_first, op_bytes);
         float4 gs[3];
         DbSlice none;
         db_aggregate_and_store_own_row<false, true>(r_src, r_ds, mesh_on, rowbase, v, c0, tb, gs, none, nullptr, wave, lane, c.done, c.count);
@@ -883,9 +830,9 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
     const bool on = r < rows;
     const int mesh = on ? r / a.nv : 0, v = on ? r - mesh * a.nv : 0;
     const int64_t op_bytes = (int64_t)rows * DB_C * 4;
-    const __amdgpu_buffer_rsrc_t r_src = db_rsrc(a.s_in, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_src = rsrc(a.s_in, op_bytes);
     const unsigned rowbase = (unsigned)mesh * (unsigned)a.nv * (DB_C * 4);
-    const unsigned own_off = on ? (unsigned)r * (DB_C * 4) + 4 * c0 : DB_OOB;
+    const unsigned own_off = on ? (unsigned)r * (DB_C * 4) + 4 * c0 : OOB;
     // round trip 1: the row's table, the first entry of its tail row, the vertex's BatchNorm parameters and running
     // statistics, the bias and the residual
     int nb[DB_W];
@@ -904,10 +851,10 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
 #pragma unroll
     for (int i = 0; i < 3; ++i) bias4[i] = db_bias4(a, c0, i), rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (a.res) {
-        const __amdgpu_buffer_rsrc_t r_res = db_rsrc(a.res, ((int64_t)rows - 1) * a.res_ld * 4 + DB_C * 4);
+        const __amdgpu_buffer_rsrc_t r_res = rsrc(a.res, ((int64_t)rows - 1) * a.res_ld * 4 + DB_C * 4);
         const unsigned roff = (unsigned)r * (unsigned)a.res_ld * 4u + 4 * c0;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) rv[i] = db_ld4(r_res, on ? roff + 4 * DB_K * i : DB_OOB);
+        for (int i = 0; i < 3; ++i) rv[i] = ld4(r_res, on ? roff + 4 * DB_K * i : OOB);
     }
     // round trip 2: the neighbour rows + the thread's own pass-through elements; the weight slice behind them (the
     // vector-memory counter retires in order: asked for first, it would hold up every gather).  A later row-block of the
@@ -916,14 +863,14 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
     constexpr int ROUND = LOAD_SLICE || !PRODUCT ? DB_W : DB_W / 2;
     float4 z[3];
 #pragma unroll
-    for (int i = 1; i < 3; ++i) z[i] = db_ld4(r_src, db_own(own_off, i));
+    for (int i = 1; i < 3; ++i) z[i] = ld4(r_src, db_own(own_off, i));
     float4 facc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int n0 = 0; n0 < DB_W; n0 += ROUND) {
         float4 sv[ROUND];
 #pragma unroll
         for (int n = 0; n < ROUND; ++n)
-            sv[n] = db_ld4(r_src, on ? rowbase + (unsigned)(nb[n0 + n] >= 0 ? nb[n0 + n] : v) * (DB_C * 4) + 4 * c0 : DB_OOB);
+            sv[n] = ld4(r_src, on ? rowbase + (unsigned)(nb[n0 + n] >= 0 ? nb[n0 + n] : v) * (DB_C * 4) + 4 * c0 : OOB);
         if (LOAD_SLICE) db_load_slice(bw, a.w_next, wave, lane);
 #pragma unroll
         for (int n = 0; n < ROUND; ++n) {
@@ -941,7 +888,7 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
             if (tc[0] < 0) break;
             float4 tv[4];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) tv[t] = db_ld4(r_src, (on && tc[t] >= 0) ? rowbase + (unsigned)tc[t] * (DB_C * 4) + 4 * c0 : DB_OOB);
+            for (int t = 0; t < 4; ++t) tv[t] = ld4(r_src, (on && tc[t] >= 0) ? rowbase + (unsigned)tc[t] * (DB_C * 4) + 4 * c0 : OOB);
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 if (tc[t] >= 0) {
@@ -955,9 +902,9 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
     float4 xo[3];
     db_norm_apply(a, bn, z, rv, on, xo); // BatchNorm on the running statistics
     if (a.x_out) {
-        const __amdgpu_buffer_rsrc_t r_x = db_rsrc(a.x_out, op_bytes);
+        const __amdgpu_buffer_rsrc_t r_x = rsrc(a.x_out, op_bytes);
 #pragma unroll
-        for (int i = 0; i < 3; ++i) db_st4(r_x, db_own(own_off, i), xo[i]);
+        for (int i = 0; i < 3; ++i) st4(r_x, db_own(own_off, i), xo[i]);
     }
     if (!PRODUCT) {
         // the coordinate head's raw support s_head[row] = X'[row] . W_head
@@ -974,13 +921,13 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
     // the next layer's product on the tile (rows beyond the last are zero rows of the panel)
     db_to_panel(lds, rl, c0, xo);
     __syncthreads();
-    float *stage = lds + DB_PANEL;
+    float *stage = lds + RB_PANEL;
     db_product(bw, lds, stage, wave, x, g);
     __syncthreads();
-    const __amdgpu_buffer_rsrc_t r_s = db_rsrc(a.s_out, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_s = rsrc(a.s_out, op_bytes);
     db_store_tile<false>(stage, r_s, [&](int rr) { // (16 consecutive rows = 12 KB contiguous)
         const int row = rb * 16 + rr;
-        return row < rows ? (unsigned)row * (DB_C * 4) : DB_OOB;
+        return row < rows ? (unsigned)row * (DB_C * 4) : OOB;
     });
     // (the next row-block writes the panel, which nobody reads any more; the staging tile only after its first barrier)
 }
@@ -988,7 +935,7 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
 template <bool PRODUCT>
 __global__ __launch_bounds__(DB_THREADS, 2) void di_fwd_kernel(geom_deform_infer a, int nrb, int nwg, int per_xcd)
 {
-    __shared__ __attribute__((aligned(16))) float lds[DB_PANEL + DB_CST];
+    __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST];
     const int w = blockIdx.x;
     const int lw = (w & 7) * per_xcd + (w >> 3); // logical workgroup: contiguous runs per XCD (workgroup w runs on XCD w % 8)
     if (lw >= nwg) return;
@@ -1020,7 +967,7 @@ constexpr int DBW_TILES = GEOM_DEFORM_WIDE_MAX_B / 16;
 template <bool PRODUCT>
 __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd a)
 {
-    __shared__ __attribute__((aligned(16))) float lds[DB_PANEL + DB_CST + DB_RED];
+    __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST + DB_RED];
     const int v = db_vertex(blockIdx.x, a.vpx, a.nv);
     if (v < 0) return;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1029,19 +976,19 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd 
     const int c0 = 4 * j;
     const int tiles = (a.b + 15) >> 4;
     const int64_t op_bytes = (int64_t)a.b * a.nv * DB_C * 4;
-    const __amdgpu_buffer_rsrc_t r_src = db_rsrc(a.s_in, op_bytes);
-    const __amdgpu_buffer_rsrc_t r_z = db_rsrc(a.z_out, op_bytes), r_x = db_rsrc(a.x_out, op_bytes);
-    const __amdgpu_buffer_rsrc_t r_res = db_rsrc(a.res, ((int64_t)a.b * a.nv - 1) * a.res_ld * 4 + DB_C * 4);
-    // byte offset of the thread's first float4 of tile t in a [b, nv, 192] operand (DB_OOB: a row at or beyond b)
+    const __amdgpu_buffer_rsrc_t r_src = rsrc(a.s_in, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_z = rsrc(a.z_out, op_bytes), r_x = rsrc(a.x_out, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_res = rsrc(a.res, ((int64_t)a.b * a.nv - 1) * a.res_ld * 4 + DB_C * 4);
+    // byte offset of the thread's first float4 of tile t in a [b, nv, 192] operand (OOB: a row at or beyond b)
     auto own = [&](int t) {
         const int mesh = 16 * t + rl;
-        return mesh < a.b ? ((unsigned)mesh * (unsigned)a.nv + (unsigned)v) * (DB_C * 4) + 4 * c0 : DB_OOB;
+        return mesh < a.b ? ((unsigned)mesh * (unsigned)a.nv + (unsigned)v) * (DB_C * 4) + 4 * c0 : OOB;
     };
     auto residual = [&](int t, float4 (&rv)[3]) {
         const int mesh = 16 * t + rl;
         const unsigned roff = ((unsigned)mesh * (unsigned)a.nv + (unsigned)v) * (unsigned)a.res_ld * 4u + 4 * c0;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) rv[i] = a.res ? db_ld4(r_res, mesh < a.b ? roff + 4 * DB_K * i : DB_OOB) : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int i = 0; i < 3; ++i) rv[i] = a.res ? ld4(r_res, mesh < a.b ? roff + 4 * DB_K * i : OOB) : make_float4(0.f, 0.f, 0.f, 0.f);
     };
     const float gamma = a.bn_w ? a.bn_w[v] : 1.f, beta = a.bn_b ? a.bn_b[v] : 0.f;
     const bool updates = a.training && tid == 0;
@@ -1065,7 +1012,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd 
             db_add_bias(z[t], bias4);
 #pragma unroll
             for (int i = 0; i < 3; ++i)
-                if (a.z_out) db_st4(r_z, db_own(own(t), i), z[t][i]);
+                if (a.z_out) st4(r_z, db_own(own(t), i), z[t][i]);
         }
     }
     // ---- 2. the weight slice for all tiles, and the first tile's residual, under the statistics
@@ -1076,7 +1023,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd 
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- 3. BatchNorm1d(verts): one statistic per vertex over its b * 192 values (two-pass: mean, then the centred second moment)
-    float *red = lds + DB_PANEL + DB_CST;
+    float *red = lds + RB_PANEL + RB_CST;
     const int n = a.b * DB_C;
     DbNorm bn;
     if (a.training) {
@@ -1104,8 +1051,8 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd 
     bn.gamma = gamma, bn.beta = beta;
 
     // ---- 4. the tiles' outputs and products
-    float *stage = lds + DB_PANEL;
-    const __amdgpu_buffer_rsrc_t r_s = db_rsrc(a.s_out, op_bytes);
+    float *stage = lds + RB_PANEL;
+    const __amdgpu_buffer_rsrc_t r_s = rsrc(a.s_out, op_bytes);
 #pragma unroll
     for (int t = 0; t < DBW_TILES; ++t) {
         if (t < tiles) {
@@ -1117,7 +1064,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd 
             float4 xo[3];
             db_norm_apply(a, bn, z[t], rv, mesh_on, xo);
 #pragma unroll
-            for (int i = 0; i < 3; ++i) db_st4(r_x, db_own(own(t), i), xo[i]);
+            for (int i = 0; i < 3; ++i) st4(r_x, db_own(own(t), i), xo[i]);
             if (!PRODUCT) {
                 // the coordinate head's product inside the last hidden layer's launch
                 if (a.w_head && a.s_head) {
@@ -1136,7 +1083,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd 
                 __syncthreads();
                 db_store_tile<false>(stage, r_s, [&](int r) {
                     const int mesh = 16 * t + r;
-                    return mesh < a.b ? ((unsigned)mesh * (unsigned)a.nv + (unsigned)v) * (DB_C * 4) : DB_OOB;
+                    return mesh < a.b ? ((unsigned)mesh * (unsigned)a.nv + (unsigned)v) * (DB_C * 4) : OOB;
                 });
                 __syncthreads(); // (the staging tile is free for the next tile's product)
             }
@@ -1147,7 +1094,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd 
 template <bool PRODUCT>
 __global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd a)
 {
-    __shared__ __attribute__((aligned(16))) float lds[DB_PANEL + DB_CST + DB_RED];
+    __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST + DB_RED];
     const int v = db_vertex(blockIdx.x, a.vpx, a.nv);
     if (v < 0) return;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1157,18 +1104,18 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd 
     const int tiles = (a.b + 15) >> 4;
     const int64_t op_bytes = (int64_t)a.b * a.nv * DB_C * 4;
     const int g_ld = a.g_ld ? a.g_ld : DB_C, g2_ld = a.g2_ld ? a.g2_ld : DB_C;
-    const __amdgpu_buffer_rsrc_t r_z = db_rsrc(a.z, op_bytes);
-    const __amdgpu_buffer_rsrc_t r_g2 = db_rsrc(a.g2, ((int64_t)a.b * a.nv - 1) * g2_ld * 4 + DB_C * 4);
-    const __amdgpu_buffer_rsrc_t r_g = db_rsrc(a.g, ((int64_t)a.b * a.nv - 1) * g_ld * 4 + DB_C * 4);
-    const __amdgpu_buffer_rsrc_t r_gr = db_rsrc(a.grad_res, op_bytes), r_dz = db_rsrc(a.dz, op_bytes);
-    // byte offset of the thread's float4 i of tile t in a [b, nv, ld] operand (DB_OOB: a row at or beyond b)
+    const __amdgpu_buffer_rsrc_t r_z = rsrc(a.z, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_g2 = rsrc(a.g2, ((int64_t)a.b * a.nv - 1) * g2_ld * 4 + DB_C * 4);
+    const __amdgpu_buffer_rsrc_t r_g = rsrc(a.g, ((int64_t)a.b * a.nv - 1) * g_ld * 4 + DB_C * 4);
+    const __amdgpu_buffer_rsrc_t r_gr = rsrc(a.grad_res, op_bytes), r_dz = rsrc(a.dz, op_bytes);
+    // byte offset of the thread's float4 i of tile t in a [b, nv, ld] operand (OOB: a row at or beyond b)
     auto at = [&](int t, int i, int ld) {
         const int mesh = 16 * t + rl;
-        return mesh < a.b ? (((unsigned)mesh * (unsigned)a.nv + (unsigned)v) * (unsigned)ld + (unsigned)(c0 + DB_K * i)) * 4u : DB_OOB;
+        return mesh < a.b ? (((unsigned)mesh * (unsigned)a.nv + (unsigned)v) * (unsigned)ld + (unsigned)(c0 + DB_K * i)) * 4u : OOB;
     };
     const float mean = a.save_mean[v], invstd = a.save_invstd[v];
     const float gamma = a.bn_w ? a.bn_w[v] : 1.f, beta = a.bn_b ? a.bn_b[v] : 0.f;
-    float *stage = lds + DB_PANEL;
+    float *stage = lds + RB_PANEL;
     float4 go[DBW_TILES][3];
 #pragma unroll
     for (int t = 0; t < DBW_TILES; ++t)
@@ -1176,7 +1123,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd 
         for (int i = 0; i < 3; ++i) go[t][i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (PRODUCT) {
         // ---- 1. aggregation backward of the layer above, tile by tile: G = [A^T . dZ_up[:, :64] | dZ_up[:, 64:]]
-        const __amdgpu_buffer_rsrc_t r_src = db_rsrc(a.dz_up, op_bytes), r_ds = db_rsrc(a.ds_up, op_bytes);
+        const __amdgpu_buffer_rsrc_t r_src = rsrc(a.dz_up, op_bytes), r_ds = rsrc(a.ds_up, op_bytes);
         const DbTable tb = db_table(v, a.ell_col_t, a.ell_val_t, a.tail_col_t, a.tail_val_t, lane);
         DbSlice bw;
 #pragma unroll
@@ -1186,7 +1133,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd 
                 const unsigned rowbase = (unsigned)mesh * (unsigned)a.nv * (DB_C * 4);
                 go[t][0] = db_aggregate<false, false>(r_src, mesh < a.b, rowbase, v, c0, tb, &go[t][1], bw, nullptr, wave, lane);
 #pragma unroll
-                for (int i = 0; i < 3; ++i) db_st4(r_ds, at(t, i, DB_C), go[t][i]); // the layer above's weight gradient reads it
+                for (int i = 0; i < 3; ++i) st4(r_ds, at(t, i, DB_C), go[t][i]); // the layer above's weight gradient reads it
             }
         }
         // ---- 2. the slice of W_up^T, once for all tiles; 3. dX = G . W_up^T
@@ -1209,13 +1156,13 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd 
         for (int t = 0; t < DBW_TILES; ++t)
             if (t < tiles && a.g) {
 #pragma unroll
-                for (int i = 0; i < 3; ++i) go[t][i] = db_ld4(r_g, at(t, i, g_ld));
+                for (int i = 0; i < 3; ++i) go[t][i] = ld4(r_g, at(t, i, g_ld));
             }
         if (a.ds_head) {
             // ---- the coordinate head inside the first backward launch (db_head_bwd_*): its input gradient joins g; the vertex's
             // partial of its weight gradient: per thread over its tiles in tile order, then the wave's rows, then the waves
-            const __amdgpu_buffer_rsrc_t r_xt = db_rsrc(a.x_top, op_bytes);
-            float *wsum = lds + DB_PANEL; // [4 waves][192 * 3]
+            const __amdgpu_buffer_rsrc_t r_xt = rsrc(a.x_top, op_bytes);
+            float *wsum = lds + RB_PANEL; // [4 waves][192 * 3]
             float part[3][4][3];
 #pragma unroll
             for (int i = 0; i < 3; ++i)
@@ -1234,7 +1181,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd 
                     }
 #pragma unroll
                     for (int i = 0; i < 3; ++i) {
-                        const float4 xt = a.dw_head ? db_ld4(r_xt, at(t, i, DB_C)) : make_float4(0.f, 0.f, 0.f, 0.f);
+                        const float4 xt = a.dw_head ? ld4(r_xt, at(t, i, DB_C)) : make_float4(0.f, 0.f, 0.f, 0.f);
                         const float xv[4] = {xt.x, xt.y, xt.z, xt.w};
                         float add[4];
 #pragma unroll
@@ -1269,13 +1216,13 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd 
             const bool mesh_on = 16 * t + rl < a.b;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                const float4 zv = db_ld4(r_z, at(t, i, DB_C));
-                const float4 s = a.g2 ? db_ld4(r_g2, at(t, i, g2_ld)) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 zv = ld4(r_z, at(t, i, DB_C));
+                const float4 s = a.g2 ? ld4(r_g2, at(t, i, g2_ld)) : make_float4(0.f, 0.f, 0.f, 0.f);
                 db_bn_bwd_elems(a, mean, invstd, gamma, beta, mesh_on, zv, go[t][i], s, xh[t][i], sum_g, sum_gx, r_gr, at(t, i, DB_C));
             }
         }
     }
-    float *red = lds + DB_PANEL + DB_CST;
+    float *red = lds + RB_PANEL + RB_CST;
     db_sum2(sum_g, sum_gx, red);
     db_publish_bn_grads(a, v, sum_g, sum_gx);
     // ---- 5. dZ, and the vertex's column sums of dZ over its meshes (per thread over its tiles, the wave's rows, the waves)
@@ -1291,7 +1238,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_bwd_kernel(geom_deform_bwd 
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 const float4 dz = db_bn_bwd_dz4(kk, go[t][i], xh[t][i], mg, mgx, mesh_on);
-                db_st4(r_dz, at(t, i, DB_C), dz);
+                st4(r_dz, at(t, i, DB_C), dz);
                 cs[i].x += dz.x, cs[i].y += dz.y, cs[i].z += dz.z, cs[i].w += dz.w;
             }
         }

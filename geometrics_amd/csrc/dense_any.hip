@@ -6,37 +6,32 @@
 // weight gradients (18 432 summed rows against a 300 x 300 output) run as ~100 workgroups without a K split, 73-97 us each
 // -- 1.25 of the 3.2 ms of an encoder step (tools/probe/encoder_profile.sh).
 //
-// One kernel, three operand forms.  A panel of an operand whose SUMMED index is contiguous in memory ("k-contiguous": the
-// rows of X in X . W, the rows of G and of W in G . W^T) is kept in LDS as [row][36] and a lane reads FOUR consecutive k of
-// its row with one ds_read_b128; a panel whose summed index is the slow one ("k-major": W in X . W, both operands of
-// X^T . G) is kept as [k][68] and read one float per MFMA.  The MFMA k-steps of a 32-deep stage are permuted so that both
-// forms agree: step s = 4 q + j gives lane group g the summed index 16 q + 4 g + j.  Bank arithmetic: [row][36] -- the 8
-// lanes a b128 read serves per cycle sit 36 floats apart = 4 banks: 32 distinct banks; [k][68] -- lane groups g, g + 1 sit
-// 4 * 68 floats = 16 banks apart, 16 lanes each: 32 distinct banks.
+// One kernel, three operand forms over the staged 64 x 64 tile of mfma_tiles.h (its panels, k permutation and bank arithmetic
+// are stated there): a panel of an operand whose SUMMED index is contiguous in memory ("k-contiguous": the rows of X in
+// X . W, the rows of G and of W in G . W^T) is kept in LDS as [row][36], a panel whose summed index is the slow one
+// ("k-major": W in X . W, both operands of X^T . G) as [k][68].
 // Workgroup = 64 x 64 output tile, four waves 2 x 2, a wave 32 x 32 = 2 x 2 MFMA tiles; global -> registers -> LDS, double
 // buffered, one barrier per stage; loads are buffer loads whose out-of-range lanes get an offset beyond the resource (zero
 // fill, no branches) and whose vector width follows the divisibility of the contiguous extent (16 / 8 / 4 bytes: 963- and
-// 3-float rows take the narrow ones).  The accumulators are taken with the operands swapped (D^T = B^T A^T) so that a lane
-// holds four consecutive COLUMNS of one row.  A long sum against few tiles (the weight gradients) is split over the summed
+// 3-float rows take the narrow ones).  A long sum against few tiles (the weight gradients) is split over the summed
 // index into `splits` partial tiles in a caller-provided workspace, added up in split order by a second launch:
 // bit-reproducible.  Small tiles on purpose: the shapes are ragged (N = 300 is 4.7 tiles), and 5 x 288 = 1440 workgroups
 // balance over the chip where 3 x 144 do not.
-#include "geom_common.h"
+#include "mfma_tiles.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+using namespace geom;
 
 constexpr int GA_THREADS = 256;
-constexpr int GA_T = 64;   // tile edge of the base tile (rows and columns); the tall tile is 128 x 64
+constexpr int GA_T = TILE_N; // tile edge of the base tile (rows and columns); the tall tile is 128 x 64
 constexpr int GA_BK = 32;  // granularity of the split chunks (a multiple of both stage depths)
-constexpr int ga_pk(int bk) { return bk + 4; }     // [row][k] panel pitch (36 / 20 floats: 8 lanes x 4 banks apart)
-constexpr int ga_pm(int rows) { return rows + 4; } // [k][row] panel pitch (68 / 132: 4 mod 8 -- see the bank arithmetic above)
-constexpr unsigned GA_OOB = 0x80000000u;
-constexpr int ga_panel(int rows, int bk) { return rows * ga_pk(bk) > bk * ga_pm(rows) ? rows * ga_pk(bk) : bk * ga_pm(rows); } // floats per buffer
+#ifdef GA_PROBE_NO_FRAG // tools/probe: the fragments of the first quarter-stage feed every MFMA
+constexpr int GA_PROBE = TILE_PROBE_NO_FRAG;
+#else
+constexpr int GA_PROBE = TILE_PROBE_NONE;
+#endif
 
 struct AnyArgs {
     const float *a, *b;
@@ -49,18 +44,13 @@ struct AnyArgs {
     int64_t a_bytes, b_bytes, c_bytes;
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ga_rsrc(const void *p, int64_t bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-
 // One operand's ROWS x 32 panel of a stage: V floats per load, PASSES loads per thread.
 // KM = false: the source is [x][k] (k contiguous), LDS [x][36];  KM = true: the source is [k][x] (x contiguous), LDS [k][ROWS + 4].
 template <bool KM, int V, int ROWS, int BK>
 struct Panel {
     static constexpr int PASSES = ROWS * BK / V / GA_THREADS;
     static_assert(PASSES >= 1, "a stage must give every thread a load");
-    unsigned off[PASSES];   // byte offset of the load at stage 0 (GA_OOB: the row / column is outside the operand)
+    unsigned off[PASSES];   // byte offset of the load at stage 0 (OOB: the row / column is outside the operand)
     unsigned lds[PASSES];   // float offset inside a panel buffer
     int kl[PASSES];         // the load's first summed index inside a stage
     unsigned step;          // bytes per stage
@@ -76,16 +66,16 @@ struct Panel {
             if (KM) {
                 constexpr int PER = ROWS / V; // loads per k row
                 k = idx / PER, x = (idx % PER) * V;
-                lds[p] = (unsigned)(k * ga_pm(ROWS) + x);
+                lds[p] = (unsigned)(k * tile_pm(ROWS) + x);
             } else {
                 constexpr int PER = BK / V; // loads per x row
                 x = idx / PER, k = (idx % PER) * V;
-                lds[p] = (unsigned)(x * ga_pk(BK) + k);
+                lds[p] = (unsigned)(x * tile_pk(BK) + k);
             }
             kl[p] = k;
             const bool in = x0 + x < X; // (X % V == 0 for the k-major form: a vector is inside or outside as a whole)
             const int64_t e = KM ? (int64_t)(k_begin + k) * ld + x0 + x : (int64_t)(x0 + x) * ld + k_begin + k;
-            off[p] = in ? (unsigned)(e * 4) : GA_OOB;
+            off[p] = in ? (unsigned)(e * 4) : OOB;
         }
         step = (unsigned)((KM ? (int64_t)BK * ld : (int64_t)BK) * 4);
     }
@@ -99,7 +89,7 @@ struct Panel {
 #ifdef GA_PROBE_NO_GLOBAL // tools/probe: no operand loads (the registers keep whatever they hold)
             if (stage > 1) continue;
 #endif
-            const unsigned o = (kl[p] < k_left && off[p] != GA_OOB) ? off[p] + (unsigned)stage * step : GA_OOB;
+            const unsigned o = (kl[p] < k_left && off[p] != OOB) ? off[p] + (unsigned)stage * step : OOB;
             if constexpr (V == 4) {
                 const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(r, o, 0, 0);
                 v[SET][p][0] = t.x, v[SET][p][1] = t.y, v[SET][p][2] = t.z, v[SET][p][3] = t.w;
@@ -130,9 +120,8 @@ struct Panel {
 template <bool A_KM, bool B_KN, int VA, int VB, int VC, int WM, int BK>
 __global__ __launch_bounds__(GA_THREADS) void any_gemm_kernel(AnyArgs q)
 {
-    constexpr int TM = 32 * WM, TN = GA_T, PK = ga_pk(BK);
-    constexpr int PA_F = ga_panel(TM, BK), PB_F = ga_panel(TN, BK);
-    constexpr int PMA = ga_pm(TM), PMB = ga_pm(TN);
+    constexpr int TM = 32 * WM, TN = GA_T;
+    constexpr int PA_F = tile_panel(TM, BK), PB_F = tile_panel(TN, BK);
     __shared__ __attribute__((aligned(16))) float lds[2 * PA_F + 2 * PB_F];
     // block -> (tile row, split) on "its" XCD, tile column fastest: the workgroups that share an A panel run next to each
     // other on one XCD's L2
@@ -146,8 +135,7 @@ __global__ __launch_bounds__(GA_THREADS) void any_gemm_kernel(AnyArgs q)
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x = lane & 15, g = lane >> 4;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int wr = 16 * WM * wm, wc = 32 * wn; // the wave's first row / column inside the tile
+    const int wr = tile_wave_row<WM>(wave), wc = tile_wave_col(wave);
 
     f32x4 acc[WM][2];
 #pragma unroll
@@ -155,7 +143,7 @@ __global__ __launch_bounds__(GA_THREADS) void any_gemm_kernel(AnyArgs q)
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    const __amdgpu_buffer_rsrc_t ra = ga_rsrc(q.a, q.a_bytes), rb = ga_rsrc(q.b, q.b_bytes);
+    const __amdgpu_buffer_rsrc_t ra = rsrc(q.a, q.a_bytes), rb = rsrc(q.b, q.b_bytes);
     Panel<A_KM, VA, TM, BK> pa;
     Panel<B_KN, VB, TN, BK> pb;
     pa.prepare(m0, q.M, q.lda, k_begin);
@@ -165,44 +153,7 @@ __global__ __launch_bounds__(GA_THREADS) void any_gemm_kernel(AnyArgs q)
     // Loads run TWO stages ahead of the MFMAs that consume them (two register sets, two LDS buffers): one stage of MFMAs is
     // 0.4 us, a round trip to L2 / HBM under load more -- with one stage of lead every stage ended waiting for its successor.
     const int k_len = k_end - k_begin;
-    auto compute = [&](const float *as, const float *bs) {
-#pragma unroll
-        for (int qq = 0; qq < BK / 16; ++qq) {
-            f32x4 a4[WM], b4[2];
-#ifdef GA_PROBE_NO_FRAG // tools/probe: the fragments of the first quarter-stage feed every MFMA (no further LDS reads)
-            if (qq > 0) {
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int i = 0; i < WM; ++i)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(acc[i][j ^ 1][0], acc[i ^ 1][j][1], acc[i][j], 0, 0, 0);
-                continue;
-            }
-#endif
-            if constexpr (!A_KM) {
-#pragma unroll
-                for (int i = 0; i < WM; ++i) a4[i] = *reinterpret_cast<const f32x4 *>(as + (wr + 16 * i + x) * PK + 16 * qq + 4 * g);
-            }
-            if constexpr (!B_KN) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j) b4[j] = *reinterpret_cast<const f32x4 *>(bs + (wc + 16 * j + x) * PK + 16 * qq + 4 * g);
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                float af[WM], bf[2];
-                const int kk = 16 * qq + 4 * g + s;
-#pragma unroll
-                for (int i = 0; i < WM; ++i) af[i] = A_KM ? as[kk * PMA + wr + 16 * i + x] : a4[i][s];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) bf[j] = B_KN ? bs[kk * PMB + wc + 16 * j + x] : b4[j][s];
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf[j], af[i], acc[i][j], 0, 0, 0);
-            }
-        }
-    };
+    auto compute = [&](const float *as, const float *bs) { tile_stage<A_KM, B_KN, WM, BK, GA_PROBE>(as, bs, wr, wc, x, g, acc); };
     if (nst > 0) {
         pa.template issue<0>(ra, 0, k_len);
         pb.template issue<0>(rb, 0, k_len);
@@ -241,27 +192,20 @@ __global__ __launch_bounds__(GA_THREADS) void any_gemm_kernel(AnyArgs q)
         }
     }
 
-    // lane (x, g) holds C[m0 + wr + 16 i + x][n0 + wc + 16 j + 4 g .. + 3]
     float *cbase = q.c + (int64_t)split * q.split_stride;
-    const __amdgpu_buffer_rsrc_t rc = ga_rsrc(cbase, q.c_bytes);
+    const __amdgpu_buffer_rsrc_t rc = rsrc(cbase, q.c_bytes);
+    // (captures by value: the bounds are then plain values and the two tests stay one select per store, no branch)
+    tile_for_each_output<WM>(acc, m0 + wr, n0 + wc, x, g, [=](int m, int n, f32x4 v) {
+        const unsigned o = (unsigned)(((int64_t)m * q.ldc + n) * 4);
+        if constexpr (VC == 4) {
+            __builtin_amdgcn_raw_buffer_store_b128((u32x4){__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])},
+                                                   rc, (m < q.M && n < q.N) ? o : OOB, 0, 0);
+        } else {
 #pragma unroll
-    for (int i = 0; i < WM; ++i) {
-        const int m = m0 + wr + 16 * i + x;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int n = n0 + wc + 16 * j + 4 * g;
-            const f32x4 v = acc[i][j];
-            const unsigned o = (unsigned)(((int64_t)m * q.ldc + n) * 4);
-            if constexpr (VC == 4) {
-                __builtin_amdgcn_raw_buffer_store_b128((u32x4){__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])},
-                                                       rc, (m < q.M && n < q.N) ? o : GA_OOB, 0, 0);
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r]), rc, (m < q.M && n + r < q.N) ? o + 4u * r : GA_OOB, 0, 0);
-            }
+            for (int r = 0; r < 4; ++r)
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r]), rc, (m < q.M && n + r < q.N) ? o + 4u * r : OOB, 0, 0);
         }
-    }
+    });
 }
 
 // out[m][n] = sum over the splits of part[s][m][n] (part rows are N floats long), in a FIXED order: lane l of the L lanes that

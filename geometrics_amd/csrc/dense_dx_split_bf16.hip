@@ -24,14 +24,12 @@
 // Probe builds (tools/probe/dx_variants.sh; never the product): -DDX_PROBE_NO_STORE, -DDX_PROBE_NO_LDS, -DDX_PROBE_NO_REFILL,
 // -DDX_PROBE_NO_PROLOGUE take one stream out of the launch each (results are then wrong; the MFMAs stay: the stores hang on a
 // condition the compiler cannot see through).
-#include "geom_common.h"
+#include "buffer_access.h"
 #include <type_traits>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace geom;
 
 constexpr int DX_THREADS = 256;
 constexpr int DX_K = 192;                       // the summed index (the layer width)
@@ -90,15 +88,8 @@ __global__ __launch_bounds__(256) void dx_planes_kernel(int cin, int cinpad, con
 }
 
 // Every global access of the product is a buffer access against one of three descriptors (g, the planes, dx; each below
-// 2 GiB, the host checks): an access that must not happen -- a row beyond the matrix, a column beyond cin, the group after the
-// last -- gets the offset DX_NOWHERE, which the hardware drops (a load returns zeros), instead of a branch around it.  Besides
-// the branches this keeps the memory counter countable: every load and store is issued on every path, so a wait for a B
-// fragment is `all but the N youngest` with N known, and never drains the stores issued since.
-constexpr unsigned DX_NOWHERE = 0x80000000u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t dx_rsrc(const void *ptr, int64_t bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(ptr), 0, (int)bytes, 0x00020000);
-}
+// 2 GiB, the host checks); an access that must not happen gets the offset OOB (buffer_access.h), so every load and store is
+// issued on every path and the waits below can count them.
 
 struct DxArgs {
     const float *g;              // [rows][192] fp32, 16-byte aligned
@@ -140,7 +131,7 @@ __device__ __forceinline__ void dx_store(const DxArgs &p, __amdgpu_buffer_rsrc_t
     for (int e = 0; e < 4; ++e)
 #pragma unroll
         for (int t = 0; t < DX_NT; ++t) {
-            const unsigned off = row + e < p.rows && col + 16 * t < p.cin ? (unsigned)(((row + e) * p.ldx + col + 16 * t) * 4) : DX_NOWHERE;
+            const unsigned off = row + e < p.rows && col + 16 * t < p.cin ? (unsigned)(((row + e) * p.ldx + col + 16 * t) * 4) : OOB;
 #ifdef DX_PROBE_NO_STORE
             if (p.ldx < 0)
 #endif
@@ -157,8 +148,8 @@ __device__ __forceinline__ void dx_sweep(const DxArgs &p, const unsigned char *l
     const int ngroups = p.cinpad / (16 * DX_NT);
     bf16x8 bf[2][DX_KB][DX_NT][3];
     bf16x8 af[2][3];
-    const __amdgpu_buffer_rsrc_t r_w = dx_rsrc(p.wp, (int64_t)3 * p.cinpad * DX_K * 2);
-    const __amdgpu_buffer_rsrc_t r_dx = dx_rsrc(p.dx, ((int64_t)(p.rows - 1) * p.ldx + p.cin) * 4);
+    const __amdgpu_buffer_rsrc_t r_w = rsrc(p.wp, (int64_t)3 * p.cinpad * DX_K * 2);
+    const __amdgpu_buffer_rsrc_t r_dx = rsrc(p.dx, ((int64_t)(p.rows - 1) * p.ldx + p.cin) * 4);
     // A fragments of (row-block, k-block): lane (lr, lg) holds g_plane[row 16 rbi + lr][k = 32 kb + 8 lg .. + 7].  Two register sets
     // in turn: the fragments of the next k-block (after the last one: of the next row-block's first) are requested in front of
     // this k-block's MFMAs -- one wave per SIMD has nobody else to cover an LDS read
@@ -168,7 +159,7 @@ __device__ __forceinline__ void dx_sweep(const DxArgs &p, const unsigned char *l
             af[set][pl] = *reinterpret_cast<const bf16x8 *>(lds + pl * DX_PLANE + lds_chunk(rbi * 16 + lr, 4 * kb + lg));
     };
     auto b_frags = [&](int set, int grp, int kb) {      // (a group beyond the last: nothing is fetched)
-        const unsigned base = grp < ngroups ? (unsigned)(dx_frag_index(grp, 0, 0, 0, lane) * 16) : DX_NOWHERE;
+        const unsigned base = grp < ngroups ? (unsigned)(dx_frag_index(grp, 0, 0, 0, lane) * 16) : OOB;
 #pragma unroll
         for (int t = 0; t < DX_NT; ++t)
 #pragma unroll
@@ -221,8 +212,8 @@ __device__ __forceinline__ void dx_sweep(const DxArgs &p, const unsigned char *l
 __device__ __forceinline__ void dx_stray(const DxArgs &p, const unsigned char *lds, int lane, int lds_rb, int rb, int grp)
 {
     const int lr = lane & 15, lg = lane >> 4;
-    const __amdgpu_buffer_rsrc_t r_w = dx_rsrc(p.wp, (int64_t)3 * p.cinpad * DX_K * 2);
-    const __amdgpu_buffer_rsrc_t r_dx = dx_rsrc(p.dx, ((int64_t)(p.rows - 1) * p.ldx + p.cin) * 4);
+    const __amdgpu_buffer_rsrc_t r_w = rsrc(p.wp, (int64_t)3 * p.cinpad * DX_K * 2);
+    const __amdgpu_buffer_rsrc_t r_dx = rsrc(p.dx, ((int64_t)(p.rows - 1) * p.ldx + p.cin) * 4);
     bf16x8 b[DX_KB][DX_NT][3];
 #pragma unroll
     for (int kb = 0; kb < DX_KB; ++kb)
@@ -263,13 +254,13 @@ __global__ __launch_bounds__(DX_THREADS, 1) void dx_split_kernel(DxArgs p)
     // first (one HBM round trip for the tile, not one per piece), then the split
 #ifndef DX_PROBE_NO_PROLOGUE
     {
-        const __amdgpu_buffer_rsrc_t r_g = dx_rsrc(p.g, (int64_t)p.rows * DX_K * 4);
+        const __amdgpu_buffer_rsrc_t r_g = rsrc(p.g, (int64_t)p.rows * DX_K * 4);
         u32x4 v[3 * DX_MAX_RB];
 #pragma unroll
         for (int i = 0; i < 3 * DX_MAX_RB; ++i) {      // piece q = tid + 256 i: row q / 48 of the tile, floats 4 (q % 48) ..
             const int q = tid + DX_THREADS * i, r = q / (DX_K / 4);
             const int row = r < 16 * n ? rb0 * 16 + r : stray_rb * 16 + r - 16 * n;      // (the stray block: LDS row-block n)
-            const unsigned off = r < 16 * n || (stray_rb >= 0 && r < 16 * n + 16) ? (unsigned)((row * DX_K + 4 * (q - r * (DX_K / 4))) * 4) : DX_NOWHERE;
+            const unsigned off = r < 16 * n || (stray_rb >= 0 && r < 16 * n + 16) ? (unsigned)((row * DX_K + 4 * (q - r * (DX_K / 4))) * 4) : OOB;
             v[i] = __builtin_amdgcn_raw_buffer_load_b128(r_g, off, 0, 0);
         }
 #pragma unroll

@@ -26,13 +26,14 @@
 //     conflict-free for the fragment reads (bank = 2*row + t resp. 16*g + x);
 //   * a weight gradient (inner dimension = all rows) is split over the rows so that all CUs work; partial tiles go to a
 //     workspace and are added up in slot order by a reduction kernel -- a fixed order, so results are bit-reproducible.
-#include "geom_common.h"
+#include "buffer_access.h"
 #include "adam_math.h"
 #include <type_traits>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using geom::f32x4;
+using geom::f3u;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct __attribute__((packed, aligned(4))) f4u { float x, y, z, w; }; // 16 bytes at 4-byte alignment (963-float rows)
 
@@ -77,7 +78,6 @@ __device__ __forceinline__ f32x4 ldg4(const float *base, unsigned byte_off)
     const f4u v = *reinterpret_cast<const f4u *>(reinterpret_cast<const char *>(base) + byte_off);
     return (f32x4){v.x, v.y, v.z, v.w};
 }
-struct __attribute__((packed, aligned(4))) f3u { float x, y, z; };
 __device__ __forceinline__ f3u ldg3(const float *base, unsigned byte_off)
 {
     return *reinterpret_cast<const f3u *>(reinterpret_cast<const char *>(base) + byte_off);

@@ -18,13 +18,11 @@
 // geom_split_bf16_planes_f32, once per weight update) so that a lane's 8 consecutive k are one 16-byte read; LDS rows are
 // padded to 80 bytes (16 rows x 16 B cover all 64 banks); double-buffered, the next block's global loads travel under the
 // current block's 108 MFMAs per wave.
-#include "geom_common.h"
+#include "buffer_access.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace geom;
 
 constexpr int SB_THREADS = 256;
 constexpr int SB_N = 192;          // output columns (the layer width)
@@ -42,7 +40,8 @@ __device__ __forceinline__ unsigned bf16_bits(float x) // round to nearest even 
 }
 __device__ __forceinline__ float bf16_value(unsigned bits) { return __uint_as_float(bits << 16); }
 
-// a -> (a0, a1, a2) as bf16 bit patterns, a0 + a1 + a2 == a exactly
+// a -> (a0, a1, a2) as bf16 bit patterns, a0 + a1 + a2 == a exactly (integer rounding: what a NaN becomes differs on purpose
+// from dense_dx_split_bf16.hip's split3 -- see the comment there)
 __device__ __forceinline__ void split3(float a, unsigned &b0, unsigned &b1, unsigned &b2)
 {
     b0 = bf16_bits(a);
@@ -86,13 +85,13 @@ __global__ __launch_bounds__(SB_THREADS, 1) void split_bf16_gemm_kernel(SbArgs p
     // X: thread (r = tid / 8, k4 = tid % 8) owns k = 4 k4 .. 4 k4 + 3 of rows r, r + 32, r + 64: three 16-byte loads (a
     // multi-dword buffer load needs dword alignment only: the 963-float rows are 4-byte aligned), eight lanes per 128-byte row piece
     const int ar = tid >> 3, ak4 = tid & 7;
-    const __amdgpu_buffer_rsrc_t r_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.a), 0, (int)((int64_t)p.m * p.k * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(p.bt), 0, (int)((int64_t)3 * SB_N * p.kpad * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_a = rsrc(p.a, (int64_t)p.m * p.k * 4);
+    const __amdgpu_buffer_rsrc_t r_b = rsrc(p.bt, (int64_t)3 * SB_N * p.kpad * 2);
     unsigned a_off[3], b_off[9], b_lds[9];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const int row = row0 + ar + 32 * i;
-        a_off[i] = row < p.m ? (unsigned)(((int64_t)row * p.k + 4 * ak4) * 4) : 0x80000000u;
+        a_off[i] = row < p.m ? (unsigned)(((int64_t)row * p.k + 4 * ak4) * 4) : OOB;
     }
     // W planes: 3 x 192 x 64 B per block = 2 304 chunks of 16 B, nine per thread: chunk q = tid + 256 t -> (plane, column, piece)
 #pragma unroll

@@ -13,28 +13,22 @@
 // k = 0, no bias and act = NONE make T the identity (the first product positions . W_h1, K = 3); act = NONE with k > 0 is the
 // adjoint tail of the head (no activation in front of its max).  The gather adds val * x in CSR order, un-fused, starting from
 // 0.f: T equals geom_zn_gcn_aggregate_fwd_f32 / _bwd_f32 on the same input bit for bit (an optional pointer receives it, written
-// by the workgroups of the first column tile).  The product is exact fp32 on v_mfma_f32_16x16x4_f32 with dense_any.hip's panels:
-// the operand whose summed index is contiguous as [row][36] (a lane reads four consecutive k with one ds_read_b128), W in the
-// forward as [k][68]; MFMA step s = 4 q + j gives lane group g the summed index 16 q + 4 g + j in both forms; operands swapped
-// so that a lane holds four consecutive columns of one row.  Workgroup = 64 x 64 tile, four waves 2 x 2; every global access is a
+// by the workgroups of the first column tile).  The product is exact fp32 on v_mfma_f32_16x16x4_f32: the staged 64 x 64 tile of
+// mfma_tiles.h with 32-deep stages -- the operand as [row][36], W as [k][68] in the forward and [row][36] in the backward (its
+// panels, k permutation and lane map are stated there; dense_any.hip runs the same tile).  Workgroup = 64 x 64 tile, four waves 2 x 2; every global access is a
 // bounds-checked 4-byte one (any M, N, K, pitch and alignment: 12-byte position rows, widths that are 2 mod 4), a wave reading
 // 128-byte runs; the next stage's raw loads are in flight during a stage's MFMAs and are transformed when they are stored to the
 // other LDS buffer: one barrier per stage.  A launch reads only what earlier launches wrote: no counters, no waiting.
-#include "geom_common.h"
+#include "mfma_tiles.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace geom;
 
 constexpr int ES_THREADS = 256;
-constexpr int ES_T = 64;        // tile edge (rows and columns)
+constexpr int ES_T = TILE_N;    // tile edge (rows and columns)
 constexpr int ES_BK = 32;       // stage depth: the aggregated columns (k <= 32) all lie in stage 0
-constexpr int ES_PK = ES_BK + 4; // [row][k] panel pitch: the 8 lanes of a b128 read sit 4 banks apart
-constexpr int ES_PM = ES_T + 4;  // [k][col] panel pitch: lane groups sit 16 banks apart
-constexpr int ES_PANEL = ES_T * ES_PK > ES_BK * ES_PM ? ES_T * ES_PK : ES_BK * ES_PM;
 constexpr int ES_PASSES = ES_T * ES_BK / ES_THREADS; // elements of a panel per thread
-
-enum { ES_ACT_NONE = 0, ES_ACT_RELU = 1, ES_ACT_ELU = 2 };
 
 struct EncArgs {
     const int *rowptr, *col; // CSR (forward) / CSR^T (backward) of the adjacency the batch shares; unused when kagg == 0
@@ -49,30 +43,13 @@ struct EncArgs {
     int M, N, K, nv, kagg, tiles_n;
 };
 
-// the two activation helpers of zn_gcn.hip (same expressions: the transformed operand is compared bit for bit)
-template <int ACT>
-__device__ __forceinline__ float es_act_fwd(float v)
-{
-    if (ACT == ES_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (ACT == ES_ACT_ELU) return v > 0.f ? v : expm1f(v);
-    return v;
-}
-
-template <int ACT>
-__device__ __forceinline__ float es_act_bwd(float g, float out)
-{
-    if (ACT == ES_ACT_RELU) return out > 0.f ? g : 0.f;
-    if (ACT == ES_ACT_ELU) return out > 0.f ? g : g * (out + 1.f);
-    return g;
-}
-
 // what the epilogue of T does to a gathered / passed-through value
 template <bool BWD, int ACT>
 __device__ __forceinline__ float es_finish(float v, bool has_bias, float bias)
 {
     if (BWD) return v;
     if (has_bias) v += bias; // (no bias: no addition -- a -0.f stays what it is, as in zn_gcn.hip)
-    return es_act_fwd<ACT>(v);
+    return act_fwd<ACT>(v);
 }
 
 // element (row, cc) of the operand in front of the gather: S, or g * act'(X)
@@ -80,15 +57,16 @@ template <bool BWD, int ACT>
 __device__ __forceinline__ float es_source(const EncArgs &q, int64_t row, int cc)
 {
     float v = q.a[row * q.lda + cc];
-    if (BWD && ACT != ES_ACT_NONE) v = es_act_bwd<ACT>(v, q.saved[row * q.ldsaved + cc]);
+    if (BWD && ACT != ACT_NONE) v = act_bwd<ACT>(v, q.saved[row * q.ldsaved + cc]);
     return v;
 }
 
 template <bool BWD, int ACT>
 __global__ __launch_bounds__(ES_THREADS) void encoder_layer_kernel(EncArgs q)
 {
-    __shared__ __attribute__((aligned(16))) float lds[4 * ES_PANEL];
-    float *const la = lds, *const lb = lds + 2 * ES_PANEL;
+    constexpr int PK = tile_pk(ES_BK), PM = tile_pm(ES_T), PANEL = tile_panel(ES_T, ES_BK); // the panels of mfma_tiles.h
+    __shared__ __attribute__((aligned(16))) float lds[4 * PANEL];
+    float *const la = lds, *const lb = lds + 2 * PANEL;
     const int tid = threadIdx.x;
     const int nt = blockIdx.x % q.tiles_n, mt = blockIdx.x / q.tiles_n;
     const int m0 = mt * ES_T, n0 = nt * ES_T;
@@ -97,7 +75,7 @@ __global__ __launch_bounds__(ES_THREADS) void encoder_layer_kernel(EncArgs q)
 
     const int lane = tid & 63, wave = tid >> 6;
     const int x = lane & 15, g = lane >> 4;
-    const int wr = 32 * (wave >> 1), wc = 32 * (wave & 1); // the wave's first row / column inside the tile
+    const int wr = tile_wave_row<2>(wave), wc = tile_wave_col(wave);
 
     // operand panel: thread -> column kk of the stage, rows r0 + 8 p (a wave reads two 128-byte runs per pass)
     const int a_kk = tid & 31, a_r0 = tid >> 5;
@@ -116,7 +94,7 @@ __global__ __launch_bounds__(ES_THREADS) void encoder_layer_kernel(EncArgs q)
             const int64_t row = m0 + a_r0 + 8 * p;
             const bool in = kin && row < q.M;
             ra[p] = in ? q.a[row * q.lda + cc] : 0.f;
-            if (BWD && ACT != ES_ACT_NONE) rs[p] = in ? q.saved[row * q.ldsaved + cc] : 0.f;
+            if (BWD && ACT != ACT_NONE) rs[p] = in ? q.saved[row * q.ldsaved + cc] : 0.f;
         }
     };
     auto load_w = [&](int st) {
@@ -140,15 +118,15 @@ __global__ __launch_bounds__(ES_THREADS) void encoder_layer_kernel(EncArgs q)
             const int64_t row = m0 + r;
             const bool in = cc < q.K && row < q.M;
             float v = ra[p];
-            if (BWD && ACT != ES_ACT_NONE) v = es_act_bwd<ACT>(v, rs[p]);
+            if (BWD && ACT != ACT_NONE) v = act_bwd<ACT>(v, rs[p]);
             v = in ? es_finish<BWD, ACT>(v, q.bias != nullptr, rbias) : 0.f;
-            as[r * ES_PK + a_kk] = v;
+            as[r * PK + a_kk] = v;
             if (writes_t && in) q.t[row * q.ldt + cc] = v;
         }
 #pragma unroll
         for (int p = 0; p < ES_PASSES; ++p) {
-            if (!BWD) bs[(w_r0 + 4 * p) * ES_PM + w_n] = rw[p];
-            else bs[(a_r0 + 8 * p) * ES_PK + a_kk] = rw[p];
+            if (!BWD) bs[(w_r0 + 4 * p) * PM + w_n] = rw[p];
+            else bs[(a_r0 + 8 * p) * PK + a_kk] = rw[p];
         }
     };
 
@@ -158,29 +136,7 @@ __global__ __launch_bounds__(ES_THREADS) void encoder_layer_kernel(EncArgs q)
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    auto compute = [&](const float *as, const float *bs) {
-#pragma unroll
-        for (int qq = 0; qq < ES_BK / 16; ++qq) {
-            f32x4 a4[2], b4[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) a4[i] = *reinterpret_cast<const f32x4 *>(as + (wr + 16 * i + x) * ES_PK + 16 * qq + 4 * g);
-            if (BWD) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j) b4[j] = *reinterpret_cast<const f32x4 *>(bs + (wc + 16 * j + x) * ES_PK + 16 * qq + 4 * g);
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                float bf[2];
-                const int kk = 16 * qq + 4 * g + s;
-#pragma unroll
-                for (int j = 0; j < 2; ++j) bf[j] = BWD ? b4[j][s] : bs[kk * ES_PM + wc + 16 * j + x];
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf[j], a4[i][s], acc[i][j], 0, 0, 0);
-            }
-        }
-    };
+    auto compute = [&](const float *as, const float *bs) { tile_stage<false, !BWD, 2, ES_BK>(as, bs, wr, wc, x, g, acc); };
 
     if (nst > 0) {
         // ---- stage 0: the columns below kagg are gathered over the row's CSR entries, in CSR order, starting from 0.f
@@ -192,7 +148,7 @@ __global__ __launch_bounds__(ES_THREADS) void encoder_layer_kernel(EncArgs q)
         if (kin && cc < q.kagg) {
             // the thread's eight rows side by side, NB entries of each per round: a round is two round trips (entries, then the
             // neighbours' elements) whatever the rows' lengths; the sum of a row stays in CSR order (rounds, then slots, ascending)
-            constexpr int NB = (BWD && ACT != ES_ACT_NONE) ? 2 : 4;
+            constexpr int NB = (BWD && ACT != ACT_NONE) ? 2 : 4;
             int e0[ES_PASSES], e1[ES_PASSES], base[ES_PASSES];
             int longest = 0;
 #pragma unroll
@@ -224,7 +180,7 @@ __global__ __launch_bounds__(ES_THREADS) void encoder_layer_kernel(EncArgs q)
                         const bool live = cj[p][j] >= 0;
                         const int64_t nb = (int64_t)base[p] + (live ? cj[p][j] : 0);
                         sj[p][j] = live ? q.a[nb * q.lda + cc] : 0.f;
-                        oj[p][j] = (live && BWD && ACT != ES_ACT_NONE) ? q.saved[nb * q.ldsaved + cc] : 0.f;
+                        oj[p][j] = (live && BWD && ACT != ACT_NONE) ? q.saved[nb * q.ldsaved + cc] : 0.f;
                     }
 #pragma unroll
                 for (int p = 0; p < ES_PASSES; ++p)
@@ -232,7 +188,7 @@ __global__ __launch_bounds__(ES_THREADS) void encoder_layer_kernel(EncArgs q)
                     for (int j = 0; j < NB; ++j)
                         if (cj[p][j] >= 0) {
                             float sv = sj[p][j];
-                            if (BWD && ACT != ES_ACT_NONE) sv = es_act_bwd<ACT>(sv, oj[p][j]);
+                            if (BWD && ACT != ACT_NONE) sv = act_bwd<ACT>(sv, oj[p][j]);
                             v0[p] += wj[p][j] * sv;
                         }
             }
@@ -250,12 +206,12 @@ __global__ __launch_bounds__(ES_THREADS) void encoder_layer_kernel(EncArgs q)
             const bool in = kin && row < q.M;
             const float v = in ? es_finish<BWD, ACT>(v0[p], q.bias != nullptr, bias0) : 0.f;
             if (writes_t && in) q.t[row * q.ldt + cc] = v;
-            la[r * ES_PK + a_kk] = v;
+            la[r * PK + a_kk] = v;
         }
 #pragma unroll
         for (int p = 0; p < ES_PASSES; ++p) {
-            if (!BWD) lb[(w_r0 + 4 * p) * ES_PM + w_n] = rw[p];
-            else lb[(a_r0 + 8 * p) * ES_PK + a_kk] = rw[p];
+            if (!BWD) lb[(w_r0 + 4 * p) * PM + w_n] = rw[p];
+            else lb[(a_r0 + 8 * p) * PK + a_kk] = rw[p];
         }
         __syncthreads();
     }
@@ -265,41 +221,34 @@ __global__ __launch_bounds__(ES_THREADS) void encoder_layer_kernel(EncArgs q)
             load_raw(st + 1);
             load_w(st + 1);
         }
-        compute(la + cur * ES_PANEL, lb + cur * ES_PANEL);
-        if (st + 1 < nst) store_stage(st + 1, la + (cur ^ 1) * ES_PANEL, lb + (cur ^ 1) * ES_PANEL);
+        compute(la + cur * PANEL, lb + cur * PANEL);
+        if (st + 1 < nst) store_stage(st + 1, la + (cur ^ 1) * PANEL, lb + (cur ^ 1) * PANEL);
         __syncthreads();
     }
 
-    // lane (x, g) holds C[m0 + wr + 16 i + x][n0 + wc + 16 j + 4 g .. + 3]
+    tile_for_each_output<2>(acc, m0 + wr, n0 + wc, x, g, [&](int m, int n, const f32x4 &v) {
+        if (m < q.M) {
+            float *o = q.c + (int64_t)m * q.ldc + n;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int m = m0 + wr + 16 * i + x;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int n = n0 + wc + 16 * j + 4 * g;
-            if (m < q.M) {
-                float *o = q.c + (int64_t)m * q.ldc + n;
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (n + r < q.N) o[r] = acc[i][j][r];
-            }
+            for (int r = 0; r < 4; ++r)
+                if (n + r < q.N) o[r] = v[r];
         }
-    }
+    });
 }
 
 template <bool BWD>
 void encoder_launch(const EncArgs &q, int act, dim3 grid, hipStream_t s)
 {
-    if (act == ES_ACT_ELU) hipLaunchKernelGGL((encoder_layer_kernel<BWD, ES_ACT_ELU>), grid, dim3(ES_THREADS), 0, s, q);
-    else if (act == ES_ACT_RELU) hipLaunchKernelGGL((encoder_layer_kernel<BWD, ES_ACT_RELU>), grid, dim3(ES_THREADS), 0, s, q);
-    else hipLaunchKernelGGL((encoder_layer_kernel<BWD, ES_ACT_NONE>), grid, dim3(ES_THREADS), 0, s, q);
+    if (act == ACT_ELU) hipLaunchKernelGGL((encoder_layer_kernel<BWD, ACT_ELU>), grid, dim3(ES_THREADS), 0, s, q);
+    else if (act == ACT_RELU) hipLaunchKernelGGL((encoder_layer_kernel<BWD, ACT_RELU>), grid, dim3(ES_THREADS), 0, s, q);
+    else hipLaunchKernelGGL((encoder_layer_kernel<BWD, ACT_NONE>), grid, dim3(ES_THREADS), 0, s, q);
 }
 
 // the size checks shared by the two directions, in front of any pointer check
 int encoder_check(int b, int nv, int c, int k, int n, int act)
 {
     if (b < 0 || nv < 0 || c < 0 || k < 0 || n < 0 || k > c) return GEOM_EINVAL;
-    if (act < ES_ACT_NONE || act > ES_ACT_ELU) return GEOM_EINVAL;
+    if (act < ACT_NONE || act > ACT_ELU) return GEOM_EINVAL;
     if (k > ES_BK) return GEOM_EUNSUPPORTED; // the aggregated columns must lie inside the first k-stage
     if ((int64_t)b * nv > 0x7fffffffLL - ES_T) return GEOM_ETOOBIG;
     return 0;
@@ -403,7 +352,7 @@ extern "C" int geom_encoder_layer_bwd_f32(int b, int nv, int c, int k, int n, co
     if ((int64_t)b * nv == 0 || n == 0) return 0;
     if (!out || ldo < n) return GEOM_EINVAL;
     if (c > 0 && (!g || !w || ldg < c || ldw < c)) return GEOM_EINVAL;
-    if (c > 0 && act != ES_ACT_NONE && (!x_saved || ldx < c)) return GEOM_EINVAL;
+    if (c > 0 && act != ACT_NONE && (!x_saved || ldx < c)) return GEOM_EINVAL;
     if (k > 0 && (!rowptrT || !colT || !valT)) return GEOM_EINVAL;
     if (t_out && ldt < c) return GEOM_EINVAL;
     EncArgs q;

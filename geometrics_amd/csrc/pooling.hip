@@ -16,7 +16,7 @@
 //     a wave owns one texel x 64 channels and sums its list with coalesced reads (no float atomics).
 // The reference's interpolation quirk is kept: weights are (ceil - x, x - floor), so a coordinate that
 // is exactly integral (incl. clamped ones) gets all-zero weights (utils.py:346-350, 372-379).
-#include "geom_common.h"
+#include "buffer_access.h"
 
 namespace {
 
@@ -84,12 +84,10 @@ __device__ __forceinline__ Texel texel(float xs, float ys, int dim)
     return t;
 }
 
-typedef unsigned pl_u32x2 __attribute__((ext_vector_type(2)));
-
 // a mesh's planes of one map as a buffer (the pair reads are 4-byte aligned only: buffer loads take that)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const float *blk, int C, int texels)
 {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(blk), 0, (int)((size_t)C * texels * 4), 0x00020000);
+    return geom::rsrc(blk, (int64_t)C * texels * 4);
 }
 
 struct Quad {
@@ -101,8 +99,8 @@ __device__ __forceinline__ Quad quad_of(__amdgpu_buffer_rsrc_t r, const Texel &t
 {
     Quad q;
     const unsigned base = (unsigned)ch * (unsigned)texels;
-    const pl_u32x2 a = __builtin_amdgcn_raw_buffer_load_b64(r, (base + (unsigned)t.p1) * 4u, 0, 0);
-    const pl_u32x2 b = __builtin_amdgcn_raw_buffer_load_b64(r, (base + (unsigned)t.p2) * 4u, 0, 0);
+    const geom::u32x2 a = __builtin_amdgcn_raw_buffer_load_b64(r, (base + (unsigned)t.p1) * 4u, 0, 0);
+    const geom::u32x2 b = __builtin_amdgcn_raw_buffer_load_b64(r, (base + (unsigned)t.p2) * 4u, 0, 0);
     q.c11 = __uint_as_float(t.y1_hi ? a.y : a.x), q.c12 = __uint_as_float(t.y2_hi ? a.y : a.x);
     q.c21 = __uint_as_float(t.y1_hi ? b.y : b.x), q.c22 = __uint_as_float(t.y2_hi ? b.y : b.x);
     return q;
@@ -480,9 +478,6 @@ static void gather_plan(const PoolArgs &a, GatherPlan &p)
     p.first_task[a.levels] = task;
 }
 
-typedef unsigned pg_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned pg_u32x2 __attribute__((ext_vector_type(2)));
-
 template <int VEC> struct PgRow {
     float x[VEC];
 };
@@ -491,10 +486,10 @@ template <int VEC> __device__ __forceinline__ PgRow<VEC> pg_load(__amdgpu_buffer
 {
     PgRow<VEC> o;
     if constexpr (VEC == 4) {
-        const pg_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
+        const geom::u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
         o.x[0] = __uint_as_float(v.x), o.x[1] = __uint_as_float(v.y), o.x[2] = __uint_as_float(v.z), o.x[3] = __uint_as_float(v.w);
     } else if constexpr (VEC == 2) {
-        const pg_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0);
+        const geom::u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0);
         o.x[0] = __uint_as_float(v.x), o.x[1] = __uint_as_float(v.y);
     } else {
         o.x[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
@@ -524,9 +519,8 @@ __device__ __forceinline__ void pg_run(const PoolArgs &a, const BinSpace &ws, co
     const int n = E1 - E0;
     const int ea = E0 + ((n * wave) >> 2), ez = E0 + ((n * (wave + 1)) >> 2); // this wave's quarter of the entries
     const int c = part * W + lane * VEC;                                          // the lane's first channel
-    const __amdgpu_buffer_rsrc_t r_g = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(grad_out + (size_t)mesh * a.nv * a.ld), 0, (int)((((size_t)a.nv - 1) * a.ld + a.ctot) * 4), 0x00020000);
-    const unsigned col_off = c < C ? (unsigned)(p.col0[l] + c) * 4u : 0x80000000u; // (out of range: the load returns zeros)
+    const __amdgpu_buffer_rsrc_t r_g = geom::rsrc(grad_out + (size_t)mesh * a.nv * a.ld, (int64_t)((((size_t)a.nv - 1) * a.ld + a.ctot) * 4));
+    const unsigned col_off = c < C ? (unsigned)(p.col0[l] + c) * 4u : geom::OOB; // (out of range: the load returns zeros)
     // the texel the quarter starts in = the number of lists that end at or before its first entry
     const int t_first = __builtin_popcountll(__ballot(lane < nt && ends <= ea));
     int cur = t_first, next = __builtin_amdgcn_readlane(ends, min(cur, GEOM_WAVE - 1));

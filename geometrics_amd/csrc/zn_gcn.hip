@@ -13,13 +13,13 @@
 // 256 B - 1 KiB runs; neighbour rows of the k-slice are re-read through L2 (the slice is
 // b*V*k*4 bytes, 5.2 MB at the BASELINE shard).  HBM-bound: algorithmic bytes = read
 // support + write out (+ CSR), see DESIGN.md.
-#include "geom_common.h"
+#include "buffer_access.h"
 
 namespace {
 
-constexpr int GCN_THREADS = 256;
+using namespace geom;
 
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_ELU = 2 };
+constexpr int GCN_THREADS = 256;
 
 struct GcnArgs {
     const int *rowptr, *col;
@@ -31,23 +31,6 @@ struct GcnArgs {
     int64_t rows;       // b * nv
     int nv, c, k;
 };
-
-template <int ACT>
-__device__ __forceinline__ float act_fwd(float v)
-{
-    if (ACT == ACT_RELU) return v > 0.f ? v : 0.f;
-    if (ACT == ACT_ELU) return v > 0.f ? v : expm1f(v);
-    return v;
-}
-
-// derivative expressed through the saved OUTPUT (what torch's relu/elu backward use)
-template <int ACT>
-__device__ __forceinline__ float act_bwd(float g, float out)
-{
-    if (ACT == ACT_RELU) return out > 0.f ? g : 0.f;
-    if (ACT == ACT_ELU) return out > 0.f ? g : g * (out + 1.f);
-    return g;
-}
 
 template <int VEC>
 struct Pack;

@@ -37,9 +37,8 @@
 //   * per row-block the gather waves request the rows of row-block i + 2, store what block i - 1 produced and finish
 //     row-block i + 1 (requested a turn ago) into the other panel: ~2 200 cycles of issue per SIMD beside the 4 608 of the
 //     MFMAs, ONE workgroup barrier per row-block; the neighbour table of the workgroup's rows sits resolved in LDS;
-//   * the panel is laid out [k-quarter g][row][52] so that the four lane groups of ds_read_b128 never share a bank
-//     (row pitch 13 x 16 B, quarter pitch a multiple of 256 B), and the k index of MFMA step (j', c) of lane group g is
-//     48 g + 4 j' + c: one 16-byte fragment read feeds four k-steps = 12 MFMAs.
+//   * the operand panel, the k permutation and the staging tile are the row-block product's of mfma_tiles.h (stated there with
+//     their bank arithmetic): one 16-byte fragment read feeds four k-steps = 12 MFMAs.
 //
 // The backward consumes the weight TRANSPOSED ([c, cin] row-major) so that its register slice loads with the same
 // contiguous 192-byte runs; the forward launch of the same layer emits that copy on the side (workgroup 0: 147 KB).
@@ -47,28 +46,24 @@
 // Row-blocks are dealt to workgroups in contiguous runs per XCD (a mesh's rows stay in one L2: its k-slice is gathered
 // ~7 times); the few row-blocks beyond an equal share (1281 = 5 * 256 + 1 at the BASELINE shard) are not given whole to
 // single workgroups (+20 % for the launch) but cut three ways by column component, +48 MFMAs on 720 for three workgroups.
-#include "geom_common.h"
+#include "mfma_tiles.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-struct __attribute__((packed, aligned(4))) f3u { float x, y, z; };
+using namespace geom;
 
 constexpr int ZS_ROLE = 256;        // threads of one role: 4 waves, one per SIMD
 constexpr int ZS_THREADS = 2 * ZS_ROLE;
-constexpr int ZS_C = 192;           // inner dimension of the product = width of the aggregated operand
+constexpr int ZS_C = RB_C;          // inner dimension of the product = width of the aggregated operand
 constexpr int ZS_K = 64;            // aggregated columns (split 3)
 constexpr int ZS_KG = ZS_K / 4;     // float4 groups of the aggregated slice = gather threads per row
 constexpr int ZS_W = 8;             // neighbour-table width
-constexpr int ZS_LDR = 52;          // floats per (quarter, row) line of the panel: 48 used, pitch 13 x 16 B (odd)
-constexpr int ZS_SUB = 16 * ZS_LDR; // one k-quarter of the panel: 832 floats, a multiple of 64 dwords
-constexpr int ZS_PANEL = 4 * ZS_SUB;
-constexpr int ZS_LDC = ZS_C + 4;    // row pitch of the output staging tile (196 % 32 == 4: the b128 writes of 8 rows hit 32 banks)
-constexpr int ZS_CST = 16 * ZS_LDC; // one 16 x 192 output tile
+#ifdef ZS_PROBE_NO_MFMA // probe build: the products on the vector unit
+constexpr int ZS_PROBE = TILE_PROBE_NO_MFMA;
+#else
+constexpr int ZS_PROBE = TILE_PROBE_NONE;
+#endif
 
-enum { ZS_ACT_NONE = 0, ZS_ACT_RELU = 1, ZS_ACT_ELU = 2 };
 enum { ZS_FWD = 0, ZS_BWD = 1 };
 
 struct ZsArgs {
@@ -95,8 +90,6 @@ struct ZsArgs {
     int q, rem, split3;             // row-blocks per workgroup; leftover row-blocks; leftovers cut three ways
 };
 
-__device__ __forceinline__ f3u ldg3(const float *p) { return *reinterpret_cast<const f3u *>(p); }
-
 #ifdef ZS_PROBE_STAMPS
 // probe build (tools/probe/zs_variants.sh): shader-clock stamps of wave 0 of every workgroup at the phase boundaries
 constexpr int ZS_STAMP_SLOTS = 64;
@@ -112,20 +105,6 @@ __device__ unsigned long long zs_stamps[1024 * ZS_STAMP_SLOTS];
 #define ZS_STAMP(i) do { } while (0)
 #endif
 
-template <int ACT>
-__device__ __forceinline__ float zs_act(float v)
-{
-    if (ACT == ZS_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (ACT == ZS_ACT_ELU) return v > 0.f ? v : expm1f(v);
-    return v;
-}
-template <int ACT>
-__device__ __forceinline__ float zs_act_bwd(float g, float out)
-{
-    if (ACT == ZS_ACT_RELU) return out > 0.f ? g : 0.f;
-    if (ACT == ZS_ACT_ELU) return out > 0.f ? g : g * (out + 1.f);
-    return g;
-}
 __device__ __forceinline__ float4 zs_masked(float4 v, unsigned m)
 {
     v.x = (m & 1u) ? v.x : 0.f, v.y = (m & 2u) ? v.y : 0.f, v.z = (m & 4u) ? v.z : 0.f, v.w = (m & 8u) ? v.w : 0.f;
@@ -137,28 +116,9 @@ template <int MODE, int ACT>
 struct ZsGather {
     float4 sv[ZS_W], own[3];
     unsigned own_bits;
-    unsigned nbits[MODE == ZS_BWD && ACT == ZS_ACT_RELU ? ZS_W : 1];
-    float4 ov[MODE == ZS_BWD && ACT == ZS_ACT_ELU ? ZS_W : 1], oo[MODE == ZS_BWD && ACT == ZS_ACT_ELU ? 3 : 1];
+    unsigned nbits[MODE == ZS_BWD && ACT == ACT_RELU ? ZS_W : 1];
+    float4 ov[MODE == ZS_BWD && ACT == ACT_ELU ? ZS_W : 1], oo[MODE == ZS_BWD && ACT == ACT_ELU ? 3 : 1];
 };
-
-// buffer addressing: a 32-bit byte offset per lane against a wave-uniform descriptor (half the address traffic of a flat
-// access per instruction -- a VMEM instruction between two MFMAs costs its issue time), loads beyond the range return 0 and
-// stores beyond it are dropped: predication without a branch in the MFMA stream
-constexpr unsigned ZS_OOB = 0x80000000u; // beyond every range here (zs_check_common bounds the arrays to < 2 GB)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t zs_rsrc(const void *p, int64_t bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, p ? (int)bytes : 0, 0x00020000);
-}
-__device__ __forceinline__ float4 zs_ld4(__amdgpu_buffer_rsrc_t r, unsigned off)
-{
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-__device__ __forceinline__ void zs_st4(__amdgpu_buffer_rsrc_t r, unsigned off, float4 v)
-{
-    __builtin_amdgcn_raw_buffer_store_b128((u32x4){__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)},
-                                           r, off, 0, 0);
-}
 
 // what both roles agree on: this workgroup's row-blocks
 struct ZsPlan {
@@ -180,9 +140,8 @@ __device__ __forceinline__ ZsPlan zs_plan(const ZsArgs &a, int w, int G)
 }
 
 // ---- MFMA role (waves 0-3) -------------------------------------------------------------------------------------------
-// Per row-block: 12 fragment reads + 144 MFMAs out of panel it % 2, the output tile to staging tile it % 2, one barrier.
-// Accumulator u of lane (x', g') holds C[row x'][48 wave + 12 g' + 3 r + u], r = 0..3 (the weight fragment is the
-// instruction's first operand): twelve consecutive output columns per lane.
+// Per row-block: 12 fragment reads + 144 MFMAs out of panel it % 2 (rowblock_product), the output tile to staging tile
+// it % 2, one barrier.
 __device__ __forceinline__ void zs_mfma_role(const ZsArgs &a, float *lds, const ZsPlan &p, const int w)
 {
     constexpr int ZS_STAMP_ROLE = 0;
@@ -192,7 +151,7 @@ __device__ __forceinline__ void zs_mfma_role(const ZsArgs &a, float *lds, const 
     const int x = lane & 15, g = lane >> 4;
     // the wave's slice of the weight: 192 x 48 in registers -- lane (x, g), step (jp, c): k = 48 g + 4 jp + c, columns
     // 48 wave + 3 x .. + 2 (clamped into the matrix)
-    const __amdgpu_buffer_rsrc_t r_b = zs_rsrc(a.bmat, (int64_t)ZS_C * a.ldb * 4);
+    const __amdgpu_buffer_rsrc_t r_b = rsrc(a.bmat, (int64_t)ZS_C * a.ldb * 4);
     const int jc = min(wave * 48 + 3 * x, a.n_out - 3);
     f3u b[12][4];
     {
@@ -221,43 +180,15 @@ __device__ __forceinline__ void zs_mfma_role(const ZsArgs &a, float *lds, const 
     ZS_STAMP(1);
     __syncthreads(); // (the gather waves' table entries)
     __syncthreads(); // panel 0 is ready
-    const float *pa = lds + g * ZS_SUB + x * ZS_LDR;
+    const auto weight = [&](int jp, int c, int u) { return u == 0 ? b[jp][c].x : u == 1 ? b[jp][c].y : b[jp][c].z; };
+    const float *pa = lds + panel_offset(48 * g, x);
     for (int it = 0; it < p.n_main; ++it) {
         ZS_STAMP(4 + 4 * it);
-        const float *panel = pa + (it & 1) * ZS_PANEL;
+        const float *panel = pa + (it & 1) * RB_PANEL;
         f32x4 acc[3];
-#pragma unroll
-        for (int u = 0; u < 3; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        f32x4 af = *reinterpret_cast<const f32x4 *>(panel);
-#pragma unroll
-        for (int jp = 0; jp < 12; ++jp) {
-            // the next group's fragment is requested in front of this group's 12 MFMAs (fenced: the compiler otherwise sinks
-            // the read to its use and every group starts with an LDS round trip)
-            f32x4 an = af;
-            if (jp + 1 < 12) an = *reinterpret_cast<const f32x4 *>(panel + 4 * (jp + 1));
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-#ifdef ZS_PROBE_NO_MFMA
-                acc[0] = acc[0] + af * b[jp][c].x, acc[1] = acc[1] + af * b[jp][c].y, acc[2] = acc[2] + af * b[jp][c].z;
-#else
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[jp][c].x, af[c], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[jp][c].y, af[c], acc[1], 0, 0, 0);
-                acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[jp][c].z, af[c], acc[2], 0, 0, 0);
-#endif
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            af = an;
-        }
+        rowblock_product<ZS_PROBE>(weight, panel, acc);
         ZS_STAMP(5 + 4 * it);
-        float e[12];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int u = 0; u < 3; ++u) e[3 * r + u] = acc[u][r];
-        float *dst = lds + 2 * ZS_PANEL + (it & 1) * ZS_CST + x * ZS_LDC + wave * 48 + 12 * g;
-#pragma unroll
-        for (int v = 0; v < 3; ++v) *reinterpret_cast<f32x4 *>(dst + 4 * v) = (f32x4){e[4 * v], e[4 * v + 1], e[4 * v + 2], e[4 * v + 3]};
+        rowblock_to_stage(acc, lds + 2 * RB_PANEL + (it & 1) * RB_CST, wave, x, g);
         ZS_STAMP(6 + 4 * it);
         __syncthreads();
         ZS_STAMP(7 + 4 * it);
@@ -265,7 +196,7 @@ __device__ __forceinline__ void zs_mfma_role(const ZsArgs &a, float *lds, const 
     // one column component of a leftover row-block shared three ways (its panel was finished during the last block): two
     // accumulators alternate (even / odd k-steps) so that no MFMA waits for its predecessor; straight to memory
     if (p.ue >= 0) {
-        const float *panel = pa + (p.n_main & 1) * ZS_PANEL;
+        const float *panel = pa + (p.n_main & 1) * RB_PANEL;
         auto partial_block = [&](auto pick, int u) {
             f32x4 p0 = {0.f, 0.f, 0.f, 0.f}, p1 = p0;
             f32x4 af = *reinterpret_cast<const f32x4 *>(panel);
@@ -320,14 +251,14 @@ __device__ __forceinline__ void zs_gather_role(const ZsArgs &a, float *lds, cons
     const int rl = tid >> 4, j = tid & 15; // row of the row-block, float4 group
     const int c0 = 4 * j;
     const bool writer_extra = p.ue <= 0;   // of the three workgroups that share a leftover row-block, one writes its operand
-    unsigned *ring = reinterpret_cast<unsigned *>(lds + 2 * ZS_PANEL + 2 * ZS_CST + 4 * ZS_C);
+    unsigned *ring = reinterpret_cast<unsigned *>(lds + 2 * RB_PANEL + 2 * RB_CST + 4 * ZS_C);
 
     const int64_t op_bytes = (int64_t)a.rows * ZS_C * 4;
-    const __amdgpu_buffer_rsrc_t r_src = zs_rsrc(a.src, op_bytes), r_saved = zs_rsrc(a.saved, op_bytes);
-    const __amdgpu_buffer_rsrc_t r_min = zs_rsrc(a.mask_in, (int64_t)a.rows * ZS_KG * 2), r_mout = zs_rsrc(a.mask_out, (int64_t)a.rows * ZS_KG * 2);
-    const __amdgpu_buffer_rsrc_t r_gp = zs_rsrc(a.head_gp, (int64_t)a.rows * 12), r_aout = zs_rsrc(a.a_out, op_bytes);
-    const __amdgpu_buffer_rsrc_t r_cout = zs_rsrc(a.c_out, (int64_t)a.rows * a.ldc * 4);
-    const __amdgpu_buffer_rsrc_t r_col = zs_rsrc(a.ell_col, (int64_t)a.nv * ZS_W * 4), r_val = zs_rsrc(a.ell_val, (int64_t)a.nv * ZS_W * 4);
+    const __amdgpu_buffer_rsrc_t r_src = rsrc(a.src, op_bytes), r_saved = rsrc(a.saved, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_min = rsrc(a.mask_in, (int64_t)a.rows * ZS_KG * 2), r_mout = rsrc(a.mask_out, (int64_t)a.rows * ZS_KG * 2);
+    const __amdgpu_buffer_rsrc_t r_gp = rsrc(a.head_gp, (int64_t)a.rows * 12), r_aout = rsrc(a.a_out, op_bytes);
+    const __amdgpu_buffer_rsrc_t r_cout = rsrc(a.c_out, (int64_t)a.rows * a.ldc * 4);
+    const __amdgpu_buffer_rsrc_t r_col = rsrc(a.ell_col, (int64_t)a.nv * ZS_W * 4), r_val = rsrc(a.ell_val, (int64_t)a.nv * ZS_W * 4);
 
     // entries of row-blocks [first, first + 8) into their ring slots: thread s < 128 resolves row s % 16 of block first + s / 16
     auto fill = [&](int first) {
@@ -359,7 +290,7 @@ __device__ __forceinline__ void zs_gather_role(const ZsArgs &a, float *lds, cons
 
     // round trip: neighbour rows of the aggregated slot + the thread's own elements (+ sign words / saved outputs)
     auto head_at = [&](unsigned row_off) -> float4 { // [scale * grad_pos | 0] of a row: lanes j != 0 read beyond the range = zeros
-        const u32x3 t = __builtin_amdgcn_raw_buffer_load_b96(r_gp, j == 0 ? row_off / (ZS_C * 4) * 12u : ZS_OOB, 0, 0);
+        const u32x3 t = __builtin_amdgcn_raw_buffer_load_b96(r_gp, j == 0 ? row_off / (ZS_C * 4) * 12u : OOB, 0, 0);
         return make_float4(a.head_scale * __uint_as_float(t.x), a.head_scale * __uint_as_float(t.y), a.head_scale * __uint_as_float(t.z), 0.f);
     };
     auto gather = [&](ZsGather<MODE, ACT> &gv, int it) {
@@ -375,17 +306,17 @@ __device__ __forceinline__ void zs_gather_role(const ZsArgs &a, float *lds, cons
             const unsigned off = o[n];
 #endif
             if (HEAD) gv.sv[n] = head_at(off);
-            else gv.sv[n] = zs_ld4(r_src, off + 4 * c0);
-            if (MODE == ZS_BWD && ACT == ZS_ACT_RELU) gv.nbits[n] = __builtin_amdgcn_raw_buffer_load_b16(r_min, off / (ZS_C * 4 / (ZS_KG * 2)) + 2 * j, 0, 0);
-            if (MODE == ZS_BWD && ACT == ZS_ACT_ELU) gv.ov[n] = zs_ld4(r_saved, off + 4 * c0);
+            else gv.sv[n] = ld4(r_src, off + 4 * c0);
+            if (MODE == ZS_BWD && ACT == ACT_RELU) gv.nbits[n] = __builtin_amdgcn_raw_buffer_load_b16(r_min, off / (ZS_C * 4 / (ZS_KG * 2)) + 2 * j, 0, 0);
+            if (MODE == ZS_BWD && ACT == ACT_ELU) gv.ov[n] = ld4(r_saved, off + 4 * c0);
         }
 #pragma unroll
         for (int i = MODE == ZS_BWD ? 0 : 1; i < 3; ++i) {
             if (HEAD) gv.own[i] = i == 0 ? head_at(own) : make_float4(0.f, 0.f, 0.f, 0.f);
-            else gv.own[i] = zs_ld4(r_src, own + 4 * c0 + 4 * ZS_K * i);
-            if (MODE == ZS_BWD && ACT == ZS_ACT_ELU) gv.oo[i] = zs_ld4(r_saved, own + 4 * c0 + 4 * ZS_K * i);
+            else gv.own[i] = ld4(r_src, own + 4 * c0 + 4 * ZS_K * i);
+            if (MODE == ZS_BWD && ACT == ACT_ELU) gv.oo[i] = ld4(r_saved, own + 4 * c0 + 4 * ZS_K * i);
         }
-        if (MODE == ZS_BWD && ACT == ZS_ACT_RELU) gv.own_bits = __builtin_amdgcn_raw_buffer_load_b16(r_min, own / (ZS_C * 4 / (ZS_KG * 2)) + 2 * j, 0, 0);
+        if (MODE == ZS_BWD && ACT == ACT_RELU) gv.own_bits = __builtin_amdgcn_raw_buffer_load_b16(r_min, own / (ZS_C * 4 / (ZS_KG * 2)) + 2 * j, 0, 0);
     };
 
     // What a block produced leaves in the NEXT turn, behind that turn's loads (the memory counter is in order: a wait for a
@@ -395,29 +326,29 @@ __device__ __forceinline__ void zs_gather_role(const ZsArgs &a, float *lds, cons
     // 16 rows = 32 partial cache lines per wave instruction, measured 2x the launch).  Rows that do not exist are stored
     // beyond the descriptor's range: dropped.
     float4 px[3];
-    unsigned px_bits = 0u, px_off = ZS_OOB;
+    unsigned px_bits = 0u, px_off = OOB;
     auto flush_x = [&]() {
 #ifdef ZS_PROBE_NO_STORE
-        px_off = ZS_OOB;
+        px_off = OOB;
 #endif
 #pragma unroll
-        for (int i = 0; i < 3; ++i) zs_st4(r_aout, px_off + 4 * c0 + 4 * ZS_K * i, px[i]);
-        if (MODE == ZS_FWD && ACT == ZS_ACT_RELU)
-            __builtin_amdgcn_raw_buffer_store_b16((unsigned short)px_bits, r_mout, px_off == ZS_OOB ? ZS_OOB : px_off / (ZS_C * 4 / (ZS_KG * 2)) + 2 * j, 0, 0);
-        px_off = ZS_OOB;
+        for (int i = 0; i < 3; ++i) st4(r_aout, px_off + 4 * c0 + 4 * ZS_K * i, px[i]);
+        if (MODE == ZS_FWD && ACT == ACT_RELU)
+            __builtin_amdgcn_raw_buffer_store_b16((unsigned short)px_bits, r_mout, px_off == OOB ? OOB : px_off / (ZS_C * 4 / (ZS_KG * 2)) + 2 * j, 0, 0);
+        px_off = OOB;
     };
     auto flush_c = [&](int it) { // the output tile of block `it` (staged by the MFMA waves, behind that block's barrier)
         const int rb = it >= 0 ? p.rb_of(it) : -1;
-        const float *tile = lds + 2 * ZS_PANEL + (it & 1) * ZS_CST;
+        const float *tile = lds + 2 * RB_PANEL + (it & 1) * RB_CST;
 #pragma unroll
         for (int v = 0; v < 3; ++v) {
             const int idx = tid + ZS_ROLE * v, r = idx / 48, c4 = idx % 48, row = rb * 16 + r;
-            const f32x4 val = *reinterpret_cast<const f32x4 *>(tile + r * ZS_LDC + 4 * c4);
-            unsigned off = rb >= 0 && row < a.rows && 4 * c4 + 3 < a.n_out ? ((unsigned)row * (unsigned)a.ldc + 4u * c4) * 4u : ZS_OOB;
+            const f32x4 val = *reinterpret_cast<const f32x4 *>(tile + r * RB_LDC + 4 * c4);
+            unsigned off = rb >= 0 && row < a.rows && 4 * c4 + 3 < a.n_out ? ((unsigned)row * (unsigned)a.ldc + 4u * c4) * 4u : OOB;
 #ifdef ZS_PROBE_NO_STORE
-            off = ZS_OOB;
+            off = OOB;
 #endif
-            zs_st4(r_cout, off, make_float4(val[0], val[1], val[2], val[3]));
+            st4(r_cout, off, make_float4(val[0], val[1], val[2], val[3]));
         }
     };
 
@@ -434,10 +365,10 @@ __device__ __forceinline__ void zs_gather_role(const ZsArgs &a, float *lds, cons
         if (MODE == ZS_BWD) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                if (ACT == ZS_ACT_RELU) gv.own[i] = zs_masked(gv.own[i], gv.own_bits >> (4 * i));
-                else if (ACT == ZS_ACT_ELU) {
-                    gv.own[i].x = zs_act_bwd<ACT>(gv.own[i].x, gv.oo[i].x), gv.own[i].y = zs_act_bwd<ACT>(gv.own[i].y, gv.oo[i].y);
-                    gv.own[i].z = zs_act_bwd<ACT>(gv.own[i].z, gv.oo[i].z), gv.own[i].w = zs_act_bwd<ACT>(gv.own[i].w, gv.oo[i].w);
+                if (ACT == ACT_RELU) gv.own[i] = zs_masked(gv.own[i], gv.own_bits >> (4 * i));
+                else if (ACT == ACT_ELU) {
+                    gv.own[i].x = act_bwd<ACT>(gv.own[i].x, gv.oo[i].x), gv.own[i].y = act_bwd<ACT>(gv.own[i].y, gv.oo[i].y);
+                    gv.own[i].z = act_bwd<ACT>(gv.own[i].z, gv.oo[i].z), gv.own[i].w = act_bwd<ACT>(gv.own[i].w, gv.oo[i].w);
                 }
             }
         }
@@ -448,10 +379,10 @@ __device__ __forceinline__ void zs_gather_role(const ZsArgs &a, float *lds, cons
             // EVERY value untouched, signed zeros included (x + -0.0 == x bit for bit) -- the skipped term of that kernel without
             // a branch (the product is formed and discarded; `v` of a padded slot is the row's own element)
             float4 v = gv.sv[n];
-            if (MODE == ZS_BWD && ACT == ZS_ACT_RELU) v = zs_masked(v, gv.nbits[n]);
-            else if (MODE == ZS_BWD && ACT == ZS_ACT_ELU) {
-                v.x = zs_act_bwd<ACT>(v.x, gv.ov[n].x), v.y = zs_act_bwd<ACT>(v.y, gv.ov[n].y);
-                v.z = zs_act_bwd<ACT>(v.z, gv.ov[n].z), v.w = zs_act_bwd<ACT>(v.w, gv.ov[n].w);
+            if (MODE == ZS_BWD && ACT == ACT_RELU) v = zs_masked(v, gv.nbits[n]);
+            else if (MODE == ZS_BWD && ACT == ACT_ELU) {
+                v.x = act_bwd<ACT>(v.x, gv.ov[n].x), v.y = act_bwd<ACT>(v.y, gv.ov[n].y);
+                v.z = act_bwd<ACT>(v.z, gv.ov[n].z), v.w = act_bwd<ACT>(v.w, gv.ov[n].w);
             }
             const bool in = (in_mask >> n) & 1u;
             const float wn = __uint_as_float(wv[n]);
@@ -464,20 +395,19 @@ __device__ __forceinline__ void zs_gather_role(const ZsArgs &a, float *lds, cons
             float4 v = i == 0 ? facc : gv.own[i];
             if (MODE == ZS_FWD) {
                 v.x += bias4[i].x, v.y += bias4[i].y, v.z += bias4[i].z, v.w += bias4[i].w;
-                v.x = zs_act<ACT>(v.x), v.y = zs_act<ACT>(v.y), v.z = zs_act<ACT>(v.z), v.w = zs_act<ACT>(v.w);
-                if (ACT == ZS_ACT_RELU) {
+                v.x = act_fwd<ACT>(v.x), v.y = act_fwd<ACT>(v.y), v.z = act_fwd<ACT>(v.z), v.w = act_fwd<ACT>(v.w);
+                if (ACT == ACT_RELU) {
                     // out > 0 (the predicate relu' is defined by): a ReLU output is +0 or positive, so its bit pattern is zero
                     // or a positive integer -- min(bits, 1) instead of a compare + select per element
                     sign_bits |= (min(__float_as_uint(v.x), 1u) | min(__float_as_uint(v.y), 1u) << 1 | min(__float_as_uint(v.z), 1u) << 2 |
                                   min(__float_as_uint(v.w), 1u) << 3) << (4 * i);
                 }
             }
-            const int col = c0 + ZS_K * i; // -> quarter col / 48, position col % 48
-            *reinterpret_cast<float4 *>(panel + (col / 48) * ZS_SUB + rl * ZS_LDR + col % 48) = v;
+            *reinterpret_cast<float4 *>(panel + panel_offset(c0 + ZS_K * i, rl)) = v;
             px[i] = v;
         }
         const bool on = misc.z != 0u && writes;
-        px_off = on ? misc.y : ZS_OOB, px_bits = sign_bits;
+        px_off = on ? misc.y : OOB, px_bits = sign_bits;
         if (MODE == ZS_BWD) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
@@ -510,7 +440,7 @@ __device__ __forceinline__ void zs_gather_role(const ZsArgs &a, float *lds, cons
         flush_c(it - 1);
         if (((it + 3) & 7) == 0) fill(it + 3); // visible behind this turn's barrier, first used in the next turn
         ZS_STAMP(5 + 4 * it);
-        finish(ready, it + 1, lds + ((it + 1) & 1) * ZS_PANEL, writes);
+        finish(ready, it + 1, lds + ((it + 1) & 1) * RB_PANEL, writes);
         ZS_STAMP(6 + 4 * it);
         __syncthreads();
         ZS_STAMP(7 + 4 * it);
@@ -529,7 +459,7 @@ __device__ __forceinline__ void zs_gather_role(const ZsArgs &a, float *lds, cons
     // ---- bias gradient: the workgroup's column sums, rows folded in a fixed order: the four rows of a wave by shuffles
     // (lanes 16 apart), the four waves' sums through LDS by the closing code of zs_body
     if (MODE == ZS_BWD && a.colsum_partial) {
-        float *cs = lds + 2 * ZS_PANEL + 2 * ZS_CST; // [4][192]
+        float *cs = lds + 2 * RB_PANEL + 2 * RB_CST; // [4][192]
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             float4 t = csum[i];
@@ -551,7 +481,7 @@ __device__ __forceinline__ void zs_body(const ZsArgs &a, float *lds, const int w
     else zs_gather_role<MODE, ACT, HEAD>(a, lds, p, w);
     if (MODE == ZS_BWD && a.colsum_partial) {
         __syncthreads();
-        const float *cs = lds + 2 * ZS_PANEL + 2 * ZS_CST;
+        const float *cs = lds + 2 * RB_PANEL + 2 * RB_CST;
         if (threadIdx.x < ZS_C) {
             const int c = threadIdx.x;
             a.colsum_partial[(size_t)w * ZS_C + c] = ((cs[c] + cs[ZS_C + c]) + cs[2 * ZS_C + c]) + cs[3 * ZS_C + c];
@@ -562,7 +492,7 @@ __device__ __forceinline__ void zs_body(const ZsArgs &a, float *lds, const int w
 template <int MODE, int ACT, bool HEAD>
 __global__ __launch_bounds__(ZS_THREADS, 2) void zs_layer_kernel(ZsArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float lds[2 * ZS_PANEL + 2 * ZS_CST + 4 * ZS_C + ZS_RING_DW];
+    __shared__ __attribute__((aligned(16))) float lds[2 * RB_PANEL + 2 * RB_CST + 4 * ZS_C + ZS_RING_DW];
     zs_body<MODE, ACT, HEAD>(a, lds, blockIdx.x, gridDim.x);
 }
 
@@ -640,7 +570,7 @@ extern "C" int geom_zn_layer_fwd_f32(int b, int nv, int c, int k, int ell_w, con
     if (!zs_aligned16(ell_col) || !zs_aligned16(ell_val) || !zs_aligned16(s_prev) || !zs_aligned16(x_out) || !zs_aligned16(s_out) ||
         (bias_prev && !zs_aligned16(bias_prev)) || ((uintptr_t)w & 3) || ((uintptr_t)wt_out & 3))
         return GEOM_EINVAL;
-    if (relu_mask && act != ZS_ACT_RELU) return GEOM_EINVAL;
+    if (relu_mask && act != ACT_RELU) return GEOM_EINVAL;
     const int rows = b * nv;
     const ZsGeo geo = zs_geometry(rows);
     ZsArgs a{};
@@ -650,9 +580,9 @@ extern "C" int geom_zn_layer_fwd_f32(int b, int nv, int c, int k, int ell_w, con
     const dim3 grid(geo.grid), block(ZS_THREADS);
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (act) {
-    case ZS_ACT_NONE: hipLaunchKernelGGL((zs_layer_kernel<ZS_FWD, ZS_ACT_NONE, false>), grid, block, 0, s, a); break;
-    case ZS_ACT_RELU: hipLaunchKernelGGL((zs_layer_kernel<ZS_FWD, ZS_ACT_RELU, false>), grid, block, 0, s, a); break;
-    case ZS_ACT_ELU: hipLaunchKernelGGL((zs_layer_kernel<ZS_FWD, ZS_ACT_ELU, false>), grid, block, 0, s, a); break;
+    case ACT_NONE: hipLaunchKernelGGL((zs_layer_kernel<ZS_FWD, ACT_NONE, false>), grid, block, 0, s, a); break;
+    case ACT_RELU: hipLaunchKernelGGL((zs_layer_kernel<ZS_FWD, ACT_RELU, false>), grid, block, 0, s, a); break;
+    case ACT_ELU: hipLaunchKernelGGL((zs_layer_kernel<ZS_FWD, ACT_ELU, false>), grid, block, 0, s, a); break;
     default: return GEOM_EINVAL;
     }
     return geom::launch_status();
@@ -675,8 +605,8 @@ extern "C" int geom_zn_layer_bwd_f32(int b, int nv, int c, int k, int ell_w, con
     if (code) return code;
     if (b == 0 || nv == 0) return 0;
     if (!ell_col_t || !ell_val_t || !wt || !g_out || !grad_in || (!grad_out && !grad_pos)) return GEOM_EINVAL;
-    if (act == ZS_ACT_RELU && !relu_mask) return GEOM_EINVAL;
-    if (act == ZS_ACT_ELU && (!out || grad_pos)) return grad_pos ? GEOM_EUNSUPPORTED : GEOM_EINVAL;
+    if (act == ACT_RELU && !relu_mask) return GEOM_EINVAL;
+    if (act == ACT_ELU && (!out || grad_pos)) return grad_pos ? GEOM_EUNSUPPORTED : GEOM_EINVAL;
     if (!zs_aligned16(ell_col_t) || !zs_aligned16(ell_val_t) || !zs_aligned16(grad_out) || !zs_aligned16(out) || !zs_aligned16(g_out) ||
         !zs_aligned16(grad_in) || ((uintptr_t)wt & 3) || ((uintptr_t)grad_pos & 3) || ((uintptr_t)colsum_partial & 3))
         return GEOM_EINVAL;
@@ -691,15 +621,15 @@ extern "C" int geom_zn_layer_bwd_f32(int b, int nv, int c, int k, int ell_w, con
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool head = grad_pos != nullptr;
     switch (act) {
-    case ZS_ACT_NONE:
-        if (head) hipLaunchKernelGGL((zs_layer_kernel<ZS_BWD, ZS_ACT_NONE, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((zs_layer_kernel<ZS_BWD, ZS_ACT_NONE, false>), grid, block, 0, s, a);
+    case ACT_NONE:
+        if (head) hipLaunchKernelGGL((zs_layer_kernel<ZS_BWD, ACT_NONE, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((zs_layer_kernel<ZS_BWD, ACT_NONE, false>), grid, block, 0, s, a);
         break;
-    case ZS_ACT_RELU:
-        if (head) hipLaunchKernelGGL((zs_layer_kernel<ZS_BWD, ZS_ACT_RELU, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((zs_layer_kernel<ZS_BWD, ZS_ACT_RELU, false>), grid, block, 0, s, a);
+    case ACT_RELU:
+        if (head) hipLaunchKernelGGL((zs_layer_kernel<ZS_BWD, ACT_RELU, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((zs_layer_kernel<ZS_BWD, ACT_RELU, false>), grid, block, 0, s, a);
         break;
-    case ZS_ACT_ELU: hipLaunchKernelGGL((zs_layer_kernel<ZS_BWD, ZS_ACT_ELU, false>), grid, block, 0, s, a); break;
+    case ACT_ELU: hipLaunchKernelGGL((zs_layer_kernel<ZS_BWD, ACT_ELU, false>), grid, block, 0, s, a); break;
     default: return GEOM_EINVAL;
     }
     return geom::launch_status();

@@ -83,6 +83,34 @@ def test_layer_entry_forward(gpu, mesh, batch, cin, cout):
     assert torch.equal(out, encoder.layer_forward(s, csr, k, bias, act, w, batch, nv))       # x_out = NULL: the same product
 
 
+@pytest.mark.parametrize("cin,cout", [(3, 60), (120, 150), (250, 300)])
+def test_layer_entry_without_a_tail_gives_the_any_shape_product_bits(gpu, cin, cout):
+    """k = 0, no bias and no activation leave the launch a plain product, and geom_gemm_f32 is the other user of the same staged
+    64 x 64 tile (csrc/mfma_tiles.h): at these widths (no split below K = 512, 32-deep stages in both, zero fill beyond K) an
+    accumulator receives the same MFMA steps in the same order in both kernels -- the same bits, forward and backward, the
+    backward also with its weight at a row pitch."""
+    from geometrics_amd import _lib, aggregation, dense, encoder
+    _, _, _, csr = _mesh("icosphere_2")
+    batch, nv = 2, csr.nv
+    rows = batch * nv
+    gen = torch.Generator(device="cpu").manual_seed(1000 * cin + cout)
+    s, g = torch.randn(rows, cin, generator=gen).cuda(), torch.randn(rows, cout, generator=gen).cuda()
+    w = (torch.randn(cin, cout, generator=gen) / cin ** 0.5).cuda()
+    none = aggregation.ACT_NONE
+
+    def same_bits(a, b):
+        return torch.equal(a.view(torch.int32), b.view(torch.int32))
+    assert same_bits(encoder.layer_forward(s, csr, 0, None, none, w, batch, nv), dense.gemm(s, w))
+    back = encoder.layer_backward(g, None, csr, 0, none, w, batch, nv)
+    assert same_bits(back, dense.gemm(g, w, trans_b=True))
+    frame = torch.full((cin, cout + 5), float("nan"), device="cuda")
+    frame[:, 3:3 + cout] = w
+    wp, out = frame[:, 3:3 + cout], torch.empty(rows, cin, device="cuda")
+    _lib.call("geom_encoder_layer_bwd_f32", batch, nv, cout, 0, cin, None, None, None, g.data_ptr(), cout, None, cout, none,
+              wp.data_ptr(), cout + 5, out.data_ptr(), cin, None, cout)
+    assert same_bits(out, dense.gemm(g, wp, trans_b=True)) and same_bits(out, back)
+
+
 @pytest.mark.parametrize("cin,cout", PAIRS)
 @pytest.mark.parametrize("mesh,batch", MESHES)
 def test_layer_entry_backward(gpu, mesh, batch, cin, cout):
