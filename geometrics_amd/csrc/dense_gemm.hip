@@ -43,14 +43,30 @@ constexpr int DG_BK = 32; // inner-dimension elements per LDS stage
 constexpr int DG_KS = 8;  // MFMA k-steps (4 elements each) per stage
 constexpr int SPLIT_RB = 6;        // weight-gradient tiles: 96 rows x 192 columns ...
 constexpr int SPLIT_RB_NARROW = 3; // ... 48 rows for layers of <= 192 inputs (see split_geometry)
-#ifndef DG_SPLIT_KP
-#define DG_SPLIT_KP 1   // measured (profiles/r04_split_kernel_ablation.txt): two waves per SIMD buy nothing -- 66.8 vs 65.7 us
-#endif
-constexpr int SPLIT_KP_WIDE = DG_SPLIT_KP;   // k-parts (waves per SIMD) of the stand-alone weight-gradient launch of a wide layer, see split_stage
 constexpr int LD_TC = 34; // stride of a [row][t] panel: fragment reads hit bank (2*row + t) % 32 -- all distinct
 
 // stride of a [t][r] panel of R columns: the smallest s >= R with s % 32 == 16 (rows t and t+1 half a bank row apart)
 __host__ __device__ constexpr int ld_rc(int r) { return ((r + 15) / 32) * 32 + 16; }
+
+// Probe knobs (tools/probe/dense_probe.cpp, profiles/README.md): each -DDG_PROBE_NO_x takes one piece of work out of the
+// stage loop -- results WRONG, only time is read.  Read here and nowhere else.
+#ifndef DG_PROBE_NO_FETCH
+#define DG_PROBE_NO_FETCH 0   // the LDS fragment reads
+#endif
+#ifndef DG_PROBE_NO_ISSUE
+#define DG_PROBE_NO_ISSUE 0   // the global loads of the panels
+#endif
+#ifndef DG_PROBE_NO_STORE
+#define DG_PROBE_NO_STORE 0   // the LDS stores of the panels
+#endif
+#ifndef DG_PROBE_NO_BARRIER
+#define DG_PROBE_NO_BARRIER 0 // the stage barrier
+#endif
+#ifndef DG_PROBE_NO_G
+#define DG_PROBE_NO_G 0       // the split product's refill of its G ring
+#endif
+constexpr bool DG_FETCH = !DG_PROBE_NO_FETCH, DG_ISSUE = !DG_PROBE_NO_ISSUE, DG_STORE = !DG_PROBE_NO_STORE,
+               DG_BARRIER = !DG_PROBE_NO_BARRIER, DG_G = !DG_PROBE_NO_G;
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Panel staging.  A panel is the slice of one operand a stage needs: R rows x 32 inner elements.
@@ -69,26 +85,30 @@ __host__ __device__ constexpr int ld_rc(int r) { return ((r + 15) / 32) * 32 + 1
 //   store_pass(p..)  registers -> LDS; ZERO: inner positions >= tmax are zero-filled (only the A operand does that: one
 //                    zero factor is enough).
 // A pass is one load / store instruction per thread; the pipeline below spreads the passes over a stage's MFMAs.
-__device__ __forceinline__ float ldg(const float *base, unsigned byte_off)
+// W = floats per load: 4 (ONE global_load_dwordx4; 4-byte alignment is enough for it -- the 963-float rows of the first
+// layer's features) where the contiguous run of the operand is a multiple of 4, 1 otherwise; 3 is the split product's G ring.
+template <int W>
+using ldg_t = std::conditional_t<W == 4, f32x4, std::conditional_t<W == 3, f3u, float>>;
+template <int W>
+__device__ __forceinline__ ldg_t<W> ldg(const float *base, unsigned byte_off)
 {
-    return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + byte_off);
-}
-__device__ __forceinline__ f32x4 ldg4(const float *base, unsigned byte_off)
-{ // 16 bytes at 4-byte alignment (still ONE global_load_dwordx4): the 963-float rows of the first layer's features
-    const f4u v = *reinterpret_cast<const f4u *>(reinterpret_cast<const char *>(base) + byte_off);
-    return (f32x4){v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ f3u ldg3(const float *base, unsigned byte_off)
-{
-    return *reinterpret_cast<const f3u *>(reinterpret_cast<const char *>(base) + byte_off);
+    const char *p = reinterpret_cast<const char *>(base) + byte_off;
+    if constexpr (W == 4) {
+        const f4u v = *reinterpret_cast<const f4u *>(p);
+        return (f32x4){v.x, v.y, v.z, v.w};
+    } else {
+        return *reinterpret_cast<const ldg_t<W> *>(p);
+    }
 }
 
-// TC panel, 16-byte loads (rows 16-byte aligned, T % 4 == 0): 8 threads per row, 32 rows per pass
-template <int R>
-struct PanelTCv {
-    static constexpr int PASSES = (R + 31) / 32;
-    static constexpr int WIDTH = 4;
-    f32x4 v[2][PASSES]; // two register sets: one being loaded while the other waits for its turn to go to LDS
+// TC panel: 32 / W threads per row, 8 * W rows per pass
+template <int R, int W>
+struct PanelTC {
+    static constexpr int WIDTH = W, TPR = 32 / W, ROWS = DG_THREADS / TPR;
+    static constexpr int PASSES = (R + ROWS - 1) / ROWS;
+    static constexpr bool EXACT = R % ROWS == 0;
+    static_assert(W == 4 || EXACT, "the 4-byte form covers whole passes");
+    ldg_t<W> v[2][PASSES]; // two register sets: one being loaded while the other waits for its turn to go to LDS
     unsigned off[PASSES];
     // rowoff(r) -> ELEMENT offset of (clamped) row r
     template <typename RowOff>
@@ -96,119 +116,65 @@ struct PanelTCv {
     {
 #pragma unroll
         for (int p = 0; p < PASSES; ++p) {
-            const int r = p * 32 + (threadIdx.x >> 3);
-            off[p] = ((unsigned)rowoff(r < R ? r : R - 1) + (threadIdx.x & 7) * 4u) * 4u;
+            const int r = p * ROWS + threadIdx.x / TPR; // W == 1: R % 8 == 0, nothing to clamp
+            off[p] = ((unsigned)rowoff(W == 1 || r < R ? r : R - 1) + (threadIdx.x % TPR) * W) * 4u;
         }
     }
     static __device__ __forceinline__ const float *stage_base(const float *g, unsigned /*ld*/, int t0) { return g + t0; }
-    static __device__ __forceinline__ unsigned stage_limit(unsigned total, unsigned /*ld*/, int t0) { return (total - 4u - (unsigned)t0) * 4u; }
+    static __device__ __forceinline__ unsigned stage_limit(unsigned total, unsigned /*ld*/, int t0) { return (total - W - (unsigned)t0) * 4u; }
     template <int SET>
-    __device__ __forceinline__ void issue_pass(int p, const float *base, unsigned limit) { v[SET][p] = ldg4(base, min(off[p], limit)); }
+    __device__ __forceinline__ void issue_pass(int p, const float *base, unsigned limit) { v[SET][p] = ldg<W>(base, min(off[p], limit)); }
     template <bool ZERO, int SET>
     __device__ __forceinline__ void store_pass(int p, float *lds, int t0, int tmax) const
     {
-        const int tl = (threadIdx.x & 7) * 4;
-        const int r = p * 32 + (threadIdx.x >> 3);
-        if (R % 32 == 0 || r < R) { // 34-float rows are 8-byte aligned: two ds_write_b64
+        const int tl = (threadIdx.x % TPR) * W;
+        const int r = p * ROWS + threadIdx.x / TPR;
+        if (EXACT || r < R) {
             const bool tin = !ZERO || t0 + tl < tmax;
-            float2 *d = reinterpret_cast<float2 *>(lds + r * LD_TC + tl);
-            d[0] = make_float2(tin ? v[SET][p][0] : 0.f, tin ? v[SET][p][1] : 0.f);
-            d[1] = make_float2(tin ? v[SET][p][2] : 0.f, tin ? v[SET][p][3] : 0.f);
+            float *d = lds + r * LD_TC + tl;
+            if constexpr (W == 4) { // 34-float rows are 8-byte aligned: two ds_write_b64
+                reinterpret_cast<float2 *>(d)[0] = make_float2(tin ? v[SET][p][0] : 0.f, tin ? v[SET][p][1] : 0.f);
+                reinterpret_cast<float2 *>(d)[1] = make_float2(tin ? v[SET][p][2] : 0.f, tin ? v[SET][p][3] : 0.f);
+            } else {
+                *d = tin ? v[SET][p] : 0.f;
+            }
         }
     }
 };
 
-// TC panel, 4-byte loads (rows that are only dword aligned: the 963-wide features): 32 threads per row, 8 rows per pass
-template <int R>
-struct PanelTCs {
-    static constexpr int PASSES = R / 8;
-    static constexpr int WIDTH = 1;
-    float v[2][PASSES];
+// RC panel, loads of W floats along r: element e = thread + 256 * p of the 32 x R/W grid
+template <int R, int W>
+struct PanelRC {
+    static constexpr int WIDTH = W, Q = R / W;
+    static constexpr int PASSES = (32 * Q + DG_THREADS - 1) / DG_THREADS;
+    static constexpr bool EXACT = (32 * Q) % DG_THREADS == 0;
+    ldg_t<W> v[2][PASSES];
     unsigned off[PASSES];
-    template <typename RowOff>
-    __device__ __forceinline__ void prepare(RowOff rowoff, unsigned /*ld*/)
-    {
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) off[p] = ((unsigned)rowoff(p * 8 + (threadIdx.x >> 5)) + (threadIdx.x & 31)) * 4u;
-    }
-    static __device__ __forceinline__ const float *stage_base(const float *g, unsigned /*ld*/, int t0) { return g + t0; }
-    static __device__ __forceinline__ unsigned stage_limit(unsigned total, unsigned /*ld*/, int t0) { return (total - 1u - (unsigned)t0) * 4u; }
-    template <int SET>
-    __device__ __forceinline__ void issue_pass(int p, const float *base, unsigned limit) { v[SET][p] = ldg(base, min(off[p], limit)); }
-    template <bool ZERO, int SET>
-    __device__ __forceinline__ void store_pass(int p, float *lds, int t0, int tmax) const
-    {
-        const int tl = threadIdx.x & 31;
-        const bool tin = !ZERO || t0 + tl < tmax;
-        lds[(p * 8 + (threadIdx.x >> 5)) * LD_TC + tl] = tin ? v[SET][p] : 0.f;
-    }
-};
-
-// RC panel, 16-byte loads along r: element e = thread + NT * p of the 32 x R/4 grid (NT = threads of the workgroup)
-template <int R, int NT = DG_THREADS>
-struct PanelRCv {
-    static constexpr int Q = R / 4;
-    static constexpr int PASSES = (32 * Q + NT - 1) / NT;
-    static constexpr bool EXACT = (32 * Q) % NT == 0;
-    static constexpr int WIDTH = 4;
-    f32x4 v[2][PASSES];
-    unsigned off[PASSES];
-    // coloff(r4) -> ELEMENT offset of the (clamped) 4-column group r4 within a row; ld = row pitch in elements
+    // coloff(r) -> ELEMENT offset within a row of the (clamped) W-column group that starts at column r; ld = row pitch in elements
     template <typename ColOff>
     __device__ __forceinline__ void prepare(ColOff coloff, unsigned ld)
     {
 #pragma unroll
         for (int p = 0; p < PASSES; ++p) {
-            const int e = threadIdx.x + p * NT;
+            const int e = threadIdx.x + p * DG_THREADS;
             const int tl = EXACT ? e / Q : min(e / Q, 31);
-            off[p] = ((unsigned)tl * ld + (unsigned)coloff(e % Q)) * 4u;
+            off[p] = ((unsigned)tl * ld + (unsigned)coloff((e % Q) * W)) * 4u;
         }
     }
     static __device__ __forceinline__ const float *stage_base(const float *g, unsigned ld, int t0) { return g + (int64_t)t0 * ld; }
-    static __device__ __forceinline__ unsigned stage_limit(unsigned total, unsigned ld, int t0) { return (total - 4u - (unsigned)t0 * ld) * 4u; }
+    static __device__ __forceinline__ unsigned stage_limit(unsigned total, unsigned ld, int t0) { return (total - W - (unsigned)t0 * ld) * 4u; }
     template <int SET>
-    __device__ __forceinline__ void issue_pass(int p, const float *base, unsigned limit) { v[SET][p] = ldg4(base, min(off[p], limit)); }
+    __device__ __forceinline__ void issue_pass(int p, const float *base, unsigned limit) { v[SET][p] = ldg<W>(base, min(off[p], limit)); }
     template <bool ZERO, int SET>
     __device__ __forceinline__ void store_pass(int p, float *lds, int t0, int tmax) const
     {
         // past the panel's last row (EXACT == false) the thread holds a copy of row 31's element (prepare clamps): it stores the
         // same value to the same address -- no branch inside the MFMA stream
-        const int e = threadIdx.x + p * NT;
-        const int tl = EXACT ? e / Q : min(e / Q, 31), r4 = e % Q;
-        f32x4 x = v[SET][p];
-        if (ZERO && !(t0 + tl < tmax)) x = (f32x4){0.f, 0.f, 0.f, 0.f};
-        *reinterpret_cast<f32x4 *>(lds + tl * ld_rc(R) + r4 * 4) = x;
-    }
-};
-
-// RC panel, 4-byte loads along r (963-wide rows): element e = thread + NT * p of the 32 x R grid
-template <int R, int NT = DG_THREADS>
-struct PanelRCs {
-    static constexpr int PASSES = (32 * R + NT - 1) / NT;
-    static constexpr bool EXACT = (32 * R) % NT == 0;
-    static constexpr int WIDTH = 1;
-    float v[2][PASSES];
-    unsigned off[PASSES];
-    template <typename ColOff>
-    __device__ __forceinline__ void prepare(ColOff coloff, unsigned ld)
-    {
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            const int e = threadIdx.x + p * NT;
-            const int tl = EXACT ? e / R : min(e / R, 31);
-            off[p] = ((unsigned)tl * ld + (unsigned)coloff(e % R)) * 4u;
-        }
-    }
-    static __device__ __forceinline__ const float *stage_base(const float *g, unsigned ld, int t0) { return g + (int64_t)t0 * ld; }
-    static __device__ __forceinline__ unsigned stage_limit(unsigned total, unsigned ld, int t0) { return (total - 1u - (unsigned)t0 * ld) * 4u; }
-    template <int SET>
-    __device__ __forceinline__ void issue_pass(int p, const float *base, unsigned limit) { v[SET][p] = ldg(base, min(off[p], limit)); }
-    template <bool ZERO, int SET>
-    __device__ __forceinline__ void store_pass(int p, float *lds, int t0, int tmax) const
-    {
-        const int e = threadIdx.x + p * NT;
-        const int tl = EXACT ? e / R : min(e / R, 31), r = e % R;      // (clamped duplicates: see PanelRCv)
-        lds[tl * ld_rc(R) + r] = (!ZERO || t0 + tl < tmax) ? v[SET][p] : 0.f;
+        const int e = threadIdx.x + p * DG_THREADS;
+        const int tl = EXACT ? e / Q : min(e / Q, 31);
+        ldg_t<W> x = v[SET][p];
+        if (ZERO && !(t0 + tl < tmax)) x = ldg_t<W>{};
+        *reinterpret_cast<ldg_t<W> *>(lds + tl * ld_rc(R) + (e % Q) * W) = x;
     }
 };
 
@@ -267,26 +233,16 @@ __device__ __forceinline__ void gemm_stage(const float *cur, float *wr, f32x4 (&
 #pragma unroll
     for (int s = 0; s < DG_KS; ++s) {
         // fragments of the next k-step (of the next stage after the last one)
-#ifndef DG_PROBE_NO_FETCH
-        if (s + 1 < DG_KS) fetch_frags<RB, NCW, A_TC, B_TC, RA, RBW, EXTRA>(f, (s + 1) & 1, cur, cur + A_FLOATS, s + 1, wave, xcb);
-        else fetch_frags<RB, NCW, A_TC, B_TC, RA, RBW, EXTRA>(f, 0, wr, wr + A_FLOATS, 0, wave, xcb);
-#endif
+        if (DG_FETCH && s + 1 < DG_KS) fetch_frags<RB, NCW, A_TC, B_TC, RA, RBW, EXTRA>(f, (s + 1) & 1, cur, cur + A_FLOATS, s + 1, wave, xcb);
+        else if (DG_FETCH) fetch_frags<RB, NCW, A_TC, B_TC, RA, RBW, EXTRA>(f, 0, wr, wr + A_FLOATS, 0, wave, xcb);
         // this k-step's share of the staging work
-#ifdef DG_PROBE_NO_ISSUE
-        if (false) {
-#else
-        if (s < 4) {
-#endif
+        if (DG_ISSUE && s < 4) {
 #pragma unroll
             for (int u = s * U / 4; u < (s + 1) * U / 4; ++u) {
                 if (u < PA::PASSES) pa.template issue_pass<SET>(u, io.a_base, io.a_limit);
                 else pb.template issue_pass<SET>(u - PA::PASSES, io.b_base, io.b_limit);
             }
-#ifdef DG_PROBE_NO_STORE
-        } else if (false) {
-#else
-        } else if (s < 7) {
-#endif
+        } else if (DG_STORE && s >= 4 && s < 7) {
 #pragma unroll
             for (int u = (s - 4) * U / 3; u < (s - 3) * U / 3; ++u) {
                 if (u < PA::PASSES) pa.template store_pass<true, SET ^ 1>(u, wr, io.st_t0, io.st_tmax);
@@ -313,9 +269,7 @@ __device__ __forceinline__ void gemm_stage(const float *cur, float *wr, f32x4 (&
         }
         __builtin_amdgcn_sched_barrier(0);
         if (s == 6) {
-#ifndef DG_PROBE_NO_BARRIER
-            __syncthreads(); // `wr` is complete; its first fragments are requested in the next k-step
-#endif
+            if (DG_BARRIER) __syncthreads(); // `wr` is complete; its first fragments are requested in the next k-step
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -369,8 +323,8 @@ __device__ __forceinline__ void rows_body(const RowArgs &q, float *lds, const in
     const int total = my_tiles * q.n_chunks * nst;
     if (total == 0) return;
 
-    typedef typename std::conditional<A_VEC, PanelTCv<RAL>, PanelTCs<RAL>>::type PA;
-    typedef typename std::conditional<B_TC, PanelTCv<CW>, PanelRCv<CW>>::type PB;
+    typedef PanelTC<RAL, A_VEC ? 4 : 1> PA;
+    typedef typename std::conditional<B_TC, PanelTC<CW, 4>, PanelRC<CW, 4>>::type PB;
     PA pa;
     PB pb;
     const unsigned a_total = (unsigned)q.I * (unsigned)q.lda;
@@ -391,7 +345,7 @@ __device__ __forceinline__ void rows_body(const RowArgs &q, float *lds, const in
         if constexpr (B_TC) {
             pb.prepare([=](int r) -> unsigned { const int j = j0 + r; return (unsigned)(j < q.J ? j : q.J - 1) * (unsigned)q.ldb; }, (unsigned)q.ldb);
         } else {
-            pb.prepare([=](int r4) -> unsigned { const int j = j0 + r4 * 4; return (unsigned)(j < q.J ? j : q.J - 4); }, (unsigned)q.ldb);
+            pb.prepare([=](int r) -> unsigned { const int j = j0 + r; return (unsigned)(j < q.J ? j : q.J - 4); }, (unsigned)q.ldb);
         }
     };
     StageIO io;
@@ -577,13 +531,9 @@ struct SplitArgs {
 // stages x 8 k-steps: the slot a k-step has just consumed is refilled at once with the same k-step of the stage after
 // next.  Measured before (probe builds with the LDS traffic removed): the G panel's LDS writes + fragment reads were ~15 of
 // the first layer's 77 us.
-// KP = k-parts: with KP == 2 the workgroup has EIGHT waves, two per SIMD -- wave v and wave v + 4 own the same 48 output
-// columns and share the X panel, the first takes the even k-steps of every stage, the second the odd ones, each into its
-// own accumulators (added up through LDS at the end: split_body).  One wave per SIMD cannot hide its own stalls (fragment
-// reads, the stage barrier, s_waitcnt in front of the LDS stores): PMC showed the matrix pipe 64-73 % busy with one wave;
-// two waves on a SIMD issue into each other's gaps.  A wave then runs KS = 8 / KP k-steps per stage: loads of the stage
-// after next in its first KS/2 steps, LDS stores in the following ones, barrier behind step KS - 2, the first fragments of
-// the next stage requested in the last step.
+// Tried and removed: a second wave per SIMD ("k-parts": eight waves, the partner taking the odd k-steps, sums exchanged through
+// LDS).  66.8 us against 65.7 -- the launch is 50 us of MFMA issue + ~9.5 us of launch, first loads and the burst of partial
+// tiles whatever else is removed (profiles/r04_split_kernel_ablation.txt; the code is in the history of this file).
 // X fragments of one k-step with WIDE LDS reads: the tile's rows are dealt to the MFMA row-blocks so that a lane's RB
 // fragment values are neighbours in the [t][r] panel -- lane x of row-blocks 4q .. 4q+3 holds rows 64q + 4x + {0,1,2,3} (one
 // ds_read_b128), a remaining pair rows 2x + {0,1} (ds_read_b64), a remaining single row x.  Which row an accumulator holds
@@ -615,38 +565,31 @@ __device__ __forceinline__ void split_frags(float (&f)[RB], const float *row, in
     if constexpr (N1 == 1) f[RB - 1] = row[64 * N4 + 32 * N2 + x];
 }
 
-template <int RB, int RA, int A_FLOATS, int SET, int KP, class PA, class Tail>
-__device__ __forceinline__ void split_stage(const float *cur, float *wr, f32x4 (&acc)[RB][3], float (&fa)[2][RB], f3u (&bq)[2][DG_KS / KP],
-                                            PA &pa, const StageIO &io, unsigned b_lane, unsigned b_step, int kpart, Tail tail)
+// gemm_stage's schedule (fragments of the next k-step first, loads in k-steps 0-3, LDS stores in 4-6, barrier behind 6, tail() in
+// the last one) over this product's fragments, MFMAs and G refill.  The two loops stay two: run from one skeleton they keep every
+// instruction count but not the register allocation of the pair and the wide split kernels (profiles/dense_gemm_resources.txt).
+template <int RB, int RA, int A_FLOATS, int SET, class PA, class Tail>
+__device__ __forceinline__ void split_stage(const float *cur, float *wr, f32x4 (&acc)[RB][3], float (&fa)[2][RB], f3u (&bq)[2][DG_KS],
+                                            PA &pa, const StageIO &io, unsigned b_lane, unsigned b_step, Tail tail)
 {
     constexpr int U = PA::PASSES;
-    constexpr int KS = DG_KS / KP;             // k-steps of this wave per stage
-    constexpr int LOADS = KS / 2;              // steps [0, LOADS): issue the loads; [LOADS, KS - 1): LDS stores
+    constexpr int KS = DG_KS;
+    constexpr int LOADS = KS / 2; // steps [0, LOADS): issue the loads; [LOADS, KS - 1): LDS stores
     constexpr int STORES = KS - 1 - LOADS;
     const int x = threadIdx.x & 15, g = (threadIdx.x >> 4) & 3;
     const float *b_base = io.b_base; // by value: `tail` re-aims io in the last k-step, the refills below belong to this aim
     const unsigned b_limit = io.b_limit;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-#ifndef DG_PROBE_NO_FETCH
-        { // X fragments of this wave's next k-step (of the next stage after the last one): global k-step KP * s' + kpart
+        if (DG_FETCH) { // X fragments of the next k-step (of the next stage after the last one)
             const float *src = s + 1 < KS ? cur : wr;
-            const int sn = (s + 1 < KS ? KP * (s + 1) : 0) + kpart;
+            const int sn = s + 1 < KS ? s + 1 : 0;
             split_frags<RB>(fa[(s + 1) & 1], src + (4 * sn + g) * ld_rc(RA), x);
         }
-#endif
-#ifdef DG_PROBE_NO_ISSUE
-        if (false) {
-#else
-        if (s < LOADS) {
-#endif
+        if (DG_ISSUE && s < LOADS) {
 #pragma unroll
             for (int u = s * U / LOADS; u < (s + 1) * U / LOADS; ++u) pa.template issue_pass<SET>(u, io.a_base, io.a_limit);
-#ifdef DG_PROBE_NO_STORE
-        } else if (false) {
-#else
-        } else if (s < KS - 1) {
-#endif
+        } else if (DG_STORE && s >= LOADS && s < KS - 1) {
 #pragma unroll
             for (int u = (s - LOADS) * U / STORES; u < (s - LOADS + 1) * U / STORES; ++u)
                 pa.template store_pass<true, SET ^ 1>(u, wr, io.st_t0, io.st_tmax);
@@ -659,9 +602,7 @@ __device__ __forceinline__ void split_stage(const float *cur, float *wr, f32x4 (
             acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.y, fa[s & 1][i], acc[i][1], 0, 0, 0);
             acc[i][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.z, fa[s & 1][i], acc[i][2], 0, 0, 0);
         }
-#ifndef DG_PROBE_NO_G
-        bq[SET][s] = ldg3(b_base, min(b_lane + (unsigned)(KP * s) * b_step, b_limit)); // the same k-step of the stage after next
-#endif
+        if (DG_G) bq[SET][s] = ldg<3>(b_base, min(b_lane + (unsigned)s * b_step, b_limit)); // the same k-step of the stage after next
 #pragma unroll
         for (int m = 0; m < RB * 3; ++m) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); // MFMA
@@ -672,25 +613,21 @@ __device__ __forceinline__ void split_stage(const float *cur, float *wr, f32x4 (
         }
         __builtin_amdgcn_sched_barrier(0);
         if (s == KS - 2) {
-#ifndef DG_PROBE_NO_BARRIER
-            __syncthreads();
-#endif
+            if (DG_BARRIER) __syncthreads();
             __builtin_amdgcn_sched_barrier(0);
         }
     }
 }
 
-template <int RB, int RBP, bool A_VEC, int KP = 1>
+template <int RB, int RBP, bool A_VEC>
 __device__ __forceinline__ void split_body(const SplitArgs &q, float *lds, int i0, int split, int nsplit, int slot, bool want_cs)
 {
     constexpr int RA = RB * 16;
     constexpr int CW = 192;
     constexpr int A_FLOATS = 32 * ld_rc(RA);
     constexpr int BUF = A_FLOATS;
-    constexpr int NT = DG_THREADS * KP;
-    constexpr int KS = DG_KS / KP;
-    const int wave = (threadIdx.x >> 6) & 3;     // which 48 output columns
-    const int kpart = KP == 1 ? 0 : (int)(threadIdx.x >> 8); // which k-steps of a stage (waves v and v + 4 share a SIMD)
+    constexpr int KS = DG_KS;
+    const int wave = threadIdx.x >> 6; // which 48 output columns
     const int x = threadIdx.x & 15, g = (threadIdx.x >> 4) & 3;
     // rows of the summed dimension in units of 4 (one MFMA k-step); T % 4 != 0 is zero-filled by the X loader
     const int n4 = (q.T + 3) / 4;
@@ -705,17 +642,15 @@ __device__ __forceinline__ void split_body(const SplitArgs &q, float *lds, int i
         for (int j = 0; j < 3; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float cs0 = 0.f, cs1 = 0.f, cs2 = 0.f; // column sums of G over this split's rows == g (mod 4), columns 48*wave + 3x ..
 
-    typedef typename std::conditional<A_VEC, PanelRCv<RA, NT>, PanelRCs<RA, NT>>::type PA;
+    typedef PanelRC<RA, A_VEC ? 4 : 1> PA;
     PA pa;
     if (nst > 0) {
-        if constexpr (A_VEC) pa.prepare([=](int r4) -> unsigned { const int i = i0 + r4 * 4; return (unsigned)(i + 3 < q.I ? i : q.I - 4); }, (unsigned)q.lda);
-        else pa.prepare([=](int r) -> unsigned { const int i = i0 + r; return (unsigned)(i < q.I ? i : q.I - 1); }, (unsigned)q.lda);
+        pa.prepare([=](int r) -> unsigned { const int i = i0 + r; return (unsigned)(i + PA::WIDTH - 1 < q.I ? i : q.I - PA::WIDTH); }, (unsigned)q.lda);
         const unsigned a_total = (unsigned)q.T * (unsigned)q.lda, b_total = (unsigned)q.T * (unsigned)q.ldb;
-        // G: this lane's 12 bytes of row g of a k-step, columns clamped into the row (J % 4 == 0 but maybe not % 3); the wave's
-        // first k-step of a stage is k-step `kpart`
+        // G: this lane's 12 bytes of row g of a k-step, columns clamped into the row (J % 4 == 0 but maybe not % 3)
         const int jc = min(wave * 48 + 3 * x, q.J - 3);
         const unsigned b_step = 4u * (unsigned)q.ldb * 4u; // four rows per k-step
-        const unsigned b_lane = ((unsigned)g * (unsigned)q.ldb + (unsigned)jc) * 4u + (unsigned)kpart * b_step;
+        const unsigned b_lane = ((unsigned)g * (unsigned)q.ldb + (unsigned)jc) * 4u;
         StageIO io;
         int l_st = 0;
         auto aim = [&]() {
@@ -733,21 +668,21 @@ __device__ __forceinline__ void split_body(const SplitArgs &q, float *lds, int i
 #pragma unroll
         for (int p = 0; p < PA::PASSES; ++p) pa.template issue_pass<0>(p, io.a_base, io.a_limit);
 #pragma unroll
-        for (int s = 0; s < KS; ++s) bq[0][s] = ldg3(io.b_base, min(b_lane + (unsigned)(KP * s) * b_step, io.b_limit));
+        for (int s = 0; s < KS; ++s) bq[0][s] = ldg<3>(io.b_base, min(b_lane + (unsigned)s * b_step, io.b_limit));
         advance();
         aim();
         io.st_t0 = t_begin + l_st * DG_BK;
 #pragma unroll
         for (int p = 0; p < PA::PASSES; ++p) pa.template issue_pass<1>(p, io.a_base, io.a_limit);
 #pragma unroll
-        for (int s = 0; s < KS; ++s) bq[1][s] = ldg3(io.b_base, min(b_lane + (unsigned)(KP * s) * b_step, io.b_limit));
+        for (int s = 0; s < KS; ++s) bq[1][s] = ldg<3>(io.b_base, min(b_lane + (unsigned)s * b_step, io.b_limit));
 #pragma unroll
         for (int p = 0; p < PA::PASSES; ++p) pa.template store_pass<true, 0>(p, lds, t_begin, t_end);
         advance();
         aim();
         io.st_tmax = t_end;
         __syncthreads();
-        split_frags<RB>(fa[0], lds + (4 * kpart + g) * ld_rc(RA), x);
+        split_frags<RB>(fa[0], lds + g * ld_rc(RA), x);
         int buf = 0;
         auto tail = [&]() {
             io.st_t0 = t_begin + l_st * DG_BK;
@@ -758,10 +693,10 @@ __device__ __forceinline__ void split_body(const SplitArgs &q, float *lds, int i
         // rows of G beyond t_end belong to the next split (their X factors are zero-filled): the bias gradient counts only
         // this split's rows
         auto colsum_stage = [&](const f3u (&b)[KS], int st) {
-            const int t0 = t_begin + st * DG_BK + g + 4 * kpart;
+            const int t0 = t_begin + st * DG_BK + g;
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
-                const bool in = t0 + 4 * KP * s < t_end;
+                const bool in = t0 + 4 * s < t_end;
                 cs0 += in ? b[s].x : 0.f, cs1 += in ? b[s].y : 0.f, cs2 += in ? b[s].z : 0.f;
             }
         };
@@ -770,49 +705,15 @@ __device__ __forceinline__ void split_body(const SplitArgs &q, float *lds, int i
                 const float *cur = lds + buf * BUF;
                 float *wr = lds + (buf ^ 1) * BUF;
                 if (want_cs) colsum_stage(bq[0], st);
-                split_stage<RB, RA, A_FLOATS, 0, KP>(cur, wr, acc, fa, bq, pa, io, b_lane, b_step, kpart, tail);
+                split_stage<RB, RA, A_FLOATS, 0>(cur, wr, acc, fa, bq, pa, io, b_lane, b_step, tail);
             }
             if (st + 1 < nst) {
                 const float *cur = lds + buf * BUF;
                 float *wr = lds + (buf ^ 1) * BUF;
                 if (want_cs) colsum_stage(bq[1], st + 1);
-                split_stage<RB, RA, A_FLOATS, 1, KP>(cur, wr, acc, fa, bq, pa, io, b_lane, b_step, kpart, tail);
+                split_stage<RB, RA, A_FLOATS, 1>(cur, wr, acc, fa, bq, pa, io, b_lane, b_step, tail);
             }
         }
-    }
-    if constexpr (KP == 2) {
-        // the odd k-steps' accumulators (and column sums) go to their even partners through LDS, lane for lane: float4
-        // (wave, i, u) of lane l at [((wave * H + i') * 3 + u) * 64 + l] -- 1 KB contiguous per wave instruction -- H = 2
-        // row-blocks per round, so that the exchange needs no more LDS than the kernel's two panels hold
-        constexpr int H = 2;
-        static_assert(DG_WAVES * H * 3 * 64 * 4 <= 2 * 32 * ld_rc(RBP * 16), "the exchange reuses the panel buffers");
-        f32x4 *xch = reinterpret_cast<f32x4 *>(lds);
-        const int l = threadIdx.x & 63;
-#pragma unroll
-        for (int i0r = 0; i0r < RB; i0r += H) {
-            __syncthreads(); // the panels (first round) / the partners' reads of the previous round are done
-            if (kpart == 1) {
-#pragma unroll
-                for (int i = i0r; i < RB && i < i0r + H; ++i)
-#pragma unroll
-                    for (int u = 0; u < 3; ++u) xch[((wave * H + (i - i0r)) * 3 + u) * 64 + l] = acc[i][u];
-            }
-            __syncthreads();
-            if (kpart == 0) {
-#pragma unroll
-                for (int i = i0r; i < RB && i < i0r + H; ++i)
-#pragma unroll
-                    for (int u = 0; u < 3; ++u) acc[i][u] = acc[i][u] + xch[((wave * H + (i - i0r)) * 3 + u) * 64 + l];
-            }
-        }
-        if (want_cs) {
-            __syncthreads();
-            float *xf = lds;
-            if (kpart == 1) xf[(wave * 3 + 0) * 64 + l] = cs0, xf[(wave * 3 + 1) * 64 + l] = cs1, xf[(wave * 3 + 2) * 64 + l] = cs2;
-            __syncthreads();
-            if (kpart == 0) cs0 += xf[(wave * 3 + 0) * 64 + l], cs1 += xf[(wave * 3 + 1) * 64 + l], cs2 += xf[(wave * 3 + 2) * 64 + l];
-        }
-        if (kpart == 1) return;
     }
     // partial tile: the lane's twelve consecutive columns of row 16 i + x
     float *dst = q.part + (int64_t)slot * (RBP * 16) * CW;
@@ -845,32 +746,25 @@ __device__ __forceinline__ void split_body(const SplitArgs &q, float *lds, int i
 
 // A_VEC: the leftover row-blocks may use 16-byte loads too (I % 4 == 0).  FULL tiles always do: their column groups never
 // reach the end of a row, so 4-byte alignment is all they need (the 963-float rows of the first layer's features).
-template <int RB, int NCW, bool A_VEC, int KP = 1>
+template <int RB, int NCW, bool A_VEC>
 __device__ __forceinline__ void split_dispatch(const SplitArgs &q, float *lds, const int w)
 {
     static_assert(NCW == 3, "the split body owns 48 columns per wave");
     const int nfull = q.full_tiles * q.s_full;
     if (w < nfull) {
         const int tile = w % q.full_tiles, split = w / q.full_tiles;
-        split_body<RB, RB, true, KP>(q, lds, tile * RB * 16, split, q.s_full, tile * q.s_full + split,
-                                     q.colsum != nullptr && tile == 0);
+        split_body<RB, RB, true>(q, lds, tile * RB * 16, split, q.s_full, tile * q.s_full + split, q.colsum != nullptr && tile == 0);
     } else {
         const int e = (w - nfull) / q.s_left, split = (w - nfull) % q.s_left;
-        split_body<1, RB, A_VEC, KP>(q, lds, (q.full_tiles * RB + e) * 16, split, q.s_left, w, false);
+        split_body<1, RB, A_VEC>(q, lds, (q.full_tiles * RB + e) * 16, split, q.s_left, w, false);
     }
 }
 
-// KP = 2: eight waves per workgroup, see split_stage -- built for the stand-alone launch of the 963-wide first layer (one
-// workgroup per CU) on the suspicion that a single wave per SIMD leaves the matrix pipe idle during its own stalls.  The
-// ablation says otherwise (tools/probe/run_probes.sh, profiles/r04_split_kernel_ablation.txt): with EVERYTHING but the
-// MFMAs removed from the loop the launch still takes 59.5 us of its 65.7 -- 50 us of MFMA issue at the full 2.39 GHz the chip
-// holds under this kernel + ~9.5 us of launch, first loads and the 18.5 MB burst of partial tiles at the end -- and a
-// second wave per SIMD changes nothing (66.8).  Kept as a build option (-DDG_SPLIT_KP=2), the shipped value is 1.
-template <int RB, int NCW, bool A_VEC, int KP>
-__global__ __launch_bounds__(DG_THREADS * KP) void dense_split_kernel(SplitArgs q)
+template <int RB, int NCW, bool A_VEC>
+__global__ __launch_bounds__(DG_THREADS) void dense_split_kernel(SplitArgs q)
 {
     __shared__ __attribute__((aligned(16))) float lds[2 * 32 * ld_rc(RB * 16)];
-    split_dispatch<RB, NCW, A_VEC, KP>(q, lds, blockIdx.x);
+    split_dispatch<RB, NCW, A_VEC>(q, lds, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -926,11 +820,10 @@ struct ReduceAdam {
 constexpr int RED_THREADS = 256;
 inline int reduce_outs(int slots) { return slots <= 32 ? 64 : slots <= 64 ? 32 : slots <= 128 ? 16 : slots <= 256 ? 8 : 4; }
 // workgroup `block` of `nblocks` of a reduction; part = RED_THREADS f32x4 of LDS, st = 3 floats of LDS
-template <bool ADAM> // false: no optimiser step (`adam` is not touched: a by-value ReduceAdam indexed by job lives in scratch)
 __device__ __forceinline__ void reduce_body(const ReduceJobs &jobs, const ReduceAdam &adam, const int block, const int nblocks,
                                             f32x4 *part, float *st)
 {
-    float *const state = ADAM ? adam.state : nullptr;
+    float *const state = adam.state; // null: no optimiser step
     // flat grid: every workgroup holds outputs (a job smaller than the largest one used to leave whole workgroups idle:
     // 5 800 of 8 670 at the BASELINE shard)
     int jb = 0;
@@ -1029,7 +922,7 @@ __global__ __launch_bounds__(RED_THREADS) void dense_reduce_kernel(ReduceJobs jo
 {
     __shared__ f32x4 part[RED_THREADS];
     __shared__ float st[3];
-    reduce_body<true>(jobs, adam, blockIdx.x, gridDim.x, part, st);
+    reduce_body(jobs, adam, blockIdx.x, gridDim.x, part, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1071,62 +964,40 @@ RowGeo row_geometry(int rows, int ncw, int cus)
     return best;
 }
 
+// launch(std::integral_constant<int, RB>) for the run-time rb in [LO, HI]: the one place a tile height becomes a template argument
+template <int LO, int HI, class Launch>
+int dispatch_rb(int rb, Launch launch)
+{
+    if constexpr (LO <= HI) {
+        if (rb != LO) return dispatch_rb<LO + 1, HI>(rb, launch);
+        launch(std::integral_constant<int, LO>{});
+        return geom::launch_status();
+    } else {
+        return GEOM_EINVAL;
+    }
+}
+
 template <int NCW, bool B_TC, bool A_VEC, int EPI>
 int launch_rows_rb(const RowArgs &q, const RowGeo &geo, hipStream_t s)
 {
-    const dim3 grid(geo.grid), block(DG_THREADS);
-    switch (geo.rb) {
-    case 1: hipLaunchKernelGGL((dense_rows_kernel<1, NCW, B_TC, A_VEC, EPI>), grid, block, 0, s, q); break;
-    case 2: hipLaunchKernelGGL((dense_rows_kernel<2, NCW, B_TC, A_VEC, EPI>), grid, block, 0, s, q); break;
-    case 3: hipLaunchKernelGGL((dense_rows_kernel<3, NCW, B_TC, A_VEC, EPI>), grid, block, 0, s, q); break;
-    case 4: hipLaunchKernelGGL((dense_rows_kernel<4, NCW, B_TC, A_VEC, EPI>), grid, block, 0, s, q); break;
-    case 5: hipLaunchKernelGGL((dense_rows_kernel<5, NCW, B_TC, A_VEC, EPI>), grid, block, 0, s, q); break;
-    case 6: hipLaunchKernelGGL((dense_rows_kernel<6, NCW, B_TC, A_VEC, EPI>), grid, block, 0, s, q); break;
-    default: return GEOM_EINVAL;
-    }
-    return geom::launch_status();
+    return dispatch_rb<1, 6>(geo.rb, [&](auto rb) {
+        hipLaunchKernelGGL((dense_rows_kernel<decltype(rb)::value, NCW, B_TC, A_VEC, EPI>), dim3(geo.grid), dim3(DG_THREADS), 0, s, q);
+    });
 }
 
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
-} // namespace
-
-// support = x . w (+ the 0N-GCN pass-through epilogue)
-extern "C" int geom_dense_fwd_f32(int rows, int cin, int c, const float *x, const float *w, int ksplit, const float *bias,
-                                  float *out, float *sup, uint16_t *mask, void *stream)
+// the operands of an input gradient  grad_x = g . w^T  on row tiles of `geo`, NCW*64 columns per chunk
+RowArgs input_gradient_args(int rows, int cin, int c, const float *g, const float *w, float *grad_x, int ncw, const RowGeo &geo)
 {
-    if (rows < 0 || cin <= 0 || c <= 0) return GEOM_EINVAL;
-    if (c % 16 != 0 || c > 192 || (int64_t)rows * cin >= (1LL << 30)) return GEOM_EUNSUPPORTED;
-    if (rows == 0) return 0;
-    if (!x || !w || !out || !aligned16(w) || !aligned16(out)) return GEOM_EINVAL;
-    const bool zn = ksplit > 0;
-    if (zn && (ksplit % 16 != 0 || ksplit >= c || !sup || !aligned16(sup) || (bias && !aligned16(bias)))) return GEOM_EINVAL;
-    const RowGeo geo = row_geometry(rows, 3, num_cus());
-    RowArgs q{x, cin, w, c, out, c, rows, c, cin, geo.n_tiles, geo.left_rb, 1, zn ? ksplit : 0, sup, bias, mask};
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool avec = cin % 4 == 0 && aligned16(x);
-    if (zn) return avec ? launch_rows_rb<3, false, true, EPI_ZN>(q, geo, s) : launch_rows_rb<3, false, false, EPI_ZN>(q, geo, s);
-    return avec ? launch_rows_rb<3, false, true, EPI_PLAIN>(q, geo, s) : launch_rows_rb<3, false, false, EPI_PLAIN>(q, geo, s);
+    return RowArgs{g, c, w, c, grad_x, cin, rows, cin, c, geo.n_tiles, geo.left_rb, (cin + ncw * 64 - 1) / (ncw * 64), 0, nullptr,
+                   nullptr, nullptr};
 }
 
-// grad_x = g . w^T   (g [rows, c], w [cin, c], grad_x [rows, cin])
-extern "C" int geom_dense_bwd_input_f32(int rows, int cin, int c, const float *g, const float *w, float *grad_x, void *stream)
-{
-    if (rows < 0 || cin <= 0 || c <= 0) return GEOM_EINVAL;
-    if (c % 4 != 0 || (int64_t)rows * (cin > c ? cin : c) >= (1LL << 30)) return GEOM_EUNSUPPORTED;
-    if (rows == 0) return 0;
-    if (!g || !w || !grad_x || !aligned16(g) || !aligned16(w)) return GEOM_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int ncw = cin > 192 ? 4 : 3;
-    const RowGeo geo = row_geometry(rows, ncw, num_cus());
-    RowArgs q{g, c, w, c, grad_x, cin, rows, cin, c, geo.n_tiles, geo.left_rb, (cin + ncw * 64 - 1) / (ncw * 64), 0, nullptr,
-              nullptr, nullptr};
-    return ncw == 4 ? launch_rows_rb<4, true, true, EPI_PLAIN>(q, geo, s) : launch_rows_rb<3, true, true, EPI_PLAIN>(q, geo, s);
-}
-
-namespace {
 struct SplitGeo {
     int rb, full_tiles, left_rb, s_full, s_left, slots;
+    int64_t partial_floats() const { return (int64_t)slots * rb * 16 * 192; } // [slots][rb*16][192]
+    int64_t colsum_offset() const { return partial_floats(); }               // the [s_full][c] column sums follow the tiles
 };
 // Tile height of a weight gradient's partial sums.  The workgroup count is fixed by the chip (one per CU), so tiles x splits
 // ~ 256 and the bytes of partial tiles written here and read back by the reduction launch are splits x (cin x c x 4): the
@@ -1157,38 +1028,86 @@ SplitGeo split_geometry(int cin, int rows, int cus)
     g.slots = g.full_tiles * g.s_full + g.left_rb * g.s_left;
     return g;
 }
+
+// the operands of the partial sums of  grad_w = x^T . g  into `workspace`, split as `geo` says
+SplitArgs split_args(int rows, int cin, int c, const float *x, const float *g, float *workspace, bool want_colsum, const SplitGeo &geo)
+{
+    return SplitArgs{x, cin, g, c, workspace, cin, c, rows, geo.full_tiles, geo.s_full, geo.left_rb, geo.s_left,
+                     want_colsum ? workspace + geo.colsum_offset() : nullptr};
+}
+
+// The argument checks of the three backward entries; `dx` / `dw`: which gradients the entry computes.  0 with rows == 0 (an
+// input gradient alone may have no rows): nothing to launch, and the pointers are not looked at.
+int check_backward(bool dx, bool dw, int rows, int cin, int c, const float *x, const float *g, const float *w, const float *grad_x,
+                   const float *workspace)
+{
+    if (rows < (dw ? 1 : 0) || cin <= 0 || c <= 0) return GEOM_EINVAL;
+    // c % 12: a lane owns whole 3-column groups of G (12-byte loads) and whole 4-column groups of the partial tile
+    if ((dw ? c % 12 != 0 || c > 192 : c % 4 != 0) || (int64_t)rows * (cin > c ? cin : c) >= (1LL << 30)) return GEOM_EUNSUPPORTED;
+    if (rows == 0) return 0;
+    if (!g || !aligned16(g)) return GEOM_EINVAL;
+    if (dx && (!w || !grad_x || !aligned16(w))) return GEOM_EINVAL;
+    if (dw && (!x || !workspace || !aligned16(workspace))) return GEOM_EINVAL;
+    return 0;
+}
+
 } // namespace
+
+// support = x . w (+ the 0N-GCN pass-through epilogue)
+extern "C" int geom_dense_fwd_f32(int rows, int cin, int c, const float *x, const float *w, int ksplit, const float *bias,
+                                  float *out, float *sup, uint16_t *mask, void *stream)
+{
+    if (rows < 0 || cin <= 0 || c <= 0) return GEOM_EINVAL;
+    if (c % 16 != 0 || c > 192 || (int64_t)rows * cin >= (1LL << 30)) return GEOM_EUNSUPPORTED;
+    if (rows == 0) return 0;
+    if (!x || !w || !out || !aligned16(w) || !aligned16(out)) return GEOM_EINVAL;
+    const bool zn = ksplit > 0;
+    if (zn && (ksplit % 16 != 0 || ksplit >= c || !sup || !aligned16(sup) || (bias && !aligned16(bias)))) return GEOM_EINVAL;
+    const RowGeo geo = row_geometry(rows, 3, num_cus());
+    RowArgs q{x, cin, w, c, out, c, rows, c, cin, geo.n_tiles, geo.left_rb, 1, zn ? ksplit : 0, sup, bias, mask};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool avec = cin % 4 == 0 && aligned16(x);
+    if (zn) return avec ? launch_rows_rb<3, false, true, EPI_ZN>(q, geo, s) : launch_rows_rb<3, false, false, EPI_ZN>(q, geo, s);
+    return avec ? launch_rows_rb<3, false, true, EPI_PLAIN>(q, geo, s) : launch_rows_rb<3, false, false, EPI_PLAIN>(q, geo, s);
+}
+
+// grad_x = g . w^T   (g [rows, c], w [cin, c], grad_x [rows, cin])
+extern "C" int geom_dense_bwd_input_f32(int rows, int cin, int c, const float *g, const float *w, float *grad_x, void *stream)
+{
+    const int code = check_backward(true, false, rows, cin, c, nullptr, g, w, grad_x, nullptr);
+    if (code || rows == 0) return code;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int ncw = cin > 192 ? 4 : 3;
+    const RowGeo geo = row_geometry(rows, ncw, num_cus());
+    const RowArgs q = input_gradient_args(rows, cin, c, g, w, grad_x, ncw, geo);
+    return ncw == 4 ? launch_rows_rb<4, true, true, EPI_PLAIN>(q, geo, s) : launch_rows_rb<3, true, true, EPI_PLAIN>(q, geo, s);
+}
 
 extern "C" int64_t geom_dense_bwd_weight_workspace_floats(int rows, int cin, int c)
 {
     if (rows <= 0 || cin <= 0 || c <= 0 || c > 192) return 0;
     const SplitGeo g = split_geometry(cin, rows, num_cus());
-    return (int64_t)g.slots * g.rb * 16 * 192 + (int64_t)(g.s_full > 0 ? g.s_full : g.s_left) * c;
+    return g.partial_floats() + (int64_t)(g.s_full > 0 ? g.s_full : g.s_left) * c;
 }
 
 // partial sums of grad_w = x^T . g into `workspace`; geom_dense_reduce_f32 finishes them (and the bias gradient)
 extern "C" int geom_dense_bwd_weight_f32(int rows, int cin, int c, const float *x, const float *g, float *workspace,
                                          int want_colsum, void *stream)
 {
-    if (rows <= 0 || cin <= 0 || c <= 0) return GEOM_EINVAL;
-    // c % 12: a lane owns whole 3-column groups of G (12-byte loads) and whole 4-column groups of the partial tile
-    if (c % 12 != 0 || c > 192 || (int64_t)rows * (cin > c ? cin : c) >= (1LL << 30)) return GEOM_EUNSUPPORTED;
-    if (!x || !g || !workspace || !aligned16(g) || !aligned16(workspace)) return GEOM_EINVAL;
+    const int code = check_backward(false, true, rows, cin, c, x, g, nullptr, nullptr, workspace);
+    if (code) return code;
     const SplitGeo geo = split_geometry(cin, rows, num_cus());
     if (want_colsum && geo.full_tiles == 0) return GEOM_EUNSUPPORTED;
-    float *colsum = want_colsum ? workspace + (int64_t)geo.slots * geo.rb * 16 * 192 : nullptr;
-    SplitArgs q{x, cin, g, c, workspace, cin, c, rows, geo.full_tiles, geo.s_full, geo.left_rb, geo.s_left, colsum};
-    const dim3 grid(geo.slots);
+    const SplitArgs q = split_args(rows, cin, c, x, g, workspace, want_colsum != 0, geo);
+    const dim3 grid(geo.slots), block(DG_THREADS);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool xvec = cin % 4 == 0 && aligned16(x);
     if (geo.rb == SPLIT_RB_NARROW) {
-        const dim3 block(DG_THREADS);
-        if (xvec) hipLaunchKernelGGL((dense_split_kernel<SPLIT_RB_NARROW, 3, true, 1>), grid, block, 0, s, q);
-        else hipLaunchKernelGGL((dense_split_kernel<SPLIT_RB_NARROW, 3, false, 1>), grid, block, 0, s, q);
+        if (xvec) hipLaunchKernelGGL((dense_split_kernel<SPLIT_RB_NARROW, 3, true>), grid, block, 0, s, q);
+        else hipLaunchKernelGGL((dense_split_kernel<SPLIT_RB_NARROW, 3, false>), grid, block, 0, s, q);
     } else {
-        const dim3 block(DG_THREADS * SPLIT_KP_WIDE);
-        if (xvec) hipLaunchKernelGGL((dense_split_kernel<SPLIT_RB, 3, true, SPLIT_KP_WIDE>), grid, block, 0, s, q);
-        else hipLaunchKernelGGL((dense_split_kernel<SPLIT_RB, 3, false, SPLIT_KP_WIDE>), grid, block, 0, s, q);
+        if (xvec) hipLaunchKernelGGL((dense_split_kernel<SPLIT_RB, 3, true>), grid, block, 0, s, q);
+        else hipLaunchKernelGGL((dense_split_kernel<SPLIT_RB, 3, false>), grid, block, 0, s, q);
     }
     return geom::launch_status();
 }
@@ -1199,32 +1118,25 @@ extern "C" int geom_dense_bwd_weight_f32(int rows, int cin, int c, const float *
 extern "C" int geom_dense_bwd_f32(int rows, int cin, int c, const float *x, const float *g, const float *w, float *grad_x,
                                   float *workspace, int want_colsum, void *stream)
 {
-    if (rows <= 0 || cin <= 0 || c <= 0) return GEOM_EINVAL;
-    if (c % 12 != 0 || c > 192 || (int64_t)rows * (cin > c ? cin : c) >= (1LL << 30)) return GEOM_EUNSUPPORTED;
-    if (!x || !g || !w || !grad_x || !workspace || !aligned16(g) || !aligned16(w) || !aligned16(workspace)) return GEOM_EINVAL;
+    int code = check_backward(true, true, rows, cin, c, x, g, w, grad_x, workspace);
+    if (code) return code;
     const int cus = num_cus();
     const bool xvec = cin % 4 == 0 && aligned16(x);
     const RowGeo rg = row_geometry(rows, 3, cus);
     const SplitGeo sg = split_geometry(cin, rows, cus);
     if (cin > 192 || !xvec || (want_colsum && sg.full_tiles == 0) || rg.rb < 2 || rg.rb > 5) { // rb 6: 82 KB of LDS, no pairing
-        int code = geom_dense_bwd_input_f32(rows, cin, c, g, w, grad_x, stream);
+        code = geom_dense_bwd_input_f32(rows, cin, c, g, w, grad_x, stream);
         if (code) return code;
         return geom_dense_bwd_weight_f32(rows, cin, c, x, g, workspace, want_colsum, stream);
     }
-    RowArgs r{g, c, w, c, grad_x, cin, rows, cin, c, rg.n_tiles, rg.left_rb, 1, 0, nullptr, nullptr, nullptr};
-    float *colsum = want_colsum ? workspace + (int64_t)sg.slots * sg.rb * 16 * 192 : nullptr;
-    SplitArgs q{x, cin, g, c, workspace, cin, c, rows, sg.full_tiles, sg.s_full, sg.left_rb, sg.s_left, colsum};
-    const dim3 grid(rg.grid + sg.slots), block(DG_THREADS);
+    const RowArgs r = input_gradient_args(rows, cin, c, g, w, grad_x, 3, rg);
+    const SplitArgs q = split_args(rows, cin, c, x, g, workspace, want_colsum != 0, sg);
     hipStream_t s = static_cast<hipStream_t>(stream);
     static_assert(SPLIT_RB_NARROW == 3, "cin <= 192 (the pair mode's range) takes the narrow split tiles");
-    switch (rg.rb) {
-    case 2: hipLaunchKernelGGL((dense_bwd_pair_kernel<2, SPLIT_RB_NARROW, true>), grid, block, 0, s, r, q, rg.grid); break;
-    case 3: hipLaunchKernelGGL((dense_bwd_pair_kernel<3, SPLIT_RB_NARROW, true>), grid, block, 0, s, r, q, rg.grid); break;
-    case 4: hipLaunchKernelGGL((dense_bwd_pair_kernel<4, SPLIT_RB_NARROW, true>), grid, block, 0, s, r, q, rg.grid); break;
-    case 5: hipLaunchKernelGGL((dense_bwd_pair_kernel<5, SPLIT_RB_NARROW, true>), grid, block, 0, s, r, q, rg.grid); break;
-    default: return GEOM_EINVAL;
-    }
-    return geom::launch_status();
+    return dispatch_rb<2, 5>(rg.rb, [&](auto rb) {
+        hipLaunchKernelGGL((dense_bwd_pair_kernel<decltype(rb)::value, SPLIT_RB_NARROW, true>), dim3(rg.grid + sg.slots),
+                           dim3(DG_THREADS), 0, s, r, q, rg.grid);
+    });
 }
 
 namespace {
@@ -1240,29 +1152,39 @@ void flat_grid(ReduceJobs &jobs, int n)
     }
 }
 
-// the jobs of geom_dense_reduce2_f32 / geom_dense_reduce_adam_f32: weight gradients first (job l = layer l), then the
-// column-sum jobs (job count + i)
-int build_reduce_jobs(ReduceJobs &jobs, int &n, int &widest, int count, const int *rows, const int *cin, const int *c,
-                      const float *const *workspaces, float *const *grad_w, int ncs, const float *const *cs_partials,
-                      const int *cs_rows, const int *cs_cols, float *const *cs_outs)
+// what a weight-gradient job needs of layer l
+inline bool bad_layer(const float *workspace, const float *grad_w, int rows, int cin, int c)
+{
+    return !workspace || !grad_w || rows <= 0 || cin <= 0 || c <= 0 || c > 192 || c % 4;
+}
+
+// the jobs of the three reduction entries: weight gradients first (job l = layer l), then the column-sum jobs (job count + i)
+int build_reduce_jobs(ReduceJobs &jobs, int count, const int *rows, const int *cin, const int *c, const float *const *workspaces,
+                      float *const *grad_w, int ncs, const float *const *cs_partials, const int *cs_rows, const int *cs_cols,
+                      float *const *cs_outs)
 {
     if (count < 0 || ncs < 0) return GEOM_EINVAL;
     if (count && (!rows || !cin || !c || !workspaces || !grad_w)) return GEOM_EINVAL;
     if (ncs && (!cs_partials || !cs_rows || !cs_cols || !cs_outs)) return GEOM_EINVAL;
     if (count + ncs > GEOM_DENSE_MAX_REDUCE_JOBS) return GEOM_ETOOBIG;
-    n = 0, widest = 0;
+    int n = 0;
     for (int l = 0; l < count; ++l) {
-        if (!workspaces[l] || !grad_w[l] || rows[l] <= 0 || cin[l] <= 0 || c[l] <= 0 || c[l] > 192 || c[l] % 4) return GEOM_EINVAL;
+        if (bad_layer(workspaces[l], grad_w[l], rows[l], cin[l], c[l])) return GEOM_EINVAL;
         const SplitGeo g = split_geometry(cin[l], rows[l], num_cus());
         jobs.job[n++] = ReduceJob{workspaces[l], grad_w[l], cin[l], c[l], g.rb * 16, 192, g.full_tiles, g.s_full, g.s_left, 0};
-        widest = cin[l] * (c[l] / 4) > widest ? cin[l] * (c[l] / 4) : widest;
     }
-    for (int i = 0; i < ncs; ++i) {
+    for (int i = 0; i < ncs; ++i) { // column sums: a 1-row "tile" per partial row, pitch = the column count
         if (!cs_partials[i] || !cs_outs[i] || cs_rows[i] < 0 || cs_cols[i] <= 0 || cs_cols[i] % 4) return GEOM_EINVAL;
         jobs.job[n++] = ReduceJob{cs_partials[i], cs_outs[i], 1, cs_cols[i], 1, cs_cols[i], 1, cs_rows[i], 0, 0};
     }
     flat_grid(jobs, n);
     return 0;
+}
+
+int launch_reduce(const ReduceJobs &jobs, const ReduceAdam &adam, void *stream)
+{
+    hipLaunchKernelGGL(dense_reduce_kernel, dim3(jobs.first[jobs.n]), dim3(RED_THREADS), 0, static_cast<hipStream_t>(stream), jobs, adam);
+    return geom::launch_status();
 }
 } // namespace
 
@@ -1277,12 +1199,8 @@ extern "C" int geom_dense_reduce2_f32(int count, const int *rows, const int *cin
     if (grad_bias) return GEOM_EINVAL; // bias gradients travel as column-sum jobs here
     if (count + ncs == 0) return 0;
     ReduceJobs jobs;
-    int n, widest;
-    const int code = build_reduce_jobs(jobs, n, widest, count, rows, cin, c, workspaces, grad_w, ncs, cs_partials, cs_rows, cs_cols, cs_outs);
-    if (code) return code;
-    ReduceAdam adam{};
-    hipLaunchKernelGGL(dense_reduce_kernel, dim3(jobs.first[n]), dim3(RED_THREADS), 0, static_cast<hipStream_t>(stream), jobs, adam);
-    return geom::launch_status();
+    const int code = build_reduce_jobs(jobs, count, rows, cin, c, workspaces, grad_w, ncs, cs_partials, cs_rows, cs_cols, cs_outs);
+    return code ? code : launch_reduce(jobs, ReduceAdam{}, stream);
 }
 
 // The same launch + the Adam step of the parameters whose gradients it finishes: w_p/w_m/w_v[l] = parameter, first and
@@ -1300,8 +1218,7 @@ extern "C" int geom_dense_reduce_adam_f32(int count, const int *rows, const int 
     if (count + ncs == 0 || !state) return GEOM_EINVAL;
     if ((count && (!w_p || !w_m || !w_v)) || (ncs && (!b_p || !b_m || !b_v))) return GEOM_EINVAL;
     ReduceJobs jobs;
-    int n, widest;
-    const int code = build_reduce_jobs(jobs, n, widest, count, rows, cin, c, workspaces, grad_w, ncs, cs_partials, cs_rows, cs_cols, cs_outs);
+    const int code = build_reduce_jobs(jobs, count, rows, cin, c, workspaces, grad_w, ncs, cs_partials, cs_rows, cs_cols, cs_outs);
     if (code) return code;
     ReduceAdam adam{};
     for (int l = 0; l < count; ++l) {
@@ -1314,35 +1231,33 @@ extern "C" int geom_dense_reduce_adam_f32(int count, const int *rows, const int 
     }
     adam.lr = lr, adam.b1 = beta1, adam.b2 = beta2, adam.eps = eps, adam.state = state;
     uintptr_t bits = 0;
-    for (int j = 0; j < n; ++j)
+    for (int j = 0; j < jobs.n; ++j)
         if (adam.p[j]) bits |= (uintptr_t)adam.p[j] | (uintptr_t)adam.m[j] | (uintptr_t)adam.v[j] | (uintptr_t)jobs.job[j].out;
     adam.vec = (bits & 15) == 0;
-    hipLaunchKernelGGL(dense_reduce_kernel, dim3(jobs.first[n]), dim3(RED_THREADS), 0, static_cast<hipStream_t>(stream), jobs, adam);
-    return geom::launch_status();
+    return launch_reduce(jobs, adam, stream);
 }
 
-// grad_w[i] (and grad_bias[i], may be NULL) of `count` layers out of their workspaces, ONE launch
+// grad_w[i] (and grad_bias[i], may be NULL) of `count` layers out of their workspaces, ONE launch: a bias gradient is the
+// column-sum job over the s_full rows of column sums its layer's split launch left behind the partial tiles
 extern "C" int geom_dense_reduce_f32(int count, const int *rows, const int *cin, const int *c, const float *const *workspaces,
                                      float *const *grad_w, float *const *grad_bias, void *stream)
 {
-    if (count < 0 || count > GEOM_DENSE_MAX_REDUCE_JOBS / 2) return GEOM_ETOOBIG;
+    constexpr int MAX = GEOM_DENSE_MAX_REDUCE_JOBS / 2;
+    if (count < 0 || count > MAX) return GEOM_ETOOBIG;
     if (count == 0) return 0;
     if (!rows || !cin || !c || !workspaces || !grad_w) return GEOM_EINVAL;
-    ReduceJobs jobs;
-    int n = 0, widest = 0;
+    const float *cs_partials[MAX];
+    float *cs_outs[MAX];
+    int cs_rows[MAX], cs_cols[MAX], ncs = 0;
     for (int l = 0; l < count; ++l) {
-        if (!workspaces[l] || !grad_w[l] || rows[l] <= 0 || cin[l] <= 0 || c[l] <= 0 || c[l] > 192 || c[l] % 4) return GEOM_EINVAL;
+        if (bad_layer(workspaces[l], grad_w[l], rows[l], cin[l], c[l])) return GEOM_EINVAL;
+        if (!grad_bias || !grad_bias[l]) continue;
         const SplitGeo g = split_geometry(cin[l], rows[l], num_cus());
-        jobs.job[n++] = ReduceJob{workspaces[l], grad_w[l], cin[l], c[l], g.rb * 16, 192, g.full_tiles, g.s_full, g.s_left, 0};
-        widest = cin[l] * (c[l] / 4) > widest ? cin[l] * (c[l] / 4) : widest;
-        if (grad_bias && grad_bias[l]) { // column sums: a 1-row "tile" per split, pitch = c
-            if (g.full_tiles == 0) return GEOM_EUNSUPPORTED;
-            jobs.job[n++] = ReduceJob{workspaces[l] + (int64_t)g.slots * g.rb * 16 * 192, grad_bias[l], 1, c[l], 1, c[l], 1,
-                                      g.s_full, 0, 0};
-        }
+        if (g.full_tiles == 0) return GEOM_EUNSUPPORTED;
+        cs_partials[ncs] = workspaces[l] + g.colsum_offset(), cs_outs[ncs] = grad_bias[l];
+        cs_rows[ncs] = g.s_full, cs_cols[ncs] = c[l], ++ncs;
     }
-    flat_grid(jobs, n);
-    hipLaunchKernelGGL(dense_reduce_kernel, dim3(jobs.first[n]), dim3(RED_THREADS), 0, static_cast<hipStream_t>(stream), jobs,
-                       ReduceAdam{});
-    return geom::launch_status();
+    ReduceJobs jobs;
+    const int code = build_reduce_jobs(jobs, count, rows, cin, c, workspaces, grad_w, ncs, cs_partials, cs_rows, cs_cols, cs_outs);
+    return code ? code : launch_reduce(jobs, ReduceAdam{}, stream);
 }

@@ -20,6 +20,11 @@ SHAPES = [
     (16, 4, 16),
     (83, 192, 192),
 ]
+# Row counts of the 192-wide layers that walk the loader and the pair launch on 256 workgroups: 4100 = 257 one-row-block
+# tiles (a workgroup takes a SECOND tile); 8200, 12300, 16400 = the pair launch at 2, 3 and 4 row-blocks per tile, each with
+# a leftover row-block (20496 above is 5); 12369 = 387 two-row-block tiles, two passes and a ragged last row-block; 24592 =
+# 6 row-blocks, where the pair entry falls back to two launches.
+PASSES = [(rows, 192, 192) for rows in (4100, 8200, 12300, 16400, 12369, 24592)]
 
 
 def _close(got, want, scale_axis=None, tol=5e-6):
@@ -72,7 +77,7 @@ def test_forward_matches_float64(rows, cin, c):
     _rows_close(out, x.double(), w.double(), "forward %dx%dx%d" % (rows, cin, c))
 
 
-@pytest.mark.parametrize("rows,cin,c", SHAPES)
+@pytest.mark.parametrize("rows,cin,c", SHAPES + PASSES)
 def test_input_gradient_matches_float64(rows, cin, c):
     from geometrics_amd import dense
     x, w, g = _operands(rows, cin, c, 1)
@@ -81,7 +86,7 @@ def test_input_gradient_matches_float64(rows, cin, c):
     _rows_close(out, g.double(), w.double().t(), "input gradient %dx%dx%d" % (rows, cin, c))
 
 
-@pytest.mark.parametrize("rows,cin,c", [s if s[2] % 12 == 0 else (s[0], s[1], 48) for s in SHAPES] + [(4000, 100, 96)])
+@pytest.mark.parametrize("rows,cin,c", [s if s[2] % 12 == 0 else (s[0], s[1], 48) for s in SHAPES] + [(4000, 100, 96)] + PASSES)
 def test_weight_and_bias_gradient_match_float64(rows, cin, c):
     from geometrics_amd import dense
     x, w, g = _operands(rows, cin, c, 2)
@@ -96,7 +101,7 @@ def test_weight_and_bias_gradient_match_float64(rows, cin, c):
     assert torch.equal(gw, gw2)
 
 
-@pytest.mark.parametrize("rows,cin", [(20496, 963), (20496, 192), (2562, 192), (83, 192)])
+@pytest.mark.parametrize("rows,cin", [(20496, 963), (20496, 192), (2562, 192), (83, 192), (12369, 192)])
 def test_split_epilogue_finishes_the_pass_through_columns(rows, cin):
     """ksplit mode (layers.py:108-116, ReLU): aggregated columns raw and compact, pass-through columns with bias + ReLU,
     sign bits of the pass-through columns."""
@@ -118,7 +123,7 @@ def test_split_epilogue_finishes_the_pass_through_columns(rows, cin):
     assert int(bits[:, :k // 16].sum()) == 0
 
 
-@pytest.mark.parametrize("rows,cin,c", [(20496, 192, 192), (7712, 192, 192), (2562, 192, 192), (20496, 963, 192), (83, 192, 192)])
+@pytest.mark.parametrize("rows,cin,c", [(20496, 192, 192), (7712, 192, 192), (2562, 192, 192), (20496, 963, 192), (83, 192, 192)] + PASSES)
 def test_pair_launch_equals_the_two_separate_launches(rows, cin, c):
     """geom_dense_bwd_f32 (one launch, two workgroups per CU) runs the same two bodies: same bits as the separate launches."""
     from geometrics_amd import dense
