@@ -99,6 +99,8 @@ def test_training_step_with_the_drivers_call_shapes(gpu):
         loss.backward()
         unused = [p for p in params if p.grad is None]
         assert len(unused) == 6          # bn14.weight / bn14.bias of each block: never called by the reference either
+        # (finite here; their VALUES -- every parameter's and map's gradient of the step bench.py times, against these very
+        # expressions -- are held in tests/test_driver_step_routes_gpu.py)
         for p in params:
             assert p.grad is None or torch.isfinite(p.grad).all()
         for group in maps:
