@@ -13,6 +13,19 @@
 // 256 B - 1 KiB runs; neighbour rows of the k-slice are re-read through L2 (the slice is
 // b*V*k*4 bytes, 5.2 MB at the BASELINE shard).  HBM-bound: algorithmic bytes = read
 // support + write out (+ CSR), see DESIGN.md.
+//
+// Three kernels -- zn_aggregate_kernel (CSR), zn_aggregate_ell_kernel (neighbour table, split 3 / 10) and
+// zn_aggregate_ell_any_kernel (neighbour table, any width) -- share ONE statement of each step ("The aggregation
+// kernels' shared steps"): Pack<VEC>'s element-wise operations; the neighbour term in two halves (term_load: the loads of
+// one neighbour row, term_add: derivative + acc += w * v); the table-row load and its slots (load_table_row,
+// load_table_slots, add_table_slots); the CSR run in batches (add_csr_run); the own element (own_element); the forward
+// epilogue (Pack::bias_act); the straddling group's partial stores (Pack::store_below / store_from); the column-sum partials
+// (write_colsum_partial) and their reduction (reduce_partials).  The summation rule -- table slots in slot order, then the
+// tail in CSR order, un-fused, from 0.f, padded slots skipped -- is term_add under `if (the slot is in the row)` and nowhere
+// else; the fused launches of zn_stack.hip, deform_block.hip and encoder_stack.hip are pinned to its bits.  The fast kernel
+// keeps its own elements with the column sums over them and its tail's index prefetch as written (registers: DESIGN.md).
+#include <type_traits>
+
 #include "buffer_access.h"
 
 namespace {
@@ -32,28 +45,121 @@ struct GcnArgs {
     int nv, c, k;
 };
 
+// VEC consecutive floats of a row, moved as one float4 / float2 / float, with the element-wise steps of the kernels below.
 template <int VEC>
-struct Pack;
+struct PackVector;
 template <>
-struct Pack<4> {
-    float4 v;
-    __device__ __forceinline__ void load(const float *p) { v = *reinterpret_cast<const float4 *>(p); }
-    __device__ __forceinline__ void store(float *p) const { *reinterpret_cast<float4 *>(p) = v; }
-    __device__ __forceinline__ float &at(int i) { return (&v.x)[i]; }
-};
+struct PackVector<4> { using type = float4; };
 template <>
-struct Pack<2> {
-    float2 v;
-    __device__ __forceinline__ void load(const float *p) { v = *reinterpret_cast<const float2 *>(p); }
-    __device__ __forceinline__ void store(float *p) const { *reinterpret_cast<float2 *>(p) = v; }
-    __device__ __forceinline__ float &at(int i) { return (&v.x)[i]; }
-};
+struct PackVector<2> { using type = float2; };
 template <>
-struct Pack<1> {
-    float v;
-    __device__ __forceinline__ void load(const float *p) { v = *p; }
-    __device__ __forceinline__ void store(float *p) const { *p = v; }
-    __device__ __forceinline__ float &at(int) { return v; }
+struct PackVector<1> { using type = float; };
+
+__device__ __forceinline__ float *elements(float4 &v) { return &v.x; }
+__device__ __forceinline__ float *elements(float2 &v) { return &v.x; }
+__device__ __forceinline__ float *elements(float &v) { return &v; }
+__device__ __forceinline__ const float *elements(const float4 &v) { return &v.x; }
+__device__ __forceinline__ const float *elements(const float2 &v) { return &v.x; }
+__device__ __forceinline__ const float *elements(const float &v) { return &v; }
+
+template <int VEC>
+struct Pack {
+    using Vector = typename PackVector<VEC>::type;
+    Vector v;
+    __device__ __forceinline__ void load(const float *p) { v = *reinterpret_cast<const Vector *>(p); }
+    __device__ __forceinline__ void store(float *p) const { *reinterpret_cast<Vector *>(p) = v; }
+    __device__ __forceinline__ float &at(int i) { return elements(v)[i]; }
+    __device__ __forceinline__ float at(int i) const { return elements(v)[i]; }
+    static __device__ __forceinline__ Pack zero()
+    {
+        Pack p;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) p.at(i) = 0.f;
+        return p;
+    }
+    __device__ __forceinline__ void add(const Pack &o)
+    {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) at(i) += o.at(i);
+    }
+    __device__ __forceinline__ void add_scaled(float w, const Pack &o) // += w * o: a product, then a sum (never fused)
+    {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) at(i) += w * o.at(i);
+    }
+    template <int ACT>
+    __device__ __forceinline__ void act_bwd_from(const Pack &out) // g -> g * act'(out)
+    {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) at(i) = act_bwd<ACT>(at(i), out.at(i));
+    }
+    __device__ __forceinline__ void keep_where(unsigned bits) // element i stays where bit i is set (relu' from sign bits)
+    {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) at(i) = (bits & (1u << i)) ? at(i) : 0.f;
+    }
+    // forward epilogue: + bias[col ...] (bias == null: none), activation.  WIDE: the bias is read as one vector (the fast kernel,
+    // whose dispatcher checks its alignment), otherwise float by float
+    template <int ACT, bool WIDE = false>
+    __device__ __forceinline__ void bias_act(const float *bias, int col)
+    {
+        if (WIDE) {
+            if (bias) {
+                Pack b;
+                b.load(bias + col);
+                add(b);
+            }
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) at(i) = act_fwd<ACT>(at(i));
+        } else {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                float t = at(i);
+                if (bias) t += bias[col + i];
+                at(i) = act_fwd<ACT>(t);
+            }
+        }
+    }
+    __device__ __forceinline__ unsigned positive_bits() const // bit i = element i > 0, the predicate relu' is defined by (act_bwd)
+    {
+        unsigned bits = 0u;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) bits |= at(i) > 0.f ? 1u << i : 0u;
+        return bits;
+    }
+    __device__ __forceinline__ void take_from(const Pack &o, int first) // elements first.. are o's
+    {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i)
+            if (i >= first) at(i) = o.at(i);
+    }
+    // The pack holds columns c0 .. c0 + VEC - 1 of `row`.  Of the group that straddles column k, the aggregating thread stores
+    // the columns below k and the pass-through thread those from k on, element by element; a whole group goes as one vector.
+    __device__ __forceinline__ void store_below(float *row, int c0, int k) const
+    {
+        if (c0 + VEC <= k) {
+            store(row + c0);
+        } else {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i)
+                if (c0 + i < k) row[c0 + i] = at(i);
+        }
+    }
+    __device__ __forceinline__ void store_from(float *row, int c0, int k) const
+    {
+        if (c0 >= k) {
+            store(row + c0);
+        } else {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i)
+                if (c0 + i >= k) row[c0 + i] = at(i);
+        }
+    }
+    __device__ __forceinline__ void store_elements(float *p) const // where p is aligned as a float only
+    {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) p[i] = at(i);
+    }
 };
 
 // Thread layout: a block owns `rows_per_block` consecutive rows of ONE mesh; thread t owns column group
@@ -67,10 +173,152 @@ struct Pack<1> {
 constexpr int GCN_NB = 8;         // neighbours fetched per batch
 constexpr int GCN_BWD_ITERS = 2;  // rows per thread in the backward (halves the bias-gradient partials)
 
+// Where a term's operand and its activation derivative are read from.
+struct Source {
+    const float *x;             // support (forward) or grad_out (backward); null in the head's backward
+    const float *saved;         // backward: forward output (act' where there is no sign mask)
+    const unsigned short *mask; // MASK: one word per (row, aggregated float4 j of kg); bit e <-> element e of that float4
+    int kg, j;
+    const float *head;          // HEAD backward: grad_pos [rows, 3]; the upstream gradient is [head_scale * grad_pos | 0 ...]
+    float head_scale;
+    int c;
+};
+
+// THE NEIGHBOUR TERM, and every other element a thread reads with the derivative folded in: VEC columns of one row, in two
+// halves.  Callers issue term_load for a whole round of rows before the first term_finish / term_add: a round is then one
+// memory round trip.  The three values of a term (operand, saved output, sign bits) live in the caller's arrays, one array
+// per value as the kernels always had them: what a variant does not read is never loaded and costs no register.
+template <int VEC_, int ACT_, bool BACKWARD_, bool MASK_ = false, bool HEAD_ = false>
+struct TermKind {
+    static_assert((!MASK_ && !HEAD_) || VEC_ == 4, "sign mask and head are the fast kernel's");
+    static constexpr int VEC = VEC_, ACT = ACT_;
+    static constexpr bool BACKWARD = BACKWARD_, MASK = MASK_, HEAD = HEAD_;
+};
+
+// load half: the operand into v (HEAD backward: synthesised from grad_pos, non-zero in the row's first float4 only) and, in the
+// backward, where act' comes from: the sign-mask word into bits, or the saved output into out
+template <class KIND, int VEC>
+__device__ __forceinline__ void term_load(Pack<VEC> &v, Pack<VEC> &out, unsigned &bits, const Source &s, int64_t row, int col)
+{
+    if (KIND::BACKWARD && KIND::HEAD) {
+        v = Pack<VEC>::zero();
+        if (col == 0) {
+            const float *gp = s.head + row * 3;
+#pragma unroll
+            for (int i = 0; i < 3 && i < VEC; ++i) v.at(i) = s.head_scale * gp[i];
+        }
+    } else {
+        v.load(s.x + row * s.c + col);
+    }
+    if (KIND::BACKWARD && KIND::MASK) bits = s.mask[row * s.kg + s.j];
+    else if (KIND::BACKWARD && KIND::ACT != ACT_NONE) out.load(s.saved + row * s.c + col);
+}
+
+// finish half: the derivative applied to the operand (in place) ...
+template <class KIND, int VEC>
+__device__ __forceinline__ void term_finish(Pack<VEC> &v, const Pack<VEC> &out, unsigned bits)
+{
+    if (KIND::BACKWARD && KIND::MASK) v.keep_where(bits);
+    else if (KIND::BACKWARD && KIND::ACT != ACT_NONE) v.template act_bwd_from<KIND::ACT>(out);
+}
+
+// ... and acc += w * v: the one statement of the sum (callers skip padded slots, they do not multiply by zero)
+template <class KIND, int VEC>
+__device__ __forceinline__ void term_add(Pack<VEC> &acc, float w, Pack<VEC> &v, const Pack<VEC> &out, unsigned bits)
+{
+    term_finish<KIND>(v, out, bits);
+    acc.add_scaled(w, v);
+}
+
+// The thread's own element of `row` (pass-through value and / or bias-gradient term).
+template <class KIND, int VEC>
+__device__ __forceinline__ void own_element(Pack<VEC> &own, const Source &s, int64_t row, int col)
+{
+    Pack<VEC> out;
+    unsigned bits = 0u;
+    term_load<KIND>(own, out, bits, s, row, col);
+    term_finish<KIND>(own, out, bits);
+}
+
+// A CSR run [e, e1) of (col, val) added to acc in order, GCN_NB entries per batch: the pairs first, then the rows, then
+// the sum; the slots past the end read the thread's own row and contribute nothing.
+template <class KIND, int VEC>
+__device__ __forceinline__ void add_csr_run(Pack<VEC> &acc, const Source &s, const int *col, const float *val, int e, int e1,
+                                            int64_t mesh_row0, int64_t row, int c0)
+{
+    for (; e < e1; e += GCN_NB) {
+        int64_t nb[GCN_NB];
+        float w[GCN_NB];
+#pragma unroll
+        for (int j = 0; j < GCN_NB; ++j) {
+            const bool in = e + j < e1;
+            nb[j] = in ? mesh_row0 + col[e + j] : row;
+            w[j] = in ? val[e + j] : 0.f;
+        }
+        Pack<VEC> sv[GCN_NB], ov[GCN_NB];
+        unsigned bits[GCN_NB] = {};
+#pragma unroll
+        for (int j = 0; j < GCN_NB; ++j) term_load<KIND>(sv[j], ov[j], bits[j], s, nb[j], c0);
+#pragma unroll
+        for (int j = 0; j < GCN_NB; ++j)
+            if (e + j < e1) term_add<KIND>(acc, w[j], sv[j], ov[j], bits[j]); // keep the CSR order of the sum
+    }
+}
+
+// Row r of a [nv][W] neighbour table (col -1 = padding), 16 bytes at a time.
+template <int W>
+__device__ __forceinline__ void load_table_row(const int *col, const float *val, int r, int (&nb)[W], float (&w)[W])
+{
+#pragma unroll
+    for (int n = 0; n < W; n += 4) {
+        const int4 ci = *reinterpret_cast<const int4 *>(col + (size_t)r * W + n);
+        const float4 wi = *reinterpret_cast<const float4 *>(val + (size_t)r * W + n);
+        nb[n] = ci.x, nb[n + 1] = ci.y, nb[n + 2] = ci.z, nb[n + 3] = ci.w;
+        w[n] = wi.x, w[n + 1] = wi.y, w[n + 2] = wi.z, w[n + 3] = wi.w;
+    }
+}
+
+// The W table slots of row r: all their loads (a padded slot reads row r itself), then the sum in slot order == CSR order.
+template <class KIND, int W, int VEC>
+__device__ __forceinline__ void load_table_slots(Pack<VEC> (&sv)[W], Pack<VEC> (&ov)[W], unsigned (&bits)[W], const Source &s,
+                                                 const int (&nb)[W], int64_t mesh_row0, int r, int c0)
+{
+#pragma unroll
+    for (int n = 0; n < W; ++n) term_load<KIND>(sv[n], ov[n], bits[n], s, mesh_row0 + (nb[n] >= 0 ? nb[n] : r), c0);
+}
+
+template <class KIND, int W, int VEC>
+__device__ __forceinline__ void add_table_slots(Pack<VEC> &acc, Pack<VEC> (&sv)[W], const Pack<VEC> (&ov)[W], const unsigned (&bits)[W],
+                                                const int (&nb)[W], const float (&w)[W])
+{
+#pragma unroll
+    for (int n = 0; n < W; ++n)
+        if (nb[n] >= 0) term_add<KIND>(acc, w[n], sv[n], ov[n], bits[n]);
+}
+
+// Block partial of the bias gradient in the row-major layouts: the threads' column sums through lds [rows_in_flight][c], row 0's
+// threads add them in row order (fixed summation order) into partial_row [c].
+template <int VEC>
+__device__ __forceinline__ void write_colsum_partial(float *lds, const Pack<VEC> &colsum, bool active, int rl, int rows_in_flight,
+                                                     int c, int c0, float *partial_row)
+{
+    if (active) colsum.store_elements(lds + rl * c + c0);
+    __syncthreads();
+    if (active && rl == 0) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            float t = 0.f;
+            for (int l = 0; l < rows_in_flight; ++l) t += lds[l * c + c0 + i];
+            partial_row[c0 + i] = t;
+        }
+    }
+}
+
 template <int VEC, int ACT, bool BACKWARD>
 __global__ __launch_bounds__(GCN_THREADS) void zn_aggregate_kernel(GcnArgs a, int groups, int rows_in_flight,
                                                                     int rows_per_block, float *colsum_partial)
 {
+    using KIND = TermKind<VEC, ACT, BACKWARD>;
     extern __shared__ float lds_colsum[]; // [rows_in_flight][c], backward with colsum only
     const int g = threadIdx.x % groups;
     const int rl = threadIdx.x / groups;
@@ -80,10 +328,9 @@ __global__ __launch_bounds__(GCN_THREADS) void zn_aggregate_kernel(GcnArgs a, in
     const int r_begin = blockIdx.x * rows_per_block;
     const int r_end = min(r_begin + rows_per_block, a.nv);
     const int64_t mesh_row0 = (int64_t)blockIdx.y * a.nv; // first row of this mesh
+    const Source src{.x = a.x, .saved = a.saved, .c = a.c};
 
-    Pack<VEC> colsum;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) colsum.at(i) = 0.f;
+    Pack<VEC> colsum = Pack<VEC>::zero();
 
     if (active) {
         for (int r = r_begin + rl; r < r_end; r += rows_in_flight) {
@@ -91,94 +338,31 @@ __global__ __launch_bounds__(GCN_THREADS) void zn_aggregate_kernel(GcnArgs a, in
             Pack<VEC> acc, own;
             const bool pass = c0 + VEC > a.k; // the group holds pass-through columns (all of them, or -- when k is not
                                               // a multiple of VEC -- the tail of the group that straddles column k)
-            if (BACKWARD || pass) { // the thread's own element: pass-through value and/or bias-gradient term
-                own.load(a.x + row * a.c + c0);
-                if (BACKWARD && ACT != ACT_NONE) {
-                    Pack<VEC> o;
-                    o.load(a.saved + row * a.c + c0);
-#pragma unroll
-                    for (int i = 0; i < VEC; ++i) own.at(i) = act_bwd<ACT>(own.at(i), o.at(i));
-                }
-            }
+            if (BACKWARD || pass) own_element<KIND>(own, src, row, c0); // pass-through value and/or bias-gradient term
             if (c0 < a.k) {
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) acc.at(i) = 0.f;
-                const int e1 = a.rowptr[r + 1];
-                for (int e = a.rowptr[r]; e < e1; e += GCN_NB) {
-                    int64_t nb[GCN_NB];
-                    float w[GCN_NB];
-#pragma unroll
-                    for (int j = 0; j < GCN_NB; ++j) {
-                        const bool in = e + j < e1;
-                        nb[j] = in ? mesh_row0 + a.col[e + j] : row;
-                        w[j] = in ? a.val[e + j] : 0.f;
-                    }
-                    Pack<VEC> sv[GCN_NB], ov[GCN_NB];
-#pragma unroll
-                    for (int j = 0; j < GCN_NB; ++j) {
-                        sv[j].load(a.x + nb[j] * a.c + c0);
-                        if (BACKWARD && ACT != ACT_NONE) ov[j].load(a.saved + nb[j] * a.c + c0);
-                    }
-#pragma unroll
-                    for (int j = 0; j < GCN_NB; ++j) {
-                        if (e + j < e1) { // keep the CSR order of the sum; padded slots contribute nothing
-#pragma unroll
-                            for (int i = 0; i < VEC; ++i) {
-                                float v = sv[j].at(i);
-                                if (BACKWARD && ACT != ACT_NONE) v = act_bwd<ACT>(v, ov[j].at(i));
-                                acc.at(i) += w[j] * v;
-                            }
-                        }
-                    }
-                }
-                if (pass) { // straddling group: the gathered values of columns >= k are discarded
-#pragma unroll
-                    for (int i = 0; i < VEC; ++i)
-                        if (c0 + i >= a.k) acc.at(i) = own.at(i);
-                }
+                acc = Pack<VEC>::zero();
+                add_csr_run<KIND>(acc, src, a.col, a.val, a.rowptr[r], a.rowptr[r + 1], mesh_row0, row, c0);
+                if (pass) acc.take_from(own, a.k - c0); // straddling group: the gathered values of columns >= k are discarded
             } else {
                 acc = own;
             }
-            if (BACKWARD) {
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) colsum.at(i) += own.at(i);
-            } else {
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    float v = acc.at(i);
-                    if (a.bias) v += a.bias[c0 + i];
-                    acc.at(i) = act_fwd<ACT>(v);
-                }
-            }
+            if (BACKWARD) colsum.add(own);
+            else acc.template bias_act<ACT>(a.bias, c0);
             acc.store(a.y + row * a.c + c0);
         }
     }
 
-    if (BACKWARD && colsum_partial) { // block partial of the bias gradient, fixed summation order
-        if (active) {
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) lds_colsum[rl * a.c + c0 + i] = colsum.at(i);
-        }
-        __syncthreads();
-        if (active && rl == 0) {
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                float t = 0.f;
-                for (int l = 0; l < rows_in_flight; ++l) t += lds_colsum[l * a.c + c0 + i];
-                colsum_partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * a.c + c0 + i] = t;
-            }
-        }
-    }
+    if (BACKWARD && colsum_partial) // block partial of the bias gradient, fixed summation order
+        write_colsum_partial(lds_colsum, colsum, active, rl, rows_in_flight, a.c, c0,
+                             colsum_partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * a.c);
 }
 
 // grad_bias[c] = sum over blocks of partial[blk][c].  16 columns x 64 block-lanes per workgroup:
 // lane l adds blocks l, l+64, ... (independent loads, pipelined), then the 64 lane sums are added
 // in ascending lane order -- a fixed tree, so the result is bit-reproducible.
 constexpr int CS_COLS = 16, CS_LANES = 64;
-__global__ __launch_bounds__(CS_COLS *CS_LANES) void colsum_final_kernel(int blocks, int c, const float *partial,
-                                                                         float *out)
+__device__ __forceinline__ void reduce_partials(float (&part)[CS_LANES][CS_COLS], int blocks, int c, const float *partial, float *out)
 {
-    __shared__ float part[CS_LANES][CS_COLS];
     const int cl = threadIdx.x % CS_COLS, lane = threadIdx.x / CS_COLS;
     const int col = blockIdx.x * CS_COLS + cl;
     float t = 0.f;
@@ -195,6 +379,13 @@ __global__ __launch_bounds__(CS_COLS *CS_LANES) void colsum_final_kernel(int blo
     }
 }
 
+__global__ __launch_bounds__(CS_COLS *CS_LANES) void colsum_final_kernel(int blocks, int c, const float *partial,
+                                                                         float *out)
+{
+    __shared__ float part[CS_LANES][CS_COLS];
+    reduce_partials(part, blocks, c, partial, out);
+}
+
 // The same reduction for several pending bias gradients in ONE launch (blockIdx.y = job): a backward pass through N
 // layers leaves N sets of partials, and N separate 4.7 us launches are 5 % of the reference's training-shape step.
 struct ColsumJobs {
@@ -207,23 +398,8 @@ __global__ __launch_bounds__(CS_COLS *CS_LANES) void colsum_batch_kernel(ColsumJ
 {
     __shared__ float part[CS_LANES][CS_COLS];
     const int job = blockIdx.y;
-    const int blocks = jobs.blocks[job], c = jobs.c[job];
-    if ((int)blockIdx.x * CS_COLS >= c) return; // a job narrower than the widest one
-    const float *partial = jobs.partial[job];
-    const int cl = threadIdx.x % CS_COLS, lane = threadIdx.x / CS_COLS;
-    const int col = blockIdx.x * CS_COLS + cl;
-    float t = 0.f;
-    if (col < c) {
-#pragma unroll 8
-        for (int b = lane; b < blocks; b += CS_LANES) t += partial[(size_t)b * c + col];
-    }
-    part[lane][cl] = t;
-    __syncthreads();
-    if (lane == 0 && col < c) {
-        float acc = 0.f;
-        for (int l = 0; l < CS_LANES; ++l) acc += part[l][cl];
-        jobs.out[job][col] = acc;
-    }
+    if ((int)blockIdx.x * CS_COLS >= jobs.c[job]) return; // a job narrower than the widest one
+    reduce_partials(part, jobs.blocks[job], jobs.c[job], jobs.partial[job], jobs.out[job]);
 }
 
 struct GcnGeometry {
@@ -266,6 +442,28 @@ inline int finish_launch(bool backward, int64_t blocks, int c, const float *part
     return geom::launch_status();
 }
 
+// Run-time values as template arguments: f is called with the value as a std::integral_constant.  Activation code (false: no
+// such code, f not called), table width 8 / 16 (the dispatcher admits no other), vector width 4 / 2 / 1.
+template <int V>
+using Const = std::integral_constant<int, V>;
+
+template <class F>
+bool with_act(int act, F &&f)
+{
+    switch (act) {
+    case ACT_NONE: f(Const<ACT_NONE>{}); return true;
+    case ACT_RELU: f(Const<ACT_RELU>{}); return true;
+    case ACT_ELU: f(Const<ACT_ELU>{}); return true;
+    default: return false;
+    }
+}
+
+template <class F>
+void with_width(int w, F &&f) { w == 8 ? f(Const<8>{}) : f(Const<16>{}); }
+
+template <class F>
+void with_vec(int vec, F &&f) { vec == 4 ? f(Const<4>{}) : vec == 2 ? f(Const<2>{}) : f(Const<1>{}); }
+
 template <int VEC, bool BACKWARD>
 int launch(const GcnArgs &a, int act, float *colsum_partial, float *grad_bias, void *stream)
 {
@@ -276,13 +474,11 @@ int launch(const GcnArgs &a, int act, float *colsum_partial, float *grad_bias, v
     dim3 grid((unsigned)geo.chunks, (unsigned)meshes), block(GCN_THREADS);
     const size_t lds = (BACKWARD && colsum_partial) ? (size_t)geo.rows_in_flight * a.c * sizeof(float) : 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (act) {
-    case ACT_NONE: hipLaunchKernelGGL((zn_aggregate_kernel<VEC, ACT_NONE, BACKWARD>), grid, block, lds, s, a, geo.groups, geo.rows_in_flight, geo.rows_per_block, colsum_partial); break;
-    case ACT_RELU: hipLaunchKernelGGL((zn_aggregate_kernel<VEC, ACT_RELU, BACKWARD>), grid, block, lds, s, a, geo.groups, geo.rows_in_flight, geo.rows_per_block, colsum_partial); break;
-    case ACT_ELU: hipLaunchKernelGGL((zn_aggregate_kernel<VEC, ACT_ELU, BACKWARD>), grid, block, lds, s, a, geo.groups, geo.rows_in_flight, geo.rows_per_block, colsum_partial); break;
-    default: return GEOM_EINVAL;
-    }
-    return finish_launch(BACKWARD, geo.blocks, a.c, colsum_partial, grad_bias, s);
+    const bool known = with_act(act, [&](auto ACT) {
+        hipLaunchKernelGGL((zn_aggregate_kernel<VEC, decltype(ACT)::value, BACKWARD>), grid, block, lds, s, a, geo.groups,
+                           geo.rows_in_flight, geo.rows_per_block, colsum_partial);
+    });
+    return known ? finish_launch(BACKWARD, geo.blocks, a.c, colsum_partial, grad_bias, s) : GEOM_EINVAL;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -339,6 +535,8 @@ __global__ __launch_bounds__(GCN_THREADS) void zn_aggregate_ell_kernel(EllArgs a
     if (!geom::xcd_assign(blockIdx.x, a.b, a.chunks, mesh_i, chunk_i)) return;
     const int64_t mesh_row0 = (int64_t)mesh_i * a.nv;
     const int c0 = 4 * j;
+    using KIND = TermKind<4, ACT, BACKWARD, MASK, HEAD>;
+    const Source src{.x = a.x, .saved = a.saved, .mask = a.mask, .kg = kg, .j = j, .head = a.head_in, .head_scale = a.head_scale, .c = a.c};
     // `iters` consecutive row tiles per workgroup (the backward uses 2: half the bias-gradient partials to reduce)
     float4 csum[NC + 1]; // bias-gradient terms of this thread's columns over its rows (backward)
 #pragma unroll
@@ -357,13 +555,7 @@ __global__ __launch_bounds__(GCN_THREADS) void zn_aggregate_ell_kernel(EllArgs a
         // round trip 1: indices, weights and the thread's own elements
         int nb[W];
         float w[W];
-#pragma unroll
-        for (int n = 0; n < W; n += 4) {
-            const int4 ci = *reinterpret_cast<const int4 *>(a.col + (size_t)r * W + n);
-            const float4 wi = *reinterpret_cast<const float4 *>(a.val + (size_t)r * W + n);
-            nb[n] = ci.x, nb[n + 1] = ci.y, nb[n + 2] = ci.z, nb[n + 3] = ci.w;
-            w[n] = wi.x, w[n + 1] = wi.y, w[n + 2] = wi.z, w[n + 3] = wi.w;
-        }
+        load_table_row<W>(a.col, a.val, r, nb, w);
         constexpr int TAIL = (ACT == ACT_NONE && NC == 2) ? 16 : 8; // entries of a long row per round (below)
         int e0 = 0, e1 = 0; // the row's entries beyond the table width, in the CSR tail
         if (a.over_ptr) e0 = a.over_ptr[r], e1 = a.over_ptr[r + 1];
@@ -393,22 +585,9 @@ __global__ __launch_bounds__(GCN_THREADS) void zn_aggregate_ell_kernel(EllArgs a
             }
         }
         // round trip 2: the neighbour rows of the aggregated slot
-        float4 sv[W], ov[W];
-        unsigned nbits[W];
-#pragma unroll
-        for (int n = 0; n < W; ++n) {
-            const int64_t nrow = mesh_row0 + (nb[n] >= 0 ? nb[n] : r);
-            if (BACKWARD && HEAD) {
-                sv[n] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (j == 0) {
-                    const float *gp = a.head_in + nrow * 3;
-                    sv[n] = make_float4(a.head_scale * gp[0], a.head_scale * gp[1], a.head_scale * gp[2], 0.f);
-                }
-            } else
-            sv[n] = *reinterpret_cast<const float4 *>(a.x + nrow * a.c + c0);
-            if (BACKWARD && MASK) nbits[n] = a.mask[nrow * kg + j];
-            else if (BACKWARD && ACT != ACT_NONE) ov[n] = *reinterpret_cast<const float4 *>(a.saved + nrow * a.c + c0);
-        }
+        Pack<4> sv[W], ov[W];
+        unsigned nbits[W] = {};
+        load_table_slots<KIND>(sv, ov, nbits, src, nb, mesh_row0, r, c0);
         int tcol[TAIL];
         float tval[TAIL];
         if (e0 < e1) { // a long row: the indices of its first TAIL extra entries travel with the neighbour rows
@@ -419,50 +598,21 @@ __global__ __launch_bounds__(GCN_THREADS) void zn_aggregate_ell_kernel(EllArgs a
                 tval[t] = a.over_val[ee];
             }
         }
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int n = 0; n < W; ++n) {
-            if (nb[n] >= 0) { // ELL order == CSR order of the row
-                float4 v = sv[n];
-                if (BACKWARD && MASK) {
-                    v.x = (nbits[n] & 1u) ? v.x : 0.f;
-                    v.y = (nbits[n] & 2u) ? v.y : 0.f;
-                    v.z = (nbits[n] & 4u) ? v.z : 0.f;
-                    v.w = (nbits[n] & 8u) ? v.w : 0.f;
-                } else if (BACKWARD && ACT != ACT_NONE) {
-                    v.x = act_bwd<ACT>(v.x, ov[n].x);
-                    v.y = act_bwd<ACT>(v.y, ov[n].y);
-                    v.z = act_bwd<ACT>(v.z, ov[n].z);
-                    v.w = act_bwd<ACT>(v.w, ov[n].w);
-                }
-                acc.x += w[n] * v.x;
-                acc.y += w[n] * v.y;
-                acc.z += w[n] * v.z;
-                acc.w += w[n] * v.w;
-            }
-        }
+        Pack<4> acc = Pack<4>::zero();
+        add_table_slots<KIND>(acc, sv, ov, nbits, nb, w); // ELL order == CSR order of the row
         // the row's entries beyond the table width (wave-divergent only at the few long rows).  TAIL entries per round:
         // their rows in one round trip, the NEXT round's indices requested meanwhile (one entry at a time the 25 extra
         // entries of a 482.obj pole cost 50 dependent round trips, and the two pole rows set the launch time)
         for (int e = e0; e < e1; e += TAIL) {
             int64_t nrow[TAIL];
             float wv[TAIL];
-            float4 tv[TAIL], to[TAIL];
-            unsigned tb[TAIL];
+            Pack<4> tv[TAIL], to[TAIL];
+            unsigned tb[TAIL] = {};
 #pragma unroll
             for (int t = 0; t < TAIL; ++t) {
                 nrow[t] = mesh_row0 + tcol[t];
                 wv[t] = tval[t];
-                if (BACKWARD && HEAD) {
-                    tv[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (j == 0) {
-                        const float *gp = a.head_in + nrow[t] * 3;
-                        tv[t] = make_float4(a.head_scale * gp[0], a.head_scale * gp[1], a.head_scale * gp[2], 0.f);
-                    }
-                } else
-                tv[t] = *reinterpret_cast<const float4 *>(a.x + nrow[t] * a.c + c0);
-                if (BACKWARD && MASK) tb[t] = a.mask[nrow[t] * kg + j];
-                else if (BACKWARD && ACT != ACT_NONE) to[t] = *reinterpret_cast<const float4 *>(a.saved + nrow[t] * a.c + c0);
+                term_load<KIND>(tv[t], to[t], tb[t], src, nrow[t], c0);
             }
             if (e + TAIL < e1) {
 #pragma unroll
@@ -473,46 +623,25 @@ __global__ __launch_bounds__(GCN_THREADS) void zn_aggregate_ell_kernel(EllArgs a
                 }
             }
 #pragma unroll
-            for (int t = 0; t < TAIL; ++t) {
-                if (e + t < e1) { // still in CSR order
-                    float4 v = tv[t];
-                    if (BACKWARD && MASK) {
-                        v.x = (tb[t] & 1u) ? v.x : 0.f;
-                        v.y = (tb[t] & 2u) ? v.y : 0.f;
-                        v.z = (tb[t] & 4u) ? v.z : 0.f;
-                        v.w = (tb[t] & 8u) ? v.w : 0.f;
-                    } else if (BACKWARD && ACT != ACT_NONE) {
-                        v.x = act_bwd<ACT>(v.x, to[t].x);
-                        v.y = act_bwd<ACT>(v.y, to[t].y);
-                        v.z = act_bwd<ACT>(v.z, to[t].z);
-                        v.w = act_bwd<ACT>(v.w, to[t].w);
-                    }
-                    acc.x += wv[t] * v.x;
-                    acc.y += wv[t] * v.y;
-                    acc.z += wv[t] * v.z;
-                    acc.w += wv[t] * v.w;
-                }
-            }
+            for (int t = 0; t < TAIL; ++t)
+                if (e + t < e1) term_add<KIND>(acc, wv[t], tv[t], to[t], tb[t]); // still in CSR order
         }
         float *yrow = a.y + row * a.c;
         unsigned sign_bits = 0u;
 #pragma unroll
         for (int i = 0; i <= NC; ++i) {
-            float4 v = i == 0 ? acc : own[i];
+            Pack<4> v;
+            v.v = i == 0 ? acc.v : own[i];
             if (!BACKWARD) {
-                if (a.bias) {
-                    const float4 bb = *reinterpret_cast<const float4 *>(a.bias + c0 + a.k * i);
-                    v.x += bb.x, v.y += bb.y, v.z += bb.z, v.w += bb.w;
-                }
-                v.x = act_fwd<ACT>(v.x), v.y = act_fwd<ACT>(v.y), v.z = act_fwd<ACT>(v.z), v.w = act_fwd<ACT>(v.w);
-                if (MASK) // out > 0, the predicate relu' is defined by (act_bwd)
-                    sign_bits |= ((v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u)) << (4 * i);
+                v.template bias_act<ACT, true>(a.bias, c0 + a.k * i);
+                if (MASK) sign_bits |= v.positive_bits() << (4 * i);
             }
-            *reinterpret_cast<float4 *>(yrow + c0 + a.k * i) = v;
+            v.store(yrow + c0 + a.k * i);
             if (!BACKWARD && HEAD && i == 0 && j == 0) { // new positions = base + scale * the three leading channels
                 const float *bp = a.head_in + row * 3;
                 float *pp = a.head_out + row * 3;
-                pp[0] = bp[0] + a.head_scale * v.x, pp[1] = bp[1] + a.head_scale * v.y, pp[2] = bp[2] + a.head_scale * v.z;
+#pragma unroll
+                for (int e = 0; e < 3; ++e) pp[e] = bp[e] + a.head_scale * v.at(e);
             }
         }
         if (!BACKWARD && MASK) a.mask[row * kg + j] = (unsigned short)sign_bits;
@@ -569,28 +698,6 @@ inline EllGeometry ell_geometry(int b, int nv, int k, bool backward)
     return g;
 }
 
-template <int ACT, bool BACKWARD, int NC, bool MASK = false, bool HEAD = false> // the table width as a template argument
-void launch_ell_w(const EllArgs &a, int w, const EllGeometry &geo, dim3 grid, size_t lds, hipStream_t s, float *partial)
-{
-    if (w == 8) hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 8, NC, MASK, HEAD>), grid, dim3(GCN_THREADS), lds, s, a, geo.rows_per_block, geo.iters, partial);
-    else hipLaunchKernelGGL((zn_aggregate_ell_kernel<ACT, BACKWARD, 16, NC, MASK, HEAD>), grid, dim3(GCN_THREADS), lds, s, a, geo.rows_per_block, geo.iters, partial);
-}
-
-template <int ACT, bool BACKWARD>
-void launch_ell_shape(const EllArgs &a, int w, int nc, const EllGeometry &geo, dim3 grid, size_t lds, hipStream_t s, float *partial)
-{
-    if (a.head_in) { // dispatch_ell admits it for split 3 with ReLU + mask or without activation only
-        if constexpr (ACT == ACT_RELU) launch_ell_w<ACT, BACKWARD, 2, true, true>(a, w, geo, grid, lds, s, partial);
-        else if constexpr (ACT == ACT_NONE) launch_ell_w<ACT, BACKWARD, 2, false, true>(a, w, geo, grid, lds, s, partial);
-        return;
-    }
-    if constexpr (ACT == ACT_RELU) {
-        if (a.mask && nc == 2) return launch_ell_w<ACT, BACKWARD, 2, true>(a, w, geo, grid, lds, s, partial);
-    }
-    if (nc == 2) launch_ell_w<ACT, BACKWARD, 2>(a, w, geo, grid, lds, s, partial);
-    else launch_ell_w<ACT, BACKWARD, 9>(a, w, geo, grid, lds, s, partial);
-}
-
 // ---------------------------------------------------------------------------------------
 // ELL table, ANY width and split: the unbatched ZERON_GCN layers of the mesh encoder (reference layers.py:34-41 with
 // models.py:299-348's widths: c = 60 ... 300, k = c / 10 = 6 ... 30 -- neither k % 4 == 0 nor c % k == 0 holds for most).
@@ -606,10 +713,12 @@ template <int VEC, int ACT, bool BACKWARD, int W>
 __global__ __launch_bounds__(GCN_THREADS) void zn_aggregate_ell_any_kernel(EllArgs a, int groups, int rows_in_flight, int rows_per_block,
                                                                             float *colsum_partial)
 {
+    using KIND = TermKind<VEC, ACT, BACKWARD>;
     extern __shared__ float lds_colsum[]; // [rows_in_flight][c], backward with colsum only
     const int r_begin = blockIdx.x * rows_per_block;
     const int r_end = min(r_begin + rows_per_block, a.nv);
     const int64_t mesh_row0 = (int64_t)blockIdx.y * a.nv;
+    const Source src{.x = a.x, .saved = a.saved, .c = a.c};
 
     // ---- the aggregated columns: COMPACT gather threads.  Item (row, j): group j < kgs of the row (kgs = the groups that hold
     // an aggregated column, the straddling one included); every lane of a wave gathers -- with the gathers left to the few
@@ -621,78 +730,18 @@ __global__ __launch_bounds__(GCN_THREADS) void zn_aggregate_ell_any_kernel(EllAr
         const int64_t row = mesh_row0 + r;
         int nb[W];
         float w[W];
-#pragma unroll
-        for (int n = 0; n < W; n += 4) { // round trip 1: the row's table entries
-            const int4 ci = *reinterpret_cast<const int4 *>(a.col + (size_t)r * W + n);
-            const float4 wi = *reinterpret_cast<const float4 *>(a.val + (size_t)r * W + n);
-            nb[n] = ci.x, nb[n + 1] = ci.y, nb[n + 2] = ci.z, nb[n + 3] = ci.w;
-            w[n] = wi.x, w[n + 1] = wi.y, w[n + 2] = wi.z, w[n + 3] = wi.w;
-        }
+        load_table_row<W>(a.col, a.val, r, nb, w); // round trip 1: the row's table entries
         int e0 = 0, e1 = 0;
         if (a.over_ptr) e0 = a.over_ptr[r], e1 = a.over_ptr[r + 1];
         Pack<VEC> sv[W], ov[W];
-#pragma unroll
-        for (int n = 0; n < W; ++n) { // round trip 2: the neighbour rows
-            const int64_t nrow = mesh_row0 + (nb[n] >= 0 ? nb[n] : r);
-            sv[n].load(a.x + nrow * a.c + c0);
-            if (BACKWARD && ACT != ACT_NONE) ov[n].load(a.saved + nrow * a.c + c0);
-        }
-        Pack<VEC> acc;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc.at(i) = 0.f;
-#pragma unroll
-        for (int n = 0; n < W; ++n) {
-            if (nb[n] >= 0) { // table order == CSR order of the row
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    float v = sv[n].at(i);
-                    if (BACKWARD && ACT != ACT_NONE) v = act_bwd<ACT>(v, ov[n].at(i));
-                    acc.at(i) += w[n] * v;
-                }
-            }
-        }
-        for (int e = e0; e < e1; e += GCN_NB) { // a row longer than the table: its CSR tail, still in order
-            int64_t tb[GCN_NB];
-            float tw[GCN_NB];
-#pragma unroll
-            for (int j = 0; j < GCN_NB; ++j) {
-                const bool in = e + j < e1;
-                tb[j] = in ? mesh_row0 + a.over_col[e + j] : row;
-                tw[j] = in ? a.over_val[e + j] : 0.f;
-            }
-            Pack<VEC> tv[GCN_NB], to[GCN_NB];
-#pragma unroll
-            for (int j = 0; j < GCN_NB; ++j) {
-                tv[j].load(a.x + tb[j] * a.c + c0);
-                if (BACKWARD && ACT != ACT_NONE) to[j].load(a.saved + tb[j] * a.c + c0);
-            }
-#pragma unroll
-            for (int j = 0; j < GCN_NB; ++j) {
-                if (e + j < e1) {
-#pragma unroll
-                    for (int i = 0; i < VEC; ++i) {
-                        float v = tv[j].at(i);
-                        if (BACKWARD && ACT != ACT_NONE) v = act_bwd<ACT>(v, to[j].at(i));
-                        acc.at(i) += tw[j] * v;
-                    }
-                }
-            }
-        }
-        if (!BACKWARD) {
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                float v = acc.at(i);
-                if (a.bias && c0 + i < a.k) v += a.bias[c0 + i];
-                acc.at(i) = act_fwd<ACT>(v);
-            }
-        }
-        if (c0 + VEC <= a.k) {
-            acc.store(a.y + row * a.c + c0);
-        } else { // the straddling group: its aggregated elements only (the others belong to the pass-through threads below)
-#pragma unroll
-            for (int i = 0; i < VEC; ++i)
-                if (c0 + i < a.k) a.y[row * a.c + c0 + i] = acc.at(i);
-        }
+        unsigned nbits[W] = {};
+        load_table_slots<KIND>(sv, ov, nbits, src, nb, mesh_row0, r, c0); // round trip 2: the neighbour rows
+        Pack<VEC> acc = Pack<VEC>::zero();
+        add_table_slots<KIND>(acc, sv, ov, nbits, nb, w);
+        add_csr_run<KIND>(acc, src, a.over_col, a.over_val, e0, e1, mesh_row0, row, c0); // a row longer than the table
+        // (the straddling group takes bias[c0 + i] for its columns >= k as well: in bounds, VEC divides c, and store_below drops them)
+        if (!BACKWARD) acc.template bias_act<ACT>(a.bias, c0);
+        acc.store_below(a.y + row * a.c, c0, a.k); // (the straddling group's other elements: the pass-through threads')
     }
 
     // ---- everything else, row-major: thread (rl, g) owns VEC consecutive columns of rows rl, rl + rows_in_flight, ...: the
@@ -703,57 +752,22 @@ __global__ __launch_bounds__(GCN_THREADS) void zn_aggregate_ell_any_kernel(EllAr
     const bool active = rl < rows_in_flight;
     const bool pass = c0 + VEC > a.k; // pass-through columns in the group (all, or the tail of the straddling group)
 
-    Pack<VEC> colsum;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) colsum.at(i) = 0.f;
+    Pack<VEC> colsum = Pack<VEC>::zero();
 
     if (active && (BACKWARD || pass)) {
         for (int r = r_begin + rl; r < r_end; r += rows_in_flight) {
             const int64_t row = mesh_row0 + r;
             Pack<VEC> own;
-            own.load(a.x + row * a.c + c0);
-            if (BACKWARD) {
-                if (ACT != ACT_NONE) {
-                    Pack<VEC> o;
-                    o.load(a.saved + row * a.c + c0);
-#pragma unroll
-                    for (int i = 0; i < VEC; ++i) own.at(i) = act_bwd<ACT>(own.at(i), o.at(i));
-                }
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) colsum.at(i) += own.at(i);
-            } else {
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    float v = own.at(i);
-                    if (a.bias) v += a.bias[c0 + i];
-                    own.at(i) = act_fwd<ACT>(v);
-                }
-            }
-            if (c0 >= a.k) {
-                own.store(a.y + row * a.c + c0);
-            } else if (pass) {
-#pragma unroll
-                for (int i = 0; i < VEC; ++i)
-                    if (c0 + i >= a.k) a.y[row * a.c + c0 + i] = own.at(i);
-            }
+            own_element<KIND>(own, src, row, c0);
+            if (BACKWARD) colsum.add(own);
+            else own.template bias_act<ACT>(a.bias, c0);
+            own.store_from(a.y + row * a.c, c0, a.k);
         }
     }
 
-    if (BACKWARD && colsum_partial) { // block partial of the bias gradient, fixed summation order
-        if (active) {
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) lds_colsum[rl * a.c + c0 + i] = colsum.at(i);
-        }
-        __syncthreads();
-        if (active && rl == 0) {
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                float t = 0.f;
-                for (int l = 0; l < rows_in_flight; ++l) t += lds_colsum[l * a.c + c0 + i];
-                colsum_partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * a.c + c0 + i] = t;
-            }
-        }
-    }
+    if (BACKWARD && colsum_partial) // block partial of the bias gradient, fixed summation order
+        write_colsum_partial(lds_colsum, colsum, active, rl, rows_in_flight, a.c, c0,
+                             colsum_partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * a.c);
 }
 
 inline GcnGeometry ell_any_geometry(int b, int nv, int c, bool backward)
@@ -771,23 +785,6 @@ inline GcnGeometry ell_any_geometry(int b, int nv, int c, bool backward)
     g.chunks = (nv + g.rows_per_block - 1) / g.rows_per_block;
     g.blocks = (int64_t)g.chunks * b;
     return g;
-}
-
-template <int VEC, int ACT, bool BACKWARD>
-void launch_ell_any_w(const EllArgs &a, int w, const GcnGeometry &geo, dim3 grid, size_t lds, hipStream_t s, float *partial)
-{
-    if (w == 8) hipLaunchKernelGGL((zn_aggregate_ell_any_kernel<VEC, ACT, BACKWARD, 8>), grid, dim3(GCN_THREADS), lds, s, a, geo.groups, geo.rows_in_flight, geo.rows_per_block, partial);
-    else hipLaunchKernelGGL((zn_aggregate_ell_any_kernel<VEC, ACT, BACKWARD, 16>), grid, dim3(GCN_THREADS), lds, s, a, geo.groups, geo.rows_in_flight, geo.rows_per_block, partial);
-}
-
-template <int ACT, bool BACKWARD>
-void launch_ell_any_vec(const EllArgs &a, int w, const GcnGeometry &geo, dim3 grid, size_t lds, hipStream_t s, float *partial)
-{
-    switch (ell_any_vec(a.c)) {
-    case 4: launch_ell_any_w<4, ACT, BACKWARD>(a, w, geo, grid, lds, s, partial); break;
-    case 2: launch_ell_any_w<2, ACT, BACKWARD>(a, w, geo, grid, lds, s, partial); break;
-    default: launch_ell_any_w<1, ACT, BACKWARD>(a, w, geo, grid, lds, s, partial); break;
-    }
 }
 
 // The table kernels' dispatcher.  Its checks are the CSR dispatcher's with the table's own in between; where the two differ:
@@ -819,26 +816,33 @@ int dispatch_ell(EllArgs a, int b, int w, int act, float *grad_bias, float *scra
         const GcnGeometry geo = ell_any_geometry(b, a.nv, a.c, BACKWARD);
         const size_t lds = (BACKWARD && partial) ? (size_t)geo.rows_in_flight * a.c * sizeof(float) : 0;
         const dim3 grid((unsigned)geo.chunks, (unsigned)b);
-        switch (act) {
-        case ACT_NONE: launch_ell_any_vec<ACT_NONE, BACKWARD>(a, w, geo, grid, lds, s, partial); break;
-        case ACT_RELU: launch_ell_any_vec<ACT_RELU, BACKWARD>(a, w, geo, grid, lds, s, partial); break;
-        case ACT_ELU: launch_ell_any_vec<ACT_ELU, BACKWARD>(a, w, geo, grid, lds, s, partial); break;
-        default: return GEOM_EINVAL;
-        }
-        return finish_launch(BACKWARD, geo.blocks, a.c, partial, grad_bias, s);
+        const bool known = with_act(act, [&](auto ACT) { with_width(w, [&](auto W) { with_vec(ell_any_vec(a.c), [&](auto VEC) {
+            hipLaunchKernelGGL((zn_aggregate_ell_any_kernel<decltype(VEC)::value, decltype(ACT)::value, BACKWARD, decltype(W)::value>),
+                               grid, dim3(GCN_THREADS), lds, s, a, geo.groups, geo.rows_in_flight, geo.rows_per_block, partial);
+        }); }); });
+        return known ? finish_launch(BACKWARD, geo.blocks, a.c, partial, grad_bias, s) : GEOM_EINVAL;
     }
     const EllGeometry geo = ell_geometry(b, a.nv, a.k, BACKWARD);
     const size_t lds = (BACKWARD && partial) ? (size_t)geo.rows_per_block * a.c * sizeof(float) : 0;
     a.b = b, a.chunks = geo.chunks;
     const dim3 grid(geom::xcd_grid(b, geo.chunks));
-    const int nc = route == ELL_FAST3 ? 2 : 9;
-    switch (act) {
-    case ACT_NONE: launch_ell_shape<ACT_NONE, BACKWARD>(a, w, nc, geo, grid, lds, s, partial); break;
-    case ACT_RELU: launch_ell_shape<ACT_RELU, BACKWARD>(a, w, nc, geo, grid, lds, s, partial); break;
-    case ACT_ELU: launch_ell_shape<ACT_ELU, BACKWARD>(a, w, nc, geo, grid, lds, s, partial); break;
-    default: return GEOM_EINVAL;
-    }
-    return finish_launch(BACKWARD, geo.blocks, a.c, partial, grad_bias, s);
+    const bool known = with_act(act, [&](auto ACT) { with_width(w, [&](auto W) {
+        constexpr int A = decltype(ACT)::value;
+        auto go = [&](auto NC, auto MASK, auto HEAD) {
+            hipLaunchKernelGGL((zn_aggregate_ell_kernel<A, BACKWARD, decltype(W)::value, decltype(NC)::value, decltype(MASK)::value, decltype(HEAD)::value>),
+                               grid, dim3(GCN_THREADS), lds, s, a, geo.rows_per_block, geo.iters, partial);
+        };
+        // head: split 3 with ReLU + mask or without activation only, and the sign mask: ReLU at split 3 only (checked above)
+        if constexpr (A == ACT_RELU) {
+            if (a.head_in) return go(Const<2>{}, std::true_type{}, std::true_type{});
+            if (a.mask) return go(Const<2>{}, std::true_type{}, std::false_type{});
+        } else if constexpr (A == ACT_NONE) {
+            if (a.head_in) return go(Const<2>{}, std::false_type{}, std::true_type{});
+        }
+        if (route == ELL_FAST3) go(Const<2>{}, std::false_type{}, std::false_type{});
+        else go(Const<9>{}, std::false_type{}, std::false_type{});
+    }); });
+    return known ? finish_launch(BACKWARD, geo.blocks, a.c, partial, grad_bias, s) : GEOM_EINVAL;
 }
 
 template <bool BACKWARD>

@@ -69,6 +69,22 @@ def uv_sphere(rings=15, segments=32):
     return V, F
 
 
+def hub_ring_adjacency(n=70, reach=5, hubs=((0, 41), (35, 27)), seed=16):
+    """A graph for the WIDTH-16 neighbour table (no triangle mesh has one): a ring lattice, every vertex joined to itself and
+    its +-reach ring neighbours (11 entries per row), with the rows of `hubs` raised to the given entry counts by extra
+    partners drawn with `seed` and mirrored -- two rows far longer than 16, every other row at most 11 + len(hubs).
+    Returns the dense float32 [n, n] 0/1 pattern ROW-NORMALISED: symmetric in structure, not in value."""
+    pat = np.zeros((n, n), np.float32)
+    for d in range(-reach, reach + 1):
+        pat[np.arange(n), (np.arange(n) + d) % n] = 1.0
+    rng = np.random.default_rng(seed)
+    for hub, entries in hubs:
+        free = [v for v in np.flatnonzero(pat[hub] == 0) if v not in [h for h, _ in hubs]]
+        pick = rng.choice(free, entries - int(pat[hub].sum()), replace=False)
+        pat[hub, pick] = pat[pick, hub] = 1.0
+    return pat / pat.sum(1, keepdims=True)
+
+
 def jittered_batch(verts, batch, first=0, sigma=0.02, seed=41):
     """Per-mesh Gaussian vertex jitter, seed 41+b (41 = the reference's default --seed)."""
     out = np.empty((batch,) + verts.shape, np.float32)
