@@ -331,3 +331,132 @@ def pool_vertex_gradient_close(got, blocks, verts, cam_mat, cam_pos, grad_out, w
     worst = rows_close(got[live], grad[live], mass[live], POOL_ROW_RTOL, what, floor=floor[live], floor_ulps=POOL_FLOOR_ULPS)
     return {"keep": keep, "zero_rows": int((grad == 0).all(-1).sum()), "zero_checked": int(zero.sum()), "live_rows": int(live.sum()),
             "worst": worst}
+
+
+# ---- the per-vertex BatchNorm + ReLU + residual average in float64, with every output's term mass (csrc/vertex_bn.hip) ----------
+BN_EPS32 = 2.0 ** -24
+# the longest chain of fp32 additions in either kernel's reduction (16 values per thread, 6 shuffle steps, 4 wave partials) + the
+# project's allowance of 8 for the products around it (test_layer_gradients_element_by_element_against_float64)
+BN_ROW_RTOL = (16 + 6 + 4 + 8) * BN_EPS32
+BN_EVAL_RTOL = 8 * BN_EPS32        # eval mode: no reduction in the forward
+BN_MAX_KNIFE = 1e-3                # share of a case's elements that may sit on the ReLU's kink (a condition, not a measurement)
+
+
+def vertex_bn64(x, gamma, beta, eps, relu, residual, scale, grad_out, grad_out2=None, running=None, momentum=None,
+                old_running=None, rtol=None):
+    """`(residual + act(BatchNorm1d(verts)(x))) * scale` on [B,V,C] and its backward in FLOAT64 on the host (numpy): one statistic
+    per vertex over its n = B * C values.  Training mode (running is None) generalises bn64: batch statistics, biased variance in
+    the normalisation; eval mode normalises with running = (mean, var).  gamma / beta None = 1 / 0; residual None = no residual
+    (the scale is then 1); grad_out None = forward only.
+
+    Returns (exact, mass, knife): two dicts keyed out, pre (the value the ReLU is applied to), save_mean, var, save_invstd,
+    running_mean, running_var (training with old_running = (mean, var) and momentum; the variance unbiased when n > 1), grad_x,
+    grad_residual, grad_weight, grad_bias -- `mass` holds what an fp32 evaluation's round-off of that output is proportional to,
+    whatever cancels (helpers.rows_close): with s = 1 / sqrt(var + eps), xh = (x - mean) s, D = s |mean| (the mean's own rounding
+    seen in normalised units), k = |gamma| s, gy = |grad_out + grad_out2| * scale * relu', P = mean gy, Q = mean(gy |xh|):
+        out            scale (|residual| + |gamma| (|xh| + D) + |beta|)
+        grad_x         k (gy + P + |xh| Q + D (Q + |xh| P))
+        grad_weight    sum gy (|xh| + D)            grad_bias   sum gy
+        var            var                          running_var   (1 - m) |old| + m var n / (n - 1)
+        save_mean      mean |x|                     running_mean  (1 - m) |old| + m mean |x|          save_invstd   s
+    knife [B,V,C] bool: the elements on the ReLU's kink -- |pre| <= 2 * rtol * (the mass of pre): an fp32 evaluation may take
+    the other branch there.  They are to be left out of the forward comparison, and the gradients returned here are those of
+    the upstream gradient with zeros at them (hand the kernel the same: `grad_out * ~knife`).  rtol defaults to BN_ROW_RTOL
+    (BN_EVAL_RTOL in eval mode)."""
+    x = np.asarray(x, np.float64)
+    b, nv, c = x.shape
+    n = b * c
+    training = running is None
+    if rtol is None:
+        rtol = BN_ROW_RTOL if training else BN_EVAL_RTOL
+    col = lambda t: np.asarray(t, np.float64).reshape(1, nv, 1)
+    g = col(gamma) if gamma is not None else np.ones((1, nv, 1))
+    be = col(beta) if beta is not None else np.zeros((1, nv, 1))
+    mean_abs = np.abs(x).mean(axis=(0, 2))
+    if training:
+        mean = x.mean(axis=(0, 2))
+        var = ((x - col(mean)) ** 2).mean(axis=(0, 2))
+    else:
+        mean, var = (np.asarray(t, np.float64) for t in running)
+    s = 1.0 / np.sqrt(var + eps)
+    xh = (x - col(mean)) * col(s)
+    D = col(s * np.abs(mean))
+    pre = xh * g + be
+    pre_mass = np.abs(g) * (np.abs(xh) + D) + np.abs(be)
+    knife = (np.abs(pre) <= 2.0 * rtol * pre_mass) if relu else np.zeros(x.shape, bool)
+    act = np.maximum(pre, 0.0) if relu else pre
+    exact = {"pre": pre, "save_mean": mean, "var": var, "save_invstd": s}
+    mass = {"pre": pre_mass, "save_mean": mean_abs, "var": var, "save_invstd": s}
+    if residual is not None:
+        r = np.asarray(residual, np.float64)
+        exact["out"], mass["out"] = (r + act) * scale, abs(scale) * (np.abs(r) + pre_mass)
+    else:
+        scale = 1.0
+        exact["out"], mass["out"] = act, pre_mass
+    if training and old_running is not None:
+        old_mean, old_var = (np.asarray(t, np.float64) for t in old_running)
+        unbiased = var * (n / (n - 1.0)) if n > 1 else var
+        exact["running_mean"] = (1 - momentum) * old_mean + momentum * mean
+        mass["running_mean"] = (1 - momentum) * np.abs(old_mean) + momentum * mean_abs
+        exact["running_var"] = (1 - momentum) * old_var + momentum * unbiased
+        mass["running_var"] = (1 - momentum) * np.abs(old_var) + momentum * unbiased
+    if grad_out is not None:
+        go = np.asarray(grad_out, np.float64) + (0.0 if grad_out2 is None else np.asarray(grad_out2, np.float64))
+        go = go * ~knife
+        exact["grad_residual"] = go * scale
+        dact = (pre > 0.0) if relu else np.ones(x.shape, bool)
+        gy = go * scale * dact
+        ay, axh = np.abs(gy), np.abs(xh)
+        sum_g, sum_gx = gy.sum(axis=(0, 2)), (gy * xh).sum(axis=(0, 2))
+        exact["grad_bias"], mass["grad_bias"] = sum_g, ay.sum(axis=(0, 2))
+        exact["grad_weight"], mass["grad_weight"] = sum_gx, (ay * (axh + D)).sum(axis=(0, 2))
+        exact["grad_x"] = g * col(s) * (gy - col(sum_g / n) - xh * col(sum_gx / n))
+        P, Q = col(ay.mean(axis=(0, 2))), col((ay * axh).mean(axis=(0, 2)))
+        mass["grad_x"] = np.abs(g) * col(s) * (ay + P + axh * Q + D * (Q + axh * P))
+    return exact, mass, knife
+
+
+# ---- the regularisers of one deformation stage term by term (csrc/regularizers.hip) ------------------------------------------------
+def stage_regularisers_chain(prev, cur, adj_orig, faces, c_lap, c_move, c_edge, gout, absolute=False, ulps=False):
+    """c_edge * sum_faces(|e1|^2 + |e2|^2 + |e3|^2)(cur) + c_lap * sum |lap(prev - cur)|^2 + c_move * sum |prev - cur|^2 and its
+    gradients, written out term by term in the dtype of `cur` (torch, host): {"value", "lapd" = lap(prev - cur) [B,V,3],
+    "grad_prev" = gout * d value / d (prev - cur), "grad_edge" = the edge term's share of grad_cur, "grad_cur" = grad_edge -
+    grad_prev}.  lap(d)[v] = d[v] - (sum_{j in row v} d[j] - d[v]) / deg[v] with the rows of the binary adjacency `adj_orig`
+    (self loops included), its transpose the same with 1 / deg[j] inside the sum (ref_ops.lap_info, utils.py:654-662).
+    absolute: the same chain with every matrix entry, every coordinate difference and every term replaced by its absolute
+    value -- the masses of rows_close (the value is not formed).  ulps (with absolute): every coordinate difference replaced
+    by one fp32 ulp of the two coordinates it is formed from, |a| + |b| -- the floor of rows_close."""
+    import torch
+    one_ulp = float(np.finfo(np.float32).eps)
+    A = adj_orig.to(cur.dtype)
+    inv_deg = (1.0 / (A.sum(1) - 1)).view(-1, 1)
+    pv = prev if prev.dim() == 3 else prev.unsqueeze(0)
+
+    def diff(a, b):
+        if ulps:
+            return one_ulp * (a.abs() + b.abs())
+        return (a - b).abs() if absolute else a - b
+
+    sign = 1.0 if absolute else -1.0
+    d = diff(pv, cur)
+    lapd = d + sign * (torch.matmul(A, d) + sign * d) * inv_deg
+    lt = lapd + sign * (torch.matmul(A, lapd * inv_deg) + sign * lapd * inv_deg)
+    grad_prev = (lt * (2.0 * c_lap) + d * (2.0 * c_move)) * abs(gout) if absolute else (lt * (2.0 * c_lap) + d * (2.0 * c_move)) * gout
+    out = {"lapd": lapd, "grad_prev": grad_prev}
+    grad_edge = torch.zeros_like(cur)
+    if c_edge != 0.0 and faces.shape[0]:
+        i1, i2, i3 = faces[:, 0], faces[:, 1], faces[:, 2]
+        p1, p2, p3 = cur[:, i1], cur[:, i2], cur[:, i3]
+        e1, e2, e3 = diff(p2, p1), diff(p3, p1), diff(p2, p3)
+        grad_edge.index_add_(1, i1, (e1 + e2) * (1.0 if absolute else -1.0))
+        grad_edge.index_add_(1, i2, e1 + e3)
+        grad_edge.index_add_(1, i3, e2 + sign * e3)
+        grad_edge = grad_edge * (2.0 * c_edge * (abs(gout) if absolute else gout))
+        edge_value = c_edge * ((e1 ** 2).sum() + (e2 ** 2).sum() + (e3 ** 2).sum())
+    else:
+        edge_value = 0.0
+    out["grad_edge"] = grad_edge
+    out["grad_cur"] = grad_edge + sign * grad_prev
+    if not absolute:
+        out["value"] = edge_value + c_lap * (lapd ** 2).sum() + c_move * (d ** 2).sum()
+    return out

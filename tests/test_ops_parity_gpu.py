@@ -10,7 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import bits, fp64_surface_gradient, golden, pool_vertex_gradient_close, rows_close
+from helpers import bits, fp64_surface_gradient, golden, pool_vertex_gradient_close, rows_close, stage_regularisers_chain
 from geometrics_amd import backward_pass, layers, meshgen, ops, utils
 from oracle import ref_ops
 
@@ -583,6 +583,160 @@ def test_stage_regularisers_against_the_drivers_expressions(gpu, mesh, template_
     assert abs(w.item() - 0.2 * a.item()) <= 1e-6 * abs(a.item())
 
 
+STAGE_REG_CASES = ("template_482_b1", "faces_outnumber_lanes", "ico42_faces_cut", "ico162_b3_no_edge", "ico162_b3_template_prev",
+                   "ico42_vertex_without_faces")
+
+
+def stage_regulariser_case(name):
+    """Host tensors of a case of the per-element stage-regulariser tests: (prev, cur, faces the kernels are given, the binary
+    adjacency, (w_lap, w_move, w_edge)).
+      template_482_b1          482 vertices, one mesh: 3856 lanes, the last workgroup part vertices and part idle
+      faces_outnumber_lanes    6 vertices, 60 faces drawn from them with repetition (nf > 8 nv: the faces set the forward grid and
+                               the vertex lanes run out first), the adjacency built from those faces
+      ico42_faces_cut          icosphere(1) with its last 3 faces taken out of `faces` only: corner lists shorter than their rows
+      ico162_b3_no_edge        three meshes, edge weight 0: the vertex -> corner tables are null
+      ico162_b3_template_prev  three meshes, the [V,3] template as prev
+      ico42_vertex_without_faces   icosphere(1) with every face of vertex 0 and all but one face of its last vertex taken out of
+                               `faces` only: an empty corner list and a list of one"""
+    rng = np.random.default_rng([545, STAGE_REG_CASES.index(name)])
+    weights = (300.0, 20.0, 0.0 if name == "ico162_b3_no_edge" else 300.0)
+    b = 3 if name.startswith("ico162") else 1
+    if name == "faces_outnumber_lanes":
+        V = rng.uniform(-0.5, 0.5, (6, 3)).astype(np.float32)
+        Fc = np.stack([rng.permutation(6)[:3] for _ in range(60)]).astype(np.int64)
+        assert Fc.max() == 5 and Fc.shape[0] > 8 * V.shape[0]
+    else:
+        V, Fc = meshgen.uv_sphere() if name == "template_482_b1" else meshgen.icosphere(2 if name.startswith("ico162") else 1)
+    adj_orig = utils.calc_adj(torch.from_numpy(np.ascontiguousarray(Fc, dtype=np.int64)))
+    if name == "ico42_faces_cut":
+        Fc = Fc[:-3]
+    elif name == "ico42_vertex_without_faces":
+        last = np.flatnonzero((Fc == Fc.max()).any(1))
+        assert not (Fc[last] == 0).any()
+        Fc = np.delete(Fc, last[1:], axis=0)
+        Fc = Fc[(Fc != 0).all(1)]
+    base = torch.from_numpy(np.ascontiguousarray(V, dtype=np.float32))
+    noise = lambda: torch.from_numpy((0.05 * rng.standard_normal((b,) + tuple(base.shape))).astype(np.float32))
+    cur = base.unsqueeze(0) + noise()
+    prev = base if name == "ico162_b3_template_prev" else base.unsqueeze(0) + noise()
+    return prev, cur, torch.from_numpy(np.ascontiguousarray(Fc, dtype=np.int64)), adj_orig, weights
+
+
+def stage_regulariser_bounds(prev, cur, faces, adj_orig, weights, gout):
+    """float64 values, masses and floors of a case (helpers.stage_regularisers_chain; the chain itself is held to the oracle's
+    restatements ref_ops.lap_info / ref_ops.calc_edge under autograd), the coefficients and rtol = (row_terms + 8) * 2^-24,
+    row_terms = the longest adjacency row or corner list of the mesh."""
+    b, nv, nf = cur.shape[0], cur.shape[1], faces.shape[0]
+    coef = (weights[0] / (b * nv), weights[1] / (b * nv), weights[2] / (3.0 * b * nf) if nf else 0.0)
+    p64, c64, a64 = prev.double(), cur.double(), adj_orig.double()
+    exact = stage_regularisers_chain(p64, c64, a64, faces, *coef, gout)
+    mass = stage_regularisers_chain(p64, c64, a64, faces, *coef, gout, absolute=True)
+    floor = stage_regularisers_chain(p64, c64, a64, faces, *coef, gout, absolute=True, ulps=True)
+    pa, ca = p64.clone().requires_grad_(True), c64.clone().requires_grad_(True)
+    ref = (weights[2] * ref_ops.calc_edge(ca, faces) + weights[0] * torch.mean(torch.sum((ref_ops.lap_info(pa, a64) - ref_ops.lap_info(ca, a64)) ** 2, -1))
+           + weights[1] * torch.mean(torch.sum((pa - ca) ** 2, -1)))
+    (ref * gout).backward()
+    scale = float(ca.grad.abs().max())
+    ref = ref.detach()
+    assert abs(float(ref) - float(exact["value"])) <= 1e-12 * abs(float(ref))
+    assert float((ca.grad - exact["grad_cur"]).abs().max()) <= 1e-12 * scale
+    if prev.dim() == 3:
+        assert float((pa.grad - exact["grad_prev"]).abs().max()) <= 1e-12 * scale
+    assert float((ref_ops.lap_info(p64 - c64, a64) - exact["lapd"]).abs().max()) <= 1e-12
+    corners = np.bincount(faces.reshape(-1).numpy(), minlength=nv)
+    row_terms = max(int(adj_orig.sum(1).max()), int(corners.max()))
+    return exact, mass, floor, coef, (row_terms + 8) * 2.0 ** -24, corners
+
+
+def stage_regulariser_outputs_close(got, exact, mass, floor, rtol, what, worst_allowed=1.0):
+    """lapd, grad_cur and (when present) grad_prev of `got` within rtol * mass + 1 ulp-floor, element by element."""
+    for key in ("lapd", "grad_cur", "grad_prev"):
+        if key in got:
+            worst = rows_close(got[key], exact[key].numpy(), mass[key].numpy(), rtol, "stage regularisers %s %s" % (what, key),
+                               floor[key].numpy(), ROW_FLOOR_ULPS)
+            assert worst <= worst_allowed, (what, key, worst)
+
+
+@pytest.mark.parametrize("case", STAGE_REG_CASES)
+def test_stage_regularisers_element_by_element_against_float64(gpu, case):
+    """The max-norm 1e-5 of the test above passes a wrong low-gradient vertex.  Here every element of grad_cur, grad_prev and the
+    saved lap(prev - cur) is held to (row_terms + 8) * 2^-24 of the sum of the absolute values of ITS OWN terms + one coordinate
+    ulp through each of them (the kernel forms prev - cur and the edge vectors as fp32 differences of coordinates), the value to
+    1e-6 -- at the launch shapes no other test has (stage_regulariser_case).  The same chain in fp32 torch on the host stays
+    under half of the bounds: no term is missing from the masses."""
+    prev, cur, faces, adj_orig, weights = stage_regulariser_case(case)
+    gout = 0.7
+    exact, mass, floor, coef, rtol, corners = stage_regulariser_bounds(prev, cur, faces, adj_orig, weights, gout)
+    b, nv, nf = cur.shape[0], cur.shape[1], faces.shape[0]
+    if case == "template_482_b1":
+        assert (8 * nv) % 256 != 0 and 8 * nv > nf
+    elif case == "faces_outnumber_lanes":
+        assert nf > 8 * nv
+    elif case == "ico42_faces_cut":
+        assert (corners < adj_orig.sum(1).numpy() - 1).any() and corners.min() >= 1
+    elif case == "ico42_vertex_without_faces":
+        assert corners[0] == 0 and corners[-1] == 1
+    host = stage_regularisers_chain(prev, cur, adj_orig, faces, *coef, gout)
+    keys = ("lapd", "grad_cur") + (("grad_prev",) if prev.dim() == 3 else ())
+    stage_regulariser_outputs_close({k: host[k].numpy() for k in keys}, exact, mass, floor, rtol, case + " (fp32 on the host)", 0.5)
+    assert abs(float(host["value"]) - float(exact["value"])) <= 1e-6 * abs(float(exact["value"]))
+    csr = layers.adjacency_csr(adj_orig.to(gpu))
+    assert int((csr.rowptr[1:] - csr.rowptr[:-1]).max()) == int(adj_orig.sum(1).max())
+    p_d, c_d = prev.to(gpu).requires_grad_(prev.dim() == 3), cur.to(gpu).requires_grad_(True)
+    loss = ops.StageRegularisers.apply(p_d, c_d, faces.to(gpu), csr.rowptr, csr.col, csr.inv_deg, *weights)
+    lapd = loss.grad_fn.saved_tensors[6]
+    assert lapd.shape == cur.shape
+    (loss * gout).backward()
+    assert abs(loss.item() - float(exact["value"])) <= 1e-6 * abs(float(exact["value"])), (loss.item(), float(exact["value"]))
+    got = {"lapd": lapd.cpu().numpy(), "grad_cur": c_d.grad.cpu().numpy()}
+    if prev.dim() == 3:
+        got["grad_prev"] = p_d.grad.cpu().numpy()
+    stage_regulariser_outputs_close(got, exact, mass, floor, rtol, case)
+
+
+@pytest.mark.parametrize("case", STAGE_REG_CASES[:2])
+def test_laplacian_and_edge_operators_element_by_element_against_float64(gpu, case):
+    """ops.Laplacian (both directions) and ops.EdgeSqLenSum on the 482-vertex template at one mesh and on the mesh whose faces
+    outnumber its vertex lanes, against the same float64 chain and masses.  The edge backward adds with float atomics: held
+    to the same mass, its bits are not."""
+    prev, cur, faces, adj_orig, _ = stage_regulariser_case(case)
+    a64 = adj_orig.double()
+    csr = layers.adjacency_csr(adj_orig.to(gpu))
+    nv = cur.shape[1]
+    rtol = (max(int(adj_orig.sum(1).max()), int(np.bincount(faces.reshape(-1).numpy(), minlength=nv).max())) + 8) * 2.0 ** -24
+    # both directions of lap against ref_ops.lap_info (the backward under autograd); the masses: the same sums of absolute values
+    inv_deg = (1.0 / (a64.sum(1) - 1)).view(-1, 1)
+    x = cur.to(gpu).requires_grad_(True)
+    lap = ops.Laplacian.apply(x, csr.rowptr, csr.col, csr.inv_deg)
+    g = torch.from_numpy(np.random.default_rng(586).standard_normal(tuple(cur.shape)).astype(np.float32))
+    lap.backward(g.to(gpu))
+    x64, g64 = cur.double(), g.double()
+    assert float((ref_ops.lap_info(x64, a64) - (x64 - (a64 @ x64 - x64) * inv_deg)).abs().max()) <= 1e-12
+    rows_close(lap.detach().cpu().numpy(), ref_ops.lap_info(x64, a64).numpy(), (x64.abs() + (a64 @ x64.abs() + x64.abs()) * inv_deg).numpy(),
+               rtol, "Laplacian forward " + case)
+    xa = x64.clone().requires_grad_(True)
+    ref_ops.lap_info(xa, a64).backward(g64)
+    rows_close(x.grad.cpu().numpy(), xa.grad.numpy(), (g64.abs() + a64 @ (g64.abs() * inv_deg) + g64.abs() * inv_deg).numpy(),
+               rtol, "Laplacian backward " + case)
+    # sum over faces of the three squared edge lengths, times an upstream gradient
+    up = 0.3
+    v = cur.to(gpu).requires_grad_(True)
+    total = ops.EdgeSqLenSum.apply(v, faces.to(gpu))
+    (total * up).backward()
+    zero = torch.zeros_like(cur).double()
+    exact = stage_regularisers_chain(zero, cur.double(), a64, faces, 0.0, 0.0, 1.0, up)
+    mass = stage_regularisers_chain(zero, cur.double(), a64, faces, 0.0, 0.0, 1.0, up, absolute=True)
+    floor = stage_regularisers_chain(zero, cur.double(), a64, faces, 0.0, 0.0, 1.0, up, absolute=True, ulps=True)
+    va = cur.double().requires_grad_(True)
+    ref = ref_ops.calc_edge(va, faces) * (3.0 * cur.shape[0] * faces.shape[0])
+    (ref * up).backward()
+    ref = ref.detach()
+    assert float((va.grad - exact["grad_edge"]).abs().max()) <= 1e-12 * float(va.grad.abs().max())
+    assert abs(total.item() - float(ref)) <= 1e-6 * abs(float(ref)), (total.item(), float(ref))
+    rows_close(v.grad.cpu().numpy(), exact["grad_edge"].numpy(), mass["grad_edge"].numpy(), rtol, "EdgeSqLenSum backward " + case,
+               floor["grad_edge"].numpy(), ROW_FLOOR_ULPS)
+
+
 def test_laplacian_on_the_reference_template_mesh(gpu):
     """482.obj has two degree-32 poles: long CSR rows, and the dense product as the checker."""
     g = golden("adj_482")
@@ -661,8 +815,9 @@ def test_tapped_layer_output_sums_its_two_gradients_in_the_batchnorm_backward(gp
     the same memory (`tap`); their two upstream gradients are added inside `geom_vertex_bn_bwd_f32` (grad_out2) instead of
     by autograd's accumulation pass.  Against the untapped layer given the pre-added gradient: outputs, running
     statistics and every gradient BIT for bit (one fp32 add either way) -- at the reference's training shape (16 x 482
-    vertices, two 33-entry pole rows -> table + CSR tail in the aggregation), on a pole-free mesh (scalar BN kernel: 48
-    columns x 5 rows), and on an adjacency with irregular degrees (generic aggregation kernel)."""
+    vertices, two 33-entry pole rows -> table + CSR tail in the aggregation), on a pole-free mesh (48 columns x 5 rows: the
+    float4 BN kernels as well -- the scalar backward with a second gradient is held in tests/test_vertex_bn_gpu.py), and on an
+    adjacency with irregular degrees (generic aggregation kernel)."""
     import copy
     from geometrics_amd import meshgen, models
     torch.manual_seed(11)
