@@ -112,3 +112,29 @@ def backward(g, csr, k, act, out, mask, want_bias, bias=None, arena=None, head=N
     elif bg.defer:
         bg.finish(int(_lib.lib().geom_zn_gcn_bwd_partial_rows(b, nv, c, k, ell_w)))
     return grad_support, bg.out
+
+
+# ---- the narrow head: the head layer of a stack, of whose output only the three position columns are ever read -------------
+def narrow_head_forward(s, bias_c, csr, k, act, base, scale, pos, want_sign):
+    """pos = base + scale * act([A . s[..., :k] | ...] + bias)[..., :3] from column group 0 of the rows alone -- the wide head's
+    steps in its order, so its bits; no [B,V,C] output.  Returns the ReLU sign words ([B*V] int16) when asked for, else None."""
+    b, nv, c = s.shape
+    sign = torch.empty(b * nv, dtype=torch.int16, device=s.device) if want_sign and act == ACT_RELU else None
+    with torch.cuda.device(s.device):
+        _lib.call("geom_zn_gcn_narrow_head_fwd_f32", b, nv, c, k, *_table(csr, False), s.data_ptr(), _lib.ptr(bias_c), act,
+                  base.data_ptr(), float(scale), pos.data_ptr(), _lib.ptr(sign))
+    return sign
+
+
+def narrow_head_backward(grad_pos, scale, sign, csr, k, act, shape, want_bias, bias=None):
+    """(columns 0..3 of the wide head's support gradient as [B*V, 4] -- its other columns are zero -- and the bias gradient,
+    whose partials keep the wide backward's partition and go to the reductions the wide head uses)."""
+    b, nv, c = shape
+    gs4 = torch.empty(b * nv, 4, dtype=torch.float32, device=grad_pos.device)
+    rows = int(_lib.lib().geom_zn_gcn_bwd_partial_rows(b, nv, c, k, csr.ell_w))
+    bg = _pass.bias_gradient(bias, c, grad_pos.device, (rows, c)) if want_bias else _pass.NO_BIAS_GRADIENT
+    with torch.cuda.device(grad_pos.device):
+        _lib.call("geom_zn_gcn_narrow_head_bwd_f32", b, nv, c, k, *_table(csr, True), grad_pos.data_ptr(), float(scale),
+                  _lib.ptr(sign), act, gs4.data_ptr(), _lib.ptr(bg.scratch))
+    bg.finish(rows)
+    return gs4, bg.out

@@ -789,6 +789,133 @@ __global__ __launch_bounds__(DG_THREADS, 2) void dense_bwd_pair_kernel(RowArgs r
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// NARROW pair: both gradients of the 192 x 192 product whose output gradient G is zero beyond column 2 (the last layer of a
+// stack that ends in positions: geometrics_amd.layers._NarrowHead).  G arrives as its four leading columns, g4 [rows, 4]
+// with column 3 zero.  An fp32 MFMA is a k-ordered fmaf chain and fma(0, w, acc) == acc for finite w, so of the pair kernel's
+// sums only the terms of the live columns are left, and a plain VALU chain in the pair kernel's order gives its bits:
+//   dX role: dX[r][i] = fmaf(g2, W[i][2], fmaf(g1, W[i][1], fmaf(g0, W[i][0], 0)))  -- rows_body meets k = 0, 1, 2 in that order;
+//            a streaming write, W[:, 0..3] read in place (pitch 192) into registers;
+//   dW role: one workgroup per (tile, split) slot of split_geometry(192, rows, cus): P[slot][il][j] for j < 3 = the fmaf chain of
+//            X[t][i0 + il] * g4[t][j] over the split's rows t_begin .. t_end ascending, as split_body walks them; column 3 and
+//            columns 4..191 of the slot's tile are +0.  The chain is serial in t, so all 256 threads stage the slot's rows of X
+//            (48 columns: the four tiles of a split are neighbouring workgroups and read whole rows between them) through
+//            LDS, NP_CHUNK rows per round with the next round's loads in flight, and lanes 0..47 of wave 0 run the chains.
+// The partial tiles keep split_body's layout: the reduction launch, its Adam epilogue and the bucket binding do not change.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int NP_CW = 192;      // the product's width, both ways
+constexpr int NP_RA = SPLIT_RB_NARROW * 16; // 48 rows of dW per tile
+constexpr int NP_CHUNK = 128;   // rows of X per staging round
+constexpr int NP_DX_ROWS = 64;  // rows of dX per workgroup: 12 float4 per thread
+struct NarrowPairArgs {
+    const float *x;  // [rows, 192]
+    const float *g4; // [rows, 4]
+    const float *w;  // [192, 192]
+    float *grad_x;   // [rows, 192]; null: the dW role alone
+    float *part;     // [slots][48][192]
+    int rows, full_tiles, s_full;
+};
+
+__device__ __forceinline__ void narrow_dw_role(const NarrowPairArgs &q, const int w)
+{
+    constexpr int XP = NP_CHUNK * (NP_RA / 4) / DG_THREADS; // float4 loads of X per thread and round
+    static_assert(NP_CHUNK * (NP_RA / 4) % DG_THREADS == 0 && NP_CHUNK <= DG_THREADS, "whole staging passes");
+    __shared__ __attribute__((aligned(16))) float xs[2][NP_CHUNK * NP_RA];
+    __shared__ f32x4 gs[2][NP_CHUNK];
+    const int tid = threadIdx.x;
+    const int tile = w % q.full_tiles, split = w / q.full_tiles;
+    const int slot = tile * q.s_full + split, i0 = tile * NP_RA;
+    const int n4 = (q.rows + 3) / 4;
+    const int t_begin = (int)((int64_t)n4 * split / q.s_full) * 4;
+    const int t_end = min((int)((int64_t)n4 * (split + 1) / q.s_full) * 4, q.rows);
+    const int nch = (t_end - t_begin + NP_CHUNK - 1) / NP_CHUNK;
+    float *dst = q.part + (int64_t)slot * NP_RA * NP_CW;
+
+    f32x4 xr[XP], gr = {0.f, 0.f, 0.f, 0.f};
+    auto load = [&](int ch) { // rows beyond the operand are clamped; the chains stop at t_end
+        const int t0 = t_begin + ch * NP_CHUNK;
+#pragma unroll
+        for (int p = 0; p < XP; ++p) {
+            const int e = p * DG_THREADS + tid;
+            const int t = min(t0 + e / (NP_RA / 4), q.rows - 1);
+            xr[p] = *reinterpret_cast<const f32x4 *>(q.x + (int64_t)t * NP_CW + i0 + (e % (NP_RA / 4)) * 4);
+        }
+        if (tid < NP_CHUNK) gr = *reinterpret_cast<const f32x4 *>(q.g4 + (int64_t)min(t0 + tid, q.rows - 1) * 4);
+    };
+    if (nch > 0) load(0);
+    // the dead columns of the tile: +0 (column group 0 is the chains')
+    for (int e = tid; e < NP_RA * (NP_CW / 4); e += DG_THREADS)
+        if (e % (NP_CW / 4) != 0) *reinterpret_cast<f32x4 *>(dst + (int64_t)e * 4) = (f32x4){0.f, 0.f, 0.f, 0.f};
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    for (int ch = 0; ch < nch; ++ch) {
+        const int buf = ch & 1;
+#pragma unroll
+        for (int p = 0; p < XP; ++p) {
+            const int e = p * DG_THREADS + tid;
+            *reinterpret_cast<f32x4 *>(&xs[buf][(e / (NP_RA / 4)) * NP_RA + (e % (NP_RA / 4)) * 4]) = xr[p];
+        }
+        if (tid < NP_CHUNK) gs[buf][tid] = gr;
+        __syncthreads();
+        if (ch + 1 < nch) load(ch + 1);
+        if (tid < NP_RA) {
+            const int n = min(NP_CHUNK, t_end - (t_begin + ch * NP_CHUNK));
+#pragma unroll 8
+            for (int t = 0; t < n; ++t) {
+                const float xv = xs[buf][t * NP_RA + tid];
+                const f32x4 gv = gs[buf][t];
+                a0 = __builtin_fmaf(xv, gv[0], a0);
+                a1 = __builtin_fmaf(xv, gv[1], a1);
+                a2 = __builtin_fmaf(xv, gv[2], a2);
+            }
+        }
+    }
+    if (tid < NP_RA) *reinterpret_cast<f32x4 *>(dst + (int64_t)tid * NP_CW) = (f32x4){a0, a1, a2, 0.f};
+}
+
+__device__ __forceinline__ void narrow_dx_role(const NarrowPairArgs &q, const int w)
+{
+    constexpr int GROUPS = NP_CW / 4;                          // float4 groups of a row
+    constexpr int PASSES = NP_DX_ROWS * GROUPS / DG_THREADS;   // 12
+    constexpr int CLASSES = 3;                                 // 256 % 48 == 16: a thread meets three column groups in turn
+    static_assert((DG_THREADS * CLASSES) % GROUPS == 0 && PASSES % CLASSES == 0, "the column groups of a thread repeat every 3 passes");
+    const int tid = threadIdx.x;
+    const int64_t row0 = (int64_t)w * NP_DX_ROWS;
+    float wr[CLASSES][4][3];
+#pragma unroll
+    for (int cl = 0; cl < CLASSES; ++cl) {
+        const int cg = (cl * DG_THREADS + tid) % GROUPS;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(q.w + (int64_t)(4 * cg + i) * NP_CW);
+            wr[cl][i][0] = v[0], wr[cl][i][1] = v[1], wr[cl][i][2] = v[2];
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+        const int e = p * DG_THREADS + tid;
+        const int64_t row = row0 + e / GROUPS;
+        const int cg = e % GROUPS;
+        if (row < q.rows) {
+            const f32x4 gv = *reinterpret_cast<const f32x4 *>(q.g4 + row * 4);
+            f32x4 o;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float *wi = wr[p % CLASSES][i];
+                o[i] = __builtin_fmaf(gv[2], wi[2], __builtin_fmaf(gv[1], wi[1], __builtin_fmaf(gv[0], wi[0], 0.f)));
+            }
+            *reinterpret_cast<f32x4 *>(q.grad_x + row * NP_CW + 4 * cg) = o;
+        }
+    }
+}
+
+// the dW slots first: their serial chains set the launch's length, the streaming dX workgroups fill in beside them
+__global__ __launch_bounds__(DG_THREADS) void dense_bwd_narrow_kernel(NarrowPairArgs q, int n_split)
+{
+    const int w = blockIdx.x;
+    if (w < n_split) narrow_dw_role(q, w);
+    else narrow_dx_role(q, w - n_split);
+}
+
 // out[i][j] = sum over the splits of tile(i) of part[slot][i % RA][j], in slot order.  One thread per 4 columns.
 struct ReduceJob {
     const float *part;
@@ -1137,6 +1264,25 @@ extern "C" int geom_dense_bwd_f32(int rows, int cin, int c, const float *x, cons
         hipLaunchKernelGGL((dense_bwd_pair_kernel<decltype(rb)::value, SPLIT_RB_NARROW, true>), dim3(rg.grid + sg.slots),
                            dim3(DG_THREADS), 0, s, r, q, rg.grid);
     });
+}
+
+// geom_dense_bwd_f32 for a 192 x 192 product whose output gradient is zero beyond column 2, given as g4 [rows, 4] (column 3
+// zero): grad_x (null: not wanted) and the partial tiles of grad_w in `workspace`, slot for slot what geom_dense_bwd_f32 writes
+// for the [rows, 192] gradient [g4 | 0] -- finite operands: where that entry point multiplies a non-finite x or w by a zero of G
+// and gets NaN, this one keeps the zero.  geom_dense_reduce_f32 finishes the partials as usual.
+extern "C" int geom_dense_bwd_narrow_f32(int rows, int cin, int c, const float *x, const float *g4, const float *w, float *grad_x,
+                                         float *workspace, void *stream)
+{
+    if (rows < 1 || cin <= 0 || c <= 0) return GEOM_EINVAL;
+    if (cin != NP_CW || c != NP_CW || (int64_t)rows * NP_CW >= (1LL << 30)) return GEOM_EUNSUPPORTED;
+    if (!x || !g4 || !workspace || !aligned16(x) || !aligned16(g4) || !aligned16(workspace)) return GEOM_EINVAL;
+    if (grad_x && (!w || !aligned16(w) || !aligned16(grad_x))) return GEOM_EINVAL;
+    const SplitGeo sg = split_geometry(cin, rows, num_cus());
+    if (sg.rb != SPLIT_RB_NARROW || sg.left_rb != 0 || sg.full_tiles < 1) return GEOM_EUNSUPPORTED;
+    const NarrowPairArgs q{x, g4, w, grad_x, workspace, rows, sg.full_tiles, sg.s_full};
+    const int n_dx = grad_x ? (rows + NP_DX_ROWS - 1) / NP_DX_ROWS : 0;
+    hipLaunchKernelGGL(dense_bwd_narrow_kernel, dim3(sg.slots + n_dx), dim3(DG_THREADS), 0, static_cast<hipStream_t>(stream), q, sg.slots);
+    return geom::launch_status();
 }
 
 namespace {

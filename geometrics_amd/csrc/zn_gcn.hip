@@ -845,6 +845,141 @@ int dispatch_ell(EllArgs a, int b, int w, int act, float *grad_bias, float *scra
     return known ? finish_launch(BACKWARD, geo.blocks, a.c, partial, grad_bias, s) : GEOM_EINVAL;
 }
 
+// ---------------------------------------------------------------------------------------
+// NARROW HEAD: the head layer when nobody reads its output beyond the three position columns (the last layer of a stack,
+// geometrics_amd.layers._NarrowHead).  Only float4 group j = 0 of the aggregated slice reaches the positions, and in the
+// backward only that group of the support gradient is non-zero, so both directions run thread (row, j = 0) of the fast
+// kernel above and nothing else -- the same steps in the same order (table slots, then the CSR tail; term_load / term_add;
+// Pack::bias_act), hence the same bits as the wide head's column group 0.  No [rows, c] tensor is written or read.
+// ---------------------------------------------------------------------------------------
+constexpr int NARROW_THREADS = 64; // forward: one row per lane, one wave per workgroup (the launch is a chain of three round trips)
+constexpr int NARROW_PARTIAL_ROWS = 32; // rows per bias-gradient partial: the fast backward's rows_per_block * iters at k = 64
+
+struct NarrowHeadArgs {
+    const int *col;
+    const float *val;
+    const int *over_ptr, *over_col;
+    const float *over_val;
+    const float *support, *bias; // forward: [rows, c], [c] (may be null)
+    const float *base;           // forward: [rows, 3]
+    float *pos;                  // forward: [rows, 3]
+    const float *grad_pos;       // backward: [rows, 3]
+    unsigned short *sign;        // ReLU: one word per row, bit e <-> element e of the row's first float4 (null: no activation)
+    float *gs;                   // backward: [rows, 4] = the support gradient's columns 0..3 (column 3 is zero)
+    float *partial;              // backward: [meshes * chunks, c] column-sum partials, zero beyond column 2 (null: none)
+    float scale;
+    int nv, c, b, chunks;
+};
+
+template <int ACT, int W>
+__global__ __launch_bounds__(NARROW_THREADS) void zn_narrow_head_fwd_kernel(NarrowHeadArgs a)
+{
+    int mesh_i, chunk_i;
+    if (!geom::xcd_assign(blockIdx.x, a.b, a.chunks, mesh_i, chunk_i)) return;
+    const int r = chunk_i * NARROW_THREADS + threadIdx.x;
+    if (r >= a.nv) return;
+    const int64_t mesh_row0 = (int64_t)mesh_i * a.nv, row = mesh_row0 + r;
+    using KIND = TermKind<4, ACT, false>;
+    const Source src{.x = a.support, .c = a.c};
+    int nb[W];
+    float w[W];
+    load_table_row<W>(a.col, a.val, r, nb, w);
+    int e0 = 0, e1 = 0;
+    if (a.over_ptr) e0 = a.over_ptr[r], e1 = a.over_ptr[r + 1];
+    Pack<4> sv[W], ov[W];
+    unsigned nbits[W] = {};
+    load_table_slots<KIND>(sv, ov, nbits, src, nb, mesh_row0, r, 0);
+    Pack<4> acc = Pack<4>::zero();
+    add_table_slots<KIND>(acc, sv, ov, nbits, nb, w);
+    add_csr_run<KIND>(acc, src, a.over_col, a.over_val, e0, e1, mesh_row0, row, 0); // a row longer than the table
+    acc.template bias_act<ACT, true>(a.bias, 0);
+    if (ACT == ACT_RELU && a.sign) a.sign[row] = (unsigned short)acc.positive_bits();
+    const float *bp = a.base + row * 3;
+    float *pp = a.pos + row * 3;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) pp[e] = bp[e] + a.scale * acc.at(e);
+}
+
+// One workgroup per bias-gradient partial of the wide head's backward: NARROW_PARTIAL_ROWS rows of one mesh, lane l < 32 owns
+// row l.  The partial's three live columns are summed as the fast kernel sums them: thread rl of its 16 adds its two rows
+// (tile 0, then tile 1) from zero, the sixteen sums are then added in rl order from zero.
+template <int ACT, int W>
+__global__ __launch_bounds__(NARROW_THREADS) void zn_narrow_head_bwd_kernel(NarrowHeadArgs a)
+{
+    __shared__ float4 own_lds[NARROW_PARTIAL_ROWS];
+    int mesh_i, chunk_i;
+    if (!geom::xcd_assign(blockIdx.x, a.b, a.chunks, mesh_i, chunk_i)) return;
+    const int rl = threadIdx.x;
+    const int r = chunk_i * NARROW_PARTIAL_ROWS + rl;
+    const int64_t mesh_row0 = (int64_t)mesh_i * a.nv, row = mesh_row0 + r;
+    using KIND = TermKind<4, ACT, true, ACT == ACT_RELU, true>;
+    const Source src{.mask = a.sign, .kg = 1, .j = 0, .head = a.grad_pos, .head_scale = a.scale, .c = a.c};
+    if (rl < NARROW_PARTIAL_ROWS) {
+        Pack<4> own = Pack<4>::zero();
+        if (r < a.nv) {
+            int nb[W];
+            float w[W];
+            load_table_row<W>(a.col, a.val, r, nb, w);
+            int e0 = 0, e1 = 0;
+            if (a.over_ptr) e0 = a.over_ptr[r], e1 = a.over_ptr[r + 1];
+            own_element<KIND>(own, src, row, 0);
+            Pack<4> sv[W], ov[W];
+            unsigned nbits[W] = {};
+            load_table_slots<KIND>(sv, ov, nbits, src, nb, mesh_row0, r, 0);
+            Pack<4> acc = Pack<4>::zero();
+            add_table_slots<KIND>(acc, sv, ov, nbits, nb, w);
+            add_csr_run<KIND>(acc, src, a.over_col, a.over_val, e0, e1, mesh_row0, row, 0);
+            acc.store(a.gs + row * 4);
+        }
+        own_lds[rl] = own.v; // zeros for the rows beyond the mesh
+    }
+    if (!a.partial) return;
+    __syncthreads();
+    float *prow = a.partial + ((size_t)mesh_i * a.chunks + chunk_i) * a.c;
+    for (int col = threadIdx.x; col < a.c; col += NARROW_THREADS) {
+        float t = 0.f;
+        if (col < 4) {
+            constexpr int HALF = NARROW_PARTIAL_ROWS / 2;
+            for (int l = 0; l < HALF; ++l) {
+                float cs = 0.f;
+                cs += elements(own_lds[l])[col];
+                cs += elements(own_lds[l + HALF])[col];
+                t += cs;
+            }
+        }
+        prow[col] = t;
+    }
+}
+
+template <bool BACKWARD>
+int dispatch_narrow_head(NarrowHeadArgs a, int k, int w, int act, void *stream)
+{
+    if (const int code = check_sizes(a.b, a.nv, a.c, k)) return code;
+    // the wide head's shapes (split 3, a table, ReLU with sign words or no activation) at the width whose backward partials are
+    // NARROW_PARTIAL_ROWS rows each
+    if (ell_route(a.c, k, w) != ELL_FAST3 || (act != ACT_RELU && act != ACT_NONE)) return GEOM_EUNSUPPORTED;
+    const EllGeometry wide = ell_geometry(a.b > 0 ? a.b : 1, a.nv > 0 ? a.nv : 1, k, true);
+    if (wide.rows_per_block * wide.iters != NARROW_PARTIAL_ROWS) return GEOM_EUNSUPPORTED;
+    if (!BACKWARD && (!a.base || !a.pos)) return GEOM_EINVAL;
+    if (BACKWARD && !a.grad_pos) return GEOM_EINVAL;
+    if (a.b == 0 || a.nv == 0) return 0;
+    if (!a.col || !a.val || (BACKWARD ? !a.gs : !a.support)) return GEOM_EINVAL;
+    if (BACKWARD && act == ACT_RELU && !a.sign) return GEOM_EINVAL;
+    if (act == ACT_NONE && a.sign) return GEOM_EINVAL;
+    if (a.over_ptr && (!a.over_col || !a.over_val)) return GEOM_EINVAL;
+    if ((((uintptr_t)a.col | (uintptr_t)a.val | (uintptr_t)a.support | (uintptr_t)a.bias | (uintptr_t)a.gs) % 16) != 0) return GEOM_EINVAL;
+    if (a.b > 65535) return GEOM_ETOOBIG;
+    a.chunks = BACKWARD ? wide.chunks : (a.nv + NARROW_THREADS - 1) / NARROW_THREADS;
+    const dim3 grid(geom::xcd_grid(a.b, a.chunks));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    with_act(act, [&](auto ACT) { with_width(w, [&](auto W) {
+        constexpr int A = decltype(ACT)::value == ACT_RELU ? ACT_RELU : ACT_NONE; // (ELU was refused above)
+        if (BACKWARD) hipLaunchKernelGGL((zn_narrow_head_bwd_kernel<A, decltype(W)::value>), grid, dim3(NARROW_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((zn_narrow_head_fwd_kernel<A, decltype(W)::value>), grid, dim3(NARROW_THREADS), 0, s, a);
+    }); });
+    return geom::launch_status();
+}
+
 template <bool BACKWARD>
 int dispatch(GcnArgs a, int b, int act, float *grad_bias, float *scratch, void *stream)
 {
@@ -969,4 +1104,26 @@ extern "C" int geom_zn_gcn_aggregate_ell_head_bwd_f32(int b, int nv, int c, int 
     EllArgs a{.col = ell_colT, .val = ell_valT, .y = grad_support, .nv = nv, .c = c, .k = k, .mask = const_cast<uint16_t *>(relu_mask),
               .over_ptr = over_ptrT, .over_col = over_colT, .over_val = over_valT, .head_in = grad_pos, .head_scale = scale};
     return dispatch_ell<true>(a, b, w, act, grad_bias, scratch, stream);
+}
+
+extern "C" int geom_zn_gcn_narrow_head_fwd_f32(int b, int nv, int c, int k, int w, const int *ell_col, const float *ell_val,
+                                               const int *over_ptr, const int *over_col, const float *over_val,
+                                               const float *support, const float *bias, int act, const float *base,
+                                               float scale, float *pos, uint16_t *sign_words, void *stream)
+{
+    NarrowHeadArgs a{.col = ell_col, .val = ell_val, .over_ptr = over_ptr, .over_col = over_col, .over_val = over_val,
+                     .support = support, .bias = bias, .base = base, .pos = pos, .sign = sign_words, .scale = scale,
+                     .nv = nv, .c = c, .b = b};
+    return dispatch_narrow_head<false>(a, k, w, act, stream);
+}
+
+extern "C" int geom_zn_gcn_narrow_head_bwd_f32(int b, int nv, int c, int k, int w, const int *ell_colT, const float *ell_valT,
+                                               const int *over_ptrT, const int *over_colT, const float *over_valT,
+                                               const float *grad_pos, float scale, const uint16_t *sign_words, int act,
+                                               float *grad_support4, float *partials, void *stream)
+{
+    NarrowHeadArgs a{.col = ell_colT, .val = ell_valT, .over_ptr = over_ptrT, .over_col = over_colT, .over_val = over_valT,
+                     .grad_pos = grad_pos, .sign = const_cast<uint16_t *>(sign_words), .gs = grad_support4, .partial = partials,
+                     .scale = scale, .nv = nv, .c = c, .b = b};
+    return dispatch_narrow_head<true>(a, k, w, act, stream);
 }

@@ -179,6 +179,15 @@ def backward_pair(x, g, w, grad_x, workspace, want_colsum=False):
                   workspace.data_ptr(), 1 if want_colsum else 0)
 
 
+def backward_narrow(x, g4, w, grad_x, workspace):
+    """backward_pair for a gradient that is zero beyond column 2, given as its leading columns g4 [rows, 4] (column 3 zero):
+    grad_x [rows, 192] (None: not wanted) and the partial tiles of x.T @ [g4 | 0], bit for bit backward_pair's."""
+    rows, cin = x.shape
+    with torch.cuda.device(x.device):
+        _lib.call("geom_dense_bwd_narrow_f32", rows, cin, w.shape[1], x.data_ptr(), g4.data_ptr(), w.data_ptr(), _lib.ptr(grad_x),
+                  workspace.data_ptr())
+
+
 def reduce(jobs, stream=None):
     """jobs = [(rows, cin, c, workspace, grad_w, grad_bias or None)]: all pending weight / bias gradients in ONE launch."""
     n = len(jobs)

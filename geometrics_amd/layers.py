@@ -9,6 +9,7 @@ the tensor's identity + version) and replaces the reference's dense `adj @ suppo
 kernel computes the feature product `input @ W` and its gradients is `products.route()`'s decision.
 """
 import math
+import os
 import weakref
 
 import torch
@@ -343,6 +344,104 @@ class _FusedBoundary(torch.autograd.Function):
         return (grad_support if need_s else None), grad_bias, grad_w, None, None, None, None, None
 
 
+# ---- the last layer of a stack that ends in positions, narrowed to the three columns that reach them ---------------------------
+# zero_n_stack_positions returns base + scale * h[..., :3]: of the last layer's 192 output columns three are read, and its output
+# gradient is [scale * grad_pos | 0 ...].  The wide route (product, _ZeroNAggregateHead, the pair launch of _Product) still
+# writes a [rows, 192] output nobody reads and a [rows, 192] support gradient whose columns 3.. are zero, and multiplies those
+# zeros through both gradient products.  _NarrowHead joins the product and the head in one node and keeps the live columns only;
+# every tensor it hands on carries the wide route's bits (csrc/zn_gcn.hip "NARROW HEAD", csrc/dense_gemm.hip "NARROW pair").
+# Used from NARROW_HEAD_MIN_ROWS rows: it moves fewer bytes at every size and the whole step is 7.6-9.4 % faster with it at 1, 2, 4
+# and 8 meshes of 2562 vertices (profiles/r08_narrow_head.txt, section 3); the threshold keeps the small shapes on the launches
+# their tests pin and goes no lower than the smallest multi-mesh shard measured (2 x 2562 rows).
+NARROW_HEAD_MIN_ROWS = 4096
+
+# None: the rule above, or the environment's GEOM_NARROW_HEAD = on | off;  "on" / "off": force the narrow route wherever the
+# operands qualify, whatever the row count / the wide route everywhere (tests, A/B measurements of one tree)
+narrow_head = None
+
+
+def _narrow_head_mode():
+    mode = narrow_head if narrow_head is not None else (os.environ.get("GEOM_NARROW_HEAD") or None)
+    if mode not in (None, "on", "off"):
+        raise ValueError("GEOM_NARROW_HEAD / layers.narrow_head must be 'on' or 'off' (got %r)" % (mode,))
+    return mode
+
+
+def _narrow_head_takes(h, layer, adj, activation, base):
+    """Whether the last layer of a stack, applied to `h` with no fused boundary below it, takes _NarrowHead: exactly where the wide
+    route is the fused head (zero_n_aggregate_head's rule) on a product routed Route(dx="pair", dw="split") of 192 x 192."""
+    mode = _narrow_head_mode()
+    if mode == "off" or current_slabs() is not None:
+        return False
+    w, bias = layer._weight(), layer.bias
+    if not (torch.is_tensor(h) and h.dim() == 3 and layer.split == 3 and w.dim() in (2, 3) and tuple(w.shape[-2:]) == (192, 192)
+            and (w.dim() == 2 or w.shape[0] == 1) and h.shape[-1] == 192):
+        return False
+    for t in (h, w, base) + (() if bias is None else (bias,)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == h.device):
+            return False
+    if not w.requires_grad or base.shape != h.shape[:-1] + (3,) or (bias is not None and bias.shape != (192,)):
+        return False
+    act, foreign, batched, csr = _route(activation, h, adj)
+    if not batched or foreign or act == _ACT_ELU or not csr.ell_w or csr.nv != h.shape[1]:
+        return False
+    rows = h.shape[0] * h.shape[1]
+    r = _products.route(rows, 192, 192, True, True, True, False, _products._own_products_preferred(), _products.use_any_shape_products)
+    # (Route(dx="pair"): the input gradient is never the one a leaf has postponed to the end of the pass)
+    return r.dx == "pair" and r.dw == "split" and (mode == "on" or rows >= NARROW_HEAD_MIN_ROWS)
+
+
+class _NarrowHead(torch.autograd.Function):
+    """positions = base + scale * act([A . S[..., :k] | S[..., k:]] + bias)[..., :3] with S = x @ W, k = 64: the last layer's
+    product (the kernel `_dense` picks: S keeps its bits, and so do the positions) and its head in one node.  Backward: the
+    head's backward on column group 0, then both gradients of the product from the [rows, 4] support gradient in one launch;
+    weight and bias gradients go to the end-of-pass reduction as the wide nodes' do."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, base, csr, act, scale, forward_kind):
+        w2 = w.reshape(w.shape[-2:])
+        x, s = _products._forward(forward_kind, x, w2)
+        if s.shape[1] != csr.nv:
+            raise RuntimeError("support has %d vertices but the adjacency has %d" % (s.shape[1], csr.nv))
+        pos = torch.empty_like(base)
+        k = s.shape[-1] // 3
+        sign = _agg.narrow_head_forward(s, bias, csr, k, act, base, scale, pos, want_sign=any(ctx.needs_input_grad[:3]))
+        ctx.csr, ctx.k, ctx.act, ctx.scale = csr, k, act, float(scale)
+        ctx.w_ref = _pass.parameter_ref(w, ctx, ctx.needs_input_grad[1])
+        ctx.bias_ref = _pass.parameter_ref(bias, ctx, ctx.needs_input_grad[2])
+        ctx.save_for_backward(x, w, *([sign] if sign is not None else []))
+        return pos
+
+    @staticmethod
+    def backward(ctx, grad_pos):
+        gp = grad_pos.contiguous()
+        x, w = ctx.saved_tensors[:2]
+        sign = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+        need_x, need_w, need_b, need_base = ctx.needs_input_grad[:4]
+        b, nv, cin = x.shape
+        rows, c = b * nv, w.shape[-1]
+        dx = grad_w = grad_bias = None
+        if need_x or need_w or need_b:
+            need_b = need_b and ctx.bias_ref is not None
+            gs4, grad_bias = _agg.narrow_head_backward(gp, ctx.scale, sign, ctx.csr, ctx.k, ctx.act, (b, nv, c), need_b,
+                                                       ctx.bias_ref() if need_b else None)
+        if need_x or need_w:
+            ws = _products._dense_kernels.weight_workspace(rows, cin, c, x.device)
+            dx = torch.empty_like(x) if need_x else None
+            _products._dense_kernels.backward_narrow(x.view(rows, cin), gs4, w.reshape(w.shape[-2:]), None if dx is None else dx.view(rows, cin), ws)
+            if need_w:
+                grad_w = _pass.weight_gradient(ctx.w_ref, w, rows, cin, c, ws)
+        return dx, grad_w, grad_bias, (gp if need_base else None), None, None, None, None
+
+
+def _narrow_head_positions(h, layer, adj, activation, base, scale):
+    act, _, _, csr = _route(activation, h, adj)
+    w = layer._weight()
+    rows = h.shape[0] * h.shape[1]
+    r = _products.route(rows, 192, 192, True, True, True, False, _products._own_products_preferred(), _products.use_any_shape_products)
+    return _NarrowHead.apply(h, w, layer.bias, base, csr, act, scale, r.forward)
+
+
 def _boundary_fuses(rows, csr, prev, layer):
     """Whether the boundary between `prev` and `layer` takes the single launch (csr: None unless the stack's input is batched
     and its activation one the kernels know)."""
@@ -355,11 +454,14 @@ def _boundary_fuses(rows, csr, prev, layer):
     return _fused.supported(csr, c, c // 3, w.shape[-1]) and _fused.plan(rows)["fwd"]
 
 
-def _stack_supports(x, adj, stack, activation):
-    """The front of a stack up to the support of its last layer: (support, link of the last boundary)."""
+def _stack_walk(x, adj, stack, activation, base=None):
+    """The front of a stack: (support of its last layer, link of the last boundary, False) -- or, given the `base` of a
+    coordinate update and a last layer that takes _NarrowHead, (INPUT of the last layer, None, True)."""
     act, foreign, _, csr = _route(activation, x, adj)
     if foreign:          # (a foreign callable is applied between the operators)
         csr = None
+    if len(stack) == 1 and base is not None and _narrow_head_takes(x, stack[0], adj, activation, base):
+        return x, None, True
     s = _dense(x, stack[0]._weight())
     link = None
     for prev, layer in zip(stack[:-1], stack[1:]):
@@ -368,9 +470,17 @@ def _stack_supports(x, adj, stack, activation):
             s = _FusedBoundary.apply(s, prev.bias, layer._weight(), csr, _split_k(s, prev), act, up, link)
             link = up
         else:
-            s = _dense(zero_n_aggregate(s, adj, prev.bias, _split_k(s, prev), activation), layer._weight())
+            h = zero_n_aggregate(s, adj, prev.bias, _split_k(s, prev), activation)
+            if layer is stack[-1] and base is not None and _narrow_head_takes(h, layer, adj, activation, base):
+                return h, None, True
+            s = _dense(h, layer._weight())
             link = None
-    return s, link
+    return s, link, False
+
+
+def _stack_supports(x, adj, stack, activation):
+    """The front of a stack up to the support of its last layer: (support, link of the last boundary)."""
+    return _stack_walk(x, adj, stack, activation)[:2]
 
 
 def zero_n_stack(x, adj, stack, activation):
@@ -382,8 +492,11 @@ def zero_n_stack(x, adj, stack, activation):
 
 
 def zero_n_stack_positions(x, adj, stack, activation, base, scale):
-    """base + scale * zero_n_stack(x, adj, stack, activation)[..., :3] -- the coordinate update of a deformation stage."""
-    s, link = _stack_supports(x, adj, stack, activation)
+    """base + scale * zero_n_stack(x, adj, stack, activation)[..., :3] -- the coordinate update of a deformation stage.  Where the
+    last layer has no fused boundary below it and qualifies (_narrow_head_takes), only the three columns are computed of it."""
+    s, link, narrow = _stack_walk(x, adj, stack, activation, base)
+    if narrow:
+        return _narrow_head_positions(s, stack[-1], adj, activation, base, scale)
     return zero_n_aggregate_head(s, adj, stack[-1].bias, _split_k(s, stack[-1]), activation, base, scale, down=link)
 
 
@@ -406,6 +519,8 @@ class _ZeroNBase(Module):
     def forward_positions(self, input, adj, activation, base, scale):
         """base + scale * self(input, adj, activation)[..., :3] -- the coordinate update of a deformation stage
         (GEOMetrics.py:121,126,131) without materialising the layer output's gradient (see zero_n_aggregate_head)."""
+        if _narrow_head_takes(input, self, adj, activation, base):
+            return _narrow_head_positions(input, self, adj, activation, base, scale)
         support = _dense(input, self._weight())
         return zero_n_aggregate_head(support, adj, self.bias, _split_k(support, self), activation, base, scale)
 

@@ -292,6 +292,14 @@ int geom_dense_bwd_weight_f32(int rows, int cin, int c, const float *x, const fl
  * cin <= 192 and x rows are 16-byte aligned, the two launches above otherwise.  workspace / reduction as above. */
 int geom_dense_bwd_f32(int rows, int cin, int c, const float *x, const float *g, const float *w, float *grad_x,
                        float *workspace, int want_colsum, void *stream);
+/* geom_dense_bwd_f32 for the 192 x 192 product (cin == c == 192, else GEOM_EUNSUPPORTED) whose output gradient is zero beyond
+ * column 2 -- the last layer of a stack that ends in positions.  g4 [rows, 4] = that gradient's columns 0..3, column 3 zero.
+ * grad_x [rows, 192] (NULL: not wanted) and the partial tiles of grad_w in `workspace` carry the bits geom_dense_bwd_f32 leaves
+ * for g = [g4 | 0] (an fp32 MFMA is a k-ordered fmaf chain and fma(0, w, acc) == acc), in the same slot layout: the
+ * reduction entry points finish them unchanged.  FINITE operands only: geom_dense_bwd_f32 multiplies x and w by the zero
+ * columns (0 * inf = NaN), this entry point never reads what meets them and keeps the zero. */
+int geom_dense_bwd_narrow_f32(int rows, int cin, int c, const float *x, const float *g4, const float *w, float *grad_x,
+                              float *workspace, void *stream);
 /* geom_dense_reduce_f32 + `ncs` column-sum jobs (cs_outs[i] = column sums of the cs_rows[i] x cs_cols[i] row-major cs_partials[i],
  * cs_cols % 4 == 0) in the same launch: the bias gradients of the aggregation backward join the weight gradients. */
 int geom_dense_reduce2_f32(int count, const int *rows, const int *cin, const int *c, const float *const *workspaces,
@@ -325,6 +333,26 @@ int geom_zn_gcn_aggregate_ell_head_bwd_f32(int b, int nv, int c, int k, int w, c
                                            const float *over_valT, const float *grad_pos, float scale,
                                            const uint16_t *relu_mask, int act, float *grad_support,
                                            float *grad_bias, float *scratch, void *stream);
+
+/* NARROW head: the head when nothing but the positions is read of the layer's output (the last layer of a stack).  Same
+ * shapes as the HEAD mode at k == 64 (split 3, c == 192; ReLU or act == 0; else GEOM_EUNSUPPORTED); only float4 group 0 of the
+ * rows is computed, by the wide kernel's steps in the wide kernel's order: the same bits, and no [b*nv, c] tensor is written.
+ *   forward : pos[r,:] = base[r,:] + scale * act(sum_table val * support[nb, 0..3] + bias[0..3])[0..2];  sign_words [b*nv]
+ *             (ReLU: bit e <-> element e > 0; NULL when no gradient is wanted; must be NULL for act == 0);
+ *   backward: grad_support4 [b*nv, 4] = columns 0..3 of the wide backward's grad_support (column 3 is zero; its columns 4..c-1
+ *             are zero by construction and not written), and -- partials != NULL -- the [geom_zn_gcn_bwd_partial_rows, c]
+ *             bias-gradient partials of the wide backward, zero beyond column 2, for geom_colsum_batch_f32 / the reduction
+ *             entry points.
+ * FINITE operands only: the wide head multiplies the zero columns of its gradient by the table's weights, and the wide
+ * product after it by the layer's weights (0 * inf = NaN); the narrow route never forms those products and keeps the zeros. */
+int geom_zn_gcn_narrow_head_fwd_f32(int b, int nv, int c, int k, int w, const int *ell_col, const float *ell_val,
+                                    const int *over_ptr, const int *over_col, const float *over_val,
+                                    const float *support, const float *bias, int act, const float *base,
+                                    float scale, float *pos, uint16_t *sign_words, void *stream);
+int geom_zn_gcn_narrow_head_bwd_f32(int b, int nv, int c, int k, int w, const int *ell_colT, const float *ell_valT,
+                                    const int *over_ptrT, const int *over_colT, const float *over_valT,
+                                    const float *grad_pos, float scale, const uint16_t *sign_words, int act,
+                                    float *grad_support4, float *partials, void *stream);
 
 /* ---- a whole layer boundary in ONE launch (csrc/zn_stack.hip; layers.py:107-116 across two consecutive layers) --------
  * The aggregation of one layer is fused into the operand load of the product that follows it (forward) / precedes it
