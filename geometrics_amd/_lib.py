@@ -38,6 +38,7 @@ DeformBwd = _header.STRUCTS["geom_deform_bwd"]
 DeformInfer = _header.STRUCTS["geom_deform_infer"]
 SurfaceCull = _header.STRUCTS["geom_surface_cull"]
 SurfaceTail = _header.STRUCTS["geom_surface_tail"]
+FaceSplit = _header.STRUCTS["geom_face_split"]
 
 # ---- package-wide reference-quirk mode (SURVEY quirk register Q1 / Q3) ------------------------------------------------
 # The shipped CUDA kernels drop the tail of every 512-wide tile of targets / triangles (chamfer_distance.cu:31-33,

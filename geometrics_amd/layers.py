@@ -126,6 +126,9 @@ def adjacency_csr(adj):
     key = id(adj)
     hit = _csr_cache.get(key)
     if hit is not None and hit[0]() is adj and hit[1] == adj._version:
+        if not hasattr(hit[2], "ell_w"):          # handed over by register_csr: its derived tables are made at first use
+            with torch.no_grad():
+                _finish_csr(hit[2])
         return hit[2]
     if not adj.is_cuda:
         raise RuntimeError("adjacency must live on a HIP device; geometrics_amd has no CPU path")
@@ -137,6 +140,30 @@ def adjacency_csr(adj):
         _finish_csr(c)
     _csr_cache[key] = (weakref.ref(adj, lambda _ref, k=key: _csr_cache.pop(k, None)), adj._version, c)
     return c
+
+
+def register_csr(adj, csr):
+    """Hand over the CSR (+ CSR^T) of the dense adjacency `adj` that its maker already has (utils.split_info fills the dense
+    matrix FROM the CSR): adjacency_csr(adj) then returns this object instead of reading the matrix back through nonzero().
+    csr: a _Csr (csr_from_parts), or the six arrays of csr_from_parts as a tuple -- registering those reads nothing on the
+    host; the derived tables (_finish_csr: the ELL width is a host decision) are made when the object is first asked for.
+    Same cache policy as adjacency_csr (tensor object + in-place version).  Returns the object."""
+    if not isinstance(csr, _Csr):
+        c = _Csr()
+        c.rowptr, c.col, c.val, c.rowptr_t, c.col_t, c.val_t = csr
+        csr = c
+    key = id(adj)
+    _csr_cache[key] = (weakref.ref(adj, lambda _ref, k=key: _csr_cache.pop(k, None)), adj._version, csr)
+    return csr
+
+
+def registered_csr(adj):
+    """The cached CSR of `adj` as it stands -- possibly without its derived tables (only rowptr / col / val and their
+    transposes are promised) -- or None: for callers that need the pattern alone and must not read the host."""
+    hit = _csr_cache.get(id(adj))
+    if hit is not None and hit[0]() is adj and hit[1] == adj._version:
+        return hit[2]
+    return None
 
 
 # ------------------------------------------------------- fused aggregation ----

@@ -916,3 +916,106 @@ __all__ = ["face_areas", "device_sum", "SampleFaces", "GatherSqDistSum", "PointT
            "Laplacian", "EdgeSqLenSum", "PoolFeatures", "VertexHead", "SegmentMax", "manual_seed", "set_rng_state",
            "draw_samples", "GtIndex", "ScanPrep",
            "chamfer_nn", "tri_distance_indexed"]
+
+
+# ---------------------------------------------- adaptive face splitting (csrc/face_split.hip) ----
+def face_curvature(verts, faces, face_list):
+    """curvature [Fa] in radians of the active faces of ONE mesh (reference old_GEOMetrics/utils.py:431-465): one launch."""
+    v = _f32(verts.detach(), "verts", 2, 3)
+    faces = _lib.require(faces, "faces", torch.int64, 2, 3)
+    face_list = _lib.require(face_list, "face_list", torch.int64, 3, 3)
+    out = torch.empty(face_list.shape[0], dtype=torch.float32, device=v.device)
+    with torch.cuda.device(v.device):
+        _lib.call("geom_face_curvature_f32", v.shape[0], v.data_ptr(), faces.shape[0], faces.data_ptr(), face_list.shape[0],
+                  face_list.data_ptr(), out.data_ptr())
+    return out
+
+
+def select_faces(curvature, angle):
+    """(selected [Fa] int64 -- its first `count` entries are the positions with (c * 180) / pi > angle, ascending --, count_top3
+    [4] int64 = {count, the positions of the three largest curvatures}), both on the device: one launch, no host read."""
+    c = _f32(curvature, "curvature", 1)
+    selected = torch.empty(c.shape[0], dtype=torch.int64, device=c.device)
+    count_top3 = torch.empty(4, dtype=torch.int64, device=c.device)
+    with torch.cuda.device(c.device):
+        _lib.call("geom_face_select_f32", c.shape[0], c.data_ptr(), float(angle), selected.data_ptr(), count_top3.data_ptr())
+    return selected, count_top3
+
+
+class SplitIndex:
+    """The index tables of one split, all int64 on the device and made without a host read (geom_hip.h, geom_face_split_index):
+    corners [S,3], split_pos / unsplit_rank [Fa], face_s [Ft], and the vertex -> split-face incidence inc_ptr [V+1] /
+    inc_item [3S] (per vertex the split faces it is a corner of, ascending) that the adjacency rows and the vertices'
+    backward both walk."""
+    __slots__ = ("s", "nv", "corners", "split_pos", "unsplit_rank", "face_s", "inc_ptr", "inc_item")
+
+
+def split_index(faces, face_list, splitting, nv):
+    """SplitIndex of splitting the active rows `splitting` (unique positions into face_list): one launch of one workgroup
+    (geom_face_split_index: scatters, two running sums, the incidence rows filled and sorted in place), no host read."""
+    ix = SplitIndex()
+    dev = faces.device
+    s = ix.s = int(splitting.numel())
+    ix.nv = int(nv)
+    new = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
+    ix.corners, ix.split_pos, ix.unsplit_rank, ix.face_s = new(s, 3), new(face_list.shape[0]), new(face_list.shape[0]), new(faces.shape[0])
+    ix.inc_ptr, ix.inc_item = new(ix.nv + 1), new(3 * s)
+    cursor = new(ix.nv)
+    with torch.cuda.device(dev):
+        _lib.call("geom_face_split_index", ix.nv, faces.shape[0], faces.data_ptr(), face_list.shape[0], face_list.data_ptr(), s,
+                  splitting.data_ptr(), ix.corners.data_ptr(), ix.split_pos.data_ptr(), ix.unsplit_rank.data_ptr(), ix.face_s.data_ptr(),
+                  ix.inc_ptr.data_ptr(), ix.inc_item.data_ptr(), cursor.data_ptr())
+    return ix
+
+
+def split_tables(faces, face_list, ix, rowptr, col, dense=True):
+    """Everything geom_face_split_tables writes, in one launch: dict of new_faces, new_face_list, rowptr, col, val, val_t, ones
+    and (dense) the two [V+S,V+S] matrices adj / adj_orig, zero-filled here and given their non-zeros by the launch."""
+    dev = faces.device
+    nv, s, nft, nfa, nnz = ix.nv, ix.s, faces.shape[0], face_list.shape[0], col.numel()
+    n, nnz_new = nv + s, nnz + 7 * s
+    out = {"new_faces": torch.empty(nft + 3 * s, 3, dtype=torch.int64, device=dev),
+           "new_face_list": torch.empty(nfa + 2 * s, 3, 3, dtype=torch.int64, device=dev),
+           "rowptr": torch.empty(n + 1, dtype=torch.int32, device=dev), "col": torch.empty(nnz_new, dtype=torch.int32, device=dev),
+           "val": torch.empty(nnz_new, dtype=torch.float32, device=dev), "val_t": torch.empty(nnz_new, dtype=torch.float32, device=dev),
+           "ones": torch.empty(nnz_new, dtype=torch.float32, device=dev),
+           "adj": torch.zeros(n, n, dtype=torch.float32, device=dev) if dense else None,
+           "adj_orig": torch.zeros(n, n, dtype=torch.float32, device=dev) if dense else None}
+    args = _lib.FaceSplit(nv, nft, nfa, s, nnz, faces.data_ptr(), face_list.data_ptr(), ix.corners.data_ptr(),
+                          ix.split_pos.data_ptr(), ix.unsplit_rank.data_ptr(), ix.face_s.data_ptr(), ix.inc_ptr.data_ptr(),
+                          ix.inc_item.data_ptr(), rowptr.data_ptr(), col.data_ptr(), out["new_faces"].data_ptr(),
+                          out["new_face_list"].data_ptr(), out["rowptr"].data_ptr(), out["col"].data_ptr(), out["val"].data_ptr(),
+                          out["val_t"].data_ptr(), out["ones"].data_ptr(), _lib.ptr(out["adj"]), _lib.ptr(out["adj_orig"]))
+    with torch.cuda.device(dev):
+        _lib.call("geom_face_split_tables", ctypes.byref(args))
+    return out
+
+
+class SplitVertices(torch.autograd.Function):
+    """(verts [V,3], features [V,C]) -> ([V+S,3], [V+S,C]): old rows copied, row V + k the mean (x/3 + y/3) + z/3 of the corners
+    of split face k (reference old_GEOMetrics/utils.py:590-596); one launch per direction, the backward a gather over the
+    SplitIndex's incidence table (no atomics: bit-reproducible)."""
+
+    @staticmethod
+    def forward(ctx, verts, features, ix):
+        v, f = _f32(verts, "verts", 2, 3), _f32(features, "features", 2)
+        if f.shape[0] != v.shape[0] or v.shape[0] != ix.nv:
+            raise RuntimeError("verts %s and features %s must both have the %d rows of the mesh" % (tuple(v.shape), tuple(f.shape), ix.nv))
+        out_v = torch.empty(ix.nv + ix.s, 3, dtype=torch.float32, device=v.device)
+        out_f = torch.empty(ix.nv + ix.s, f.shape[1], dtype=torch.float32, device=v.device)
+        with torch.cuda.device(v.device):
+            _lib.call("geom_split_vertices_fwd_f32", ix.nv, ix.s, f.shape[1], v.data_ptr(), f.data_ptr(), ix.corners.data_ptr(),
+                      out_v.data_ptr(), out_f.data_ptr())
+        ctx.ix, ctx.c = ix, f.shape[1]
+        return out_v, out_f
+
+    @staticmethod
+    def backward(ctx, grad_v, grad_f):
+        ix = ctx.ix
+        gv, gf = grad_v.contiguous(), grad_f.contiguous()
+        out_v = torch.empty(ix.nv, 3, dtype=torch.float32, device=gv.device)
+        out_f = torch.empty(ix.nv, ctx.c, dtype=torch.float32, device=gv.device)
+        with torch.cuda.device(gv.device):
+            _lib.call("geom_split_vertices_bwd_f32", ix.nv, ix.s, ctx.c, gv.data_ptr(), gf.data_ptr(), ix.inc_ptr.data_ptr(),
+                      ix.inc_item.data_ptr(), out_v.data_ptr(), out_f.data_ptr())
+        return out_v, out_f, None

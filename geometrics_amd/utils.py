@@ -54,6 +54,111 @@ def adj_init(faces):
     return {"adj": normalize_adj(adj_orig.clone()), "adj_orig": adj_orig, "faces": faces}
 
 
+# ------------------------------------- adaptive face splitting (old_GEOMetrics/utils.py) ----
+def calc_face_list(faces):
+    """int64 [F,3,3] on the device: row i, slot j = [the face across edge j, the label that face gives the shared edge, i], edges
+    0 / 1 / 2 = the vertex pairs (0,1), (1,2), (0,2) (reference old_GEOMetrics/utils.py:158-179, an O(F^2) python loop there;
+    here one sort of the 3F edge keys).  Set-up code on torch ops, one host read (the check).  An edge that is not shared by
+    exactly two faces raises -- the reference silently returns a ragged list for such a mesh."""
+    faces = torch.as_tensor(faces)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError("faces must be [F,3] (got shape %s)" % (tuple(faces.shape),))
+    faces = faces.to(torch.int64)
+    nf = faces.shape[0]
+    a = torch.stack((faces[:, 0], faces[:, 1], faces[:, 0]), dim=1)          # edge j of face i: (a, b)[i, j]
+    b = torch.stack((faces[:, 1], faces[:, 2], faces[:, 2]), dim=1)
+    span = faces.max() + 1 if nf else 1
+    keys = (torch.minimum(a, b) * span + torch.maximum(a, b)).reshape(-1)    # entry 3 i + j
+    order = torch.argsort(keys, stable=True)
+    sorted_keys = keys[order]
+    paired = nf > 0 and (3 * nf) % 2 == 0
+    if paired:
+        first, second = sorted_keys[0::2], sorted_keys[1::2]
+        paired = bool((first == second).all() & (first[1:] != second[:-1]).all())
+    if not paired:
+        raise RuntimeError("calc_face_list: every edge must be shared by exactly two faces (a closed manifold triangle mesh)")
+    partner = torch.empty_like(order)
+    partner[order[0::2]] = order[1::2]
+    partner[order[1::2]] = order[0::2]
+    own = torch.arange(nf, device=faces.device).repeat_interleave(3)
+    return torch.stack((torch.div(partner, 3, rounding_mode="floor"), partner % 3, own), dim=1).reshape(nf, 3, 3).contiguous()
+
+
+_active_cache = {}   # id(face_list) -> (weakref, version, faces weakref, faces version, active faces)
+
+
+def active_faces(info):
+    """info['faces'][info['face_list'][:, 0, 2]]: the faces the losses run on after a split (the reference's calc_edge and its
+    driver take them the same way, old_GEOMetrics/utils.py:674-677).  Cached per face_list TENSOR OBJECT (and in-place version,
+    and the faces it was taken from), as ops.vertex_faces caches: every loss call on a split mesh passes the same tensor as
+    'faces', so the tables keyed on that tensor are built once."""
+    import weakref
+    face_list, faces = info["face_list"], info["faces"]
+    key = id(face_list)
+    hit = _active_cache.get(key)
+    if hit is not None and hit[0]() is face_list and hit[1] == face_list._version and hit[2]() is faces and hit[3] == faces._version:
+        return hit[4]
+    with torch.no_grad():
+        active = faces.index_select(0, face_list[:, 0, 2]).contiguous()
+    _active_cache[key] = (weakref.ref(face_list, lambda _ref, k=key: _active_cache.pop(k, None)), face_list._version,
+                          weakref.ref(faces), faces._version, active)
+    return active
+
+
+def calc_curve(verts, info, angle=70):
+    """Positions into info['face_list'] of the faces whose mean dihedral angle to their three neighbours exceeds `angle` degrees,
+    ascending (reference old_GEOMetrics/utils.py:431-473); fewer than 3 such faces: the 3 faces of largest curvature, largest
+    first (the reference's topk(sorted=False) leaves their order open).  A face with a zero-area face among itself and its
+    neighbours has curvature NaN and is never selected.  Two launches and ONE host read (the count, which the size of the
+    result depends on).  Not differentiable: the result is indices."""
+    curvature = ops.face_curvature(verts, info["faces"], info["face_list"])
+    selected, count_top3 = ops.select_faces(curvature, angle)
+    count, *top3 = count_top3.tolist()                 # the one host read
+    if count < 3:
+        if min(top3) < 0:
+            raise RuntimeError("calc_curve: fewer than 3 faces have a curvature (degenerate or too small a mesh)")
+        return count_top3[1:].clone()
+    return selected[:count]
+
+
+def split_info(info, verts, features, splitting, number):
+    """Split the active faces at positions `splitting` of info['face_list'] (reference old_GEOMetrics/utils.py:481-634): a
+    vertex at each such face's centre -- position and features the mean (x/3 + y/3) + z/3 of its corners --, the face replaced
+    by its three children (x,y,n), (n,y,z), (x,n,z).  Returns (new_info, new_verts [V+S,3], new_features [V+S,C]); new_info has
+    'adj' (normalised) and 'adj_orig' (binary), dense fp32 [V+S,V+S] on the device, 'faces' int64 [Ft+3S,3] (the split faces
+    stay in it, dead) and 'face_list' int64 [Fa+2S,3,3] -- rows and every index exactly the reference's: the unsplit rows in
+    their old order, then the S first, S second and S third children.  Differentiable in verts and features.
+      * `number` must equal len(splitting) (the reference takes both and trusts them);
+      * `splitting` must hold UNIQUE positions in [0, Fa): not checked -- checking would need a host read, and this function
+        makes none (info['adj_orig'] not yet seen by the layers is read once, as for any adjacency);
+      * the dense matrices are filled from the CSR of the new adjacency, which is handed to the layers at the same time
+        (layers.register_csr): adjacency_csr(new_info['adj'] / ['adj_orig']) never reads the matrices back."""
+    from . import layers
+    splitting = torch.as_tensor(splitting, device=verts.device).to(torch.int64).reshape(-1).contiguous()
+    if int(number) != splitting.numel():
+        raise RuntimeError("split_info: number (%d) must be len(splitting) (%d)" % (int(number), splitting.numel()))
+    faces = ops._lib.require(info["faces"], "info['faces']", torch.int64, 2, 3)
+    face_list = ops._lib.require(info["face_list"], "info['face_list']", torch.int64, 3, 3)
+    if face_list.shape[1] != 3:
+        raise RuntimeError("info['face_list'] must be [Fa,3,3] (got shape %s)" % (tuple(face_list.shape),))
+    if splitting.numel() > face_list.shape[0]:
+        raise RuntimeError("split_info: %d positions for %d active faces" % (splitting.numel(), face_list.shape[0]))
+    nv = verts.shape[0]
+    old = layers.registered_csr(info["adj_orig"]) or layers.adjacency_csr(info["adj_orig"])
+    if not getattr(old, "symmetric_structure", True):      # (a CSR this function handed over is symmetric by construction)
+        raise RuntimeError("info['adj_orig'] must have a symmetric pattern")
+    if old.rowptr.numel() != nv + 1:
+        raise RuntimeError("info['adj_orig'] is %d x %d but verts has %d rows" % (old.rowptr.numel() - 1, old.rowptr.numel() - 1, nv))
+    ix = ops.split_index(faces, face_list, splitting, nv)
+    t = ops.split_tables(faces, face_list, ix, old.rowptr, old.col)
+    new_verts, new_features = ops.SplitVertices.apply(verts, features, ix)
+    # the pattern is symmetric: it is its own transpose; the normalised matrix's transpose has the columns' 1 / row length
+    layers.register_csr(t["adj"], (t["rowptr"], t["col"], t["val"], t["rowptr"], t["col"], t["val_t"]))
+    layers.register_csr(t["adj_orig"], (t["rowptr"], t["col"], t["ones"], t["rowptr"], t["col"], t["ones"]))
+    new_info = {"adj": t["adj"], "adj_orig": t["adj_orig"], "faces": t["new_faces"], "face_list": t["new_face_list"]}
+    return new_info, new_verts, new_features
+
+
 # ------------------------------------------------------------------- sampling ----
 def batch_sample(verts, faces, num=10000, draws=None):
     """Area-weighted random surface points [B,num,3], differentiable in verts

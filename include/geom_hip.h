@@ -597,6 +597,59 @@ int geom_edge_sqlen_fwd_f32(int b, int nv, const float *verts, int nf, const int
 int geom_edge_sqlen_bwd_f32(int b, int nv, const float *verts, int nf, const int64_t *faces,
                             const float *coef_dev, float coef_host, float *grad_verts, void *stream);
 
+/* ---- adaptive face splitting (old_GEOMetrics/utils.py:431-634: calc_curve, split_info; csrc/face_split.hip) ----------
+ * One unbatched mesh: verts [nv,3], faces int64 [nft,3] (every face ever made; split ones stay, dead), face_list int64
+ * [nfa,3,3] (the ACTIVE faces: row i, slot j = {neighbour across edge j, the label that neighbour gives this face, i's own
+ * index in faces}).  Every index a kernel follows is checked against the size of what it points into; a row that names
+ * something outside gives NaN (floats) or is left unwritten (tables), never an access out of bounds.
+ *
+ * curvature[i] = mean over the three neighbours of acos(clamp(n_own . n_nb, -1 + 1e-5, 1 - 1e-5)) in radians, the normals
+ * cross(p2 - p1, p3 - p1) / |.| with p1 = v[f[1]], p2 = v[f[0]], p3 = v[f[2]] recomputed by the thread (utils.py:437-465, same
+ * operations in the same order).  A zero-area face among the four gives NaN. */
+int geom_face_curvature_f32(int nv, const float *verts, int nft, const int64_t *faces, int nfa, const int64_t *face_list,
+                            float *curvature, void *stream);
+/* selected[0 .. count) = the positions i with (curvature[i] * 180) / pi > angle in fp32, ascending (NaN never); count_top3
+ * int64 [4] = {count, the positions of the three largest curvatures, largest first, lower position first on ties, -1 where the
+ * list has fewer than three numbers}.  selected: int64 [nfa].  One workgroup, fixed order. */
+int geom_face_select_f32(int nfa, const float *curvature, float angle, int64_t *selected, int64_t *count_top3, void *stream);
+/* The index tables of a split from splitting [s] (unique positions into face_list), in ONE launch of one workgroup, without a
+ * host read: the tables listed below (all written in full), cursor: int64 [nv] of scratch.  A position, face id or corner outside
+ * its range is skipped (corners then hold -1).  s > nfa, a negative size or a missing pointer: GEOM_EINVAL. */
+int geom_face_split_index(int nv, int nft, const int64_t *faces, int nfa, const int64_t *face_list, int s, const int64_t *splitting,
+                          int64_t *corners, int64_t *split_pos, int64_t *unsplit_rank, int64_t *face_s, int64_t *inc_ptr,
+                          int64_t *inc_item, int64_t *cursor, void *stream);
+/* The tables after splitting the s active rows splitting[0 .. s) (unique), in ONE launch.  Index tables (geom_face_split_index
+ * makes them; all int64): corners [s,3] = faces[face_list[splitting[k]][0][2]]; split_pos [nfa] = k at splitting[k], -1
+ * elsewhere; unsplit_rank [nfa] = how many unsplit rows precede row i; face_s [nft] = k at the face id of splitting[k], -1
+ * elsewhere; inc_ptr [nv+1] / inc_item [3s]: per vertex the k of the split faces it is a corner of, ascending.
+ * rowptr / col: CSR of the old adjacency WITH self loops, symmetric pattern, columns ascending per row, nnz entries.  Written:
+ *   new_faces [nft+3s,3]      old rows, then the s first, s second, s third children (x,y,n), (n,y,z), (x,n,z), n = nv + k
+ *   new_face_list [nfa+2s,3,3] unsplit rows in old order, then the children in the same order; a neighbour that was split is
+ *                             replaced by its child with the same edge label (utils.py:509-579)
+ *   new_rowptr [nv+s+1], new_col [nnz+7s]   the new pattern (symmetric again: it serves as its own transpose)
+ *   new_val / new_val_t [nnz+7s]   1 / (row length) of the entry's row / of its column: the normalised adjacency and its transpose
+ *   new_ones [nnz+7s]         1.0: the values of the binary adjacency
+ *   adj / adj_orig [(nv+s),(nv+s)]  the non-zeros of the two dense matrices (the caller zero-fills; either may be NULL) */
+typedef struct geom_face_split {
+    int nv, nft, nfa, s, nnz;
+    const int64_t *faces, *face_list, *corners, *split_pos, *unsplit_rank, *face_s, *inc_ptr, *inc_item;
+    const int *rowptr, *col;
+    int64_t *new_faces, *new_face_list;
+    int *new_rowptr, *new_col;
+    float *new_val, *new_val_t, *new_ones, *adj, *adj_orig;
+} geom_face_split;
+int geom_face_split_tables(const geom_face_split *args, void *stream);
+/* out_verts [nv+s,3] / out_features [nv+s,c]: the old rows copied, row nv + k = (x/3 + y/3) + z/3 of the rows corners[k] =
+ * (x, y, z), true divisions in that order (utils.py:595).  Feature columns move in 16-byte groups when c % 4 == 0 and both
+ * feature pointers are 16-byte aligned, one by one otherwise.  c == 0: positions only. */
+int geom_split_vertices_fwd_f32(int nv, int s, int c, const float *verts, const float *features, const int64_t *corners,
+                                float *out_verts, float *out_features, void *stream);
+/* The transpose: grad[u] = grad_out[u] + sum over the split faces k with corner u, ascending in k, of grad_out[nv + k] / 3
+ * (inc_ptr / inc_item as above).  A gather without atomics: bit-reproducible. */
+int geom_split_vertices_bwd_f32(int nv, int s, int c, const float *grad_out_verts, const float *grad_out_features,
+                                const int64_t *inc_ptr, const int64_t *inc_item, float *grad_verts, float *grad_features,
+                                void *stream);
+
 /* ---- per-vertex BatchNorm + ReLU + residual average (SURVEY 8f "next" row 2; models.py:222-297) --------
  * nn.BatchNorm1d(verts) applied to x [b,nv,c]: one statistic per vertex over its b*c values, then
  *     out = (residual + act(bn(x))) * scale      (residual == NULL: out = act(bn(x)))
