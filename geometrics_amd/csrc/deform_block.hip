@@ -937,7 +937,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void di_fwd_kernel(geom_deform_infer
 {
     __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST];
     const int w = blockIdx.x;
-    const int lw = (w & 7) * per_xcd + (w >> 3); // logical workgroup: contiguous runs per XCD (workgroup w runs on XCD w % 8)
+    const int lw = geom::xcd_run_item(w, per_xcd); // logical workgroup: contiguous runs per XCD (workgroup w runs on XCD w % 8)
     if (lw >= nwg) return;
     const int q = nrb / nwg, rem = nrb - q * nwg;
     const int first = lw * q + (lw < rem ? lw : rem), count = q + (lw < rem ? 1 : 0);

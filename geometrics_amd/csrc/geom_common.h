@@ -65,12 +65,6 @@ __host__ __device__ __forceinline__ bool ref_tail_skipped(int k, int m)
     return (k - t0) >= len - (len & 3);
 }
 
-// XCD-aware work assignment.  MI355X dispatches workgroup `bid` to XCD `bid % 8`, and every XCD
-// has its own 4 MiB L2.  Jobs (a mesh, or a (direction, mesh) pair) whose workgroups all read the
-// same records are therefore pinned to one XCD: slot = bid % 8 owns jobs slot, slot+8, ...; within a
-// slot the `tiles` workgroups of a job are consecutive.  Grid size = 8 * tiles * ceil(jobs / 8);
-// workgroups whose job index falls beyond `jobs` exit.  Placement only affects speed (L2 hits
-// instead of 8x refetch through the fabric), never results.
 // A store other workgroups of the SAME launch may read after a flag hand-off (the finalize tail of the fused surface scan):
 // agent scope = written through the XCD's L2, so the producer needs no L2 write-back (a release fence costs a buffer_wbl2
 // per wave: 9 000 of them made that launch 245 us instead of 45) -- only s_waitcnt vmcnt(0) before it signs off.
@@ -81,6 +75,21 @@ __device__ __forceinline__ void store_agent(T *p, T v)
 }
 
 constexpr int NUM_XCD = 8;
+
+// XCD-aware work assignment.  MI355X dispatches workgroup `bid` to XCD `bid % 8`, and every XCD
+// has its own 4 MiB L2.  Placement only affects speed (L2 hits instead of 8x refetch through the
+// fabric), never results.  Two schemes:
+//
+// 1. A contiguous run of items per XCD: the n items of a launch are numbered so that neighbours read the same
+// data; XCD x owns items x * per_xcd ... (x + 1) * per_xcd - 1, one after the other.  The grid is n rounded up to
+// a multiple of 8, per_xcd = grid / 8; a workgroup whose item is n or beyond exits.
+__host__ __device__ __forceinline__ unsigned xcd_run_grid(size_t n) { return (unsigned)((n + 7) / 8 * 8); }
+__device__ __forceinline__ int xcd_run_item(int bid, int per_xcd) { return (bid & 7) * per_xcd + (bid >> 3); }
+
+// 2. Jobs pinned to an XCD.  Jobs (a mesh, or a (direction, mesh) pair) whose workgroups all read the
+// same records are pinned to one XCD: slot = bid % 8 owns jobs slot, slot+8, ...; within a
+// slot the `tiles` workgroups of a job are consecutive.  Grid size = 8 * tiles * ceil(jobs / 8);
+// workgroups whose job index falls beyond `jobs` exit.
 // With fewer than 8 jobs every job is spread over floor(8 / jobs) XCDs (its tiles interleaved), so
 // a small batch still uses the whole chip.
 __host__ __device__ __forceinline__ int xcd_spread(int jobs) { return jobs >= NUM_XCD ? 1 : NUM_XCD / jobs; }

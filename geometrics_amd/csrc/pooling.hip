@@ -34,6 +34,7 @@ struct PoolArgs {
     int channels[GEOM_POOL_MAX_LEVELS], dims[GEOM_POOL_MAX_LEVELS];
     int levels, b, nv, ctot;
     int chunks; // 64-channel chunks of all maps together
+    int zc;     // chunk slices of a vertex-tile launch = min(chunks, PL_MAX_CHUNKS): a workgroup walks chunks z, z + zc, ...
     int ld;     // floats between two vertex rows of the pooled features / of their gradient (>= ctot: a column slice of a wider buffer)
 };
 
@@ -82,6 +83,18 @@ __device__ __forceinline__ Texel texel(float xs, float ys, int dim)
     t.p1 = ix1 * dim + yb, t.p2 = ix2 * dim + yb;
     t.y1_hi = iy1 != yb, t.y2_hi = iy2 != yb;
     return t;
+}
+
+// The four (texel, weight) corners a vertex contributes to a map's gradient, f(texel, weight) for each in the order 11, 12, 21,
+// 22; a corner of zero weight is dropped.  (The products are the forward's (A*c11)*G, (H*c12)*A, (G*c21)*B, (B*c22)*H at c = 1.)
+template <class F>
+__device__ __forceinline__ void corners(const Texel &t, F f)
+{
+    const float w11 = t.G * t.A, w12 = t.A * t.H, w21 = t.B * t.G, w22 = t.H * t.B;
+    if (w11 != 0.f) f(t.i11, w11);
+    if (w12 != 0.f) f(t.i12, w12);
+    if (w21 != 0.f) f(t.i21, w21);
+    if (w22 != 0.f) f(t.i22, w22);
 }
 
 // a mesh's planes of one map as a buffer (the pair reads are 4-byte aligned only: buffer loads take that)
@@ -169,24 +182,42 @@ __device__ __forceinline__ void chunk_quads(const PoolArgs &a, const Chunk &ck, 
 struct PoolWork {
     int v0, mesh, z;
     bool live;
+    int lane, v; // the thread's lane and its vertex (lanes past the mesh's last vertex repeat it)
 };
 
-__device__ __forceinline__ PoolWork pool_work(const PoolArgs &a, int zc, int bid, int nblocks)
+__device__ __forceinline__ PoolWork pool_work(const PoolArgs &a, int bid, int nblocks)
 {
     const int tiles = (a.nv + PL_VERTS - 1) / PL_VERTS;
-    const int w = (bid & 7) * (nblocks >> 3) + (bid >> 3);
+    const int w = geom::xcd_run_item(bid, nblocks >> 3);
     PoolWork k;
-    k.live = w < tiles * a.b * zc;
+    k.live = w < tiles * a.b * a.zc;
     const int r = w / tiles;
-    k.v0 = (w - r * tiles) * PL_VERTS, k.mesh = r / zc, k.z = r - k.mesh * zc; // (chunks inside a mesh: every XCD gets maps of every size)
+    k.v0 = (w - r * tiles) * PL_VERTS, k.mesh = r / a.zc, k.z = r - k.mesh * a.zc; // (chunks inside a mesh: every XCD gets maps of every size)
+    k.lane = threadIdx.x & (GEOM_WAVE - 1);
+    k.v = min(k.v0 + k.lane, a.nv - 1);
     return k;
 }
 
-static inline unsigned pool_grid(int nv, int b, int zc)
+static inline unsigned pool_grid(const PoolArgs &a)
 {
-    const size_t n = (size_t)((nv + PL_VERTS - 1) / PL_VERTS) * b * zc;
-    return (unsigned)((n + 7) / 8 * 8);
+    return geom::xcd_run_grid((size_t)((a.nv + PL_VERTS - 1) / PL_VERTS) * a.b * a.zc);
 }
+
+// A live work item's walk over its chunks: the vertex is projected once; body(chunk, the vertex's texels in that chunk's map, the
+// chunk's channels) per chunk (one chunk per workgroup up to PL_MAX_CHUNKS chunks).  The body is the whole workgroup's: it may
+// hold barriers.
+template <class Body>
+__device__ __forceinline__ void pool_chunks(const PoolArgs &a, const PoolWork &k, Body body)
+{
+    const Projection pr = project(a, k.mesh, k.v);
+    for (int z = k.z; z < a.chunks; z += a.zc) {
+        const Chunk ck = chunk_of(a, z);
+        body(ck, texel(pr.xs, pr.ys, a.dims[ck.level]), min(GEOM_WAVE, a.channels[ck.level] - ck.cc));
+    }
+}
+
+// the LDS tile a vertex-tile workgroup transposes through: [vertex][channel of the chunk] (+ 1: conflict-free both ways)
+using PoolTile = float[PL_VERTS][GEOM_WAVE + 1];
 
 // What the caller is going to concatenate IN FRONT of the pooled features (GEOMetrics.py:123,128: the previous features;
 // models.py:241: the coordinates), copied into the free columns of the wide buffer by workgroups BESIDE the pooling ones -- the
@@ -200,9 +231,9 @@ struct PoolFronts {
     int work_blocks; // the pooling workgroups in front of the copying ones
 };
 
-__global__ __launch_bounds__(PL_THREADS) void pool_fwd_kernel(PoolArgs a, float *out, int zc, PoolFronts fr)
+__global__ __launch_bounds__(PL_THREADS) void pool_fwd_kernel(PoolArgs a, float *out, PoolFronts fr)
 {
-    __shared__ float tile[PL_VERTS][GEOM_WAVE + 1];
+    __shared__ PoolTile tile;
     if ((int)blockIdx.x >= fr.work_blocks) {
         const int fb = (int)blockIdx.x - fr.work_blocks;
         const int f = (fr.count > 1 && fb >= fr.first_block[1]) ? 1 : 0;
@@ -217,17 +248,10 @@ __global__ __launch_bounds__(PL_THREADS) void pool_fwd_kernel(PoolArgs a, float 
         }
         return;
     }
-    const PoolWork k = pool_work(a, zc, blockIdx.x, fr.work_blocks);
+    const PoolWork k = pool_work(a, blockIdx.x, fr.work_blocks);
     if (!k.live) return;
-    const int mesh = k.mesh, v0 = k.v0;
-    const int lane = threadIdx.x & (GEOM_WAVE - 1);
-    const int v = min(v0 + lane, a.nv - 1);
-    const Projection pr = project(a, mesh, v);
-    for (int z = k.z; z < a.chunks; z += zc) { // (one chunk per workgroup up to PL_MAX_CHUNKS chunks)
-        const Chunk ck = chunk_of(a, z);
-        const int dim = a.dims[ck.level], C = a.channels[ck.level], cc = ck.cc;
-        const Texel t = texel(pr.xs, pr.ys, dim);
-        const int nch = min(GEOM_WAVE, C - cc);
+    const int mesh = k.mesh, v0 = k.v0, lane = k.lane;
+    pool_chunks(a, k, [&](const Chunk &ck, const Texel &t, int nch) {
         chunk_quads(a, ck, mesh, t, nch, [&](int c, const Quad &q) {
             const float s1 = (t.A * q.c11) * t.G, s2 = (t.H * q.c12) * t.A;
             const float s3 = (t.G * q.c21) * t.B, s4 = (t.B * q.c22) * t.H;
@@ -235,7 +259,7 @@ __global__ __launch_bounds__(PL_THREADS) void pool_fwd_kernel(PoolArgs a, float 
         });
         __syncthreads();
         // a wave writes one vertex's 64 channels per round (lanes <-> channels: 256 contiguous bytes, no index arithmetic)
-        float *o = out + ((size_t)mesh * a.nv + v0) * a.ld + ck.off + cc + lane;
+        float *o = out + ((size_t)mesh * a.nv + v0) * a.ld + ck.off + ck.cc + lane;
         for (int vv = threadIdx.x >> 6; vv < min(PL_VERTS, a.nv - v0); vv += PL_WAVES) {
 #ifdef PL_PROBE_NO_STORE
             if (tile[vv][lane] == 1.2345f)
@@ -243,73 +267,84 @@ __global__ __launch_bounds__(PL_THREADS) void pool_fwd_kernel(PoolArgs a, float 
             if (lane < nch) o[(size_t)vv * a.ld] = tile[vv][lane];
         }
         __syncthreads();
-    }
+    });
 }
 
+// The backward pass's workspace: what its two launches hand each other.  Laid out by pool_ws_layout (the texel lists' part is
+// described in geom_hip.h); the bodies ask for a place here instead of multiplying out.
+struct BinSpace {
+    int *offsets;        // per (mesh, level): dim*dim + 1 ints, level-major inside a mesh
+    int *ent_v;          // per (mesh, level): 4*nv vertex ids
+    float *ent_w;        // per (mesh, level): 4*nv weights
+    float *vert_partial; // [PL_MAX_CHUNKS][b][nv][2]
+    int b, nv, levels;
+    int off_stride;                      // ints per mesh in `offsets`
+    int level_off[GEOM_POOL_MAX_LEVELS]; // start of level l inside a mesh's offsets block
+
+    // where the lists of the texels of (mesh, level l) start, [dim*dim + 1]
+    __device__ __forceinline__ int *offs(int mesh, int l) const { return offsets + (size_t)mesh * off_stride + level_off[l]; }
+    // the two entry lists of (mesh, level l), which those offsets index
+    __device__ __forceinline__ size_t list_at(int mesh, int l) const { return ((size_t)mesh * levels + l) * 4 * nv; }
+    __device__ __forceinline__ int *list_v(int mesh, int l) const { return ent_v + list_at(mesh, l); }
+    __device__ __forceinline__ float *list_w(int mesh, int l) const { return ent_w + list_at(mesh, l); }
+    // chunk slice z's share of d loss / d (xs, ys) of a vertex: two floats
+    __device__ __forceinline__ float *sums(int z, int mesh, int v) const { return vert_partial + (((size_t)z * b + mesh) * nv + v) * 2; }
+};
+
 // d loss / d verts: vertex-tiled like the forward (the gradient w.r.t. a vertex sums over all channels).  A workgroup owns
-// one 64-channel chunk and leaves its share of d loss / d (xs, ys) per vertex in `partial` [chunk][mesh][vertex][2];
+// one 64-channel chunk and leaves its share of d loss / d (xs, ys) per vertex in the workspace (BinSpace::sums);
 // pool_bwd_verts_finish_body adds the chunks up in chunk order (fixed: bit-reproducible) and chains the sum through the
 // clamp, the perspective divide and the camera matrix.
 struct VertsLds {
-    float tile[PL_VERTS][GEOM_WAVE + 1];
+    PoolTile tile;
     float part[PL_WAVES][2][PL_VERTS];
 };
 
-__device__ __forceinline__ void pool_bwd_verts_body(const PoolArgs &a, const float *grad_out, float *partial, int zc, int bid,
-                                                    int nblocks, VertsLds &L)
+__device__ __forceinline__ void pool_bwd_verts_body(const PoolArgs &a, const BinSpace &ws, const float *grad_out, int bid, int nblocks,
+                                                    VertsLds &L)
 {
-    auto &tile = L.tile;
-    auto &part = L.part;
-    const PoolWork k = pool_work(a, zc, bid, nblocks);
+    const PoolWork k = pool_work(a, bid, nblocks);
     if (!k.live) return;
-    const int mesh = k.mesh, v0 = k.v0;
-    const int lane = threadIdx.x & (GEOM_WAVE - 1), wave = threadIdx.x >> 6;
-    const bool live = v0 + lane < a.nv;
-    const int v = min(v0 + lane, a.nv - 1);
-    const Projection pr = project(a, mesh, v);
+    const int mesh = k.mesh, v0 = k.v0, lane = k.lane, wave = threadIdx.x >> 6;
     float ax = 0.f, ay = 0.f; // this wave's share of d loss / d (xs, ys) of the lane's vertex over the workgroup's chunks
-    for (int z = k.z; z < a.chunks; z += zc) {
-        const Chunk ck = chunk_of(a, z);
-        const int dim = a.dims[ck.level], C = a.channels[ck.level], cc = ck.cc;
-        const Texel t = texel(pr.xs, pr.ys, dim);
-        const int nch = min(GEOM_WAVE, C - cc);
-        const float *gi = grad_out + ((size_t)mesh * a.nv + v0) * a.ld + ck.off + cc + (lane < nch ? lane : 0);
+    pool_chunks(a, k, [&](const Chunk &ck, const Texel &t, int nch) {
+        const float *gi = grad_out + ((size_t)mesh * a.nv + v0) * a.ld + ck.off + ck.cc + (lane < nch ? lane : 0);
         for (int vv = wave; vv < PL_VERTS; vv += PL_WAVES) // (a wave reads one vertex's 64 channels per round)
-            tile[vv][lane] = (v0 + vv < a.nv && lane < nch) ? gi[(size_t)vv * a.ld] : 0.f;
+            L.tile[vv][lane] = (v0 + vv < a.nv && lane < nch) ? gi[(size_t)vv * a.ld] : 0.f;
         __syncthreads();
         float gx = 0.f, gy = 0.f;
         chunk_quads(a, ck, mesh, t, nch, [&](int c, const Quad &q) { // (a padding lane's sums are dropped below)
-            const float g = tile[lane][c];
+            const float g = L.tile[lane][c];
             const float c11 = q.c11, c12 = q.c12, c21 = q.c21, c22 = q.c22;
             gx += g * (((-c11 * t.G) - (t.H * c12)) + ((t.G * c21) + (c22 * t.H)));
             gy += g * (((-t.A * c11) + (c12 * t.A)) + ((-c21 * t.B) + (t.B * c22)));
         });
+        const int dim = a.dims[ck.level];
         if (t.in_x) ax += gx * dim; // the clamp passes the gradient only inside the map
         if (t.in_y) ay += gy * dim;
         __syncthreads();
-    }
-    part[wave][0][lane] = ax;
-    part[wave][1][lane] = ay;
+    });
+    L.part[wave][0][lane] = ax;
+    L.part[wave][1][lane] = ay;
     __syncthreads();
-    if (wave == 0 && live) {
+    if (wave == 0 && v0 + lane < a.nv) {
         float sx = 0.f, sy = 0.f;
         for (int w = 0; w < PL_WAVES; ++w) {
-            sx += part[w][0][lane];
-            sy += part[w][1][lane];
+            sx += L.part[w][0][lane];
+            sy += L.part[w][1][lane];
         }
-        float *o = partial + (((size_t)k.z * a.b + mesh) * a.nv + v) * 2;
+        float *o = ws.sums(k.z, mesh, k.v);
         o[0] = sx, o[1] = sy;
     }
 }
 
-__device__ __forceinline__ void pool_bwd_verts_finish_body(const PoolArgs &a, const float *partial, int chunks, float *grad_verts,
-                                                           int mesh, int v)
+__device__ __forceinline__ void pool_bwd_verts_finish_body(const PoolArgs &a, const BinSpace &ws, float *grad_verts, int mesh, int v)
 {
     if (v >= a.nv) return;
     const Projection pr = project(a, mesh, v);
     float sx = 0.f, sy = 0.f;
-    for (int z = 0; z < chunks; ++z) {
-        const float *p = partial + (((size_t)z * a.b + mesh) * a.nv + v) * 2;
+    for (int z = 0; z < a.zc; ++z) {
+        const float *p = ws.sums(z, mesh, v);
         sx += p[0], sy += p[1];
     }
     // xs = h/223, ys = w/223; h = (-Y)/(-Z)*F + 112, w = X/(-Z)*F + 112
@@ -341,76 +376,63 @@ __device__ __forceinline__ void pool_bwd_verts_finish_body(const PoolArgs &a, co
 constexpr int BIN_THREADS = 256;
 constexpr int BIN_MAX_TEXELS = 4096; // dim <= 64
 
-struct BinSpace {
-    int *offsets;   // per (mesh, level): dim*dim + 1 ints, level-major inside a mesh
-    int *ent_v;     // per (mesh, level): 4*nv vertex ids
-    float *ent_w;   // per (mesh, level): 4*nv weights
-    int off_stride; // ints per mesh in `offsets`
-    int level_off[GEOM_POOL_MAX_LEVELS]; // start of level l inside a mesh's offsets block
-    float *vert_partial; // [PL_MAX_CHUNKS][b][nv][2]
-};
-
 struct BinLds {
     int counts[BIN_MAX_TEXELS + 1];
     int wave_sum[BIN_THREADS / GEOM_WAVE];
 };
 
-__device__ __forceinline__ void pool_bin_body(const PoolArgs &a, const BinSpace &ws, int l, int mesh, BinLds &L)
+// f(vertex, texel, weight) for every corner of a mesh's vertices in one map: a pass of the binning workgroup over its vertices
+template <class F>
+__device__ __forceinline__ void mesh_corners(const PoolArgs &a, int mesh, int dim, F f)
 {
-    auto &counts = L.counts;
-    auto &wave_sum = L.wave_sum;
-    const int dim = a.dims[l], texels = dim * dim;
-    for (int i = threadIdx.x; i <= texels; i += BIN_THREADS) counts[i] = 0;
-    __syncthreads();
     for (int v = threadIdx.x; v < a.nv; v += BIN_THREADS) {
         const Projection pr = project(a, mesh, v);
-        const Texel t = texel(pr.xs, pr.ys, dim);
-        if (t.G * t.A != 0.f) atomicAdd(&counts[t.i11], 1);
-        if (t.A * t.H != 0.f) atomicAdd(&counts[t.i12], 1);
-        if (t.B * t.G != 0.f) atomicAdd(&counts[t.i21], 1);
-        if (t.H * t.B != 0.f) atomicAdd(&counts[t.i22], 1);
+        corners(texel(pr.xs, pr.ys, dim), [&](int i, float w) { f(v, i, w); });
     }
+}
+
+__device__ __forceinline__ void pool_bin_body(const PoolArgs &a, const BinSpace &ws, int l, int mesh, BinLds &L)
+{
+    const int dim = a.dims[l], texels = dim * dim;
+    for (int i = threadIdx.x; i <= texels; i += BIN_THREADS) L.counts[i] = 0;
+    __syncthreads();
+    mesh_corners(a, mesh, dim, [&](int, int i, float) { atomicAdd(&L.counts[i], 1); });
     __syncthreads();
     // exclusive scan of counts[0..texels): thread owns a contiguous run, wave shuffle scan, wave totals
     const int per = (texels + BIN_THREADS - 1) / BIN_THREADS;
     const int i0 = threadIdx.x * per;
     int run = 0;
-    for (int i = i0; i < min(i0 + per, texels); ++i) run += counts[i];
+    for (int i = i0; i < min(i0 + per, texels); ++i) run += L.counts[i];
     const int lane = threadIdx.x & (GEOM_WAVE - 1), wave = threadIdx.x >> 6;
     int incl = run;
     for (int o = 1; o < GEOM_WAVE; o <<= 1) {
         const int t = __shfl_up(incl, o, GEOM_WAVE);
         if (lane >= o) incl += t;
     }
-    if (lane == GEOM_WAVE - 1) wave_sum[wave] = incl;
+    if (lane == GEOM_WAVE - 1) L.wave_sum[wave] = incl;
     __syncthreads();
     int base = 0;
-    for (int w = 0; w < wave; ++w) base += wave_sum[w];
+    for (int w = 0; w < wave; ++w) base += L.wave_sum[w];
     int excl = base + incl - run;
-    int *offs = ws.offsets + (size_t)mesh * ws.off_stride + ws.level_off[l];
+    int *offs = ws.offs(mesh, l);
     for (int i = i0; i < min(i0 + per, texels); ++i) {
-        const int c = counts[i];
-        counts[i] = excl; // becomes the fill cursor
+        const int c = L.counts[i];
+        L.counts[i] = excl; // becomes the fill cursor
         offs[i] = excl;
         excl += c;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         int total = 0;
-        for (int w = 0; w < BIN_THREADS / GEOM_WAVE; ++w) total += wave_sum[w];
+        for (int w = 0; w < BIN_THREADS / GEOM_WAVE; ++w) total += L.wave_sum[w];
         offs[texels] = total;
     }
-    int *ev = ws.ent_v + ((size_t)mesh * a.levels + l) * 4 * a.nv;
-    float *ew = ws.ent_w + ((size_t)mesh * a.levels + l) * 4 * a.nv;
-    for (int v = threadIdx.x; v < a.nv; v += BIN_THREADS) {
-        const Projection pr = project(a, mesh, v);
-        const Texel t = texel(pr.xs, pr.ys, dim);
-        const float w11 = t.G * t.A, w12 = t.A * t.H, w21 = t.B * t.G, w22 = t.H * t.B;
-        if (w11 != 0.f) { const int p = atomicAdd(&counts[t.i11], 1); ev[p] = v; ew[p] = w11; }
-        if (w12 != 0.f) { const int p = atomicAdd(&counts[t.i12], 1); ev[p] = v; ew[p] = w12; }
-        if (w21 != 0.f) { const int p = atomicAdd(&counts[t.i21], 1); ev[p] = v; ew[p] = w21; }
-        if (w22 != 0.f) { const int p = atomicAdd(&counts[t.i22], 1); ev[p] = v; ew[p] = w22; }
-    }
+    int *ev = ws.list_v(mesh, l);
+    float *ew = ws.list_w(mesh, l);
+    mesh_corners(a, mesh, dim, [&](int v, int i, float w) {
+        const int p = atomicAdd(&L.counts[i], 1);
+        ev[p] = v, ew[p] = w;
+    });
 }
 
 // The backward pass is TWO launches of two roles each (the four bodies were launches of their own until round 6: at the
@@ -420,8 +442,8 @@ __device__ __forceinline__ void pool_bin_body(const PoolArgs &a, const BinSpace 
 //   2. pool_bwd_grads_kernel: the map gradient from the lists BESIDE the vertex gradient from the per-chunk sums.
 static_assert(BIN_THREADS == PL_THREADS, "the two roles of a launch share its workgroup size");
 
-__global__ __launch_bounds__(PL_THREADS) void pool_bwd_lists_kernel(PoolArgs a, BinSpace ws, const float *grad_out, int zc,
-                                                                    int bin_blocks, int verts_blocks)
+__global__ __launch_bounds__(PL_THREADS) void pool_bwd_lists_kernel(PoolArgs a, BinSpace ws, const float *grad_out, int bin_blocks,
+                                                                    int verts_blocks)
 {
     __shared__ union Lds {
         BinLds bin;
@@ -429,7 +451,7 @@ __global__ __launch_bounds__(PL_THREADS) void pool_bwd_lists_kernel(PoolArgs a, 
         __device__ Lds() {}
     } lds;
     if ((int)blockIdx.x < bin_blocks) pool_bin_body(a, ws, (int)blockIdx.x % a.levels, (int)blockIdx.x / a.levels, lds.bin);
-    else pool_bwd_verts_body(a, grad_out, ws.vert_partial, zc, (int)blockIdx.x - bin_blocks, verts_blocks, lds.verts);
+    else pool_bwd_verts_body(a, ws, grad_out, (int)blockIdx.x - bin_blocks, verts_blocks, lds.verts);
 }
 
 // What this kernel has to avoid is not traffic but INSTRUCTIONS and TAILS.  The lists are short and skewed: at the training
@@ -508,9 +530,9 @@ __device__ __forceinline__ void pg_run(const PoolArgs &a, const BinSpace &ws, co
     const int dim = a.dims[l], C = a.channels[l], texels = dim * dim;
     const int log_t = p.log_t[l], T = 1 << log_t;
     const int tx0 = run << log_t, nt = min(T, texels - tx0); // texels of this run
-    const int *offs = ws.offsets + (size_t)mesh * ws.off_stride + ws.level_off[l] + tx0;
-    const int *ev = ws.ent_v + ((size_t)mesh * a.levels + l) * 4 * a.nv;
-    const float *ew = ws.ent_w + ((size_t)mesh * a.levels + l) * 4 * a.nv;
+    const int *offs = ws.offs(mesh, l) + tx0;
+    const int *ev = ws.list_v(mesh, l);
+    const float *ew = ws.list_w(mesh, l);
     // where the list of texel `lane` ends (lanes past the run: the end of the run's range)
     const int ends = offs[min(lane + 1, nt)];
     const int E0 = offs[0], E1 = __builtin_amdgcn_readlane(ends, GEOM_WAVE - 1);
@@ -595,18 +617,17 @@ __device__ __forceinline__ void pg_run(const PoolArgs &a, const BinSpace &ws, co
 // finish_z >= 0: the workgroups of that grid.z slice chain the vertex tiles' sums to grad_verts (256 vertices each); gather_tasks
 // = the runs of all maps (0: no map wants a gradient)
 __global__ __launch_bounds__(PL_THREADS) void pool_bwd_grads_kernel(PoolArgs a, BinSpace ws, GatherPlan p, const float *grad_out,
-                                                                    int gather_tasks, int finish_z, int finish_chunks,
-                                                                    float *grad_verts)
+                                                                    int gather_tasks, int finish_z, float *grad_verts)
 {
     __shared__ __attribute__((aligned(16))) float tile[PG_TILE + GEOM_WAVE];
     if ((int)blockIdx.z == finish_z) {
-        pool_bwd_verts_finish_body(a, ws.vert_partial, finish_chunks, grad_verts, blockIdx.y, (int)blockIdx.x * PL_THREADS + (int)threadIdx.x);
+        pool_bwd_verts_finish_body(a, ws, grad_verts, blockIdx.y, (int)blockIdx.x * PL_THREADS + (int)threadIdx.x);
         return;
     }
-    // workgroups go to the eight XCDs round robin (gridDim.x is a multiple of 8: XCD = blockIdx.x % 8): give an XCD CONSECUTIVE
-    // runs -- the 2 x 2 texels a vertex touches then meet in one L2 (its gradient row is fetched from HBM once, not per XCD),
-    // and so do the short runs of a small map that share a 128-byte line of the output
-    const int task = (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
+    // an XCD gets CONSECUTIVE runs (gridDim.x is a multiple of 8) -- the 2 x 2 texels a vertex touches then meet in one L2 (its
+    // gradient row is fetched from HBM once, not per XCD), and so do the short runs of a small map that share a 128-byte line
+    // of the output
+    const int task = geom::xcd_run_item(blockIdx.x, gridDim.x >> 3);
     if (task >= gather_tasks) return;
     int l = 0;
     while (l + 1 < a.levels && task >= p.first_task[l + 1]) ++l;
@@ -623,9 +644,12 @@ __global__ __launch_bounds__(PL_THREADS) void pool_bwd_grads_kernel(PoolArgs a, 
     }
 }
 
-int fill_args(PoolArgs &a, int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos, int levels,
-              const float *const *blocks, const int *channels, const int *dims)
+// The launch arguments of every entry point, checked.  ld: floats between two vertex rows of the pooled features / of their
+// gradient (0 = the pooled width).  todo = false: an empty batch, nothing to launch (the return value is then 0).
+int fill_args(PoolArgs &a, bool &todo, int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos, int levels,
+              const float *const *blocks, const int *channels, const int *dims, int64_t ld)
 {
+    todo = false;
     if (b < 0 || nv < 0 || levels < 0 || levels > GEOM_POOL_MAX_LEVELS) return GEOM_EINVAL;
     if (!verts || !cam_mat || !cam_pos || (levels > 0 && (!blocks || !channels || !dims))) return GEOM_EINVAL;
     if (b > 65535 || (size_t)((nv + PL_VERTS - 1) / PL_VERTS) * b * PL_MAX_CHUNKS > (size_t)INT_MAX - 8) return GEOM_ETOOBIG;
@@ -637,23 +661,32 @@ int fill_args(PoolArgs &a, int b, int nv, const float *verts, const float *cam_m
         a.ctot += channels[l];
         a.chunks += (channels[l] + GEOM_WAVE - 1) / GEOM_WAVE;
     }
-    a.ld = a.ctot;
+    if (b == 0 || nv == 0 || levels == 0) return 0;
+    if (ld && (ld < a.ctot || ld > INT_MAX)) return GEOM_EINVAL;
+    a.ld = ld ? (int)ld : a.ctot;
+    a.zc = a.chunks < PL_MAX_CHUNKS ? a.chunks : PL_MAX_CHUNKS;
+    todo = true;
     return 0;
 }
 
 } // namespace
 
-static int pool_fwd_launch(PoolArgs &a, int b, int nv, float *out, int64_t out_ld, int n_fronts, const float *const *fronts,
-                           const int *widths, const int *cols, float *buf, void *stream)
+// out_ld: floats between two vertex rows of `out` (0 = the pooled width: a contiguous [b,nv,sum channels] tensor; larger: the
+// features are written as a column slice of a wider row-major buffer -- the deformation block's concatenated input);
+// n_fronts: up to two tensors fronts[f] [b, nv, widths[f]] (contiguous) copied into columns [cols[f], cols[f] + widths[f]) of the
+// wide buffer `buf` (row pitch out_ld, `out` = buf + the pooled features' first column) by the same launch: what the caller
+// concatenates in front of the pooled features (GEOMetrics.py:123,128; models.py:241)
+extern "C" int geom_pool_features_fwd_fronts_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
+                                                 int levels, const float *const *blocks, const int *channels, const int *dims,
+                                                 float *out, int64_t out_ld, int n_fronts, const float *const *fronts,
+                                                 const int *widths, const int *cols, float *buf, void *stream)
 {
+    PoolArgs a;
+    bool todo;
+    if (int rc = fill_args(a, todo, b, nv, verts, cam_mat, cam_pos, levels, blocks, channels, dims, out_ld); rc || !todo) return rc;
     if (!out) return GEOM_EINVAL;
-    if (out_ld) {
-        if (out_ld < a.ctot || out_ld > INT_MAX) return GEOM_EINVAL;
-        a.ld = (int)out_ld;
-    }
     PoolFronts fr{};
-    const int zc = a.chunks < PL_MAX_CHUNKS ? a.chunks : PL_MAX_CHUNKS;
-    fr.work_blocks = (int)pool_grid(nv, b, zc);
+    fr.work_blocks = (int)pool_grid(a);
     if (n_fronts < 0 || n_fronts > PL_MAX_FRONTS || (n_fronts && (!fronts || !widths || !cols || !buf))) return GEOM_EINVAL;
     int extra = 0;
     for (int f = 0; f < n_fronts; ++f) {
@@ -664,62 +697,52 @@ static int pool_fwd_launch(PoolArgs &a, int b, int nv, float *out, int64_t out_l
         extra += (int)blocks;
     }
     fr.first_block[n_fronts] = extra, fr.count = n_fronts, fr.dst = buf;
-    hipLaunchKernelGGL(pool_fwd_kernel, dim3(fr.work_blocks + extra), dim3(PL_THREADS), 0, static_cast<hipStream_t>(stream), a, out, zc, fr);
+    hipLaunchKernelGGL(pool_fwd_kernel, dim3(fr.work_blocks + extra), dim3(PL_THREADS), 0, static_cast<hipStream_t>(stream), a, out, fr);
     return geom::launch_status();
 }
 
-// out_ld: floats between two vertex rows of `out` (0 = the pooled width: a contiguous [b,nv,sum channels] tensor; larger: the
-// features are written as a column slice of a wider row-major buffer -- the deformation block's concatenated input)
+// the same with nothing in front
 extern "C" int geom_pool_features_fwd_ld_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
                                              int levels, const float *const *blocks, const int *channels, const int *dims,
                                              float *out, int64_t out_ld, void *stream)
 {
-    PoolArgs a;
-    if (int rc = fill_args(a, b, nv, verts, cam_mat, cam_pos, levels, blocks, channels, dims)) return rc;
-    if (b == 0 || nv == 0 || levels == 0) return 0;
-    return pool_fwd_launch(a, b, nv, out, out_ld, 0, nullptr, nullptr, nullptr, nullptr, stream);
+    return geom_pool_features_fwd_fronts_f32(b, nv, verts, cam_mat, cam_pos, levels, blocks, channels, dims, out, out_ld, 0, nullptr,
+                                             nullptr, nullptr, nullptr, stream);
 }
 
-// ... and up to two tensors fronts[f] [b, nv, widths[f]] (contiguous) copied into columns [cols[f], cols[f] + widths[f]) of the
-// wide buffer `buf` (row pitch out_ld, `out` = buf + the pooled features' first column) by the same launch: what the caller
-// concatenates in front of the pooled features (GEOMetrics.py:123,128; models.py:241)
-extern "C" int geom_pool_features_fwd_fronts_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
-                                                 int levels, const float *const *blocks, const int *channels, const int *dims,
-                                                 float *out, int64_t out_ld, int n_fronts, const float *const *fronts,
-                                                 const int *widths, const int *cols, float *buf, void *stream)
-{
-    PoolArgs a;
-    if (int rc = fill_args(a, b, nv, verts, cam_mat, cam_pos, levels, blocks, channels, dims)) return rc;
-    if (b == 0 || nv == 0 || levels == 0) return 0;
-    return pool_fwd_launch(a, b, nv, out, out_ld, n_fronts, fronts, widths, cols, buf, stream);
-}
+// The workspace at `base` (only its addresses are formed here; a null base serves the size query) and its size in bytes: the
+// offsets block, the vertex ids, the weights (geom_hip.h), then -- 16-byte aligned -- the per-chunk shares of d loss / d (xs, ys)
+// of every vertex (pool_bwd_verts_body).
+struct BinLayout {
+    BinSpace ws;
+    size_t bytes;
+};
 
-static size_t pool_ws_layout(int b, int nv, int levels, const int *dims, BinSpace *ws, void *base)
+static BinLayout pool_ws_layout(int b, int nv, int levels, const int *dims, void *base)
 {
-    int per_mesh = 0;
+    BinLayout lay{};
+    BinSpace &ws = lay.ws;
+    ws.b = b, ws.nv = nv, ws.levels = levels;
     for (int l = 0; l < levels; ++l) {
-        if (ws) ws->level_off[l] = per_mesh;
-        per_mesh += dims[l] * dims[l] + 1;
+        ws.level_off[l] = ws.off_stride;
+        ws.off_stride += dims[l] * dims[l] + 1;
     }
-    const size_t off_bytes = ((size_t)b * per_mesh * sizeof(int) + 15) / 16 * 16;
+    const size_t off_bytes = ((size_t)b * ws.off_stride * sizeof(int) + 15) / 16 * 16;
     const size_t ent = (size_t)b * levels * 4 * nv;
-    if (ws) {
-        char *p = static_cast<char *>(base);
-        ws->offsets = reinterpret_cast<int *>(p);
-        ws->ent_v = reinterpret_cast<int *>(p + off_bytes);
-        ws->ent_w = reinterpret_cast<float *>(p + off_bytes + ent * sizeof(int));
-        ws->off_stride = per_mesh;
-    }
     const size_t lists = (off_bytes + ent * (sizeof(int) + sizeof(float)) + 15) / 16 * 16;
-    if (ws) ws->vert_partial = reinterpret_cast<float *>(static_cast<char *>(base) + lists);
-    // + the per-chunk shares of d loss / d (xs, ys) of every vertex (pool_bwd_verts_body)
-    return lists + (size_t)PL_MAX_CHUNKS * b * nv * 2 * sizeof(float);
+    const uintptr_t p = reinterpret_cast<uintptr_t>(base);
+    ws.offsets = reinterpret_cast<int *>(p);
+    ws.ent_v = reinterpret_cast<int *>(p + off_bytes);
+    ws.ent_w = reinterpret_cast<float *>(p + off_bytes + ent * sizeof(int));
+    ws.vert_partial = reinterpret_cast<float *>(p + lists);
+    lay.bytes = lists + (size_t)PL_MAX_CHUNKS * b * nv * 2 * sizeof(float);
+    return lay;
 }
 
 extern "C" size_t geom_pool_features_bwd_workspace_bytes(int b, int nv, int levels, const int *dims)
 {
     if (b <= 0 || nv <= 0 || levels <= 0 || levels > GEOM_POOL_MAX_LEVELS || !dims) return 0;
-    return pool_ws_layout(b, nv, levels, dims, nullptr, nullptr);
+    return pool_ws_layout(b, nv, levels, dims, nullptr).bytes;
 }
 
 // grad_ld: floats between two vertex rows of `grad_out` (0 = the pooled width; larger: the gradient is read in place out of a
@@ -730,39 +753,32 @@ extern "C" int geom_pool_features_bwd_ld_f32(int b, int nv, const float *verts, 
                                              void *workspace, size_t workspace_bytes, void *stream)
 {
     PoolArgs a;
-    if (int rc = fill_args(a, b, nv, verts, cam_mat, cam_pos, levels, blocks, channels, dims)) return rc;
-    if (b == 0 || nv == 0 || levels == 0) return 0;
+    bool todo;
+    if (int rc = fill_args(a, todo, b, nv, verts, cam_mat, cam_pos, levels, blocks, channels, dims, grad_ld); rc || !todo) return rc;
     if (!grad_out) return GEOM_EINVAL;
-    if (grad_ld) {
-        if (grad_ld < a.ctot || grad_ld > INT_MAX) return GEOM_EINVAL;
-        a.ld = (int)grad_ld;
-    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     bool any_map = false;
     for (int l = 0; l < levels; ++l) {
         a.grad_blocks[l] = grad_blocks ? grad_blocks[l] : nullptr;
         any_map = any_map || a.grad_blocks[l];
         if (dims[l] * dims[l] > BIN_MAX_TEXELS) return GEOM_EUNSUPPORTED;
-
     }
     if (!any_map && !grad_verts) return 0;
-    BinSpace ws;
-    const size_t need = pool_ws_layout(b, nv, levels, dims, &ws, workspace);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) return GEOM_EINVAL;
+    const BinLayout lay = pool_ws_layout(b, nv, levels, dims, workspace);
+    if (!workspace || workspace_bytes < lay.bytes || ((uintptr_t)workspace & 15)) return GEOM_EINVAL;
     GatherPlan plan;
     gather_plan(a, plan);
     if (plan.max_parts > 65534 || (size_t)nv * a.ld * 4 > (size_t)INT_MAX) return GEOM_ETOOBIG;
-    const int zc = a.chunks < PL_MAX_CHUNKS ? a.chunks : PL_MAX_CHUNKS;
     const int bin_blocks = any_map ? levels * b : 0;
-    const unsigned verts_blocks = grad_verts ? pool_grid(nv, b, zc) : 0;
-    hipLaunchKernelGGL(pool_bwd_lists_kernel, dim3(bin_blocks + verts_blocks), dim3(PL_THREADS), 0, s, a, ws, grad_out, zc, bin_blocks,
+    const unsigned verts_blocks = grad_verts ? pool_grid(a) : 0;
+    hipLaunchKernelGGL(pool_bwd_lists_kernel, dim3(bin_blocks + verts_blocks), dim3(PL_THREADS), 0, s, a, lay.ws, grad_out, bin_blocks,
                        (int)verts_blocks);
     const int gather_tasks = any_map ? plan.first_task[levels] : 0;
     const int parts = any_map ? plan.max_parts : 0;
-    int gx = (gather_tasks + 7) / 8 * 8;
-    if (grad_verts && gx < (nv + PL_THREADS - 1) / PL_THREADS) gx = ((nv + PL_THREADS - 1) / PL_THREADS + 7) / 8 * 8;
-    hipLaunchKernelGGL(pool_bwd_grads_kernel, dim3(gx, b, parts + (grad_verts ? 1 : 0)), dim3(PL_THREADS), 0, s, a, ws, plan, grad_out,
-                       gather_tasks, grad_verts ? parts : -1, zc, grad_verts);
+    const int finish_blocks = grad_verts ? (nv + PL_THREADS - 1) / PL_THREADS : 0; // the finish role's slice needs this many in x
+    const unsigned gx = geom::xcd_run_grid(gather_tasks > finish_blocks ? gather_tasks : finish_blocks);
+    hipLaunchKernelGGL(pool_bwd_grads_kernel, dim3(gx, b, parts + (grad_verts ? 1 : 0)), dim3(PL_THREADS), 0, s, a, lay.ws, plan, grad_out,
+                       gather_tasks, grad_verts ? parts : -1, grad_verts);
     return geom::launch_status();
 }
 

@@ -129,7 +129,7 @@ __device__ __forceinline__ ZsPlan zs_plan(const ZsArgs &a, int w, int G)
 {
     ZsPlan p;
     p.q = a.q, p.n_main = a.q, p.extra_rb = -1, p.ue = -1;
-    if ((G & 7) == 0) p.base = ((w & 7) * (G >> 3) + (w >> 3)) * a.q; // contiguous runs per XCD (workgroup w runs on XCD w % 8)
+    if ((G & 7) == 0) p.base = geom::xcd_run_item(w, G >> 3) * a.q; // contiguous runs per XCD (workgroup w runs on XCD w % 8)
     else p.base = w * a.q;
     if (a.split3) {
         if (w < 3 * a.rem) p.extra_rb = a.q * G + w / 3, p.ue = w % 3; // a third of a leftover row-block (column component ue)

@@ -92,8 +92,9 @@ class _InputTap(torch.autograd.Function):
         ctx.in_place = (features.dim() == 3 and features.is_cuda and features.dtype == torch.float32 and pooled.dtype == torch.float32
                         and features.shape[:2] == pooled.shape[:2] and _ops.headroom_of(pooled) == nf)
         if ctx.in_place:
-            buf = _ops._headroom[pooled.untyped_storage().data_ptr()][0]()
-            if not _ops._already_placed(buf, 0, features):      # (the pooling launch may have copied them: batched_pooling(fronts=))
+            rec = _ops.wide_buffer_of(pooled)
+            buf = rec.buf
+            if not rec.holds(0, features):      # (the pooling launch may have copied them: batched_pooling(fronts=))
                 buf[..., :nf].copy_(features)
             _ops._register_headroom(buf, 0)
             full = buf

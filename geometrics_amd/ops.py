@@ -591,36 +591,63 @@ class StageRegularisers(torch.autograd.Function):
 # The driver builds a deformation block's input as cat(positions, cat(previous features, pooled features)) (GEOMetrics.py:118-131,
 # models.py:241): two copies of ~35 MB forward per stage, and slicing copies of the same size when the gradient of the
 # concatenation is taken apart again.  A pooling call that is told how many columns will be put IN FRONT of its output
-# (`headroom`) allocates the wide buffer itself and writes its features at that column offset (geom_pool_features_fwd_ld_f32); the
+# (`headroom`) allocates the wide buffer itself and writes its features at that column offset (geom_pool_features_fwd_fronts_f32); the
 # later "concatenations" (`concat_in_front`) only copy the narrow operand into the free columns and widen the view, and in the
 # backward pass every consumer reads its column slice of the ONE wide gradient in place.
-_headroom = {}     # storage address -> (weak reference to the wide buffer, columns still free in front of the view handed out,
-#                      {first column: (address, version, width) of a tensor the pooling launch already copied there})
+_headroom = {}     # storage address of a wide buffer -> its _WideBuffer
 
 
-def _register_headroom(buf, free, placed=None):
+class _WideBuffer:
+    """What the registry knows of one wide buffer: `ref`, a weak reference to it (the entry goes when the buffer does); `free`,
+    the columns still free in front of the view handed out; `placed`, {first column: stamp of a tensor the pooling launch already
+    copied there}."""
+    __slots__ = ("ref", "free", "placed")
+
+    def __init__(self, ref, free, placed):
+        self.ref, self.free, self.placed = ref, free, placed
+
+    @property
+    def buf(self):
+        return self.ref()
+
+    @staticmethod
+    def stamp(t):
+        return (t.data_ptr(), t._version, t.shape[2])
+
+    def place(self, col, t):
+        """Note that columns [col, col + width) are going to hold `t` as it is now."""
+        self.placed[col] = self.stamp(t)
+
+    def holds(self, col, t):
+        """Whether columns [col, col + width) already hold `t` (PoolFeatures(fronts=...) copied it there)."""
+        return self.placed.get(col) == self.stamp(t)
+
+
+def _register_headroom(buf, free):
+    """Enter the wide buffer `buf` with `free` columns in front of the view handed out, or shrink its free columns (what has been
+    placed in it stays known).  Returns its record."""
     import weakref
     key = buf.untyped_storage().data_ptr()
-    if placed is None:
-        old = _headroom.get(key)
-        placed = old[2] if old is not None and old[0]() is buf else {}
-    _headroom[key] = (weakref.ref(buf, lambda _r, k=key: _headroom.pop(k, None)), free, placed)
+    old = _headroom.get(key)
+    placed = old.placed if old is not None and old.buf is buf else {}      # (a recycled address: another buffer's record)
+    rec = _headroom[key] = _WideBuffer(weakref.ref(buf, lambda _r, k=key: _headroom.pop(k, None)), free, placed)
+    return rec
 
 
-def _already_placed(buf, col, t):
-    """Whether columns [col, col + width) of the wide buffer already hold `t` (PoolFeatures(fronts=...) copied it there)."""
-    hit = _headroom.get(buf.untyped_storage().data_ptr())
-    return hit is not None and hit[0]() is buf and hit[2].get(col) == (t.data_ptr(), t._version, t.shape[2])
+def wide_buffer_of(view):
+    """The record of the wide buffer whose storage `view` lives in, or None."""
+    rec = _headroom.get(view.untyped_storage().data_ptr())
+    return rec if rec is not None and rec.buf is not None else None
 
 
 def headroom_of(t):
     """Free columns in front of `t` [B,V,C] inside a wide buffer made by PoolFeatures(headroom=...) / concat_in_front, or 0."""
     if not (torch.is_tensor(t) and t.dim() == 3 and t.is_cuda and t.stride(2) == 1):
         return 0
-    hit = _headroom.get(t.untyped_storage().data_ptr())
-    if hit is None or hit[0]() is None:
+    rec = wide_buffer_of(t)
+    if rec is None:
         return 0
-    buf, free = hit[0](), hit[1]
+    buf, free = rec.buf, rec.free
     ld = buf.shape[2]
     if t.stride(1) != ld or t.stride(0) != t.shape[1] * ld or t.shape[:2] != buf.shape[:2] or t.storage_offset() != free:
         return 0
@@ -634,10 +661,10 @@ class _ConcatInFront(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, front, view):
-        hit = _headroom[view.untyped_storage().data_ptr()]
-        buf, free = hit[0](), hit[1]
+        rec = wide_buffer_of(view)
+        buf, free = rec.buf, rec.free
         cf = front.shape[2]
-        if not _already_placed(buf, free - cf, front):
+        if not rec.holds(free - cf, front):
             buf[..., free - cf:free].copy_(front)
         out = buf[..., free - cf:]
         _register_headroom(buf, free - cf)
@@ -686,7 +713,7 @@ class PoolFeatures(torch.autograd.Function):
         chans = (ctypes.c_int * n)(*[t.shape[1] for t in blks])
         dims = (ctypes.c_int * n)(*[t.shape[2] for t in blks])
         ctot = sum(t.shape[1] for t in blks)
-        placed, srcs = {}, []
+        srcs, own = [], []       # (contiguous front, its first column); (column, front) of those that are the caller's own tensor
         if fronts:
             col = 0
             for t in fronts:
@@ -696,25 +723,24 @@ class PoolFeatures(torch.autograd.Function):
                 c = t.detach().contiguous()
                 srcs.append((c, col))
                 if c.data_ptr() == t.data_ptr():       # (a copy made here is not what the caller will hand to the concatenation)
-                    placed[col] = (t.data_ptr(), t._version, t.shape[2])
+                    own.append((col, t))
                 col += t.shape[2]
             if col != headroom or len(srcs) > 2:
                 raise RuntimeError("at most two fronts, whose widths add up to the headroom")
         if headroom > 0:      # the features as the trailing columns of a wider buffer: see concat_in_front
             buf = torch.empty(b, nv, headroom + ctot, dtype=torch.float32, device=v.device)
             out = buf[..., headroom:]
-            _register_headroom(buf, headroom, placed)
+            rec = _register_headroom(buf, headroom)
+            for col, t in own:
+                rec.place(col, t)
         else:
-            out = torch.empty(b, nv, ctot, dtype=torch.float32, device=v.device)
+            buf, out = None, torch.empty(b, nv, ctot, dtype=torch.float32, device=v.device)
+        m = len(srcs)
         with torch.cuda.device(v.device):
-            if srcs:
-                m = len(srcs)
-                _lib.call("geom_pool_features_fwd_fronts_f32", b, nv, v.data_ptr(), cam_mat.data_ptr(), cam_pos.data_ptr(), n,
-                          ptrs, chans, dims, out.data_ptr(), headroom + ctot, m, (ctypes.c_void_p * m)(*[t.data_ptr() for t, _ in srcs]),
-                          (ctypes.c_int * m)(*[t.shape[2] for t, _ in srcs]), (ctypes.c_int * m)(*[c for _, c in srcs]), buf.data_ptr())
-            else:
-                _lib.call("geom_pool_features_fwd_ld_f32", b, nv, v.data_ptr(), cam_mat.data_ptr(), cam_pos.data_ptr(), n,
-                          ptrs, chans, dims, out.data_ptr(), headroom + ctot if headroom > 0 else 0)
+            _lib.call("geom_pool_features_fwd_fronts_f32", b, nv, v.data_ptr(), cam_mat.data_ptr(), cam_pos.data_ptr(), n,
+                      ptrs, chans, dims, out.data_ptr(), headroom + ctot if headroom > 0 else 0, m,
+                      (ctypes.c_void_p * m)(*[t.data_ptr() for t, _ in srcs]), (ctypes.c_int * m)(*[t.shape[2] for t, _ in srcs]),
+                      (ctypes.c_int * m)(*[c for _, c in srcs]), _lib.ptr(buf))
         ctx.save_for_backward(v, cam_mat, cam_pos, *blks)
         ctx.meta = (ptrs, chans, dims, n)
         return out

@@ -680,7 +680,14 @@ int geom_vertex_bn_bwd_f32(int b, int nv, int c, const float *x, const float *gr
  * map gradient is computed as a gather over texel -> (vertex, weight) lists built in `workspace` (device,
  * 16-byte aligned, >= geom_pool_features_bwd_workspace_bytes(...) bytes), which also holds the per-channel-chunk
  * partial sums of the vertex gradient (added up in chunk order by a finishing launch): required whenever a
- * gradient is requested (ABI 9; GEOM_EINVAL otherwise); dims[l] <= 64, else GEOM_EUNSUPPORTED. */
+ * gradient is requested (ABI 9; GEOM_EINVAL otherwise); dims[l] <= 64, else GEOM_EUNSUPPORTED.
+ * The lists' part of the workspace after a backward call that asked for a map gradient, in this order:
+ *   offsets: int32, per mesh one block of sum over l of (dims[l]*dims[l] + 1) ints, level-major -- inside level l's part,
+ *            entry t is where texel t's list starts and entry dims[l]*dims[l] where the last one ends; the offsets of all
+ *            meshes together are padded to a multiple of 16 bytes;
+ *   vertex ids: int32, 4*nv per (mesh, level), (mesh, level) number mesh*levels + l: the lists of that map, texel after texel;
+ *   weights:    float, 4*nv per (mesh, level), entry for entry beside the vertex ids.
+ * The order inside a list is not defined (an atomic cursor fills it).  The per-chunk sums follow, 16-byte aligned. */
 size_t geom_pool_features_bwd_workspace_bytes(int b, int nv, int levels, const int *dims);
 #define GEOM_POOL_MAX_LEVELS 8
 /* Forward and backward take a ROW PITCH: out_ld / grad_ld = floats between two vertex rows (0 = the pooled width).

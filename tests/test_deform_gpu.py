@@ -348,8 +348,9 @@ def test_block_input_assembled_in_place_equals_the_concatenations(gpu):
         p, f_prev = pos.clone().requires_grad_(True), prev.clone().requires_grad_(True)
         pooled = utils.batched_pooling(ms, p, img, headroom=3 + 192 if in_place else 0, fronts=(p, f_prev) if fronts else None)
         if fronts:      # the pooling launch placed both: the concatenations below copy nothing
-            buf = ops._headroom[pooled.untyped_storage().data_ptr()][0]()
-            assert ops._already_placed(buf, 0, p) and ops._already_placed(buf, 3, f_prev)
+            rec = ops.wide_buffer_of(pooled)
+            buf = rec.buf
+            assert buf is not None and rec.holds(0, p) and rec.holds(3, f_prev)
             assert torch.equal(buf[..., :3], p.detach()) and torch.equal(buf[..., 3:195], f_prev.detach())
         assert (ops.headroom_of(pooled) == 195) == in_place
         f = utils.concat_features(f_prev, pooled) if in_place else torch.cat((f_prev, pooled), dim=-1)
