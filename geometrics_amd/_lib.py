@@ -1,7 +1,9 @@
 """ctypes binding of libgeom_hip.so (the C ABI declared in include/geom_hip.h).
 
 torch is used only for device memory and the current HIP stream; the signatures, argument structs and limits are read
-from the header (_header.py): plain pointers and sizes.  Loading fails loudly -- there is no fallback implementation.
+from the header (_header.py).  call() / status() / args() take tensors for the pointers and check them against the pointee
+types declared there; lib() is the plain binding (every pointer untyped).  Loading fails loudly -- there is no fallback
+implementation.
 """
 import ctypes
 import os
@@ -69,14 +71,125 @@ def quirk_flags():
     return FLAG_REF_TAIL_TRUNC if _reference_quirks else 0
 
 
+# ---- what may stand for a pointer of the ABI ---------------------------------------------------------------------------------
+# None (NULL); a python int or a ctypes object (a host pointer, address arithmetic: passed on unchecked); a torch.Tensor -- on a
+# HIP device, of a dtype the pointee declared in the header admits, on the device of every other tensor of the call; for a
+# struct pointer an instance of that struct (args() below) or a list of them (a host array); for a `type *const *` a list /
+# tuple of tensors and None.  Contiguity and shape are NOT looked at here (column views with a leading-dimension argument are
+# legitimate): require() and the wrappers do that.  The smallest table that admits what the package passes:
+ADMITS = {"float": (torch.float32,), "int": (torch.int32,), "int64_t": (torch.int64,),
+          "uint16_t": (torch.int16,),      # sign masks, bf16 planes
+          "uint64_t": (torch.int64,),      # the sampler state
+          "void": None}                    # any dtype
+# entry point / struct -> (number of arguments, [(position, name, C type, depth, admitted dtypes, struct class)] of its pointers)
+_plans = {}
+
+
+def _plan(name):
+    """What to do with each pointer parameter of `name`, worked out from the header's table the first time `name` is called."""
+    described = list(_header.PARAMETERS[name])
+    if name in _header.PROTOTYPES and (not described or described.pop()[1:] != ("void", 1)):      # status() supplies the stream
+        raise RuntimeError("%s takes no stream: call it on lib() directly" % name)
+    pointers = []
+    for i, (param, pointee, depth) in enumerate(described):
+        struct = _header.STRUCTS.get(pointee)
+        if depth and struct is None and pointee not in ADMITS:
+            raise RuntimeError("%s: no tensor dtype is known for `%s %s%s`" % (name, pointee, "*" * depth, param))
+        if depth:
+            pointers.append((i, param, "%s %s" % (pointee, "*" * depth), depth, None if struct else ADMITS[pointee], struct))
+    _plans[name] = plan = (len(described), pointers)
+    return plan
+
+
+def _address(name, p, t, dev):
+    """data_ptr() of tensor `t` given for pointer `p` of `name` after the checks above -> (address, the call's device)."""
+    why = None
+    if not t.is_cuda:
+        why = "it must live on a HIP device"
+    elif p[4] is not None and t.dtype not in p[4]:
+        why = "it must be %s" % " or ".join(map(str, p[4]))
+    elif dev is not None and t.device != dev:
+        why = "the call's other tensors are on %s" % dev
+    if why:
+        raise RuntimeError("%s: parameter `%s` (declared `%s%s`) was given a %s tensor on %s -- %s"
+                           % (name, p[1], p[2], p[1], t.dtype, t.device, why))
+    return t.data_ptr(), t.device
+
+
+def _struct_device(name, p, a, dev):
+    """Struct `a` given for pointer `p` of `name`: of the declared type, its tensors (args() below) on the call's device."""
+    if type(a) is not p[5]:
+        raise RuntimeError("%s: parameter `%s` (declared `%s%s`) was given a %s" % (name, p[1], p[2], p[1], type(a).__name__))
+    on = a.__dict__.get("_device")
+    if on is not None and dev is not None and on != dev:
+        raise RuntimeError("%s: the tensors of `%s` are on %s, the call's other tensors on %s" % (name, p[1], on, dev))
+    return on if dev is None else dev
+
+
+def convert(name, values):
+    """The C arguments of entry point (or the field values of struct) `name` from `values` under the rule above, and the
+    device of the tensors among them (None: there were none).  Eager steps are host-bound: one test per tensor on the way
+    through, _address() to say what was wrong."""
+    count, pointers = _plans.get(name) or _plan(name)
+    if len(values) != count:
+        raise RuntimeError("%s takes %d arguments%s (%d given)" % (name, count, " and the stream" if name in _header.PROTOTYPES
+                                                                    else "", len(values)))
+    out, dev = list(values), None
+    for p in pointers:
+        a = out[p[0]]
+        if a is None or type(a) is int:
+            continue
+        if isinstance(a, torch.Tensor):
+            d = a.device
+            if (d == dev or (dev is None and a.is_cuda)) and p[3] == 1 and (p[4] is None or a.dtype in p[4]):
+                out[p[0]], dev = a.data_ptr(), d
+            elif p[3] != 1:
+                raise RuntimeError("%s: parameter `%s` (declared `%s%s`) takes a list of tensors" % (name, p[1], p[2], p[1]))
+            else:
+                out[p[0]], dev = _address(name, p, a, dev)
+        elif isinstance(a, (list, tuple)):
+            if p[5] is not None:          # a host array of argument structs
+                out[p[0]] = array = (p[5] * len(a))()
+                for j, s in enumerate(a):
+                    dev = _struct_device(name, p, s, dev)
+                    array[j] = s
+            elif p[3] == 2:
+                out[p[0]] = array = (ctypes.c_void_p * len(a))()
+                for j, t in enumerate(a):
+                    if t is not None:
+                        array[j], dev = _address(name, p, t, dev)
+            else:
+                raise RuntimeError("%s: parameter `%s` (declared `%s%s`) takes no list" % (name, p[1], p[2], p[1]))
+        elif isinstance(a, ctypes.Structure):
+            dev = _struct_device(name, p, a, dev)
+            out[p[0]] = ctypes.byref(a)
+    return out, dev
+
+
+def args(struct, *values):
+    """An argument struct of the header from its field values in header order, pointers under the same rule.  The struct
+    remembers the device of its tensors for the call it goes into; the tensors are the caller's to keep until the launch is
+    issued."""
+    cvalues, dev = convert(struct.__name__, values)
+    a = struct(*cvalues)
+    a._device = dev
+    return a
+
+
 def status(name, *args, stream=None):
-    """Invoke an entry point on the current stream of the current device (or on `stream`, a raw hipStream_t) and return its
-    code: 0, a hipError_t or a negative GEOM_E* -- for callers that look at GEOM_EUNSUPPORTED before they check()."""
-    return getattr(lib(), name)(*args, stream_ptr() if stream is None else stream)
+    """Invoke an entry point on the device of its tensor arguments (the current one when it has none), on that device's current
+    stream (or on `stream`, a raw hipStream_t), and return its code: 0, a hipError_t or a negative GEOM_E* -- for callers that
+    look at GEOM_EUNSUPPORTED before they check()."""
+    cargs, dev = convert(name, args)
+    fn = getattr(lib(), name)
+    if dev is not None and dev.index != torch.cuda.current_device():
+        with torch.cuda.device(dev):
+            return fn(*cargs, stream_ptr() if stream is None else stream)
+    return fn(*cargs, stream_ptr() if stream is None else stream)
 
 
 def call(name, *args):
-    """Invoke an entry point on the current stream of the current device and raise on failure."""
+    """Invoke an entry point as status() does and raise on failure."""
     check(status(name, *args), name)
 
 

@@ -31,7 +31,7 @@ def relu_mask(s, k):
 def _table(csr, transposed):
     """The table arguments of an entry point: width, columns, values, and the CSR tail of the rows longer than the table."""
     col, val, over = (csr.ell_col_t, csr.ell_val_t, csr.over_t) if transposed else (csr.ell_col, csr.ell_val, csr.over)
-    return (csr.ell_w, _lib.ptr(col), _lib.ptr(val)) + tuple(map(_lib.ptr, over or (None, None, None)))
+    return (csr.ell_w, col, val) + tuple(over or (None, None, None))
 
 
 def _table_took(csr, name, *args):
@@ -49,16 +49,13 @@ def forward(s, bias_c, csr, k, act, out, want_mask=False, head=None):
     refusal is an error).  Returns the ReLU sign mask when one was asked for and written."""
     b, nv, c = s.shape
     mask = relu_mask(s, k) if want_mask and act == ACT_RELU and csr.ell_w else None
-    operands = (s.data_ptr(), _lib.ptr(bias_c), act, out.data_ptr())
-    with torch.cuda.device(s.device):
-        if head is not None:
-            base, scale, pos = head
-            _lib.call("geom_zn_gcn_aggregate_ell_head_fwd_f32", b, nv, c, k, *_table(csr, False), *operands, _lib.ptr(mask),
-                      base.data_ptr(), float(scale), pos.data_ptr())
-        elif not _table_took(csr, "geom_zn_gcn_aggregate_ell_fwd_f32", b, nv, c, k, *_table(csr, False), *operands, _lib.ptr(mask)):
-            mask = None
-            _lib.call("geom_zn_gcn_aggregate_fwd_f32", b, nv, c, k, csr.rowptr.data_ptr(), csr.col.data_ptr(), csr.val.data_ptr(),
-                      *operands)
+    operands = (s, bias_c, act, out)
+    if head is not None:
+        base, scale, pos = head
+        _lib.call("geom_zn_gcn_aggregate_ell_head_fwd_f32", b, nv, c, k, *_table(csr, False), *operands, mask, base, float(scale), pos)
+    elif not _table_took(csr, "geom_zn_gcn_aggregate_ell_fwd_f32", b, nv, c, k, *_table(csr, False), *operands, mask):
+        mask = None
+        _lib.call("geom_zn_gcn_aggregate_fwd_f32", b, nv, c, k, csr.rowptr, csr.col, csr.val, *operands)
     return mask
 
 
@@ -93,20 +90,16 @@ def backward(g, csr, k, act, out, mask, want_bias, bias=None, arena=None, head=N
         scratch = (rows, c) if below is not None else _lib.lib().geom_zn_gcn_bwd_scratch_floats(b, nv, c)
         bg = _pass.bias_gradient(bias, c, device, scratch, opted_in=arena is not None)
     ell_w = csr.ell_w
-    results = (grad_support.data_ptr(), _lib.ptr(bg.now), _lib.ptr(bg.scratch))
-    with torch.cuda.device(device):
-        if below is not None:      # (the boundary below picks its input gradient up from the link instead of computing it)
-            _fused.layer_backward(g, out, mask, csr, k, act, below.wt, g_out=grad_support, grad_in=below.take_dx(b, nv),
-                                  colsum_partial=bg.scratch, grad_pos=grad_pos, head_scale=scale, shape=(b, nv, c))
-            below.stamp(grad_support)
-        elif head is not None:
-            _lib.call("geom_zn_gcn_aggregate_ell_head_bwd_f32", b, nv, c, k, *_table(csr, True), grad_pos.data_ptr(), scale,
-                      _lib.ptr(mask), act, *results)
-        elif not _table_took(csr, "geom_zn_gcn_aggregate_ell_bwd_f32", b, nv, c, k, *_table(csr, True), g.data_ptr(), _lib.ptr(out),
-                             _lib.ptr(mask), act, *results):
-            ell_w = 0
-            _lib.call("geom_zn_gcn_aggregate_bwd_f32", b, nv, c, k, csr.rowptr_t.data_ptr(), csr.col_t.data_ptr(),
-                      csr.val_t.data_ptr(), g.data_ptr(), _lib.ptr(out), act, *results)
+    results = (grad_support, bg.now, bg.scratch)
+    if below is not None:      # (the boundary below picks its input gradient up from the link instead of computing it)
+        _fused.layer_backward(g, out, mask, csr, k, act, below.wt, g_out=grad_support, grad_in=below.take_dx(b, nv),
+                              colsum_partial=bg.scratch, grad_pos=grad_pos, head_scale=scale, shape=(b, nv, c))
+        below.stamp(grad_support)
+    elif head is not None:
+        _lib.call("geom_zn_gcn_aggregate_ell_head_bwd_f32", b, nv, c, k, *_table(csr, True), grad_pos, scale, mask, act, *results)
+    elif not _table_took(csr, "geom_zn_gcn_aggregate_ell_bwd_f32", b, nv, c, k, *_table(csr, True), g, out, mask, act, *results):
+        ell_w = 0
+        _lib.call("geom_zn_gcn_aggregate_bwd_f32", b, nv, c, k, csr.rowptr_t, csr.col_t, csr.val_t, g, out, act, *results)
     if below is not None:          # the boundary kernel never reduces its partials itself
         bg.finish(rows)
     elif bg.defer:
@@ -120,9 +113,7 @@ def narrow_head_forward(s, bias_c, csr, k, act, base, scale, pos, want_sign):
     steps in its order, so its bits; no [B,V,C] output.  Returns the ReLU sign words ([B*V] int16) when asked for, else None."""
     b, nv, c = s.shape
     sign = torch.empty(b * nv, dtype=torch.int16, device=s.device) if want_sign and act == ACT_RELU else None
-    with torch.cuda.device(s.device):
-        _lib.call("geom_zn_gcn_narrow_head_fwd_f32", b, nv, c, k, *_table(csr, False), s.data_ptr(), _lib.ptr(bias_c), act,
-                  base.data_ptr(), float(scale), pos.data_ptr(), _lib.ptr(sign))
+    _lib.call("geom_zn_gcn_narrow_head_fwd_f32", b, nv, c, k, *_table(csr, False), s, bias_c, act, base, float(scale), pos, sign)
     return sign
 
 
@@ -133,8 +124,7 @@ def narrow_head_backward(grad_pos, scale, sign, csr, k, act, shape, want_bias, b
     gs4 = torch.empty(b * nv, 4, dtype=torch.float32, device=grad_pos.device)
     rows = int(_lib.lib().geom_zn_gcn_bwd_partial_rows(b, nv, c, k, csr.ell_w))
     bg = _pass.bias_gradient(bias, c, grad_pos.device, (rows, c)) if want_bias else _pass.NO_BIAS_GRADIENT
-    with torch.cuda.device(grad_pos.device):
-        _lib.call("geom_zn_gcn_narrow_head_bwd_f32", b, nv, c, k, *_table(csr, True), grad_pos.data_ptr(), float(scale),
-                  _lib.ptr(sign), act, gs4.data_ptr(), _lib.ptr(bg.scratch))
+    _lib.call("geom_zn_gcn_narrow_head_bwd_f32", b, nv, c, k, *_table(csr, True), grad_pos, float(scale), sign, act, gs4,
+              bg.scratch)
     bg.finish(rows)
     return gs4, bg.out

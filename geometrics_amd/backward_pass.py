@@ -265,13 +265,9 @@ def _ints(seq):
     return (ctypes.c_int * len(seq))(*seq)
 
 
-def _ptrs(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
 def _colsum_args(jobs):
-    return (len(jobs), _ptrs([j.partials for j in jobs]), _ints([j.rows for j in jobs]), _ints([j.cols for j in jobs]),
-            _ptrs([j.out for j in jobs]))
+    return (len(jobs), [j.partials for j in jobs], _ints([j.rows for j in jobs]), _ints([j.cols for j in jobs]),
+            [j.out for j in jobs])
 
 
 def _by_stream(jobs):
@@ -283,10 +279,9 @@ def _by_stream(jobs):
 
 def _launch_colsums(jobs):
     for stream, group in _by_stream(jobs):
-        with torch.cuda.device(stream.device):
-            for c0 in range(0, len(group), _lib.COLSUM_MAX_JOBS):
-                _lib.check(_lib.status("geom_colsum_batch_f32", *_colsum_args(group[c0:c0 + _lib.COLSUM_MAX_JOBS]),
-                                       stream=stream.cuda_stream), "geom_colsum_batch_f32")
+        for c0 in range(0, len(group), _lib.COLSUM_MAX_JOBS):
+            _lib.check(_lib.status("geom_colsum_batch_f32", *_colsum_args(group[c0:c0 + _lib.COLSUM_MAX_JOBS]),
+                                   stream=stream.cuda_stream), "geom_colsum_batch_f32")
 
 
 def _launch_reduces(jobs):
@@ -298,7 +293,7 @@ def _launch_joint(reduces, colsums, stream):
     """Weight AND bias gradients in one launch -- with the optimiser's step when the launch finishes the gradient of every one
     of its parameters."""
     weights = (len(reduces), _ints([j.rows for j in reduces]), _ints([j.cin for j in reduces]), _ints([j.c for j in reduces]),
-               _ptrs([j.workspace for j in reduces]), _ptrs([j.out for j in reduces]))
+               [j.workspace for j in reduces], [j.out for j in reduces])
     biases = _colsum_args(colsums)
     opt = switches.optimizer
     slots = None
@@ -307,20 +302,19 @@ def _launch_joint(reduces, colsums, stream):
         slots = [index.get(id(job.param())) if job.param is not None else None for job in reduces + colsums]
         if None in slots or sorted(slots) != list(range(len(opt.params))) or opt.params[0].device != stream.device:
             slots = None
-    with torch.cuda.device(stream.device):
-        if slots is None:
-            _lib.check(_lib.status("geom_dense_reduce2_f32", *weights, None, *biases, stream=stream.cuda_stream),
-                       "geom_dense_reduce2_f32")
-        else:
-            pick = lambda seq, ks: _ptrs([seq[k] for k in ks])
-            wk, bk = slots[:len(reduces)], slots[len(reduces):]
-            params = [p.data for p in opt.params]
-            _lib.check(_lib.status(
-                "geom_dense_reduce_adam_f32",
-                *weights, pick(params, wk), pick(opt.exp_avg, wk), pick(opt.exp_avg_sq, wk),
-                *biases, pick(params, bk), pick(opt.exp_avg, bk), pick(opt.exp_avg_sq, bk), float(opt.lr), float(opt.betas[0]),
-                float(opt.betas[1]), float(opt.eps), opt.state.data_ptr(), stream=stream.cuda_stream), "geom_dense_reduce_adam_f32")
-            opt._stepped_in_backward = True
+    if slots is None:
+        _lib.check(_lib.status("geom_dense_reduce2_f32", *weights, None, *biases, stream=stream.cuda_stream),
+                   "geom_dense_reduce2_f32")
+    else:
+        pick = lambda seq, ks: [seq[k] for k in ks]
+        wk, bk = slots[:len(reduces)], slots[len(reduces):]
+        params = [p.data for p in opt.params]
+        _lib.check(_lib.status(
+            "geom_dense_reduce_adam_f32",
+            *weights, pick(params, wk), pick(opt.exp_avg, wk), pick(opt.exp_avg_sq, wk),
+            *biases, pick(params, bk), pick(opt.exp_avg, bk), pick(opt.exp_avg_sq, bk), float(opt.lr), float(opt.betas[0]),
+            float(opt.betas[1]), float(opt.eps), opt.state, stream=stream.cuda_stream), "geom_dense_reduce_adam_f32")
+        opt._stepped_in_backward = True
 
 
 # ---- the registry: autograd graph-task id -> the record of that pass ----------------------------------------------------------

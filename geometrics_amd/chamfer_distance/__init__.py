@@ -111,9 +111,7 @@ def chamfer_nn_culled(xyz1, xyz2, order1="morton", order2="morton", flags=None, 
     idx2 = torch.empty(b, m, dtype=torch.int32, device=dev)
     L = _lib.lib()
     ws = torch.empty(max(int(L.geom_chamfer_nn_culled_workspace_floats(b, n, m)), 4), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("geom_chamfer_nn_culled_f32", b, n, xyz1.data_ptr(), m, xyz2.data_ptr(), _lib.ptr(o1), _lib.ptr(o2),
-                  dist1.data_ptr(), idx1.data_ptr(), dist2.data_ptr(), idx2.data_ptr(), flags, ws.data_ptr())
+    _lib.call("geom_chamfer_nn_culled_f32", b, n, xyz1, m, xyz2, o1, o2, dist1, idx1, dist2, idx2, flags, ws)
     return dist1, idx1, dist2, idx2
 
 
@@ -124,10 +122,7 @@ def forward_cuda(xyz1, xyz2, dist1, dist2, idx1, idx2, flags=None):
         flags = default_flags()
     b, n, _ = xyz1.shape
     m = xyz2.shape[1]
-    with torch.cuda.device(xyz1.device):
-        code = _lib.status("geom_chamfer_nn_f32", b, n, xyz1.data_ptr(), m, xyz2.data_ptr(),
-                           dist1.data_ptr(), idx1.data_ptr(), dist2.data_ptr(), idx2.data_ptr(), flags)
-    _lib.check(code, "geom_chamfer_nn_f32")
+    _lib.call("geom_chamfer_nn_f32", b, n, xyz1, m, xyz2, dist1, idx1, dist2, idx2, flags)
 
 
 class ChamferDistanceFunction(torch.autograd.Function):

@@ -122,10 +122,6 @@ def serves_wide(block, features, pooled, csr):
         bn._synchronised() or bn.momentum is None for bn in hidden_layers(block)[1])
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 TAIL = _lib.DEFORM_TAIL      # entries of an adjacency row beyond the 8-wide neighbour table that the launches take
 
 
@@ -167,10 +163,7 @@ def pack_weights(weights, zero=None):
     dev = w2[0].device
     fwd = torch.empty(n, 192 * 192, dtype=torch.float32, device=dev)
     bwd = torch.empty(n, 192 * 192, dtype=torch.float32, device=dev)
-    ptrs = (ctypes.c_void_p * n)(*[w.data_ptr() for w in w2])
-    with torch.cuda.device(dev):
-        _lib.call("geom_deform_pack_weights_zero_f32", n, ptrs, fwd.data_ptr(), bwd.data_ptr(), _p(zero),
-                  0 if zero is None else zero.numel())
+    _lib.call("geom_deform_pack_weights_zero_f32", n, w2, fwd, bwd, zero, 0 if zero is None else zero.numel())
     return fwd, bwd
 
 
@@ -192,7 +185,7 @@ _chain_lock = threading.Lock()
 def chain_fits(nv, device):
     if not chain:
         return False
-    with torch.cuda.device(device):
+    with torch.cuda.device(device):      # (the occupancy query and the capture test are about the current device and stream)
         if not _lib.lib().geom_deform_chain_fits(int(nv)):
             return False
         mine = torch.cuda.current_stream(device)
@@ -216,33 +209,27 @@ def _forward_args(s_in, bias, csr, bn_w, bn_b, run_mean, run_var, training, mome
                   save_mean, save_invstd, w_next=None, s_out=None, w_head=None, s_head=None):
     b, nv, c = s_in.shape
     tail = _tail_tables(csr)
-    return _lib.DeformFwd(b, nv, c, 64, csr.ell_w, _p(s_in), _p(bias), _p(csr.ell_col), _p(csr.ell_val), _p(tail[0]), _p(tail[1]),
-                          _p(bn_w), _p(bn_b), _p(run_mean), _p(run_var), int(training), float(momentum), float(eps),
-                          int(relu), _p(res), res.stride(1) if res is not None else 0, float(scale), _p(z_out), _p(x_out),
-                          _p(save_mean), _p(save_invstd), _p(w_next), _p(s_out), _p(w_head), _p(s_head), 0)
+    return _lib.args(_lib.DeformFwd, b, nv, c, 64, csr.ell_w, s_in, bias, csr.ell_col, csr.ell_val, tail[0], tail[1], bn_w,
+                     bn_b, run_mean, run_var, int(training), float(momentum), float(eps), int(relu), res,
+                     res.stride(1) if res is not None else 0, float(scale), z_out, x_out, save_mean, save_invstd, w_next, s_out,
+                     w_head, s_head, 0)
 
 
 def layer_forward(s_in, *args, **kwargs):
     """One forward launch (geom_deform_layer_fwd_f32); w_next = the next layer's weight PACKED (pack_weights()[0][l]); see
     include/geom_hip.h for the operands."""
-    a = _forward_args(s_in, *args, **kwargs)
-    with torch.cuda.device(s_in.device):
-        _lib.call("geom_deform_layer_fwd_f32", ctypes.addressof(a))
+    _lib.call("geom_deform_layer_fwd_f32", _forward_args(s_in, *args, **kwargs))
 
 
 def wide_layer_forward(s_in, *args, **kwargs):
     """layer_forward for 17 .. WIDE_MAX_BATCH meshes (geom_deform_layer_wide_fwd_f32): same arguments, same results."""
-    a = _forward_args(s_in, *args, **kwargs)
-    with torch.cuda.device(s_in.device):
-        _lib.call("geom_deform_layer_wide_fwd_f32", ctypes.addressof(a))
+    _lib.call("geom_deform_layer_wide_fwd_f32", _forward_args(s_in, *args, **kwargs))
 
 
-def chain_forward(layers, done, device):
+def chain_forward(layers, done):
     """`layers` (lists of layer_forward's arguments) as ONE launch (geom_deform_chain_fwd_f32); done: int32 [nv * CTR_STRIDE],
     zero."""
-    structs = (_lib.DeformFwd * len(layers))(*[_forward_args(*a, **k) for a, k in layers])
-    with torch.cuda.device(device):
-        _lib.call("geom_deform_chain_fwd_f32", len(layers), ctypes.addressof(structs), done.data_ptr())
+    _lib.call("geom_deform_chain_fwd_f32", len(layers), [_forward_args(*a, **k) for a, k in layers], done)
 
 
 def rows_operand(t, shape, limit=None):
@@ -276,10 +263,9 @@ def _backward_args(shape, csr, z, bn_w, bn_b, save_mean, save_invstd, relu, has_
     tail = _tail_tables(csr)
     g, g_ld = rows_operand(g, shape)
     g2, g2_ld = rows_operand(g2, shape)
-    a = _lib.DeformBwd(b, nv, c, 64, csr.ell_w, _p(dz_up), _p(csr.ell_col_t), _p(csr.ell_val_t), _p(tail[2]), _p(tail[3]),
-                       _p(ds_up), _p(wt_up), _p(g), _p(g2), g_ld, g2_ld, _p(z), _p(bn_w), _p(bn_b), _p(save_mean),
-                       _p(save_invstd), int(relu), int(has_res), float(scale), _p(grad_res), _p(dz), _p(grad_bn_w),
-                       _p(grad_bn_b), _p(colsum), _p(ds_head), _p(w_head), _p(x_top), _p(dw_head), 0)
+    a = _lib.args(_lib.DeformBwd, b, nv, c, 64, csr.ell_w, dz_up, csr.ell_col_t, csr.ell_val_t, tail[2], tail[3], ds_up, wt_up,
+                  g, g2, g_ld, g2_ld, z, bn_w, bn_b, save_mean, save_invstd, int(relu), int(has_res), float(scale), grad_res,
+                  dz, grad_bn_w, grad_bn_b, colsum, ds_head, w_head, x_top, dw_head, 0)
     return a, (g, g2)
 
 
@@ -287,24 +273,20 @@ def layer_backward(shape, csr, z, *args, **kwargs):
     """One backward launch (geom_deform_layer_bwd_f32); wt_up = the layer above's weight, TRANSPOSED and packed
     (pack_weights()[1][l])."""
     a, _keep = _backward_args(shape, csr, z, *args, **kwargs)
-    with torch.cuda.device(z.device):
-        _lib.call("geom_deform_layer_bwd_f32", ctypes.addressof(a))
+    _lib.call("geom_deform_layer_bwd_f32", a)
 
 
 def wide_layer_backward(shape, csr, z, *args, **kwargs):
     """layer_backward for 17 .. WIDE_MAX_BATCH meshes (geom_deform_layer_wide_bwd_f32): same arguments, same results."""
     a, _keep = _backward_args(shape, csr, z, *args, **kwargs)
-    with torch.cuda.device(z.device):
-        _lib.call("geom_deform_layer_wide_bwd_f32", ctypes.addressof(a))
+    _lib.call("geom_deform_layer_wide_bwd_f32", a)
 
 
-def chain_backward(layers, done, device, ds_first=None):
+def chain_backward(layers, done, ds_first=None):
     """`layers` (lists of layer_backward's arguments, the top layer first) as ONE launch (geom_deform_chain_bwd_f32); ds_first:
     receives the aggregation backward of the last layer's dZ (the chain's first layer has no activation behind its support)."""
     built = [_backward_args(*a, **k) for a, k in layers]
-    structs = (_lib.DeformBwd * len(built))(*[b[0] for b in built])
-    with torch.cuda.device(device):
-        _lib.call("geom_deform_chain_bwd_f32", len(built), ctypes.addressof(structs), done.data_ptr(), _p(ds_first))
+    _lib.call("geom_deform_chain_bwd_f32", len(built), [b[0] for b in built], done, ds_first)
 
 
 class _HiddenChain(torch.autograd.Function):
@@ -357,7 +339,7 @@ class _HiddenChain(torch.autograd.Function):
                 forward_launch(*call[0], **call[1])
             s_cur = s_buf[i & 1]
         if as_chain:
-            chain_forward(calls, counters[0], dev)
+            chain_forward(calls, counters[0])
         ctx.counters = counters[1] if as_chain else None
         ctx.csr, ctx.relu, ctx.head = csr, relu, w_head is not None
         ctx.head_shape = None if w_head is None else tuple(w_head.shape)
@@ -431,7 +413,7 @@ class _HiddenChain(torch.autograd.Function):
         # the existing operator
         if calls is not None:
             g_s1 = torch.empty(b, nv, c, **f32)
-            chain_backward(calls, counters, dev, ds_first=g_s1)
+            chain_backward(calls, counters, ds_first=g_s1)
         else:
             g_s1, _ = _layers.aggregate_backward(dzs[0], csr, 64, _layers._ACT_NONE, None, None, False)
         rows = b * nv
@@ -446,12 +428,8 @@ class _HiddenChain(torch.autograd.Function):
             g_head = torch.empty(c * 3, **f32)
             jobs.append((dw_head, c * 3, g_head))
         n = len(jobs)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.status(
-                "geom_colsum_batch_f32",
-                n, (ctypes.c_void_p * n)(*[j[0].data_ptr() for j in jobs]), (ctypes.c_int * n)(*([nv] * n)),
-                (ctypes.c_int * n)(*[j[1] for j in jobs]), (ctypes.c_void_p * n)(*[j[2].data_ptr() for j in jobs])),
-                "geom_colsum_batch_f32")
+        _lib.call("geom_colsum_batch_f32", n, [j[0] for j in jobs], (ctypes.c_int * n)(*([nv] * n)),
+                  (ctypes.c_int * n)(*[j[1] for j in jobs]), [j[2] for j in jobs])
         grads = [g_bias[i] for i in range(L)] + [g_w[i].view(1, c, c) for i in range(L - 1)] \
             + [g_bnw[i] for i in range(L)] + [g_bnb[i] for i in range(L)]
         g_wh = None
@@ -479,11 +457,9 @@ def infer_layer_forward(s_in, bias, csr, bn_w, bn_b, run_mean, run_var, eps, rel
     b, nv, c = s_in.shape
     tail = _tail_tables(csr)
     res, res_ld = rows_operand(res, (b, nv, c), OFFSET_LIMIT)
-    a = _lib.DeformInfer(b, nv, c, 64, csr.ell_w, _p(s_in), _p(bias), _p(csr.ell_col), _p(csr.ell_val), _p(tail[0]), _p(tail[1]),
-                         _p(bn_w), _p(bn_b), _p(run_mean), _p(run_var), float(eps), int(relu), _p(res), res_ld, float(scale),
-                         _p(x_out), _p(w_next), _p(s_out), _p(w_head), _p(s_head))
-    with torch.cuda.device(s_in.device):
-        _lib.call("geom_deform_infer_fwd_f32", ctypes.addressof(a))
+    a = _lib.args(_lib.DeformInfer, b, nv, c, 64, csr.ell_w, s_in, bias, csr.ell_col, csr.ell_val, tail[0], tail[1], bn_w, bn_b,
+                  run_mean, run_var, float(eps), int(relu), res, res_ld, float(scale), x_out, w_next, s_out, w_head, s_head)
+    _lib.call("geom_deform_infer_fwd_f32", a)
 
 
 def inference_chain(block, s1, lead, csr, head=None):

@@ -79,8 +79,7 @@ def wide_dx_planes(w):
         raise ValueError("wide_dx_planes: a contiguous 2-D float32 tensor on a HIP device")
     cin, c = w.shape
     planes = torch.empty(3 * int(_lib.lib().geom_dense_dx_split_cinpad(cin)) * c, dtype=torch.int16, device=w.device)
-    with torch.cuda.device(w.device):
-        _lib.call("geom_dense_dx_split_planes_f32", cin, c, w.data_ptr(), planes.data_ptr())
+    _lib.call("geom_dense_dx_split_planes_f32", cin, c, w, planes)
     return planes
 
 
@@ -109,8 +108,7 @@ def backward_input_split(g, w, out=None):
     out = torch.empty(rows, cin, dtype=torch.float32, device=g.device) if out is None else out
     if not (_row_major(out) and out.dtype == torch.float32 and out.device == g.device and tuple(out.shape) == (rows, cin)):
         raise ValueError("backward_input_split: out must be a float32 [%d, %d] tensor with contiguous rows on g's device" % (rows, cin))
-    with torch.cuda.device(g.device):
-        _lib.call("geom_dense_dx_split_f32", rows, cin, c, g.data_ptr(), planes.data_ptr(), out.data_ptr(), out.stride(0) if rows > 1 else cin)
+    _lib.call("geom_dense_dx_split_f32", rows, cin, c, g, planes, out, out.stride(0) if rows > 1 else cin)
     return out
 
 
@@ -119,8 +117,7 @@ def forward(x, w, out=None):
     rows, cin = x.shape
     c = w.shape[1]
     out = torch.empty(rows, c, dtype=torch.float32, device=x.device) if out is None else out
-    with torch.cuda.device(x.device):
-        _lib.call("geom_dense_fwd_f32", rows, cin, c, x.data_ptr(), w.data_ptr(), 0, None, out.data_ptr(), None, None)
+    _lib.call("geom_dense_fwd_f32", rows, cin, c, x, w, 0, None, out, None, None)
     return out
 
 
@@ -129,9 +126,7 @@ def forward_split(x, w, bias, ksplit, out, sup, mask):
     sign bits of the finished columns into mask [rows, c/16] (uint16 as int16)."""
     rows, cin = x.shape
     c = w.shape[1]
-    with torch.cuda.device(x.device):
-        _lib.call("geom_dense_fwd_f32", rows, cin, c, x.data_ptr(), w.data_ptr(), ksplit, _lib.ptr(bias), out.data_ptr(),
-                  sup.data_ptr(), _lib.ptr(mask))
+    _lib.call("geom_dense_fwd_f32", rows, cin, c, x, w, ksplit, bias, out, sup, mask)
 
 
 def backward_input(g, w, out=None):
@@ -139,8 +134,7 @@ def backward_input(g, w, out=None):
     rows, c = g.shape
     cin = w.shape[0]
     out = torch.empty(rows, cin, dtype=torch.float32, device=g.device) if out is None else out
-    with torch.cuda.device(g.device):
-        _lib.call("geom_dense_bwd_input_f32", rows, cin, c, g.data_ptr(), w.data_ptr(), out.data_ptr())
+    _lib.call("geom_dense_bwd_input_f32", rows, cin, c, g, w, out)
     return out
 
 
@@ -159,12 +153,11 @@ def backward_weight_partials(x, g, workspace, want_colsum=False):
     rows, cin = x.shape
     c = g.shape[1]
     probe = launch_probe
-    with torch.cuda.device(x.device):
+    with torch.cuda.device(x.device):      # (the probe's events go to the current stream)
         if probe is not None:
             start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             start.record()
-        _lib.call("geom_dense_bwd_weight_f32", rows, cin, c, x.data_ptr(), g.data_ptr(), workspace.data_ptr(),
-                  1 if want_colsum else 0)
+        _lib.call("geom_dense_bwd_weight_f32", rows, cin, c, x, g, workspace, 1 if want_colsum else 0)
         if probe is not None:
             end.record()
             probe.append((rows, cin, c, start, end))
@@ -174,18 +167,14 @@ def backward_pair(x, g, w, grad_x, workspace, want_colsum=False):
     """grad_x = g @ w.T and the partial tiles of x.T @ g (+ column sums of g) -- ONE launch where the shape allows."""
     rows, cin = x.shape
     c = g.shape[1]
-    with torch.cuda.device(x.device):
-        _lib.call("geom_dense_bwd_f32", rows, cin, c, x.data_ptr(), g.data_ptr(), w.data_ptr(), grad_x.data_ptr(),
-                  workspace.data_ptr(), 1 if want_colsum else 0)
+    _lib.call("geom_dense_bwd_f32", rows, cin, c, x, g, w, grad_x, workspace, 1 if want_colsum else 0)
 
 
 def backward_narrow(x, g4, w, grad_x, workspace):
     """backward_pair for a gradient that is zero beyond column 2, given as its leading columns g4 [rows, 4] (column 3 zero):
     grad_x [rows, 192] (None: not wanted) and the partial tiles of x.T @ [g4 | 0], bit for bit backward_pair's."""
     rows, cin = x.shape
-    with torch.cuda.device(x.device):
-        _lib.call("geom_dense_bwd_narrow_f32", rows, cin, w.shape[1], x.data_ptr(), g4.data_ptr(), w.data_ptr(), _lib.ptr(grad_x),
-                  workspace.data_ptr())
+    _lib.call("geom_dense_bwd_narrow_f32", rows, cin, w.shape[1], x, g4, w, grad_x, workspace)
 
 
 def reduce(jobs, stream=None):
@@ -198,11 +187,9 @@ def reduce(jobs, stream=None):
             reduce(jobs[i:i + _lib.DENSE_MAX_LAYERS], stream)
         return
     ints = lambda k: (ctypes.c_int * n)(*[j[k] for j in jobs])
-    ptrs = lambda k: (ctypes.c_void_p * n)(*[None if j[k] is None else j[k].data_ptr() for j in jobs])
-    dev = jobs[0][3].device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.status("geom_dense_reduce_f32", n, ints(0), ints(1), ints(2), ptrs(3), ptrs(4), ptrs(5), stream=stream),
-                   "geom_dense_reduce_f32")
+    tensors = lambda k: [j[k] for j in jobs]
+    _lib.check(_lib.status("geom_dense_reduce_f32", n, ints(0), ints(1), ints(2), tensors(3), tensors(4), tensors(5), stream=stream),
+               "geom_dense_reduce_f32")
 
 
 def backward_weight(x, g, want_bias=False):
@@ -251,9 +238,8 @@ def gemm(a, b, trans_a=False, trans_b=False, out=None, workspace=None):
     need = int(_lib.lib().geom_gemm_workspace_floats(m, n, k))
     if need and (workspace is None or workspace.numel() < need):
         workspace = torch.empty(need, dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.call("geom_gemm_f32", m, n, k, a.data_ptr(), a.stride(0), 1 if trans_a else 0, b.data_ptr(), b.stride(0),
-                  0 if trans_b else 1, out.data_ptr(), out.stride(0), _lib.ptr(workspace) if need else None, need)
+    _lib.call("geom_gemm_f32", m, n, k, a, a.stride(0), 1 if trans_a else 0, b, b.stride(0), 0 if trans_b else 1, out,
+              out.stride(0), workspace if need else None, need)
     return out
 
 
@@ -265,8 +251,7 @@ def split_bf16_planes(w):
     k, n = w.shape
     kpad = int(_lib.lib().geom_split_bf16_kpad(k))
     planes = torch.empty(3, n, kpad, dtype=torch.int16, device=w.device)
-    with torch.cuda.device(w.device):
-        _lib.call("geom_split_bf16_planes_f32", k, n, w.data_ptr(), planes.data_ptr())
+    _lib.call("geom_split_bf16_planes_f32", k, n, w, planes)
     return planes
 
 
@@ -279,6 +264,5 @@ def gemm_split_bf16(a, planes, terms=6, out=None):
     if planes.shape[2] != int(_lib.lib().geom_split_bf16_kpad(k)):
         raise ValueError("gemm_split_bf16: the planes belong to another k")
     out = torch.empty(m, n, dtype=torch.float32, device=a.device) if out is None else out
-    with torch.cuda.device(a.device):
-        _lib.call("geom_gemm_split_bf16_f32", m, k, n, a.data_ptr(), planes.data_ptr(), out.data_ptr(), int(terms))
+    _lib.call("geom_gemm_split_bf16_f32", m, k, n, a, planes, out, int(terms))
     return out

@@ -41,9 +41,8 @@ def layer_forward(s, csr, k, bias, act, w, b, nv, x_out=None):
     """T(s) . w for s [b * nv, c] and w [c, n] (see include/geom_hip.h); x_out: receives T(s)."""
     c, n = w.shape
     out = torch.empty(b * nv, n, dtype=torch.float32, device=s.device)
-    with torch.cuda.device(s.device):
-        _lib.call("geom_encoder_layer_fwd_f32", b, nv, c, k, n, _lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(csr.val),
-                  s.data_ptr(), c, _lib.ptr(bias), act, w.data_ptr(), n, out.data_ptr(), n, _lib.ptr(x_out), c)
+    _lib.call("geom_encoder_layer_fwd_f32", b, nv, c, k, n, csr.rowptr, csr.col, csr.val, s, c, bias, act, w, n, out, n, x_out,
+              c)
     return out
 
 
@@ -51,9 +50,8 @@ def layer_backward(g, x_saved, csr, k, act, w, b, nv, t_out=None):
     """T(g, x_saved) . w^T for g [b * nv, c] and w [n, c] (see include/geom_hip.h); t_out: receives T."""
     n, c = w.shape
     out = torch.empty(b * nv, n, dtype=torch.float32, device=g.device)
-    with torch.cuda.device(g.device):
-        _lib.call("geom_encoder_layer_bwd_f32", b, nv, c, k, n, _lib.ptr(csr.rowptr_t), _lib.ptr(csr.col_t), _lib.ptr(csr.val_t),
-                  g.data_ptr(), c, _lib.ptr(x_saved), c, act, w.data_ptr(), c, out.data_ptr(), n, _lib.ptr(t_out), c)
+    _lib.call("geom_encoder_layer_bwd_f32", b, nv, c, k, n, csr.rowptr_t, csr.col_t, csr.val_t, g, c, x_saved, c, act, w, c,
+              out, n, t_out, c)
     return out
 
 
@@ -133,9 +131,7 @@ class _LatentL1(torch.autograd.Function):
             raise RuntimeError("latent_loss: latent_pred %s, train_latent %s and on_latent %s do not match"
                                % (tuple(p.shape), tuple(t.shape), tuple(o.shape)))
         loss = torch.empty(1, dtype=torch.float32, device=p.device)
-        with torch.cuda.device(p.device):
-            _lib.call("geom_latent_l1_fwd_f32", p.shape[0], p.shape[1], p.data_ptr(), t.data_ptr(), o.data_ptr(), float(weight),
-                      loss.data_ptr())
+        _lib.call("geom_latent_l1_fwd_f32", p.shape[0], p.shape[1], p, t, o, float(weight), loss)
         ctx.save_for_backward(p, t, o)
         ctx.weight = float(weight)
         return loss.view(())
@@ -145,9 +141,7 @@ class _LatentL1(torch.autograd.Function):
         p, t, o = ctx.saved_tensors
         go = grad_loss.contiguous().view(1)
         grad = torch.empty_like(p)
-        with torch.cuda.device(p.device):
-            _lib.call("geom_latent_l1_bwd_f32", p.shape[0], p.shape[1], p.data_ptr(), t.data_ptr(), o.data_ptr(), ctx.weight,
-                      go.data_ptr(), grad.data_ptr())
+        _lib.call("geom_latent_l1_bwd_f32", p.shape[0], p.shape[1], p, t, o, ctx.weight, go, grad)
         return grad, None, None, None
 
 

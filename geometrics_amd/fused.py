@@ -50,10 +50,8 @@ def layer_forward(s_prev, bias_prev, csr, k, act, w, x_out=None, mask=None, s_ou
     n_out = w.shape[1]
     x_out = torch.empty_like(s_prev) if x_out is None else x_out
     s_out = torch.empty(b, nv, n_out, dtype=torch.float32, device=s_prev.device) if s_out is None else s_out
-    with torch.cuda.device(s_prev.device):
-        _lib.call("geom_zn_layer_fwd_f32", b, nv, c, k, csr.ell_w, csr.ell_col.data_ptr(), csr.ell_val.data_ptr(),
-                  s_prev.data_ptr(), _lib.ptr(bias_prev), act, w.data_ptr(), n_out, x_out.data_ptr(), _lib.ptr(mask),
-                  s_out.data_ptr(), _lib.ptr(wt_out))
+    _lib.call("geom_zn_layer_fwd_f32", b, nv, c, k, csr.ell_w, csr.ell_col, csr.ell_val, s_prev, bias_prev, act, w, n_out,
+              x_out, mask, s_out, wt_out)
     return x_out, s_out
 
 
@@ -66,8 +64,6 @@ def layer_backward(grad_out, out, mask, csr, k, act, wt, g_out=None, grad_in=Non
     dev = wt.device
     g_out = torch.empty(b, nv, c, dtype=torch.float32, device=dev) if g_out is None else g_out
     grad_in = torch.empty(b, nv, n_in, dtype=torch.float32, device=dev) if grad_in is None else grad_in
-    with torch.cuda.device(dev):
-        _lib.call("geom_zn_layer_bwd_f32", b, nv, c, k, csr.ell_w, csr.ell_col_t.data_ptr(), csr.ell_val_t.data_ptr(),
-                  _lib.ptr(grad_out), _lib.ptr(out), _lib.ptr(mask), act, _lib.ptr(grad_pos), float(head_scale), wt.data_ptr(),
-                  n_in, g_out.data_ptr(), grad_in.data_ptr(), _lib.ptr(colsum_partial))
+    _lib.call("geom_zn_layer_bwd_f32", b, nv, c, k, csr.ell_w, csr.ell_col_t, csr.ell_val_t, grad_out, out, mask, act, grad_pos,
+              float(head_scale), wt, n_in, g_out, grad_in, colsum_partial)
     return g_out, grad_in

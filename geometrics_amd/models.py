@@ -42,11 +42,8 @@ class _VertexBN(torch.autograd.Function):
         out = _layers._new_like(xc, "normalised", _layers.current_slabs())   # a slot of the pass's stacked buffers when batching is on
         mean = torch.empty(nv, dtype=torch.float32, device=dev)
         invstd = torch.empty(nv, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("geom_vertex_bn_fwd_f32", b, nv, c, xc.data_ptr(), _lib.ptr(weight), _lib.ptr(bias),
-                      _lib.ptr(running_mean), _lib.ptr(running_var), int(training), float(momentum), float(eps),
-                      int(relu), _lib.ptr(res), res_ld or c, float(scale), out.data_ptr(), mean.data_ptr(),
-                      invstd.data_ptr())
+        _lib.call("geom_vertex_bn_fwd_f32", b, nv, c, xc, weight, bias, running_mean, running_var, int(training),
+                  float(momentum), float(eps), int(relu), res, res_ld or c, float(scale), out, mean, invstd)
         if training:
             ctx.save_for_backward(xc, weight, bias, mean, invstd)
         else:
@@ -69,10 +66,8 @@ class _VertexBN(torch.autograd.Function):
         grad_res = torch.empty_like(x) if ctx.has_res else None
         gw = torch.empty(nv, dtype=torch.float32, device=x.device) if weight is not None else None
         gb = torch.empty(nv, dtype=torch.float32, device=x.device) if bias is not None else None
-        with torch.cuda.device(x.device):
-            _lib.call("geom_vertex_bn_bwd_f32", b, nv, c, x.data_ptr(), g.data_ptr(), _lib.ptr(weight), _lib.ptr(bias),
-                      mean.data_ptr(), invstd.data_ptr(), int(ctx.relu), int(ctx.has_res), float(ctx.scale),
-                      grad_x.data_ptr(), _lib.ptr(grad_res), _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(g2))
+        _lib.call("geom_vertex_bn_bwd_f32", b, nv, c, x, g, weight, bias, mean, invstd, int(ctx.relu), int(ctx.has_res),
+                  float(ctx.scale), grad_x, grad_res, gw, gb, g2)
         return grad_x, gw, gb, None, None, grad_res, None, None, None, None, None, None
 
 

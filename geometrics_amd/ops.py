@@ -24,8 +24,7 @@ def face_areas(verts, faces):
     faces = _lib.require(faces, "faces", torch.int64, 2, 3)
     b, nv, _ = verts.shape
     out = torch.empty(b, faces.shape[0], dtype=torch.float32, device=verts.device)
-    with torch.cuda.device(verts.device):
-        _lib.call("geom_face_areas_f32", b, nv, verts.data_ptr(), faces.shape[0], faces.data_ptr(), out.data_ptr())
+    _lib.call("geom_face_areas_f32", b, nv, verts, faces.shape[0], faces, out)
     return out
 
 
@@ -33,8 +32,7 @@ def device_sum(x, scale=1.0):
     """0-dim tensor scale*sum(x) with a fixed reduction tree (bit-reproducible)."""
     x = x.contiguous()
     out = torch.empty((), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.call("geom_sum_f32", x.numel(), x.data_ptr(), float(scale), out.data_ptr())
+    _lib.call("geom_sum_f32", x.numel(), x, float(scale), out)
     return out
 
 
@@ -56,9 +54,7 @@ class SampleFaces(torch.autograd.Function):
         if choices.shape[0] != b or u.shape != choices.shape or v.shape != choices.shape:
             raise RuntimeError("choices/u/v must all be [B,num]")
         points = torch.empty(b, num, 3, dtype=torch.float32, device=verts_c.device)
-        with torch.cuda.device(verts_c.device):
-            _lib.call("geom_sample_faces_fwd_f32", b, nv, verts_c.data_ptr(), faces.shape[0], faces.data_ptr(),
-                      num, choices.data_ptr(), u.data_ptr(), v.data_ptr(), points.data_ptr())
+        _lib.call("geom_sample_faces_fwd_f32", b, nv, verts_c, faces.shape[0], faces, num, choices, u, v, points)
         ctx.save_for_backward(faces, choices, u, v)
         ctx.nv = nv
         return points
@@ -69,9 +65,7 @@ class SampleFaces(torch.autograd.Function):
         grad_points = grad_points.contiguous()
         b, num, _ = grad_points.shape
         grad_verts = torch.zeros(b, ctx.nv, 3, dtype=torch.float32, device=grad_points.device)
-        with torch.cuda.device(grad_points.device):
-            _lib.call("geom_sample_faces_bwd_f32", b, ctx.nv, faces.shape[0], faces.data_ptr(), num,
-                      choices.data_ptr(), u.data_ptr(), v.data_ptr(), grad_points.data_ptr(), grad_verts.data_ptr())
+        _lib.call("geom_sample_faces_bwd_f32", b, ctx.nv, faces.shape[0], faces, num, choices, u, v, grad_points, grad_verts)
         return grad_verts, None, None, None, None
 
 
@@ -95,9 +89,7 @@ class GatherSqDistSum(torch.autograd.Function):
         g_src = torch.empty_like(src_c) if need_src else None
         g_dst = torch.zeros_like(dst_c) if need_dst else None
         grad = grad.contiguous()
-        with torch.cuda.device(src_c.device):
-            _lib.call("geom_chamfer_grad_f32", b, n, src_c.data_ptr(), m, dst_c.data_ptr(), idx.data_ptr(),
-                      grad.data_ptr(), 1.0, _lib.ptr(g_src), 0, _lib.ptr(g_dst))
+        _lib.call("geom_chamfer_grad_f32", b, n, src_c, m, dst_c, idx, grad, 1.0, g_src, 0, g_dst)
         return g_src, g_dst, None, None
 
 
@@ -115,10 +107,8 @@ class PointToTriangleSum(torch.autograd.Function):
         sq = torch.empty(b, n, dtype=torch.float32, device=dev)
         closest = torch.empty(b, n, 3, dtype=torch.float32, device=dev)
         weights = torch.empty(b, n, 3, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("geom_p2tri_loss_fwd_f32", b, n, xyz_c.data_ptr(), nv, verts_c.data_ptr(), faces.shape[0],
-                      faces.data_ptr(), option.data_ptr(), index.data_ptr(), sq.data_ptr(), closest.data_ptr(),
-                      weights.data_ptr())
+        _lib.call("geom_p2tri_loss_fwd_f32", b, n, xyz_c, nv, verts_c, faces.shape[0], faces, option, index, sq, closest,
+                  weights)
         ctx.save_for_backward(xyz_c, faces, index, closest, weights)
         ctx.nv = nv
         return device_sum(sq)
@@ -129,10 +119,8 @@ class PointToTriangleSum(torch.autograd.Function):
         b, n, _ = xyz.shape
         grad_verts = torch.zeros(b, ctx.nv, 3, dtype=torch.float32, device=xyz.device)
         grad = grad.contiguous()
-        with torch.cuda.device(xyz.device):
-            _lib.call("geom_p2tri_loss_bwd_f32", b, n, xyz.data_ptr(), ctx.nv, faces.shape[0], faces.data_ptr(),
-                      index.data_ptr(), closest.data_ptr(), weights.data_ptr(), grad.data_ptr(), 1.0,
-                      grad_verts.data_ptr())
+        _lib.call("geom_p2tri_loss_bwd_f32", b, n, xyz, ctx.nv, faces.shape[0], faces, index, closest, weights, grad, 1.0,
+                  grad_verts)
         return None, grad_verts, None, None, None
 
 
@@ -180,8 +168,7 @@ class GtIndex:
         # the index HOLDS the cloud's memory: while it lives the allocator cannot hand that address to another cloud (a
         # recycled address at version 0 would pass the check below and be scanned through the OLD cloud's index)
         self._cloud = gt
-        with torch.cuda.device(gt.device):
-            _lib.call("geom_nn_cull_index_f32", b, n, gt.data_ptr(), order.data_ptr(), self.index.data_ptr())
+        _lib.call("geom_nn_cull_index_f32", b, n, gt, order, self.index)
 
     def check(self, gt):
         if tuple(gt.shape[:2]) != self.shape or gt.device != self.device or (gt.data_ptr(), gt._version) != self.source:
@@ -303,7 +290,7 @@ class SurfaceLoss(torch.autograd.Function):
         cull = None
         if gt_index is not None and prep is not None and prep.sample_index is not None and not two_sided:
             gt_index.check(gt_c)    # the culled Chamfer tiles: both clouds' indices are there
-            cull = _lib.SurfaceCull(gt_index.order.data_ptr(), gt_index.index.data_ptr(), prep.sample_index.data_ptr(), None)
+            cull = _lib.args(_lib.SurfaceCull, gt_index.order, gt_index.index, prep.sample_index, None)
         if not two_sided:
             ws_bytes = L.geom_tri_distance_workspace_bytes(b, n_gt, nf)
             ws_ready = tri_ws is not None and have_points      # written by the draw launch (ops.draw_samples(prepare_scan_for=...))
@@ -313,69 +300,60 @@ class SurfaceLoss(torch.autograd.Function):
             tri_order = face_order(verts_c, faces)      # cached k-d leaf order of the faces: two-level scan
             tri_d, option, index = torch.empty(b, n_gt, **f32), torch.empty(b, n_gt, **i32), torch.empty(b, n_gt, **i32)
             sq, closest, weights = torch.empty(b, n_gt, **f32), torch.empty(b, n_gt, 3, **f32), torch.empty(b, n_gt, 3, **f32)
-        with torch.cuda.device(dev):
-            if not have_points:
-                _lib.call("geom_sample_faces_fwd_f32", b, nv, verts_c.data_ptr(), nf, faces.data_ptr(), num,
-                          choices.data_ptr(), u.data_ptr(), v.data_ptr(), points.data_ptr())
-            # Both arg-min scans -- Chamfer NN in both directions and (one-sided loss) the point-to-triangle scan with
-            # the closest point / weights / squared distance of the winner -- in ONE call: one heterogeneous launch
-            # behind the triangle-record prep.  (Round 1 ran them back to back: two streams inside a captured graph cost
-            # 5-10 us per fork/join edge.)  When a gradient is wanted the scans also write every point's gradient record
-            # into the backward scratch.
-            want = bool(ctx.needs_input_grad[0])
-            order = torch.empty(L.geom_surface_order_words(b, nf, num, n_gt), dtype=torch.int32, device=dev)
-            coef_s, coef_o = scale / (b * num), scale / (b * n_gt)
-            wrote = ctypes.c_int(0)
-            flags = _chamfer.default_flags()
-            if not two_sided and ws_ready:
-                flags |= _lib.FLAG_TRI_WS_READY
-            if two_sided:
-                tri_args = (nv, None, nf, None, None, None, None, None, None, None, None)    # nf still sizes the scratch layout
-                ws_ptr, ws_len = None, 0
-            else:
-                tri_args = (nv, verts_c.data_ptr(), nf, faces.data_ptr(), _lib.ptr(tri_order), tri_d.data_ptr(),
-                            option.data_ptr(), index.data_ptr(), sq.data_ptr(), closest.data_ptr(), weights.data_ptr())
-                ws_ptr, ws_len = ws.data_ptr(), ws_bytes
-            # one-sided loss: the finalize pass (below) rides in the scan launch as extra (role) workgroups where the launch is
-            # the fused one and a mesh's faces + points fit its LDS (tail.finalized says so): each mesh is ordered as soon
-            # as ITS triangle tiles are through instead of in a launch of its own behind the slowest tile
-            tail = None
-            if not two_sided and scan_finalize_tail and mesh_weight is None:    # (the in-launch roles know no per-mesh factors)
-                tail = _lib.SurfaceTail(choices.data_ptr(), scale / sq_pred.numel(), scale / sq.numel(), int(want), out.data_ptr(), 0)
-            _lib.check(_lib.status(
-                "geom_surface_scan_f32",
-                b, n_gt, gt_c.data_ptr(), num, points.data_ptr(), sq_gt.data_ptr(), idx_p.data_ptr(), sq_pred.data_ptr(),
-                idx_g.data_ptr(), *tri_args, u.data_ptr(), v.data_ptr(), coef_s, coef_o, order.data_ptr() if want else None,
-                flags, ws_ptr, ws_len, ctypes.byref(wrote), ctypes.byref(cull) if cull is not None else None,
-                ctypes.byref(tail) if tail is not None else None), "geom_surface_scan_f32")
-            # finalize: the loss reduction AND, when a gradient is wanted, the backward's preparation (points counting-sorted
-            # by face in ascending id order; the records too when the scans could not write them) in one launch; the
-            # backward is then a single gather launch
-            other_sq = sq_gt if two_sided else sq
-            args = (b, nf, num, choices.data_ptr(), u.data_ptr(), v.data_ptr(), points.data_ptr(), n_gt, gt_c.data_ptr(),
-                    idx_g.data_ptr(), idx_p.data_ptr() if two_sided else None, None if two_sided else index.data_ptr(),
-                    None if two_sided else closest.data_ptr(), None if two_sided else weights.data_ptr(),
-                    sq_pred.data_ptr(), other_sq.data_ptr(), scale / sq_pred.numel(), scale / other_sq.numel(), coef_s, coef_o)
-            if tail is None or not tail.finalized:
-                wptr = _lib.ptr(mesh_weight)
-                code = _lib.status("geom_surface_finalize_w_f32", *args, int(want), wrote.value, order.data_ptr(), out.data_ptr(), wptr)
-                if code == _lib.EUNSUPPORTED:       # too many faces + points for the in-LDS ordering: loss only, scatter backward
-                    if mesh_weight is not None and want:
-                        raise RuntimeError("per-mesh weights need the ordered backward (faces + points of a mesh within ~38 000)")
-                    want = False
-                    code = _lib.status("geom_surface_finalize_w_f32", *args, 0, 0, order.data_ptr(), out.data_ptr(), wptr)
-                _lib.check(code, "geom_surface_finalize_w_f32")
-            ctx.order = order if want else None
-            if tail is not None and tail.finalized and want:
+        if not have_points:
+            _lib.call("geom_sample_faces_fwd_f32", b, nv, verts_c, nf, faces, num, choices, u, v, points)
+        # Both arg-min scans -- Chamfer NN in both directions and (one-sided loss) the point-to-triangle scan with
+        # the closest point / weights / squared distance of the winner -- in ONE call: one heterogeneous launch
+        # behind the triangle-record prep.  (Round 1 ran them back to back: two streams inside a captured graph cost
+        # 5-10 us per fork/join edge.)  When a gradient is wanted the scans also write every point's gradient record
+        # into the backward scratch.
+        want = bool(ctx.needs_input_grad[0])
+        order = torch.empty(L.geom_surface_order_words(b, nf, num, n_gt), dtype=torch.int32, device=dev)
+        coef_s, coef_o = scale / (b * num), scale / (b * n_gt)
+        wrote = ctypes.c_int(0)
+        flags = _chamfer.default_flags()
+        if not two_sided and ws_ready:
+            flags |= _lib.FLAG_TRI_WS_READY
+        if two_sided:
+            tri_args = (nv, None, nf, None, None, None, None, None, None, None, None)    # nf still sizes the scratch layout
+            ws, ws_bytes = None, 0
+        else:
+            tri_args = (nv, verts_c, nf, faces, tri_order, tri_d, option, index, sq, closest, weights)
+        # one-sided loss: the finalize pass (below) rides in the scan launch as extra (role) workgroups where the launch is
+        # the fused one and a mesh's faces + points fit its LDS (tail.finalized says so): each mesh is ordered as soon
+        # as ITS triangle tiles are through instead of in a launch of its own behind the slowest tile
+        tail = None
+        if not two_sided and scan_finalize_tail and mesh_weight is None:    # (the in-launch roles know no per-mesh factors)
+            tail = _lib.args(_lib.SurfaceTail, choices, scale / sq_pred.numel(), scale / sq.numel(), int(want), out, 0)
+        _lib.call("geom_surface_scan_f32", b, n_gt, gt_c, num, points, sq_gt, idx_p, sq_pred, idx_g, *tri_args, u, v, coef_s, coef_o,
+                  order if want else None, flags, ws, ws_bytes, ctypes.byref(wrote), cull, tail)
+        # finalize: the loss reduction AND, when a gradient is wanted, the backward's preparation (points counting-sorted
+        # by face in ascending id order; the records too when the scans could not write them) in one launch; the
+        # backward is then a single gather launch
+        other_sq = sq_gt if two_sided else sq
+        args = (b, nf, num, choices, u, v, points, n_gt, gt_c, idx_g, idx_p if two_sided else None, None if two_sided else index,
+                None if two_sided else closest, None if two_sided else weights, sq_pred, other_sq, scale / sq_pred.numel(),
+                scale / other_sq.numel(), coef_s, coef_o)
+        if tail is None or not tail.finalized:
+            code = _lib.status("geom_surface_finalize_w_f32", *args, int(want), wrote.value, order, out, mesh_weight)
+            if code == _lib.EUNSUPPORTED:       # too many faces + points for the in-LDS ordering: loss only, scatter backward
+                if mesh_weight is not None and want:
+                    raise RuntimeError("per-mesh weights need the ordered backward (faces + points of a mesh within ~38 000)")
+                want = False
+                code = _lib.status("geom_surface_finalize_w_f32", *args, 0, 0, order, out, mesh_weight)
+            _lib.check(code, "geom_surface_finalize_w_f32")
+        ctx.order = order if want else None
+        if tail is not None and tail.finalized and want:
+            with torch.cuda.device(dev):      # (the watch records an event and asks about capture on the current stream)
                 _watch_roles(order, b, nf, num + n_gt)
-            if scan_capture is not None:
-                scan_capture.update(idx_gt=idx_p, idx_pred=idx_g, sq_gt=sq_gt, sq_pred=sq_pred, choices=choices, u=u, v=v, points=points)
-                if not two_sided:
-                    scan_capture.update(tri_index=index, tri_option=option, tri_dist=tri_d)
-            if two_sided:
-                ctx.save_for_backward(faces, choices, u, v, points, gt_c, idx_g, idx_p)
-            else:
-                ctx.save_for_backward(faces, choices, u, v, points, gt_c, idx_g, index, closest, weights)
+        if scan_capture is not None:
+            scan_capture.update(idx_gt=idx_p, idx_pred=idx_g, sq_gt=sq_gt, sq_pred=sq_pred, choices=choices, u=u, v=v, points=points)
+            if not two_sided:
+                scan_capture.update(tri_index=index, tri_option=option, tri_dist=tri_d)
+        if two_sided:
+            ctx.save_for_backward(faces, choices, u, v, points, gt_c, idx_g, idx_p)
+        else:
+            ctx.save_for_backward(faces, choices, u, v, points, gt_c, idx_g, index, closest, weights)
         ctx.two_sided, ctx.scale, ctx.nv = two_sided, scale, nv
         ctx.mesh_weight = mesh_weight
         ctx.mark_non_differentiable(sq_gt, sq_pred)
@@ -390,29 +368,25 @@ class SurfaceLoss(torch.autograd.Function):
         n_gt, nf, nv = gt.shape[1], faces.shape[0], ctx.nv
         dev = points.device
         grad = grad.contiguous()
-        with torch.cuda.device(dev):
-            if ctx.order is not None:           # prepared by the forward's finalize launch: one gather, no atomics
-                vf_ptr, vf_item = vertex_faces(faces, nv)
-                grad_verts = torch.empty(b, nv, 3, dtype=torch.float32, device=dev)
-                _lib.call("geom_surface_gather_w_f32", b, nv, nf, vf_ptr.data_ptr(), vf_item.data_ptr(), num, n_gt, 1,
-                          ctx.order.data_ptr(), grad.data_ptr(), _lib.ptr(ctx.mesh_weight), grad_verts.data_ptr())
-            elif ctx.mesh_weight is not None:
-                raise RuntimeError("per-mesh weights need the ordered backward")
+        if ctx.order is not None:           # prepared by the forward's finalize launch: one gather, no atomics
+            vf_ptr, vf_item = vertex_faces(faces, nv)
+            grad_verts = torch.empty(b, nv, 3, dtype=torch.float32, device=dev)
+            _lib.call("geom_surface_gather_w_f32", b, nv, nf, vf_ptr, vf_item, num, n_gt, 1, ctx.order, grad,
+                      ctx.mesh_weight, grad_verts)
+        elif ctx.mesh_weight is not None:
+            raise RuntimeError("per-mesh weights need the ordered backward")
+        else:
+            # a mesh whose faces + points do not fit the ordering pass's LDS (> ~38 000 together): scatter formulation
+            # (fp32 atomics into a zeroed gradient; same values up to summation order)
+            grad_verts = torch.zeros(b, nv, 3, dtype=torch.float32, device=dev)
+            if ctx.two_sided:
+                for other_idx, via_nn, coef in ((saved[6], 0, ctx.scale / (b * num)), (saved[7], 1, ctx.scale / (b * n_gt))):
+                    _lib.call("geom_sample_chamfer_bwd_f32", b, nv, nf, faces, num, choices, u, v, points, n_gt, gt,
+                              other_idx, via_nn, grad, coef, grad_verts)
             else:
-                # a mesh whose faces + points do not fit the ordering pass's LDS (> ~38 000 together): scatter formulation
-                # (fp32 atomics into a zeroed gradient; same values up to summation order)
-                grad_verts = torch.zeros(b, nv, 3, dtype=torch.float32, device=dev)
-                if ctx.two_sided:
-                    for other_idx, via_nn, coef in ((saved[6], 0, ctx.scale / (b * num)), (saved[7], 1, ctx.scale / (b * n_gt))):
-                        _lib.call("geom_sample_chamfer_bwd_f32", b, nv, nf, faces.data_ptr(), num, choices.data_ptr(),
-                                  u.data_ptr(), v.data_ptr(), points.data_ptr(), n_gt, gt.data_ptr(), other_idx.data_ptr(),
-                                  via_nn, grad.data_ptr(), coef, grad_verts.data_ptr())
-                else:
-                    index, closest, weights = saved[7:10]
-                    _lib.call("geom_surface_loss_bwd_f32", b, nv, nf, faces.data_ptr(), num, choices.data_ptr(),
-                              u.data_ptr(), v.data_ptr(), points.data_ptr(), n_gt, gt.data_ptr(), saved[6].data_ptr(),
-                              index.data_ptr(), closest.data_ptr(), weights.data_ptr(), grad.data_ptr(),
-                              ctx.scale / (b * num), ctx.scale / (b * n_gt), grad_verts.data_ptr())
+                index, closest, weights = saved[7:10]
+                _lib.call("geom_surface_loss_bwd_f32", b, nv, nf, faces, num, choices, u, v, points, n_gt, gt, saved[6],
+                          index, closest, weights, grad, ctx.scale / (b * num), ctx.scale / (b * n_gt), grad_verts)
         return grad_verts, None, None, None, None, None, None, None, None, None, None, None, None
 
 
@@ -425,9 +399,7 @@ class Laplacian(torch.autograd.Function):
         x = _f32(positions, "positions", 3, 3)
         b, nv, _ = x.shape
         out = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.call("geom_laplacian_f32", b, nv, rowptr.data_ptr(), col.data_ptr(), inv_deg.data_ptr(),
-                      x.data_ptr(), 0, out.data_ptr())
+        _lib.call("geom_laplacian_f32", b, nv, rowptr, col, inv_deg, x, 0, out)
         ctx.save_for_backward(rowptr, col, inv_deg)
         return out
 
@@ -437,9 +409,7 @@ class Laplacian(torch.autograd.Function):
         g = grad.contiguous()
         b, nv, _ = g.shape
         out = torch.empty_like(g)
-        with torch.cuda.device(g.device):
-            _lib.call("geom_laplacian_f32", b, nv, rowptr.data_ptr(), col.data_ptr(), inv_deg.data_ptr(),
-                      g.data_ptr(), 1, out.data_ptr())
+        _lib.call("geom_laplacian_f32", b, nv, rowptr, col, inv_deg, g, 1, out)
         return out, None, None, None
 
 
@@ -453,9 +423,7 @@ class EdgeSqLenSum(torch.autograd.Function):
         faces = _lib.require(faces, "faces", torch.int64, 2, 3)
         b, nv, _ = v.shape
         per_face = torch.empty(b, faces.shape[0], dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            _lib.call("geom_edge_sqlen_fwd_f32", b, nv, v.data_ptr(), faces.shape[0], faces.data_ptr(),
-                      per_face.data_ptr())
+        _lib.call("geom_edge_sqlen_fwd_f32", b, nv, v, faces.shape[0], faces, per_face)
         ctx.save_for_backward(v, faces)
         return device_sum(per_face)
 
@@ -465,9 +433,7 @@ class EdgeSqLenSum(torch.autograd.Function):
         b, nv, _ = v.shape
         grad = grad.contiguous()
         grad_verts = torch.zeros_like(v)
-        with torch.cuda.device(v.device):
-            _lib.call("geom_edge_sqlen_bwd_f32", b, nv, v.data_ptr(), faces.shape[0], faces.data_ptr(),
-                      grad.data_ptr(), 1.0, grad_verts.data_ptr())
+        _lib.call("geom_edge_sqlen_bwd_f32", b, nv, v, faces.shape[0], faces, grad, 1.0, grad_verts)
         return grad_verts, None
 
 
@@ -503,14 +469,13 @@ class FanOut(torch.autograd.Function):
                 total = total + g
             return total, None
         out = torch.empty(first.shape, dtype=torch.float32, device=first.device)
-        ptrs = (ctypes.c_void_p * len(given))(*[g.data_ptr() for g, _ in given])
+        ptrs = [g for g, _ in given]
         width = first.shape[-1]
-        with torch.cuda.device(out.device):
-            if all(ld == width for _, ld in given):
-                _lib.call("geom_sum_tensors_f32", len(given), ptrs, out.numel(), out.data_ptr())
-            else:
-                lds = (ctypes.c_int64 * len(given))(*[ld for _, ld in given])
-                _lib.call("geom_sum_tensors_rows_f32", len(given), ptrs, lds, out.numel() // width, width, out.data_ptr())
+        if all(ld == width for _, ld in given):
+            _lib.call("geom_sum_tensors_f32", len(given), ptrs, out.numel(), out)
+        else:
+            lds = (ctypes.c_int64 * len(given))(*[ld for _, ld in given])
+            _lib.call("geom_sum_tensors_rows_f32", len(given), ptrs, lds, out.numel() // width, width, out)
         return out, None
 
 
@@ -529,9 +494,7 @@ class SumScalars(torch.autograd.Function):
             for t in ts[1:]:
                 total = total + t
             return total
-        ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        with torch.cuda.device(out.device):
-            _lib.call("geom_sum_tensors_f32", len(ts), ptrs, 1, out.data_ptr())
+        _lib.call("geom_sum_tensors_f32", len(ts), ts, 1, out)
         return out
 
     @staticmethod
@@ -560,9 +523,8 @@ class StageRegularisers(torch.autograd.Function):
         c_edge = float(w_edge) / (3.0 * b * nf) if nf else 0.0
         lapd = torch.empty_like(c)
         partial = torch.empty(int(_lib.lib().geom_stage_regularisers_blocks(b, nv, nf)), dtype=torch.float32, device=c.device)
-        with torch.cuda.device(c.device):
-            _lib.call("geom_stage_regularisers_fwd_f32", b, nv, p.data_ptr(), int(batched), c.data_ptr(), nf, faces.data_ptr(),
-                      rowptr.data_ptr(), col.data_ptr(), inv_deg.data_ptr(), c_lap, c_move, c_edge, lapd.data_ptr(), partial.data_ptr())
+        _lib.call("geom_stage_regularisers_fwd_f32", b, nv, p, int(batched), c, nf, faces, rowptr, col, inv_deg, c_lap, c_move,
+                  c_edge, lapd, partial)
         ctx.save_for_backward(p, c, faces, rowptr, col, inv_deg, lapd)
         ctx.coef, ctx.batched = (c_lap, c_move, c_edge), batched
         return device_sum(partial)
@@ -577,11 +539,8 @@ class StageRegularisers(torch.autograd.Function):
         want_prev = ctx.needs_input_grad[0]
         grad_cur = torch.empty_like(c)
         grad_prev = torch.empty_like(c) if want_prev else None
-        with torch.cuda.device(c.device):
-            _lib.call("geom_stage_regularisers_bwd_f32", b, nv, p.data_ptr(), int(ctx.batched), c.data_ptr(), faces.shape[0],
-                      faces.data_ptr(), rowptr.data_ptr(), col.data_ptr(), inv_deg.data_ptr(), _lib.ptr(vf_ptr), _lib.ptr(vf_item),
-                      c_lap, c_move, c_edge, lapd.data_ptr(), g.data_ptr(), _lib.ptr(grad_prev if ctx.batched else None),
-                      grad_cur.data_ptr())
+        _lib.call("geom_stage_regularisers_bwd_f32", b, nv, p, int(ctx.batched), c, faces.shape[0], faces, rowptr, col, inv_deg,
+                  vf_ptr, vf_item, c_lap, c_move, c_edge, lapd, g, grad_prev if ctx.batched else None, grad_cur)
         if want_prev and not ctx.batched:      # a template that asks for its gradient: the sum over the batch of -grad_cur's lap/move part
             raise RuntimeError("StageRegularisers: the gradient with respect to an unbatched [V,3] prev is not implemented")
         return grad_prev, (grad_cur if ctx.needs_input_grad[1] else None), None, None, None, None, None, None, None
@@ -709,7 +668,6 @@ class PoolFeatures(torch.autograd.Function):
             if blk.shape[0] != b or blk.shape[2] != blk.shape[3]:
                 raise RuntimeError("feature maps must be [B, C, dim, dim] with the vertex batch size")
         n = len(blks)
-        ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in blks])
         chans = (ctypes.c_int * n)(*[t.shape[1] for t in blks])
         dims = (ctypes.c_int * n)(*[t.shape[2] for t in blks])
         ctot = sum(t.shape[1] for t in blks)
@@ -736,20 +694,18 @@ class PoolFeatures(torch.autograd.Function):
         else:
             buf, out = None, torch.empty(b, nv, ctot, dtype=torch.float32, device=v.device)
         m = len(srcs)
-        with torch.cuda.device(v.device):
-            _lib.call("geom_pool_features_fwd_fronts_f32", b, nv, v.data_ptr(), cam_mat.data_ptr(), cam_pos.data_ptr(), n,
-                      ptrs, chans, dims, out.data_ptr(), headroom + ctot if headroom > 0 else 0, m,
-                      (ctypes.c_void_p * m)(*[t.data_ptr() for t, _ in srcs]), (ctypes.c_int * m)(*[t.shape[2] for t, _ in srcs]),
-                      (ctypes.c_int * m)(*[c for _, c in srcs]), _lib.ptr(buf))
+        _lib.call("geom_pool_features_fwd_fronts_f32", b, nv, v, cam_mat, cam_pos, n, blks, chans, dims, out,
+                  headroom + ctot if headroom > 0 else 0, m, [t for t, _ in srcs],
+                  (ctypes.c_int * m)(*[t.shape[2] for t, _ in srcs]), (ctypes.c_int * m)(*[c for _, c in srcs]), buf)
         ctx.save_for_backward(v, cam_mat, cam_pos, *blks)
-        ctx.meta = (ptrs, chans, dims, n)
+        ctx.meta = (chans, dims, n)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         v, cam_mat, cam_pos = ctx.saved_tensors[:3]
         blks = ctx.saved_tensors[3:]
-        ptrs, chans, dims, n = ctx.meta
+        chans, dims, n = ctx.meta
         b, nv, _ = v.shape
         ctot = grad_out.shape[2]
         # the gradient in place when it is a column slice of a wider row-major buffer (the block's input gradient), else contiguous
@@ -760,7 +716,6 @@ class PoolFeatures(torch.autograd.Function):
             g, g_ld = grad_out.contiguous(), ctot
         need_blocks = [ctx.needs_input_grad[4 + i] for i in range(n)]
         gblks = [torch.empty_like(t) if need else None for t, need in zip(blks, need_blocks)]
-        gptrs = (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in gblks])
         gverts = torch.empty_like(v) if ctx.needs_input_grad[0] else None
         ws, ws_bytes = None, 0
         if any(need_blocks) or gverts is not None:
@@ -768,9 +723,8 @@ class PoolFeatures(torch.autograd.Function):
             # of the vertex gradient
             ws_bytes = _lib.lib().geom_pool_features_bwd_workspace_bytes(b, nv, n, dims)
             ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            _lib.call("geom_pool_features_bwd_ld_f32", b, nv, v.data_ptr(), cam_mat.data_ptr(), cam_pos.data_ptr(), n,
-                      ptrs, chans, dims, g.data_ptr(), g_ld if g_ld != ctot else 0, gptrs, _lib.ptr(gverts), _lib.ptr(ws), ws_bytes)
+        _lib.call("geom_pool_features_bwd_ld_f32", b, nv, v, cam_mat, cam_pos, n, blks, chans, dims, g,
+                  g_ld if g_ld != ctot else 0, gblks, gverts, ws, ws_bytes)
         return (gverts, None, None, None) + tuple(gblks)
 
 
@@ -788,9 +742,7 @@ class SegmentMax(torch.autograd.Function):
         arg = torch.empty(nseg, c, dtype=torch.int32, device=x_.device)
         ws_bytes = _lib.lib().geom_segment_max_workspace_bytes(nseg, c, int(max_len))
         ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=x_.device)
-        with torch.cuda.device(x_.device):
-            _lib.call("geom_segment_max_fwd_f32", nseg, offsets.data_ptr(), int(max_len), c, x_.data_ptr(),
-                      out.data_ptr(), arg.data_ptr(), ws.data_ptr(), ws_bytes)
+        _lib.call("geom_segment_max_fwd_f32", nseg, offsets, int(max_len), c, x_, out, arg, ws, ws_bytes)
         ctx.save_for_backward(offsets, arg)
         ctx.rows = x_.shape[0]
         ctx.mark_non_differentiable(arg)
@@ -802,9 +754,7 @@ class SegmentMax(torch.autograd.Function):
         g = grad_out.contiguous()
         nseg, c = arg.shape
         grad_x = torch.empty(ctx.rows, c, dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            _lib.call("geom_segment_max_bwd_f32", nseg, offsets.data_ptr(), ctx.rows, c, g.data_ptr(), arg.data_ptr(),
-                      grad_x.data_ptr())
+        _lib.call("geom_segment_max_bwd_f32", nseg, offsets, ctx.rows, c, g, arg, grad_x)
         return grad_x, None, None
 
 
@@ -828,8 +778,15 @@ def manual_seed(seed, device=None, mesh_offset=0):
 def set_rng_state(state, device=None):
     """Make `state` (a tensor manual_seed returned) the sampler stream of `device`: lets one process alternate
     between several independent streams (e.g. two shards stepped in turn)."""
+    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.int64 and tuple(state.shape) == (4,)):
+        raise RuntimeError("set_rng_state: the state is a 4-element int64 tensor on a HIP device, as manual_seed returns it (got %s)"
+                           % ("%s %s on %s" % (state.dtype, tuple(state.shape), state.device) if isinstance(state, torch.Tensor)
+                              else type(state).__name__))
     dev = state.device if device is None else torch.device(device)
-    _rng_states[dev.index if dev.index is not None else torch.cuda.current_device()] = state
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    if state.device.index != key:
+        raise RuntimeError("set_rng_state: the state is on %s, the stream it is set for on cuda:%d" % (state.device, key))
+    _rng_states[key] = state
 
 
 def _rng_state(dev):
@@ -865,35 +822,30 @@ def draw_samples(verts, faces, num, generator=None, with_points=False, prepare_s
     u = torch.empty(b, num, dtype=torch.float32, device=dev)
     v = torch.empty(b, num, dtype=torch.float32, device=dev)
     uniforms = points = None
-    with torch.cuda.device(dev):
-        if generator is None:
-            if with_points:
-                points = torch.empty(b, num, 3, dtype=torch.float32, device=dev)
-            if with_points and prepare_scan_for:
-                n_gt, nf = int(prepare_scan_for), faces.shape[0]
-                ws_bytes = _lib.lib().geom_tri_distance_workspace_bytes(b, n_gt, nf)
-                tri_ws = torch.empty(max(ws_bytes, 16) // 4, dtype=torch.float32, device=dev)
-                prepared = ctypes.c_int(0)
-                cull = s_index = None
-                if gt_index is not None:
-                    s_index = torch.empty(max(int(_lib.lib().geom_nn_cull_index_floats(b, num)), 4), dtype=torch.float32, device=dev)
-                    cull = _lib.SurfaceCull(None, None, s_index.data_ptr(), _lib.ptr(faces_in_order(verts_c, faces)))
-                code = _lib.status(
-                    "geom_surface_prepare_f32",
-                    b, nv, verts_c.data_ptr(), nf, faces.data_ptr(), num, _rng_state(dev).data_ptr(), choices.data_ptr(),
-                    u.data_ptr(), v.data_ptr(), points.data_ptr(), n_gt, _lib.ptr(face_order(verts_c, faces)), 0,
-                    tri_ws.data_ptr(), ws_bytes, ctypes.byref(prepared), ctypes.byref(cull) if cull is not None else None)
-                if code == 0:
-                    if prepared.value & 2:
-                        return choices, u, v, points, ScanPrep(tri_ws, s_index)
-                    return choices, u, v, points, (tri_ws if prepared.value else None)
-            else:
-                code = _lib.status("geom_draw_samples_rng_f32", b, nv, verts_c.data_ptr(), faces.shape[0], faces.data_ptr(), num,
-                                   _rng_state(dev).data_ptr(), choices.data_ptr(), u.data_ptr(), v.data_ptr(), _lib.ptr(points))
+    if generator is None:
+        if with_points:
+            points = torch.empty(b, num, 3, dtype=torch.float32, device=dev)
+        if with_points and prepare_scan_for:
+            n_gt, nf = int(prepare_scan_for), faces.shape[0]
+            ws_bytes = _lib.lib().geom_tri_distance_workspace_bytes(b, n_gt, nf)
+            tri_ws = torch.empty(max(ws_bytes, 16) // 4, dtype=torch.float32, device=dev)
+            prepared = ctypes.c_int(0)
+            cull = s_index = None
+            if gt_index is not None:
+                s_index = torch.empty(max(int(_lib.lib().geom_nn_cull_index_floats(b, num)), 4), dtype=torch.float32, device=dev)
+                cull = _lib.args(_lib.SurfaceCull, None, None, s_index, faces_in_order(verts_c, faces))
+            code = _lib.status("geom_surface_prepare_f32", b, nv, verts_c, nf, faces, num, _rng_state(dev), choices, u, v, points,
+                               n_gt, face_order(verts_c, faces), 0, tri_ws, ws_bytes, ctypes.byref(prepared), cull)
+            if code == 0:
+                if prepared.value & 2:
+                    return choices, u, v, points, ScanPrep(tri_ws, s_index)
+                return choices, u, v, points, (tri_ws if prepared.value else None)
         else:
-            uniforms = torch.rand(3, b, num, device=dev, generator=generator)
-            code = _lib.status("geom_draw_samples_f32", b, nv, verts_c.data_ptr(), faces.shape[0], faces.data_ptr(), num,
-                               uniforms.data_ptr(), choices.data_ptr(), u.data_ptr(), v.data_ptr())
+            code = _lib.status("geom_draw_samples_rng_f32", b, nv, verts_c, faces.shape[0], faces, num, _rng_state(dev),
+                               choices, u, v, points)
+    else:
+        uniforms = torch.rand(3, b, num, device=dev, generator=generator)
+        code = _lib.status("geom_draw_samples_f32", b, nv, verts_c, faces.shape[0], faces, num, uniforms, choices, u, v)
     if code == _lib.EUNSUPPORTED:
         if uniforms is None:
             uniforms = torch.rand(3, b, num, device=dev)
@@ -920,9 +872,7 @@ class VertexHead(torch.autograd.Function):
             raise RuntimeError("feat must be [B,V,C] with C a multiple of 4 matching base [B,V,3]")
         pos = torch.empty_like(b_)
         rows = b_.shape[0] * b_.shape[1]
-        with torch.cuda.device(b_.device):
-            _lib.call("geom_vertex_head_fwd_f32", rows, f_.shape[2], b_.data_ptr(), f_.data_ptr(), float(scale),
-                      pos.data_ptr())
+        _lib.call("geom_vertex_head_fwd_f32", rows, f_.shape[2], b_, f_, float(scale), pos)
         ctx.scale, ctx.c = float(scale), f_.shape[2]
         return pos
 
@@ -933,8 +883,7 @@ class VertexHead(torch.autograd.Function):
         grad_feat = None
         if ctx.needs_input_grad[1]:
             grad_feat = torch.empty(g.shape[0], g.shape[1], ctx.c, dtype=torch.float32, device=g.device)
-            with torch.cuda.device(g.device):
-                _lib.call("geom_vertex_head_bwd_f32", rows, ctx.c, g.data_ptr(), ctx.scale, grad_feat.data_ptr())
+            _lib.call("geom_vertex_head_bwd_f32", rows, ctx.c, g, ctx.scale, grad_feat)
         return (g if ctx.needs_input_grad[0] else None), grad_feat, None
 
 
@@ -951,9 +900,7 @@ def face_curvature(verts, faces, face_list):
     faces = _lib.require(faces, "faces", torch.int64, 2, 3)
     face_list = _lib.require(face_list, "face_list", torch.int64, 3, 3)
     out = torch.empty(face_list.shape[0], dtype=torch.float32, device=v.device)
-    with torch.cuda.device(v.device):
-        _lib.call("geom_face_curvature_f32", v.shape[0], v.data_ptr(), faces.shape[0], faces.data_ptr(), face_list.shape[0],
-                  face_list.data_ptr(), out.data_ptr())
+    _lib.call("geom_face_curvature_f32", v.shape[0], v, faces.shape[0], faces, face_list.shape[0], face_list, out)
     return out
 
 
@@ -963,8 +910,7 @@ def select_faces(curvature, angle):
     c = _f32(curvature, "curvature", 1)
     selected = torch.empty(c.shape[0], dtype=torch.int64, device=c.device)
     count_top3 = torch.empty(4, dtype=torch.int64, device=c.device)
-    with torch.cuda.device(c.device):
-        _lib.call("geom_face_select_f32", c.shape[0], c.data_ptr(), float(angle), selected.data_ptr(), count_top3.data_ptr())
+    _lib.call("geom_face_select_f32", c.shape[0], c, float(angle), selected, count_top3)
     return selected, count_top3
 
 
@@ -987,10 +933,8 @@ def split_index(faces, face_list, splitting, nv):
     ix.corners, ix.split_pos, ix.unsplit_rank, ix.face_s = new(s, 3), new(face_list.shape[0]), new(face_list.shape[0]), new(faces.shape[0])
     ix.inc_ptr, ix.inc_item = new(ix.nv + 1), new(3 * s)
     cursor = new(ix.nv)
-    with torch.cuda.device(dev):
-        _lib.call("geom_face_split_index", ix.nv, faces.shape[0], faces.data_ptr(), face_list.shape[0], face_list.data_ptr(), s,
-                  splitting.data_ptr(), ix.corners.data_ptr(), ix.split_pos.data_ptr(), ix.unsplit_rank.data_ptr(), ix.face_s.data_ptr(),
-                  ix.inc_ptr.data_ptr(), ix.inc_item.data_ptr(), cursor.data_ptr())
+    _lib.call("geom_face_split_index", ix.nv, faces.shape[0], faces, face_list.shape[0], face_list, s, splitting, ix.corners,
+              ix.split_pos, ix.unsplit_rank, ix.face_s, ix.inc_ptr, ix.inc_item, cursor)
     return ix
 
 
@@ -1007,13 +951,10 @@ def split_tables(faces, face_list, ix, rowptr, col, dense=True):
            "ones": torch.empty(nnz_new, dtype=torch.float32, device=dev),
            "adj": torch.zeros(n, n, dtype=torch.float32, device=dev) if dense else None,
            "adj_orig": torch.zeros(n, n, dtype=torch.float32, device=dev) if dense else None}
-    args = _lib.FaceSplit(nv, nft, nfa, s, nnz, faces.data_ptr(), face_list.data_ptr(), ix.corners.data_ptr(),
-                          ix.split_pos.data_ptr(), ix.unsplit_rank.data_ptr(), ix.face_s.data_ptr(), ix.inc_ptr.data_ptr(),
-                          ix.inc_item.data_ptr(), rowptr.data_ptr(), col.data_ptr(), out["new_faces"].data_ptr(),
-                          out["new_face_list"].data_ptr(), out["rowptr"].data_ptr(), out["col"].data_ptr(), out["val"].data_ptr(),
-                          out["val_t"].data_ptr(), out["ones"].data_ptr(), _lib.ptr(out["adj"]), _lib.ptr(out["adj_orig"]))
-    with torch.cuda.device(dev):
-        _lib.call("geom_face_split_tables", ctypes.byref(args))
+    args = _lib.args(_lib.FaceSplit, nv, nft, nfa, s, nnz, faces, face_list, ix.corners, ix.split_pos, ix.unsplit_rank,
+                     ix.face_s, ix.inc_ptr, ix.inc_item, rowptr, col, out["new_faces"], out["new_face_list"], out["rowptr"],
+                     out["col"], out["val"], out["val_t"], out["ones"], out["adj"], out["adj_orig"])
+    _lib.call("geom_face_split_tables", args)
     return out
 
 
@@ -1029,9 +970,7 @@ class SplitVertices(torch.autograd.Function):
             raise RuntimeError("verts %s and features %s must both have the %d rows of the mesh" % (tuple(v.shape), tuple(f.shape), ix.nv))
         out_v = torch.empty(ix.nv + ix.s, 3, dtype=torch.float32, device=v.device)
         out_f = torch.empty(ix.nv + ix.s, f.shape[1], dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            _lib.call("geom_split_vertices_fwd_f32", ix.nv, ix.s, f.shape[1], v.data_ptr(), f.data_ptr(), ix.corners.data_ptr(),
-                      out_v.data_ptr(), out_f.data_ptr())
+        _lib.call("geom_split_vertices_fwd_f32", ix.nv, ix.s, f.shape[1], v, f, ix.corners, out_v, out_f)
         ctx.ix, ctx.c = ix, f.shape[1]
         return out_v, out_f
 
@@ -1041,7 +980,5 @@ class SplitVertices(torch.autograd.Function):
         gv, gf = grad_v.contiguous(), grad_f.contiguous()
         out_v = torch.empty(ix.nv, 3, dtype=torch.float32, device=gv.device)
         out_f = torch.empty(ix.nv, ctx.c, dtype=torch.float32, device=gv.device)
-        with torch.cuda.device(gv.device):
-            _lib.call("geom_split_vertices_bwd_f32", ix.nv, ix.s, ctx.c, gv.data_ptr(), gf.data_ptr(), ix.inc_ptr.data_ptr(),
-                      ix.inc_item.data_ptr(), out_v.data_ptr(), out_f.data_ptr())
+        _lib.call("geom_split_vertices_bwd_f32", ix.nv, ix.s, ctx.c, gv, gf, ix.inc_ptr, ix.inc_item, out_v, out_f)
         return out_v, out_f, None

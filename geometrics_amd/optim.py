@@ -159,10 +159,6 @@ class FusedAdam:
         self._lr_sent = lrs
 
     # ---- the step ----------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _ptrs(tensors):
-        return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
     @property
     def step_count(self):
         """Steps taken so far (one host read)."""
@@ -219,17 +215,17 @@ class FusedAdam:
                 chunks[-1][1].append(i)
             else:
                 chunks.append((lr, [i]))
-        with torch.cuda.device(self.params[0].device):
+        with torch.cuda.device(self.params[0].device):      # (the table step asks about capture and copies on the current stream)
             if self.table or (self.table is None and len(chunks) > 1):
                 self._table_step(live, grads, grad_scale)
             else:
                 self._check_groups(self.param_groups)
                 for k, (lr, chunk) in enumerate(chunks):
-                    pick = lambda seq: self._ptrs([seq[i] for i in chunk])
+                    pick = lambda seq: [seq[i] for i in chunk]
                     sizes = (ctypes.c_int64 * len(chunk))(*[self.params[i].numel() for i in chunk])
                     _lib.call("geom_adam_step_f32", len(chunk), pick([p.data for p in self.params]), pick(grads),
-                              pick(self.exp_avg), pick(self.exp_avg_sq), sizes, lr, float(self.betas[0]),
-                              float(self.betas[1]), float(self.eps), float(grad_scale), self.state.data_ptr(),
+                              pick(self.exp_avg), pick(self.exp_avg_sq), sizes, lr, float(self.betas[0]), float(self.betas[1]),
+                              float(self.eps), float(grad_scale), self.state,
                               int(k + 1 == len(chunks)))      # only the last chunk advances the device-side step state
         for i in stepped:
             self._stepped[i] = True
@@ -285,8 +281,8 @@ class FusedAdam:
             tab.dev.copy_(host, non_blocking=True)
             tab.key = key
         tab.captured = tab.captured or capturing
-        _lib.call("geom_adam_table_step_f32", n, tab.dev.data_ptr(), tab.blocks, self._lr_dev.data_ptr(), float(self.betas[0]),
-                  float(self.betas[1]), float(self.eps), float(grad_scale), self.state.data_ptr(), 1)
+        _lib.call("geom_adam_table_step_f32", n, tab.dev, tab.blocks, self._lr_dev, float(self.betas[0]), float(self.betas[1]),
+                  float(self.eps), float(grad_scale), self.state, 1)
 
     # ---- checkpoints -------------------------------------------------------------------------------------------------------
     def state_dict(self):

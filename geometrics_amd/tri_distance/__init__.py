@@ -125,13 +125,13 @@ def soup_order(tri1, tri2, tri3):
     return order
 
 
-def _order_ptr(order, m, dev):
+def _checked_order(order, m, dev):
     if order is None:
-        return None, None
+        return None
     order = _lib.require(order, "order", torch.int32, 1)
     if order.numel() != m or order.device != dev:
         raise RuntimeError("order must be an int32 permutation of the %d triangles on %s" % (m, dev))
-    return order, order.data_ptr()
+    return order
 
 
 def _outputs(b, n, dev):
@@ -152,14 +152,11 @@ def _scan(names, xyz1, m, geometry, outputs, flags, use_workspace, order):
     between xyz and order (the three corner arrays, or nv / verts / nf / faces); outputs: (dist, point, index)."""
     b, n, _ = xyz1.shape
     dev = xyz1.device
-    out = tuple(t.data_ptr() for t in outputs) + (flags,)
-    with torch.cuda.device(dev):
-        if use_workspace:
-            ws, nbytes = _workspace(b, n, m, dev)
-            order, order_ptr = _order_ptr(order, m, dev)
-            code = _lib.status(names[0], b, n, xyz1.data_ptr(), *geometry, order_ptr, *out, ws.data_ptr(), nbytes)
-        else:
-            code = _lib.status(names[1], b, n, xyz1.data_ptr(), *geometry, *out)
+    if use_workspace:
+        ws, nbytes = _workspace(b, n, m, dev)
+        code = _lib.status(names[0], b, n, xyz1, *geometry, _checked_order(order, m, dev), *outputs, flags, ws, nbytes)
+    else:
+        code = _lib.status(names[1], b, n, xyz1, *geometry, *outputs, flags)
     _lib.check(code, names[1])
 
 
@@ -169,7 +166,7 @@ def forward_cuda(xyz1, tri1, tri2, tri3, dist, point, index, flags=None, use_wor
         flags = _lib.quirk_flags()
     m = tri1.shape[1]
     _scan(("geom_tri_distance_ws_f32", "geom_tri_distance_f32"), xyz1, m,
-          (m, tri1.data_ptr(), tri2.data_ptr(), tri3.data_ptr()), (dist, point, index), flags, use_workspace, order)
+          (m, tri1, tri2, tri3), (dist, point, index), flags, use_workspace, order)
 
 
 def tri_distance(xyz1, tri1, tri2, tri3, flags=None, use_workspace=True, order="auto"):
@@ -208,7 +205,7 @@ def tri_distance_indexed(xyz1, verts, faces, flags=None, use_workspace=True, ord
     if use_workspace and isinstance(order, str):
         order = face_order(verts, faces)
     _scan(("geom_tri_distance_indexed_ws_f32", "geom_tri_distance_indexed_f32"), xyz1, faces.shape[0],
-          (verts.shape[1], verts.data_ptr(), faces.shape[0], faces.data_ptr()), outputs, flags, use_workspace, order)
+          (verts.shape[1], verts, faces.shape[0], faces), outputs, flags, use_workspace, order)
     return outputs
 
 

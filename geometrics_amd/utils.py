@@ -315,8 +315,7 @@ def batch_camera_info(param):
         b = p3.shape[0]
         cam_mat = torch.empty(b, 3, 3, dtype=torch.float32, device=param.device)
         cam_pos = torch.empty(b, 3, dtype=torch.float32, device=param.device)
-        with torch.cuda.device(param.device):
-            _lib.call("geom_camera_info_f32", b, p3.data_ptr(), cam_mat.data_ptr(), cam_pos.data_ptr())
+        _lib.call("geom_camera_info_f32", b, p3, cam_mat, cam_pos)
         return cam_mat, cam_pos
     theta = (math.pi * param[:, 0] / 180.0) % 360.0
     phi = (math.pi * param[:, 1] / 180.0) % 360.0

@@ -57,6 +57,19 @@ def test_reader_parses_every_accepted_form_exactly():
         "geom_words": (ctypes.c_int64, [_u, _f]),
         "geom_launch": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     }
+    scalar = lambda *names: [(n, "scalar", 0) for n in names]
+    described = _header.describe(SYNTHETIC)
+    assert described[0] == prototypes and list(described[1]) == list(structs) and described[2] == constants
+    assert described[3] == {
+        "geom_version": [],
+        "geom_strerror": scalar("code"),
+        "geom_args": scalar("b", "nv") + [("a", "float", 1), ("b2", "float", 1)] + scalar("x", "y", "z")
+        + [("faces", "int64_t", 1)] + scalar("bytes", "flags", "n"),
+        "geom_bytes": scalar("b", "n", "have"),
+        "geom_words": scalar("flags", "scale"),
+        "geom_launch": scalar("count") + [("tensors", "float", 2), ("args", "geom_args", 1), ("mask", "uint16_t", 1),
+                                          ("out", "float", 1), ("stream", "void", 1)],
+    }
 
 
 @pytest.mark.parametrize("declaration, complaint", [
@@ -66,6 +79,9 @@ def test_reader_parses_every_accepted_form_exactly():
     ("short geom_f(int n);", "short"),
     ("float *geom_f(int n);", "returns a pointer"),
     ("typedef struct geom_s { int a; double d; } geom_s;", "double"),
+    ("int geom_f(const double *x);", "double *"),                                    # a pointee the mapping does not hold
+    ("typedef struct geom_s { int a; const short *d; } geom_s;", "short *"),
+    ("int geom_f(const geom_later *args, void *stream);", "geom_later *"),           # a struct nothing declares
     ("int geom_f(int (*callback)(int), void *stream);", "occurrences"),              # nothing the grammar can consume
     ("int geom_f(int n) { return n; }", "occurrences"),
     ("int geom_version(void);", "occurrences"),                                      # declared twice
@@ -105,6 +121,24 @@ def test_struct_layouts_are_the_c_compilers(tmp_path):
             got[(name, field)] = getattr(cls, field).offset
     assert got == expected
     assert len(expected) == sum(1 + len(cls._fields_) for cls in _header.STRUCTS.values())
+
+
+def test_every_pointer_of_the_real_header_has_a_dtype_rule():
+    """Each pointer parameter and field points to an argument struct or to a type the call boundary's dtype table knows."""
+    assert set(_header.PARAMETERS) == set(_header.PROTOTYPES) | set(_header.STRUCTS)
+    pointers = 0
+    for name, described in _header.PARAMETERS.items():
+        fields = _header.STRUCTS[name]._fields_ if name in _header.STRUCTS else None
+        ctypes_of = [t for _, t in fields] if fields else _header.PROTOTYPES[name][1]
+        assert len(described) == len(ctypes_of), name
+        for (param, pointee, depth), ctype in zip(described, ctypes_of):
+            assert (depth > 0) == (ctype is _vp) and (depth == 0) == (pointee == "scalar"), (name, param)
+            if depth:
+                pointers += 1
+                assert depth in (1, 2) and (pointee in _lib.ADMITS or (pointee in _header.STRUCTS and depth == 1)), (name, param)
+        if fields:
+            assert [f for f, _ in fields] == [p for p, _, _ in described], name
+    assert pointers > 500
 
 
 def test_python_limits_are_the_headers():
