@@ -65,7 +65,7 @@ __device__ __forceinline__ void draw_samples_body(int chunk, int mesh, unsigned 
                                                   float *points, const DrawSort &srt)
 {
     __shared__ float cdf[DRAW_MAX_FACES];
-    __shared__ float wave_total[DRAW_THREADS / GEOM_WAVE];
+    __shared__ float wave_total[DRAW_THREADS / GEOM_WAVE], wave_top[DRAW_THREADS / GEOM_WAVE];
     const float *V = verts + (size_t)mesh * nv * 3;
     // the random stream's state is requested first: read after the CDF it would add a dependent round trip to a launch
     // that is a chain of them (face ids -> corners -> scan -> search -> face ids -> corners -> store)
@@ -110,6 +110,7 @@ __device__ __forceinline__ void draw_samples_body(int chunk, int mesh, unsigned 
     const int per = (nf + DRAW_THREADS - 1) / DRAW_THREADS; // consecutive faces per thread
     const int f0 = threadIdx.x * per;
     float run = 0.f;
+    bool weighs = false; // one of this thread's entries weighs something
     const int f1 = min(f0 + per, nf);
 #pragma unroll 4
     for (int f = f0; f < f1; ++f) { // local inclusive sums
@@ -131,8 +132,10 @@ __device__ __forceinline__ void draw_samples_body(int chunk, int mesh, unsigned 
         const geom::V3 v2 = draw_ld3(V + 3 * c2);
         const geom::V3 x = v0 - v1, y = v1 - v2;
         const float ca = x.y * y.z - x.z * y.y, cb = x.z * y.x - x.x * y.z, cc = x.x * y.y - x.y * y.x;
-        run += real ? sqrtf((ca * ca + cb * cb) + cc * cc) / 2.f : 0.f;
-        cdf[f] = run;
+        const float area = real ? sqrtf((ca * ca + cb * cb) + cc * cc) / 2.f : 0.f;
+        run += area;
+        weighs |= area > 0.f;
+        cdf[f] = area > 0.f ? run : -run; // the sign bit marks an entry that weighs nothing (run >= 0; -0.f where it is 0)
     }
     // exclusive offset of this thread: wave scan of the thread totals, then scan of the 16 wave totals
     float incl = run;
@@ -145,9 +148,31 @@ __device__ __forceinline__ void draw_samples_body(int chunk, int mesh, unsigned 
     float base = 0.f;
     for (int w = 0; w < wave; ++w) base += wave_total[w];
     const float offset = base + (incl - run);
-    for (int f = f0; f < min(f0 + per, nf); ++f) cdf[f] += offset;
+    // THE TABLE the search reads: entry f = the LARGEST offset + local sum over the entries <= f that weigh something (0 in front of
+    // the first).  The three pieces of the sum associate differently on either side of a thread boundary, so the sums themselves
+    // step down by an ulp here and there, and up across some entries that weigh nothing (a face of zero area, a face_order entry
+    // that is no face) -- about one draw in 10^6 landed on such an entry.  A running maximum that skips them is non-decreasing and
+    // flat across them BY CONSTRUCTION, whatever the sums round to, and max is exactly associative: per thread, wave scan, wave
+    // maxima, like the sums.  Where the sums ascend (every mesh whose faces all weigh more than an ulp of the total) the table IS
+    // the sums.  Inside a thread offset + local sum ascends with the local sum, so the thread's largest is its last: offset + run.
+    float top = weighs ? offset + run : 0.f;
+    for (int off = 1; off < GEOM_WAVE; off <<= 1) {
+        const float t = __shfl_up(top, off, GEOM_WAVE);
+        if (lane >= off) top = fmaxf(top, t);
+    }
+    if (lane == GEOM_WAVE - 1) wave_top[wave] = top;
+    float peak = __shfl_up(top, 1, GEOM_WAVE); // exclusive: the largest in front of this thread
+    if (lane == 0) peak = 0.f;
     __syncthreads();
-    const float total = cdf[nf - 1];
+    for (int w = 0; w < wave; ++w) peak = fmaxf(peak, wave_top[w]);
+    for (int f = f0; f < f1; ++f) {
+        const float c = cdf[f];
+        if (!(__float_as_uint(c) >> 31)) peak = fmaxf(peak, c + offset);
+        cdf[f] = peak;
+    }
+    __syncthreads();
+    const float total = cdf[nf - 1]; // the largest sum; target = r0 * total < total for r0 <= 1 - 2^-24, so the search ends on
+                                     // an entry above the one in front of it: one that weighs something
     if constexpr (SORTED) { // (chunk_part / scan_part were written in front of the CDF scan's barrier)
         float before = 0.f, all = 0.f; // spacings of the chunks in front of this one / of all samples + the extra one
 #pragma unroll

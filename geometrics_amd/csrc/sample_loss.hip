@@ -55,9 +55,14 @@ __global__ __launch_bounds__(PT_THREADS) void face_areas_kernel(int b, int nv, c
 // uniforms (the reference: a python loop of B torch.multinomial calls plus two sample_n calls,
 // utils.py:604-612, 627-628).  One workgroup = one (mesh, 1024-sample chunk): it rebuilds the
 // mesh's face-area CDF in LDS (areas as in face_areas_kernel, block-wide inclusive scan in a fixed
-// order) and every thread inverts it for its sample with a binary search: face = first f with
-// cdf[f] > U0 * total.  Same distribution as multinomial(areas, num, replacement=True); the
-// stream of draws is our own (torch's generator stream is not reproducible across devices either).
+// order, then a running maximum over the faces of positive area: non-decreasing and flat across a
+// face of zero area whatever the sums round to -- draw_body.h) and every thread inverts it for its
+// sample with a binary search: face = first f with cdf[f] > U0 * total.
+// multinomial(areas, num, replacement=True) up to fp32 rounding: a face of zero area is never
+// drawn, every other face with a probability within a few 2^-24 of its share (tests/
+// test_draw_exact_host.py holds all 2^24 uniforms to the float64 inverse CDF); a face below an ulp
+// of the mesh's area may not be drawn at all.  The stream of draws is our own (torch's generator
+// stream is not reproducible across devices either).
 __global__ __launch_bounds__(DRAW_THREADS) void draw_samples_kernel(int nv, const float *verts, int nf,
                                                                      const int64_t *faces, int num,
                                                                      const float *uniforms, int64_t plane,

@@ -803,8 +803,8 @@ def _rng_state(dev):
 
 def draw_samples(verts, faces, num, generator=None, with_points=False, prepare_scan_for=None, gt_index=None):
     """The random part of batch_sample (reference utils.py:604-612, 627-628): choices [B,num] ~
-    area-weighted with replacement, u = sqrt(U1), v = U2, in ONE kernel: per-mesh face-area CDF in LDS,
-    binary search per sample, uniforms from an in-kernel Philox stream whose position lives on the device
+    area-weighted with replacement, u = sqrt(U1), v = U2, in ONE kernel: per-mesh face-area CDF in LDS (monotone by
+    construction: a face of zero area is never drawn), binary search per sample, uniforms from an in-kernel Philox stream whose position lives on the device
     (graph replays draw fresh numbers; no generator bookkeeping launches).  With an explicit torch
     `generator` the uniforms come from torch.rand instead; meshes with more than 16384 faces take the
     torch.multinomial route.  with_points=True also returns the sampled points [B,num,3] (or None when the

@@ -136,7 +136,9 @@ int geom_face_areas_f32(int b, int nv, const float *verts, int nf, const int64_t
 /* The random part of batch_sample (utils.py:604-612, 627-628) from caller-supplied uniforms
  * uniforms[3][b][num] in [0,1):  choices[b,num] = area-weighted face id (inverse CDF of the face areas
  * at uniforms[0], i.e. multinomial with replacement), u = sqrt(uniforms[1]), v = uniforms[2].
- * nf <= 16384 (the CDF lives in LDS), otherwise GEOM_EUNSUPPORTED. */
+ * The table searched is the running maximum of the fp32 CDF over the faces of positive area (csrc/draw_body.h):
+ * non-decreasing and flat across a face of zero area, which is therefore never drawn for uniforms[0] <= 1 - 2^-24.
+ * nf <= 16384 (the table lives in LDS), otherwise GEOM_EUNSUPPORTED. */
 int geom_draw_samples_f32(int b, int nv, const float *verts, int nf, const int64_t *faces, int num,
                           const float *uniforms, int64_t *choices, float *u, float *v, void *stream);
 /* Same draws from an in-kernel counter-based generator (Philox4x32-10): rng_state = 4 device uint64
