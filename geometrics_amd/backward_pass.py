@@ -26,6 +26,7 @@ import torch
 
 from . import _lib
 from . import dense as _dense_kernels
+from ._identity import ByTensor
 
 
 _DEFAULTS = {"defer": False,      # deferred_parameter_gradients(): bias / weight gradients finished at the end of the pass
@@ -100,40 +101,38 @@ def set_optimizer(opt):
 # A parameter bound to a tensor of its shape gets its gradient WRITTEN THERE by the layers' launches: the end-of-pass reduction
 # writes straight into the flat all-reduce bucket, autograd adopts the tensor as `.grad` (a fresh contiguous tensor object of
 # the parameter's layout is taken as is), and the bucket's pack launch has nothing left to gather.
-_gradient_targets = {}
+_gradient_targets = ByTensor(versioned=False)      # parameter (whatever the optimiser has done to it in place) -> its target
 
 
 def bind_gradient_targets(params, tensors):
     """`tensors[i]` (same shape / dtype / device as `params[i]`, contiguous) receives the gradient of `params[i]` from now on;
     None unbinds.  Only gradients the layers produce themselves land there (a library-product fallback returns its own tensor)."""
     for p, t in zip(params, tensors):
-        key = id(p)
         if t is None:
-            _gradient_targets.pop(key, None)
+            _gradient_targets.drop(p)
             continue
         if t.shape != p.shape or t.dtype != p.dtype or t.device != p.device or not t.is_contiguous():
             raise ValueError("a gradient target must match its parameter's shape, dtype and device and be contiguous")
-        _gradient_targets[key] = (weakref.ref(p, lambda _r, k=key: _gradient_targets.pop(k, None)), t)
+        _gradient_targets.put(t, p)
 
 
 def _gradient_buffer(param, like):
     """Where the gradient of `param` (may be None: unknown) goes: its bound target, else a new tensor like `like`."""
-    hit = _gradient_targets.get(id(param)) if param is not None else None
+    target = _gradient_targets.get(param) if param is not None else None
     # (a parameter that already holds a gradient is being ACCUMULATED into: the new gradient must not overwrite the old one's
     # memory, which is what the target is by then)
     # (a parameter fed by more than one live autograd node -- a shared weight or bias, a layer applied twice -- has its
     # gradients ADDED by the engine: each node needs memory of its own, or the second would overwrite the first's before the
     # sum is formed; GradBucket.pack() gathers a gradient that did not land in its view by copy)
-    if (hit is not None and hit[0]() is param and hit[1].shape == like.shape and param.grad is None
-            and _user_count(param) <= 1):
-        return hit[1].detach()           # a fresh tensor object over the target's memory (autograd adopts it as .grad)
+    if target is not None and target.shape == like.shape and param.grad is None and _user_count(param) <= 1:
+        return target.detach()           # a fresh tensor object over the target's memory (autograd adopts it as .grad)
     return torch.zeros_like(like) if switches.zero_fill else torch.empty_like(like)
 
 
 # ---- parameter -> the live autograd nodes that produce a gradient for it: a parameter shared by two layers (or a layer applied
 # twice) gets its gradients ADDED by the engine inside the pass, which reads them on arrival -- more than one live node means
 # immediate reduction for all of them.  Nodes leave the set when their graph is freed.
-_users = {}          # id(param) -> (weak reference to the param, WeakSet of nodes); keyed by identity, tensors do not compare
+_users = ByTensor(versioned=False)      # parameter -> WeakSet of nodes
 
 
 def parameter_ref(param, node, needs_grad):
@@ -142,17 +141,16 @@ def parameter_ref(param, node, needs_grad):
     if param is None:
         return None
     if needs_grad:
-        key = id(param)
-        entry = _users.get(key)
-        if entry is None or entry[0]() is not param:
-            entry = _users[key] = (weakref.ref(param, lambda _ref, k=key: _users.pop(k, None)), weakref.WeakSet())
-        entry[1].add(node)
+        nodes = _users.get(param)
+        if nodes is None:
+            nodes = _users.put(weakref.WeakSet(), param)
+        nodes.add(node)
     return weakref.ref(param)
 
 
 def _user_count(param):
-    entry = _users.get(id(param))
-    return len(entry[1]) if entry is not None and entry[0]() is param else 0
+    nodes = _users.get(param)
+    return len(nodes) if nodes is not None else 0
 
 
 def _alias(t):

@@ -35,6 +35,7 @@
 // The chain kernels sit at 256 VGPRs already (tools/kernel_resources.sh): one body templated over the tile count, or the eval
 // table walk folded into db_aggregate, would trade these orders for one that fits none of them.
 #include "mfma_tiles.h"
+#include "device_facts.h"
 
 namespace {
 
@@ -1446,21 +1447,19 @@ extern "C" int geom_deform_pack_weights_zero_f32(int count, const float *const *
 extern "C" int geom_deform_chain_fits(int nv)
 {
     if (nv <= 0) return 0;
-    static int slots[64] = {0}; // per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (!slots[dev]) {
-        int per_cu = 0;
-        hipDeviceProp_t prop;
-        int per_cu_b = 0;
+    static int slots[geom::MAX_DEVICES] = {0}; // per device: the occupancy query is not free
+    const geom::DeviceFacts *dev = geom::device_facts();
+    if (!dev) return 0;
+    int &have = slots[dev->device];
+    if (!have) {
+        int per_cu = 0, per_cu_b = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, db_fwd_chain_kernel, DB_THREADS, 0) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_b, db_bwd_chain_kernel, DB_THREADS, 0) != hipSuccess ||
-            hipGetDeviceProperties(&prop, dev) != hipSuccess)
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_b, db_bwd_chain_kernel, DB_THREADS, 0) != hipSuccess)
             return 0;
         per_cu = per_cu < per_cu_b ? per_cu : per_cu_b;
-        slots[dev] = per_cu * prop.multiProcessorCount > 0 ? per_cu * prop.multiProcessorCount : -1;
+        have = per_cu > 0 ? per_cu * dev->compute_units : -1;
     }
-    return slots[dev] >= 8 * ((nv + 7) / 8);
+    return have >= 8 * ((nv + 7) / 8);
 }
 
 // `count` consecutive layers (layers[l + 1].s_in == layers[l].s_out, all but possibly the last with a product) in ONE launch;

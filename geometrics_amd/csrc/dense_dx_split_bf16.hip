@@ -25,6 +25,7 @@
 // -DDX_PROBE_NO_PROLOGUE take one stream out of the launch each (results are then wrong; the MFMAs stay: the stores hang on a
 // condition the compiler cannot see through).
 #include "buffer_access.h"
+#include "device_facts.h"
 #include <type_traits>
 
 namespace {
@@ -291,18 +292,6 @@ __global__ __launch_bounds__(DX_THREADS, 1) void dx_split_kernel(DxArgs p)
     if (stray_rb >= 0 && wave == 3) dx_stray(p, lds, lane, n, stray_rb, stray_grp);
 }
 
-int compute_units()
-{
-    static int cus[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev]) {
-        int n = 0;
-        cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    }
-    return cus[dev];
-}
-
 } // namespace
 
 // rows of the planes buffer: cin rounded up to whole column groups of a wave
@@ -334,16 +323,11 @@ extern "C" int geom_dense_dx_split_f32(int rows, int cin, int c, const float *g,
     // (32-bit byte offsets against descriptors below 2 GiB)
     if ((int64_t)cinpad * DX_K * 6 >= (1LL << 31) || (int64_t)rows * ldx * 4 >= (1LL << 31) || (int64_t)rows * DX_K * 4 >= (1LL << 31)) return GEOM_ETOOBIG;
     DxArgs p{g, planes, dx, rows, cin, cinpad, ldx, 0};
-    static bool configured[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && !configured[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(dx_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DX_LDS) != hipSuccess)
-            return GEOM_EINVAL;
-        configured[dev] = true;
-    }
+    const geom::DeviceFacts *dev = geom::device_facts();
+    if (int code = geom::allow_dynamic_lds(dx_split_kernel, DX_LDS, dev)) return code;
     // whole rounds of one workgroup per compute unit, each with at most DX_MAX_RB row-blocks, as evenly as they divide
     const int64_t nrb = ((int64_t)rows + 15) >> 4;
-    const int64_t cus = compute_units();
+    const int64_t cus = dev ? dev->compute_units : 256;
     const int64_t rounds = (nrb + DX_MAX_RB * cus - 1) / (DX_MAX_RB * cus);
     const int64_t grid = nrb < rounds * cus ? nrb : rounds * cus;
     // what the equal shares leave over (fewer row-blocks than workgroups) goes out a column group each, where there are

@@ -27,6 +27,7 @@
 //   * a weight gradient (inner dimension = all rows) is split over the rows so that all CUs work; partial tiles go to a
 //     workspace and are added up in slot order by a reduction kernel -- a fixed order, so results are bit-reproducible.
 #include "buffer_access.h"
+#include "device_facts.h"
 #include "adam_math.h"
 #include <type_traits>
 
@@ -1056,16 +1057,11 @@ __global__ __launch_bounds__(RED_THREADS) void dense_reduce_kernel(ReduceJobs jo
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 
+// compute units of the current device (256, an MI355X's, when it is unknown): asked once per entry-point call
 int num_cus()
 {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
+    const geom::DeviceFacts *dev = geom::device_facts();
+    return dev ? dev->compute_units : 256;
 }
 
 // rows-kernel geometry: RB row-blocks per tile such that the busiest workgroup does the least work
@@ -1198,16 +1194,22 @@ extern "C" int geom_dense_fwd_f32(int rows, int cin, int c, const float *x, cons
     return avec ? launch_rows_rb<3, false, true, EPI_PLAIN>(q, geo, s) : launch_rows_rb<3, false, false, EPI_PLAIN>(q, geo, s);
 }
 
-// grad_x = g . w^T   (g [rows, c], w [cin, c], grad_x [rows, cin])
-extern "C" int geom_dense_bwd_input_f32(int rows, int cin, int c, const float *g, const float *w, float *grad_x, void *stream)
+// (the two halves of the backward, for `cus` compute units: geom_dense_bwd_f32 asks for the device once and issues both)
+static int bwd_input(int cus, int rows, int cin, int c, const float *g, const float *w, float *grad_x, void *stream)
 {
     const int code = check_backward(true, false, rows, cin, c, nullptr, g, w, grad_x, nullptr);
     if (code || rows == 0) return code;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int ncw = cin > 192 ? 4 : 3;
-    const RowGeo geo = row_geometry(rows, ncw, num_cus());
+    const RowGeo geo = row_geometry(rows, ncw, cus);
     const RowArgs q = input_gradient_args(rows, cin, c, g, w, grad_x, ncw, geo);
     return ncw == 4 ? launch_rows_rb<4, true, true, EPI_PLAIN>(q, geo, s) : launch_rows_rb<3, true, true, EPI_PLAIN>(q, geo, s);
+}
+
+// grad_x = g . w^T   (g [rows, c], w [cin, c], grad_x [rows, cin])
+extern "C" int geom_dense_bwd_input_f32(int rows, int cin, int c, const float *g, const float *w, float *grad_x, void *stream)
+{
+    return bwd_input(num_cus(), rows, cin, c, g, w, grad_x, stream);
 }
 
 extern "C" int64_t geom_dense_bwd_weight_workspace_floats(int rows, int cin, int c)
@@ -1217,13 +1219,11 @@ extern "C" int64_t geom_dense_bwd_weight_workspace_floats(int rows, int cin, int
     return g.partial_floats() + (int64_t)(g.s_full > 0 ? g.s_full : g.s_left) * c;
 }
 
-// partial sums of grad_w = x^T . g into `workspace`; geom_dense_reduce_f32 finishes them (and the bias gradient)
-extern "C" int geom_dense_bwd_weight_f32(int rows, int cin, int c, const float *x, const float *g, float *workspace,
-                                         int want_colsum, void *stream)
+static int bwd_weight(int cus, int rows, int cin, int c, const float *x, const float *g, float *workspace, int want_colsum, void *stream)
 {
     const int code = check_backward(false, true, rows, cin, c, x, g, nullptr, nullptr, workspace);
     if (code) return code;
-    const SplitGeo geo = split_geometry(cin, rows, num_cus());
+    const SplitGeo geo = split_geometry(cin, rows, cus);
     if (want_colsum && geo.full_tiles == 0) return GEOM_EUNSUPPORTED;
     const SplitArgs q = split_args(rows, cin, c, x, g, workspace, want_colsum != 0, geo);
     const dim3 grid(geo.slots), block(DG_THREADS);
@@ -1239,6 +1239,13 @@ extern "C" int geom_dense_bwd_weight_f32(int rows, int cin, int c, const float *
     return geom::launch_status();
 }
 
+// partial sums of grad_w = x^T . g into `workspace`; geom_dense_reduce_f32 finishes them (and the bias gradient)
+extern "C" int geom_dense_bwd_weight_f32(int rows, int cin, int c, const float *x, const float *g, float *workspace,
+                                         int want_colsum, void *stream)
+{
+    return bwd_weight(num_cus(), rows, cin, c, x, g, workspace, want_colsum, stream);
+}
+
 // Both gradients of one layer: grad_x = g . w^T and the partial sums of grad_w = x^T . g (finished by geom_dense_reduce_f32).
 // One launch with two workgroups per CU (dense_bwd_pair_kernel) when both halves fit that mode: cin <= 192 (one column chunk
 // for the input gradient) and 16-byte aligned x rows; two launches otherwise (the 963-wide first layer).
@@ -1252,9 +1259,9 @@ extern "C" int geom_dense_bwd_f32(int rows, int cin, int c, const float *x, cons
     const RowGeo rg = row_geometry(rows, 3, cus);
     const SplitGeo sg = split_geometry(cin, rows, cus);
     if (cin > 192 || !xvec || (want_colsum && sg.full_tiles == 0) || rg.rb < 2 || rg.rb > 5) { // rb 6: 82 KB of LDS, no pairing
-        code = geom_dense_bwd_input_f32(rows, cin, c, g, w, grad_x, stream);
+        code = bwd_input(cus, rows, cin, c, g, w, grad_x, stream);
         if (code) return code;
-        return geom_dense_bwd_weight_f32(rows, cin, c, x, g, workspace, want_colsum, stream);
+        return bwd_weight(cus, rows, cin, c, x, g, workspace, want_colsum, stream);
     }
     const RowArgs r = input_gradient_args(rows, cin, c, g, w, grad_x, 3, rg);
     const SplitArgs q = split_args(rows, cin, c, x, g, workspace, want_colsum != 0, sg);
@@ -1304,8 +1311,9 @@ inline bool bad_layer(const float *workspace, const float *grad_w, int rows, int
     return !workspace || !grad_w || rows <= 0 || cin <= 0 || c <= 0 || c > 192 || c % 4;
 }
 
-// the jobs of the three reduction entries: weight gradients first (job l = layer l), then the column-sum jobs (job count + i)
-int build_reduce_jobs(ReduceJobs &jobs, int count, const int *rows, const int *cin, const int *c, const float *const *workspaces,
+// the jobs of the three reduction entries, for `cus` compute units: weight gradients first (job l = layer l), then the column-sum
+// jobs (job count + i)
+int build_reduce_jobs(ReduceJobs &jobs, int cus, int count, const int *rows, const int *cin, const int *c, const float *const *workspaces,
                       float *const *grad_w, int ncs, const float *const *cs_partials, const int *cs_rows, const int *cs_cols,
                       float *const *cs_outs)
 {
@@ -1316,7 +1324,7 @@ int build_reduce_jobs(ReduceJobs &jobs, int count, const int *rows, const int *c
     int n = 0;
     for (int l = 0; l < count; ++l) {
         if (bad_layer(workspaces[l], grad_w[l], rows[l], cin[l], c[l])) return GEOM_EINVAL;
-        const SplitGeo g = split_geometry(cin[l], rows[l], num_cus());
+        const SplitGeo g = split_geometry(cin[l], rows[l], cus);
         jobs.job[n++] = ReduceJob{workspaces[l], grad_w[l], cin[l], c[l], g.rb * 16, 192, g.full_tiles, g.s_full, g.s_left, 0};
     }
     for (int i = 0; i < ncs; ++i) { // column sums: a 1-row "tile" per partial row, pitch = the column count
@@ -1345,7 +1353,7 @@ extern "C" int geom_dense_reduce2_f32(int count, const int *rows, const int *cin
     if (grad_bias) return GEOM_EINVAL; // bias gradients travel as column-sum jobs here
     if (count + ncs == 0) return 0;
     ReduceJobs jobs;
-    const int code = build_reduce_jobs(jobs, count, rows, cin, c, workspaces, grad_w, ncs, cs_partials, cs_rows, cs_cols, cs_outs);
+    const int code = build_reduce_jobs(jobs, num_cus(), count, rows, cin, c, workspaces, grad_w, ncs, cs_partials, cs_rows, cs_cols, cs_outs);
     return code ? code : launch_reduce(jobs, ReduceAdam{}, stream);
 }
 
@@ -1364,7 +1372,7 @@ extern "C" int geom_dense_reduce_adam_f32(int count, const int *rows, const int 
     if (count + ncs == 0 || !state) return GEOM_EINVAL;
     if ((count && (!w_p || !w_m || !w_v)) || (ncs && (!b_p || !b_m || !b_v))) return GEOM_EINVAL;
     ReduceJobs jobs;
-    const int code = build_reduce_jobs(jobs, count, rows, cin, c, workspaces, grad_w, ncs, cs_partials, cs_rows, cs_cols, cs_outs);
+    const int code = build_reduce_jobs(jobs, num_cus(), count, rows, cin, c, workspaces, grad_w, ncs, cs_partials, cs_rows, cs_cols, cs_outs);
     if (code) return code;
     ReduceAdam adam{};
     for (int l = 0; l < count; ++l) {
@@ -1395,15 +1403,16 @@ extern "C" int geom_dense_reduce_f32(int count, const int *rows, const int *cin,
     const float *cs_partials[MAX];
     float *cs_outs[MAX];
     int cs_rows[MAX], cs_cols[MAX], ncs = 0;
+    const int cus = num_cus();
     for (int l = 0; l < count; ++l) {
         if (bad_layer(workspaces[l], grad_w[l], rows[l], cin[l], c[l])) return GEOM_EINVAL;
         if (!grad_bias || !grad_bias[l]) continue;
-        const SplitGeo g = split_geometry(cin[l], rows[l], num_cus());
+        const SplitGeo g = split_geometry(cin[l], rows[l], cus);
         if (g.full_tiles == 0) return GEOM_EUNSUPPORTED;
         cs_partials[ncs] = workspaces[l] + g.colsum_offset(), cs_outs[ncs] = grad_bias[l];
         cs_rows[ncs] = g.s_full, cs_cols[ncs] = c[l], ++ncs;
     }
     ReduceJobs jobs;
-    const int code = build_reduce_jobs(jobs, count, rows, cin, c, workspaces, grad_w, ncs, cs_partials, cs_rows, cs_cols, cs_outs);
+    const int code = build_reduce_jobs(jobs, cus, count, rows, cin, c, workspaces, grad_w, ncs, cs_partials, cs_rows, cs_cols, cs_outs);
     return code ? code : launch_reduce(jobs, ReduceAdam{}, stream);
 }

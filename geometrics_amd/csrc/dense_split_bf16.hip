@@ -19,6 +19,7 @@
 // padded to 80 bytes (16 rows x 16 B cover all 64 banks); double-buffered, the next block's global loads travel under the
 // current block's 108 MFMAs per wave.
 #include "buffer_access.h"
+#include "device_facts.h"
 
 namespace {
 
@@ -232,13 +233,7 @@ extern "C" int geom_gemm_split_bf16_f32(int m, int k, int n, const float *a, con
     if (!a || !planes || !c || ((uintptr_t)planes & 15) || ((uintptr_t)a & 3) || ((uintptr_t)c & 3)) return GEOM_EINVAL;
     if ((int64_t)m * k >= (1LL << 31)) return GEOM_ETOOBIG;
     SbArgs p{a, reinterpret_cast<const unsigned short *>(planes), c, m, k, geom_split_bf16_kpad(k), terms};
-    static bool configured[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && !configured[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(split_bf16_gemm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * SB_BUF) != hipSuccess)
-            return GEOM_EINVAL;
-        configured[dev] = true;
-    }
+    if (int code = geom::allow_dynamic_lds(split_bf16_gemm_kernel, 2 * SB_BUF)) return code;
     hipLaunchKernelGGL(split_bf16_gemm_kernel, dim3((m + SB_TM - 1) / SB_TM), dim3(SB_THREADS), 2 * SB_BUF, static_cast<hipStream_t>(stream), p);
     return geom::launch_status();
 }

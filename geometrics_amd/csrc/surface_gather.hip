@@ -19,6 +19,7 @@
 // grad_verts is written once per element (no zero-fill, no float atomics) and is bit-reproducible.  The scratch the two
 // launches share is laid out in surface_layout.h.
 #include "geom_common.h"
+#include "device_facts.h"
 #include "tri_math.h"
 #include "surface_layout.h"
 #include "finalize_body.h"
@@ -31,27 +32,15 @@ constexpr int SGA_THREADS = 256;
 constexpr int ORD_THREADS = 1024;
 constexpr int ORD_WAVES = ORD_THREADS / GEOM_WAVE;
 constexpr int VTX_LANES = 8;    // lanes that share a vertex in the gather: one incident face each, then an ordered fold
-// dynamic LDS one workgroup may take for the ordering pass: what the device grants (160 KiB on gfx950) minus 10 KiB for the
-// kernels' static arrays; read from the device once, so a part with less LDS answers GEOM_EUNSUPPORTED instead of failing
-// the launch
-inline size_t ord_lds_limit()
+// dynamic LDS one workgroup may take for the ordering pass: what the device grants (160 KiB on gfx950; 64 KiB assumed of an
+// unknown one) minus 10 KiB for the kernels' static arrays, so a part with less LDS answers GEOM_EUNSUPPORTED instead of
+// failing the launch
+inline size_t ord_lds_limit(const geom::DeviceFacts *dev)
 {
-    static size_t limit = 0;
-    if (!limit) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        size_t have = 64 * 1024;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) {
-            have = prop.sharedMemPerBlock;
-            if (prop.sharedMemPerBlockOptin > have) have = prop.sharedMemPerBlockOptin;
-            if (prop.maxSharedMemoryPerMultiProcessor > have) have = prop.maxSharedMemoryPerMultiProcessor;
-        }
-        limit = have > 16 * 1024 ? have - 10 * 1024 : have;
-        if (limit > 150 * 1024) limit = 150 * 1024;
-    }
-    return limit;
+    const size_t have = dev ? dev->lds_per_block_optin : 64 * 1024;
+    const size_t limit = have > 16 * 1024 ? have - 10 * 1024 : have;
+    return limit > 150 * 1024 ? 150 * 1024 : limit;
 }
-#define ORD_LDS_LIMIT (ord_lds_limit())
 
 using geom_finalize::OTHER_NONE;
 using geom_finalize::OTHER_NN;
@@ -180,10 +169,12 @@ extern "C" int geom_surface_finalize_w_f32(int b, int nf, int num, const int64_t
     const int64_t per64 = (int64_t)num + (other != OTHER_NONE ? n_gt : 0);
     if (per64 > 0x3fffffff) return GEOM_ETOOBIG;
     const int per = (int)per64;
+    const geom::DeviceFacts *dev = geom::device_facts();
+    const size_t ord_lds = ord_lds_limit(dev);
     if (want_order) {
         if (num > 0 && (!choices || !u || !v || !points || !gt || !idx_g || n_gt == 0)) return GEOM_EINVAL;
         if (index && (!closest || !weights || !gt)) return GEOM_EINVAL;
-        if (order_lds_bytes(nf, per) > ORD_LDS_LIMIT) return GEOM_EUNSUPPORTED;
+        if (order_lds_bytes(nf, per) > ord_lds) return GEOM_EUNSUPPORTED;
     }
     const SurfaceScratch scr = geom_surface_scratch(order, b, nf, (int64_t)num + n_gt);
     FinalizeArgs a{choices, u, v, points, gt, idx_g, idx_p, index, closest, weights, sq_sample, sq_other, scale_sample,
@@ -194,14 +185,10 @@ extern "C" int geom_surface_finalize_w_f32(int b, int nf, int num, const int64_t
     // documented fallback beyond the ordering limit (want_order = 0 + scatter backward) really launches
     const size_t lds = geom_finalize::finalize_lds_ints(nf, per, ORD_THREADS, want_order != 0) * sizeof(int);
     if (per <= geom_finalize::FIN_REG_POINTS) {
-        static const hipError_t opt_in = hipFuncSetAttribute(reinterpret_cast<const void *>(surface_finalize_kernel<true>),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)ORD_LDS_LIMIT + 1024);
-        (void)opt_in;
+        (void)geom::allow_dynamic_lds(surface_finalize_kernel<true>, (int)ord_lds + 1024, dev); // (a refusal: the launch reports it)
         hipLaunchKernelGGL(surface_finalize_kernel<true>, dim3(want_order ? b + 1 : 1), dim3(ORD_THREADS), lds, s, a);
     } else {
-        static const hipError_t opt_in = hipFuncSetAttribute(reinterpret_cast<const void *>(surface_finalize_kernel<false>),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)ORD_LDS_LIMIT + 1024);
-        (void)opt_in;
+        (void)geom::allow_dynamic_lds(surface_finalize_kernel<false>, (int)ord_lds + 1024, dev);
         hipLaunchKernelGGL(surface_finalize_kernel<false>, dim3(want_order ? b + 1 : 1), dim3(ORD_THREADS), lds, s, a);
     }
     return geom::launch_status();

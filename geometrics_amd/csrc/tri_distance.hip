@@ -35,6 +35,7 @@
 // arrays the reference materialises (utils.py:467-469) never exist.
 // Arithmetic: tri_math.h (literal operation order of tri_distance.cu:140-191).
 #include "geom_common.h"
+#include "device_facts.h"
 #include "tri_math.h"
 #include "nn_scan.h"
 #include "surface_layout.h"
@@ -1142,16 +1143,8 @@ struct ScanTail {
 // (64 meshes on the 256 CUs of an MI355X; a partition with fewer CUs takes fewer)
 inline int scan_tail_max_meshes()
 {
-    static int most[64] = {0}; // per device: a process may drive partitions of different sizes
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1;
-    if (!most[dev]) {
-        int cus = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        most[dev] = cus >= 8 ? cus / 4 : 1;
-    }
-    return most[dev];
+    const geom::DeviceFacts *dev = geom::device_facts();
+    return dev && dev->compute_units >= 8 ? dev->compute_units / 4 : 1;
 }
 constexpr int SCAN_TAIL_LDS_INTS = 11776; // 46 KB: three workgroups per CU still fit (the BASELINE mesh needs 11 173)
 

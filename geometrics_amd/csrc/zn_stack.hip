@@ -47,6 +47,7 @@
 // ~7 times); the few row-blocks beyond an equal share (1281 = 5 * 256 + 1 at the BASELINE shard) are not given whole to
 // single workgroups (+20 % for the launch) but cut three ways by column component, +48 MFMAs on 720 for three workgroups.
 #include "mfma_tiles.h"
+#include "device_facts.h"
 
 namespace {
 
@@ -496,18 +497,10 @@ __global__ __launch_bounds__(ZS_THREADS, 2) void zs_layer_kernel(ZsArgs a)
     zs_body<MODE, ACT, HEAD>(a, lds, blockIdx.x, gridDim.x);
 }
 
-int zs_cus()
+int zs_cus() // partitions / devices of different sizes get a grid sized for themselves
 {
-    static int cus[64]; // per device: partitions / devices of different sizes get a grid sized for themselves
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev]) {
-        hipDeviceProp_t prop;
-        int n = 0;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        cus[dev] = n > 0 ? n : 256;
-    }
-    return cus[dev];
+    const geom::DeviceFacts *dev = geom::device_facts();
+    return dev ? dev->compute_units : 256;
 }
 
 struct ZsGeo {

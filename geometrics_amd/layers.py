@@ -10,7 +10,6 @@ kernel computes the feature product `input @ W` and its gradients is `products.r
 """
 import math
 import os
-import weakref
 
 import torch
 import torch.nn.functional as F
@@ -23,6 +22,7 @@ from . import aggregation as _agg
 from . import backward_pass as _pass
 from . import fused as _fused
 from . import products as _products
+from ._identity import ByTensor, MemoryStamp
 # (re-exported: bench.py and dist.py use the public names, models, ops, deform and the tests the private ones)
 from .backward_pass import (_alias, _gradient_buffer, bind_gradient_targets, deferred_parameter_gradients,  # noqa: F401
                             late_input_gradients)
@@ -41,7 +41,7 @@ class _Csr:
                  "_deform_tail")      # (geometrics_amd.deform: the rows' entries beyond the table as a second fixed-width table)
 
 
-_csr_cache = {}   # id(adjacency tensor) -> (weakref, version, _Csr)
+_csr_cache = ByTensor()   # adjacency tensor -> its _Csr
 
 
 def _to_csr(dense):
@@ -114,22 +114,21 @@ def csr_from_parts(rowptr, col, val, rowptr_t, col_t, val_t):
 
 def adjacency_csr(adj):
     """CSR + CSR^T (+ ELL tables) of a dense [V,V] adjacency, cached per TENSOR OBJECT and in-place
-    version.  The key is the object's identity guarded by a weak reference -- never the data pointer,
-    which the caching allocator hands to the next adjacency of the same size (auto_encoder.py builds a
-    fresh one per mesh).  Building reads the dense matrix once (one host sync, at first use only)."""
+    version (_identity.ByTensor: never the data pointer, which the caching allocator hands to the next
+    adjacency of the same size -- auto_encoder.py builds a fresh one per mesh).  Building reads the dense
+    matrix once (one host sync, at first use only)."""
     if isinstance(adj, _Csr):
         return adj
     if hasattr(adj, "csr") and isinstance(adj.csr, _Csr):     # a RaggedMeshBatch
         return adj.csr
     if adj.dim() != 2 or adj.shape[0] != adj.shape[1]:
         raise RuntimeError("adjacency must be a square [V,V] tensor, got %s" % (tuple(adj.shape),))
-    key = id(adj)
-    hit = _csr_cache.get(key)
-    if hit is not None and hit[0]() is adj and hit[1] == adj._version:
-        if not hasattr(hit[2], "ell_w"):          # handed over by register_csr: its derived tables are made at first use
+    hit = _csr_cache.get(adj)
+    if hit is not None:
+        if not hasattr(hit, "ell_w"):          # handed over by register_csr: its derived tables are made at first use
             with torch.no_grad():
-                _finish_csr(hit[2])
-        return hit[2]
+                _finish_csr(hit)
+        return hit
     if not adj.is_cuda:
         raise RuntimeError("adjacency must live on a HIP device; geometrics_amd has no CPU path")
     with torch.no_grad():
@@ -138,8 +137,7 @@ def adjacency_csr(adj):
         c.rowptr, c.col, c.val = _to_csr(dense)
         c.rowptr_t, c.col_t, c.val_t = _to_csr(dense.t())
         _finish_csr(c)
-    _csr_cache[key] = (weakref.ref(adj, lambda _ref, k=key: _csr_cache.pop(k, None)), adj._version, c)
-    return c
+    return _csr_cache.put(c, adj)
 
 
 def register_csr(adj, csr):
@@ -147,23 +145,18 @@ def register_csr(adj, csr):
     matrix FROM the CSR): adjacency_csr(adj) then returns this object instead of reading the matrix back through nonzero().
     csr: a _Csr (csr_from_parts), or the six arrays of csr_from_parts as a tuple -- registering those reads nothing on the
     host; the derived tables (_finish_csr: the ELL width is a host decision) are made when the object is first asked for.
-    Same cache policy as adjacency_csr (tensor object + in-place version).  Returns the object."""
+    Same cache as adjacency_csr (_identity.ByTensor: tensor object + in-place version).  Returns the object."""
     if not isinstance(csr, _Csr):
         c = _Csr()
         c.rowptr, c.col, c.val, c.rowptr_t, c.col_t, c.val_t = csr
         csr = c
-    key = id(adj)
-    _csr_cache[key] = (weakref.ref(adj, lambda _ref, k=key: _csr_cache.pop(k, None)), adj._version, csr)
-    return csr
+    return _csr_cache.put(csr, adj)
 
 
 def registered_csr(adj):
     """The cached CSR of `adj` as it stands -- possibly without its derived tables (only rowptr / col / val and their
     transposes are promised) -- or None: for callers that need the pattern alone and must not read the host."""
-    hit = _csr_cache.get(id(adj))
-    if hit is not None and hit[0]() is adj and hit[1] == adj._version:
-        return hit[2]
-    return None
+    return _csr_cache.get(adj)
 
 
 # ------------------------------------------------------- fused aggregation ----
@@ -293,28 +286,22 @@ class _StackLink:
     backward) computes this boundary's input gradient with it and leaves it in `dx`, stamped with the address of the support
     gradient it was computed from -- the boundary uses it only when that very tensor arrives as its incoming gradient (an
     engine that summed several consumers' gradients hands over another tensor, and the product is computed here as usual)."""
-    __slots__ = ("wt", "dx", "g_ref", "g_version", "wanted")
+    __slots__ = ("wt", "dx", "g_ref", "wanted")
 
     def __init__(self):
         self.wt = self.dx = self.g_ref = None
-        self.g_version = -1
         self.wanted = False
 
     def stamp(self, g):
-        """`dx` was computed from the support gradient `g`: remember the tensor itself (held, so that its address cannot be
-        recycled) and its version counter (an engine that accumulates another consumer's gradient IN PLACE keeps the address
-        and bumps the version)."""
-        self.g_ref, self.g_version = g, g._version
+        """`dx` was computed from the support gradient `g` as it is now (_identity.MemoryStamp: an engine that accumulates
+        another consumer's gradient IN PLACE keeps the address and bumps the version)."""
+        self.g_ref = MemoryStamp(g)
 
     def claim_dx(self, g):
-        """The precomputed input gradient if `g` is the very tensor (same memory, same version) it was computed from."""
-        dx, ref, ver = self.dx, self.g_ref, self.g_version
+        """The precomputed input gradient if `g` is the very memory (at the same version) it was computed from; one shot."""
+        dx, stamp = self.dx, self.g_ref
         self.dx = self.g_ref = None
-        if dx is None or ref is None:
-            return None
-        same = (g.data_ptr() == ref.data_ptr() and g.shape.numel() == ref.shape.numel() and g._version == ver
-                and ref._version == ver)
-        return dx if same else None
+        return dx if dx is not None and stamp is not None and stamp.matches(g) else None
 
     def take_dx(self, b, nv):
         self.dx = torch.empty(b, nv, self.wt.shape[1], dtype=torch.float32, device=self.wt.device)

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from . import chamfer_distance as _chamfer
+from ._identity import ByTensor, MemoryStamp
 from .chamfer_distance import chamfer_nn
 from .tri_distance import face_order, faces_in_order, morton_order, tri_distance_indexed
 
@@ -124,16 +125,15 @@ class PointToTriangleSum(torch.autograd.Function):
         return None, grad_verts, None, None, None
 
 
-_vf_cache = {}   # id(faces) -> (weakref, version, nv, vf_ptr, vf_item)
+_vf_cache = ByTensor()   # faces (extra: the vertex count) -> (vf_ptr, vf_item)
 
 
 def vertex_faces(faces, nv):
     """Static CSR vertex -> incident (face << 2 | corner), ascending per vertex: what the gather backward walks.
-    Built once per faces TENSOR OBJECT / in-place version / vertex count (same caching policy as the adjacency CSR)."""
-    key = id(faces)
-    hit = _vf_cache.get(key)
-    if hit is not None and hit[0]() is faces and hit[1] == faces._version and hit[2] == nv:
-        return hit[3], hit[4]
+    Built once per faces TENSOR OBJECT / in-place version / vertex count (_identity.ByTensor, as the adjacency CSR is)."""
+    hit = _vf_cache.get(faces, extra=nv)
+    if hit is not None:
+        return hit
     with torch.no_grad():
         flat = faces.reshape(-1)
         if flat.numel() and (int(flat.min()) < 0 or int(flat.max()) >= nv):
@@ -143,8 +143,7 @@ def vertex_faces(faces, nv):
         vf_ptr = torch.zeros(nv + 1, dtype=torch.int64, device=faces.device)
         vf_ptr[1:] = torch.cumsum(torch.bincount(flat, minlength=nv), 0)
         vf_ptr = vf_ptr.to(torch.int32).contiguous()
-    _vf_cache[key] = (weakref.ref(faces, lambda _ref, k=key: _vf_cache.pop(k, None)), faces._version, nv, vf_ptr, vf_item)
-    return vf_ptr, vf_item
+    return _vf_cache.put((vf_ptr, vf_item), faces, extra=nv)
 
 
 class GtIndex:
@@ -164,14 +163,13 @@ class GtIndex:
         self.order = order
         self.index = torch.empty(max(int(_lib.lib().geom_nn_cull_index_floats(b, n)), 4), dtype=torch.float32, device=gt.device)
         self.shape, self.device = (b, n), gt.device
-        self.source = (gt.data_ptr(), gt._version)
-        # the index HOLDS the cloud's memory: while it lives the allocator cannot hand that address to another cloud (a
+        # the stamp HOLDS the cloud's memory: while the index lives the allocator cannot hand that address to another cloud (a
         # recycled address at version 0 would pass the check below and be scanned through the OLD cloud's index)
-        self._cloud = gt
+        self.source = MemoryStamp(gt)
         _lib.call("geom_nn_cull_index_f32", b, n, gt, order, self.index)
 
     def check(self, gt):
-        if tuple(gt.shape[:2]) != self.shape or gt.device != self.device or (gt.data_ptr(), gt._version) != self.source:
+        if tuple(gt.shape[:2]) != self.shape or gt.device != self.device or not self.source.matches(gt):
             raise RuntimeError("this GtIndex was built for another ground-truth tensor (or the tensor was modified since)")
 
 
@@ -558,8 +556,8 @@ _headroom = {}     # storage address of a wide buffer -> its _WideBuffer
 
 class _WideBuffer:
     """What the registry knows of one wide buffer: `ref`, a weak reference to it (the entry goes when the buffer does); `free`,
-    the columns still free in front of the view handed out; `placed`, {first column: stamp of a tensor the pooling launch already
-    copied there}."""
+    the columns still free in front of the view handed out; `placed`, {first column: (stamp, width) of a tensor the pooling launch
+    already copied there} -- the stamps hold those tensors' memory until the wide buffer dies (_identity.MemoryStamp)."""
     __slots__ = ("ref", "free", "placed")
 
     def __init__(self, ref, free, placed):
@@ -569,23 +567,19 @@ class _WideBuffer:
     def buf(self):
         return self.ref()
 
-    @staticmethod
-    def stamp(t):
-        return (t.data_ptr(), t._version, t.shape[2])
-
     def place(self, col, t):
         """Note that columns [col, col + width) are going to hold `t` as it is now."""
-        self.placed[col] = self.stamp(t)
+        self.placed[col] = (MemoryStamp(t), t.shape[2])
 
     def holds(self, col, t):
         """Whether columns [col, col + width) already hold `t` (PoolFeatures(fronts=...) copied it there)."""
-        return self.placed.get(col) == self.stamp(t)
+        hit = self.placed.get(col)
+        return hit is not None and hit[1] == t.shape[2] and hit[0].matches(t)
 
 
 def _register_headroom(buf, free):
     """Enter the wide buffer `buf` with `free` columns in front of the view handed out, or shrink its free columns (what has been
     placed in it stays known).  Returns its record."""
-    import weakref
     key = buf.untyped_storage().data_ptr()
     old = _headroom.get(key)
     placed = old.placed if old is not None and old.buf is buf else {}      # (a recycled address: another buffer's record)

@@ -12,13 +12,12 @@ the result.  `tri_distance_indexed` derives a k-d tree leaf order of the face ce
 (`face_order`, cached on the tensor's identity -- mesh deformation keeps a topology's order coherent);
 `morton_order` is the device-only alternative.
 """
-import weakref
-
 import torch
 
 from .. import _lib
+from .._identity import ByTensor
 
-_order_cache = {}   # id(faces) -> (weakref, version, order)
+_order_cache = ByTensor()   # faces -> [visiting order, the faces in that order (made when first asked for)]
 
 
 def morton_order(centroids):
@@ -66,17 +65,15 @@ def kd_order(centroids, leaf=16):
 
 def face_order(verts, faces):
     """Coherent visiting order of `faces` [F,3], from the centroids of the first mesh of `verts` [B,V,3] the
-    face list is seen with; cached per faces TENSOR OBJECT and in-place version (same policy as the CSR cache)."""
-    key = id(faces)
-    hit = _order_cache.get(key)
-    if hit is not None and hit[0]() is faces and hit[1] == faces._version:
-        return hit[2]
+    face list is seen with; cached per faces TENSOR OBJECT and in-place version (_identity.ByTensor)."""
+    hit = _order_cache.get(faces)
+    if hit is not None:
+        return hit[0]
     if verts.shape[0] == 0 or faces.shape[0] == 0:
         return None
     with torch.no_grad():
         order = kd_order(verts[0][faces].mean(dim=1))
-    _order_cache[key] = (weakref.ref(faces, lambda _ref, k=key: _order_cache.pop(k, None)), faces._version, order)
-    return order
+    return _order_cache.put([order, None], faces)[0]
 
 
 def faces_in_order(verts, faces):
@@ -85,11 +82,10 @@ def faces_in_order(verts, faces):
     order = face_order(verts, faces)
     if order is None:
         return None
-    hit = _order_cache.get(id(faces))
-    if len(hit) == 3:
-        hit = hit + (faces[order.long()].to(torch.int32).contiguous(),)
-        _order_cache[id(faces)] = hit
-    return hit[3]
+    hit = _order_cache.get(faces)
+    if hit[1] is None:
+        hit[1] = faces[order.long()].to(torch.int32).contiguous()
+    return hit[1]
 
 
 # ---- the reference-shaped entry (tri1 / tri2 / tri3 corner tensors, tri_distance.py:9-43): no face list to key a cache on --

@@ -16,6 +16,7 @@ import math
 import torch
 
 from . import ops
+from ._identity import ByTensor
 from .encoder import latent_loss  # noqa: F401  (GEOMetrics.py:165-171 on two kernels, no host read)
 from .chamfer_distance import ChamferDistance
 from .tri_distance import TriDistance
@@ -84,24 +85,19 @@ def calc_face_list(faces):
     return torch.stack((torch.div(partner, 3, rounding_mode="floor"), partner % 3, own), dim=1).reshape(nf, 3, 3).contiguous()
 
 
-_active_cache = {}   # id(face_list) -> (weakref, version, faces weakref, faces version, active faces)
+_active_cache = ByTensor()   # (face_list, faces) -> the active faces
 
 
 def active_faces(info):
     """info['faces'][info['face_list'][:, 0, 2]]: the faces the losses run on after a split (the reference's calc_edge and its
-    driver take them the same way, old_GEOMetrics/utils.py:674-677).  Cached per face_list TENSOR OBJECT (and in-place version,
-    and the faces it was taken from), as ops.vertex_faces caches: every loss call on a split mesh passes the same tensor as
-    'faces', so the tables keyed on that tensor are built once."""
-    import weakref
+    driver take them the same way, old_GEOMetrics/utils.py:674-677).  Cached per face_list and faces TENSOR OBJECTS and their
+    in-place versions (_identity.ByTensor): every loss call on a split mesh passes the same tensor as 'faces', so the tables
+    keyed on that tensor are built once."""
     face_list, faces = info["face_list"], info["faces"]
-    key = id(face_list)
-    hit = _active_cache.get(key)
-    if hit is not None and hit[0]() is face_list and hit[1] == face_list._version and hit[2]() is faces and hit[3] == faces._version:
-        return hit[4]
-    with torch.no_grad():
-        active = faces.index_select(0, face_list[:, 0, 2]).contiguous()
-    _active_cache[key] = (weakref.ref(face_list, lambda _ref, k=key: _active_cache.pop(k, None)), face_list._version,
-                          weakref.ref(faces), faces._version, active)
+    active = _active_cache.get(face_list, faces)
+    if active is None:
+        with torch.no_grad():
+            active = _active_cache.put(faces.index_select(0, face_list[:, 0, 2]).contiguous(), face_list, faces)
     return active
 
 

@@ -295,6 +295,9 @@ def test_new_entry_points_reject_bad_arguments_without_a_gpu():
     assert L.geom_adam_step_f32(1, None, None, None, None, None, 1e-3, .9, .999, 1e-8, 1.0, None, 1, None) == -1
     assert L.geom_adam_step_f32(0, None, None, None, None, None, 1e-3, .9, .999, 1e-8, 1.0, None, 1, None) == 0
     assert L.geom_chamfer_nn_f32(1, 4, p, 4, p, p, p, p, p, _lib.FLAG_NN_FMA | _lib.FLAG_REF_TAIL_TRUNC, None) == -1
+    if not torch.cuda.is_available():      # an unknown device (csrc/device_facts.h): no chain launch fits, grids are sized for 256 CUs
+        assert L.geom_deform_chain_fits(482) == 0
+        assert L.geom_dense_bwd_weight_workspace_floats(20496, 963, 192) == 4723392
 
 
 def test_dense_plan_routes_each_product_by_shape():

@@ -384,6 +384,35 @@ def test_block_input_assembled_in_place_equals_the_concatenations(gpu):
     assert all(float((x.grad - y.grad).abs().max()) <= 1e-5 * float(y.grad.abs().max()) for x, y in zip(ms, ms2))
 
 
+def test_a_front_placed_by_the_pooling_launch_is_not_mistaken_for_the_next_tensor_at_its_address(gpu):
+    """A front the pooling launch copied into the wide buffer is remembered by its memory; once that tensor is dropped, the
+    allocator hands its block to the next tensor of the same shape (at version 0, as the old one was).  The concatenation
+    must then copy the NEW tensor's columns -- the record holds the placed front's memory, so the address cannot come back
+    while the wide buffer lives.  Values only: whether the allocator would have reused the block is not this test's business."""
+    torch.manual_seed(15)
+    maps = [torch.randn(2, 4, 8, 8, device=gpu), torch.randn(2, 4, 4, 4, device=gpu)]
+    cams = torch.tensor([[30.0, 20.0, 1.2], [37.0, 20.0, 1.2]], device=gpu)
+    pos = torch.randn(2, 12, 3, device=gpu)
+    feat = torch.randn(2, 12, 5, device=gpu)
+    pooled = utils.batched_pooling(maps, pos, cams, headroom=8, fronts=(pos, feat))
+    del feat
+    feat2 = torch.randn(2, 12, 5, device=gpu)
+    out = utils.concat_features(feat2, pooled)
+    plain = utils.batched_pooling(maps, pos, cams)
+    assert out.shape == (2, 12, 13)
+    assert torch.equal(out[..., :5], feat2)
+    assert torch.equal(out[..., 5:], plain)
+    # the block's own concatenation (models._InputTap) with the 3-column front
+    front = torch.randn(2, 12, 3, device=gpu)
+    pooled = utils.batched_pooling(maps, pos, cams, headroom=3, fronts=(front,))
+    del front
+    front2 = torch.randn(2, 12, 3, device=gpu)
+    full, lead = models._InputTap.apply(front2, pooled, 3)
+    assert full.shape == (2, 12, 11)
+    assert torch.equal(full[..., :3], front2) and torch.equal(lead, front2)
+    assert torch.equal(full[..., 3:], plain)
+
+
 def _block_step(block, feats, pooled, adj):
     for p in block.parameters():
         p.grad = None
