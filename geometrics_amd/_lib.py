@@ -38,6 +38,8 @@ DEFORM_WIDE_MAX_B = _C["DEFORM_WIDE_MAX_B"]
 DeformFwd = _header.STRUCTS["geom_deform_fwd"]
 DeformBwd = _header.STRUCTS["geom_deform_bwd"]
 DeformInfer = _header.STRUCTS["geom_deform_infer"]
+DeformPlainFwd = _header.STRUCTS["geom_deform_plain_fwd"]
+DeformPlainBwd = _header.STRUCTS["geom_deform_plain_bwd"]
 SurfaceCull = _header.STRUCTS["geom_surface_cull"]
 SurfaceTail = _header.STRUCTS["geom_surface_tail"]
 FaceSplit = _header.STRUCTS["geom_face_split"]

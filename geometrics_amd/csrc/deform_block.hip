@@ -34,6 +34,8 @@
 // need the slice's registers); the eval body walks a per-row table and, once the slice is live, gathers in two rounds of four.
 // The chain kernels sit at 256 VGPRs already (tools/kernel_resources.sh): one body templated over the tile count, or the eval
 // table walk folded into db_aggregate, would trade these orders for one that fits none of them.
+// The BatchNorm-free block of the old driver (dp_fwd_row_block / dp_bwd_row_block, geom_deform_plain_{fwd,bwd}_f32) takes the
+// eval body's tiling and the same steps, with a CSR overflow list of any length behind the 8-wide table.
 #include "mfma_tiles.h"
 #include "device_facts.h"
 
@@ -947,6 +949,272 @@ __global__ __launch_bounds__(DB_THREADS, 2) void di_fwd_kernel(geom_deform_infer
     for (int i = 1; i < count; ++i) di_row_block<PRODUCT, false>(a, first + i, lds, bw);
 }
 
+// ---- the BatchNorm-free block on split meshes (geom_deform_plain_{fwd,bwd}_f32; reference models.py:138-201 on
+// old_GEOMetrics/layers.py:106-149): the old driver runs it on ONE unbatched mesh whose vertex count grows with every face
+// split and whose rows get long (a pole of 65 entries after one split of 482.obj).  No statistic ties the rows of a vertex
+// together, so tiling, grid and schedule are the eval launch's (di_row_block / di_fwd_kernel: 16 consecutive rows of [b * nv],
+// <= DI_WGS workgroups with q or q + 1 row-blocks each behind one register-resident weight slice).  What differs:
+//   * no BatchNorm step (absent, not an identity map): X' = relu?(Z) (+ residual, * scale);
+//   * a row's entries beyond the 8-wide table come from a CSR overflow list of ANY length, walked four entries per round trip
+//     by the row's own 16 lanes up to the row's own end (the rows of a wave have different lengths);
+//   * a backward launch: aggregation backward of the layer above + its input-gradient product + this layer's mask, with the
+//     bias-gradient (and head-weight) partials per ROW-BLOCK -- whichever workgroup runs a row-block writes the same partial row.
+
+// The aggregated float4 of a thread's row v: table slots, then the overflow entries, in CSR order (zn_gcn.hip's order and
+// arithmetic).  ROUND table rows are in flight at once; LOAD_SLICE: the wave's weight slice is requested behind the first round.
+template <bool LOAD_SLICE, int ROUND>
+__device__ __forceinline__ float4 dp_aggregate(__amdgpu_buffer_rsrc_t r_src, bool on, unsigned rowbase, int v, int c0, const int *ell_col,
+                                               const float *ell_val, const int *over_ptr, const int *over_col, const float *over_val,
+                                               DbSlice &bw, const float *packed, int wave, int lane)
+{
+    int nb[DB_W];
+    float wv[DB_W];
+    {
+        const int4 ci0 = *reinterpret_cast<const int4 *>(ell_col + (size_t)v * DB_W), ci1 = *reinterpret_cast<const int4 *>(ell_col + (size_t)v * DB_W + 4);
+        const float4 wi0 = *reinterpret_cast<const float4 *>(ell_val + (size_t)v * DB_W), wi1 = *reinterpret_cast<const float4 *>(ell_val + (size_t)v * DB_W + 4);
+        nb[0] = ci0.x, nb[1] = ci0.y, nb[2] = ci0.z, nb[3] = ci0.w, nb[4] = ci1.x, nb[5] = ci1.y, nb[6] = ci1.z, nb[7] = ci1.w;
+        wv[0] = wi0.x, wv[1] = wi0.y, wv[2] = wi0.z, wv[3] = wi0.w, wv[4] = wi1.x, wv[5] = wi1.y, wv[6] = wi1.z, wv[7] = wi1.w;
+    }
+    int e = 0, end = 0; // the row's overflow entries [e, end)
+    if (over_ptr && on) e = over_ptr[v], end = over_ptr[v + 1];
+    float4 facc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int n0 = 0; n0 < DB_W; n0 += ROUND) {
+        float4 sv[ROUND];
+#pragma unroll
+        for (int n = 0; n < ROUND; ++n)
+            sv[n] = ld4(r_src, on ? rowbase + (unsigned)(nb[n0 + n] >= 0 ? nb[n0 + n] : v) * (DB_C * 4) + 4 * c0 : OOB);
+        if (LOAD_SLICE && n0 == 0) db_load_slice(bw, packed, wave, lane);
+#pragma unroll
+        for (int n = 0; n < ROUND; ++n) {
+            if (nb[n0 + n] >= 0) { // ELL order == CSR order of the row
+                facc.x += wv[n0 + n] * sv[n].x, facc.y += wv[n0 + n] * sv[n].y, facc.z += wv[n0 + n] * sv[n].z, facc.w += wv[n0 + n] * sv[n].w;
+            }
+        }
+    }
+    for (; e < end; e += 4) { // (a group of 16 lanes leaves at its own row's end)
+        int tc[4];
+        float tw[4];
+        float4 tv[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int at = e + t < end ? e + t : end - 1;
+            tc[t] = over_col[at], tw[t] = over_val[at];
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) tv[t] = ld4(r_src, e + t < end ? rowbase + (unsigned)tc[t] * (DB_C * 4) + 4 * c0 : OOB);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (e + t < end) {
+                facc.x += tw[t] * tv[t].x, facc.y += tw[t] * tv[t].y, facc.z += tw[t] * tv[t].z, facc.w += tw[t] * tv[t].w;
+            }
+        }
+    }
+    return facc;
+}
+
+// relu?(Z) (+ residual, * scale) of one element; `on` = false: a row beyond the last, zero
+__device__ __forceinline__ float dp_act_one(const geom_deform_plain_fwd &a, float zz, float r, bool on)
+{
+    float y = zz;
+    if (a.relu) y = y > 0.f ? y : 0.f;
+    if (a.res) y = (r + y) * a.scale;
+    return on ? y : 0.f;
+}
+
+template <bool PRODUCT, bool LOAD_SLICE>
+__device__ __forceinline__ void dp_fwd_row_block(const geom_deform_plain_fwd &a, const int rb, float *lds, DbSlice &bw)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = lane & 15, g = lane >> 4; // matrix-core coordinates
+    const int rl = tid >> 4, j = tid & 15;  // row of the block and float4 group of the gather thread
+    const int c0 = 4 * j;
+    const int rows = a.b * a.nv;
+    const int r = rb * 16 + rl;
+    const bool on = r < rows;
+    const int mesh = on ? r / a.nv : 0, v = on ? r - mesh * a.nv : 0;
+    const int64_t op_bytes = (int64_t)rows * DB_C * 4;
+    const __amdgpu_buffer_rsrc_t r_src = rsrc(a.s_in, op_bytes);
+    const unsigned rowbase = (unsigned)mesh * (unsigned)a.nv * (DB_C * 4);
+    const unsigned own_off = on ? (unsigned)r * (DB_C * 4) + 4 * c0 : OOB;
+    float4 bias4[3], rv[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) bias4[i] = db_bias4(a, c0, i), rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (a.res) {
+        const __amdgpu_buffer_rsrc_t r_res = rsrc(a.res, ((int64_t)rows - 1) * a.res_ld * 4 + DB_C * 4);
+        const unsigned roff = (unsigned)r * (unsigned)a.res_ld * 4u + 4 * c0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) rv[i] = ld4(r_res, on ? roff + 4 * DB_K * i : OOB);
+    }
+    // (a later row-block of the workgroup holds the slice already: its table rows go in two rounds of four, as di_row_block's)
+    constexpr int ROUND = LOAD_SLICE || !PRODUCT ? DB_W : DB_W / 2;
+    float4 z[3];
+#pragma unroll
+    for (int i = 1; i < 3; ++i) z[i] = ld4(r_src, db_own(own_off, i));
+    z[0] = dp_aggregate<LOAD_SLICE, ROUND>(r_src, on, rowbase, v, c0, a.ell_col, a.ell_val, a.over_ptr, a.over_col, a.over_val, bw,
+                                           a.w_next, wave, lane);
+    db_add_bias(z, bias4);
+    float4 xo[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        xo[i] = make_float4(dp_act_one(a, z[i].x, rv[i].x, on), dp_act_one(a, z[i].y, rv[i].y, on), dp_act_one(a, z[i].z, rv[i].z, on),
+                            dp_act_one(a, z[i].w, rv[i].w, on));
+    if (a.z_out) {
+        const __amdgpu_buffer_rsrc_t r_z = rsrc(a.z_out, op_bytes);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) st4(r_z, db_own(own_off, i), z[i]);
+    }
+    if (a.x_out) {
+        const __amdgpu_buffer_rsrc_t r_x = rsrc(a.x_out, op_bytes);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) st4(r_x, db_own(own_off, i), xo[i]);
+    }
+    if (!PRODUCT) {
+        if (a.w_head) { // the coordinate head's raw support s_head[row] = X'[row] . W_head
+            float h[3];
+            db_head_fwd(xo, a.w_head, c0, h);
+            if (j == 0 && on) {
+                float *dst = a.s_head + (size_t)r * 3;
+                dst[0] = h[0], dst[1] = h[1], dst[2] = h[2];
+            }
+        }
+        return;
+    }
+    db_to_panel(lds, rl, c0, xo); // (rows beyond the last are zero rows of the panel)
+    __syncthreads();
+    float *stage = lds + RB_PANEL;
+    db_product(bw, lds, stage, wave, x, g);
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t r_s = rsrc(a.s_out, op_bytes);
+    db_store_tile<false>(stage, r_s, [&](int rr) {
+        const int row = rb * 16 + rr;
+        return row < rows ? (unsigned)row * (DB_C * 4) : OOB;
+    });
+}
+
+// logical workgroup -> its run of row-blocks [first, first + count): di_fwd_kernel's dealing
+__device__ __forceinline__ bool dp_run(int nrb, int nwg, int per_xcd, int &first, int &count)
+{
+    const int lw = geom::xcd_run_item(blockIdx.x, per_xcd);
+    if (lw >= nwg) return false;
+    const int q = nrb / nwg, rem = nrb - q * nwg;
+    first = lw * q + (lw < rem ? lw : rem), count = q + (lw < rem ? 1 : 0);
+    return true;
+}
+
+template <bool PRODUCT>
+__global__ __launch_bounds__(DB_THREADS, 2) void dp_fwd_kernel(geom_deform_plain_fwd a, int nrb, int nwg, int per_xcd)
+{
+    __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST];
+    int first, count;
+    if (!dp_run(nrb, nwg, per_xcd, first, count)) return;
+    DbSlice bw;
+    dp_fwd_row_block<PRODUCT, PRODUCT>(a, first, lds, bw);
+    for (int i = 1; i < count; ++i) dp_fwd_row_block<PRODUCT, false>(a, first + i, lds, bw);
+}
+
+template <bool PRODUCT, bool LOAD_SLICE>
+__device__ __forceinline__ void dp_bwd_row_block(const geom_deform_plain_bwd &a, const int rb, float *lds, DbSlice &bw)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = lane & 15, g = lane >> 4;
+    const int rl = tid >> 4, j = tid & 15;
+    const int c0 = 4 * j;
+    const int rows = a.b * a.nv;
+    const int r = rb * 16 + rl;
+    const bool on = r < rows;
+    const int mesh = on ? r / a.nv : 0, v = on ? r - mesh * a.nv : 0;
+    const int64_t op_bytes = (int64_t)rows * DB_C * 4;
+    const unsigned rowbase = (unsigned)mesh * (unsigned)a.nv * (DB_C * 4);
+    const unsigned own_off = on ? (unsigned)r * (DB_C * 4) + 4 * c0 : OOB;
+    float *stage = lds + RB_PANEL;
+    float4 go[3];
+    if (PRODUCT) {
+        // ---- aggregation backward of the layer above, G = [A^T . dZ_up[:, :64] | dZ_up[:, 64:]], and dX = G . W_up^T
+        const __amdgpu_buffer_rsrc_t r_src = rsrc(a.dz_up, op_bytes), r_ds = rsrc(a.ds_up, op_bytes);
+        constexpr int ROUND = LOAD_SLICE ? DB_W : DB_W / 2;
+        float4 gs[3]; // (stored: the layer above's weight gradient reads it, X^T . G)
+#pragma unroll
+        for (int i = 1; i < 3; ++i) gs[i] = ld4(r_src, db_own(own_off, i));
+        gs[0] = dp_aggregate<LOAD_SLICE, ROUND>(r_src, on, rowbase, v, c0, a.ell_col_t, a.ell_val_t, a.over_ptr_t, a.over_col_t, a.over_val_t,
+                                                bw, a.wt_up, wave, lane);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) st4(r_ds, db_own(own_off, i), gs[i]);
+        db_to_panel(lds, rl, c0, gs); // (rows beyond the last read zeros: zero rows of the tile)
+        __syncthreads();
+        db_product(bw, lds, stage, wave, x, g);
+        __syncthreads();
+        db_load_tile(stage, rl, c0, go);
+    } else {
+        // ---- the top layer: the caller's gradient, and the coordinate head's backward (db_head_bwd_*)
+        const int g_ld = a.g_ld ? a.g_ld : DB_C;
+        const __amdgpu_buffer_rsrc_t r_g = rsrc(a.g, ((int64_t)rows - 1) * g_ld * 4 + DB_C * 4);
+        const unsigned g_off = on ? ((unsigned)r * (unsigned)g_ld + (unsigned)c0) * 4u : OOB;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) go[i] = a.g ? ld4(r_g, db_own(g_off, i)) : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (a.ds_head) {
+            float dsh[3] = {0.f, 0.f, 0.f};
+            if (on) {
+                const float *src = a.ds_head + (size_t)r * 3;
+                dsh[0] = src[0], dsh[1] = src[1], dsh[2] = src[2];
+            }
+            const __amdgpu_buffer_rsrc_t r_xt = rsrc(a.x_top, op_bytes);
+            float *wsum = stage; // [4 waves][192 * 3]
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const float4 xt = a.dw_head ? ld4(r_xt, db_own(own_off, i)) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float xv[4] = {xt.x, xt.y, xt.z, xt.w};
+                float add[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int col = c0 + DB_K * i + e;
+                    add[e] = db_head_bwd_input(dsh, a.w_head, col);
+                    if (a.dw_head) {
+#pragma unroll
+                        for (int o = 0; o < 3; ++o) db_head_bwd_weight_rows(xv[e] * dsh[o], wsum, col, o);
+                    }
+                }
+                go[i].x += add[0], go[i].y += add[1], go[i].z += add[2], go[i].w += add[3];
+            }
+            if (a.dw_head) db_head_bwd_weight_reduce(wsum, a.dw_head, rb); // the ROW-BLOCK's partial
+        }
+    }
+    // ---- this layer: the pending residual gradient, the residual's scale, the ReLU mask (Z > 0: X' loses it under a residual)
+    const int g2_ld = a.g2_ld ? a.g2_ld : DB_C;
+    const __amdgpu_buffer_rsrc_t r_z = rsrc(a.z, op_bytes), r_g2 = rsrc(a.g2, ((int64_t)rows - 1) * g2_ld * 4 + DB_C * 4);
+    const __amdgpu_buffer_rsrc_t r_gr = rsrc(a.grad_res, op_bytes), r_dz = rsrc(a.dz, op_bytes);
+    const unsigned g2_off = on ? ((unsigned)r * (unsigned)g2_ld + (unsigned)c0) * 4u : OOB;
+    float4 dz[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float4 zv = a.relu ? ld4(r_z, db_own(own_off, i)) : make_float4(1.f, 1.f, 1.f, 1.f);
+        const float4 g2v = a.g2 ? ld4(r_g2, db_own(g2_off, i)) : make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 gg = make_float4(go[i].x + g2v.x, go[i].y + g2v.y, go[i].z + g2v.z, go[i].w + g2v.w);
+        if (a.has_res) {
+            gg.x *= a.scale, gg.y *= a.scale, gg.z *= a.scale, gg.w *= a.scale;
+            if (a.grad_res) st4(r_gr, db_own(own_off, i), gg);
+        }
+        dz[i] = make_float4((on && zv.x > 0.f) ? gg.x : 0.f, (on && zv.y > 0.f) ? gg.y : 0.f, (on && zv.z > 0.f) ? gg.z : 0.f,
+                            (on && zv.w > 0.f) ? gg.w : 0.f);
+        st4(r_dz, db_own(own_off, i), dz[i]);
+    }
+    if (a.colsum) db_colsum(dz, stage, a.colsum, rb, c0); // the row-block's partial of this layer's bias gradient
+}
+
+template <bool PRODUCT>
+__global__ __launch_bounds__(DB_THREADS, 2) void dp_bwd_kernel(geom_deform_plain_bwd a, int nrb, int nwg, int per_xcd)
+{
+    __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST];
+    int first, count;
+    if (!dp_run(nrb, nwg, per_xcd, first, count)) return;
+    DbSlice bw;
+    dp_bwd_row_block<PRODUCT, PRODUCT>(a, first, lds, bw);
+    for (int i = 1; i < count; ++i) {
+        __syncthreads(); // (the staging tile: the column sums of the row-block before are read)
+        dp_bwd_row_block<PRODUCT, false>(a, first + i, lds, bw);
+    }
+}
+
 // ---- training batches of 17 .. GEOM_DEFORM_WIDE_MAX_B meshes (geom_deform_layer_wide_{fwd,bwd}_f32): one launch per hidden
 // layer and direction, still one workgroup per VERTEX; the vertex's b rows are T = ceil(b / 16) <= 4 row tiles of the matrix
 // core (tile t, tile row rl = mesh 16 t + rl; rows at or beyond b are zero rows of the panel and store nothing).
@@ -1412,6 +1680,81 @@ extern "C" int geom_deform_infer_fwd_f32(const geom_deform_infer *args, void *st
     if (l.w_next) hipLaunchKernelGGL((di_fwd_kernel<true>), grid, block, 0, s, l, nrb, nwg, per_xcd);
     else hipLaunchKernelGGL((di_fwd_kernel<false>), grid, block, 0, s, l, nrb, nwg, per_xcd);
     return geom::launch_status();
+}
+
+namespace {
+// what the two plain entry points ask alike: the shape, and a table with its values / an overflow list with all three arrays
+bool dp_shape_and_tables_ok(int b, int nv, int c, int k, const int *ell_col, const float *ell_val, const int *over_ptr, const int *over_col,
+                            const float *over_val)
+{
+    if (b < 1 || nv < 1 || c != DB_C || k != DB_K) return false;
+    if ((int64_t)b * nv * DB_C >= (1LL << 29)) return false; // 32-bit byte offsets
+    if ((ell_col != nullptr) != (ell_val != nullptr)) return false;
+    if ((over_col || over_val) && !over_ptr) return false;
+    if (over_ptr && (!over_col || !over_val)) return false;
+    return db_aligned16(ell_col) && db_aligned16(ell_val) && !((uintptr_t)over_ptr & 3) && !((uintptr_t)over_col & 3) && !((uintptr_t)over_val & 3);
+}
+// a row pitch in floats (0 = 192) of an operand read in place
+bool dp_pitch_ok(const void *p, int ld, int b, int nv)
+{
+    if (ld && ld < DB_C) return false;
+    return !((uintptr_t)p & 3) && (int64_t)b * nv * (ld ? ld : DB_C) < (1LL << 29);
+}
+template <typename Args, typename Launch>
+int dp_launch(const Args &l, Launch launch)
+{
+    const int nrb = (l.b * l.nv + 15) / 16;
+    const int nwg = nrb < DI_WGS ? nrb : DI_WGS, per_xcd = (nwg + 7) / 8;
+    launch(dim3(8 * per_xcd), dim3(DB_THREADS), nrb, nwg, per_xcd);
+    return geom::launch_status();
+}
+} // namespace
+
+// One hidden layer of the BatchNorm-free block, forward (see dp_fwd_row_block).  Every invalid argument is GEOM_EINVAL, decided
+// on the host before anything is enqueued.
+extern "C" int geom_deform_plain_fwd_f32(const geom_deform_plain_fwd *args, void *stream)
+{
+    if (!args) return GEOM_EINVAL;
+    geom_deform_plain_fwd l = *args;
+    if (!dp_shape_and_tables_ok(l.b, l.nv, l.c, l.k, l.ell_col, l.ell_val, l.over_ptr, l.over_col, l.over_val)) return GEOM_EINVAL;
+    if (!l.s_in || !l.ell_col) return GEOM_EINVAL;
+    if ((l.w_next != nullptr) != (l.s_out != nullptr)) return GEOM_EINVAL;
+    if ((l.w_head != nullptr) != (l.s_head != nullptr) || (l.w_head && l.w_next)) return GEOM_EINVAL; // the head rides without a product
+    if (!l.z_out && !l.x_out && !l.s_out && !l.s_head) return GEOM_EINVAL;                            // nothing to write
+    if (l.res && (l.res_ld < DB_C || !dp_pitch_ok(l.res, l.res_ld, l.b, l.nv))) return GEOM_EINVAL;
+    if (!db_aligned16(l.s_in) || !db_aligned16(l.bias) || !db_aligned16(l.z_out) || !db_aligned16(l.x_out) || !db_aligned16(l.s_out) ||
+        !db_aligned16(l.w_next) || ((uintptr_t)l.w_head & 3) || ((uintptr_t)l.s_head & 3))
+        return GEOM_EINVAL;
+    if (!l.res) l.scale = 1.f;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dp_launch(l, [&](dim3 grid, dim3 block, int nrb, int nwg, int per_xcd) {
+        if (l.w_next) hipLaunchKernelGGL((dp_fwd_kernel<true>), grid, block, 0, s, l, nrb, nwg, per_xcd);
+        else hipLaunchKernelGGL((dp_fwd_kernel<false>), grid, block, 0, s, l, nrb, nwg, per_xcd);
+    });
+}
+
+// ... and backward (see dp_bwd_row_block): with dz_up the aggregation backward and input-gradient product of the layer above,
+// without it the top layer (the caller's gradient, the coordinate head).
+extern "C" int geom_deform_plain_bwd_f32(const geom_deform_plain_bwd *args, void *stream)
+{
+    if (!args) return GEOM_EINVAL;
+    geom_deform_plain_bwd l = *args;
+    if (!dp_shape_and_tables_ok(l.b, l.nv, l.c, l.k, l.ell_col_t, l.ell_val_t, l.over_ptr_t, l.over_col_t, l.over_val_t)) return GEOM_EINVAL;
+    if (!l.dz || (l.relu && !l.z)) return GEOM_EINVAL;
+    const bool product = l.dz_up != nullptr;
+    if (product ? (!l.ell_col_t || !l.ds_up || !l.wt_up || l.g) : (l.ds_up || l.wt_up || (!l.g && !l.ds_head))) return GEOM_EINVAL;
+    if (l.ds_head ? (product || !l.w_head || (l.dw_head && !l.x_top)) : (l.dw_head != nullptr)) return GEOM_EINVAL;
+    if (!dp_pitch_ok(l.g, l.g_ld, l.b, l.nv) || !dp_pitch_ok(l.g2, l.g2_ld, l.b, l.nv)) return GEOM_EINVAL;
+    if (!db_aligned16(l.dz_up) || !db_aligned16(l.ds_up) || !db_aligned16(l.wt_up) || !db_aligned16(l.z) || !db_aligned16(l.grad_res) ||
+        !db_aligned16(l.dz) || !db_aligned16(l.colsum) || !db_aligned16(l.x_top) || !db_aligned16(l.dw_head) || ((uintptr_t)l.ds_head & 3) ||
+        ((uintptr_t)l.w_head & 3))
+        return GEOM_EINVAL;
+    if (!l.has_res) l.scale = 1.f;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dp_launch(l, [&](dim3 grid, dim3 block, int nrb, int nwg, int per_xcd) {
+        if (product) hipLaunchKernelGGL((dp_bwd_kernel<true>), grid, block, 0, s, l, nrb, nwg, per_xcd);
+        else hipLaunchKernelGGL((dp_bwd_kernel<false>), grid, block, 0, s, l, nrb, nwg, per_xcd);
+    });
 }
 
 // fwd[l] / bwd[l] (each count x 36 864 floats, either may be NULL) = the register-slice order of w[l] / w[l]^T that

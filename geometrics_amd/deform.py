@@ -31,6 +31,9 @@ separate operators above 16 meshes until the route has been timed against them.
 Eval mode under no_grad (`serves_inference`, `inference_chain`): BatchNorm on the running statistics is a per-vertex affine map,
 so the layer launch (geom_deform_infer_fwd_f32) tiles 16 consecutive rows of the flattened [B * V] rows instead of a vertex's
 batch rows -- any batch, no cross-workgroup waits, nothing written to the BatchNorm state.
+
+The BatchNorm-free block of the old driver (models.MeshDeformationBlock: `serves_plain`, `_PlainChain`, at the end of this
+file): the same row tiling with a training backward (geom_deform_plain_{fwd,bwd}_f32), rows of any length -- split meshes.
 """
 import collections
 import ctypes
@@ -510,3 +513,190 @@ def hidden_chain(block, s1, lead, csr, head=None):
         return _HiddenChain.apply(s1, lead, csr, stats, momentum, eps, None, *params) + (None,)
     feats, s_head = _HiddenChain.apply(s1, lead, csr, stats, momentum, eps, head.weight1, *params)
     return feats, feats, s_head
+
+
+# ---- the BatchNorm-free block of the old driver on split meshes (models.MeshDeformationBlock; reference models.py:138-201) ----
+# One launch per hidden layer and direction (geom_deform_plain_{fwd,bwd}_f32): rows of any length, any vertex count, no
+# condition on the adjacency's table width or symmetry.  ON: one block's eager forward + backward takes 1.59 ms against 3.23
+# (482 vertices) and 1.20 ms against 2.61 (1442 vertices after a split of every face) for the separate operators, beyond the
+# run-to-run spread at both (tools/time_plain_block.py, profiles/plain_block.txt); GEOM_DEFORM_PLAIN=0 keeps the separate operators.
+plain = os.environ.get("GEOM_DEFORM_PLAIN", "1") != "0"
+
+
+def plain_layers(block):
+    """gc1..gc13 of a models.MeshDeformationBlock."""
+    return [getattr(block, "gc%d" % i) for i in range(1, LAYERS + 1)]
+
+
+def plain_head(block):
+    """The block's coordinate layer where its product rides in the launches (192 -> 3 with a bias), else None."""
+    head = block.gc15
+    return head if tuple(head.weight1.shape) == (192, 3) and head.bias is not None else None
+
+
+def serves_plain(block, features, pooled, csr):
+    """Whether the launches serve this call of `block` (a models.MeshDeformationBlock), the cheap questions first: the
+    switches, a 192-wide block, fp32 [V,*] inputs on a HIP device with nv * 192 < 2^29 (32-bit byte offsets), and per hidden
+    layer a bias and the 192 widths.  Nothing is asked of the adjacency: any table width, any row length, any pattern."""
+    if not (enabled and plain) or block.hidden != 192:
+        return False
+    if not (torch.is_tensor(features) and torch.is_tensor(pooled) and features.is_cuda and pooled.is_cuda
+            and features.dtype == torch.float32 and pooled.dtype == torch.float32 and features.dim() == 2 and pooled.dim() == 2):
+        return False
+    if features.shape[0] < 1 or features.shape[0] * 192 >= OFFSET_LIMIT:
+        return False
+    for i, gc in enumerate(plain_layers(block)):
+        w = gc.weight1
+        if gc.bias is None or w.dtype != torch.float32 or w.shape[-1] != 192 or (i > 0 and w.shape[-2] != 192):
+            return False
+    return True
+
+
+def plain_tables(csr):
+    """((ell_col, ell_val, over), (ell_col_t, ell_val_t, over_t)) of A and A^T at table width 8 -- layers._to_ell, whatever
+    csr.ell_w is; over = (ptr, col, val) of the rows' entries beyond the table, or None.  Cached on the csr object."""
+    cached = getattr(csr, "_deform_plain", None)
+    if cached is None:
+        with torch.no_grad():
+            cached = (_layers._to_ell(csr.rowptr, csr.col, csr.val, 8), _layers._to_ell(csr.rowptr_t, csr.col_t, csr.val_t, 8))
+        csr._deform_plain = cached
+    return cached
+
+
+def plain_layer_forward(s_in, bias, csr, relu, res, scale, z_out=None, x_out=None, w_next=None, s_out=None, w_head=None, s_head=None):
+    """One forward launch (geom_deform_plain_fwd_f32) over s_in [b,nv,192] or [nv,192]; w_next PACKED (pack_weights()[0][l]);
+    see include/geom_hip.h for the operands."""
+    b, nv = (1, s_in.shape[0]) if s_in.dim() == 2 else s_in.shape[:2]
+    (col, val, over), _ = plain_tables(csr)
+    over = over or (None, None, None)
+    res, res_ld = rows_operand(None if res is None else res.reshape(b, nv, -1), (b, nv, 192), OFFSET_LIMIT)
+    a = _lib.args(_lib.DeformPlainFwd, b, nv, 192, 64, s_in, bias, col, val, over[0], over[1], over[2], int(relu), res, res_ld,
+                  float(scale), z_out, x_out, w_next, s_out, w_head, s_head)
+    _lib.call("geom_deform_plain_fwd_f32", a)
+
+
+def plain_layer_backward(shape, csr, z, relu, has_res, scale, dz, dz_up=None, ds_up=None, wt_up=None, g=None, g2=None, grad_res=None,
+                         colsum=None, ds_head=None, w_head=None, x_top=None, dw_head=None):
+    """One backward launch (geom_deform_plain_bwd_f32) over `shape` = (b, nv, 192); wt_up = the layer above's weight,
+    TRANSPOSED and packed (pack_weights()[1][l]); colsum [ceil(b nv / 16), 192] and dw_head [ceil(b nv / 16), 576]."""
+    b, nv, c = shape
+    _, (col_t, val_t, over_t) = plain_tables(csr)
+    over_t = over_t or (None, None, None)
+    g, g_ld = rows_operand(None if g is None else g.reshape(b, nv, -1), shape, OFFSET_LIMIT)
+    g2, g2_ld = rows_operand(None if g2 is None else g2.reshape(b, nv, -1), shape, OFFSET_LIMIT)
+    product = dz_up is not None
+    a = _lib.args(_lib.DeformPlainBwd, b, nv, c, 64, dz_up, col_t if product else None, val_t if product else None,
+                  over_t[0] if product else None, over_t[1] if product else None, over_t[2] if product else None, ds_up, wt_up,
+                  g, g2, g_ld, g2_ld, z, int(relu), int(has_res), float(scale), grad_res, dz, colsum, ds_head, w_head, x_top, dw_head)
+    _lib.call("geom_deform_plain_bwd_f32", a)
+
+
+class _PlainChain(torch.autograd.Function):
+    """X_14 = the thirteen hidden layers of a models.MeshDeformationBlock applied to S_1 [V,192], and the raw support of its
+    coordinate head: apply(s1, lead, csr, w_head, *biases[13], *weights[12] (gc2..gc13)) -> (features [V,192], s_head [V,3]
+    or a second handle on the features when w_head is None).  _HiddenChain without the BatchNorm: one launch per layer and
+    direction, Z and X' kept for the backward only when a gradient is wanted."""
+
+    @staticmethod
+    def forward(ctx, s1, lead, csr, w_head, *params):
+        L = LAYERS
+        biases, weights = params[:L], params[L:2 * L - 1]
+        s1 = _lib.require(s1, "s1", torch.float32, 2, 192)
+        nv, c = s1.shape
+        if nv != csr.nv:
+            raise RuntimeError("support has %d vertices but the adjacency has %d" % (nv, csr.nv))
+        lead3, _ = rows_operand(lead.unsqueeze(0), (1, nv, c), OFFSET_LIMIT)
+        f32 = dict(dtype=torch.float32, device=s1.device)
+        train = any(ctx.needs_input_grad)
+        # with gradients every layer's Z (the mask: X' loses it under a residual) and X' (the weight gradients) are kept;
+        # without, only what a later launch reads: the outputs a residual taps, in two buffers in turn
+        xs = torch.empty(L, nv, c, **f32) if train else None
+        zs = torch.empty(L, nv, c, **f32) if train else None
+        x_bufs = None if train else (torch.empty(nv, c, **f32), torch.empty(nv, c, **f32))
+        out = xs[L - 1] if train else torch.empty(nv, c, **f32)
+        s_buf = (torch.empty(nv, c, **f32), torch.empty(nv, c, **f32))
+        w2, wts = pack_weights(weights)     # w2[i - 1] / wts[i - 1] = W_{i+1} / its transpose, in register-slice order
+        wh = s_head = None
+        if w_head is not None:
+            wh, s_head = head_weight(w_head), torch.empty(nv, 3, **f32)
+        kept = {}
+        s_cur = s1
+        for i, src, nxt, head, tap in SCHEDULE:
+            res = None if src is None else (lead3 if src == "lead" else kept[src])
+            x_out = xs[i - 1] if train else (out if head else (x_bufs[(i // 2) & 1] if tap else None))
+            plain_layer_forward(s_cur, biases[i - 1], csr, relu, res, 0.5, z_out=zs[i - 1] if train else None, x_out=x_out,
+                                w_next=w2[i - 1] if nxt else None, s_out=s_buf[i & 1] if nxt else None,
+                                w_head=wh if head else None, s_head=s_head if head else None)
+            if x_out is not None:
+                kept[i] = x_out
+            s_cur = s_buf[i & 1]
+        ctx.csr, ctx.relu, ctx.head = csr, relu, w_head is not None
+        ctx.head_shape = None if w_head is None else tuple(w_head.shape)
+        ctx.set_materialize_grads(False)
+        if train:
+            ctx.save_for_backward(xs, zs, wts, *([wh] if w_head is not None else []))
+        return (out, s_head) if w_head is not None else (out, _layers._alias(out))
+
+    @staticmethod
+    def backward(ctx, g_a, g_b):
+        L = LAYERS
+        xs, zs, wts = ctx.saved_tensors[:3]
+        csr = ctx.csr
+        _, nv, c = xs.shape
+        f32 = dict(dtype=torch.float32, device=xs.device)
+        n_in = 4 + 2 * L - 1
+        if g_a is None and g_b is None:
+            return (None,) * n_in
+        ds_head = w_head = dw_head = None
+        nrb = (nv + 15) // 16
+        if ctx.head:                       # g_b is the gradient of the head's raw support [V,3]
+            w_head = ctx.saved_tensors[3]
+            if g_b is not None:
+                ds_head = g_b.contiguous()
+                dw_head = torch.empty(nrb, c * 3, **f32) if ctx.needs_input_grad[3] else None
+            g_top, g_top2 = g_a, None
+        else:
+            g_top, g_top2 = (g_a, g_b) if g_a is not None else (g_b, None)
+        dzs = torch.empty(L, nv, c, **f32)          # dzs[i - 1] = dZ_i
+        dss = torch.empty(L - 1, nv, c, **f32)      # dss[i - 2] = dS_i, i = 2..L
+        colsum = torch.empty(L, nrb, c, **f32)      # per row-block partials of the bias gradients
+        pending = {}                                # j -> gradient that reaches layer j's output through a residual average
+        g_lead = None
+        for i, src, _, top, _ in reversed(SCHEDULE):
+            grad_res = torch.empty(nv, c, **f32) if src is not None else None
+            common = dict(grad_res=grad_res, colsum=colsum[i - 1])
+            if top:
+                what = dict(g=g_top, g2=g_top2, ds_head=ds_head, w_head=w_head if ds_head is not None else None,
+                            x_top=xs[L - 1] if dw_head is not None else None, dw_head=dw_head, **common)
+            else:
+                what = dict(dz_up=dzs[i], ds_up=dss[i - 1], wt_up=wts[i - 1], g2=pending.pop(i, None), **common)
+            plain_layer_backward((1, nv, c), csr, zs[i - 1], ctx.relu, src is not None, 0.5, dzs[i - 1], **what)
+            if src == "lead":
+                g_lead = grad_res
+            elif src is not None:
+                pending[src] = pending[src] + grad_res if src in pending else grad_res
+        assert not pending, "a residual gradient was left without its layer"
+        # dS_1 = aggregation backward of the first layer (no activation between S_1 and Z_1): the existing operator
+        g_s1, _ = _layers.aggregate_backward(dzs[0].unsqueeze(0), csr, 64, _layers._ACT_NONE, None, None, False)
+        g_w = torch.bmm(xs[:L - 1].transpose(1, 2), dss)      # dW_i = X_i^T . dS_i, i = 2..L: one strided-batched product
+        g_bias = torch.empty(L, c, **f32)
+        jobs = [(colsum[i], c, g_bias[i]) for i in range(L)]
+        g_head = None
+        if dw_head is not None:
+            g_head = torch.empty(c * 3, **f32)
+            jobs.append((dw_head, c * 3, g_head))
+        n = len(jobs)
+        _lib.call("geom_colsum_batch_f32", n, [j[0] for j in jobs], (ctypes.c_int * n)(*([nrb] * n)),
+                  (ctypes.c_int * n)(*[j[1] for j in jobs]), [j[2] for j in jobs])
+        grads = [g_bias[i] for i in range(L)] + [g_w[i] for i in range(L - 1)]
+        g_wh = None if g_head is None else g_head.view(ctx.head_shape)
+        return (g_s1.view(nv, c), g_lead, None, g_wh, *grads)
+
+
+def plain_chain(block, s1, lead, csr, head=None):
+    """The thirteen hidden layers of `block` applied to the first layer's raw support: (features, raw support of `head` or
+    None)."""
+    gcs = plain_layers(block)
+    params = [g.bias for g in gcs] + [g.weight1 for g in gcs[1:]]
+    feats, second = _PlainChain.apply(s1, lead, csr, None if head is None else head.weight1, *params)
+    return feats, (second if head is not None else None)

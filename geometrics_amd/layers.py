@@ -38,7 +38,8 @@ class _Csr:
     __slots__ = ("rowptr", "col", "val", "rowptr_t", "col_t", "val_t", "nv", "nnz",
                  "ell_w", "ell_col", "ell_val", "ell_col_t", "ell_val_t", "inv_deg", "over", "over_t",
                  "symmetric_structure",
-                 "_deform_tail")      # (geometrics_amd.deform: the rows' entries beyond the table as a second fixed-width table)
+                 "_deform_tail",      # (geometrics_amd.deform: the rows' entries beyond the table as a second fixed-width table)
+                 "_deform_plain")     # (geometrics_amd.deform: 8-wide tables + CSR overflow lists of A and A^T, whatever ell_w is)
 
 
 _csr_cache = ByTensor()   # adjacency tensor -> its _Csr
@@ -587,6 +588,57 @@ class Batch_Image_ZERON_GCNGCN(_ZeroNBase):
 
     def _weight(self):
         return self.weight1
+
+
+class Image_ZERON_GCNGCN(_ZeroNBase):
+    """Unbatched [V,Cin] input with a 2-D [Cin,Cout] `weight1` and the first C//3 channels aggregated (reference
+    old_GEOMetrics/layers.py:106-149: the layer of the old driver's MeshDeformationBlock; state_dict keys and shapes are its
+    checkpoints').  `adj`: the old driver's info dict (its 'adj' entry is taken), a dense [V,V] tensor or a _Csr.  The HIP
+    operators are fp32 on the device; any other input (a CPU tensor, float64: what the fixtures are checked with) is evaluated
+    with the reference's own expression on the dense adjacency."""
+    split = 3
+
+    def __init__(self, in_features, out_features, bias=True):
+        super().__init__()
+        self.in_features, self.out_features = in_features, out_features
+        self.weight1 = Parameter(torch.empty(in_features, out_features))
+        if bias:
+            self.bias = Parameter(torch.empty(out_features))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        _uniform(self.weight1, 0.6 * 6.0 / math.sqrt(self.weight1.size(1) + self.weight1.size(0)))
+        if self.bias is not None:
+            _uniform(self.bias, 0.1)
+
+    def _weight(self):
+        return self.weight1
+
+    def forward(self, input, adj, activation):
+        adj = plain_adjacency(adj)
+        if on_device_operators(input, adj):
+            return super().forward(input, adj, activation)
+        support = torch.mm(input, self.weight1)
+        k = _split_k(support, self)
+        output = torch.cat((torch.mm(adj, support[:, :k]), support[:, k:]), dim=1)
+        if self.bias is not None:
+            output = output + self.bias
+        return activation(output)
+
+
+def plain_adjacency(adj):
+    """The adjacency an unbatched layer was given: the old driver hands its layers an info dict whose 'adj' entry it is."""
+    return adj["adj"] if isinstance(adj, dict) else adj
+
+
+def on_device_operators(input, adj):
+    """Whether the HIP operators take an unbatched layer's call: an fp32 input on a HIP device with a _Csr or a dense fp32
+    adjacency beside it."""
+    if not (torch.is_tensor(input) and input.is_cuda and input.dtype == torch.float32):
+        return False
+    return isinstance(adj, _Csr) or (torch.is_tensor(adj) and adj.is_cuda)
 
 
 class _MaxPoolBase(Module):

@@ -25,7 +25,7 @@ from . import _lib
 from . import deform as _deform
 from . import encoder as _encoder
 from . import layers as _layers
-from .layers import Batch_Image_ZERON_GCNGCN, BatchGCNMax, BatchZERON_GCN, GCNMax, ZERON_GCN, _alias
+from .layers import Batch_Image_ZERON_GCNGCN, BatchGCNMax, BatchZERON_GCN, GCNMax, Image_ZERON_GCNGCN, ZERON_GCN, _alias
 
 
 def _identity(x):
@@ -316,6 +316,53 @@ class BatchMeshDeformationBlock(nn.Module):
                     x, taps[i] = x
             coords = self.gc15(x, adj, _identity)
         return taps[_deform.LAYERS], coords
+
+
+class MeshDeformationBlock(nn.Module):
+    """Reference models.py:138-201: the block the old driver (old_GEOMetrics/GEOMetrics.py:102-118) runs on ONE unbatched
+    mesh between two face splits -- 13 hidden Image_ZERON_GCNGCN layers with ReLU, a residual average after every pair (the
+    batched block's schedule: deform.SCHEDULE), no BatchNorm, and a coordinate head `gc15`.  There is no gc14, as in the
+    reference.  `forward(features [V,F], pooled [V,P], adj) -> (features [V,hidden], coords [V,output_features])`; adj: the
+    old driver's info dict, a dense [V,V] tensor or a layers._Csr.
+
+    At the block's own width (192) on a HIP device every hidden layer is ONE launch per direction at any vertex count and
+    any row length (deform.serves_plain, geom_deform_plain_{fwd,bwd}_f32); everything else -- and CPU tensors -- takes the
+    layers one by one."""
+
+    def __init__(self, input_features, hidden=192, output_features=3):
+        super().__init__()
+        self.gc1 = Image_ZERON_GCNGCN(input_features, hidden)
+        for i in range(2, 14):
+            setattr(self, "gc%d" % i, Image_ZERON_GCNGCN(hidden, hidden))
+        self.gc15 = Image_ZERON_GCNGCN(hidden, output_features)
+        self.hidden = hidden
+
+    def forward(self, features, pooled, adj):
+        adj = _layers.plain_adjacency(adj)
+        full = torch.cat((features, pooled), dim=1)
+        if full.shape[1] < self.hidden:
+            raise RuntimeError("the block input has %d columns, fewer than the %d hidden ones" % (full.shape[1], self.hidden))
+        lead = full[:, :self.hidden]
+        if _layers.on_device_operators(full, adj):
+            csr = _layers.adjacency_csr(adj)
+            if _deform.serves_plain(self, features, pooled, csr):
+                # the first layer's product and the head's aggregation stay the layers'
+                head = _deform.plain_head(self)
+                s1 = _layers._dense(full, self.gc1.weight1)
+                feats, s15 = _deform.plain_chain(self, s1, lead, csr, head=head)
+                if head is not None:
+                    return feats, _layers.zero_n_aggregate(s15, csr, head.bias, 3 // head.split, None)
+                return feats, self.gc15(feats, csr, _identity)
+            adj = csr
+        act = F.relu if _deform.relu else _identity
+        x, outs = full, {"lead": lead}
+        for i, src, _, _, tap in _deform.SCHEDULE:
+            x = getattr(self, "gc%d" % i)(x, adj, act)
+            if src is not None:
+                x = (outs.pop(src) + x) / 2
+            if tap:
+                outs[i] = x
+        return x, self.gc15(x, adj, _identity)
 
 
 class MeshEncoder(nn.Module):

@@ -484,6 +484,54 @@ typedef struct geom_deform_infer {
     const float *w_head; float *s_head;
 } geom_deform_infer;
 int geom_deform_infer_fwd_f32(const geom_deform_infer *args, void *stream);
+/* A hidden layer of the BatchNorm-FREE block (reference models.py:138-201, MeshDeformationBlock on Image_ZERON_GCNGCN layers:
+ * old_GEOMetrics/layers.py:106-149 -- what the old driver runs between two face splits) in one launch per direction, for ANY
+ * vertex count and ANY row length.  Tiling and grid are geom_deform_infer_fwd_f32's: 16 consecutive rows of the flattened
+ * [b * nv] rows per tile, at most 512 workgroups taking q or q + 1 tiles in turn behind one register-resident weight slice.
+ * The adjacency comes as the first 8 entries of every row as a table (ell_col / ell_val [nv, 8], col -1 = padding) and the
+ * rest of the row as a CSR overflow list (over_ptr [nv + 1], over_col, over_val; all NULL: no row is longer) of unbounded
+ * length -- layers._to_ell(rowptr, col, val, 8); summation in CSR order (table slots, then the overflow entries): the bits of
+ * geom_zn_gcn_aggregate_*_f32.
+ *   forward:   Z     = [A . s_in[:, :64] | s_in[:, 64:]] + bias                                  -> z_out (optional)
+ *              X'    = relu?(Z) ; with res: (res + .) * scale                                    -> x_out (optional)
+ *              s_out = X' . w_next (packed: geom_deform_pack_weights_f32's fwd[l]) or, without a product, s_head [b,nv,3] =
+ *              X' . w_head (w_head [192,3] row-major); at least one output must be given.
+ *   backward:  (dz_up != NULL)  ds_up = [A^T . dz_up[:, :64] | dz_up[:, 64:]]  (stored: the weight gradient above reads it)
+ *                               dX    = ds_up . W_up^T (wt_up packed: bwd[l])  (+ g2)
+ *              (dz_up == NULL)  dX    = g (+ g2) (+ ds_head [b,nv,3] . w_head^T; g may then be NULL), and dw_head
+ *                               [nrb,192,3] = per-tile partials of x_top^T . ds_head
+ *              has_res: dX *= scale, grad_res = dX;  dz = relu ? (z > 0 ? dX : 0) : dX  (z: the forward's z_out; needed with relu)
+ *              colsum (optional) [nrb,192]: the tile's column sums of dz in row order.  nrb = ceil(b * nv / 16): one partial row
+ *              per TILE, so the sums geom_colsum_batch_f32 forms of them do not depend on how tiles are dealt to workgroups.
+ * c == 192, k == 64, b * nv * 192 < 2^29 (also with res_ld / g_ld / g2_ld in place of 192: 32-bit byte offsets).  Rows of
+ * res, g and g2 at any pitch >= 192 floats (0 = 192), 4-byte aligned; every other array 16-byte aligned.  Anything else, a
+ * NULL required pointer, a product beside a head, a table without its values, an overflow list without its ptr: GEOM_EINVAL. */
+typedef struct geom_deform_plain_fwd {
+    int b, nv, c, k;
+    const float *s_in, *bias;                                   /* bias [192] or NULL */
+    const int *ell_col; const float *ell_val;                   /* [nv, 8] */
+    const int *over_ptr, *over_col; const float *over_val;      /* the rows' entries 8, 9, ... or NULL */
+    int relu;
+    const float *res; int res_ld; float scale;                  /* optional residual [b,nv,res_ld >= 192] */
+    float *z_out, *x_out;
+    const float *w_next; float *s_out;
+    const float *w_head; float *s_head;
+} geom_deform_plain_fwd;
+typedef struct geom_deform_plain_bwd {
+    int b, nv, c, k;
+    const float *dz_up;
+    const int *ell_col_t; const float *ell_val_t;               /* the tables of A^T */
+    const int *over_ptr_t, *over_col_t; const float *over_val_t;
+    float *ds_up; const float *wt_up;
+    const float *g, *g2;
+    int g_ld, g2_ld;
+    const float *z;
+    int relu, has_res; float scale;
+    float *grad_res, *dz, *colsum;
+    const float *ds_head, *w_head, *x_top; float *dw_head;
+} geom_deform_plain_bwd;
+int geom_deform_plain_fwd_f32(const geom_deform_plain_fwd *args, void *stream);
+int geom_deform_plain_bwd_f32(const geom_deform_plain_bwd *args, void *stream);
 /* EXPERIMENT (csrc/dense_split_bf16.hip; on no default route): c [m, 192] = a [m, k] . w [k, 192] on the BF16 matrix cores with
  * exact fp32 products -- every fp32 operand is the exact sum of three bf16 numbers, the products a_i b_j are exact in fp32,
  * terms = 6 keeps those with i + j <= 2 (the rest is below 2^-24 of |a b|), 9 keeps all; fp32 accumulation, the leading

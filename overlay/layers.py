@@ -12,4 +12,4 @@ from torch.nn.modules.module import Module  # noqa: F401
 from torch.nn.parameter import Parameter  # noqa: F401
 
 from geometrics_amd.layers import (BatchGCNMax, BatchZERON_GCN, Batch_Image_ZERON_GCNGCN,  # noqa: F401
-                                   GCNMax, ZERON_GCN)
+                                   GCNMax, Image_ZERON_GCNGCN, ZERON_GCN)

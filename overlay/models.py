@@ -1,5 +1,5 @@
 """Overlay module for the reference's `models.py`: everything stays the user's reference code (VGG,
-encoders, decoder) except `BatchMeshDeformationBlock`, `MeshEncoder` and `BatchMeshEncoder`, which are replaced by the fused-kernel
+encoders, decoder) except `BatchMeshDeformationBlock`, `MeshDeformationBlock`, `MeshEncoder` and `BatchMeshEncoder`, which are replaced by the fused-kernel
 versions with identical attribute names and state_dict keys (geometrics_amd/models.py).  Same mechanism as
 overlay/utils.py: the reference file further down sys.path is executed and its names re-exported."""
 import importlib.util
@@ -24,4 +24,5 @@ _spec.loader.exec_module(_reference_models)
 
 globals().update({k: v for k, v in vars(_reference_models).items() if not k.startswith("__")})
 
-from geometrics_amd.models import BatchMeshDeformationBlock, BatchMeshEncoder, MeshEncoder, VertexBatchNorm  # noqa: E402,F401
+from geometrics_amd.models import (BatchMeshDeformationBlock, BatchMeshEncoder, MeshDeformationBlock, MeshEncoder,  # noqa: E402,F401
+                                   VertexBatchNorm)
