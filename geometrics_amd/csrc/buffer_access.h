@@ -46,15 +46,15 @@ enum { ACT_NONE = 0, ACT_RELU = 1, ACT_ELU = 2 };
 template <int ACT>
 __device__ __forceinline__ float act_fwd(float v)
 {
-    if (ACT == ACT_RELU) return v > 0.f ? v : 0.f;
+    if (ACT == ACT_RELU) return v <= 0.f ? 0.f : v; // (torch.relu: NaN stays NaN)
     if (ACT == ACT_ELU) return v > 0.f ? v : expm1f(v);
     return v;
 }
 template <int ACT>
 __device__ __forceinline__ float act_bwd(float g, float out)
 {
-    if (ACT == ACT_RELU) return out > 0.f ? g : 0.f;
-    if (ACT == ACT_ELU) return out > 0.f ? g : g * (out + 1.f);
+    if (ACT == ACT_RELU) return out <= 0.f ? 0.f : g; // (threshold_backward: a NaN output lets g through)
+    if (ACT == ACT_ELU) return out > 0.f ? g : g * (out + 1.f); // (a NaN output: NaN)
     return g;
 }
 

@@ -311,7 +311,7 @@ template <typename Args> // (relu, res and scale are the layer's: geom_deform_fw
 __device__ __forceinline__ float db_norm_one(const Args &a, const DbNorm &bn, float zz, float r, bool on)
 {
     float y = (zz - bn.mean) * bn.invstd * bn.gamma + bn.beta;
-    if (a.relu) y = y > 0.f ? y : 0.f;
+    if (a.relu) y = y <= 0.f ? 0.f : y;
     if (a.res) y = (r + y) * a.scale;
     return on ? y : 0.f;
 }
@@ -405,7 +405,7 @@ __device__ __forceinline__ float db_bn_bwd_elem(const geom_deform_bwd &a, float 
     gg += second;
     if (a.has_res) gg *= a.scale;
     const float pass = gg;
-    if (a.relu && !(xhat * gamma + beta > 0.f)) gg = 0.f;
+    if (a.relu && xhat * gamma + beta <= 0.f) gg = 0.f;
     if (!mesh_on) gg = 0.f;
     sum_g += gg;
     sum_gx += gg * xhat;
@@ -1017,7 +1017,7 @@ __device__ __forceinline__ float4 dp_aggregate(__amdgpu_buffer_rsrc_t r_src, boo
 __device__ __forceinline__ float dp_act_one(const geom_deform_plain_fwd &a, float zz, float r, bool on)
 {
     float y = zz;
-    if (a.relu) y = y > 0.f ? y : 0.f;
+    if (a.relu) y = y <= 0.f ? 0.f : y;
     if (a.res) y = (r + y) * a.scale;
     return on ? y : 0.f;
 }
@@ -1194,8 +1194,8 @@ __device__ __forceinline__ void dp_bwd_row_block(const geom_deform_plain_bwd &a,
             gg.x *= a.scale, gg.y *= a.scale, gg.z *= a.scale, gg.w *= a.scale;
             if (a.grad_res) st4(r_gr, db_own(own_off, i), gg);
         }
-        dz[i] = make_float4((on && zv.x > 0.f) ? gg.x : 0.f, (on && zv.y > 0.f) ? gg.y : 0.f, (on && zv.z > 0.f) ? gg.z : 0.f,
-                            (on && zv.w > 0.f) ? gg.w : 0.f);
+        dz[i] = make_float4((on && !(zv.x <= 0.f)) ? gg.x : 0.f, (on && !(zv.y <= 0.f)) ? gg.y : 0.f, (on && !(zv.z <= 0.f)) ? gg.z : 0.f,
+                            (on && !(zv.w <= 0.f)) ? gg.w : 0.f);
         st4(r_dz, db_own(own_off, i), dz[i]);
     }
     if (a.colsum) db_colsum(dz, stage, a.colsum, rb, c0); // the row-block's partial of this layer's bias gradient

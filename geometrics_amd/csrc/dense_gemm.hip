@@ -431,8 +431,8 @@ __device__ __forceinline__ void rows_body(const RowArgs &q, float *lds, const in
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float t = v[r] + bb[r];
-                    v[r] = t > 0.f ? t : 0.f;
-                    bits |= (t > 0.f ? 1u : 0u) << r;
+                    v[r] = t <= 0.f ? 0.f : t;
+                    bits |= (t <= 0.f ? 0u : 1u) << r; // (act_bwd's rule: set for a NaN)
                 }
                 if (q.mask) { // 16 sign bits per (row, column block): the four g-lanes of a row combine their nibbles
                     unsigned m = bits << (4 * g);

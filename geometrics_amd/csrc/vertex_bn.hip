@@ -104,7 +104,7 @@ __global__ __launch_bounds__(BN_THREADS) void vertex_bn_fwd_kernel(BnArgs a)
         if (e < n) {
             const int bi = e / a.c, ci = e - bi * a.c;
             float y = (xv[i] - mean) * invstd * g + be;
-            if (a.relu) y = y > 0.f ? y : 0.f;
+            if (a.relu) y = y <= 0.f ? 0.f : y;
             if (a.res) y = (a.res[((size_t)bi * a.nv + v) * a.res_ld + ci] + y) * a.scale;
             a.out[((size_t)bi * a.nv + v) * a.c + ci] = y;
         }
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(BN_THREADS) void vertex_bn_fwd_vec_kernel(BnArgs a)
     }
     auto finish = [&](float x, float r) {
         float y = (x - mean) * invstd * g + be;
-        if (a.relu) y = y > 0.f ? y : 0.f;
+        if (a.relu) y = y <= 0.f ? 0.f : y;
         if (a.res) y = (r + y) * a.scale;
         return y;
     };
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(BN_THREADS) void vertex_bn_bwd_kernel(BnBwdArgs a)
                 go *= a.scale;
                 if (a.grad_res) a.grad_res[o] = go;
             }
-            if (a.relu && !(xh[i] * g + be > 0.f)) go = 0.f;
+            if (a.relu && xh[i] * g + be <= 0.f) go = 0.f;
             gy[i] = go;
             sum_g += go;
             sum_gx += go * xh[i];
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(BN_THREADS) void vertex_bn_bwd_vec_kernel(BnBwdArgs
         x = (x - mean) * invstd;
         if (a.has_res) go *= a.scale;
         const float pass = go;
-        if (a.relu && !(x * g + be > 0.f)) go = 0.f;
+        if (a.relu && x * g + be <= 0.f) go = 0.f;
         sum_g += go;
         sum_gx += go * x;
         return pass;

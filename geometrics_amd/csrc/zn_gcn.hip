@@ -120,11 +120,11 @@ struct Pack {
             }
         }
     }
-    __device__ __forceinline__ unsigned positive_bits() const // bit i = element i > 0, the predicate relu' is defined by (act_bwd)
+    __device__ __forceinline__ unsigned positive_bits() const // bit i = !(element i <= 0), the predicate relu' is defined by (act_bwd)
     {
         unsigned bits = 0u;
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) bits |= at(i) > 0.f ? 1u << i : 0u;
+        for (int i = 0; i < VEC; ++i) bits |= at(i) <= 0.f ? 0u : 1u << i;
         return bits;
     }
     __device__ __forceinline__ void take_from(const Pack &o, int first) // elements first.. are o's

@@ -398,8 +398,8 @@ __device__ __forceinline__ void zs_gather_role(const ZsArgs &a, float *lds, cons
                 v.x += bias4[i].x, v.y += bias4[i].y, v.z += bias4[i].z, v.w += bias4[i].w;
                 v.x = act_fwd<ACT>(v.x), v.y = act_fwd<ACT>(v.y), v.z = act_fwd<ACT>(v.z), v.w = act_fwd<ACT>(v.w);
                 if (ACT == ACT_RELU) {
-                    // out > 0 (the predicate relu' is defined by): a ReLU output is +0 or positive, so its bit pattern is zero
-                    // or a positive integer -- min(bits, 1) instead of a compare + select per element
+                    // !(out <= 0) (the predicate relu' is defined by): a ReLU output is +0, positive or NaN, so its bit pattern is zero
+                    // or a non-zero integer -- min(bits, 1) instead of a compare + select per element
                     sign_bits |= (min(__float_as_uint(v.x), 1u) | min(__float_as_uint(v.y), 1u) << 1 | min(__float_as_uint(v.z), 1u) << 2 |
                                   min(__float_as_uint(v.w), 1u) << 3) << (4 * i);
                 }

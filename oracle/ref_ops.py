@@ -120,14 +120,30 @@ def normalize_adj(mx):
     return torch.diag(r_inv) @ mx
 
 
-def zero_n_layer(x, adj, weight, bias, split, activation):
+def dense_aggregate(adj, support):
+    """adj @ support: the reference's product (layers.py:38).  0 * NaN is NaN there: one non-finite value of `support` reaches
+    every row of its column."""
+    return adj @ support
+
+
+def sparse_aggregate(adj, support):
+    """The same sum over the NON-ZEROS of `adj` [V,V] alone -- what a CSR row or a neighbour table holds, and so what the
+    kernels add up: a non-finite value of `support` [...,V,k] reaches the rows that have its vertex as a neighbour and no
+    other.  Differentiable; on finite operands equal to dense_aggregate up to the round-off of the rows' sums."""
+    rows, cols = torch.nonzero(adj, as_tuple=True)
+    val = adj[rows, cols].to(support.dtype)
+    out = torch.zeros_like(support)
+    return out.index_add(-2, rows, val[:, None] * support[..., cols, :])
+
+
+def zero_n_layer(x, adj, weight, bias, split, activation, aggregate=dense_aggregate):
     """layers.py:34-41 / 107-116 / 143-152: support = x W; first C//split columns multiplied by
-    the dense adjacency; concat; + bias; activation."""
+    the dense adjacency (aggregate: dense_aggregate or sparse_aggregate); concat; + bias; activation."""
     if weight.dim() == 3:
         weight = weight[0]
     support = x @ weight
     k = support.shape[-1] // split
-    out = torch.cat((adj @ support[..., :k], support[..., k:]), dim=-1)
+    out = torch.cat((aggregate(adj, support[..., :k]), support[..., k:]), dim=-1)
     if bias is not None:
         out = out + bias
     return activation(out)

@@ -80,20 +80,23 @@ def bn64(z, gamma, beta, eps):
     return (z - mean) / (var + eps).sqrt() * gamma.view(1, -1, 1) + beta.view(1, -1, 1), mean.flatten(), var.flatten()
 
 
-def block64(block, feats, pooled, adj, relu=True, stats=None, running=None, pre=None):
+def block64(block, feats, pooled, adj, relu=True, stats=None, running=None, pre=None, aggregate=None):
     """models.py:237-297 restated in float64 on the host (dense adjacency, torch ops): returns (features, coords, parameters)
     -- the parameters as float64 leaves, whose .grad a backward pass fills.  Each layer normalises with ITS BatchNorm's eps.
     stats (a list): receives every layer's batch statistics (mean, biased variance) in order.  running ({layer: (mean, var)}):
     eval mode -- those statistics normalise instead of the batch's.  pre (a list): receives every layer's pre-activation (what
-    the ReLU is applied to)."""
+    the ReLU is applied to).  aggregate: ref_ops.dense_aggregate (the default, the reference's product) or
+    ref_ops.sparse_aggregate (the sum over a row's stored entries, which is what the kernels form)."""
     import torch
+    from oracle import ref_ops
+    aggregate = aggregate or ref_ops.dense_aggregate
     p = {k: v.detach().double().cpu().requires_grad_(v.requires_grad) for k, v in block.named_parameters()}
     adj = adj.double().cpu()
 
     def gc(i, x):
         sup = x @ p["gc%d.weight1" % i][0]
         k = sup.shape[-1] // 3
-        return torch.cat((adj @ sup[..., :k], sup[..., k:]), dim=-1) + p["gc%d.bias" % i]
+        return torch.cat((aggregate(adj, sup[..., :k]), sup[..., k:]), dim=-1) + p["gc%d.bias" % i]
 
     def layer(i, x):
         gamma, beta, eps = p["bn%d.weight" % i], p["bn%d.bias" % i], float(getattr(block, "bn%d" % i).eps)
@@ -300,6 +303,37 @@ def rows_close(actual, exact, mass, rtol, what="", floor=None, floor_ulps=0.0):
     return worst
 
 
+def nonfinite_close(got, want64, mass, rtol, what="", kinds=True):
+    """`got` (an fp32 evaluation) against `want64` (float64) where `want64` holds NaN and Inf, in this order:
+      1. isfinite(got) == isfinite(want64) for EVERY element;
+      2. kinds: NaN, +Inf and -Inf agree element by element (False where only the mask is determinate: Inf - Inf in a variance);
+      3. the elements finite in want64 pass rows_close(rtol) -- the bound the finite test of the same kernel uses.
+    mass: the |.|-chain of the float64 run with every non-finite factor replaced by 0 (finite wherever want64 is)."""
+    got, want64, mass = (np.asarray(x.detach().cpu() if hasattr(x, "detach") else x, np.float64) for x in (got, want64, mass))
+    assert got.shape == want64.shape == mass.shape, "%s: shapes %s %s %s" % (what, got.shape, want64.shape, mass.shape)
+    fin_got, fin_want = np.isfinite(got), np.isfinite(want64)
+    bad = np.argwhere(fin_got != fin_want)
+    assert not len(bad), "%s: %d elements finite on one side only (of %d non-finite in float64), first at %s: got %r, float64 %r" \
+        % (what, len(bad), (~fin_want).sum(), tuple(bad[0]), got[tuple(bad[0])], want64[tuple(bad[0])])
+    if kinds:
+        for name, pick in (("NaN", np.isnan), ("+Inf", np.isposinf), ("-Inf", np.isneginf)):
+            bad = np.argwhere(pick(got) != pick(want64))
+            assert not len(bad), "%s: %s differs at %d elements, first at %s: got %r, float64 %r" \
+                % (what, name, len(bad), tuple(bad[0]), got[tuple(bad[0])], want64[tuple(bad[0])])
+    if not fin_want.any():
+        return 0.0
+    assert np.isfinite(mass[fin_want]).all(), "%s: the mass of a finite element is not finite" % what
+    return rows_close(got[fin_want], want64[fin_want], mass[fin_want], rtol, what)
+
+
+def finite_part(t):
+    """t with every non-finite element replaced by 0 (torch or numpy): the factor a mass chain carries in its place."""
+    import torch
+    if torch.is_tensor(t):
+        return torch.where(torch.isfinite(t), t, torch.zeros_like(t))
+    return np.where(np.isfinite(t), t, 0.0)
+
+
 # ---- the pooling's vertex-position gradient per element (oracle/ref_ops.py pool_vertex_gradient) -------------------------------
 POOL_NEAR = 1e-3          # texels: vertices closer than this to a texel line are left out (the gradient jumps across the line;
 #                           the fp32 texel coordinate is within 1e-5 of the float64 one: 100 times the rounding)
@@ -404,8 +438,8 @@ def vertex_bn64(x, gamma, beta, eps, relu, residual, scale, grad_out, grad_out2=
         go = np.asarray(grad_out, np.float64) + (0.0 if grad_out2 is None else np.asarray(grad_out2, np.float64))
         go = go * ~knife
         exact["grad_residual"] = go * scale
-        dact = (pre > 0.0) if relu else np.ones(x.shape, bool)
-        gy = go * scale * dact
+        dact = ~(pre <= 0.0) if relu else np.ones(x.shape, bool)        # torch's threshold_backward: a NaN lets the gradient through
+        gy = np.where(dact, go * scale, 0.0)                            # (a select, as torch's: a non-finite gradient behind a closed ReLU is 0)
         ay, axh = np.abs(gy), np.abs(xh)
         sum_g, sum_gx = gy.sum(axis=(0, 2)), (gy * xh).sum(axis=(0, 2))
         exact["grad_bias"], mass["grad_bias"] = sum_g, ay.sum(axis=(0, 2))
