@@ -24,18 +24,22 @@
 // tile goes through that product's LDS panel, one ds_read_b128 per 12 MFMAs.  482 workgroups of 4 waves, two resident per CU: while one
 // waits for its gathers the other runs its 144 MFMAs per wave.
 //
-// Three forward bodies (db_fwd_body: plain and chain launches, one row tile per vertex; dbw_fwd_kernel: up to four tiles per
-// vertex; di_row_block: eval, 16 consecutive rows of [b * nv]) and two backward ones (db_bwd_body, dbw_bwd_kernel) run the SAME
-// layer.  Its steps -- bias, BatchNorm + ReLU + residual, the statistics and their publication, the coordinate head both ways,
-// the staging tile's way out, the BatchNorm backward, the column sums -- are stated once, as the db_* helpers behind
-// db_to_panel, and every body calls them: the wide route must give the plain route's bits, the eval route vertex_bn's.
-// The bodies themselves stay apart, because their SCHEDULES differ on purpose: the plain body requests the weight slice inside
+// Three tilings run the SAME layer: one row tile per vertex (db_fwd_body / db_bwd_body: the launches per layer and the chain
+// launches), up to four tiles per vertex (dbw_fwd_kernel / dbw_bwd_kernel) and 16 consecutive rows of [b * nv] (di_row_block:
+// eval; dp_fwd_row_block / dp_bwd_row_block: the BatchNorm-free block of the old driver).  The layer's steps -- a table row's
+// unpacking, bias, BatchNorm + ReLU + residual, the statistics and their publication, the coordinate head both ways, the staging
+// tile's way out, the BatchNorm backward, the column sums -- are stated once, as the db_* helpers around db_to_panel, and every
+// body calls them: the wide route must give the one-tile route's bits, the eval route vertex_bn's.  The three row-block kernels
+// share the dealing of row-blocks to workgroups (db_deal_row_blocks) and the host's grid (db_launch_row_blocks), the two plain
+// ones their gather (db_row_aggregate).
+// What stays apart, and why: the SCHEDULES differ on purpose -- the one-tile body requests the weight slice inside
 // db_aggregate<SLICE>, behind its gathers; the wide body once, behind the gathers of ALL tiles (a pole's 32 tail rows per tile
-// need the slice's registers); the eval body walks a per-row table and, once the slice is live, gathers in two rounds of four.
-// The chain kernels sit at 256 VGPRs already (tools/kernel_resources.sh): one body templated over the tile count, or the eval
-// table walk folded into db_aggregate, would trade these orders for one that fits none of them.
-// The BatchNorm-free block of the old driver (dp_fwd_row_block / dp_bwd_row_block, geom_deform_plain_{fwd,bwd}_f32) takes the
-// eval body's tiling and the same steps, with a CSR overflow list of any length behind the 8-wide table.
+// need the slice's registers); the row-block bodies walk a per-row table and, once the slice is live, gather in two rounds of
+// four.  The chain kernels sit at 256 VGPRs already (tools/kernel_resources.sh): one body templated over the tile count, or
+// the row-block table walk folded into db_aggregate, would trade these orders for one that fits none of them.  And a step
+// stays written out in a body where the shared statement costs that body registers it does not have: the top layer's head
+// backward (shared, db_bwd_chain_kernel spills 7 VGPRs instead of 5), the residual load (db_fwd_chain_kernel spills 41 SGPRs
+// instead of 39), and the row-block bodies' (see their section).  profiles/rowblock_resources.txt has the figures.
 #include "mfma_tiles.h"
 #include "device_facts.h"
 
@@ -184,6 +188,15 @@ __global__ __launch_bounds__(256) void db_pack_kernel(DbPackArgs a)
 // (26 000 cycles in the gather phase against 8 500: tools/probe/db_stamps.py).
 // a vertex's row of the neighbour table + its tail row (round trip 1 of a layer: scalar loads -- the same for every thread of
 // the workgroup -- and ONE vector load of the tail row); a chain launch fetches it once for all its layers
+// vertex v's row of the neighbour table: scalar loads where v is the same for the whole workgroup (db_table), vector loads per
+// row where every row of a tile has its own vertex (the row-block bodies)
+__device__ __forceinline__ void db_table_row(const int *ell_col, const float *ell_val, int v, int (&nb)[DB_W], float (&wv)[DB_W])
+{
+    const int4 ci0 = *reinterpret_cast<const int4 *>(ell_col + (size_t)v * DB_W), ci1 = *reinterpret_cast<const int4 *>(ell_col + (size_t)v * DB_W + 4);
+    const float4 wi0 = *reinterpret_cast<const float4 *>(ell_val + (size_t)v * DB_W), wi1 = *reinterpret_cast<const float4 *>(ell_val + (size_t)v * DB_W + 4);
+    nb[0] = ci0.x, nb[1] = ci0.y, nb[2] = ci0.z, nb[3] = ci0.w, nb[4] = ci1.x, nb[5] = ci1.y, nb[6] = ci1.z, nb[7] = ci1.w;
+    wv[0] = wi0.x, wv[1] = wi0.y, wv[2] = wi0.z, wv[3] = wi0.w, wv[4] = wi1.x, wv[5] = wi1.y, wv[6] = wi1.z, wv[7] = wi1.w;
+}
 struct DbTable {
     int nb[DB_W];
     float wv[DB_W];
@@ -200,10 +213,7 @@ __device__ __forceinline__ DbTable db_table(int v, const int *ell_col, const flo
         t.tcol = tail_col[(size_t)v * DB_TAIL + (lane & (DB_TAIL - 1))];
         t.tval = tail_val[(size_t)v * DB_TAIL + (lane & (DB_TAIL - 1))];
     }
-    const int4 ci0 = *reinterpret_cast<const int4 *>(ell_col + (size_t)v * DB_W), ci1 = *reinterpret_cast<const int4 *>(ell_col + (size_t)v * DB_W + 4);
-    const float4 wi0 = *reinterpret_cast<const float4 *>(ell_val + (size_t)v * DB_W), wi1 = *reinterpret_cast<const float4 *>(ell_val + (size_t)v * DB_W + 4);
-    t.nb[0] = ci0.x, t.nb[1] = ci0.y, t.nb[2] = ci0.z, t.nb[3] = ci0.w, t.nb[4] = ci1.x, t.nb[5] = ci1.y, t.nb[6] = ci1.z, t.nb[7] = ci1.w;
-    t.wv[0] = wi0.x, t.wv[1] = wi0.y, t.wv[2] = wi0.z, t.wv[3] = wi0.w, t.wv[4] = wi1.x, t.wv[5] = wi1.y, t.wv[6] = wi1.z, t.wv[7] = wi1.w;
+    db_table_row(ell_col, ell_val, v, t.nb, t.wv);
     t.has_tail = tail_col != nullptr;
     return t;
 }
@@ -370,6 +380,16 @@ __device__ __forceinline__ void db_head_fwd(const float4 (&xo)[3], const float *
 #pragma unroll
     for (int m = 8; m > 0; m >>= 1) {
         h[0] += __shfl_xor(h[0], m, GEOM_WAVE), h[1] += __shfl_xor(h[1], m, GEOM_WAVE), h[2] += __shfl_xor(h[2], m, GEOM_WAVE);
+    }
+}
+// ... stored as the raw support s_head[row] = X'[row] . W_head by the first lane of the row's group
+__device__ __forceinline__ void db_head_store(const float4 (&xo)[3], const float *w_head, float *s_head, size_t row, bool on, int c0)
+{
+    float h[3];
+    db_head_fwd(xo, w_head, c0, h);
+    if (c0 == 0 && on) {
+        float *dst = s_head + row * 3;
+        dst[0] = h[0], dst[1] = h[1], dst[2] = h[2];
     }
 }
 
@@ -575,14 +595,7 @@ __device__ __forceinline__ void db_fwd_body(const geom_deform_fwd &a, const int 
     }
     if (!PRODUCT) {
         // ---- the coordinate head's product inside the last hidden layer's launch
-        if (a.w_head && a.s_head) {
-            float h[3];
-            db_head_fwd(xo, a.w_head, c0, h);
-            if (j == 0 && mesh_on) {
-                float *dst = a.s_head + ((size_t)rl * a.nv + v) * 3;
-                dst[0] = h[0], dst[1] = h[1], dst[2] = h[2];
-            }
-        }
+        if (a.w_head && a.s_head) db_head_store(xo, a.w_head, a.s_head, (size_t)rl * a.nv + v, mesh_on, c0);
         return;
     }
 
@@ -797,30 +810,180 @@ __global__ __launch_bounds__(DB_THREADS, 2) void db_bwd_chain_kernel(DbBwdChain 
     }
 }
 
-// ---- the eval-mode forward (geom_deform_infer_fwd_f32): one launch per hidden layer, BatchNorm on the running statistics
+// ---- the row-block launches, one per hidden layer and direction: the eval-mode forward (geom_deform_infer_fwd_f32:
+// di_row_block, di_fwd_kernel) and the BatchNorm-free block of the old driver on split meshes (geom_deform_plain_{fwd,bwd}_f32:
+// dp_fwd_row_block, dp_bwd_row_block; reference models.py:138-201 on old_GEOMetrics/layers.py:106-149)
 //
-//   Z   = [A . S[:, :64] | S[:, 64:]] + bias          zn_gcn.hip's order and arithmetic (table slots, then the tail, in CSR order)
-//   X'  = ReLU((Z - rm_v) * (1 / sqrtf(rv_v + eps)) * gamma_v + beta_v) (+ residual, * scale)   vertex_bn.hip's eval branch
+//   Z   = [A . S[:, :64] | S[:, 64:]] + bias          zn_gcn.hip's order and arithmetic (table slots, then the row's tail, in CSR order)
+//   X'  = ReLU((Z - rm_v) * (1 / sqrtf(rv_v + eps)) * gamma_v + beta_v) (+ residual, * scale)   eval: vertex_bn.hip's eval branch
+//   X'  = relu?(Z) (+ residual, * scale)               plain: NO BatchNorm step (absent, not an identity map: (z - 0) * 1 * 1 + 0
+//                                                      would turn -0.0 into +0.0)
 //   S'  = X' . W_next                                  exact fp32 on v_mfma_f32_16x16x4_f32 (db_product)
 //
-// Tiling: in eval mode BatchNorm1d(verts) is a fixed per-vertex affine map -- no reduction over the batch is left -- so the rows
-// are independent apart from the gather, and the tile is 16 CONSECUTIVE rows of the flattened [b * nv] row space (a row-block;
-// it may span two meshes: every row gathers inside its own mesh).  At the driver's validation batch of 1 that fills the MFMA
-// rows the training tiling (one vertex = one tile, its batch rows = the tile's rows) leaves 15/16 empty, and any batch works.
-// The table, the BatchNorm parameters and the statistics are per ROW here (vector loads; the training kernel has one vertex
-// per workgroup and reads them with scalar loads); a pole's tail is walked four entries per round trip by its own 16 lanes
-// (the wave's weight slice is live across it: there are no registers for more).
+// Tiling: in eval mode BatchNorm1d(verts) is a fixed per-vertex affine map and the plain block has none -- no reduction over the
+// batch is left -- so the rows are independent apart from the gather, and the tile is 16 CONSECUTIVE rows of the flattened
+// [b * nv] row space (a row-block; it may span two meshes: every row gathers inside its own mesh).  At the driver's validation
+// batch of 1, and on the ONE unbatched mesh of the old driver, that fills the MFMA rows the training tiling (one vertex = one
+// tile, its batch rows = the tile's rows) leaves 15/16 empty, and any batch works.  The table, the BatchNorm parameters and the
+// statistics are per ROW here (vector loads; the training kernel has one vertex per workgroup and reads them with scalar loads).
+// A row's tail is walked four entries per round trip by the row's own 16 lanes, up to the row's own end (the rows of a wave have
+// different lengths; the wave's weight slice is live across the walk: there are no registers for more).  The eval launch reads
+// the training launches' second table, [nv][DB_TAIL] with -1 padding (the 33-entry poles of 482.obj); the plain launches a CSR
+// overflow list of ANY length -- the old driver's vertex count grows with every face split and its rows get long (a pole of 65
+// entries after one split of 482.obj).
 //
 // Work per workgroup: a workgroup keeps the wave's 192 x 48 weight slice in registers (36 KB per wave, 147 KB per workgroup)
-// and runs q or q + 1 consecutive row-blocks (zn_stack.hip's q / rem dealing) over at most DI_WGS = 512 workgroups -- two per
-// CU of an MI355X, the residency of __launch_bounds__(256, 2).  Batch 1 (31 row-blocks) and batch 16 (482) get one row-block
-// per workgroup: the launch is one latency chain (table -> gathers -> product), and more workgroups are more chains in flight.
+// and runs q or q + 1 consecutive row-blocks (db_deal_row_blocks) over at most DI_WGS = 512 workgroups -- two per CU of an
+// MI355X, the residency of __launch_bounds__(256, 2).  Batch 1 (31 row-blocks) and batch 16 (482) get one row-block per
+// workgroup: the launch is one latency chain (table -> gathers -> product), and more workgroups are more chains in flight.
 // Above 512 row-blocks a workgroup takes two or more in turn instead of a new workgroup re-reading the 147 KB slice from L2:
 // at batch 40 (1 205 row-blocks) 512 slices are read instead of 1 205.  Logical workgroup order follows db_vertex: contiguous
 // row-block runs per XCD, so the neighbour rows a run gathers stay in one L2.
 // No workgroup waits for another: a launch depends only on the one before it in stream order.
+//
+// The plain block's backward launch: aggregation backward of the layer above + its input-gradient product + this layer's mask,
+// with the bias-gradient (and head-weight) partials per ROW-BLOCK -- whichever workgroup runs a row-block writes the same partial
+// row.
+//
+// The eval body and the plain forward body run the same steps and stay two texts: their tails are different data, one four-entry
+// step for both walkers adds 16 loads to each eval kernel, and dp_fwd_kernel<false> -- at 96 VGPRs, the last count with 5 waves
+// per SIMD -- needs 98 with the row-block geometry as a value struct, with a shared residual load or with db_head_store
+// (profiles/rowblock_resources.txt has each variant's figures).
 constexpr int DI_WGS = 512;
 
+// The aggregated float4 of a thread's row v in the plain launches: table slots, then the CSR overflow entries [over_ptr[v],
+// over_ptr[v + 1]), in CSR order (zn_gcn.hip's order and arithmetic).  ROUND table rows are in flight at once; LOAD_SLICE: the
+// wave's weight slice is requested behind the first round.
+template <bool LOAD_SLICE, int ROUND>
+__device__ __forceinline__ float4 db_row_aggregate(__amdgpu_buffer_rsrc_t r_src, bool on, unsigned rowbase, int v, int c0, const int *ell_col,
+                                                   const float *ell_val, const int *over_ptr, const int *over_col, const float *over_val,
+                                                   DbSlice &bw, const float *packed, int wave, int lane)
+{
+    int nb[DB_W];
+    float wv[DB_W];
+    db_table_row(ell_col, ell_val, v, nb, wv);
+    int e = 0, end = 0; // the row's overflow entries [e, end)
+    if (over_ptr && on) e = over_ptr[v], end = over_ptr[v + 1];
+    float4 facc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int n0 = 0; n0 < DB_W; n0 += ROUND) {
+        float4 sv[ROUND];
+#pragma unroll
+        for (int n = 0; n < ROUND; ++n)
+            sv[n] = ld4(r_src, on ? rowbase + (unsigned)(nb[n0 + n] >= 0 ? nb[n0 + n] : v) * (DB_C * 4) + 4 * c0 : OOB);
+        if (LOAD_SLICE && n0 == 0) db_load_slice(bw, packed, wave, lane);
+#pragma unroll
+        for (int n = 0; n < ROUND; ++n) {
+            if (nb[n0 + n] >= 0) { // ELL order == CSR order of the row
+                facc.x += wv[n0 + n] * sv[n].x, facc.y += wv[n0 + n] * sv[n].y, facc.z += wv[n0 + n] * sv[n].z, facc.w += wv[n0 + n] * sv[n].w;
+            }
+        }
+    }
+    for (; e < end; e += 4) { // (a group of 16 lanes leaves at its own row's end)
+        int tc[4];
+        float tw[4];
+        float4 tv[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int at = e + t < end ? e + t : end - 1;
+            tc[t] = over_col[at], tw[t] = over_val[at];
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) tv[t] = ld4(r_src, e + t < end ? rowbase + (unsigned)tc[t] * (DB_C * 4) + 4 * c0 : OOB);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (e + t < end) {
+                facc.x += tw[t] * tv[t].x, facc.y += tw[t] * tv[t].y, facc.z += tw[t] * tv[t].z, facc.w += tw[t] * tv[t].w;
+            }
+        }
+    }
+    return facc;
+}
+
+// relu?(Z) (+ residual, * scale) of one element; `on` = false: a row beyond the last, zero
+__device__ __forceinline__ float dp_act_one(const geom_deform_plain_fwd &a, float zz, float r, bool on)
+{
+    float y = zz;
+    if (a.relu) y = y <= 0.f ? 0.f : y;
+    if (a.res) y = (r + y) * a.scale;
+    return on ? y : 0.f;
+}
+
+template <bool PRODUCT, bool LOAD_SLICE>
+__device__ __forceinline__ void dp_fwd_row_block(const geom_deform_plain_fwd &a, const int rb, float *lds, DbSlice &bw)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = lane & 15, g = lane >> 4; // matrix-core coordinates
+    const int rl = tid >> 4, j = tid & 15;  // row of the block and float4 group of the gather thread
+    const int c0 = 4 * j;
+    const int rows = a.b * a.nv;
+    const int r = rb * 16 + rl;
+    const bool on = r < rows;
+    const int mesh = on ? r / a.nv : 0, v = on ? r - mesh * a.nv : 0;
+    const int64_t op_bytes = (int64_t)rows * DB_C * 4;
+    const __amdgpu_buffer_rsrc_t r_src = rsrc(a.s_in, op_bytes);
+    const unsigned rowbase = (unsigned)mesh * (unsigned)a.nv * (DB_C * 4);
+    const unsigned own_off = on ? (unsigned)r * (DB_C * 4) + 4 * c0 : OOB;
+    // round trip 1: the bias and the residual; the row's table behind them, inside db_row_aggregate
+    float4 bias4[3], rv[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) bias4[i] = db_bias4(a, c0, i), rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (a.res) {
+        const __amdgpu_buffer_rsrc_t r_res = rsrc(a.res, ((int64_t)rows - 1) * a.res_ld * 4 + DB_C * 4);
+        const unsigned roff = (unsigned)r * (unsigned)a.res_ld * 4u + 4 * c0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) rv[i] = ld4(r_res, on ? roff + 4 * DB_K * i : OOB);
+    }
+    // round trip 2 (the row's table in front of it): the neighbour rows + the thread's own pass-through elements, the weight
+    // slice behind them.  A later row-block of the workgroup holds the slice already: its table rows go in two rounds of four
+    // (no registers for eight rows in flight beside the slice)
+    constexpr int ROUND = LOAD_SLICE || !PRODUCT ? DB_W : DB_W / 2;
+    float4 z[3];
+#pragma unroll
+    for (int i = 1; i < 3; ++i) z[i] = ld4(r_src, db_own(own_off, i));
+    z[0] = db_row_aggregate<LOAD_SLICE, ROUND>(r_src, on, rowbase, v, c0, a.ell_col, a.ell_val, a.over_ptr, a.over_col, a.over_val, bw,
+                                               a.w_next, wave, lane);
+    db_add_bias(z, bias4);
+    float4 xo[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        xo[i] = make_float4(dp_act_one(a, z[i].x, rv[i].x, on), dp_act_one(a, z[i].y, rv[i].y, on), dp_act_one(a, z[i].z, rv[i].z, on),
+                            dp_act_one(a, z[i].w, rv[i].w, on));
+    if (a.z_out) {
+        const __amdgpu_buffer_rsrc_t r_z = rsrc(a.z_out, op_bytes);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) st4(r_z, db_own(own_off, i), z[i]);
+    }
+    if (a.x_out) {
+        const __amdgpu_buffer_rsrc_t r_x = rsrc(a.x_out, op_bytes);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) st4(r_x, db_own(own_off, i), xo[i]);
+    }
+    if (!PRODUCT) {
+        if (a.w_head) { // db_head_store, written out: through it dp_fwd_kernel<false> takes 98 VGPRs, a wave per SIMD fewer
+            float h[3];
+            db_head_fwd(xo, a.w_head, c0, h);
+            if (j == 0 && on) {
+                float *dst = a.s_head + (size_t)r * 3;
+                dst[0] = h[0], dst[1] = h[1], dst[2] = h[2];
+            }
+        }
+        return;
+    }
+    db_to_panel(lds, rl, c0, xo); // (rows beyond the last are zero rows of the panel)
+    __syncthreads();
+    float *stage = lds + RB_PANEL;
+    db_product(bw, lds, stage, wave, x, g);
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t r_s = rsrc(a.s_out, op_bytes);
+    db_store_tile<false>(stage, r_s, [&](int rr) { // (16 consecutive rows = 12 KB contiguous)
+        const int row = rb * 16 + rr;
+        return row < rows ? (unsigned)row * (DB_C * 4) : OOB;
+    });
+    // (the next row-block writes the panel, which nobody reads any more; the staging tile only after its first barrier)
+}
+
+// The eval launch's row-block: the same steps on its own schedule (see the section's last paragraph)
 template <bool PRODUCT, bool LOAD_SLICE>
 __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const int rb, float *lds, DbSlice &bw)
 {
@@ -840,12 +1003,7 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
     // statistics, the bias and the residual
     int nb[DB_W];
     float wv[DB_W];
-    {
-        const int4 ci0 = *reinterpret_cast<const int4 *>(a.ell_col + (size_t)v * DB_W), ci1 = *reinterpret_cast<const int4 *>(a.ell_col + (size_t)v * DB_W + 4);
-        const float4 wi0 = *reinterpret_cast<const float4 *>(a.ell_val + (size_t)v * DB_W), wi1 = *reinterpret_cast<const float4 *>(a.ell_val + (size_t)v * DB_W + 4);
-        nb[0] = ci0.x, nb[1] = ci0.y, nb[2] = ci0.z, nb[3] = ci0.w, nb[4] = ci1.x, nb[5] = ci1.y, nb[6] = ci1.z, nb[7] = ci1.w;
-        wv[0] = wi0.x, wv[1] = wi0.y, wv[2] = wi0.z, wv[3] = wi0.w, wv[4] = wi1.x, wv[5] = wi1.y, wv[6] = wi1.z, wv[7] = wi1.w;
-    }
+    db_table_row(a.ell_col, a.ell_val, v, nb, wv);
     const int tail0 = a.tail_col ? a.tail_col[(size_t)v * DB_TAIL] : -1;
     const float gamma = a.bn_w ? a.bn_w[v] : 1.f, beta = a.bn_b ? a.bn_b[v] : 0.f;
     const float mean = a.run_mean[v], invstd = 1.f / sqrtf(a.run_var[v] + a.eps);
@@ -910,15 +1068,7 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
         for (int i = 0; i < 3; ++i) st4(r_x, db_own(own_off, i), xo[i]);
     }
     if (!PRODUCT) {
-        // the coordinate head's raw support s_head[row] = X'[row] . W_head
-        if (a.w_head) {
-            float h[3];
-            db_head_fwd(xo, a.w_head, c0, h);
-            if (j == 0 && on) {
-                float *dst = a.s_head + (size_t)r * 3;
-                dst[0] = h[0], dst[1] = h[1], dst[2] = h[2];
-            }
-        }
+        if (a.w_head) db_head_store(xo, a.w_head, a.s_head, (size_t)r, on, c0); // the coordinate head's raw support
         return;
     }
     // the next layer's product on the tile (rows beyond the last are zero rows of the panel)
@@ -935,179 +1085,33 @@ __device__ __forceinline__ void di_row_block(const geom_deform_infer &a, const i
     // (the next row-block writes the panel, which nobody reads any more; the staging tile only after its first barrier)
 }
 
-template <bool PRODUCT>
-__global__ __launch_bounds__(DB_THREADS, 2) void di_fwd_kernel(geom_deform_infer a, int nrb, int nwg, int per_xcd)
+// logical workgroup -> its run of row-blocks [first, first + count) (zn_stack.hip's q / rem dealing)
+__device__ __forceinline__ bool db_deal_row_blocks(int nrb, int nwg, int per_xcd, int &first, int &count)
 {
-    __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST];
-    const int w = blockIdx.x;
-    const int lw = geom::xcd_run_item(w, per_xcd); // logical workgroup: contiguous runs per XCD (workgroup w runs on XCD w % 8)
-    if (lw >= nwg) return;
-    const int q = nrb / nwg, rem = nrb - q * nwg;
-    const int first = lw * q + (lw < rem ? lw : rem), count = q + (lw < rem ? 1 : 0);
-    DbSlice bw;
-    di_row_block<PRODUCT, PRODUCT>(a, first, lds, bw);
-    for (int i = 1; i < count; ++i) di_row_block<PRODUCT, false>(a, first + i, lds, bw);
-}
-
-// ---- the BatchNorm-free block on split meshes (geom_deform_plain_{fwd,bwd}_f32; reference models.py:138-201 on
-// old_GEOMetrics/layers.py:106-149): the old driver runs it on ONE unbatched mesh whose vertex count grows with every face
-// split and whose rows get long (a pole of 65 entries after one split of 482.obj).  No statistic ties the rows of a vertex
-// together, so tiling, grid and schedule are the eval launch's (di_row_block / di_fwd_kernel: 16 consecutive rows of [b * nv],
-// <= DI_WGS workgroups with q or q + 1 row-blocks each behind one register-resident weight slice).  What differs:
-//   * no BatchNorm step (absent, not an identity map): X' = relu?(Z) (+ residual, * scale);
-//   * a row's entries beyond the 8-wide table come from a CSR overflow list of ANY length, walked four entries per round trip
-//     by the row's own 16 lanes up to the row's own end (the rows of a wave have different lengths);
-//   * a backward launch: aggregation backward of the layer above + its input-gradient product + this layer's mask, with the
-//     bias-gradient (and head-weight) partials per ROW-BLOCK -- whichever workgroup runs a row-block writes the same partial row.
-
-// The aggregated float4 of a thread's row v: table slots, then the overflow entries, in CSR order (zn_gcn.hip's order and
-// arithmetic).  ROUND table rows are in flight at once; LOAD_SLICE: the wave's weight slice is requested behind the first round.
-template <bool LOAD_SLICE, int ROUND>
-__device__ __forceinline__ float4 dp_aggregate(__amdgpu_buffer_rsrc_t r_src, bool on, unsigned rowbase, int v, int c0, const int *ell_col,
-                                               const float *ell_val, const int *over_ptr, const int *over_col, const float *over_val,
-                                               DbSlice &bw, const float *packed, int wave, int lane)
-{
-    int nb[DB_W];
-    float wv[DB_W];
-    {
-        const int4 ci0 = *reinterpret_cast<const int4 *>(ell_col + (size_t)v * DB_W), ci1 = *reinterpret_cast<const int4 *>(ell_col + (size_t)v * DB_W + 4);
-        const float4 wi0 = *reinterpret_cast<const float4 *>(ell_val + (size_t)v * DB_W), wi1 = *reinterpret_cast<const float4 *>(ell_val + (size_t)v * DB_W + 4);
-        nb[0] = ci0.x, nb[1] = ci0.y, nb[2] = ci0.z, nb[3] = ci0.w, nb[4] = ci1.x, nb[5] = ci1.y, nb[6] = ci1.z, nb[7] = ci1.w;
-        wv[0] = wi0.x, wv[1] = wi0.y, wv[2] = wi0.z, wv[3] = wi0.w, wv[4] = wi1.x, wv[5] = wi1.y, wv[6] = wi1.z, wv[7] = wi1.w;
-    }
-    int e = 0, end = 0; // the row's overflow entries [e, end)
-    if (over_ptr && on) e = over_ptr[v], end = over_ptr[v + 1];
-    float4 facc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int n0 = 0; n0 < DB_W; n0 += ROUND) {
-        float4 sv[ROUND];
-#pragma unroll
-        for (int n = 0; n < ROUND; ++n)
-            sv[n] = ld4(r_src, on ? rowbase + (unsigned)(nb[n0 + n] >= 0 ? nb[n0 + n] : v) * (DB_C * 4) + 4 * c0 : OOB);
-        if (LOAD_SLICE && n0 == 0) db_load_slice(bw, packed, wave, lane);
-#pragma unroll
-        for (int n = 0; n < ROUND; ++n) {
-            if (nb[n0 + n] >= 0) { // ELL order == CSR order of the row
-                facc.x += wv[n0 + n] * sv[n].x, facc.y += wv[n0 + n] * sv[n].y, facc.z += wv[n0 + n] * sv[n].z, facc.w += wv[n0 + n] * sv[n].w;
-            }
-        }
-    }
-    for (; e < end; e += 4) { // (a group of 16 lanes leaves at its own row's end)
-        int tc[4];
-        float tw[4];
-        float4 tv[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int at = e + t < end ? e + t : end - 1;
-            tc[t] = over_col[at], tw[t] = over_val[at];
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) tv[t] = ld4(r_src, e + t < end ? rowbase + (unsigned)tc[t] * (DB_C * 4) + 4 * c0 : OOB);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            if (e + t < end) {
-                facc.x += tw[t] * tv[t].x, facc.y += tw[t] * tv[t].y, facc.z += tw[t] * tv[t].z, facc.w += tw[t] * tv[t].w;
-            }
-        }
-    }
-    return facc;
-}
-
-// relu?(Z) (+ residual, * scale) of one element; `on` = false: a row beyond the last, zero
-__device__ __forceinline__ float dp_act_one(const geom_deform_plain_fwd &a, float zz, float r, bool on)
-{
-    float y = zz;
-    if (a.relu) y = y <= 0.f ? 0.f : y;
-    if (a.res) y = (r + y) * a.scale;
-    return on ? y : 0.f;
-}
-
-template <bool PRODUCT, bool LOAD_SLICE>
-__device__ __forceinline__ void dp_fwd_row_block(const geom_deform_plain_fwd &a, const int rb, float *lds, DbSlice &bw)
-{
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int x = lane & 15, g = lane >> 4; // matrix-core coordinates
-    const int rl = tid >> 4, j = tid & 15;  // row of the block and float4 group of the gather thread
-    const int c0 = 4 * j;
-    const int rows = a.b * a.nv;
-    const int r = rb * 16 + rl;
-    const bool on = r < rows;
-    const int mesh = on ? r / a.nv : 0, v = on ? r - mesh * a.nv : 0;
-    const int64_t op_bytes = (int64_t)rows * DB_C * 4;
-    const __amdgpu_buffer_rsrc_t r_src = rsrc(a.s_in, op_bytes);
-    const unsigned rowbase = (unsigned)mesh * (unsigned)a.nv * (DB_C * 4);
-    const unsigned own_off = on ? (unsigned)r * (DB_C * 4) + 4 * c0 : OOB;
-    float4 bias4[3], rv[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) bias4[i] = db_bias4(a, c0, i), rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.res) {
-        const __amdgpu_buffer_rsrc_t r_res = rsrc(a.res, ((int64_t)rows - 1) * a.res_ld * 4 + DB_C * 4);
-        const unsigned roff = (unsigned)r * (unsigned)a.res_ld * 4u + 4 * c0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) rv[i] = ld4(r_res, on ? roff + 4 * DB_K * i : OOB);
-    }
-    // (a later row-block of the workgroup holds the slice already: its table rows go in two rounds of four, as di_row_block's)
-    constexpr int ROUND = LOAD_SLICE || !PRODUCT ? DB_W : DB_W / 2;
-    float4 z[3];
-#pragma unroll
-    for (int i = 1; i < 3; ++i) z[i] = ld4(r_src, db_own(own_off, i));
-    z[0] = dp_aggregate<LOAD_SLICE, ROUND>(r_src, on, rowbase, v, c0, a.ell_col, a.ell_val, a.over_ptr, a.over_col, a.over_val, bw,
-                                           a.w_next, wave, lane);
-    db_add_bias(z, bias4);
-    float4 xo[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        xo[i] = make_float4(dp_act_one(a, z[i].x, rv[i].x, on), dp_act_one(a, z[i].y, rv[i].y, on), dp_act_one(a, z[i].z, rv[i].z, on),
-                            dp_act_one(a, z[i].w, rv[i].w, on));
-    if (a.z_out) {
-        const __amdgpu_buffer_rsrc_t r_z = rsrc(a.z_out, op_bytes);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) st4(r_z, db_own(own_off, i), z[i]);
-    }
-    if (a.x_out) {
-        const __amdgpu_buffer_rsrc_t r_x = rsrc(a.x_out, op_bytes);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) st4(r_x, db_own(own_off, i), xo[i]);
-    }
-    if (!PRODUCT) {
-        if (a.w_head) { // the coordinate head's raw support s_head[row] = X'[row] . W_head
-            float h[3];
-            db_head_fwd(xo, a.w_head, c0, h);
-            if (j == 0 && on) {
-                float *dst = a.s_head + (size_t)r * 3;
-                dst[0] = h[0], dst[1] = h[1], dst[2] = h[2];
-            }
-        }
-        return;
-    }
-    db_to_panel(lds, rl, c0, xo); // (rows beyond the last are zero rows of the panel)
-    __syncthreads();
-    float *stage = lds + RB_PANEL;
-    db_product(bw, lds, stage, wave, x, g);
-    __syncthreads();
-    const __amdgpu_buffer_rsrc_t r_s = rsrc(a.s_out, op_bytes);
-    db_store_tile<false>(stage, r_s, [&](int rr) {
-        const int row = rb * 16 + rr;
-        return row < rows ? (unsigned)row * (DB_C * 4) : OOB;
-    });
-}
-
-// logical workgroup -> its run of row-blocks [first, first + count): di_fwd_kernel's dealing
-__device__ __forceinline__ bool dp_run(int nrb, int nwg, int per_xcd, int &first, int &count)
-{
-    const int lw = geom::xcd_run_item(blockIdx.x, per_xcd);
+    const int lw = geom::xcd_run_item(blockIdx.x, per_xcd); // contiguous runs per XCD (workgroup w runs on XCD w % 8)
     if (lw >= nwg) return false;
     const int q = nrb / nwg, rem = nrb - q * nwg;
     first = lw * q + (lw < rem ? lw : rem), count = q + (lw < rem ? 1 : 0);
     return true;
 }
 
+// (two kernel names: tools and profiles tell the eval launch from the plain one by them)
+template <bool PRODUCT>
+__global__ __launch_bounds__(DB_THREADS, 2) void di_fwd_kernel(geom_deform_infer a, int nrb, int nwg, int per_xcd)
+{
+    __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST];
+    int first, count;
+    if (!db_deal_row_blocks(nrb, nwg, per_xcd, first, count)) return;
+    DbSlice bw;
+    di_row_block<PRODUCT, PRODUCT>(a, first, lds, bw);
+    for (int i = 1; i < count; ++i) di_row_block<PRODUCT, false>(a, first + i, lds, bw);
+}
 template <bool PRODUCT>
 __global__ __launch_bounds__(DB_THREADS, 2) void dp_fwd_kernel(geom_deform_plain_fwd a, int nrb, int nwg, int per_xcd)
 {
     __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST];
     int first, count;
-    if (!dp_run(nrb, nwg, per_xcd, first, count)) return;
+    if (!db_deal_row_blocks(nrb, nwg, per_xcd, first, count)) return;
     DbSlice bw;
     dp_fwd_row_block<PRODUCT, PRODUCT>(a, first, lds, bw);
     for (int i = 1; i < count; ++i) dp_fwd_row_block<PRODUCT, false>(a, first + i, lds, bw);
@@ -1136,8 +1140,8 @@ __device__ __forceinline__ void dp_bwd_row_block(const geom_deform_plain_bwd &a,
         float4 gs[3]; // (stored: the layer above's weight gradient reads it, X^T . G)
 #pragma unroll
         for (int i = 1; i < 3; ++i) gs[i] = ld4(r_src, db_own(own_off, i));
-        gs[0] = dp_aggregate<LOAD_SLICE, ROUND>(r_src, on, rowbase, v, c0, a.ell_col_t, a.ell_val_t, a.over_ptr_t, a.over_col_t, a.over_val_t,
-                                                bw, a.wt_up, wave, lane);
+        gs[0] = db_row_aggregate<LOAD_SLICE, ROUND>(r_src, on, rowbase, v, c0, a.ell_col_t, a.ell_val_t, a.over_ptr_t, a.over_col_t,
+                                                    a.over_val_t, bw, a.wt_up, wave, lane);
 #pragma unroll
         for (int i = 0; i < 3; ++i) st4(r_ds, db_own(own_off, i), gs[i]);
         db_to_panel(lds, rl, c0, gs); // (rows beyond the last read zeros: zero rows of the tile)
@@ -1206,7 +1210,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dp_bwd_kernel(geom_deform_plain
 {
     __shared__ __attribute__((aligned(16))) float lds[RB_PANEL + RB_CST];
     int first, count;
-    if (!dp_run(nrb, nwg, per_xcd, first, count)) return;
+    if (!db_deal_row_blocks(nrb, nwg, per_xcd, first, count)) return;
     DbSlice bw;
     dp_bwd_row_block<PRODUCT, PRODUCT>(a, first, lds, bw);
     for (int i = 1; i < count; ++i) {
@@ -1336,14 +1340,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void dbw_fwd_kernel(geom_deform_fwd 
             for (int i = 0; i < 3; ++i) st4(r_x, db_own(own(t), i), xo[i]);
             if (!PRODUCT) {
                 // the coordinate head's product inside the last hidden layer's launch
-                if (a.w_head && a.s_head) {
-                    float h[3];
-                    db_head_fwd(xo, a.w_head, c0, h);
-                    if (j == 0 && mesh_on) {
-                        float *dst = a.s_head + ((size_t)(16 * t + rl) * a.nv + v) * 3;
-                        dst[0] = h[0], dst[1] = h[1], dst[2] = h[2];
-                    }
-                }
+                if (a.w_head && a.s_head) db_head_store(xo, a.w_head, a.s_head, (size_t)(16 * t + rl) * a.nv + v, mesh_on, c0);
             } else {
                 // (the panel's readers and the staging tile's are behind the previous tile's two barriers)
                 db_to_panel(lds, rl, c0, xo);
@@ -1592,6 +1589,17 @@ int db_launch_layer(const Args *args, void *stream, int min_b, int max_b)
     return geom::launch_status();
 }
 
+// The grid of a row-block launch (the eval and the two plain entry points): ceil(b nv / 16) row-blocks dealt to at most DI_WGS
+// logical workgroups, in runs per XCD.  launch(grid, block, nrb, nwg, per_xcd) enqueues the kernel.
+template <typename Args, typename Launch>
+int db_launch_row_blocks(const Args &l, Launch launch)
+{
+    const int nrb = (l.b * l.nv + 15) / 16;
+    const int nwg = nrb < DI_WGS ? nrb : DI_WGS, per_xcd = (nwg + 7) / 8;
+    launch(dim3(8 * per_xcd), dim3(DB_THREADS), nrb, nwg, per_xcd);
+    return geom::launch_status();
+}
+
 } // namespace
 
 #ifdef DB_PROBE_STAMPS
@@ -1673,13 +1681,11 @@ extern "C" int geom_deform_infer_fwd_f32(const geom_deform_infer *args, void *st
     if (!db_aligned16(a.tail_col) || !db_aligned16(a.tail_val)) return GEOM_EINVAL;
     geom_deform_infer l = a;
     if (!l.res) l.scale = 1.f;
-    const int nrb = (a.b * a.nv + 15) / 16;
-    const int nwg = nrb < DI_WGS ? nrb : DI_WGS, per_xcd = (nwg + 7) / 8;
-    const dim3 grid(8 * per_xcd), block(DB_THREADS);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (l.w_next) hipLaunchKernelGGL((di_fwd_kernel<true>), grid, block, 0, s, l, nrb, nwg, per_xcd);
-    else hipLaunchKernelGGL((di_fwd_kernel<false>), grid, block, 0, s, l, nrb, nwg, per_xcd);
-    return geom::launch_status();
+    return db_launch_row_blocks(l, [&](dim3 grid, dim3 block, int nrb, int nwg, int per_xcd) {
+        if (l.w_next) hipLaunchKernelGGL((di_fwd_kernel<true>), grid, block, 0, s, l, nrb, nwg, per_xcd);
+        else hipLaunchKernelGGL((di_fwd_kernel<false>), grid, block, 0, s, l, nrb, nwg, per_xcd);
+    });
 }
 
 namespace {
@@ -1700,14 +1706,6 @@ bool dp_pitch_ok(const void *p, int ld, int b, int nv)
     if (ld && ld < DB_C) return false;
     return !((uintptr_t)p & 3) && (int64_t)b * nv * (ld ? ld : DB_C) < (1LL << 29);
 }
-template <typename Args, typename Launch>
-int dp_launch(const Args &l, Launch launch)
-{
-    const int nrb = (l.b * l.nv + 15) / 16;
-    const int nwg = nrb < DI_WGS ? nrb : DI_WGS, per_xcd = (nwg + 7) / 8;
-    launch(dim3(8 * per_xcd), dim3(DB_THREADS), nrb, nwg, per_xcd);
-    return geom::launch_status();
-}
 } // namespace
 
 // One hidden layer of the BatchNorm-free block, forward (see dp_fwd_row_block).  Every invalid argument is GEOM_EINVAL, decided
@@ -1727,7 +1725,7 @@ extern "C" int geom_deform_plain_fwd_f32(const geom_deform_plain_fwd *args, void
         return GEOM_EINVAL;
     if (!l.res) l.scale = 1.f;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dp_launch(l, [&](dim3 grid, dim3 block, int nrb, int nwg, int per_xcd) {
+    return db_launch_row_blocks(l, [&](dim3 grid, dim3 block, int nrb, int nwg, int per_xcd) {
         if (l.w_next) hipLaunchKernelGGL((dp_fwd_kernel<true>), grid, block, 0, s, l, nrb, nwg, per_xcd);
         else hipLaunchKernelGGL((dp_fwd_kernel<false>), grid, block, 0, s, l, nrb, nwg, per_xcd);
     });
@@ -1751,7 +1749,7 @@ extern "C" int geom_deform_plain_bwd_f32(const geom_deform_plain_bwd *args, void
         return GEOM_EINVAL;
     if (!l.has_res) l.scale = 1.f;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dp_launch(l, [&](dim3 grid, dim3 block, int nrb, int nwg, int per_xcd) {
+    return db_launch_row_blocks(l, [&](dim3 grid, dim3 block, int nrb, int nwg, int per_xcd) {
         if (product) hipLaunchKernelGGL((dp_bwd_kernel<true>), grid, block, 0, s, l, nrb, nwg, per_xcd);
         else hipLaunchKernelGGL((dp_bwd_kernel<false>), grid, block, 0, s, l, nrb, nwg, per_xcd);
     });

@@ -97,13 +97,18 @@ def _servable(block, features, pooled, csr):
     return True
 
 
-def serves(block, features, pooled, csr):
-    """Whether the fused training launches serve this call of `block` (a models.BatchMeshDeformationBlock): _servable, in
-    training mode with gradients, at most 16 meshes, local BatchNorm statistics with a momentum (each layer takes its own)."""
-    if not block.training or not torch.is_grad_enabled() or (features.dim() == 3 and features.shape[0] > 16):
+def _serves_training(block, features, pooled, csr, lo, hi):
+    """_servable in training mode with gradients, lo <= b <= hi meshes, local BatchNorm statistics with a momentum (each layer
+    takes its own)."""
+    if not block.training or not torch.is_grad_enabled() or (features.dim() == 3 and not lo <= features.shape[0] <= hi):
         return False
     return _servable(block, features, pooled, csr) and not any(
         bn._synchronised() or bn.momentum is None for bn in hidden_layers(block)[1])
+
+
+def serves(block, features, pooled, csr):
+    """Whether the fused training launches serve this call of `block` (a models.BatchMeshDeformationBlock): at most 16 meshes."""
+    return _serves_training(block, features, pooled, csr, 0, 16)
 
 
 # Training batches of 17 .. WIDE_MAX_BATCH meshes on the launches with ceil(b / 16) row tiles per vertex
@@ -117,12 +122,7 @@ WIDE_MAX_BATCH = _lib.DEFORM_WIDE_MAX_B
 def serves_wide(block, features, pooled, csr):
     """Whether the wide training launches serve this call of `block`: the clauses of serves() with 17 <= b <= WIDE_MAX_BATCH
     meshes, and the `wide` switch."""
-    if not wide or not block.training or not torch.is_grad_enabled() or features.dim() != 3:
-        return False
-    if not 16 < features.shape[0] <= WIDE_MAX_BATCH:
-        return False
-    return _servable(block, features, pooled, csr) and not any(
-        bn._synchronised() or bn.momentum is None for bn in hidden_layers(block)[1])
+    return wide and features.dim() == 3 and _serves_training(block, features, pooled, csr, 17, WIDE_MAX_BATCH)
 
 
 TAIL = _lib.DEFORM_TAIL      # entries of an adjacency row beyond the 8-wide neighbour table that the launches take
@@ -292,6 +292,103 @@ def chain_backward(layers, done, ds_first=None):
     _lib.call("geom_deform_chain_bwd_f32", len(built), [b[0] for b in built], done, ds_first)
 
 
+def _stacked(xs):
+    """x_out policy of _forward_walk: every layer's output is kept, layer i's in xs[i - 1] (a backward pass reads them)."""
+    return lambda layer: xs[layer.index - 1]
+
+
+def _dense_like(t):
+    return torch.empty_like(t, memory_format=torch.contiguous_format)  # (the launches assume a pitch of 192)
+
+
+def _rotating(like, out):
+    """x_out policy of _forward_walk: only what a later launch or the caller reads is stored.  The outputs a residual taps
+    (layer 2k's is the residual of layer 2k + 2, and layer 12's of layer 13) go to two buffers in turn, the last layer's to `out`."""
+    bufs = (_dense_like(like), _dense_like(like))
+    return lambda layer: out if layer.head else (bufs[(layer.index // 2) & 1] if layer.tap else None)
+
+
+def _forward_walk(s1, lead, x_out_of, w2, w_head, s_head):
+    """The forward walk over SCHEDULE that every route makes.  Yields per layer (layer, residual tensor or None, s_in, x_out,
+    keywords): s_in = s1, then the two support buffers in turn; x_out = x_out_of(layer) (_stacked or _rotating), remembered for
+    the layers whose residual it is; keywords = w_next (w2[i - 1], packed) / s_out where a product follows, w_head / s_head
+    where the coordinate head rides in the launch."""
+    s_buf = (_dense_like(s1), _dense_like(s1))
+    kept = {}
+    s_cur = s1
+    for layer in SCHEDULE:
+        i, src = layer.index, layer.residual
+        res = None if src is None else (lead if src == "lead" else kept[src])
+        x_out = x_out_of(layer)
+        yield layer, res, s_cur, x_out, dict(w_next=w2[i - 1] if layer.product else None, s_out=s_buf[i & 1] if layer.product else None,
+                                             w_head=w_head if layer.head else None, s_head=s_head if layer.head else None)
+        if x_out is not None:
+            kept[i] = x_out
+        s_cur = s_buf[i & 1]
+
+
+def _backward_walk(xs, wts, head, g_a, g_b, w_head, want_dw_head, partial_rows, emit, add=torch.add):
+    """The backward walk over reversed(SCHEDULE) of both autograd nodes.  xs [13, *shape, 192] = the kept outputs, wts = the
+    packed transposed weights; head: the node's second output is the coordinate head's raw support (g_b = its gradient) rather
+    than a second handle on the features.  partial_rows: rows of a layer's bias-gradient (and head-weight) partials -- nv, or
+    ceil(nv / 16) for the launches that write them per row-block.  emit(i, top, what) launches layer i (or collects it for a
+    chain launch) with its own operands beside `what` (the keywords both launches share); add(a, b) joins two residual
+    gradients that reach one layer.  Returns (dzs, dss, colsum, dw_head, g_lead)."""
+    L = LAYERS
+    shape, c = tuple(xs.shape[1:]), xs.shape[-1]
+    f32 = dict(dtype=torch.float32, device=xs.device)
+    ds_head = dw_head = None
+    if head:                           # g_b is the gradient of the head's raw support
+        if g_b is not None:
+            ds_head = g_b.contiguous()
+            dw_head = torch.empty(partial_rows, c * 3, **f32) if want_dw_head else None
+        g_top, g_top2 = g_a, None
+    else:
+        g_top, g_top2 = (g_a, g_b) if g_a is not None else (g_b, None)      # (read in place at any row pitch)
+    dzs = torch.empty(L, *shape, **f32)            # dzs[i - 1] = dZ_i
+    dss = torch.empty(L - 1, *shape, **f32)        # dss[i - 2] = dS_i = gradient of layer i's raw support, i = 2..L
+    colsum = torch.empty(L, partial_rows, c, **f32)
+    pending = {}                                   # j -> gradient that reaches layer j's output through a residual average
+    g_lead = None
+    for i, src, _, top, _ in reversed(SCHEDULE):
+        grad_res = torch.empty(*shape, **f32) if src is not None else None
+        common = dict(dz=dzs[i - 1], grad_res=grad_res, colsum=colsum[i - 1])
+        if top:
+            what = dict(g=g_top, g2=g_top2, ds_head=ds_head, w_head=w_head if ds_head is not None else None,
+                        x_top=xs[L - 1] if dw_head is not None else None, dw_head=dw_head, **common)
+        else:
+            what = dict(dz_up=dzs[i], ds_up=dss[i - 1], wt_up=wts[i - 1], g2=pending.pop(i, None), **common)
+        emit(i, top, what)
+        if src == "lead":
+            g_lead = grad_res
+        elif src is not None:
+            pending[src] = add(pending[src], grad_res) if src in pending else grad_res
+    assert not pending, "a residual gradient was left without its layer"
+    return dzs, dss, colsum, dw_head, g_lead
+
+
+def _reduce_gradients(xs, dss, colsum, dw_head):
+    """The end of a backward pass: (bias gradients [13, 192], weight gradients [12, 192, 192], head-weight gradient [576] or
+    None).  dW_i = X_i^T . dS_i, i = 2..L: one strided-batched product over the stacked activations and support gradients.
+    Bias gradients: the launches' partial column sums added up in row order, all 13 layers and the head's [192, 3] partials in
+    ONE launch (torch's reduction over the middle axis of [13, 482, 192] took 38 us; geom_colsum_batch_f32 is the reduction
+    the aggregation backward's partials go through: fixed order, ~5 us)."""
+    L = LAYERS
+    c, parts = xs.shape[-1], colsum.shape[1]
+    f32 = dict(dtype=torch.float32, device=xs.device)
+    g_w = torch.bmm(xs[:L - 1].view(L - 1, -1, c).transpose(1, 2), dss.view(L - 1, -1, c))
+    g_bias = torch.empty(L, c, **f32)
+    jobs = [(colsum[i], c, g_bias[i]) for i in range(L)]
+    g_head = None
+    if dw_head is not None:
+        g_head = torch.empty(c * 3, **f32)
+        jobs.append((dw_head, c * 3, g_head))
+    n = len(jobs)
+    _lib.call("geom_colsum_batch_f32", n, [j[0] for j in jobs], (ctypes.c_int * n)(*([parts] * n)),
+              (ctypes.c_int * n)(*[j[1] for j in jobs]), [j[2] for j in jobs])
+    return g_bias, g_w, g_head
+
+
 class _HiddenChain(torch.autograd.Function):
     """X_14 = the thirteen hidden layers applied to S_1 (see the module docstring).  apply(s1, lead, csr, stats, momentum,
     eps, *biases[13], *weights[12] (gc2..gc13), *bn_weights[13], *bn_biases[13]); stats = [(running_mean, running_var)] * 13,
@@ -316,8 +413,6 @@ class _HiddenChain(torch.autograd.Function):
         xs = torch.empty(L, b, nv, c, **f32)          # xs[i - 1] = X_{i+1}, the output of layer i
         zs = torch.empty(L, b, nv, c, **f32)          # zs[i - 1] = Z_i, what BN_i normalised
         means, invstds = torch.empty(L, nv, **f32), torch.empty(L, nv, **f32)
-        s_buf = (torch.empty(b, nv, c, **f32), torch.empty(b, nv, c, **f32))
-        s_cur = s1
         # (a chain launch needs a symmetric pattern: vertex v rewrites its support row once the vertices of ITS row are done
         # with the previous layer, and those must be all the vertices that gather v's row -- A[u][v] != 0 => A[v][u] != 0)
         # (above 16 meshes: the wide launches, layer by layer -- never a chain, no counters)
@@ -330,17 +425,14 @@ class _HiddenChain(torch.autograd.Function):
         wh = s_head = None
         if w_head is not None:
             wh, s_head = head_weight(w_head), torch.empty(b, nv, 3, **f32)
-        for i, src, nxt, head, _ in SCHEDULE:
-            res = None if src is None else (lead if src == "lead" else xs[src - 1])
-            call = ((s_cur, biases[i - 1], csr, bn_w[i - 1], bn_b[i - 1], stats[i - 1][0], stats[i - 1][1], True, momentum[i - 1],
-                     eps[i - 1], relu, res, 0.5, zs[i - 1], xs[i - 1], means[i - 1], invstds[i - 1]),
-                    dict(w_next=w2[i - 1] if nxt else None, s_out=s_buf[i & 1] if nxt else None,
-                         w_head=wh if head else None, s_head=s_head if head else None))
+        for layer, res, s_in, x_out, kw in _forward_walk(s1, lead, _stacked(xs), w2, wh, s_head):
+            i = layer.index
+            call = ((s_in, biases[i - 1], csr, bn_w[i - 1], bn_b[i - 1], stats[i - 1][0], stats[i - 1][1], True, momentum[i - 1],
+                     eps[i - 1], relu, res, 0.5, zs[i - 1], x_out, means[i - 1], invstds[i - 1]), kw)
             if as_chain:
                 calls.append(call)
             else:
                 forward_launch(*call[0], **call[1])
-            s_cur = s_buf[i & 1]
         if as_chain:
             chain_forward(calls, counters[0])
         ctx.counters = counters[1] if as_chain else None
@@ -349,9 +441,7 @@ class _HiddenChain(torch.autograd.Function):
         ctx.set_materialize_grads(False)      # a handle nobody uses (the last block's features) arrives as None, not as 5.9 MB of zeros
         ctx.save_for_backward(xs, zs, means, invstds, wts, *bn_w, *bn_b, *([wh] if w_head is not None else []))
         out = xs[L - 1]
-        if w_head is not None:
-            return out, s_head
-        return out, _layers._alias(out)
+        return (out, s_head) if w_head is not None else (out, _layers._alias(out))
 
     @staticmethod
     def backward(ctx, g_a, g_b):
@@ -366,21 +456,8 @@ class _HiddenChain(torch.autograd.Function):
         n_in = 7 + 4 * L - 1
         if g_a is None and g_b is None:
             return (None,) * n_in
-        ds_head = w_head = dw_head = None
-        if ctx.head:                       # g_b is the gradient of the head's raw support [B,V,3]
-            w_head = saved[5 + 2 * L]
-            if g_b is not None:
-                ds_head = g_b.contiguous()
-                dw_head = torch.empty(nv, c * 3, **f32) if ctx.needs_input_grad[6] else None
-            g_top, g_top2 = g_a, None
-        else:
-            g_top, g_top2 = (g_a, g_b) if g_a is not None else (g_b, None)      # (read in place at any row pitch: layer_backward)
-        dzs = torch.empty(L, b, nv, c, **f32)         # dzs[i - 1] = dZ_i
-        dss = torch.empty(L - 1, b, nv, c, **f32)     # dss[i - 2] = dS_i = gradient of layer i's raw support, i = 2..L
+        w_head = saved[5 + 2 * L] if ctx.head else None
         g_bnw, g_bnb = torch.empty(L, nv, **f32), torch.empty(L, nv, **f32)
-        colsum = torch.empty(L, nv, c, **f32)
-        pending = {}                                   # j -> gradient that reaches layer j's output through a residual average
-        g_lead = None
         # (the forward ran as one launch: so does the backward, if this stream still owns the device's chain launches)
         counters = ctx.counters
         # (its counters are good for ONE pass: a second backward over a retained graph takes the launches per layer)
@@ -388,30 +465,22 @@ class _HiddenChain(torch.autograd.Function):
         if calls is not None:
             ctx.counters = None
         backward_launch = layer_backward if b <= 16 else wide_layer_backward
-        for i, src, _, top, _ in reversed(SCHEDULE):
-            grad_res = torch.empty(b, nv, c, **f32) if src is not None else None
-            common = dict(relu=ctx.relu, has_res=src is not None, scale=0.5, dz=dzs[i - 1], grad_bn_w=g_bnw[i - 1], grad_bn_b=g_bnb[i - 1],
-                          grad_res=grad_res, colsum=colsum[i - 1])
+
+        def emit(i, top, what):
             where = ((b, nv, c), csr, zs[i - 1], bn_w[i - 1], bn_b[i - 1], means[i - 1], invstds[i - 1])
-            if top:
-                what = dict(g=g_top, g2=g_top2, ds_head=ds_head, w_head=w_head if ds_head is not None else None,
-                            x_top=xs[L - 1] if dw_head is not None else None, dw_head=dw_head, **common)
-            else:
-                what = dict(dz_up=dzs[i], ds_up=dss[i - 1], wt_up=wts[i - 1], g2=pending.pop(i, None), **common)
+            what = dict(what, relu=ctx.relu, has_res=SCHEDULE[i - 1].residual is not None, scale=0.5, grad_bn_w=g_bnw[i - 1],
+                        grad_bn_b=g_bnb[i - 1])
             if calls is None:
                 backward_launch(*where, **what)
             else:
                 calls.append((where, what))
-            if src == "lead":
-                g_lead = grad_res
-            elif src is not None:
-                if src in pending:
-                    if calls is not None:
-                        raise RuntimeError("two residual gradients for one layer: not expressible inside one launch")
-                    pending[src] = pending[src] + grad_res
-                else:
-                    pending[src] = grad_res
-        assert not pending, "a residual gradient was left without its layer"
+
+        def add(first, second):
+            if calls is not None:
+                raise RuntimeError("two residual gradients for one layer: not expressible inside one launch")
+            return first + second
+
+        dzs, dss, colsum, dw_head, g_lead = _backward_walk(xs, wts, ctx.head, g_a, g_b, w_head, ctx.needs_input_grad[6], nv, emit, add)
         # dS_1 = aggregation backward of the first layer (no activation between S_1 and Z_1): a last step of the chain launch, or
         # the existing operator
         if calls is not None:
@@ -419,25 +488,10 @@ class _HiddenChain(torch.autograd.Function):
             chain_backward(calls, counters, ds_first=g_s1)
         else:
             g_s1, _ = _layers.aggregate_backward(dzs[0], csr, 64, _layers._ACT_NONE, None, None, False)
-        rows = b * nv
-        g_w = torch.bmm(xs[:L - 1].view(L - 1, rows, c).transpose(1, 2), dss.view(L - 1, rows, c))     # dW_i = X_i^T . dS_i, i = 2..L
-        # bias gradients: the vertices' column sums added up in vertex order, all 13 layers in ONE launch (torch's reduction over
-        # the middle axis of [13, 482, 192] took 38 us; geom_colsum_batch_f32 is the reduction the aggregation backward's
-        # partials go through: fixed order, ~5 us)
-        g_bias = torch.empty(L, c, **f32)
-        jobs = [(colsum[i], c, g_bias[i]) for i in range(L)]
-        g_head = None
-        if dw_head is not None:            # the head's weight gradient: the vertices' [192, 3] partials added up by the same launch
-            g_head = torch.empty(c * 3, **f32)
-            jobs.append((dw_head, c * 3, g_head))
-        n = len(jobs)
-        _lib.call("geom_colsum_batch_f32", n, [j[0] for j in jobs], (ctypes.c_int * n)(*([nv] * n)),
-                  (ctypes.c_int * n)(*[j[1] for j in jobs]), [j[2] for j in jobs])
+        g_bias, g_w, g_head = _reduce_gradients(xs, dss, colsum, dw_head)
         grads = [g_bias[i] for i in range(L)] + [g_w[i].view(1, c, c) for i in range(L - 1)] \
             + [g_bnw[i] for i in range(L)] + [g_bnb[i] for i in range(L)]
-        g_wh = None
-        if g_head is not None:
-            g_wh = g_head.view(ctx.head_shape)
+        g_wh = None if g_head is None else g_head.view(ctx.head_shape)
         return (g_s1, g_lead, None, None, None, None, g_wh, *grads)
 
 
@@ -476,26 +530,13 @@ def inference_chain(block, s1, lead, csr, head=None):
     f32 = dict(dtype=torch.float32, device=dev)
     gcs, bns = hidden_layers(block)
     w2, _ = pack_weights([g.weight1 for g in gcs[1:]])
-    # outputs a residual reads (SCHEDULE's tap): layer 2k's output is the residual of layer 2k + 2 (and layer 12's of layer 13),
-    # so two buffers in turn; the last layer writes the caller's tensor
-    x_bufs = (torch.empty(b, nv, c, **f32), torch.empty(b, nv, c, **f32))
-    s_bufs = (torch.empty(b, nv, c, **f32), torch.empty(b, nv, c, **f32))
     out = torch.empty(b, nv, c, **f32)
     wh = s_head = None
     if head is not None:
         wh, s_head = head_weight(head.weight1), torch.empty(b, nv, 3, **f32)
-    xs = {}
-    s_cur = s1
-    for i, src, _, last, keep in SCHEDULE:
-        res = None if src is None else (lead if src == "lead" else xs[src])
-        x_out = out if last else (x_bufs[(i // 2) & 1] if keep else None)
-        bn = bns[i - 1]
-        infer_layer_forward(s_cur, gcs[i - 1].bias, csr, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu, res,
-                            0.5, x_out, w_next=None if last else w2[i - 1], s_out=None if last else s_bufs[i & 1],
-                            w_head=wh if last else None, s_head=s_head if last else None)
-        if x_out is not None:
-            xs[i] = x_out
-        s_cur = s_bufs[i & 1]
+    for layer, res, s_in, x_out, kw in _forward_walk(s1, lead, _rotating(s1, out), w2, wh, s_head):
+        gc, bn = gcs[layer.index - 1], bns[layer.index - 1]
+        infer_layer_forward(s_in, gc.bias, csr, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu, res, 0.5, x_out, **kw)
     return out, out, s_head
 
 
@@ -609,27 +650,17 @@ class _PlainChain(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=s1.device)
         train = any(ctx.needs_input_grad)
         # with gradients every layer's Z (the mask: X' loses it under a residual) and X' (the weight gradients) are kept;
-        # without, only what a later launch reads: the outputs a residual taps, in two buffers in turn
+        # without, only what a later launch reads (_rotating)
         xs = torch.empty(L, nv, c, **f32) if train else None
         zs = torch.empty(L, nv, c, **f32) if train else None
-        x_bufs = None if train else (torch.empty(nv, c, **f32), torch.empty(nv, c, **f32))
         out = xs[L - 1] if train else torch.empty(nv, c, **f32)
-        s_buf = (torch.empty(nv, c, **f32), torch.empty(nv, c, **f32))
         w2, wts = pack_weights(weights)     # w2[i - 1] / wts[i - 1] = W_{i+1} / its transpose, in register-slice order
         wh = s_head = None
         if w_head is not None:
             wh, s_head = head_weight(w_head), torch.empty(nv, 3, **f32)
-        kept = {}
-        s_cur = s1
-        for i, src, nxt, head, tap in SCHEDULE:
-            res = None if src is None else (lead3 if src == "lead" else kept[src])
-            x_out = xs[i - 1] if train else (out if head else (x_bufs[(i // 2) & 1] if tap else None))
-            plain_layer_forward(s_cur, biases[i - 1], csr, relu, res, 0.5, z_out=zs[i - 1] if train else None, x_out=x_out,
-                                w_next=w2[i - 1] if nxt else None, s_out=s_buf[i & 1] if nxt else None,
-                                w_head=wh if head else None, s_head=s_head if head else None)
-            if x_out is not None:
-                kept[i] = x_out
-            s_cur = s_buf[i & 1]
+        for layer, res, s_in, x_out, kw in _forward_walk(s1, lead3, _stacked(xs) if train else _rotating(s1, out), w2, wh, s_head):
+            i = layer.index
+            plain_layer_forward(s_in, biases[i - 1], csr, relu, res, 0.5, z_out=zs[i - 1] if train else None, x_out=x_out, **kw)
         ctx.csr, ctx.relu, ctx.head = csr, relu, w_head is not None
         ctx.head_shape = None if w_head is None else tuple(w_head.shape)
         ctx.set_materialize_grads(False)
@@ -643,51 +674,19 @@ class _PlainChain(torch.autograd.Function):
         xs, zs, wts = ctx.saved_tensors[:3]
         csr = ctx.csr
         _, nv, c = xs.shape
-        f32 = dict(dtype=torch.float32, device=xs.device)
         n_in = 4 + 2 * L - 1
         if g_a is None and g_b is None:
             return (None,) * n_in
-        ds_head = w_head = dw_head = None
-        nrb = (nv + 15) // 16
-        if ctx.head:                       # g_b is the gradient of the head's raw support [V,3]
-            w_head = ctx.saved_tensors[3]
-            if g_b is not None:
-                ds_head = g_b.contiguous()
-                dw_head = torch.empty(nrb, c * 3, **f32) if ctx.needs_input_grad[3] else None
-            g_top, g_top2 = g_a, None
-        else:
-            g_top, g_top2 = (g_a, g_b) if g_a is not None else (g_b, None)
-        dzs = torch.empty(L, nv, c, **f32)          # dzs[i - 1] = dZ_i
-        dss = torch.empty(L - 1, nv, c, **f32)      # dss[i - 2] = dS_i, i = 2..L
-        colsum = torch.empty(L, nrb, c, **f32)      # per row-block partials of the bias gradients
-        pending = {}                                # j -> gradient that reaches layer j's output through a residual average
-        g_lead = None
-        for i, src, _, top, _ in reversed(SCHEDULE):
-            grad_res = torch.empty(nv, c, **f32) if src is not None else None
-            common = dict(grad_res=grad_res, colsum=colsum[i - 1])
-            if top:
-                what = dict(g=g_top, g2=g_top2, ds_head=ds_head, w_head=w_head if ds_head is not None else None,
-                            x_top=xs[L - 1] if dw_head is not None else None, dw_head=dw_head, **common)
-            else:
-                what = dict(dz_up=dzs[i], ds_up=dss[i - 1], wt_up=wts[i - 1], g2=pending.pop(i, None), **common)
-            plain_layer_backward((1, nv, c), csr, zs[i - 1], ctx.relu, src is not None, 0.5, dzs[i - 1], **what)
-            if src == "lead":
-                g_lead = grad_res
-            elif src is not None:
-                pending[src] = pending[src] + grad_res if src in pending else grad_res
-        assert not pending, "a residual gradient was left without its layer"
+        w_head = ctx.saved_tensors[3] if ctx.head else None
+
+        def emit(i, top, what):
+            plain_layer_backward((1, nv, c), csr, zs[i - 1], ctx.relu, SCHEDULE[i - 1].residual is not None, 0.5, **what)
+
+        # (the launches write the bias-gradient and head-weight partials per row-block)
+        dzs, dss, colsum, dw_head, g_lead = _backward_walk(xs, wts, ctx.head, g_a, g_b, w_head, ctx.needs_input_grad[3], (nv + 15) // 16, emit)
         # dS_1 = aggregation backward of the first layer (no activation between S_1 and Z_1): the existing operator
         g_s1, _ = _layers.aggregate_backward(dzs[0].unsqueeze(0), csr, 64, _layers._ACT_NONE, None, None, False)
-        g_w = torch.bmm(xs[:L - 1].transpose(1, 2), dss)      # dW_i = X_i^T . dS_i, i = 2..L: one strided-batched product
-        g_bias = torch.empty(L, c, **f32)
-        jobs = [(colsum[i], c, g_bias[i]) for i in range(L)]
-        g_head = None
-        if dw_head is not None:
-            g_head = torch.empty(c * 3, **f32)
-            jobs.append((dw_head, c * 3, g_head))
-        n = len(jobs)
-        _lib.call("geom_colsum_batch_f32", n, [j[0] for j in jobs], (ctypes.c_int * n)(*([nrb] * n)),
-                  (ctypes.c_int * n)(*[j[1] for j in jobs]), [j[2] for j in jobs])
+        g_bias, g_w, g_head = _reduce_gradients(xs, dss, colsum, dw_head)
         grads = [g_bias[i] for i in range(L)] + [g_w[i] for i in range(L - 1)]
         g_wh = None if g_head is None else g_head.view(ctx.head_shape)
         return (g_s1.view(nv, c), g_lead, None, g_wh, *grads)

@@ -15,7 +15,9 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))      # (the plain block's cases)
 from geometrics_amd import _lib, aggregation, deform, dense, encoder, fused, layers, meshgen, models, utils  # noqa: E402
+import deform_plain_helpers as dph  # noqa: E402
 
 OUT = None
 CALLS = []
@@ -138,6 +140,67 @@ def deform_cases():
         f, c = block(feats, pooled, adj)
     save("deform_eval_00", f)
     save("deform_eval_01", c)
+    for b in (18, 40):                 # 543 and 1205 row-blocks on 512 workgroups: later row-blocks behind the slice a workgroup holds
+        gen = torch.Generator(device="cpu").manual_seed(b)
+        feats, pooled = rand(gen, b, nv, 3), rand(gen, b, nv, 197)
+        case("deform block eval b=%d" % b)
+        with torch.no_grad():
+            f, c = block(feats, pooled, adj)
+        save("deform_eval_b%d_00" % b, f)
+        save("deform_eval_b%d_01" % b, c)
+    plain_block_cases()
+    plain_launch_cases()
+
+
+def plain_block_cases():
+    """models.MeshDeformationBlock forward + backward on the 482-vertex sphere and the 519-vertex split mesh with its 65-entry
+    row: every output, input gradient and parameter gradient."""
+    for which in ("b", "d"):
+        adj = torch.from_numpy(dph.launch_adjacency(which)).cuda()
+        nv = adj.shape[0]
+        block = dph.fill_plain_parameters(models.MeshDeformationBlock(195), 50 + ord(which)).cuda()
+        gen = torch.Generator(device="cpu").manual_seed(ord(which))
+        feats, pooled = rand(gen, nv, 3).requires_grad_(True), rand(gen, nv, 192).requires_grad_(True)
+        case("plain block %s nv=%d" % (which, nv))
+        f, c = block(feats, pooled, adj)
+        (f * torch.linspace(-1, 1, f.shape[-1], device=f.device)).sum().add((c * c).sum()).backward()
+        outs = [f, c, feats.grad, pooled.grad] + [p.grad for _, p in sorted(block.named_parameters()) if p.grad is not None]
+        for i, t in enumerate(outs):
+            save("plain_block_%s_%02d" % (which, i), t)
+
+
+def plain_launch_cases():
+    """Single plain launches at 18 x 482 rows (543 row-blocks on 512 workgroups: some workgroups take a second row-block), a
+    residual at a pitch wider than 192, with a product and with the head, forward and backward."""
+    adj = torch.from_numpy(dph.launch_adjacency("b")).cuda()
+    csr = layers.adjacency_csr(adj)
+    b, nv = 18, csr.nv
+    gen = torch.Generator(device="cpu").manual_seed(1800)
+    s, bias, w, w_head = rand(gen, b, nv, 192), 0.1 * rand(gen, 192), 0.1 * rand(gen, 192, 192), 0.1 * rand(gen, 192, 3)
+    res = rand(gen, b, nv, 259)[:, :, :192]
+    w2, wts = deform.pack_weights([w])
+    z, x, s_out = (torch.zeros(b, nv, 192, device="cuda") for _ in range(3))
+    case("plain fwd b=18 product")
+    deform.plain_layer_forward(s, bias, csr, True, res, 0.5, z_out=z, x_out=x, w_next=w2[0], s_out=s_out)
+    x_last, s_head = torch.zeros(b, nv, 192, device="cuda"), torch.zeros(b, nv, 3, device="cuda")
+    case("plain fwd b=18 head")
+    deform.plain_layer_forward(s, bias, csr, True, res, 0.5, x_out=x_last, w_head=w_head, s_head=s_head)
+    for name, t in (("z", z), ("x", x), ("s", s_out), ("x_last", x_last), ("s_head", s_head)):
+        save("plain_fwd_%s" % name, t)
+    nrb = (b * nv + 15) // 16
+    dz_up, g2, g, ds_head = rand(gen, b, nv, 192), rand(gen, b, nv, 259)[:, :, 67:], rand(gen, b, nv, 259)[:, :, :192], rand(gen, b, nv, 3)
+    dz, ds_up, grad_res, colsum = (torch.zeros(*shape, device="cuda") for shape in [(b, nv, 192)] * 3 + [(nrb, 192)])
+    case("plain bwd b=18 product")
+    deform.plain_layer_backward((b, nv, 192), csr, z, True, True, 0.5, dz, dz_up=dz_up, ds_up=ds_up, wt_up=wts[0], g2=g2,
+                                grad_res=grad_res, colsum=colsum)
+    for name, t in (("dz", dz), ("ds_up", ds_up), ("grad_res", grad_res), ("colsum", colsum)):
+        save("plain_bwd_%s" % name, t)
+    dw_head = torch.zeros(nrb, 576, device="cuda")
+    case("plain bwd b=18 head")
+    deform.plain_layer_backward((b, nv, 192), csr, z, True, True, 0.5, dz, g=g, g2=g2, grad_res=grad_res, colsum=colsum,
+                                ds_head=ds_head, w_head=w_head, x_top=x, dw_head=dw_head)
+    for name, t in (("dz", dz), ("grad_res", grad_res), ("colsum", colsum), ("dw_head", dw_head)):
+        save("plain_bwd_top_%s" % name, t)
 
 
 def main():
