@@ -24,6 +24,7 @@ FLAG_FIX_REGION6 = _C["FLAG_FIX_REGION6"]
 FLAG_TRI_BRUTE_FORCE = _C["FLAG_TRI_BRUTE_FORCE"]
 FLAG_NN_FMA = _C["FLAG_NN_FMA"]
 FLAG_TRI_WS_READY = _C["FLAG_TRI_WS_READY"]
+FLAG_NN_SAMPLES_ONLY = _C["FLAG_NN_SAMPLES_ONLY"]
 ADAM_MAX_TENSORS = _C["ADAM_MAX_TENSORS"]
 ADAM_STATE_WORDS = _C["ADAM_STATE_WORDS"]
 COLSUM_MAX_JOBS = _C["COLSUM_MAX_JOBS"]

@@ -53,15 +53,14 @@ __global__ __launch_bounds__(NN_THREADS) void chamfer_nn_kernel(NNJob job)
     __shared__ int part_i[NN_WAVES][NN_QUERIES];
 
     // (direction, mesh) jobs are pinned to XCDs so a job's target set is fetched into one L2 only
-    const int longer = job.n > job.m ? job.n : job.m;
     int jobid, qtile;
-    if (!geom::xcd_assign(blockIdx.x, 2 * job.b, (longer + NN_QUERIES - 1) / NN_QUERIES, jobid, qtile)) return;
+    if (!geom::xcd_assign(blockIdx.x, nn_jobs(job), nn_job_tiles(job), jobid, qtile)) return;
     const int dir = geom::nn_job_dir(jobid, job.b);
     const int mesh = jobid % job.b;
     const int nq = dir ? job.m : job.n;
     const int nt = dir ? job.n : job.m;
     const int q0 = qtile * NN_QUERIES;
-    if (q0 >= nq) return; // tiles are sized for the longer direction
+    if (q0 >= nq) return; // tiles are sized for the longer direction (nn_job_tiles)
 
     const float *Q = (dir ? job.xyz2 : job.xyz1) + (size_t)mesh * nq * 3;
     const float *T = (dir ? job.xyz1 : job.xyz2) + (size_t)mesh * nt * 3;
@@ -196,14 +195,16 @@ extern "C" int geom_chamfer_nn_f32(int b, int n, const float *xyz, int m, const 
     if (b < 0 || n < 0 || m < 0) return GEOM_EINVAL;
     if (b == 0 || (n == 0 && m == 0)) return 0;
     if (n == 0 || m == 0) return GEOM_EINVAL; // a direction with no targets has no arg-min
-    if (!xyz || !xyz2 || !result || !result_i || !result2 || !result2_i) return GEOM_EINVAL;
-    NNJob job{xyz, xyz2, result, result2, result_i, result2_i, b, n, m};
-    const int longer = n > m ? n : m;
-    const int64_t blocks = (int64_t)geom::NUM_XCD * ((longer + NN_QUERIES - 1) / NN_QUERIES) * ((2 * (int64_t)b + 7) / 8);
-    if (blocks > 0x7fffffffLL) return GEOM_ETOOBIG;
-    dim3 grid(geom::xcd_grid(2 * b, (longer + NN_QUERIES - 1) / NN_QUERIES), 1, 1);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    // GEOM_FLAG_NN_SAMPLES_ONLY: only the direction whose queries are xyz2 -- half the grid, result / result_i not looked at
+    const bool one_dir = flags & GEOM_FLAG_NN_SAMPLES_ONLY;
+    if (!xyz || !xyz2 || !result2 || !result2_i || (!one_dir && (!result || !result_i))) return GEOM_EINVAL;
     if ((flags & GEOM_FLAG_REF_TAIL_TRUNC) && (flags & GEOM_FLAG_NN_FMA)) return GEOM_EINVAL; // one arithmetic per quirk mode
+    if (one_dir && (flags & GEOM_FLAG_REF_TAIL_TRUNC)) return GEOM_EINVAL; // the truncation mode keeps its own two-direction kernel
+    NNJob job{xyz, xyz2, result, result2, result_i, result2_i, b, n, m, one_dir ? 1 : 2};
+    const int64_t blocks = (int64_t)geom::NUM_XCD * nn_job_tiles(job) * (((int64_t)nn_jobs(job) + 7) / 8);
+    if (blocks > 0x7fffffffLL) return GEOM_ETOOBIG;
+    dim3 grid(geom::xcd_grid(nn_jobs(job), nn_job_tiles(job)), 1, 1);
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (flags & GEOM_FLAG_REF_TAIL_TRUNC)
         hipLaunchKernelGGL(chamfer_nn_kernel<true>, grid, dim3(NN_THREADS), 0, s, job);
     else if (flags & GEOM_FLAG_NN_FMA)
@@ -251,7 +252,7 @@ extern "C" int geom_chamfer_nn_culled_f32(int b, int n, const float *xyz, int m,
     if (flags & ~GEOM_FLAG_NN_FMA) return GEOM_EUNSUPPORTED;
 #endif
     if (b > 65535) return GEOM_ETOOBIG;
-    NNJob job{xyz, xyz2, result, result2, result_i, result2_i, b, n, m};
+    NNJob job{xyz, xyz2, result, result2, result_i, result2_i, b, n, m, 2};
     float *index1 = workspace, *index2 = workspace + geom_nn_cull_index_floats(b, n);
     int rc = geom_nn_cull_index_f32(b, n, xyz, order1, index1, stream);
     if (rc == 0) rc = geom_nn_cull_index_f32(b, m, xyz2, order2, index2, stream);
@@ -260,16 +261,15 @@ extern "C" int geom_chamfer_nn_culled_f32(int b, int n, const float *xyz, int m,
     const float *xs1 = reinterpret_cast<const float *>(sph1 + (size_t)b * (n / NNS_GROUP));
     const float *xs2 = reinterpret_cast<const float *>(sph2 + (size_t)b * (m / NNS_GROUP));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int longer = n > m ? n : m;
 #ifdef NN_CULL_STATS
     NNCull cu{xs1, xs2, order1, order2, sph1, sph2, flags >> 16};
     flags &= 0xffff;
 #else
     NNCull cu{xs1, xs2, order1, order2, sph1, sph2};
 #endif
-    const int64_t blocks = (int64_t)geom::NUM_XCD * ((longer + NN_QUERIES - 1) / NN_QUERIES) * ((2 * (int64_t)b + 7) / 8);
+    const int64_t blocks = (int64_t)geom::NUM_XCD * nn_job_tiles(job) * (((int64_t)nn_jobs(job) + 7) / 8);
     if (blocks > 0x7fffffffLL) return GEOM_ETOOBIG;
-    dim3 grid(geom::xcd_grid(2 * b, (longer + NN_QUERIES - 1) / NN_QUERIES), 1, 1);
+    dim3 grid(geom::xcd_grid(nn_jobs(job), nn_job_tiles(job)), 1, 1);
     if (flags & GEOM_FLAG_NN_FMA) hipLaunchKernelGGL(chamfer_nn_culled_kernel<true>, grid, dim3(NNS_THREADS), 0, s, job, cu);
     else hipLaunchKernelGGL(chamfer_nn_culled_kernel<false>, grid, dim3(NNS_THREADS), 0, s, job, cu);
     return geom::launch_status();

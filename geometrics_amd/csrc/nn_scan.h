@@ -12,7 +12,18 @@ struct NNJob {
     float *dist1, *dist2;
     int *idx1, *idx2;
     int b, n, m;
+    int dirs; // 2: both directions; 1: only the one whose queries are xyz2 (GEOM_FLAG_NN_SAMPLES_ONLY: dist1 / idx1 untouched)
 };
+
+// THE job geometry of a Chamfer launch, host and device: nn_jobs (direction, mesh) jobs -- direction 1 (queries = xyz2) owns the
+// first b (geom::nn_job_dir), so one direction is simply the first half -- of nn_job_tiles query tiles each, sized for the
+// longest query cloud that is scanned
+__host__ __device__ __forceinline__ int nn_jobs(const NNJob &job) { return job.dirs * job.b; }
+__host__ __device__ __forceinline__ int nn_job_tiles(const NNJob &job)
+{
+    const int longest = job.dirs == 2 && job.n > job.m ? job.n : job.m;
+    return (longest + NN_QUERIES - 1) / NN_QUERIES;
+}
 
 // optional epilogue of the fused surface scan: the gradient record of every point the finalize / gather passes of the
 // surface loss need (csrc/surface_gather.hip): {(point - partner) * coef, flag}, {corner weights}
@@ -56,9 +67,8 @@ __device__ __forceinline__ void nn_scalar_body(const NNJob &job, int bid, const 
     __shared__ float part_d[NNS_WAVES][NN_QUERIES];
     __shared__ int part_i[NNS_WAVES][NN_QUERIES];
 
-    const int longer = job.n > job.m ? job.n : job.m;
     int jobid, qtile;
-    if (!geom::xcd_assign(bid, 2 * job.b, (longer + NN_QUERIES - 1) / NN_QUERIES, jobid, qtile)) return;
+    if (!geom::xcd_assign(bid, nn_jobs(job), nn_job_tiles(job), jobid, qtile)) return;
     const int dir = geom::nn_job_dir(jobid, job.b);
     const int mesh = jobid % job.b;
     const int nq = dir ? job.m : job.n;
@@ -66,7 +76,7 @@ __device__ __forceinline__ void nn_scalar_body(const NNJob &job, int bid, const 
     const int q0 = qtile * NN_QUERIES;
     if (q0 >= nq) return;
 
-    const float *Q = (dir ? job.xyz2 : job.xyz1) + (size_t)mesh * nq * 3;
+    const float *Q =(dir ? job.xyz2 : job.xyz1) + (size_t)mesh * nq * 3;
     const float *__restrict__ T = (dir ? job.xyz1 : job.xyz2) + (size_t)mesh * nt * 3;
     float *out_d = (dir ? job.dist2 : job.dist1) + (size_t)mesh * nq;
     int *out_i = (dir ? job.idx2 : job.idx1) + (size_t)mesh * nq;
@@ -322,9 +332,8 @@ __device__ __forceinline__ void nn_culled_body(const NNJob &job, const NNCull &c
     auto &part_i = L.part_i;
     auto &part_g = L.part_g;
 
-    const int longer = job.n > job.m ? job.n : job.m;
     int jobid, qtile;
-    if (!geom::xcd_assign(bid, 2 * job.b, (longer + NN_QUERIES - 1) / NN_QUERIES, jobid, qtile)) return;
+    if (!geom::xcd_assign(bid, nn_jobs(job), nn_job_tiles(job), jobid, qtile)) return;
     const int dir = geom::nn_job_dir(jobid, job.b);
     const int mesh = jobid % job.b;
     const int nq = dir ? job.m : job.n;

@@ -1156,12 +1156,14 @@ constexpr int SCAN_TAIL_LDS_INTS = 11776; // 46 KB: three workgroups per CU stil
 // which counter a tile signs (-1: a padding workgroup) -- computed in front of the tile's body so that ONE register lives
 // across it (the geometry this takes -- b, n, the tile counts -- pushed scalar registers of the brute-force Chamfer loop
 // into spills when it was evaluated behind the body: 49 -> 59 us)
-__device__ __forceinline__ int scan_tile_counter(int bid, int tri_blocks, int b, int n, int nn_tiles)
+__device__ __forceinline__ int scan_tile_counter(int bid, int tri_blocks, int b, int n, int nn_job_count, int nn_tiles)
 {
     int job, tile;
     if (bid < tri_blocks) return geom::xcd_assign(bid, b, (n + TRI_QUERIES - 1) / TRI_QUERIES, job, tile) ? job : -1;
-    // Chamfer tiles: only the direction the loss needs (the sampled points' squared distances) is counted
-    return geom::xcd_assign(bid - tri_blocks, 2 * b, nn_tiles, job, tile) && geom::nn_job_dir(job, b) == 1 ? b + job % b : -1;
+    // Chamfer tiles: only the direction the loss needs (the sampled points' squared distances) is counted.  nn_job_count /
+    // nn_tiles are the bodies' own nn_jobs / nn_job_tiles: a tile that signs another counter than its body's job leaves the
+    // roles waiting in vain
+    return geom::xcd_assign(bid - tri_blocks, nn_job_count, nn_tiles, job, tile) && geom::nn_job_dir(job, b) == 1 ? b + job % b : -1;
 }
 
 __device__ __forceinline__ void scan_tile_done(int *done, int counter)
@@ -1299,7 +1301,7 @@ __global__ __launch_bounds__(8 * GEOM_WAVE, CULL ? 5 : 1) void surface_scan_kern
             return;
         }
         const int bid = (int)blockIdx.x - tail.lead; // tile index (tail.lead = 0 without a finalize tail)
-        const int sign = tail.done ? scan_tile_counter(bid, tri_blocks, b, n, tail.expect_job) : -1;
+        const int sign = tail.done ? scan_tile_counter(bid, tri_blocks, b, n, nn_jobs(job), nn_job_tiles(job)) : -1;
         // (s_setprio(3) on either kind of tile: 41.6 / 43.3 against 42.4 us -- within the noise, not kept)
         if (bid < tri_blocks) tri_scan_grouped_body<false, FIX6, 8>(bid, xyz, b, n, m, ws, dist, point, index, surf, lds.tri);
         else nn_culled_body<FMA>(job, cull, bid - tri_blocks, rr, lds.nn);
@@ -1542,7 +1544,8 @@ __global__ __launch_bounds__(NNS_THREADS) void nn_records_kernel(NNJob job, NNRe
 
 // The two arg-min scans of the surface loss in one call (utils.py:451 + 470: chamfer_dist, then tri_dist on the gathered
 // corners).  gt [b,n_gt,3] against the sampled points [b,num,3]: NN both ways (sq_gt / idx_p for the gt points, sq_pred /
-// idx_g for the sampled points, as geom_chamfer_nn_f32(gt, points)); and, when verts != NULL, gt against the mesh
+// idx_g for the sampled points, as geom_chamfer_nn_f32(gt, points); GEOM_FLAG_NN_SAMPLES_ONLY: the sampled points' direction
+// alone -- the only one the one-sided loss reads); and, when verts != NULL, gt against the mesh
 // (tri_dist / option / index + the point-to-surface quantities sq / closest / weights, as geom_tri_surface_fwd_f32).
 // Where the step fuses (surface_step_fuses) both scans run as ONE heterogeneous launch after the triangle-record prep;
 // otherwise as the separate launches.  order_scratch (may be NULL): the finalize scratch of geom_surface_finalize_f32 --
@@ -1562,23 +1565,26 @@ extern "C" int geom_surface_scan_f32(int b, int n_gt, const float *gt, int num, 
     if (b < 0 || n_gt < 0 || num < 0 || nf < 0 || nv < 0) return GEOM_EINVAL;
     if (b == 0) return 0;
     if (n_gt == 0 || num == 0) return GEOM_EINVAL;
-    if (!gt || !points || !sq_gt || !idx_p || !sq_pred || !idx_g) return GEOM_EINVAL;
+    // GEOM_FLAG_NN_SAMPLES_ONLY: the Chamfer jobs of the gt points (sq_gt / idx_p) are not run -- the one-sided loss reads
+    // neither; the two-sided records (no tri scan) need both directions, the truncation mode keeps its own kernels
+    const bool one_dir = flags & GEOM_FLAG_NN_SAMPLES_ONLY;
+    if (!gt || !points || !sq_pred || !idx_g || (!one_dir && (!sq_gt || !idx_p))) return GEOM_EINVAL;
     const bool tri = verts != nullptr;
+    if (one_dir && (!tri || (flags & GEOM_FLAG_REF_TAIL_TRUNC))) return GEOM_EINVAL;
     if (tri && (!faces || !tri_dist || !option || !index || !sq || !closest || !weights || nf == 0 || nv == 0)) return GEOM_EINVAL;
     if (order_scratch && (!u || !v || ((uintptr_t)order_scratch & 15))) return GEOM_EINVAL;
     if (b > 65535 || nf >= (1 << 26)) return GEOM_ETOOBIG;
-    const unsigned nn_flags = flags & (GEOM_FLAG_REF_TAIL_TRUNC | GEOM_FLAG_NN_FMA);
+    const unsigned nn_flags = flags & (GEOM_FLAG_REF_TAIL_TRUNC | GEOM_FLAG_NN_FMA | GEOM_FLAG_NN_SAMPLES_ONLY);
     const unsigned tri_flags = flags & (GEOM_FLAG_REF_TAIL_TRUNC | GEOM_FLAG_FIX_REGION6 | GEOM_FLAG_TRI_BRUTE_FORCE);
     if ((nn_flags & GEOM_FLAG_REF_TAIL_TRUNC) && (nn_flags & GEOM_FLAG_NN_FMA)) return GEOM_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t cap = (int64_t)num + n_gt;
     const SurfaceScratch scr = geom_surface_scratch(order_scratch, b, nf, cap);
     float4 *rec = scr.rec;
-    NNJob job{gt, points, sq_gt, sq_pred, idx_p, idx_g, b, n_gt, num};
-    const int longer = n_gt > num ? n_gt : num;
-    const int nn_tiles = (longer + NN_QUERIES - 1) / NN_QUERIES;
-    if ((int64_t)geom::NUM_XCD * nn_tiles * ((2 * (int64_t)b + 7) / 8) > 0x3fffffffLL) return GEOM_ETOOBIG;
-    const unsigned nn_blocks = geom::xcd_grid(2 * b, nn_tiles);
+    NNJob job{gt, points, sq_gt, sq_pred, idx_p, idx_g, b, n_gt, num, one_dir ? 1 : 2};
+    const int nn_tiles = nn_job_tiles(job); // grid, tile bodies, completion counters and the roles' expectations: one count
+    if ((int64_t)geom::NUM_XCD * nn_tiles * (((int64_t)nn_jobs(job) + 7) / 8) > 0x3fffffffLL) return GEOM_ETOOBIG;
+    const unsigned nn_blocks = geom::xcd_grid(nn_jobs(job), nn_tiles);
     const bool fma = nn_flags & GEOM_FLAG_NN_FMA;
     // records of the NN side: the sampled points always; the gt points through their nearest sample only without a tri scan
     NNRecords rr{rec, u, v, coef_sample, coef_other, (int)cap, tri ? 0 : 1};

@@ -4,6 +4,7 @@ Every function launches on torch's current stream, allocates its outputs with to
 never synchronises with the host, so a whole training step can be captured in a HIP graph.
 """
 import ctypes
+import os
 import weakref
 
 import torch
@@ -233,6 +234,11 @@ def finalize_roles_gave_up():
 # tri_dist of the point-to-triangle scan.  None: off.
 scan_capture = None
 
+# The one-sided loss with f1=False reads only the sampled points' nearest gt points: utils.batch_point_to_surface then leaves
+# the other direction of the Chamfer scan out (GEOM_FLAG_NN_SAMPLES_ONLY: half the Chamfer tiles of the scan launch).  True
+# (tools, A/B timing: GEOM_NN_DIRECTIONS=both): always scan both directions, as before the flag existed -- same loss and gradient.
+nn_both_directions = os.environ.get("GEOM_NN_DIRECTIONS", "") == "both"
+
 
 class SurfaceLoss(torch.autograd.Function):
     """The whole sampled-surface loss of the reference in one autograd node.
@@ -246,11 +252,13 @@ class SurfaceLoss(torch.autograd.Function):
     Backward: a gather -- the points are binned by face (integer atomics) and every vertex sums the points on its
     incident faces in a fixed order: no float atomics, no zero-fill, bit-reproducible (csrc/surface_gather.hip); the
     gradient of the sampled points is never materialised.  Returns (loss, sq_gt, sq_pred); the squared NN
-    distances feed the F1 score and are not differentiable."""
+    distances feed the F1 score and are not differentiable.  need_gt_nn=False (one-sided loss only): the nearest sampled
+    point of every gt point, which only the F1 score and the inspection hook read, is not searched; None stands in sq_gt's
+    place."""
 
     @staticmethod
     def forward(ctx, verts, faces, gt, choices, u, v, two_sided, scale, points=None, tri_ws=None, loss_out=None, gt_index=None,
-                mesh_weight=None):
+                mesh_weight=None, need_gt_nn=True):
         """mesh_weight (optional, [B] fp32 on the meshes' device): per-mesh factors -- loss = sum_m w[m] * (mesh m's share of the
         loss above), mesh m's gradient times w[m] (geom_surface_finalize_w_f32 / geom_surface_gather_w_f32)."""
         verts_c = _f32(verts.detach(), "verts", 3, 3)
@@ -280,8 +288,11 @@ class SurfaceLoss(torch.autograd.Function):
             if not (loss_out.is_cuda and loss_out.device == dev and loss_out.dtype == torch.float32 and loss_out.numel() == 1):
                 raise RuntimeError("loss_out must be ONE fp32 element on the mesh batch's device")
             out = loss_out.detach().view(())
-        sq_gt, sq_pred = torch.empty(b, n_gt, **f32), torch.empty(b, num, **f32)
-        idx_p, idx_g = torch.empty(b, n_gt, **i32), torch.empty(b, num, **i32)
+        flags = _chamfer.default_flags()
+        # the gt points' direction of the Chamfer scan is left out where nothing reads it (the truncation mode keeps both)
+        one_dir = not need_gt_nn and not two_sided and not (flags & _lib.FLAG_REF_TAIL_TRUNC)
+        sq_pred, idx_g = torch.empty(b, num, **f32), torch.empty(b, num, **i32)
+        sq_gt, idx_p = (None, None) if one_dir else (torch.empty(b, n_gt, **f32), torch.empty(b, n_gt, **i32))
         prep = tri_ws if isinstance(tri_ws, ScanPrep) else None
         if prep is not None:
             tri_ws = prep.tri_ws
@@ -309,9 +320,10 @@ class SurfaceLoss(torch.autograd.Function):
         order = torch.empty(L.geom_surface_order_words(b, nf, num, n_gt), dtype=torch.int32, device=dev)
         coef_s, coef_o = scale / (b * num), scale / (b * n_gt)
         wrote = ctypes.c_int(0)
-        flags = _chamfer.default_flags()
         if not two_sided and ws_ready:
             flags |= _lib.FLAG_TRI_WS_READY
+        if one_dir:
+            flags |= _lib.FLAG_NN_SAMPLES_ONLY
         if two_sided:
             tri_args = (nv, None, nf, None, None, None, None, None, None, None, None)    # nf still sizes the scratch layout
             ws, ws_bytes = None, 0
@@ -354,7 +366,7 @@ class SurfaceLoss(torch.autograd.Function):
             ctx.save_for_backward(faces, choices, u, v, points, gt_c, idx_g, index, closest, weights)
         ctx.two_sided, ctx.scale, ctx.nv = two_sided, scale, nv
         ctx.mesh_weight = mesh_weight
-        ctx.mark_non_differentiable(sq_gt, sq_pred)
+        ctx.mark_non_differentiable(*(t for t in (sq_gt, sq_pred) if t is not None))
         ctx.set_materialize_grads(False)    # no zero tensors (two fill launches) for the two distance outputs
         return out, sq_gt, sq_pred
 
@@ -385,7 +397,7 @@ class SurfaceLoss(torch.autograd.Function):
                 index, closest, weights = saved[7:10]
                 _lib.call("geom_surface_loss_bwd_f32", b, nv, nf, faces, num, choices, u, v, points, n_gt, gt, saved[6],
                           index, closest, weights, grad, ctx.scale / (b * num), ctx.scale / (b * n_gt), grad_verts)
-        return grad_verts, None, None, None, None, None, None, None, None, None, None, None, None
+        return grad_verts, None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 class Laplacian(torch.autograd.Function):

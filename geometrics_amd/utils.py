@@ -193,8 +193,10 @@ def _surface_loss(pred_vert, adj_info, gt_points, num, f1, draws, two_sided, los
     mesh_weight = None
     if isinstance(weight, torch.Tensor):      # per-mesh factors: the loss's own scale stays, the kernels apply the factors
         mesh_weight, weight = weight, 1.0
+    # the nearest sampled point of every gt point: read by the F1 score, the two-sided loss and the inspection hook only
+    need_gt_nn = bool(f1) or two_sided or ops.scan_capture is not None or ops.nn_both_directions
     loss, sq_gt, sq_pred = ops.SurfaceLoss.apply(pred_vert, faces, gt_points, choices, u, v, two_sided, LOSS_SCALE * weight,
-                                                 points, tri_ws, loss_out, gt_index, mesh_weight)
+                                                 points, tri_ws, loss_out, gt_index, mesh_weight, need_gt_nn)
     if f1:
         return loss, _f_score(sq_gt, sq_pred, num)
     return loss

@@ -55,6 +55,9 @@ extern "C" {
 
 #define GEOM_FLAG_TRI_WS_READY 16u    /* geom_surface_scan_f32: `workspace` still holds the triangle records a previous call
                                       * wrote for the SAME verts / faces / order / flags: the prep launch is skipped */
+#define GEOM_FLAG_NN_SAMPLES_ONLY 32u /* geom_chamfer_nn_f32 / geom_surface_scan_f32: scan only the direction whose queries are
+                                      * the SECOND cloud (the sampled points of the surface loss); the first cloud's outputs are
+                                      * neither read nor written and may be NULL.  See the two entry points */
 
 int geom_abi_version(void);
 /* static string for a code returned by any entry point */
@@ -67,7 +70,10 @@ const char *geom_strerror(int code);
  *   xyz  [b,n,3], xyz2 [b,m,3]
  *   result  [b,n] / result_i  [b,n]: squared distance / index of the nearest xyz2 point of each xyz point
  *   result2 [b,m] / result2_i [b,m]: the other direction
- * Arg-min is the sequential-scan one: first target seeds, strict '<', lowest index wins ties. */
+ * Arg-min is the sequential-scan one: first target seeds, strict '<', lowest index wins ties.
+ * GEOM_FLAG_NN_SAMPLES_ONLY: half the launch -- only result2 / result2_i (queries xyz2, targets xyz) are computed, the same
+ * bits as without the flag; result / result_i are neither read nor written and may be NULL (without the flag a NULL output
+ * stays GEOM_EINVAL).  GEOM_EINVAL together with GEOM_FLAG_REF_TAIL_TRUNC (that mode keeps its own two-direction kernel). */
 int geom_chamfer_nn_f32(int b, int n, const float *xyz, int m, const float *xyz2,
                         float *result, int *result_i, float *result2, int *result2_i,
                         unsigned flags, void *stream);
@@ -802,6 +808,12 @@ int geom_surface_prepare_f32(int b, int nv, const float *verts, int nf, const in
  * either way.  (One rule in the library decides this for geom_surface_prepare_f32 and for this call.)
  * flags: GEOM_FLAG_FIX_REGION6 / _TRI_BRUTE_FORCE / _REF_TAIL_TRUNC /
  * _NN_FMA as for the separate entry points.  workspace: as geom_tri_distance_workspace_bytes(b, n_gt, nf).
+ * GEOM_FLAG_NN_SAMPLES_ONLY: the nearest sampled point of every gt point is not searched -- the one-sided loss
+ * (batch_point_to_surface with f1=False: utils.py:441-488) reads only sq_pred / idx_g, and that direction is half of the
+ * Chamfer tiles of every route (fused brute-force, fused culled with or without the tail, separate launches).  sq_gt /
+ * idx_p are then neither read nor written and may be NULL; every other output is what it is without the flag, bit for bit.
+ * Without the flag NULL sq_gt / idx_p stay GEOM_EINVAL.  GEOM_EINVAL with the flag when verts == NULL (the two-sided
+ * records go through idx_p) or together with GEOM_FLAG_REF_TAIL_TRUNC (its legacy kernels scan both directions).
  * order_scratch (may be NULL): the `order` buffer of geom_surface_finalize_f32; the scans then also write every
  * point's gradient record into it (u, v [b,num]: the draws of the sampled points; coef_sample / coef_other as for the
  * finalize) and *records_written = 1; the variants that cannot (split query tiles, brute force, tail truncation)

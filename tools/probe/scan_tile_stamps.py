@@ -2,7 +2,8 @@
 tiles + Chamfer tiles, 8-mesh BASELINE shard) on the instrumented build (-DSCAN_TILE_STAMPS: every workgroup stamps the
 100 MHz wall clock at entry and exit) and prints: tile durations per kind, how many tiles run at once, how long the launch's
 slots sit idle at its end.      bash tools/probe/run_probes.sh   (build container)
-    GEOM_LIB_OVERRIDE=tools/probe/bin/libgeom_scan_stamps.so GEOM_ALLOW_STALE_LIB=1 python tools/probe/scan_tile_stamps.py [--plain]"""
+    GEOM_LIB_OVERRIDE=tools/probe/bin/libgeom_scan_stamps.so GEOM_ALLOW_STALE_LIB=1 python tools/probe/scan_tile_stamps.py [--plain] [--samples-only]
+--samples-only: the launch of the one-sided loss, GEOM_FLAG_NN_SAMPLES_ONLY (half the Chamfer jobs)."""
 import ctypes
 import os
 import sys
@@ -14,6 +15,7 @@ import bench                                   # noqa: E402
 from geometrics_amd import _lib, ops           # noqa: E402
 
 plain = "--plain" in sys.argv
+one_dir = _lib.FLAG_NN_SAMPLES_ONLY if "--samples-only" in sys.argv else 0
 tail = "--tail" in sys.argv          # the finalize pass inside the launch (its role workgroups lead the grid)
 bench.CULLED_CHAMFER = not plain
 dev = torch.device("cuda:0")
@@ -25,16 +27,16 @@ with torch.no_grad():
     for rep in range(4):                       # the last repetition is read: warm caches and clocks
         prep = ops.draw_samples(pos, w.faces, bench.S_PTS, with_points=True, prepare_scan_for=bench.G_PTS, gt_index=w.gt_index)
         if plain:
-            call = bench.fused_scan_call(w, pos, prep[3])
+            call = bench.fused_scan_call(w, pos, prep[3], one_dir)
             call()
-            call = bench.fused_scan_call(w, pos, prep[3], _lib.FLAG_TRI_WS_READY, share=call)
+            call = bench.fused_scan_call(w, pos, prep[3], _lib.FLAG_TRI_WS_READY | one_dir, share=call)
         else:
-            call = bench.fused_scan_call(w, pos, prep[3], prep=prep, tail=tail)
+            call = bench.fused_scan_call(w, pos, prep[3], one_dir, prep=prep, tail=tail)
         torch.cuda.synchronize()
         call()
         torch.cuda.synchronize()
 tri_tiles = 8 * ((bench.G_PTS + 63) // 64)
-nn_tiles = 2 * 8 * ((max(bench.G_PTS, bench.S_PTS) + 63) // 64)
+nn_tiles = 8 * ((bench.S_PTS + 63) // 64) if one_dir else 2 * 8 * ((max(bench.G_PTS, bench.S_PTS) + 63) // 64)
 rows = tri_tiles + nn_tiles + (16 if tail else 0)
 buf = np.zeros((rows, 4), dtype=np.int64)
 _lib.check(L.geom_probe_read_scan_stamps(buf.ctypes.data, rows), "geom_probe_read_scan_stamps")
