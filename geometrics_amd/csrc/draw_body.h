@@ -57,16 +57,37 @@ struct DrawSort {
 };
 constexpr int DRAW_SORT_CHUNKS = 4; // samples per mesh on the sorted route: at most 4096
 
+// RAGGED (geom_draw_samples_ragged_f32): every mesh of the batch owns its faces.  `verts` is then the UNION of the meshes'
+// vertices (no per-mesh stride), `faces` the union face list [nft,3] indexing it, and mesh m's faces are the entries
+// face_list[face_off[m] .. face_off[m + 1]) of it: its face count is known on the device only.  Position f of a mesh is the
+// face face_list[face_off[m] + f]; the table is built over positions with the mesh's OWN count deciding the partition, so it
+// is, bit for bit, the table the shared-faces launch builds for that mesh alone.  The choices written are union face ids.
+struct DrawRagged {
+    const int *face_list; // [nft] faces grouped by mesh, ascending inside a mesh
+    const int *face_off;  // [b + 1]
+    int nft;              // faces of the union: ids and offsets are clamped to it (a bad table cannot index out of range)
+};
+// the faces of `mesh`: false when it has none or more than the table holds (count is then what the tables say)
+__device__ __forceinline__ bool draw_ragged_span(const DrawRagged &rag, int mesh, const int *&list, int &count)
+{
+    const int off = min(max(rag.face_off[mesh], 0), rag.nft);
+    count = min(max(rag.face_off[mesh + 1], off), rag.nft) - off;
+    list = rag.face_list + off;
+    return count > 0 && count <= DRAW_MAX_FACES;
+}
+__device__ __forceinline__ int draw_ragged_face(const DrawRagged &rag, const int *list, int f) { return min(max(list[f], 0), rag.nft - 1); }
+
 // chunk / mesh: which 1024 samples of which mesh; groups: workgroups of this launch that run this body (the arrival count)
-template <bool SORTED>
+template <bool SORTED, bool RAGGED = false>
 __device__ __forceinline__ void draw_samples_body(int chunk, int mesh, unsigned long long groups, int nv, const float *verts,
                                                   int nf, const int64_t *faces, int num, const float *uniforms, int64_t plane,
                                                   unsigned long long *rng_state, int64_t *choices, float *u, float *v,
-                                                  float *points, const DrawSort &srt)
+                                                  float *points, const DrawSort &srt, const DrawRagged &rag = DrawRagged{})
 {
+    static_assert(!(SORTED && RAGGED), "the sorted route draws from one shared face list");
     __shared__ float cdf[DRAW_MAX_FACES];
     __shared__ float wave_total[DRAW_THREADS / GEOM_WAVE], wave_top[DRAW_THREADS / GEOM_WAVE];
-    const float *V = verts + (size_t)mesh * nv * 3;
+    const float *V = RAGGED ? verts : verts + (size_t)mesh * nv * 3;
     // the random stream's state is requested first: read after the CDF it would add a dependent round trip to a launch
     // that is a chain of them (face ids -> corners -> scan -> search -> face ids -> corners -> store)
     unsigned long long seed = 0ull, pos = 0ull, mesh0 = 0ull;
@@ -74,6 +95,37 @@ __device__ __forceinline__ void draw_samples_body(int chunk, int mesh, unsigned 
         seed = rng_state[0];
         pos = rng_state[1];
         mesh0 = rng_state[3];
+    }
+    // last workgroup in: nobody reads the old position any more (called by one thread, behind a barrier: every thread of the
+    // workgroup holds the position before the workgroup reports in)
+    auto report_in = [&] {
+        if (atomicAdd(&rng_state[2], 1ull) == groups - 1ull) {
+            rng_state[2] = 0ull;
+            rng_state[1] = pos + 1ull;
+        }
+    };
+    const int *list = nullptr; // RAGGED: the mesh's faces
+    if constexpr (RAGGED) {
+        // THE FAIL-SAFE: a mesh without faces, or with more than the table holds, draws nothing -- a valid face id (its first
+        // listed face, or 0) and NaN coordinates, so that nothing downstream indexes out of range and the loss comes out NaN.
+        // The workgroup still reports in: the stream position advances once per call whatever the meshes hold.
+        if (!draw_ragged_span(rag, mesh, list, nf)) {
+            const int64_t safe = nf > 0 ? draw_ragged_face(rag, list, 0) : 0;
+            const int i = chunk * DRAW_THREADS + threadIdx.x;
+            if (i < num) {
+                const int64_t o = (int64_t)mesh * num + i;
+                const float nan = __uint_as_float(0x7fc00000u);
+                choices[o] = safe;
+                u[o] = nan;
+                v[o] = nan;
+                if (points) points[3 * o + 0] = points[3 * o + 1] = points[3 * o + 2] = nan;
+            }
+            if (rng_state) {
+                __syncthreads();
+                if (threadIdx.x == 0) report_in();
+            }
+            return;
+        }
     }
     const int lane = threadIdx.x & (GEOM_WAVE - 1), wave = threadIdx.x >> 6;
     __shared__ float chunk_part[SORTED ? DRAW_SORT_CHUNKS : 1][DRAW_THREADS / GEOM_WAVE]; // SORTED: spacing sums per chunk and wave
@@ -114,7 +166,7 @@ __device__ __forceinline__ void draw_samples_body(int chunk, int mesh, unsigned 
     const int f1 = min(f0 + per, nf);
 #pragma unroll 4
     for (int f = f0; f < f1; ++f) { // local inclusive sums
-        int ff = f;
+        int ff = RAGGED ? draw_ragged_face(rag, list, f) : f;
         bool real = true;
         int64_t c0, c1, c2;
         if (SORTED && srt.face_order && srt.pfaces) { // position f of the visiting order, corners listed in that order
@@ -188,12 +240,7 @@ __device__ __forceinline__ void draw_samples_body(int chunk, int mesh, unsigned 
 
     if (rng_state) {
         __syncthreads(); // every thread of this workgroup holds the position before the workgroup reports in
-        if (threadIdx.x == 0) {
-            if (atomicAdd(&rng_state[2], 1ull) == groups - 1ull) { // last one in: nobody reads the old position any more
-                rng_state[2] = 0ull;
-                rng_state[1] = pos + 1ull;
-            }
-        }
+        if (threadIdx.x == 0) report_in();
     }
     // sample i of the mesh: the draw and its outputs
     const int i = chunk * DRAW_THREADS + threadIdx.x;
@@ -221,6 +268,7 @@ __device__ __forceinline__ void draw_samples_body(int chunk, int mesh, unsigned 
             const int ff = srt.face_order[lo];
             lo = ff >= 0 && ff < nf ? ff : 0;
         }
+        if constexpr (RAGGED) lo = draw_ragged_face(rag, list, lo); // position -> union face id
         choices[o] = lo;
         const float su = sqrtf(r1);
         u[o] = su;

@@ -73,6 +73,17 @@ __global__ __launch_bounds__(DRAW_THREADS) void draw_samples_kernel(int nv, cons
                              plane, rng_state, choices, u, v, points, DrawSort{});
 }
 
+// The same draws for a batch whose meshes own their faces (draw_body.h, RAGGED): blockIdx.y's faces are its span of
+// face_list, corners come from the union vertex array, choices are union face ids.
+__global__ __launch_bounds__(DRAW_THREADS) void draw_samples_ragged_kernel(const float *verts, const int64_t *faces, DrawRagged rag,
+                                                                            int num, const float *uniforms, int64_t plane,
+                                                                            unsigned long long *rng_state, int64_t *choices,
+                                                                            float *u, float *v, float *points)
+{
+    draw_samples_body<false, true>(blockIdx.x, blockIdx.y, (unsigned long long)gridDim.x * gridDim.y, 0, verts, 0, faces, num,
+                                   uniforms, plane, rng_state, choices, u, v, points, DrawSort{}, rag);
+}
+
 // -------------------------------------------------------------- face sampling ----
 struct SampleArgs {
     const float *verts;
@@ -450,6 +461,22 @@ extern "C" int geom_draw_samples_rng_f32(int b, int nv, const float *verts, int 
     hipLaunchKernelGGL(draw_samples_kernel, dim3((num + DRAW_THREADS - 1) / DRAW_THREADS, b), dim3(DRAW_THREADS), 0, s,
                        nv, verts, nf, faces, num, static_cast<const float *>(nullptr), (int64_t)b * num,
                        reinterpret_cast<unsigned long long *>(rng_state), choices, u, v, points);
+    return geom::launch_status();
+}
+
+extern "C" int geom_draw_samples_ragged_f32(int b, int nv, const float *verts, int nf, const int64_t *faces,
+                                            const int *face_list, const int *face_off, int num, const float *uniforms,
+                                            uint64_t *rng_state, int64_t *choices, float *u, float *v, float *points,
+                                            void *stream)
+{
+    if (b < 0 || nv < 0 || nf < 0 || num < 0) return GEOM_EINVAL;
+    if (b == 0 || num == 0) return 0;
+    if (nf == 0 || nv == 0 || !verts || !faces || !face_list || !face_off || !choices || !u || !v) return GEOM_EINVAL;
+    if (!uniforms == !rng_state) return GEOM_EINVAL; // exactly one source of uniforms
+    if (b > 65535) return GEOM_ETOOBIG;
+    hipLaunchKernelGGL(draw_samples_ragged_kernel, dim3((num + DRAW_THREADS - 1) / DRAW_THREADS, b), dim3(DRAW_THREADS), 0,
+                       static_cast<hipStream_t>(stream), verts, faces, DrawRagged{face_list, face_off, nf}, num, uniforms,
+                       (int64_t)b * num, reinterpret_cast<unsigned long long *>(rng_state), choices, u, v, points);
     return geom::launch_status();
 }
 

@@ -10,7 +10,9 @@
 //                                     it is the in-library cross-check of the other three.
 //   2. tri_distance_culled_kernel     culled scan with in-kernel staging from (verts, faces) or the three
 //                                     corner arrays -- what the workspace-free entry points (the exact
-//                                     reference prototypes) run.
+//                                     reference prototypes) run.  Scans 1 and 2 also take a RAGGED batch
+//                                     (geom_tri_distance_ragged_f32): every mesh scans its own span of a grouped
+//                                     face list over one union vertex array (FETCH_RAGGED, ragged_enter).
 //   3. tri_prep_kernel + tri_scan_ws_kernel (+ tri_finalize_kernel)
 //                                     culled scan over per-triangle records in a caller-provided workspace
 //                                     (flat: every query tests every triangle sphere).
@@ -59,14 +61,28 @@ struct TriJob {
     float *dist;
     int *point, *index;
     int b, n, m, nv;
+    const int *face_list, *face_off;  // ragged variant: [nft] faces grouped by mesh, [b + 1] where each mesh's group starts
+    int nft;                          // ragged variant: faces of the union (m is a mesh's own count inside the kernel)
 };
+
+// Where a triangle's corners come from.  DIRECT: the three corner arrays.  INDEXED: verts[mesh] through ONE face list shared by
+// the batch.  RAGGED: every mesh owns its faces -- verts is the union of the meshes' vertices (no per-mesh stride), faces the
+// union face list, and the triangles of mesh `mesh` are the POSITIONS k of its span of face_list (ragged_enter).  A bool
+// converts to the first two, so the callers that only know "indexed or not" say <INDEXED> as before.
+constexpr int FETCH_DIRECT = 0, FETCH_INDEXED = 1, FETCH_RAGGED = 2;
 
 __device__ __forceinline__ V3 load3(const float *p) { return geom::mk(p[0], p[1], p[2]); }
 
-template <bool INDEXED>
+template <int FETCH>
 __device__ __forceinline__ void fetch_triangle(const TriJob &job, int mesh, int k, V3 &A, V3 &B, V3 &C)
 {
-    if (INDEXED) {
+    static_assert(FETCH == FETCH_DIRECT || FETCH == FETCH_INDEXED || FETCH == FETCH_RAGGED, "unknown fetch mode");
+    if (FETCH == FETCH_RAGGED) { // job: narrowed to the mesh by ragged_enter; a bad id in the table cannot index out of range
+        const size_t f = (size_t)min(max(job.face_list[k], 0), job.nft - 1);
+        A = load3(job.verts + 3 * job.faces[3 * f + 0]);
+        B = load3(job.verts + 3 * job.faces[3 * f + 1]);
+        C = load3(job.verts + 3 * job.faces[3 * f + 2]);
+    } else if (FETCH == FETCH_INDEXED) {
         const float *V = job.verts + (size_t)mesh * job.nv * 3;
         A = load3(V + 3 * job.faces[3 * (size_t)k + 0]);
         B = load3(V + 3 * job.faces[3 * (size_t)k + 1]);
@@ -77,6 +93,32 @@ __device__ __forceinline__ void fetch_triangle(const TriJob &job, int mesh, int 
         B = load3(job.tri2 + o);
         C = load3(job.tri3 + o);
     }
+}
+
+// RAGGED: narrow the job to the faces of `mesh` -- m becomes its face count F_m, face_list starts at its first face, so
+// that triangle k of the scan is POSITION k of the mesh (positions ascend with the face id: position order is tie order).
+// false: the mesh has no face (nothing may be fetched for it).  Offsets are clamped to the union's face count.
+__device__ __forceinline__ bool ragged_enter(TriJob &job, int mesh)
+{
+    const int off = min(max(job.face_off[mesh], 0), job.nft);
+    job.m = min(max(job.face_off[mesh + 1], off), job.nft) - off;
+    job.face_list += off;
+    return job.m > 0;
+}
+// what a scan writes for query q of a mesh that has no face: (NaN, region 0, face 0)
+__device__ __forceinline__ void ragged_empty(const TriJob &job, int mesh, int q, bool live)
+{
+    if (!live) return;
+    const size_t o = (size_t)mesh * job.n + q;
+    job.dist[o] = __uint_as_float(0x7fc00000u);
+    job.point[o] = 0;
+    job.index[o] = 0;
+}
+// the `index` a scan writes for the winner k: the triangle itself, or (RAGGED) the union face at that position
+template <int FETCH>
+__device__ __forceinline__ int winner_index(const TriJob &job, int k)
+{
+    return FETCH == FETCH_RAGGED ? min(max(job.face_list[k], 0), job.nft - 1) : k;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -205,9 +247,10 @@ __device__ __forceinline__ void tri_finish(V3 p, V3 a0, V3 b0, V3 c0, int m, boo
 }
 
 // ---------------------------------------------------------------------------------------
-template <bool INDEXED, bool TRUNC, bool FIX6>
+template <int FETCH, bool TRUNC, bool FIX6>
 __global__ __launch_bounds__(TRI_THREADS) void tri_distance_kernel(TriJob job)
 {
+    static_assert(!(TRUNC && FETCH == FETCH_RAGGED), "the reference's tail truncation knows one shared face list");
     // record = {A.xyz, skip}, {B.xyz, -}, {C.xyz, -}
     __shared__ float4 tile[TRI_CHUNK * 3];
     __shared__ float part_d[TRI_WAVES][TRI_QUERIES];
@@ -217,6 +260,12 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_distance_kernel(TriJob job)
     const TriQuery tq = tri_query(job.xyz, mesh, job.n, blockIdx.x * TRI_QUERIES);
     const int lane = tq.lane, wave = tq.wave;
     const V3 p = tq.p;
+    if constexpr (FETCH == FETCH_RAGGED) {
+        if (!ragged_enter(job, mesh)) { // workgroup-uniform
+            ragged_empty(job, mesh, tq.q, tq.live);
+            return;
+        }
+    }
 
     float best = INFINITY;
     int best_key = INT_MAX; // (triangle << 3) | region
@@ -225,7 +274,7 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_distance_kernel(TriJob job)
         const int len = min(TRI_CHUNK, job.m - c0);
         for (int t = threadIdx.x; t < len; t += TRI_THREADS) {
             V3 A, B, C;
-            fetch_triangle<INDEXED>(job, mesh, c0 + t, A, B, C);
+            fetch_triangle<FETCH>(job, mesh, c0 + t, A, B, C);
             put_corners(tile + 3 * t, A, B, C, (TRUNC && geom::ref_tail_skipped(c0 + t, job.m)) ? 1.f : 0.f);
         }
         __syncthreads();
@@ -265,12 +314,12 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_distance_kernel(TriJob job)
             }
         }
         V3 A, B, C;
-        fetch_triangle<INDEXED>(job, mesh, 0, A, B, C);
+        fetch_triangle<FETCH>(job, mesh, 0, A, B, C);
         tri_finish<TRUNC, FIX6>(p, A, B, C, job.m, acc_k == INT_MAX, acc_d, acc_k);
         const size_t o = (size_t)mesh * job.n + tq.q;
         job.dist[o] = acc_d;
         job.point[o] = acc_k & 7;
-        job.index[o] = acc_k >> 3;
+        job.index[o] = winner_index<FETCH>(job, acc_k >> 3);
     }
 }
 
@@ -331,9 +380,10 @@ __device__ __forceinline__ float4 bounding_sphere(V3 A, V3 B, V3 C)
     return make_float4(c.x, c.y, c.z, r_eff);
 }
 
-template <bool INDEXED, bool TRUNC, bool FIX6>
+template <int FETCH, bool TRUNC, bool FIX6>
 __global__ __launch_bounds__(TRI_THREADS) void tri_distance_culled_kernel(TriJob job)
 {
+    static_assert(!(TRUNC && FETCH == FETCH_RAGGED), "the reference's tail truncation knows one shared face list");
     __shared__ float4 sph[CULL_CHUNK];        // {centre, r_eff}
     __shared__ float4 cor[CULL_CHUNK][3];     // corners A, B, C of the staged chunk
     __shared__ unsigned long long qbest[TRI_QUERIES];
@@ -344,6 +394,12 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_distance_culled_kernel(TriJob
     const TriQuery tq = tri_query(job.xyz, mesh, job.n, blockIdx.x * TRI_QUERIES);
     const int lane = tq.lane, wave = tq.wave;
     const V3 p = tq.p;
+    if constexpr (FETCH == FETCH_RAGGED) {
+        if (!ragged_enter(job, mesh)) { // workgroup-uniform, in front of the first barrier
+            ragged_empty(job, mesh, tq.q, tq.live);
+            return;
+        }
+    }
     const float p_mag = l1_norm(p);
     if (wave == 0) {
         qbest[lane] = KEY_NONE;
@@ -359,7 +415,7 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_distance_culled_kernel(TriJob
             const int len = min(CULL_CHUNK, hints - c0);
             for (int t = threadIdx.x; t < len; t += TRI_THREADS) {
                 V3 A, B, C;
-                fetch_triangle<INDEXED>(job, mesh, (c0 + t) * HINT_STRIDE, A, B, C);
+                fetch_triangle<FETCH>(job, mesh, (c0 + t) * HINT_STRIDE, A, B, C);
                 sph[t] = bounding_sphere<FIX6>(A, B, C);
             }
             __syncthreads();
@@ -377,7 +433,7 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_distance_culled_kernel(TriJob
         }
         if (!(TRUNC && geom::ref_tail_skipped(near_k, job.m))) {
             V3 A, B, C;
-            fetch_triangle<INDEXED>(job, mesh, near_k, A, B, C);
+            fetch_triangle<FETCH>(job, mesh, near_k, A, B, C);
             tri_evaluate<FIX6, false>(p, A, B, C, near_k, &qbest[lane]);
         }
         __syncthreads();
@@ -404,7 +460,7 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_distance_culled_kernel(TriJob
         const int len = min(CULL_CHUNK, job.m - c0);
         for (int t = threadIdx.x; t < len; t += TRI_THREADS) {
             V3 A, B, C;
-            fetch_triangle<INDEXED>(job, mesh, c0 + t, A, B, C);
+            fetch_triangle<FETCH>(job, mesh, c0 + t, A, B, C);
             float4 rec = bounding_sphere<FIX6>(A, B, C);
             if (TRUNC && geom::ref_tail_skipped(c0 + t, job.m)) rec.x = INFINITY; // culled unless s is inf/NaN
             sph[t] = rec;
@@ -446,12 +502,12 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_distance_culled_kernel(TriJob
         int acc_k;
         tri_unpack(word, acc_d, acc_k);
         V3 A, B, C;
-        fetch_triangle<INDEXED>(job, mesh, 0, A, B, C);
+        fetch_triangle<FETCH>(job, mesh, 0, A, B, C);
         tri_finish<TRUNC, FIX6>(p, A, B, C, job.m, word == KEY_NONE, acc_d, acc_k);
         const size_t o = (size_t)mesh * job.n + tq.q;
         job.dist[o] = acc_d;
         job.point[o] = acc_k & 7;
-        job.index[o] = acc_k >> 3;
+        job.index[o] = winner_index<FETCH>(job, acc_k >> 3);
     }
 }
 
@@ -1439,6 +1495,19 @@ int launch_tri(const TriJob &job, unsigned flags, void *stream)
     return geom::launch_status();
 }
 
+// the same two kernels for a batch whose meshes own their faces (no truncation mode: the caller refused it)
+int launch_tri_ragged(const TriJob &job, unsigned flags, void *stream)
+{
+    const dim3 grid((job.n + TRI_QUERIES - 1) / TRI_QUERIES, job.b, 1), block(TRI_THREADS);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool brute = flags & GEOM_FLAG_TRI_BRUTE_FORCE, fix6 = flags & GEOM_FLAG_FIX_REGION6;
+    with_flags([&](auto BRUTE, auto F6) {
+        if constexpr (BRUTE()) hipLaunchKernelGGL((tri_distance_kernel<FETCH_RAGGED, false, F6()>), grid, block, 0, s, job);
+        else hipLaunchKernelGGL((tri_distance_culled_kernel<FETCH_RAGGED, false, F6()>), grid, block, 0, s, job);
+    }, brute, fix6);
+    return geom::launch_status();
+}
+
 // The argument checks every tri entry point opens with (INDEXED: verts + faces, else the three corner arrays); the first
 // failing check decides the code.  TRI_EMPTY: nothing to do, the entry point returns 0.  more_missing: a further required
 // pointer of the entry point's own is null.
@@ -1487,6 +1556,19 @@ extern "C" int geom_tri_distance_indexed_f32(int b, int n, const float *xyz, int
 {
     const TriJob job{xyz, nullptr, nullptr, nullptr, verts, faces, dist, point, index, b, n, nf, nv};
     return tri_entry<true, false>(job, flags, nullptr, nullptr, 0, stream);
+}
+
+// Every mesh scans its OWN faces: mesh m's triangles are the faces face_list[face_off[m] .. face_off[m + 1]) of the union
+// face list, corners from the union verts; `index` is a union face id.  The checks are the indexed entry point's (nf the
+// union's face count) plus the two tables; the positions of a mesh share the key's 28 bits with nf < 2^26.
+extern "C" int geom_tri_distance_ragged_f32(int b, int n, const float *xyz, int nv, const float *verts, int nf,
+                                            const int64_t *faces, const int *face_list, const int *face_off, float *dist,
+                                            int *point, int *index, unsigned flags, void *stream)
+{
+    const TriJob job{xyz, nullptr, nullptr, nullptr, verts, faces, dist, point, index, b, n, nf, nv, face_list, face_off, nf};
+    if (const int code = tri_check<true>(job, !face_list || !face_off)) return code == TRI_EMPTY ? 0 : code;
+    if (flags & GEOM_FLAG_REF_TAIL_TRUNC) return GEOM_EINVAL;
+    return launch_tri_ragged(job, flags, stream);
 }
 
 // where the finalize tail's completion counters sit in a workspace of geom_tri_distance_workspace_bytes(b, n, m) bytes

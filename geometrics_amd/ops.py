@@ -866,6 +866,149 @@ def draw_samples(verts, faces, num, generator=None, with_points=False, prepare_s
     return choices, u, v
 
 
+# ------------------------------------- ragged batches: every mesh owns its faces ----
+def _ragged_mesh(verts, faces, face_list, face_off):
+    """The checked union mesh of a ragged batch: (verts [Vt,3] fp32, faces [Ft,3] int64, face_list int32 [Ft], face_off int32
+    [B+1]) contiguous on one device, and B."""
+    verts = _f32(verts.detach(), "verts", 2, 3)
+    faces = _lib.require(faces, "faces", torch.int64, 2, 3)
+    face_list = _lib.require(face_list, "face_list", torch.int32, 1)
+    face_off = _lib.require(face_off, "face_off", torch.int32, 1)
+    _lib.same_device(verts, faces, face_list, face_off)
+    if face_list.numel() != faces.shape[0] or face_off.numel() < 1:
+        raise RuntimeError("face_list must list the %d faces and face_off hold B+1 offsets (ragged.group_faces)" % faces.shape[0])
+    return verts, faces, face_list, face_off, face_off.numel() - 1
+
+
+def draw_samples_ragged(verts, faces, face_list, face_off, num, generator=None, with_points=False):
+    """draw_samples for a ragged batch (verts [Vt,3] the union, face_list / face_off from ragged.group_faces): `num` samples
+    per mesh from its OWN faces, choices [B,num] UNION face ids, u = sqrt(U1), v = U2 -- per mesh exactly what draw_samples
+    draws for that mesh's faces as mesh m of a batch of B, from the same in-kernel stream (or torch.rand uniforms with an
+    explicit `generator`).  One launch, no host read.  A mesh with no face or more than 16384 gets a valid face id and NaN
+    u / v / points (its face count is known on the device only): a loss on them is NaN, nothing indexes out of range."""
+    verts, faces, face_list, face_off, b = _ragged_mesh(verts, faces, face_list, face_off)
+    dev = verts.device
+    choices = torch.empty(b, num, dtype=torch.int64, device=dev)
+    u = torch.empty(b, num, dtype=torch.float32, device=dev)
+    v = torch.empty(b, num, dtype=torch.float32, device=dev)
+    points = torch.empty(b, num, 3, dtype=torch.float32, device=dev) if with_points else None
+    uniforms = None if generator is None else torch.rand(3, b, num, device=dev, generator=generator)
+    _lib.call("geom_draw_samples_ragged_f32", b, verts.shape[0], verts, faces.shape[0], faces, face_list, face_off, num, uniforms,
+              _rng_state(dev) if generator is None else None, choices, u, v, points)
+    return (choices, u, v, points) if with_points else (choices, u, v)
+
+
+def tri_distance_ragged(xyz, verts, faces, face_list, face_off, flags=None):
+    """(dist [B,N] fp32, point [B,N] int32 region codes, index [B,N] int32 UNION face ids): the closest triangle of every query
+    xyz[m] among the faces of mesh m only -- per mesh the bits of tri_distance_indexed on that mesh alone.  The workspace-free
+    culled scan (_lib.FLAG_TRI_BRUTE_FORCE: every pair).  A mesh without faces: (NaN, 0, 0)."""
+    xyz = _f32(xyz.detach(), "xyz", 3, 3)
+    verts, faces, face_list, face_off, b = _ragged_mesh(verts, faces, face_list, face_off)
+    if xyz.shape[0] != b or xyz.device != verts.device:
+        raise RuntimeError("xyz must be [B,N,3] on the meshes' device with B = %d meshes" % b)
+    n, dev = xyz.shape[1], xyz.device
+    dist = torch.empty(b, n, dtype=torch.float32, device=dev)
+    point = torch.empty(b, n, dtype=torch.int32, device=dev)
+    index = torch.empty(b, n, dtype=torch.int32, device=dev)
+    _lib.call("geom_tri_distance_ragged_f32", b, n, xyz, verts.shape[0], verts, faces.shape[0], faces, face_list, face_off, dist,
+              point, index, _lib.quirk_flags() if flags is None else flags)
+    return dist, point, index
+
+
+_row_offsets = {}     # (device, rows, stride) -> int32 [rows,1] = row * stride
+
+
+def _offsets_by_row(rows, stride, dev):
+    """int32 [rows,1] holding row * stride: what turns per-mesh indices [B,n] into indices of the flattened batch."""
+    make = lambda: (torch.arange(rows, dtype=torch.int32, device=dev) * stride).view(rows, 1)
+    if torch.cuda.is_current_stream_capturing():      # (memory made during a capture belongs to the graph: never kept)
+        return make()
+    key = (dev, rows, stride)
+    if key not in _row_offsets:
+        _row_offsets[key] = make()
+    return _row_offsets[key]
+
+
+class RaggedSurfaceLoss(torch.autograd.Function):
+    """SurfaceLoss for a ragged batch: B meshes with their own faces on one union vertex array, one call instead of B.
+
+    Value: the mean over the meshes of what SurfaceLoss gives for that mesh alone -- scale * (sum sq_pred / (B num) +
+    sum sq_other / (B N)).  Only the two steps that must know which faces belong to which mesh run on the ragged kernels (the
+    draw: ops.draw_samples_ragged, and the point-to-triangle scan); everything else sees either regular [B, ., 3] clouds
+    (the Chamfer scan at b = B) or the union as ONE mesh at b = 1 with the union's face ids (gather, closest point,
+    backward).  Backward: the fp32-atomic scatter kernels of SurfaceLoss's overflow fallback.  No host read."""
+
+    @staticmethod
+    def forward(ctx, verts, faces, face_list, face_off, gt, choices, u, v, two_sided, scale, points=None, need_gt_nn=True):
+        verts_c, faces, face_list, face_off, b = _ragged_mesh(verts, faces, face_list, face_off)
+        gt_c = _f32(gt.detach(), "gt_points", 3, 3)
+        if gt_c.shape[0] != b or gt_c.device != verts_c.device:
+            raise RuntimeError("gt_points must be [B,N,3] on the meshes' device with B = %d meshes" % b)
+        choices = _lib.require(choices.reshape(b, -1), "choices", torch.int64, 2)
+        u, v = _f32(u.reshape(b, -1), "u", 2), _f32(v.reshape(b, -1), "v", 2)
+        if u.shape != choices.shape or v.shape != choices.shape:
+            raise RuntimeError("choices/u/v must all be [B,num]")
+        nv, nf, num, n_gt, dev = verts_c.shape[0], faces.shape[0], choices.shape[1], gt_c.shape[1], verts_c.device
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        if points is None:      # replayed draws: the union is one mesh of B * num samples
+            points = torch.empty(b, num, 3, **f32)
+            _lib.call("geom_sample_faces_fwd_f32", 1, nv, verts_c, nf, faces, b * num, choices, u, v, points)
+        else:
+            points = _f32(points.detach(), "points", 3, 3)
+            if points.shape != (b, num, 3):
+                raise RuntimeError("points must be [B,num,3] for the given draws")
+        flags = _chamfer.default_flags()
+        if flags & _lib.FLAG_REF_TAIL_TRUNC:
+            raise RuntimeError("the ragged surface loss has no reference-quirk mode (set_reference_quirks(False))")
+        # Chamfer: samples and gt are regular clouds per mesh; the gt points' direction only where something reads it
+        one_dir = not need_gt_nn and not two_sided
+        sq_pred, idx_g = torch.empty(b, num, **f32), torch.empty(b, num, **i32)
+        sq_gt, idx_p = (None, None) if one_dir else (torch.empty(b, n_gt, **f32), torch.empty(b, n_gt, **i32))
+        _lib.call("geom_chamfer_nn_f32", b, n_gt, gt_c, num, points, sq_gt, idx_p, sq_pred, idx_g,
+                  flags | (_lib.FLAG_NN_SAMPLES_ONLY if one_dir else 0))
+        if two_sided:
+            other_sq = sq_gt
+        else:                   # every gt point against the faces of ITS mesh, then the closest point on the winner (b = 1)
+            option, index = torch.empty(b, n_gt, **i32), torch.empty(b, n_gt, **i32)
+            other_sq, closest, weights = torch.empty(b, n_gt, **f32), torch.empty(b, n_gt, 3, **f32), torch.empty(b, n_gt, 3, **f32)
+            _lib.call("geom_tri_distance_ragged_f32", b, n_gt, gt_c, nv, verts_c, nf, faces, face_list, face_off,
+                      torch.empty(b, n_gt, **f32), option, index, 0)
+            _lib.call("geom_p2tri_loss_fwd_f32", 1, b * n_gt, gt_c, nv, verts_c, nf, faces, option, index, other_sq, closest, weights)
+        parts, out = torch.empty(2, **f32), torch.empty((), **f32)
+        _lib.call("geom_sum_f32", sq_pred.numel(), sq_pred, scale / sq_pred.numel(), parts)
+        _lib.call("geom_sum_f32", other_sq.numel(), other_sq, scale / other_sq.numel(), parts[1:])
+        _lib.call("geom_sum_f32", 2, parts, 1.0, out)
+        if ctx.needs_input_grad[0]:     # the backward sees ONE mesh: per-mesh neighbour indices become indices of the flat batch
+            idx_g_flat = idx_g + _offsets_by_row(b, n_gt, dev)
+            if two_sided:
+                ctx.save_for_backward(faces, choices, u, v, points, gt_c, idx_g_flat, idx_p + _offsets_by_row(b, num, dev))
+            else:
+                ctx.save_for_backward(faces, choices, u, v, points, gt_c, idx_g_flat, index, closest, weights)
+        ctx.two_sided, ctx.scale, ctx.nv = two_sided, scale, nv
+        ctx.mark_non_differentiable(*(t for t in (sq_gt, sq_pred) if t is not None))
+        ctx.set_materialize_grads(False)
+        return out, sq_gt, sq_pred
+
+    @staticmethod
+    def backward(ctx, grad, _g1, _g2):
+        saved = ctx.saved_tensors
+        faces, choices, u, v, points, gt, idx_g = saved[:7]
+        b, num, _ = points.shape
+        n_gt, nf, nv = gt.shape[1], faces.shape[0], ctx.nv
+        grad = grad.contiguous()
+        grad_verts = torch.zeros(nv, 3, dtype=torch.float32, device=points.device)
+        coef_s, coef_o = ctx.scale / (b * num), ctx.scale / (b * n_gt)
+        if ctx.two_sided:
+            for other_idx, via_nn, coef in ((idx_g, 0, coef_s), (saved[7], 1, coef_o)):
+                _lib.call("geom_sample_chamfer_bwd_f32", 1, nv, nf, faces, b * num, choices, u, v, points, b * n_gt, gt, other_idx,
+                          via_nn, grad, coef, grad_verts)
+        else:
+            index, closest, weights = saved[7:10]
+            _lib.call("geom_surface_loss_bwd_f32", 1, nv, nf, faces, b * num, choices, u, v, points, b * n_gt, gt, idx_g, index,
+                      closest, weights, grad, coef_s, coef_o, grad_verts)
+        return (grad_verts,) + (None,) * 11
+
+
 class VertexHead(torch.autograd.Function):
     """pos = base + scale * feat[..., :3] in one kernel; the adjoint writes grad_feat = [scale*grad_pos | 0]
     in one pass (a slice + mul + add costs two launches forward and mul + zero-fill + strided copy backward)."""
@@ -895,7 +1038,7 @@ class VertexHead(torch.autograd.Function):
 
 __all__ = ["face_areas", "device_sum", "SampleFaces", "GatherSqDistSum", "PointToTriangleSum", "SurfaceLoss",
            "Laplacian", "EdgeSqLenSum", "PoolFeatures", "VertexHead", "SegmentMax", "manual_seed", "set_rng_state",
-           "draw_samples", "GtIndex", "ScanPrep",
+           "draw_samples", "GtIndex", "ScanPrep", "RaggedSurfaceLoss", "draw_samples_ragged", "tri_distance_ragged",
            "chamfer_nn", "tri_distance_indexed"]
 
 

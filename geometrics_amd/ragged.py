@@ -10,6 +10,7 @@ per-mesh maximum is a segmented reduction (csrc/segment.hip).
 import torch
 
 from . import layers
+from ._identity import ByTensor
 
 
 class RaggedMeshBatch:
@@ -99,4 +100,37 @@ class RaggedMeshBatch:
         return list(torch.split(x, self.sizes, dim=0))
 
 
-__all__ = ["RaggedMeshBatch"]
+# ------------------------------------------------- ragged batches of meshes with their OWN faces (the surface loss) ----
+# After the first adaptive split every image of a batch owns a topology.  The batch is then ONE union mesh -- vertices
+# concatenated as above, faces [Ft,3] indexing the union -- plus the id of its mesh per face.  The two searches of the surface
+# loss must not cross from one mesh into another, so they walk the faces GROUPED by mesh.
+_group_cache = ByTensor()    # (faces, face_mesh) or (face_mesh,), extra: the mesh count -> (face_list, face_off)
+
+
+def group_faces(face_mesh, b, faces=None):
+    """(face_list int32 [Ft], face_off int32 [b+1]) on face_mesh's device: face_list = argsort(face_mesh, stable=True), the
+    faces grouped by mesh and ascending inside a mesh; face_off = [0, cumsum(bincount(face_mesh, minlength=b))], where each
+    group starts.  Position k of mesh m is the face face_list[face_off[m] + k].  Torch ops only, no host read (the counts
+    come from a binary search over the sorted ids, which unlike bincount needs none); a face whose id is outside [0, b)
+    belongs to no mesh.  Cached per (faces, face_mesh) TENSOR OBJECTS and their in-place versions, as utils.active_faces."""
+    if face_mesh.dim() != 1:
+        raise RuntimeError("face_mesh must be [Ft] (got shape %s)" % (tuple(face_mesh.shape),))
+    keys = (face_mesh,) if faces is None else (faces, face_mesh)
+    hit = _group_cache.get(*keys, extra=int(b))
+    if hit is None:
+        with torch.no_grad():
+            ids = face_mesh.detach().to(torch.int64)
+            order = torch.argsort(ids, stable=True)
+            bounds = torch.arange(int(b) + 1, dtype=torch.int64, device=ids.device)
+            face_off = torch.searchsorted(ids[order].contiguous(), bounds)      # first position whose id is >= m
+            hit = _group_cache.put((order.to(torch.int32).contiguous(), face_off.to(torch.int32).contiguous()), *keys, extra=int(b))
+    return hit
+
+
+def face_mesh(faces, vert_mesh):
+    """vert_mesh[faces[:, 0]]: the mesh of every face from the mesh of every vertex -- for callers that track ids per vertex
+    (through utils.split_info a new vertex inherits its face's mesh)."""
+    return vert_mesh[faces[:, 0]]
+
+
+__all__ = ["RaggedMeshBatch", "group_faces", "face_mesh"]

@@ -223,6 +223,45 @@ def batch_point_to_surface(pred_vert, adj_info, gt_points, num=1000, f1=False, d
     return _surface_loss(pred_vert, adj_info, gt_points, num, f1, draws, False, loss_out, gt_index, weight)
 
 
+def _ragged_surface_loss(verts, faces, face_mesh, gt_points, num, f1, draws, two_sided):
+    from . import ragged
+    if gt_points.dim() != 3:
+        raise RuntimeError("gt_points must be [B,N,3] (got shape %s)" % (tuple(gt_points.shape),))
+    if face_mesh.dim() != 1 or face_mesh.shape[0] != faces.shape[0]:
+        raise RuntimeError("face_mesh must hold one mesh id per face: [%d] (got shape %s)" % (faces.shape[0], tuple(face_mesh.shape)))
+    b = gt_points.shape[0]
+    face_list, face_off = ragged.group_faces(face_mesh, b, faces)
+    points = None
+    if draws is None:       # one launch draws AND gathers the points
+        choices, u, v, points = ops.draw_samples_ragged(verts, faces, face_list, face_off, num, with_points=True)
+    else:
+        choices, u, v = draws
+    need_gt_nn = bool(f1) or two_sided
+    loss, sq_gt, sq_pred = ops.RaggedSurfaceLoss.apply(verts, faces, face_list, face_off, gt_points, choices, u, v, two_sided,
+                                                       LOSS_SCALE, points, need_gt_nn)
+    if f1:
+        return loss, _f_score(sq_gt, sq_pred, num)
+    return loss
+
+
+def ragged_point_to_surface(verts, faces, face_mesh, gt_points, num=1000, f1=False, draws=None):
+    """batch_point_to_surface for a RAGGED batch: B meshes with their own faces, as after an adaptive split.  verts [Vt,3]
+    fp32 (differentiable): the meshes' vertices concatenated, as in ragged.RaggedMeshBatch; faces [Ft,3] int64 into verts: the
+    faces the loss runs on (active_faces for split meshes); face_mesh [Ft] in [0, B): the mesh of every face, in any order
+    (ragged.face_mesh derives it from per-vertex ids); gt_points [B,N,3].  Value: the mean over m of
+    batch_point_to_surface(verts[None], {'faces': the faces of mesh m}, gt_points[m:m+1], num) -- 3000 * (sum sq_pred / (B num)
+    + sum sq_tri / (B N)) -- in ONE call: neither search crosses from one mesh into another and every mesh gets `num`
+    samples.  draws=(choices [B,num] UNION face ids, u, v) replays draws.  No host read unless f1=True, no padding.  Each
+    mesh may hold 1 to 16384 faces; a mesh outside that makes the loss NaN (ops.draw_samples_ragged)."""
+    return _ragged_surface_loss(verts, faces, face_mesh, gt_points, num, f1, draws, False)
+
+
+def ragged_point_to_point(verts, faces, face_mesh, gt_points, num=1000, f1=False, draws=None):
+    """batch_point_to_point for a ragged batch: arguments and contract as ragged_point_to_surface, the mean over m of
+    batch_point_to_point on mesh m alone."""
+    return _ragged_surface_loss(verts, faces, face_mesh, gt_points, num, f1, draws, True)
+
+
 def calc_point_to_line(p, triangles, point_options):
     """mean |closest(p; a,b,c, option) - p|^2 for per-point triangles (reference utils.py:506-550).
     p [N,3]; triangles = (a, b, c) each [N,3]; point_options [N] int."""

@@ -104,6 +104,18 @@ int geom_tri_distance_indexed_f32(int b, int n, const float *xyz, int nv, const 
                                   int nf, const int64_t *faces,
                                   float *dist, int *point, int *index, unsigned flags, void *stream);
 
+/* The same scan for a RAGGED batch: every mesh owns its faces.  verts [nv,3] is the union of the meshes' vertices, faces
+ * [nf,3] int64 the union face list indexing it; face_list int32 [nf] lists the faces grouped by mesh, ascending inside a mesh,
+ * and face_off int32 [b+1] says where each group starts (python: ragged.group_faces).  Queries xyz [b,n,3] of mesh m are
+ * scanned against the faces face_list[face_off[m] .. face_off[m+1]) only: dist / point are, bit for bit, those of
+ * geom_tri_distance_indexed_f32 on that mesh alone (ties go to the lowest face id), index [b,n] is the UNION face id.
+ * The workspace-free culled scan; GEOM_FLAG_TRI_BRUTE_FORCE and GEOM_FLAG_FIX_REGION6 as above, GEOM_FLAG_REF_TAIL_TRUNC is
+ * GEOM_EINVAL.  A mesh without faces gets dist NaN, point 0, index 0 (nothing is fetched for it); face counts live on the
+ * device only, so that is no error.  nf < 2^26; table entries outside [0, nf) are clamped, never followed. */
+int geom_tri_distance_ragged_f32(int b, int n, const float *xyz, int nv, const float *verts,
+                                 int nf, const int64_t *faces, const int *face_list, const int *face_off,
+                                 float *dist, int *point, int *index, unsigned flags, void *stream);
+
 /* Workspace variants (what the python operators call): identical results; the scan reads
  * per-triangle {bounding sphere, corners} records that a prep kernel writes into `workspace`
  * (device memory, 16-byte aligned, at least geom_tri_distance_workspace_bytes(b, n, m) bytes,
@@ -158,6 +170,16 @@ int geom_draw_samples_f32(int b, int nv, const float *verts, int nf, const int64
 int geom_draw_samples_rng_f32(int b, int nv, const float *verts, int nf, const int64_t *faces, int num,
                               uint64_t *rng_state, int64_t *choices, float *u, float *v, float *points,
                               void *stream);
+/* The same draws for a RAGGED batch (verts / faces / face_list / face_off as for geom_tri_distance_ragged_f32): `num` samples
+ * per mesh from the mesh's OWN faces.  Exactly one of uniforms ([3][b][num]) and rng_state is given, the other NULL.  Mesh m
+ * draws what geom_draw_samples_f32 / _rng_f32 draw for (verts, the faces of mesh m in face_list order) as mesh m of a batch
+ * of b -- the same table, uniforms and Philox counter (sample, first global mesh index + m, position) -- and choices [b,num]
+ * holds UNION face ids.  points [b,num,3] may be NULL.  A mesh with no face or more than 16384 (its table lives in LDS; the
+ * count is known on the device only) gets a valid face id in choices (its first listed face, or 0) and NaN in u, v and
+ * points: no index is out of range and a loss on them is NaN.  The stream position advances once per call either way. */
+int geom_draw_samples_ragged_f32(int b, int nv, const float *verts, int nf, const int64_t *faces, const int *face_list,
+                                 const int *face_off, int num, const float *uniforms, uint64_t *rng_state,
+                                 int64_t *choices, float *u, float *v, float *points, void *stream);
 /* points[b,num,3] = (1-u)*x + (u*(1-v))*y + (u*v)*z with x,y,z the corners of face
  * choices[b,num] (int64 face ids), u already sqrt'ed (utils.py:615-631). */
 int geom_sample_faces_fwd_f32(int b, int nv, const float *verts, int nf, const int64_t *faces,
