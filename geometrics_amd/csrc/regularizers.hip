@@ -191,7 +191,195 @@ __global__ __launch_bounds__(RG_THREADS) void stage_reg_bwd_kernel(StageRegArgs 
     a.grad_cur[3 * vi + 0] = ge.x - g.x, a.grad_cur[3 * vi + 1] = ge.y - g.y, a.grad_cur[3 * vi + 2] = ge.z - g.z;
 }
 
+// ---- the same regularisers for a RAGGED batch: b meshes with their own topology on ONE union mesh ------------------------------
+// After the first adaptive split every image of a batch owns its vertices, faces and adjacency; the union's vertices and faces
+// stand in any order (new vertices at the end: the meshes interleave).  The means are per mesh, so a vertex's or a face's term
+// is multiplied by ITS mesh's entry of coef [3,b] = (w_lap[m] / (b V_m), w_move[m] / (b V_m), w_edge[m] / (3 b F_m)), which the
+// caller fills on the device (the counts are known there only).  Same structure as the pair above: eight lanes per vertex, the
+// fixed xor tree, one partial per workgroup forward, a gather backward, no float atomics.  Every index that is followed --
+// rowptr, col, the corners of a face, vf_ptr, vf_item, the mesh ids -- is checked against what it points into; an id outside
+// [0, b) selects coefficient 0 (that vertex or face has no term; its position is still read by its neighbours' Laplacians).
+struct RaggedRegArgs {
+    const float *prev, *cur;       // [nv,3] each; prev null with rowptr
+    int b, nv, nf, nnz;
+    const int64_t *faces;          // null: no edge term
+    const int *vert_mesh, *face_mesh;
+    const float *coef;             // [3,b]
+    const int *rowptr, *col;       // null: neither the Laplacian nor the displacement term
+    const float *inv_deg;
+    const int *vf_ptr, *vf_item;   // backward
+    float *lapd, *partial;
+    const float *gout;
+    float *grad_prev, *grad_cur;
+};
+
+__device__ __forceinline__ float rr_coef(const RaggedRegArgs &a, int row, int mesh)
+{
+    return (unsigned)mesh < (unsigned)a.b ? a.coef[(size_t)row * a.b + mesh] : 0.f;
+}
+__device__ __forceinline__ V3 rr_d(const RaggedRegArgs &a, int j) { return ld3(a.prev + 3 * (size_t)j) - ld3(a.cur + 3 * (size_t)j); }
+__device__ __forceinline__ int rr_clamp(int e, int hi) { return e < 0 ? 0 : e > hi ? hi : e; }
+// the three corners of face f, or false when one of them is no vertex of the union
+__device__ __forceinline__ bool rr_face(const RaggedRegArgs &a, int f, V3 &p1, V3 &p2, V3 &p3)
+{
+    const int64_t i1 = a.faces[3 * (size_t)f + 0], i2 = a.faces[3 * (size_t)f + 1], i3 = a.faces[3 * (size_t)f + 2];
+    if ((uint64_t)i1 >= (uint64_t)a.nv || (uint64_t)i2 >= (uint64_t)a.nv || (uint64_t)i3 >= (uint64_t)a.nv) return false;
+    p1 = ld3(a.cur + 3 * i1), p2 = ld3(a.cur + 3 * i2), p3 = ld3(a.cur + 3 * i3);
+    return true;
+}
+
+__global__ __launch_bounds__(RG_THREADS) void ragged_reg_fwd_kernel(RaggedRegArgs a)
+{
+    __shared__ float red[RG_THREADS / GEOM_WAVE];
+    const int64_t i = (int64_t)blockIdx.x * RG_THREADS + threadIdx.x;
+    const int64_t vi = i / RG_SUB;
+    const int sub = (int)(i % RG_SUB);
+    float t = 0.f;
+    if (a.rowptr) {
+        const bool vertex_on = vi < a.nv; // (uniform over the 8 lanes of a vertex)
+        const int v = vertex_on ? (int)vi : 0;
+        V3 s = geom::mk(0.f, 0.f, 0.f);
+        if (vertex_on) {
+            const int end = rr_clamp(a.rowptr[v + 1], a.nnz);
+            for (int e = rr_clamp(a.rowptr[v], a.nnz) + sub; e < end; e += RG_SUB) {
+                const int j = a.col[e];
+                if ((unsigned)j < (unsigned)a.nv) s = s + rr_d(a, j);
+            }
+        }
+        s = rg_fold8(s);
+        if (vertex_on && sub == 0) {
+            const V3 self = rr_d(a, v);
+            const V3 lap = self - (s - self) * a.inv_deg[v];
+            a.lapd[3 * vi + 0] = lap.x, a.lapd[3 * vi + 1] = lap.y, a.lapd[3 * vi + 2] = lap.z;
+            const int mesh = a.vert_mesh[v];
+            t = rr_coef(a, 0, mesh) * geom::dot3(lap, lap) + rr_coef(a, 1, mesh) * geom::dot3(self, self);
+        }
+    }
+    if (a.faces && i < a.nf) {
+        V3 p1, p2, p3;
+        if (rr_face(a, (int)i, p1, p2, p3)) {
+            const V3 e1 = p2 - p1, e2 = p3 - p1, e3 = p2 - p3;
+            t += rr_coef(a, 2, a.face_mesh[i]) * ((geom::dot3(e1, e1) + geom::dot3(e2, e2)) + geom::dot3(e3, e3));
+        }
+    }
+    // a mesh of [0, b) without a vertex (or without a face, its edge weight not 0) has a non-finite entry that no vertex or
+    // face reads: the mean over nothing is NaN, as in the reference.  0 * entry carries it into the sum and leaves a finite one be.
+    if (blockIdx.x == 0)
+        for (int k = threadIdx.x; k < 3 * a.b; k += RG_THREADS) t += 0.f * a.coef[k];
+    for (int off = GEOM_WAVE / 2; off > 0; off >>= 1) t += __shfl_down(t, off, GEOM_WAVE);
+    if ((threadIdx.x & (GEOM_WAVE - 1)) == 0) red[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) a.partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// A vertex's neighbours need not share its mesh (nor have one), so the Laplacian coefficient is looked up per neighbour.
+__global__ __launch_bounds__(RG_THREADS) void ragged_reg_bwd_kernel(RaggedRegArgs a)
+{
+    const int64_t i = (int64_t)blockIdx.x * RG_THREADS + threadIdx.x;
+    const int64_t vi = i / RG_SUB;
+    const int sub = (int)(i % RG_SUB);
+    const bool on = vi < a.nv;
+    const int v = on ? (int)vi : 0;
+    const float go = a.gout[0];
+    V3 s = geom::mk(0.f, 0.f, 0.f);
+    if (a.rowptr && on) {
+        const int end = rr_clamp(a.rowptr[v + 1], a.nnz);
+        for (int e = rr_clamp(a.rowptr[v], a.nnz) + sub; e < end; e += RG_SUB) {
+            const int j = a.col[e];
+            if ((unsigned)j < (unsigned)a.nv) s = s + ld3(a.lapd + 3 * (size_t)j) * (a.inv_deg[j] * rr_coef(a, 0, a.vert_mesh[j]));
+        }
+    }
+    s = rg_fold8(s);
+    V3 ge = geom::mk(0.f, 0.f, 0.f);
+    if (a.vf_ptr) {
+        if (on) {
+            const int end = rr_clamp(a.vf_ptr[v + 1], 3 * a.nf);
+            for (int e = rr_clamp(a.vf_ptr[v], 3 * a.nf) + sub; e < end; e += RG_SUB) { // the vertex's (face, corner) list
+                const int item = a.vf_item[e], f = item >> 2, corner = item & 3;
+                V3 p1, p2, p3;
+                if ((unsigned)f >= (unsigned)a.nf || corner == 3 || !rr_face(a, f, p1, p2, p3)) continue;
+                const V3 e1 = p2 - p1, e2 = p3 - p1, e3 = p2 - p3;
+                ge = ge + (corner == 0 ? (e1 + e2) * -1.f : corner == 1 ? e1 + e3 : e2 - e3) * rr_coef(a, 2, a.face_mesh[f]);
+            }
+        }
+        ge = rg_fold8(ge) * (2.f * go);
+    }
+    if (!on || sub != 0) return;
+    V3 g = geom::mk(0.f, 0.f, 0.f);
+    if (a.rowptr) {
+        const int mesh = a.vert_mesh[v];
+        const V3 y = ld3(a.lapd + 3 * (size_t)v) * rr_coef(a, 0, mesh);
+        const V3 lty = y - (s - y * a.inv_deg[v]);                                           // transposed Laplacian of coef * lapd
+        g = (lty * 2.f + rr_d(a, v) * (2.f * rr_coef(a, 1, mesh))) * go;                     // d total / d (prev - cur)[v]
+        if (a.grad_prev) a.grad_prev[3 * vi + 0] = g.x, a.grad_prev[3 * vi + 1] = g.y, a.grad_prev[3 * vi + 2] = g.z;
+    }
+    a.grad_cur[3 * vi + 0] = ge.x - g.x, a.grad_cur[3 * vi + 1] = ge.y - g.y, a.grad_cur[3 * vi + 2] = ge.z - g.z;
+}
+
 } // namespace
+
+// The stage regularisers of a ragged batch (see RaggedRegArgs).  partial [geom_ragged_regularisers_blocks(nv, nf)] per-workgroup
+// sums of  sum_f coef[2][face_mesh[f]] (|e1|^2+|e2|^2+|e3|^2)(cur) + sum_v coef[0][vert_mesh[v]] |lap(prev - cur)_v|^2
+// + coef[1][vert_mesh[v]] |(prev - cur)_v|^2  (finish with geom_sum_f32), lapd [nv,3] = lap(prev - cur) for the backward.
+// rowptr == NULL: the edge term alone (prev, vert_mesh, col, inv_deg, lapd are not read); faces == NULL or nf == 0: no edge term.
+extern "C" int64_t geom_ragged_regularisers_blocks(int nv, int nf)
+{
+    const int64_t nvt = (int64_t)(nv > 0 ? nv : 0) * RG_SUB;
+    const int64_t n = nvt > nf ? nvt : nf;
+    return (n + RG_THREADS - 1) / RG_THREADS;
+}
+namespace {
+// what both directions refuse; fills the shared part of the arguments
+int ragged_reg_args(RaggedRegArgs &a, int b, int nv, const float *prev, const float *cur, int nf, const int64_t *faces,
+                    const int *vert_mesh, const int *face_mesh, const float *coef, int nnz, const int *rowptr, const int *col,
+                    const float *inv_deg, const float *lapd)
+{
+    if (!cur || !coef) return GEOM_EINVAL;
+    if (rowptr && (!prev || !vert_mesh || !col || !inv_deg || !lapd)) return GEOM_EINVAL;
+    if (nf > 0 && faces && !face_mesh) return GEOM_EINVAL;
+    a.prev = prev, a.cur = cur, a.b = b, a.nv = nv, a.nf = nf, a.nnz = nnz, a.faces = nf > 0 ? faces : nullptr;
+    a.vert_mesh = vert_mesh, a.face_mesh = face_mesh, a.coef = coef, a.rowptr = rowptr, a.col = col, a.inv_deg = inv_deg;
+    a.lapd = const_cast<float *>(lapd);
+    return 0;
+}
+} // namespace
+extern "C" int geom_ragged_regularisers_fwd_f32(int b, int nv, const float *prev, const float *cur, int nf, const int64_t *faces,
+                                                const int *vert_mesh, const int *face_mesh, const float *coef, int nnz,
+                                                const int *rowptr, const int *col, const float *inv_deg, float *lapd,
+                                                float *partial, void *stream)
+{
+    if (b < 0 || nv < 0 || nf < 0 || nnz < 0) return GEOM_EINVAL;
+    if (b > INT32_MAX / 3 || nf > INT32_MAX / 3) return GEOM_ETOOBIG; // 3 b table entries, 3 nf corners: int indices
+    if (b == 0 || nv == 0) return 0;
+    RaggedRegArgs a{};
+    if (!partial) return GEOM_EINVAL;
+    if (const int code = ragged_reg_args(a, b, nv, prev, cur, nf, faces, vert_mesh, face_mesh, coef, nnz, rowptr, col, inv_deg, lapd))
+        return code;
+    a.partial = partial;
+    hipLaunchKernelGGL(ragged_reg_fwd_kernel, dim3((unsigned)geom_ragged_regularisers_blocks(nv, nf)), dim3(RG_THREADS), 0,
+                       static_cast<hipStream_t>(stream), a);
+    return geom::launch_status();
+}
+// grad_cur [nv,3] (and grad_prev [nv,3] when given; rowptr != NULL only) of gout[0] * that sum; vf_ptr [nv+1] / vf_item [3 nf] as
+// geom_stage_regularisers_bwd_f32, NULL (with faces) when there is no edge term.
+extern "C" int geom_ragged_regularisers_bwd_f32(int b, int nv, const float *prev, const float *cur, int nf, const int64_t *faces,
+                                                const int *vert_mesh, const int *face_mesh, const float *coef, int nnz,
+                                                const int *rowptr, const int *col, const float *inv_deg, const int *vf_ptr,
+                                                const int *vf_item, const float *lapd, const float *gout, float *grad_prev,
+                                                float *grad_cur, void *stream)
+{
+    if (b < 0 || nv < 0 || nf < 0 || nnz < 0) return GEOM_EINVAL;
+    if (b > INT32_MAX / 3 || nf > INT32_MAX / 3) return GEOM_ETOOBIG; // 3 b table entries, 3 nf corners: int indices
+    if (b == 0 || nv == 0) return 0;
+    RaggedRegArgs a{};
+    if (!gout || !grad_cur || (grad_prev && !rowptr)) return GEOM_EINVAL;
+    if (const int code = ragged_reg_args(a, b, nv, prev, cur, nf, faces, vert_mesh, face_mesh, coef, nnz, rowptr, col, inv_deg, lapd))
+        return code;
+    if (a.faces && (!vf_ptr || !vf_item)) return GEOM_EINVAL;
+    a.vf_ptr = a.faces ? vf_ptr : nullptr, a.vf_item = vf_item, a.gout = gout, a.grad_prev = grad_prev, a.grad_cur = grad_cur;
+    hipLaunchKernelGGL(ragged_reg_bwd_kernel, rg_grid((int64_t)nv * RG_SUB), dim3(RG_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    return geom::launch_status();
+}
 
 // partial [geom_stage_regularisers_blocks(b, nv, nf)] per-workgroup sums of
 //   c_edge * sum_faces(|e1|^2+|e2|^2+|e3|^2)(cur) + c_lap * sum_v |lap(prev - cur)|^2 + c_move * sum_v |prev - cur|^2

@@ -556,6 +556,59 @@ class StageRegularisers(torch.autograd.Function):
         return grad_prev, (grad_cur if ctx.needs_input_grad[1] else None), None, None, None, None, None, None, None
 
 
+class RaggedStageRegularisers(torch.autograd.Function):
+    """StageRegularisers for a RAGGED batch on one union mesh: prev, cur [Vt,3]; faces [Ft,3] int64 into
+    the union or None (no edge term); face_mesh [Ft], vert_mesh [Vt] int32 mesh ids; coef [3,b] fp32 on the device
+    (ragged.regulariser_tables: the weights over each mesh's own counts); (rowptr, col, inv_deg) the union's adjacency, or
+    all None: the edge term alone (prev and vert_mesh None as well).  The sum over the vertices and faces of each one's term
+    times ITS mesh's coefficient: ONE launch forward (+ the fixed-order sum of its partials), ONE backward, no host read."""
+
+    @staticmethod
+    def forward(ctx, prev, cur, faces, face_mesh, vert_mesh, coef, rowptr, col, inv_deg):
+        c = _f32(cur, "cur", 2, 3)
+        nv = c.shape[0]
+        coef = _f32(coef, "coef", 2)
+        b = coef.shape[1]
+        if coef.shape[0] != 3 or b == 0 or nv == 0:
+            raise RuntimeError("coef must be [3,b] with b >= 1 and the union must hold a vertex (got %s, %d vertices)"
+                               % (tuple(coef.shape), nv))
+        lap = rowptr is not None
+        p = lapd = None
+        if lap:
+            p = _f32(prev, "prev", 2, 3)
+            if p.shape != c.shape or vert_mesh.shape != (nv,) or rowptr.numel() != nv + 1 or inv_deg.numel() != nv:
+                raise RuntimeError("prev, vert_mesh and the adjacency must describe cur's %d vertices" % nv)
+            lapd = torch.empty_like(c)
+        nf = 0
+        if faces is not None and faces.shape[0]:
+            faces = _lib.require(faces, "faces", torch.int64, 2, 3)
+            nf = faces.shape[0]
+            if face_mesh.shape != (nf,):
+                raise RuntimeError("face_mesh must be [%d], one id per face (got %s)" % (nf, tuple(face_mesh.shape)))
+        else:
+            faces = None
+        partial = torch.empty(int(_lib.lib().geom_ragged_regularisers_blocks(nv, nf)), dtype=torch.float32, device=c.device)
+        nnz = col.numel() if lap else 0
+        _lib.call("geom_ragged_regularisers_fwd_f32", b, nv, p, c, nf, faces, vert_mesh, face_mesh, coef, nnz, rowptr, col, inv_deg,
+                  lapd, partial)
+        ctx.save_for_backward(p, c, faces, face_mesh, vert_mesh, coef, rowptr, col, inv_deg, lapd)
+        return device_sum(partial)
+
+    @staticmethod
+    def backward(ctx, grad):
+        p, c, faces, face_mesh, vert_mesh, coef, rowptr, col, inv_deg, lapd = ctx.saved_tensors
+        nv, b = c.shape[0], coef.shape[1]
+        nf = faces.shape[0] if faces is not None else 0
+        vf_ptr, vf_item = vertex_faces(faces, nv) if nf else (None, None)
+        want_prev = p is not None and ctx.needs_input_grad[0]
+        grad_cur = torch.empty_like(c)
+        grad_prev = torch.empty_like(c) if want_prev else None
+        _lib.call("geom_ragged_regularisers_bwd_f32", b, nv, p, c, nf, faces, vert_mesh, face_mesh, coef,
+                  col.numel() if col is not None else 0, rowptr, col, inv_deg, vf_ptr, vf_item, lapd, grad.contiguous(), grad_prev,
+                  grad_cur)
+        return grad_prev, (grad_cur if ctx.needs_input_grad[1] else None), None, None, None, None, None, None, None
+
+
 # ---- feature buffers with HEADROOM: concatenation without torch.cat ------------------------------------------------------------
 # The driver builds a deformation block's input as cat(positions, cat(previous features, pooled features)) (GEOMetrics.py:118-131,
 # models.py:241): two copies of ~35 MB forward per stage, and slicing copies of the same size when the gradient of the

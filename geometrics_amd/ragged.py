@@ -46,20 +46,7 @@ class RaggedMeshBatch:
                 raise RuntimeError("meshes are (verts [V,3], faces [F,3]) pairs")
             shifted.append(f.to(dev, torch.int64) + base)
             base += v.shape[0]
-        faces = torch.cat(shifted)
-        a, b, c = faces[:, 0], faces[:, 1], faces[:, 2]
-        loops = torch.arange(total, device=dev)
-        rows = torch.cat([a, a, b, b, c, c, loops])
-        cols = torch.cat([b, c, a, c, a, b, loops])
-        keys = torch.unique(rows * total + cols)          # sorted: row-major == CSR order
-        rows, cols = keys // total, keys % total
-        counts = torch.bincount(rows, minlength=total)
-        rowptr = torch.zeros(total + 1, dtype=torch.int64, device=dev)
-        rowptr[1:] = torch.cumsum(counts, 0)
-        r_inv = 1.0 / counts.to(torch.float32)            # normalize_adj: 1 / row sum of the binary matrix
-        rowptr, col = rowptr.to(torch.int32), cols.to(torch.int32).contiguous()
-        # the pattern is symmetric, so CSR^T shares rowptr/col and only swaps which row's scale an entry carries
-        csr = layers.csr_from_parts(rowptr, col, r_inv[rows].contiguous(), rowptr, col, r_inv[cols].contiguous())
+        csr = csr_from_faces(torch.cat(shifted), total)
         verts = torch.cat([v.to(dev, torch.float32) for v in verts_list]).contiguous()
         return cls(verts, sizes, csr)
 
@@ -133,4 +120,99 @@ def face_mesh(faces, vert_mesh):
     return vert_mesh[faces[:, 0]]
 
 
-__all__ = ["RaggedMeshBatch", "group_faces", "face_mesh"]
+def csr_from_faces(faces, nv):
+    """The adjacency of a union mesh straight from its triangles: faces [Ft,3] int64 into nv vertices -> a layers._Csr of the
+    binary pattern with self loops, block-diagonal wherever no face joins two meshes; its values are the normalised adjacency
+    D^-1 (A + I) of utils.py:96-131 (pass it wherever a layer takes `adj`), its rowptr / col / inv_deg are what the Laplacian
+    and utils.ragged_stage_regularisers read.  Assembled directly in CSR: no dense [V,V] matrix is ever formed and the number
+    of distinct edges is the one host read of the assembly (layers' derived tables look at the row lengths once more); build
+    it once per topology and keep the result."""
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int64:
+        raise RuntimeError("faces must be [Ft,3] int64 (got %s %s)" % (faces.dtype, tuple(faces.shape)))
+    total, dev = int(nv), faces.device
+    with torch.no_grad():
+        a, b, c = faces[:, 0], faces[:, 1], faces[:, 2]
+        loops = torch.arange(total, device=dev)
+        rows = torch.cat([a, a, b, b, c, c, loops])
+        cols = torch.cat([b, c, a, c, a, b, loops])
+        keys = torch.unique(rows * total + cols)          # sorted: row-major == CSR order
+        rows, cols = keys // total, keys % total
+        # where each row starts: a search over the sorted rows (bincount would read its maximum on the host)
+        rowptr = torch.searchsorted(rows.contiguous(), torch.arange(total + 1, device=dev))
+        counts = rowptr[1:] - rowptr[:-1]
+        r_inv = 1.0 / counts.to(torch.float32)            # normalize_adj: 1 / row sum of the binary matrix
+        rowptr, col = rowptr.to(torch.int32), cols.to(torch.int32).contiguous()
+        # the pattern is symmetric, so CSR^T shares rowptr/col and only swaps which row's scale an entry carries
+        return layers.csr_from_parts(rowptr, col, r_inv[rows].contiguous(), rowptr, col, r_inv[cols].contiguous())
+
+
+_count_cache = ByTensor()    # (ids,), extra: the mesh count -> (ids int32, counts int64 [b])
+
+
+def mesh_counts(ids, b):
+    """(ids as int32 [n], counts int64 [b]) on ids' device: how many vertices (or faces) every mesh of [0, b) holds.  An id
+    outside [0, b) belongs to no mesh and is counted nowhere (it is stored as -1 or b).  A sort and a binary search, no host
+    read (bincount needs one); cached per ids TENSOR OBJECT and in-place version, as group_faces."""
+    if ids.dim() != 1 or ids.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("mesh ids must be a one-dimensional int32 or int64 tensor (got %s %s)" % (ids.dtype, tuple(ids.shape)))
+    hit = _count_cache.get(ids, extra=int(b))
+    if hit is None:
+        with torch.no_grad():
+            clamped = ids.detach().to(torch.int64).clamp(-1, int(b))
+            bounds = torch.arange(int(b) + 1, dtype=torch.int64, device=ids.device)
+            starts = torch.searchsorted(torch.sort(clamped).values, bounds)      # first position whose id is >= m
+            hit = _count_cache.put((clamped.to(torch.int32).contiguous(), (starts[1:] - starts[:-1]).contiguous()), ids, extra=int(b))
+    return hit
+
+
+_coef_cache = ByTensor()     # the id tensors and the weight tensors, extra: (b, the python weights, ...) -> coef [3,b]
+
+
+def _weight_row(w, b, dev):
+    if torch.is_tensor(w):
+        if w.shape != (b,) or w.dtype != torch.float32 or w.device != dev:
+            raise RuntimeError("a per-mesh weight must be a [%d] float32 tensor on %s (got %s %s on %s)"
+                               % (b, dev, w.dtype, tuple(w.shape), w.device))
+        return w.detach().to(torch.float64)
+    return torch.full((b,), float(w), dtype=torch.float64, device=dev)
+
+
+def regulariser_coefficients(vert_counts, face_counts, b, w_lap, w_move, w_edge):
+    """coef [3,b] fp32 of the ragged stage regularisers from the per-mesh counts (int64 [b] each, on their device; vert_counts
+    None: no Laplacian and no displacement term): rows w_lap[m] / (b V_m), w_move[m] / (b V_m), w_edge[m] / (3 b F_m), formed in
+    float64 and rounded once.  A weight is a python float or a [b] fp32 tensor.  The reference's mean over nothing is NaN: a
+    mesh without a vertex gets NaN in the first two rows WHATEVER its weights, a mesh without a face NaN in the third where
+    its edge weight is not 0 (and 0 where it is).  Torch ops on the counts' device, no host read."""
+    dev = face_counts.device
+    nan = torch.full((b,), float("nan"), dtype=torch.float64, device=dev)
+    zero = torch.zeros(b, dtype=torch.float64, device=dev)
+    if vert_counts is None:
+        lap = move = zero
+    else:
+        per_mesh = b * vert_counts.to(torch.float64)
+        lap, move = (torch.where(vert_counts == 0, nan, torch.where(w == 0, zero, w / per_mesh))
+                     for w in (_weight_row(w_lap, b, dev), _weight_row(w_move, b, dev)))
+    w = _weight_row(w_edge, b, dev)
+    edge = torch.where(w == 0, zero, torch.where(face_counts == 0, nan, w / (3.0 * b * face_counts.to(torch.float64))))
+    return torch.stack((lap, move, edge)).to(torch.float32).contiguous()
+
+
+def regulariser_tables(face_mesh, vert_mesh, b, w_lap, w_move, w_edge):
+    """(face_mesh int32, vert_mesh int32 or None, coef [3,b]) for ops.RaggedStageRegularisers; vert_mesh None: the edge term
+    alone.  The table is cached per id and weight TENSOR OBJECTS (and their in-place versions), the mesh count and the python
+    weights: a training step rebuilds nothing."""
+    b = int(b)
+    weights = (w_lap, w_move, w_edge)
+    keys = [t for t in (face_mesh, vert_mesh) + weights if torch.is_tensor(t)]
+    extra = (b, vert_mesh is None) + tuple(None if torch.is_tensor(w) else float(w) for w in weights)
+    hit = _coef_cache.get(*keys, extra=extra)
+    if hit is None:
+        with torch.no_grad():
+            fm, face_counts = mesh_counts(face_mesh, b)
+            vm, vert_counts = (None, None) if vert_mesh is None else mesh_counts(vert_mesh, b)
+            hit = _coef_cache.put((fm, vm, regulariser_coefficients(vert_counts, face_counts, b, *weights)), *keys, extra=extra)
+    return hit
+
+
+__all__ = ["RaggedMeshBatch", "group_faces", "face_mesh", "csr_from_faces", "mesh_counts", "regulariser_coefficients",
+           "regulariser_tables"]

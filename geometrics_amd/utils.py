@@ -340,6 +340,41 @@ def stage_regularisers(prev, cur, adj_info, lap_weight=1.0, move_weight=0.0, edg
                                        edge_weight)
 
 
+def ragged_stage_regularisers(prev, cur, faces, face_mesh, vert_mesh, csr, b, lap_weight=1.0, move_weight=0.0, edge_weight=0.0):
+    """stage_regularisers for a RAGGED batch: b meshes with their own topology, as after an adaptive split, on ONE union mesh
+    (DESIGN.md section 4e).  prev, cur [Vt,3] fp32 (both differentiable): the union's vertices in any order; faces [Ft,3]
+    int64 into the union: the faces the edge term runs on (active_faces); face_mesh [Ft], vert_mesh [Vt]: the mesh of every
+    face / vertex, in any order -- an id outside [0, b) belongs to no mesh: no term, but its position is still read by its
+    neighbours' Laplacians; csr: the union's adjacency (ragged.csr_from_faces, RaggedMeshBatch.csr), None: the edge term
+    alone; each weight a python float or a [b] fp32 device tensor (not differentiable).  Value:
+        (1/b) sum_m [ w_edge[m] calc_edge(cur_m, faces_m) + w_lap[m] mean_{v in m} |lap(prev)_v - lap(cur)_v|^2
+                      + w_move[m] mean_{v in m} |prev_v - cur_v|^2 ]
+    -- the mean over m of stage_regularisers on mesh m alone, in ONE autograd node with one launch per direction and no host
+    read once the per-mesh counts and the coefficient table are cached (per id / weight tensor OBJECTS).  With [b] weights
+    three stages stacked into one union of 3b meshes are one call.  A mesh of [0, b) without a vertex, or without a face at an
+    edge weight other than 0, makes the value NaN (the reference's mean over nothing)."""
+    from . import ragged
+    from .layers import adjacency_csr
+    b = int(b)
+    if b < 1:
+        raise RuntimeError("a ragged batch holds at least one mesh (b = %d)" % b)
+    no_edge = not torch.is_tensor(edge_weight) and float(edge_weight) == 0.0
+    if csr is None:
+        fm, _, coef = ragged.regulariser_tables(face_mesh, None, b, 0.0, 0.0, edge_weight)
+        return ops.RaggedStageRegularisers.apply(None, cur, faces, fm, None, coef, None, None, None)
+    csr = adjacency_csr(csr)
+    if csr.nv != cur.shape[0]:
+        raise RuntimeError("the adjacency has %d rows, the union %d vertices" % (csr.nv, cur.shape[0]))
+    fm, vm, coef = ragged.regulariser_tables(face_mesh, vert_mesh, b, lap_weight, move_weight, edge_weight)
+    return ops.RaggedStageRegularisers.apply(prev, cur, None if no_edge else faces, fm, vm, coef, csr.rowptr, csr.col, csr.inv_deg)
+
+
+def ragged_calc_edge(verts, faces, face_mesh, b):
+    """batch_calc_edge for a ragged batch: the mean over the meshes of calc_edge(verts_m, faces_m) (reference utils.py:636-651)
+    on the union's verts [Vt,3]; arguments as ragged_stage_regularisers.  No adjacency is needed or touched."""
+    return ragged_stage_regularisers(None, verts, faces, face_mesh, None, None, b, 0.0, 0.0, 1.0)
+
+
 # ------------------------------------------------ image-feature pooling (SURVEY 8f, row 3) ----
 def batch_camera_info(param):
     """Camera rotation rows [B,3,3] and position [B,3] from (azimuth deg, elevation deg, distance)

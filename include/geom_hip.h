@@ -596,6 +596,29 @@ int geom_stage_regularisers_bwd_f32(int b, int nv, const float *prev, int prev_b
                                     const int64_t *faces, const int *rowptr, const int *col, const float *inv_deg,
                                     const int *vf_ptr, const int *vf_item, float c_lap, float c_move, float c_edge,
                                     const float *lapd, const float *gout, float *grad_prev, float *grad_cur, void *stream);
+/* The same regularisers for a RAGGED batch: b meshes with their own vertices, faces and adjacency on ONE union mesh of nv
+ * vertices and nf faces in any order (after utils.split_info the meshes interleave).  prev, cur, lapd, the gradients [nv,3];
+ * vert_mesh [nv], face_mesh [nf]: the mesh of every vertex / face; coef [3,b] (device) = the weights over the means' counts,
+ * w_lap[m] / (b V_m), w_move[m] / (b V_m), w_edge[m] / (3 b F_m): a vertex's or face's term is multiplied by ITS mesh's entry,
+ * an id outside [0, b) selects 0 (no term; the position is still read by the neighbours' Laplacians).  (rowptr [nv+1],
+ * col [nnz], inv_deg [nv]): the union's adjacency as geom_laplacian_f32 takes it; rowptr == NULL: the edge term alone (prev,
+ * vert_mesh, col, inv_deg, lapd, grad_prev unused).  faces == NULL or nf == 0: no edge term (vf_ptr, vf_item unused).
+ * forward: partial[geom_ragged_regularisers_blocks(nv, nf)], finish with geom_sum_f32; 0 * every entry of coef is added, so a
+ * non-finite entry (the caller's mark of a mesh without a vertex, or without a face at an edge weight != 0: the reference's
+ * mean over nothing) makes the sum NaN although no vertex reads it.  Every index followed (rowptr, col, face corners, vf_ptr,
+ * vf_item, mesh ids) is checked against what it points into; what fails the check is skipped.  No float atomics: two runs give
+ * the same bits.  A negative size or a missing pointer: GEOM_EINVAL; b or nf above INT32_MAX / 3: GEOM_ETOOBIG; b == 0 or
+ * nv == 0: nothing is done, 0. */
+int64_t geom_ragged_regularisers_blocks(int nv, int nf);
+int geom_ragged_regularisers_fwd_f32(int b, int nv, const float *prev, const float *cur, int nf, const int64_t *faces,
+                                     const int *vert_mesh, const int *face_mesh, const float *coef, int nnz,
+                                     const int *rowptr, const int *col, const float *inv_deg, float *lapd,
+                                     float *partial, void *stream);
+int geom_ragged_regularisers_bwd_f32(int b, int nv, const float *prev, const float *cur, int nf, const int64_t *faces,
+                                     const int *vert_mesh, const int *face_mesh, const float *coef, int nnz,
+                                     const int *rowptr, const int *col, const float *inv_deg, const int *vf_ptr,
+                                     const int *vf_item, const float *lapd, const float *gout, float *grad_prev,
+                                     float *grad_cur, void *stream);
 
 /* out = ((t[0] + t[1]) + t[2]) + ... element by element, count <= GEOM_SUM_MAX_TENSORS contiguous fp32 tensors of n elements (HOST
  * array of device pointers): the gradients that reach one tensor through several consumers, summed by ONE launch in a fixed order

@@ -1,0 +1,197 @@
+"""The ragged test batches of tests/test_ragged_regularisers_host.py / _gpu.py -- meshes with their OWN vertices, faces and
+adjacency on one union mesh whose vertices and faces interleave -- and the stage regularisers of such a batch written out per
+mesh with helpers.stage_regularisers_chain and scattered into union order: float64 values, masses and floors."""
+import numpy as np
+import torch
+
+from geometrics_amd import meshgen, utils
+from helpers import stage_regularisers_chain
+from oracle import ref_ops
+
+KEYS = ("lapd", "grad_prev", "grad_edge", "grad_cur")
+SCALAR_WEIGHTS = (300.0, 20.0, 300.0)
+
+
+class RegBatch:
+    """meshes: [(verts [V,3], all faces [F,3] -- the adjacency's --, the faces the edge term gets)], concatenated, then the
+    union's vertices permuted by a seeded permutation and the faces relabelled and shuffled.  Host torch tensors: prev, cur
+    [Vt,3] fp32, faces [Ft,3] int64 (the edge term's), adj_faces (all), face_mesh [Ft], vert_mesh [Vt] int64; per mesh m
+    vids[m] (its vertices' union ids in the mesh's own order), local_faces[m] (its edge faces in its own numbering, in union
+    face order) and adj[m] (its dense binary adjacency with self loops)."""
+
+    def __init__(self, meshes, seed):
+        rng = np.random.default_rng(seed)
+        self.b = len(meshes)
+        off = np.concatenate(([0], np.cumsum([len(v) for v, _, _ in meshes])))
+        vt = int(off[-1])
+        perm = rng.permutation(vt)                                         # concatenated index -> union index
+        base = np.empty((vt, 3), np.float32)
+        base[perm] = np.concatenate([v for v, _, _ in meshes]).astype(np.float32)
+        vert_mesh = np.empty(vt, np.int64)
+        vert_mesh[perm] = np.repeat(np.arange(self.b), np.diff(off))
+        edge_faces = np.concatenate([perm[f + off[m]] for m, (_, _, f) in enumerate(meshes)])
+        ids = np.repeat(np.arange(self.b), [len(f) for _, _, f in meshes])
+        shuffle = rng.permutation(len(edge_faces))
+        noise = lambda: (0.05 * rng.standard_normal((vt, 3))).astype(np.float32)
+        self.cur, self.prev = torch.from_numpy(base + noise()), torch.from_numpy(base + noise())
+        self.faces = torch.from_numpy(np.ascontiguousarray(edge_faces[shuffle], dtype=np.int64))
+        self.face_mesh = torch.from_numpy(np.ascontiguousarray(ids[shuffle]))
+        self.vert_mesh = torch.from_numpy(vert_mesh)
+        self.adj_faces = torch.from_numpy(np.ascontiguousarray(np.concatenate([perm[f + off[m]] for m, (_, f, _) in enumerate(meshes)]),
+                                                               dtype=np.int64))
+        self.vids, self.local_faces, self.adj = [], [], []
+        for m, (v, f_all, _) in enumerate(meshes):
+            vids = perm[off[m]:off[m + 1]]
+            local = np.full(vt, -1, np.int64)
+            local[vids] = np.arange(len(vids))
+            mine = local[self.faces[self.face_mesh == m].numpy()].reshape(-1, 3)
+            assert (mine >= 0).all()
+            self.vids.append(torch.from_numpy(np.ascontiguousarray(vids)))
+            self.local_faces.append(torch.from_numpy(mine))
+            adj = utils.calc_adj(torch.from_numpy(np.ascontiguousarray(f_all, dtype=np.int64)))
+            assert adj.shape[0] == len(v)
+            self.adj.append(adj)
+        self.vt, self.ft = vt, int(self.faces.shape[0])
+
+    def union_adj(self):
+        """The dense binary adjacency of the union (block-diagonal up to the permutation)."""
+        out = torch.zeros(self.vt, self.vt)
+        for vids, adj in zip(self.vids, self.adj):
+            out[vids.view(-1, 1), vids.view(1, -1)] = adj
+        return out
+
+
+def mixed():
+    """Closed meshes of very different sizes: icospheres 0 and 1, the 482-vertex uv sphere (two 33-entry rows), icosphere 2."""
+    meshes = [meshgen.icosphere(0), meshgen.icosphere(1), meshgen.uv_sphere(), meshgen.icosphere(2)]
+    rb = RegBatch([(v, f, f) for v, f in meshes], 301)
+    assert rb.vt == 12 + 42 + 482 + 162 and (8 * rb.vt) % 256 != 0
+    assert not (np.diff(rb.vert_mesh.numpy()) >= 0).all() and not (np.diff(rb.face_mesh.numpy()) >= 0).all()
+    return rb
+
+
+EDGE_CUT_REPEATS = 32
+
+
+def edge_cut():
+    """Two level-1 icospheres whose edge term gets a slice of the faces the adjacency comes from -- the first loses its last
+    three faces (corner lists shorter than the rows), the second every face of its vertex 0 and all but one face of its last
+    vertex (an empty corner list and a list of one) -- and an icosahedron that carries its face list many times over, so that
+    the faces outnumber the vertex lanes (Ft > 8 Vt; four copies cannot reach that: a closed mesh has F = 2 V - 4)."""
+    v1, f1 = meshgen.icosphere(1)
+    last = np.flatnonzero((f1 == f1.max()).any(1))
+    assert not (f1[last] == 0).any()
+    cut = np.delete(f1, last[1:], axis=0)
+    cut = cut[(cut != 0).all(1)]
+    v0, f0 = meshgen.icosphere(0)
+    rb = RegBatch([(v1, f1, f1[:-3]), (v1, f1, cut), (v0, f0, np.tile(f0, (EDGE_CUT_REPEATS, 1)))], 302)
+    corners = np.bincount(rb.local_faces[1].reshape(-1).numpy(), minlength=42)
+    assert corners[0] == 0 and corners[-1] == 1 and rb.ft > 8 * rb.vt and EDGE_CUT_REPEATS >= 4
+    return rb
+
+
+def single():
+    """One 482-vertex mesh: b = 1."""
+    v, f = meshgen.uv_sphere()
+    return RegBatch([(v, f, f)], 303)
+
+
+BATCHES = {"mixed": mixed, "edge-cut": edge_cut, "single": single}
+
+
+def mesh_weight(w, m):
+    return float(w[m]) if isinstance(w, (list, tuple, np.ndarray)) else float(w)
+
+
+def coefficients(rb, weights, m):
+    """(w_lap / (b V_m), w_move / (b V_m), w_edge / (3 b F_m)) of mesh m."""
+    nv, nf = len(rb.vids[m]), int(rb.local_faces[m].shape[0])
+    w_lap, w_move, w_edge = (mesh_weight(w, m) for w in weights)
+    return w_lap / (rb.b * nv), w_move / (rb.b * nv), (w_edge / (3.0 * rb.b * nf) if nf else 0.0)
+
+
+def union_chain(rb, weights, gout, dtype=torch.float64, absolute=False, ulps=False, edit=None):
+    """helpers.stage_regularisers_chain of every mesh alone (its own dense adjacency, its local faces, its coefficients),
+    the per-vertex outputs scattered into union order [Vt,3] and the values added.  edit(m, adj, faces, coef) -> the same
+    three, changed: how the host test loses a term."""
+    out = {k: torch.zeros(rb.vt, 3, dtype=dtype) for k in KEYS}
+    value = 0.0
+    for m in range(rb.b):
+        adj, faces, coef = rb.adj[m], rb.local_faces[m], coefficients(rb, weights, m)
+        if edit is not None:
+            adj, faces, coef = edit(m, adj, faces, coef)
+        vids = rb.vids[m]
+        one = stage_regularisers_chain(rb.prev[vids].to(dtype)[None], rb.cur[vids].to(dtype)[None], adj.to(dtype), faces, *coef, gout,
+                                       absolute=absolute, ulps=ulps)
+        for k in KEYS:
+            out[k][vids] = one[k][0]
+        if not absolute:
+            value = value + one["value"]
+    if not absolute:
+        out["value"] = value
+    return out
+
+
+def reference_value(rb, weights, union_counts=False):
+    """The value from the oracle's restatements per mesh under float64 autograd: (value, d / d cur, d / d prev) in union order.
+    union_counts: every mean divided by the UNION's counts (1 / Vt, 1 / (3 Ft)) in place of the mesh's own -- what a kernel
+    that ignores the mesh ids computes."""
+    cur = rb.cur.double().requires_grad_(True)
+    prev = rb.prev.double().requires_grad_(True)
+    total = 0.0
+    for m in range(rb.b):
+        vids, faces, a64 = rb.vids[m], rb.local_faces[m], rb.adj[m].double()
+        c, p = cur[vids][None], prev[vids][None]
+        w_lap, w_move, w_edge = (mesh_weight(w, m) for w in weights)
+        lap = ((ref_ops.lap_info(p, a64) - ref_ops.lap_info(c, a64)) ** 2).sum(-1)
+        move = ((p - c) ** 2).sum(-1)
+        if union_counts:
+            e = [((c[:, faces[:, i]] - c[:, faces[:, j]]) ** 2).sum() for i, j in ((1, 0), (2, 0), (1, 2))]
+            total = total + w_edge * (e[0] + e[1] + e[2]) / (3.0 * rb.ft) + (w_lap * lap.sum() + w_move * move.sum()) / rb.vt
+        else:
+            edge = w_edge * ref_ops.calc_edge(c, faces) if faces.shape[0] and w_edge != 0.0 else 0.0
+            total = total + (edge + w_lap * lap.mean() + w_move * move.mean()) / rb.b
+    return total, cur, prev
+
+
+def bounds(rb, weights, gout):
+    """(exact, mass, floor, rtol) for test_ops_parity_gpu.stage_regulariser_outputs_close in union order.  The chain is held to
+    the oracle's restatements (ref_ops.calc_edge / lap_info per mesh under autograd) at 1e-12, as stage_regulariser_bounds
+    does.  An element's rtol is (row_terms + 8) * 2^-24 with row_terms = the longest adjacency row or corner list of ITS mesh;
+    the returned scalar is the largest of them and the masses of the other meshes are scaled down to theirs."""
+    exact = union_chain(rb, weights, gout)
+    mass = union_chain(rb, weights, gout, absolute=True)
+    floor = union_chain(rb, weights, gout, absolute=True, ulps=True)
+    ref, cur, prev = reference_value(rb, weights)
+    (ref * gout).backward()
+    scale, ref = float(cur.grad.abs().max()), ref.detach()
+    assert abs(float(ref) - float(exact["value"])) <= 1e-12 * abs(float(ref))
+    assert float((cur.grad - exact["grad_cur"]).abs().max()) <= 1e-12 * scale
+    assert float((prev.grad - exact["grad_prev"]).abs().max()) <= 1e-12 * scale
+    rtols = []
+    for m in range(rb.b):
+        vids, a64 = rb.vids[m], rb.adj[m].double()
+        d = (rb.prev[vids].double() - rb.cur[vids].double())[None]
+        assert float((ref_ops.lap_info(d, a64)[0] - exact["lapd"][vids]).abs().max()) <= 1e-12
+        corners = np.bincount(rb.local_faces[m].reshape(-1).numpy(), minlength=len(vids))
+        rtols.append((max(int(rb.adj[m].sum(1).max()), int(corners.max())) + 8) * 2.0 ** -24)
+    rtol = max(rtols)
+    for m in range(rb.b):
+        for k in KEYS:
+            mass[k][rb.vids[m]] *= rtols[m] / rtol
+    return exact, mass, floor, rtol
+
+
+def counts_and_coefficients(ids_v, ids_f, b, weights):
+    """The numpy restatement of ragged.mesh_counts and ragged.regulariser_coefficients: (V_m [b], F_m [b], coef [3,b] fp32).
+    ids outside [0, b) are counted nowhere; a mesh without a vertex has NaN in the first two rows whatever its weights, a mesh
+    without a face NaN in the third unless its edge weight is 0."""
+    count = lambda ids: np.array([(np.asarray(ids) == m).sum() for m in range(b)], np.int64)
+    nv, nf = count(ids_v), count(ids_f)
+    w = [np.full(b, x, np.float64) if np.isscalar(x) else np.asarray(x, np.float64) for x in weights]
+    coef = np.zeros((3, b), np.float64)
+    for m in range(b):
+        for row in (0, 1):
+            coef[row, m] = np.nan if nv[m] == 0 else 0.0 if w[row][m] == 0 else w[row][m] / (b * nv[m])
+        coef[2, m] = 0.0 if w[2][m] == 0 else np.nan if nf[m] == 0 else w[2][m] / (3.0 * b * nf[m])
+    return nv, nf, coef.astype(np.float32)
