@@ -185,7 +185,7 @@ __device__ __forceinline__ void draw_samples_body(int chunk, int mesh, unsigned 
         const geom::V3 x = v0 - v1, y = v1 - v2;
         const float ca = x.y * y.z - x.z * y.y, cb = x.z * y.x - x.x * y.z, cc = x.x * y.y - x.y * y.x;
         const float area = real ? sqrtf((ca * ca + cb * cb) + cc * cc) / 2.f : 0.f;
-        run += area;
+        run += area > 0.f ? area : 0.f; // only what weighs: a NaN area adds nothing, exactly like a zero one (which adds 0 either way)
         weighs |= area > 0.f;
         cdf[f] = area > 0.f ? run : -run; // the sign bit marks an entry that weighs nothing (run >= 0; -0.f where it is 0)
     }

@@ -355,6 +355,15 @@ __device__ __forceinline__ void pool_bwd_verts_finish_body(const PoolArgs &a, co
     const float gZ = (gh * ((-pr.Y) * PL_FOCAL) + gw * (pr.X * PL_FOCAL)) / (d * d); // d(.)/dd * dd/dZ, dd/dZ = -1 twice
     const float *M = a.cam_mat + (size_t)mesh * 9;
     float *gv = grad_verts + ((size_t)mesh * a.nv + v) * 3;
+    // The clamp is a SELECT.  The test is on the SUMS, not on in_x / in_y: where nothing came through -- a vertex the clamp held
+    // on both axes of every map, a vertex whose projection is NaN (every comparison of in_x / in_y fails), or terms that cancel
+    // exactly -- sx == sy == 0 and the row is exactly zero, where the chain below gives a zero of either sign for a finite
+    // projection and 0 * NaN for a NaN one.  A non-finite sum is not zero and goes through the chain.  (The projection is
+    // requested in front of the sums on purpose: its loads travel with theirs; this path does not use it.)
+    if (sx == 0.f && sy == 0.f) {
+        gv[0] = gv[1] = gv[2] = 0.f;
+        return;
+    }
     gv[0] = PL_SCALE * ((gX * M[0] + gY * M[3]) + gZ * M[6]);
     gv[1] = PL_SCALE * ((gX * M[1] + gY * M[4]) + gZ * M[7]);
     gv[2] = PL_SCALE * ((gX * M[2] + gY * M[5]) + gZ * M[8]);

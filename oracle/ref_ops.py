@@ -252,7 +252,7 @@ def pool_vertex_gradient(blocks, verts, cam_mat, cam_pos, grad_out):
     """d (sum grad_out * pool_features) / d verts in FLOAT64 from the closed form, TERM BY TERM -- one term per (vertex, map,
     channel).  With f_c = A c11 G + H c12 A + G c21 B + B c22 H and floor / ceil piecewise constant,
         d f_c / d x = (-c11 G - H c12) + (G c21 + c22 H),     d f_c / d y = (-A c11 + c12 A) + (-c21 B + B c22)
-    per texel; a texel coordinate is xs * dim, the clamp to [0, dim - 1] passes the gradient only inside (bounds included), and
+    per texel; a texel coordinate is xs * dim, the clamp to [0, dim - 1] passes the gradient only inside (bounds included; a select), and
     J = d (xs, ys) / d vertex [B,V,2,3] chains through the perspective divide, the camera matrix and the 0.57.  Returns float64
     numpy arrays in the sense of helpers.fp64_surface_gradient / helpers.rows_close:
       grad  [B,V,3]  sum_c g_c * d f_c / d (x, y) * dim * [inside the clamp] * J;
@@ -281,11 +281,13 @@ def pool_vertex_gradient(blocks, verts, cam_mat, cam_pos, grad_out):
         A, B, G, H = (w.unsqueeze(-1) for w in (A, B, G, H))
         g = grad_out[..., col:col + c]
         col += c
-        inside = torch.stack(((rx >= 0) & (rx <= dim - 1), (ry >= 0) & (ry <= dim - 1)), dim=-1).double() * dim  # [B,V,2]
+        inside = torch.stack(((rx >= 0) & (rx <= dim - 1), (ry >= 0) & (ry <= dim - 1)), dim=-1)                # [B,V,2]
+        # (the clamp's backward is a SELECT, as torch's: a non-finite term behind a clamp that holds is 0, not 0 * NaN)
+        through = lambda t: torch.where(inside, t * dim, torch.zeros_like(t))
         terms = (torch.stack((-c11 * G, -H * c12, G * c21, c22 * H)), torch.stack((-A * c11, c12 * A, -c21 * B, B * c22)))
-        d = torch.stack([(g * t.sum(0)).sum(-1) for t in terms], dim=-1) * inside                              # [B,V,2]
-        d_abs = torch.stack([(g.abs() * t.abs().sum(0)).sum(-1) for t in terms], dim=-1) * inside
-        ulp = (eps * dim * (g.abs() * (c11.abs() + c12.abs() + c21.abs() + c22.abs())).sum(-1)).unsqueeze(-1) * inside
+        d = through(torch.stack([(g * t.sum(0)).sum(-1) for t in terms], dim=-1))                              # [B,V,2]
+        d_abs = through(torch.stack([(g.abs() * t.abs().sum(0)).sum(-1) for t in terms], dim=-1))
+        ulp = through((eps * dim * (g.abs() * (c11.abs() + c12.abs() + c21.abs() + c22.abs())).sum(-1)).unsqueeze(-1).expand(-1, -1, 2))
         grad += (d.unsqueeze(-1) * J).sum(2)
         mass += (d_abs.unsqueeze(-1) * J.abs()).sum(2)
         floor += (ulp.unsqueeze(-1) * J.abs()).sum(2)

@@ -55,11 +55,12 @@ def face_areas_f32(verts, faces):
     """fp32 areas [nf] with the kernel's expression: x = v0 - v1, y = v1 - v2, sqrt((ca^2 + cb^2) + cc^2) / 2 (no contraction)."""
     verts = np.asarray(verts, dtype=np.float32)
     v0, v1, v2 = (verts[faces[:, k]] for k in range(3))
-    x, y = v0 - v1, v1 - v2
-    ca = x[:, 1] * y[:, 2] - x[:, 2] * y[:, 1]
-    cb = x[:, 2] * y[:, 0] - x[:, 0] * y[:, 2]
-    cc = x[:, 0] * y[:, 1] - x[:, 1] * y[:, 0]
-    return (np.sqrt((ca * ca + cb * cb) + cc * cc) / np.float32(2)).astype(np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):            # (a non-finite vertex: Inf - Inf, 0 * Inf are what the kernel forms)
+        x, y = v0 - v1, v1 - v2
+        ca = x[:, 1] * y[:, 2] - x[:, 2] * y[:, 1]
+        cb = x[:, 2] * y[:, 0] - x[:, 0] * y[:, 2]
+        cc = x[:, 0] * y[:, 1] - x[:, 1] * y[:, 0]
+        return (np.sqrt((ca * ca + cb * cb) + cc * cc) / np.float32(2)).astype(np.float32)
 
 
 def scanned_sums_f32(weights):
@@ -93,17 +94,30 @@ def scanned_sums_f32(weights):
     return (local + offset[:, None]).astype(np.float32).reshape(-1)[:nf]
 
 
-def table(weights):
+def weighing(areas):
+    """What a face adds to the running sums: its area where `area > 0`, else 0 -- a NaN area weighs nothing, exactly like a
+    zero one.  No bit changes for finite areas: a zero area added 0 before."""
+    areas = np.asarray(areas, dtype=np.float32)
+    return np.where(areas > 0, areas, np.float32(0)).astype(np.float32)
+
+
+def table(weights, sums=None):
     """The fp32 table the search reads, [nf]: entry f = the largest scanned sum over the entries <= f that weigh something, 0 in
     front of the first.  max is exactly associative, so the order the kernel takes it in (per thread, wave scan, wave maxima)
-    does not matter."""
+    does not matter; it is the kernel's fmaxf, which passes over a NaN sum (an Inf area: Inf - Inf in its thread's offset).
+    `sums` (the tests' planted faults): another scan than scanned_sums_f32 of what weighs."""
     weights = np.asarray(weights, dtype=np.float32)
-    return np.maximum.accumulate(np.where(weights > 0, scanned_sums_f32(weights), np.float32(0))).astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        if sums is None:
+            sums = scanned_sums_f32(weighing(weights))
+        steps = np.concatenate(([np.float32(0)], np.where(weights > 0, sums, np.float32(0)))).astype(np.float32)
+        return np.fmax.accumulate(steps)[1:]                      # (the kernel's maximum starts from 0 in front of the first entry)
 
 
 def search_targets(tab, r0):
     """target = r0 * total in fp32: below the total for r0 <= 1 - 2^-24 whenever the total is positive."""
-    return (np.asarray(r0, dtype=np.float32) * tab[-1]).astype(np.float32)
+    with np.errstate(invalid="ignore"):                           # (0 * Inf: a NaN target ends on the last face, like an Inf one)
+        return (np.asarray(r0, dtype=np.float32) * tab[-1]).astype(np.float32)
 
 
 def search(tab, target):
@@ -151,7 +165,8 @@ def sampled_points(verts, faces, choices, su, v):
     x, y, z = (np.asarray(verts, dtype=np.float32)[faces[choices, k]] for k in range(3))
     one = np.float32(1)
     w0, w1, w2 = one - su, su * (one - v), su * v
-    return ((x * w0[:, None] + y * w1[:, None]) + z * w2[:, None]).astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        return ((x * w0[:, None] + y * w1[:, None]) + z * w2[:, None]).astype(np.float32)
 
 
 # ------------------------------------------------------------------------------------ the float64 reference and its bound ----

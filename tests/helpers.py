@@ -274,7 +274,7 @@ def fp64_surface_gradient(verts, faces, gt, choices, u, v, two_sided, scale=3000
     # rounding of the coordinates themselves (ulps of max|coordinate|), however small it is -- a gt point lying 1e-5 from the
     # surface has a term a thousand times smaller than that rounding.  `floor` = one coordinate ulp through every term that
     # meets in the element; the bound is rtol * mass + floor_ulps * floor.
-    ulp = float(np.finfo(np.float32).eps) * float(max(np.abs(verts).max(), np.abs(gt).max()))
+    ulp = float(np.finfo(np.float32).eps) * float(max(np.abs(finite_part(verts)).max(), np.abs(gt).max()))   # (finite_part: below)
     for (vid, c), coef in zip(groups, (scale / (b * num), scale / (b * n_gt))):
         index = vid.reshape(b, -1, 1).expand(-1, -1, 3)
         g = c.grad.reshape(b, -1, 3)
@@ -451,7 +451,7 @@ def vertex_bn64(x, gamma, beta, eps, relu, residual, scale, grad_out, grad_out2=
 
 
 # ---- the regularisers of one deformation stage term by term (csrc/regularizers.hip) ------------------------------------------------
-def stage_regularisers_chain(prev, cur, adj_orig, faces, c_lap, c_move, c_edge, gout, absolute=False, ulps=False):
+def stage_regularisers_chain(prev, cur, adj_orig, faces, c_lap, c_move, c_edge, gout, absolute=False, ulps=False, aggregate=None):
     """c_edge * sum_faces(|e1|^2 + |e2|^2 + |e3|^2)(cur) + c_lap * sum |lap(prev - cur)|^2 + c_move * sum |prev - cur|^2 and its
     gradients, written out term by term in the dtype of `cur` (torch, host): {"value", "lapd" = lap(prev - cur) [B,V,3],
     "grad_prev" = gout * d value / d (prev - cur), "grad_edge" = the edge term's share of grad_cur, "grad_cur" = grad_edge -
@@ -459,10 +459,13 @@ def stage_regularisers_chain(prev, cur, adj_orig, faces, c_lap, c_move, c_edge, 
     (self loops included), its transpose the same with 1 / deg[j] inside the sum (ref_ops.lap_info, utils.py:654-662).
     absolute: the same chain with every matrix entry, every coordinate difference and every term replaced by its absolute
     value -- the masses of rows_close (the value is not formed).  ulps (with absolute): every coordinate difference replaced
-    by one fp32 ulp of the two coordinates it is formed from, |a| + |b| -- the floor of rows_close."""
+    by one fp32 ulp of the two coordinates it is formed from, |a| + |b| -- the floor of rows_close.  aggregate: torch.matmul (the
+    default: the reference's dense product, where 0 * NaN poisons every row of the mesh) or ref_ops.sparse_aggregate (the sum
+    over a row's STORED entries, what the kernels walk: a non-finite row reaches its neighbours only)."""
     import torch
     one_ulp = float(np.finfo(np.float32).eps)
     A = adj_orig.to(cur.dtype)
+    matmul = aggregate or torch.matmul
     inv_deg = (1.0 / (A.sum(1) - 1)).view(-1, 1)
     pv = prev if prev.dim() == 3 else prev.unsqueeze(0)
 
@@ -473,8 +476,8 @@ def stage_regularisers_chain(prev, cur, adj_orig, faces, c_lap, c_move, c_edge, 
 
     sign = 1.0 if absolute else -1.0
     d = diff(pv, cur)
-    lapd = d + sign * (torch.matmul(A, d) + sign * d) * inv_deg
-    lt = lapd + sign * (torch.matmul(A, lapd * inv_deg) + sign * lapd * inv_deg)
+    lapd = d + sign * (matmul(A, d) + sign * d) * inv_deg
+    lt = lapd + sign * (matmul(A, lapd * inv_deg) + sign * lapd * inv_deg)
     grad_prev = (lt * (2.0 * c_lap) + d * (2.0 * c_move)) * abs(gout) if absolute else (lt * (2.0 * c_lap) + d * (2.0 * c_move)) * gout
     out = {"lapd": lapd, "grad_prev": grad_prev}
     grad_edge = torch.zeros_like(cur)

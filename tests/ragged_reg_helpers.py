@@ -110,10 +110,10 @@ def coefficients(rb, weights, m):
     return w_lap / (rb.b * nv), w_move / (rb.b * nv), (w_edge / (3.0 * rb.b * nf) if nf else 0.0)
 
 
-def union_chain(rb, weights, gout, dtype=torch.float64, absolute=False, ulps=False, edit=None):
+def union_chain(rb, weights, gout, dtype=torch.float64, absolute=False, ulps=False, edit=None, aggregate=None):
     """helpers.stage_regularisers_chain of every mesh alone (its own dense adjacency, its local faces, its coefficients),
     the per-vertex outputs scattered into union order [Vt,3] and the values added.  edit(m, adj, faces, coef) -> the same
-    three, changed: how the host test loses a term."""
+    three, changed: how the host test loses a term.  aggregate: see stage_regularisers_chain."""
     out = {k: torch.zeros(rb.vt, 3, dtype=dtype) for k in KEYS}
     value = 0.0
     for m in range(rb.b):
@@ -122,7 +122,7 @@ def union_chain(rb, weights, gout, dtype=torch.float64, absolute=False, ulps=Fal
             adj, faces, coef = edit(m, adj, faces, coef)
         vids = rb.vids[m]
         one = stage_regularisers_chain(rb.prev[vids].to(dtype)[None], rb.cur[vids].to(dtype)[None], adj.to(dtype), faces, *coef, gout,
-                                       absolute=absolute, ulps=ulps)
+                                       absolute=absolute, ulps=ulps, aggregate=aggregate)
         for k in KEYS:
             out[k][vids] = one[k][0]
         if not absolute:
