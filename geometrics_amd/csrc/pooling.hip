@@ -14,6 +14,9 @@
 //     matrix to grad_verts in closed form;
 //   * backward, maps: inverted into a gather -- a binning kernel builds texel -> (vertex, weight) lists, then
 //     a wave owns one texel x 64 channels and sums its list with coalesced reads (no float atomics).
+// A batch of meshes with their OWN vertex counts (after an adaptive split) is one union of vertices with a mesh id each: the
+// same bodies instantiated a second time (RG below), a workgroup owning 64 positions of the vertices grouped by mesh and every
+// lane bringing its own mesh -- geom_pool_features_ragged_*, DESIGN.md section 4f.
 // The reference's interpolation quirk is kept: weights are (ceil - x, x - floor), so a coordinate that
 // is exactly integral (incl. clamped ones) gets all-zero weights (utils.py:346-350, 372-379).
 #include "buffer_access.h"
@@ -36,15 +39,55 @@ struct PoolArgs {
     int chunks; // 64-channel chunks of all maps together
     int zc;     // chunk slices of a vertex-tile launch = min(chunks, PL_MAX_CHUNKS): a workgroup walks chunks z, z + zc, ...
     int ld;     // floats between two vertex rows of the pooled features / of their gradient (>= ctot: a column slice of a wider buffer)
+    // the RAGGED launches (a union of b meshes with their own vertex counts): nv = the union's vertices
+    // in any order, rows of verts / out / grad_out / grad_verts = union vertex ids; null in the batched launches
+    const int *vert_mesh; // [nv] the mesh of every vertex (anything outside [0, b): no mesh)
+    const int *vert_list; // [nv] the vertices grouped by mesh (ragged.group_vertices)
+    const int *vert_off;  // [b + 1] where each mesh's group starts in vert_list
 };
+
+// Every body below is stated once and instantiated twice: RG = false, the batched launches ([b, nv] rows, a workgroup's mesh is
+// uniform), RG = true, the ragged ones (the mesh is the LANE's).  What differs is where a row lives and which mesh it belongs to:
+template <bool RG>
+__device__ __forceinline__ size_t vert_row(const PoolArgs &a, int mesh, int v)
+{
+    if constexpr (RG) return (size_t)v;
+    else return (size_t)mesh * a.nv + v;
+}
+
+// position `pos` of the grouped list as a vertex of the union (held inside the union whatever the list holds)
+__device__ __forceinline__ int list_vertex(const PoolArgs &a, int pos) { return min(max(a.vert_list[pos], 0), a.nv - 1); }
+
+// a ragged vertex's mesh; ok = false: an id outside [0, b), the vertex of no mesh (mesh 0 then stands in for every address)
+struct MeshOf {
+    int mesh;
+    bool ok;
+};
+__device__ __forceinline__ MeshOf mesh_of(const PoolArgs &a, int v)
+{
+    const int m = a.vert_mesh[v];
+    const bool ok = (unsigned)m < (unsigned)a.b;
+    return MeshOf{ok ? m : 0, ok};
+}
+
+// where mesh `mesh`'s group starts in the grouped list and how many positions it holds (inside the list whatever vert_off holds)
+struct Group {
+    int p0, n;
+};
+__device__ __forceinline__ Group group_of(const int *vert_off, int nv, int mesh)
+{
+    const int p0 = min(max(vert_off[mesh], 0), nv);
+    return Group{p0, min(max(vert_off[mesh + 1] - p0, 0), nv - p0)};
+}
 
 struct Projection {
     float X, Y, Z, xs, ys;
 };
 
+template <bool RG>
 __device__ __forceinline__ Projection project(const PoolArgs &a, int mesh, int v)
 {
-    const float *p = a.verts + ((size_t)mesh * a.nv + v) * 3;
+    const float *p = a.verts + vert_row<RG>(a, mesh, v) * 3;
     const float *M = a.cam_mat + (size_t)mesh * 9, *cp = a.cam_pos + (size_t)mesh * 3;
     const float ax = p[0] * PL_SCALE - cp[0], ay = p[1] * PL_SCALE - cp[1], az = p[2] * PL_SCALE - cp[2];
     Projection r;
@@ -145,15 +188,19 @@ __device__ __forceinline__ Chunk chunk_of(const PoolArgs &a, int z)
 // a workgroup serves only 64 vertices per staged chunk, the copy's round trip and two barriers are not amortised.)
 constexpr int PL_INFLIGHT = 8;
 
-template <class Body>
+// RG: ONE buffer over the planes of all meshes, the lane's mesh is a plane offset inside it (the host bounds b * C * texels * 4
+// below 2^32)
+template <bool RG, class Body>
 __device__ __forceinline__ void chunk_quads(const PoolArgs &a, const Chunk &ck, int mesh, const Texel &t, int nch, Body body)
 {
     const int dim = a.dims[ck.level], C = a.channels[ck.level], texels = dim * dim;
-    const __amdgpu_buffer_rsrc_t r_blk = plane_rsrc(a.blocks[ck.level] + (size_t)mesh * C * texels, C, texels);
+    const __amdgpu_buffer_rsrc_t r_blk =
+        RG ? plane_rsrc(a.blocks[ck.level], a.b * C, texels) : plane_rsrc(a.blocks[ck.level] + (size_t)mesh * C * texels, C, texels);
+    const int ch0 = RG ? mesh * C + ck.cc : ck.cc; // the chunk's first plane inside the buffer
     const int wave = threadIdx.x >> 6;
     if (texels == 1) { // a 1 x 1 map: its one value four times (the weights are zero: the coordinate is integral)
         for (int c = wave; c < nch; c += PL_WAVES) {
-            const float x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r_blk, (unsigned)(ck.cc + c) * 4u, 0, 0));
+            const float x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r_blk, (unsigned)(ch0 + c) * 4u, 0, 0));
             body(c, Quad{x, x, x, x});
         }
         return;
@@ -165,7 +212,7 @@ __device__ __forceinline__ void chunk_quads(const PoolArgs &a, const Chunk &ck, 
 #ifdef PL_PROBE_NO_LOADS
             q[j] = Quad{t.A, t.B, t.G, (float)(c + j)};
 #else
-            q[j] = quad_of(r_blk, t, ck.cc + min(c + PL_WAVES * j, nch - 1), texels);
+            q[j] = quad_of(r_blk, t, ch0 + min(c + PL_WAVES * j, nch - 1), texels);
 #endif
         }
 #pragma unroll
@@ -179,37 +226,52 @@ __device__ __forceinline__ void chunk_quads(const PoolArgs &a, const Chunk &ck, 
 // vertex tiles of one (mesh, chunk) -- which all read the same 64 planes -- run on one XCD, one after the other, and the planes
 // come out of HBM once.  (As a 3-D grid with the tiles in x, the eight tiles of a mesh went to eight XCDs and every L2 fetched
 // every map: 29 us forward at the training shape, 24 with paired reads, against ~10 for the bytes.)
+//
+// RG: a work item is (tile of 64 consecutive POSITIONS of the grouped list, chunk slice), tile-fastest inside a chunk slice all the
+// same: the list is sorted by mesh, so consecutive tiles still read the same planes.  v0 is then the tile's first position, the
+// mesh is the lane's own (a tile may straddle one mesh boundary or several) and the grid knows no per-mesh tile count.
 struct PoolWork {
     int v0, mesh, z;
     bool live;
-    int lane, v; // the thread's lane and its vertex (lanes past the mesh's last vertex repeat it)
+    int lane, v; // the thread's lane and its vertex (lanes past the mesh's / the list's last vertex repeat it)
+    bool ok;     // RG: the vertex belongs to a mesh of the batch
 };
 
+template <bool RG>
 __device__ __forceinline__ PoolWork pool_work(const PoolArgs &a, int bid, int nblocks)
 {
     const int tiles = (a.nv + PL_VERTS - 1) / PL_VERTS;
     const int w = geom::xcd_run_item(bid, nblocks >> 3);
     PoolWork k;
-    k.live = w < tiles * a.b * a.zc;
+    k.live = w < tiles * (RG ? 1 : a.b) * a.zc;
     const int r = w / tiles;
-    k.v0 = (w - r * tiles) * PL_VERTS, k.mesh = r / a.zc, k.z = r - k.mesh * a.zc; // (chunks inside a mesh: every XCD gets maps of every size)
+    k.v0 = (w - r * tiles) * PL_VERTS;
     k.lane = threadIdx.x & (GEOM_WAVE - 1);
-    k.v = min(k.v0 + k.lane, a.nv - 1);
+    if constexpr (RG) {
+        k.z = r;
+        k.v = list_vertex(a, min(k.v0 + k.lane, a.nv - 1));
+        const MeshOf m = mesh_of(a, k.v);
+        k.mesh = m.mesh, k.ok = m.ok;
+    } else {
+        k.mesh = r / a.zc, k.z = r - k.mesh * a.zc; // (chunks inside a mesh: every XCD gets maps of every size)
+        k.v = min(k.v0 + k.lane, a.nv - 1);
+        k.ok = true;
+    }
     return k;
 }
 
-static inline unsigned pool_grid(const PoolArgs &a)
+static inline unsigned pool_grid(const PoolArgs &a, bool ragged = false)
 {
-    return geom::xcd_run_grid((size_t)((a.nv + PL_VERTS - 1) / PL_VERTS) * a.b * a.zc);
+    return geom::xcd_run_grid((size_t)((a.nv + PL_VERTS - 1) / PL_VERTS) * (ragged ? 1 : a.b) * a.zc);
 }
 
 // A live work item's walk over its chunks: the vertex is projected once; body(chunk, the vertex's texels in that chunk's map, the
 // chunk's channels) per chunk (one chunk per workgroup up to PL_MAX_CHUNKS chunks).  The body is the whole workgroup's: it may
 // hold barriers.
-template <class Body>
+template <bool RG, class Body>
 __device__ __forceinline__ void pool_chunks(const PoolArgs &a, const PoolWork &k, Body body)
 {
-    const Projection pr = project(a, k.mesh, k.v);
+    const Projection pr = project<RG>(a, k.mesh, k.v);
     for (int z = k.z; z < a.chunks; z += a.zc) {
         const Chunk ck = chunk_of(a, z);
         body(ck, texel(pr.xs, pr.ys, a.dims[ck.level]), min(GEOM_WAVE, a.channels[ck.level] - ck.cc));
@@ -231,10 +293,12 @@ struct PoolFronts {
     int work_blocks; // the pooling workgroups in front of the copying ones
 };
 
+// (RG: nothing in front; a vertex of no mesh gets a row of zeros -- a select, whatever its position or mesh 0's planes hold)
+template <bool RG>
 __global__ __launch_bounds__(PL_THREADS) void pool_fwd_kernel(PoolArgs a, float *out, PoolFronts fr)
 {
     __shared__ PoolTile tile;
-    if ((int)blockIdx.x >= fr.work_blocks) {
+    if (!RG && (int)blockIdx.x >= fr.work_blocks) {
         const int fb = (int)blockIdx.x - fr.work_blocks;
         const int f = (fr.count > 1 && fb >= fr.first_block[1]) ? 1 : 0;
         const int64_t total = (int64_t)a.b * a.nv * fr.width[f];
@@ -248,23 +312,27 @@ __global__ __launch_bounds__(PL_THREADS) void pool_fwd_kernel(PoolArgs a, float 
         }
         return;
     }
-    const PoolWork k = pool_work(a, blockIdx.x, fr.work_blocks);
+    const PoolWork k = pool_work<RG>(a, blockIdx.x, fr.work_blocks);
     if (!k.live) return;
     const int mesh = k.mesh, v0 = k.v0, lane = k.lane;
-    pool_chunks(a, k, [&](const Chunk &ck, const Texel &t, int nch) {
-        chunk_quads(a, ck, mesh, t, nch, [&](int c, const Quad &q) {
+    const bool ok = k.ok;
+    pool_chunks<RG>(a, k, [&](const Chunk &ck, const Texel &t, int nch) {
+        chunk_quads<RG>(a, ck, mesh, t, nch, [&](int c, const Quad &q) {
             const float s1 = (t.A * q.c11) * t.G, s2 = (t.H * q.c12) * t.A;
             const float s3 = (t.G * q.c21) * t.B, s4 = (t.B * q.c22) * t.H;
-            tile[lane][c] = ((s1 + s2) + s3) + s4;
+            const float s = ((s1 + s2) + s3) + s4;
+            tile[lane][c] = (RG && !ok) ? 0.f : s;
         });
         __syncthreads();
-        // a wave writes one vertex's 64 channels per round (lanes <-> channels: 256 contiguous bytes, no index arithmetic)
-        float *o = out + ((size_t)mesh * a.nv + v0) * a.ld + ck.off + ck.cc + lane;
+        // a wave writes one vertex's 64 channels per round (lanes <-> channels: 256 contiguous bytes, no index arithmetic; RG:
+        // the rows are scattered over the union, each still one such run)
+        float *o = out + (RG ? 0 : ((size_t)mesh * a.nv + v0) * a.ld) + ck.off + ck.cc + lane;
         for (int vv = threadIdx.x >> 6; vv < min(PL_VERTS, a.nv - v0); vv += PL_WAVES) {
+            const size_t row = RG ? (size_t)list_vertex(a, v0 + vv) : (size_t)vv;
 #ifdef PL_PROBE_NO_STORE
             if (tile[vv][lane] == 1.2345f)
 #endif
-            if (lane < nch) o[(size_t)vv * a.ld] = tile[vv][lane];
+            if (lane < nch) o[row * a.ld] = tile[vv][lane];
         }
         __syncthreads();
     });
@@ -276,17 +344,23 @@ struct BinSpace {
     int *offsets;        // per (mesh, level): dim*dim + 1 ints, level-major inside a mesh
     int *ent_v;          // per (mesh, level): 4*nv vertex ids
     float *ent_w;        // per (mesh, level): 4*nv weights
-    float *vert_partial; // [PL_MAX_CHUNKS][b][nv][2]
-    int b, nv, levels;
+    float *vert_partial; // [PL_MAX_CHUNKS][b][nv][2] (ragged: [PL_MAX_CHUNKS][nv][2], by union vertex)
+    int b, nv, levels;                   // (ragged: b = 1 for the sums, nv = the union's vertices)
+    const int *vert_off;                 // ragged: where each mesh's group starts (its lists start at four times that)
     int off_stride;                      // ints per mesh in `offsets`
     int level_off[GEOM_POOL_MAX_LEVELS]; // start of level l inside a mesh's offsets block
 
     // where the lists of the texels of (mesh, level l) start, [dim*dim + 1]
     __device__ __forceinline__ int *offs(int mesh, int l) const { return offsets + (size_t)mesh * off_stride + level_off[l]; }
     // the two entry lists of (mesh, level l), which those offsets index
-    __device__ __forceinline__ size_t list_at(int mesh, int l) const { return ((size_t)mesh * levels + l) * 4 * nv; }
-    __device__ __forceinline__ int *list_v(int mesh, int l) const { return ent_v + list_at(mesh, l); }
-    __device__ __forceinline__ float *list_w(int mesh, int l) const { return ent_w + list_at(mesh, l); }
+    // (ragged: level-major, 4 * nv entries per level; a mesh's lists start at 4 * its group's start and hold union vertex ids)
+    template <bool RG> __device__ __forceinline__ size_t list_at(int mesh, int l) const
+    {
+        if constexpr (RG) return ((size_t)l * nv + group_of(vert_off, nv, mesh).p0) * 4;
+        else return ((size_t)mesh * levels + l) * 4 * nv;
+    }
+    template <bool RG> __device__ __forceinline__ int *list_v(int mesh, int l) const { return ent_v + list_at<RG>(mesh, l); }
+    template <bool RG> __device__ __forceinline__ float *list_w(int mesh, int l) const { return ent_w + list_at<RG>(mesh, l); }
     // chunk slice z's share of d loss / d (xs, ys) of a vertex: two floats
     __device__ __forceinline__ float *sums(int z, int mesh, int v) const { return vert_partial + (((size_t)z * b + mesh) * nv + v) * 2; }
 };
@@ -300,20 +374,24 @@ struct VertsLds {
     float part[PL_WAVES][2][PL_VERTS];
 };
 
+template <bool RG>
 __device__ __forceinline__ void pool_bwd_verts_body(const PoolArgs &a, const BinSpace &ws, const float *grad_out, int bid, int nblocks,
                                                     VertsLds &L)
 {
-    const PoolWork k = pool_work(a, bid, nblocks);
+    const PoolWork k = pool_work<RG>(a, bid, nblocks);
     if (!k.live) return;
     const int mesh = k.mesh, v0 = k.v0, lane = k.lane, wave = threadIdx.x >> 6;
     float ax = 0.f, ay = 0.f; // this wave's share of d loss / d (xs, ys) of the lane's vertex over the workgroup's chunks
-    pool_chunks(a, k, [&](const Chunk &ck, const Texel &t, int nch) {
-        const float *gi = grad_out + ((size_t)mesh * a.nv + v0) * a.ld + ck.off + ck.cc + (lane < nch ? lane : 0);
-        for (int vv = wave; vv < PL_VERTS; vv += PL_WAVES) // (a wave reads one vertex's 64 channels per round)
-            L.tile[vv][lane] = (v0 + vv < a.nv && lane < nch) ? gi[(size_t)vv * a.ld] : 0.f;
+    pool_chunks<RG>(a, k, [&](const Chunk &ck, const Texel &t, int nch) {
+        const float *gi = grad_out + (RG ? 0 : ((size_t)mesh * a.nv + v0) * a.ld) + ck.off + ck.cc + (lane < nch ? lane : 0);
+        for (int vv = wave; vv < PL_VERTS; vv += PL_WAVES) { // (a wave reads one vertex's 64 channels per round)
+            float g = 0.f;
+            if (v0 + vv < a.nv && lane < nch) g = gi[(RG ? (size_t)list_vertex(a, v0 + vv) : (size_t)vv) * a.ld];
+            L.tile[vv][lane] = g;
+        }
         __syncthreads();
         float gx = 0.f, gy = 0.f;
-        chunk_quads(a, ck, mesh, t, nch, [&](int c, const Quad &q) { // (a padding lane's sums are dropped below)
+        chunk_quads<RG>(a, ck, mesh, t, nch, [&](int c, const Quad &q) { // (a padding lane's sums are dropped below)
             const float g = L.tile[lane][c];
             const float c11 = q.c11, c12 = q.c12, c21 = q.c21, c22 = q.c22;
             gx += g * (((-c11 * t.G) - (t.H * c12)) + ((t.G * c21) + (c22 * t.H)));
@@ -333,18 +411,30 @@ __device__ __forceinline__ void pool_bwd_verts_body(const PoolArgs &a, const Bin
             sx += L.part[w][0][lane];
             sy += L.part[w][1][lane];
         }
-        float *o = ws.sums(k.z, mesh, k.v);
+        if (RG && !k.ok) sx = sy = 0.f; // (the vertex of no mesh: a select, whatever mesh 0's planes gave)
+        float *o = ws.sums(k.z, RG ? 0 : mesh, k.v);
         o[0] = sx, o[1] = sy;
     }
 }
 
+// (RG: v is a vertex of the union and brings its own mesh; the vertex of no mesh gets a zero row without a look at the sums)
+template <bool RG>
 __device__ __forceinline__ void pool_bwd_verts_finish_body(const PoolArgs &a, const BinSpace &ws, float *grad_verts, int mesh, int v)
 {
     if (v >= a.nv) return;
-    const Projection pr = project(a, mesh, v);
+    if constexpr (RG) {
+        const MeshOf m = mesh_of(a, v);
+        if (!m.ok) {
+            float *gv = grad_verts + (size_t)v * 3;
+            gv[0] = gv[1] = gv[2] = 0.f;
+            return;
+        }
+        mesh = m.mesh;
+    }
+    const Projection pr = project<RG>(a, mesh, v);
     float sx = 0.f, sy = 0.f;
     for (int z = 0; z < a.zc; ++z) {
-        const float *p = ws.sums(z, mesh, v);
+        const float *p = ws.sums(z, RG ? 0 : mesh, v);
         sx += p[0], sy += p[1];
     }
     // xs = h/223, ys = w/223; h = (-Y)/(-Z)*F + 112, w = X/(-Z)*F + 112
@@ -354,7 +444,7 @@ __device__ __forceinline__ void pool_bwd_verts_finish_body(const PoolArgs &a, co
     const float gY = -gh * (PL_FOCAL / d);
     const float gZ = (gh * ((-pr.Y) * PL_FOCAL) + gw * (pr.X * PL_FOCAL)) / (d * d); // d(.)/dd * dd/dZ, dd/dZ = -1 twice
     const float *M = a.cam_mat + (size_t)mesh * 9;
-    float *gv = grad_verts + ((size_t)mesh * a.nv + v) * 3;
+    float *gv = grad_verts + vert_row<RG>(a, mesh, v) * 3;
     // The clamp is a SELECT.  The test is on the SUMS, not on in_x / in_y: where nothing came through -- a vertex the clamp held
     // on both axes of every map, a vertex whose projection is NaN (every comparison of in_x / in_y fails), or terms that cancel
     // exactly -- sx == sy == 0 and the row is exactly zero, where the chain below gives a zero of either sign for a finite
@@ -391,21 +481,25 @@ struct BinLds {
 };
 
 // f(vertex, texel, weight) for every corner of a mesh's vertices in one map: a pass of the binning workgroup over its vertices
-template <class F>
+// (RG: the positions of the mesh's group in the grouped list; v is then a vertex of the union)
+template <bool RG, class F>
 __device__ __forceinline__ void mesh_corners(const PoolArgs &a, int mesh, int dim, F f)
 {
-    for (int v = threadIdx.x; v < a.nv; v += BIN_THREADS) {
-        const Projection pr = project(a, mesh, v);
+    const Group g = RG ? group_of(a.vert_off, a.nv, mesh) : Group{0, a.nv};
+    for (int i = threadIdx.x; i < g.n; i += BIN_THREADS) {
+        const int v = RG ? list_vertex(a, g.p0 + i) : i;
+        const Projection pr = project<RG>(a, mesh, v);
         corners(texel(pr.xs, pr.ys, dim), [&](int i, float w) { f(v, i, w); });
     }
 }
 
+template <bool RG>
 __device__ __forceinline__ void pool_bin_body(const PoolArgs &a, const BinSpace &ws, int l, int mesh, BinLds &L)
 {
     const int dim = a.dims[l], texels = dim * dim;
     for (int i = threadIdx.x; i <= texels; i += BIN_THREADS) L.counts[i] = 0;
     __syncthreads();
-    mesh_corners(a, mesh, dim, [&](int, int i, float) { atomicAdd(&L.counts[i], 1); });
+    mesh_corners<RG>(a, mesh, dim, [&](int, int i, float) { atomicAdd(&L.counts[i], 1); });
     __syncthreads();
     // exclusive scan of counts[0..texels): thread owns a contiguous run, wave shuffle scan, wave totals
     const int per = (texels + BIN_THREADS - 1) / BIN_THREADS;
@@ -436,9 +530,9 @@ __device__ __forceinline__ void pool_bin_body(const PoolArgs &a, const BinSpace 
         for (int w = 0; w < BIN_THREADS / GEOM_WAVE; ++w) total += L.wave_sum[w];
         offs[texels] = total;
     }
-    int *ev = ws.list_v(mesh, l);
-    float *ew = ws.list_w(mesh, l);
-    mesh_corners(a, mesh, dim, [&](int v, int i, float w) {
+    int *ev = ws.list_v<RG>(mesh, l);
+    float *ew = ws.list_w<RG>(mesh, l);
+    mesh_corners<RG>(a, mesh, dim, [&](int v, int i, float w) {
         const int p = atomicAdd(&L.counts[i], 1);
         ev[p] = v, ew[p] = w;
     });
@@ -451,6 +545,7 @@ __device__ __forceinline__ void pool_bin_body(const PoolArgs &a, const BinSpace 
 //   2. pool_bwd_grads_kernel: the map gradient from the lists BESIDE the vertex gradient from the per-chunk sums.
 static_assert(BIN_THREADS == PL_THREADS, "the two roles of a launch share its workgroup size");
 
+template <bool RG>
 __global__ __launch_bounds__(PL_THREADS) void pool_bwd_lists_kernel(PoolArgs a, BinSpace ws, const float *grad_out, int bin_blocks,
                                                                     int verts_blocks)
 {
@@ -459,8 +554,8 @@ __global__ __launch_bounds__(PL_THREADS) void pool_bwd_lists_kernel(PoolArgs a, 
         VertsLds verts;
         __device__ Lds() {}
     } lds;
-    if ((int)blockIdx.x < bin_blocks) pool_bin_body(a, ws, (int)blockIdx.x % a.levels, (int)blockIdx.x / a.levels, lds.bin);
-    else pool_bwd_verts_body(a, ws, grad_out, (int)blockIdx.x - bin_blocks, verts_blocks, lds.verts);
+    if ((int)blockIdx.x < bin_blocks) pool_bin_body<RG>(a, ws, (int)blockIdx.x % a.levels, (int)blockIdx.x / a.levels, lds.bin);
+    else pool_bwd_verts_body<RG>(a, ws, grad_out, (int)blockIdx.x - bin_blocks, verts_blocks, lds.verts);
 }
 
 // What this kernel has to avoid is not traffic but INSTRUCTIONS and TAILS.  The lists are short and skewed: at the training
@@ -528,7 +623,7 @@ template <int VEC> __device__ __forceinline__ PgRow<VEC> pg_load(__amdgpu_buffer
     return o;
 }
 
-template <int VEC>
+template <int VEC, bool RG>
 __device__ __forceinline__ void pg_run(const PoolArgs &a, const BinSpace &ws, const GatherPlan &p, const float *grad_out, int l,
                                        int run, int part, float *tile)
 {
@@ -540,8 +635,8 @@ __device__ __forceinline__ void pg_run(const PoolArgs &a, const BinSpace &ws, co
     const int log_t = p.log_t[l], T = 1 << log_t;
     const int tx0 = run << log_t, nt = min(T, texels - tx0); // texels of this run
     const int *offs = ws.offs(mesh, l) + tx0;
-    const int *ev = ws.list_v(mesh, l);
-    const float *ew = ws.list_w(mesh, l);
+    const int *ev = ws.list_v<RG>(mesh, l);
+    const float *ew = ws.list_w<RG>(mesh, l);
     // where the list of texel `lane` ends (lanes past the run: the end of the run's range)
     const int ends = offs[min(lane + 1, nt)];
     const int E0 = offs[0], E1 = __builtin_amdgcn_readlane(ends, GEOM_WAVE - 1);
@@ -550,7 +645,9 @@ __device__ __forceinline__ void pg_run(const PoolArgs &a, const BinSpace &ws, co
     const int n = E1 - E0;
     const int ea = E0 + ((n * wave) >> 2), ez = E0 + ((n * (wave + 1)) >> 2); // this wave's quarter of the entries
     const int c = part * W + lane * VEC;                                          // the lane's first channel
-    const __amdgpu_buffer_rsrc_t r_g = geom::rsrc(grad_out + (size_t)mesh * a.nv * a.ld, (int64_t)((((size_t)a.nv - 1) * a.ld + a.ctot) * 4));
+    // (RG: the lists hold union vertex ids, the gradient rows are the union's)
+    const __amdgpu_buffer_rsrc_t r_g =
+        geom::rsrc(grad_out + (RG ? 0 : (size_t)mesh * a.nv * a.ld), (int64_t)((((size_t)a.nv - 1) * a.ld + a.ctot) * 4));
     const unsigned col_off = c < C ? (unsigned)(p.col0[l] + c) * 4u : geom::OOB; // (out of range: the load returns zeros)
     // the texel the quarter starts in = the number of lists that end at or before its first entry
     const int t_first = __builtin_popcountll(__ballot(lane < nt && ends <= ea));
@@ -625,12 +722,15 @@ __device__ __forceinline__ void pg_run(const PoolArgs &a, const BinSpace &ws, co
 
 // finish_z >= 0: the workgroups of that grid.z slice chain the vertex tiles' sums to grad_verts (256 vertices each); gather_tasks
 // = the runs of all maps (0: no map wants a gradient)
+// (RG: the finish role's slice is one row of workgroups over the union, blockIdx.y = 0)
+template <bool RG>
 __global__ __launch_bounds__(PL_THREADS) void pool_bwd_grads_kernel(PoolArgs a, BinSpace ws, GatherPlan p, const float *grad_out,
                                                                     int gather_tasks, int finish_z, float *grad_verts)
 {
     __shared__ __attribute__((aligned(16))) float tile[PG_TILE + GEOM_WAVE];
     if ((int)blockIdx.z == finish_z) {
-        pool_bwd_verts_finish_body(a, ws, grad_verts, blockIdx.y, (int)blockIdx.x * PL_THREADS + (int)threadIdx.x);
+        if (RG && blockIdx.y) return;
+        pool_bwd_verts_finish_body<RG>(a, ws, grad_verts, blockIdx.y, (int)blockIdx.x * PL_THREADS + (int)threadIdx.x);
         return;
     }
     // an XCD gets CONSECUTIVE runs (gridDim.x is a multiple of 8) -- the 2 x 2 texels a vertex touches then meet in one L2 (its
@@ -647,9 +747,9 @@ __global__ __launch_bounds__(PL_THREADS) void pool_bwd_grads_kernel(PoolArgs a, 
 #endif
     const int run = task - p.first_task[l];
     switch (p.vec[l]) {
-    case 4: pg_run<4>(a, ws, p, grad_out, l, run, part, tile); break;
-    case 2: pg_run<2>(a, ws, p, grad_out, l, run, part, tile); break;
-    default: pg_run<1>(a, ws, p, grad_out, l, run, part, tile); break;
+    case 4: pg_run<4, RG>(a, ws, p, grad_out, l, run, part, tile); break;
+    case 2: pg_run<2, RG>(a, ws, p, grad_out, l, run, part, tile); break;
+    default: pg_run<1, RG>(a, ws, p, grad_out, l, run, part, tile); break;
     }
 }
 
@@ -662,6 +762,7 @@ int fill_args(PoolArgs &a, bool &todo, int b, int nv, const float *verts, const 
     if (b < 0 || nv < 0 || levels < 0 || levels > GEOM_POOL_MAX_LEVELS) return GEOM_EINVAL;
     if (!verts || !cam_mat || !cam_pos || (levels > 0 && (!blocks || !channels || !dims))) return GEOM_EINVAL;
     if (b > 65535 || (size_t)((nv + PL_VERTS - 1) / PL_VERTS) * b * PL_MAX_CHUNKS > (size_t)INT_MAX - 8) return GEOM_ETOOBIG;
+    a.vert_mesh = a.vert_list = a.vert_off = nullptr;
     a.verts = verts, a.cam_mat = cam_mat, a.cam_pos = cam_pos, a.levels = levels, a.b = b, a.nv = nv, a.ctot = 0, a.chunks = 0;
     for (int l = 0; l < levels; ++l) {
         if (!blocks[l] || channels[l] <= 0 || dims[l] <= 0) return GEOM_EINVAL;
@@ -706,7 +807,7 @@ extern "C" int geom_pool_features_fwd_fronts_f32(int b, int nv, const float *ver
         extra += (int)blocks;
     }
     fr.first_block[n_fronts] = extra, fr.count = n_fronts, fr.dst = buf;
-    hipLaunchKernelGGL(pool_fwd_kernel, dim3(fr.work_blocks + extra), dim3(PL_THREADS), 0, static_cast<hipStream_t>(stream), a, out, fr);
+    hipLaunchKernelGGL(pool_fwd_kernel<false>, dim3(fr.work_blocks + extra), dim3(PL_THREADS), 0, static_cast<hipStream_t>(stream), a, out, fr);
     return geom::launch_status();
 }
 
@@ -727,24 +828,26 @@ struct BinLayout {
     size_t bytes;
 };
 
-static BinLayout pool_ws_layout(int b, int nv, int levels, const int *dims, void *base)
+// ragged: nv = the union's vertices; the offsets as above, 4 * nv ids and weights per LEVEL (a mesh's lists at four times its
+// group's start), the per-chunk sums by union vertex
+static BinLayout pool_ws_layout(int b, int nv, int levels, const int *dims, void *base, bool ragged = false)
 {
     BinLayout lay{};
     BinSpace &ws = lay.ws;
-    ws.b = b, ws.nv = nv, ws.levels = levels;
+    ws.b = ragged ? 1 : b, ws.nv = nv, ws.levels = levels;
     for (int l = 0; l < levels; ++l) {
         ws.level_off[l] = ws.off_stride;
         ws.off_stride += dims[l] * dims[l] + 1;
     }
     const size_t off_bytes = ((size_t)b * ws.off_stride * sizeof(int) + 15) / 16 * 16;
-    const size_t ent = (size_t)b * levels * 4 * nv;
+    const size_t ent = (size_t)(ragged ? 1 : b) * levels * 4 * nv;
     const size_t lists = (off_bytes + ent * (sizeof(int) + sizeof(float)) + 15) / 16 * 16;
     const uintptr_t p = reinterpret_cast<uintptr_t>(base);
     ws.offsets = reinterpret_cast<int *>(p);
     ws.ent_v = reinterpret_cast<int *>(p + off_bytes);
     ws.ent_w = reinterpret_cast<float *>(p + off_bytes + ent * sizeof(int));
     ws.vert_partial = reinterpret_cast<float *>(p + lists);
-    lay.bytes = lists + (size_t)PL_MAX_CHUNKS * b * nv * 2 * sizeof(float);
+    lay.bytes = lists + (size_t)PL_MAX_CHUNKS * ws.b * nv * 2 * sizeof(float);
     return lay;
 }
 
@@ -752,6 +855,39 @@ extern "C" size_t geom_pool_features_bwd_workspace_bytes(int b, int nv, int leve
 {
     if (b <= 0 || nv <= 0 || levels <= 0 || levels > GEOM_POOL_MAX_LEVELS || !dims) return 0;
     return pool_ws_layout(b, nv, levels, dims, nullptr).bytes;
+}
+
+// the two launches of a backward pass from checked arguments (a.vert_* set: the ragged instantiations)
+template <bool RG>
+static int launch_bwd(PoolArgs &a, const int *dims, const float *grad_out, float *const *grad_blocks, float *grad_verts, void *workspace,
+                      size_t workspace_bytes, void *stream)
+{
+    const int b = a.b, nv = a.nv, levels = a.levels;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    bool any_map = false;
+    for (int l = 0; l < levels; ++l) {
+        a.grad_blocks[l] = grad_blocks ? grad_blocks[l] : nullptr;
+        any_map = any_map || a.grad_blocks[l];
+        if (dims[l] * dims[l] > BIN_MAX_TEXELS) return GEOM_EUNSUPPORTED;
+    }
+    if (!any_map && !grad_verts) return 0;
+    BinLayout lay = pool_ws_layout(b, nv, levels, dims, workspace, RG);
+    lay.ws.vert_off = a.vert_off;
+    if (!workspace || workspace_bytes < lay.bytes || ((uintptr_t)workspace & 15)) return GEOM_EINVAL;
+    GatherPlan plan;
+    gather_plan(a, plan);
+    if (plan.max_parts > 65534 || (size_t)nv * a.ld * 4 > (size_t)INT_MAX) return GEOM_ETOOBIG;
+    const int bin_blocks = any_map ? levels * b : 0;
+    const unsigned verts_blocks = grad_verts ? pool_grid(a, RG) : 0;
+    hipLaunchKernelGGL(pool_bwd_lists_kernel<RG>, dim3(bin_blocks + verts_blocks), dim3(PL_THREADS), 0, s, a, lay.ws, grad_out, bin_blocks,
+                       (int)verts_blocks);
+    const int gather_tasks = any_map ? plan.first_task[levels] : 0;
+    const int parts = any_map ? plan.max_parts : 0;
+    const int finish_blocks = grad_verts ? (nv + PL_THREADS - 1) / PL_THREADS : 0; // the finish role's slice needs this many in x
+    const unsigned gx = geom::xcd_run_grid(gather_tasks > finish_blocks ? gather_tasks : finish_blocks);
+    hipLaunchKernelGGL(pool_bwd_grads_kernel<RG>, dim3(gx, b, parts + (grad_verts ? 1 : 0)), dim3(PL_THREADS), 0, s, a, lay.ws, plan,
+                       grad_out, gather_tasks, grad_verts ? parts : -1, grad_verts);
+    return geom::launch_status();
 }
 
 // grad_ld: floats between two vertex rows of `grad_out` (0 = the pooled width; larger: the gradient is read in place out of a
@@ -765,30 +901,59 @@ extern "C" int geom_pool_features_bwd_ld_f32(int b, int nv, const float *verts, 
     bool todo;
     if (int rc = fill_args(a, todo, b, nv, verts, cam_mat, cam_pos, levels, blocks, channels, dims, grad_ld); rc || !todo) return rc;
     if (!grad_out) return GEOM_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    bool any_map = false;
+    return launch_bwd<false>(a, dims, grad_out, grad_blocks, grad_verts, workspace, workspace_bytes, stream);
+}
+
+// ---- the ragged launches: a union of b meshes with their own vertex counts (geom_hip.h) -------------------
+// The limits of the ragged entry points, looked at BEFORE any pointer: maps up to 64 x 64 (forward too: one rule for the pair), and
+// the planes of ALL meshes of a map inside one buffer resource, whose offsets are 32 bits.
+static int ragged_limits(int b, int vt, int levels, const int *channels, const int *dims)
+{
+    if (b < 0 || vt < 0 || levels < 0 || levels > GEOM_POOL_MAX_LEVELS || (levels > 0 && (!channels || !dims))) return GEOM_EINVAL;
     for (int l = 0; l < levels; ++l) {
-        a.grad_blocks[l] = grad_blocks ? grad_blocks[l] : nullptr;
-        any_map = any_map || a.grad_blocks[l];
-        if (dims[l] * dims[l] > BIN_MAX_TEXELS) return GEOM_EUNSUPPORTED;
+        if (channels[l] <= 0 || dims[l] <= 0) return GEOM_EINVAL;
+        if (dims[l] > 64) return GEOM_EUNSUPPORTED;
     }
-    if (!any_map && !grad_verts) return 0;
-    const BinLayout lay = pool_ws_layout(b, nv, levels, dims, workspace);
-    if (!workspace || workspace_bytes < lay.bytes || ((uintptr_t)workspace & 15)) return GEOM_EINVAL;
-    GatherPlan plan;
-    gather_plan(a, plan);
-    if (plan.max_parts > 65534 || (size_t)nv * a.ld * 4 > (size_t)INT_MAX) return GEOM_ETOOBIG;
-    const int bin_blocks = any_map ? levels * b : 0;
-    const unsigned verts_blocks = grad_verts ? pool_grid(a) : 0;
-    hipLaunchKernelGGL(pool_bwd_lists_kernel, dim3(bin_blocks + verts_blocks), dim3(PL_THREADS), 0, s, a, lay.ws, grad_out, bin_blocks,
-                       (int)verts_blocks);
-    const int gather_tasks = any_map ? plan.first_task[levels] : 0;
-    const int parts = any_map ? plan.max_parts : 0;
-    const int finish_blocks = grad_verts ? (nv + PL_THREADS - 1) / PL_THREADS : 0; // the finish role's slice needs this many in x
-    const unsigned gx = geom::xcd_run_grid(gather_tasks > finish_blocks ? gather_tasks : finish_blocks);
-    hipLaunchKernelGGL(pool_bwd_grads_kernel, dim3(gx, b, parts + (grad_verts ? 1 : 0)), dim3(PL_THREADS), 0, s, a, lay.ws, plan, grad_out,
-                       gather_tasks, grad_verts ? parts : -1, grad_verts);
+    for (int l = 0; l < levels; ++l)
+        if ((uint64_t)b * (uint64_t)channels[l] * (uint64_t)(dims[l] * dims[l]) * 4 >= (1ull << 32)) return GEOM_ETOOBIG;
+    return 0;
+}
+
+extern "C" int geom_pool_features_ragged_fwd_f32(int b, int vt, const float *verts, const int *vert_mesh, const int *vert_list,
+                                                 const float *cam_mat, const float *cam_pos, int levels, const float *const *blocks,
+                                                 const int *channels, const int *dims, float *out, int64_t out_ld, void *stream)
+{
+    if (int rc = ragged_limits(b, vt, levels, channels, dims)) return rc;
+    PoolArgs a;
+    bool todo;
+    if (int rc = fill_args(a, todo, b, vt, verts, cam_mat, cam_pos, levels, blocks, channels, dims, out_ld); rc || !todo) return rc;
+    if (!out || !vert_mesh || !vert_list) return GEOM_EINVAL;
+    a.vert_mesh = vert_mesh, a.vert_list = vert_list;
+    PoolFronts fr{};
+    fr.work_blocks = (int)pool_grid(a, true);
+    hipLaunchKernelGGL(pool_fwd_kernel<true>, dim3(fr.work_blocks), dim3(PL_THREADS), 0, static_cast<hipStream_t>(stream), a, out, fr);
     return geom::launch_status();
+}
+
+extern "C" size_t geom_pool_features_ragged_bwd_workspace_bytes(int b, int vt, int levels, const int *dims)
+{
+    if (b <= 0 || vt <= 0 || levels <= 0 || levels > GEOM_POOL_MAX_LEVELS || !dims) return 0;
+    return pool_ws_layout(b, vt, levels, dims, nullptr, true).bytes;
+}
+
+extern "C" int geom_pool_features_ragged_bwd_f32(int b, int vt, const float *verts, const int *vert_mesh, const int *vert_list,
+                                                 const int *vert_off, const float *cam_mat, const float *cam_pos, int levels,
+                                                 const float *const *blocks, const int *channels, const int *dims,
+                                                 const float *grad_out, int64_t grad_ld, float *const *grad_blocks, float *grad_verts,
+                                                 void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (int rc = ragged_limits(b, vt, levels, channels, dims)) return rc;
+    PoolArgs a;
+    bool todo;
+    if (int rc = fill_args(a, todo, b, vt, verts, cam_mat, cam_pos, levels, blocks, channels, dims, grad_ld); rc || !todo) return rc;
+    if (!grad_out || !vert_mesh || !vert_list || !vert_off) return GEOM_EINVAL;
+    a.vert_mesh = vert_mesh, a.vert_list = vert_list, a.vert_off = vert_off;
+    return launch_bwd<true>(a, dims, grad_out, grad_blocks, grad_verts, workspace, workspace_bytes, stream);
 }
 
 // ---- camera from (azimuth deg, elevation deg, distance): reference utils.py:286-313 -----------------------------------------

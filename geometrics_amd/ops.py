@@ -787,6 +787,65 @@ class PoolFeatures(torch.autograd.Function):
         return (gverts, None, None, None) + tuple(gblks)
 
 
+class RaggedPoolFeatures(torch.autograd.Function):
+    """PoolFeatures for a RAGGED batch on one union mesh (DESIGN.md section 4f): verts [Vt,3], the union's vertices in any order;
+    vert_mesh [Vt] int32, the mesh of every vertex (ragged.mesh_counts' clamped ids); (vert_list, vert_off) from
+    ragged.group_vertices; cam_mat [B,3,3], cam_pos [B,3]; blocks [B,C,d,d].  Row v of the [Vt, sum C] result is PoolFeatures' row
+    for vertex v as a vertex of mesh vert_mesh[v] alone; a vertex of no mesh gets zeros and no gradient.  The batched kernels'
+    bodies with the mesh per lane: one launch forward, two backward, no host read."""
+
+    @staticmethod
+    def forward(ctx, verts, vert_mesh, vert_list, vert_off, cam_mat, cam_pos, *blocks):
+        v = _f32(verts, "verts_union", 2, 3)
+        cam_mat = _f32(cam_mat, "cam_mat", 3, 3)
+        cam_pos = _f32(cam_pos, "cam_pos", 2, 3)
+        vert_mesh = _lib.require(vert_mesh, "vert_mesh", torch.int32, 1)
+        vert_list = _lib.require(vert_list, "vert_list", torch.int32, 1)
+        vert_off = _lib.require(vert_off, "vert_off", torch.int32, 1)
+        blks = [_f32(b, "block", 4) for b in blocks]
+        vt, b = v.shape[0], cam_pos.shape[0]
+        if vt == 0 or b == 0 or not blks:
+            raise RuntimeError("the union must hold a vertex, the batch a mesh and a feature map (got %d vertices, %d meshes, %d maps)"
+                               % (vt, b, len(blks)))
+        if vert_mesh.shape[0] != vt or vert_list.shape[0] != vt or vert_off.shape[0] != b + 1 or cam_mat.shape[0] != b:
+            raise RuntimeError("vert_mesh and vert_list must hold one entry per vertex of the union (%d), vert_off and the cameras one "
+                               "per mesh (%d)" % (vt, b))
+        for blk in blks:
+            if blk.shape[0] != b or blk.shape[2] != blk.shape[3]:
+                raise RuntimeError("feature maps must be [B, C, dim, dim] with the cameras' batch size")
+        n = len(blks)
+        chans = (ctypes.c_int * n)(*[t.shape[1] for t in blks])
+        dims = (ctypes.c_int * n)(*[t.shape[2] for t in blks])
+        out = torch.empty(vt, sum(t.shape[1] for t in blks), dtype=torch.float32, device=v.device)
+        _lib.call("geom_pool_features_ragged_fwd_f32", b, vt, v, vert_mesh, vert_list, cam_mat, cam_pos, n, blks, chans, dims, out, 0)
+        ctx.save_for_backward(v, vert_mesh, vert_list, vert_off, cam_mat, cam_pos, *blks)
+        ctx.meta = (chans, dims, n)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        v, vert_mesh, vert_list, vert_off, cam_mat, cam_pos = ctx.saved_tensors[:6]
+        blks = ctx.saved_tensors[6:]
+        chans, dims, n = ctx.meta
+        vt, b = v.shape[0], cam_pos.shape[0]
+        ctot = grad_out.shape[1]
+        # the gradient in place when it is a column slice of a wider row-major buffer (the block's input gradient), else contiguous
+        if grad_out.stride(1) == 1 and grad_out.stride(0) >= ctot and grad_out.is_cuda and grad_out.dtype == torch.float32:
+            g, g_ld = grad_out, grad_out.stride(0)
+        else:
+            g, g_ld = grad_out.contiguous(), ctot
+        need_blocks = [ctx.needs_input_grad[6 + i] for i in range(n)]
+        gblks = [torch.empty_like(t) if need else None for t, need in zip(blks, need_blocks)]
+        gverts = torch.empty_like(v) if ctx.needs_input_grad[0] else None
+        ws, ws_bytes = None, 0
+        if any(need_blocks) or gverts is not None:
+            ws_bytes = _lib.lib().geom_pool_features_ragged_bwd_workspace_bytes(b, vt, n, dims)
+            ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=v.device)
+        _lib.call("geom_pool_features_ragged_bwd_f32", b, vt, v, vert_mesh, vert_list, vert_off, cam_mat, cam_pos, n, blks, chans, dims,
+                  g, g_ld if g_ld != ctot else 0, gblks, gverts, ws, ws_bytes)
+        return (gverts, None, None, None, None, None) + tuple(gblks)
+
+
 class SegmentMax(torch.autograd.Function):
     """Column maximum per mesh of a ragged batch: x [sum(V), C], offsets [B+1] int64 (device) -> [B, C]
     (GCNMax's `torch.max(i_s, dim=0)[0]`, reference layers.py:78, for every mesh at once).  The gradient goes to
@@ -1090,7 +1149,7 @@ class VertexHead(torch.autograd.Function):
 
 
 __all__ = ["face_areas", "device_sum", "SampleFaces", "GatherSqDistSum", "PointToTriangleSum", "SurfaceLoss",
-           "Laplacian", "EdgeSqLenSum", "PoolFeatures", "VertexHead", "SegmentMax", "manual_seed", "set_rng_state",
+           "Laplacian", "EdgeSqLenSum", "PoolFeatures", "RaggedPoolFeatures", "VertexHead", "SegmentMax", "manual_seed", "set_rng_state",
            "draw_samples", "GtIndex", "ScanPrep", "RaggedSurfaceLoss", "draw_samples_ragged", "tri_distance_ragged",
            "chamfer_nn", "tri_distance_indexed"]
 

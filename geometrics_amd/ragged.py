@@ -92,6 +92,17 @@ class RaggedMeshBatch:
 # concatenated as above, faces [Ft,3] indexing the union -- plus the id of its mesh per face.  The two searches of the surface
 # loss must not cross from one mesh into another, so they walk the faces GROUPED by mesh.
 _group_cache = ByTensor()    # (faces, face_mesh) or (face_mesh,), extra: the mesh count -> (face_list, face_off)
+_vertex_group_cache = ByTensor()    # (vert_mesh,), extra: the mesh count -> (vert_list, vert_off)
+
+
+def _group_by_mesh(ids, b):
+    """(list int32 [n], off int32 [b+1]) of int64 mesh ids: the items grouped by id, in their own order inside a group (a stable
+    argsort), and the first position whose id is >= m for m = 0 ... b (a binary search over the sorted ids, which unlike
+    bincount needs no host read).  The one statement of the construction group_faces and group_vertices hand out."""
+    order = torch.argsort(ids, stable=True)
+    bounds = torch.arange(int(b) + 1, dtype=torch.int64, device=ids.device)
+    off = torch.searchsorted(ids[order].contiguous(), bounds)      # first position whose id is >= m
+    return order.to(torch.int32).contiguous(), off.to(torch.int32).contiguous()
 
 
 def group_faces(face_mesh, b, faces=None):
@@ -106,11 +117,23 @@ def group_faces(face_mesh, b, faces=None):
     hit = _group_cache.get(*keys, extra=int(b))
     if hit is None:
         with torch.no_grad():
-            ids = face_mesh.detach().to(torch.int64)
-            order = torch.argsort(ids, stable=True)
-            bounds = torch.arange(int(b) + 1, dtype=torch.int64, device=ids.device)
-            face_off = torch.searchsorted(ids[order].contiguous(), bounds)      # first position whose id is >= m
-            hit = _group_cache.put((order.to(torch.int32).contiguous(), face_off.to(torch.int32).contiguous()), *keys, extra=int(b))
+            hit = _group_cache.put(_group_by_mesh(face_mesh.detach().to(torch.int64), b), *keys, extra=int(b))
+    return hit
+
+
+def group_vertices(vert_mesh, b):
+    """(vert_list int32 [Vt], vert_off int32 [b+1]) on vert_mesh's device, for the ragged pooling: the
+    union's vertices grouped by mesh -- a stable argsort of the ids clamped to [-1, b], so a vertex of no mesh stands in front of
+    mesh 0's group or behind the last one's -- and where each group starts: position k of mesh m is the vertex
+    vert_list[vert_off[m] + k], and [vert_off[0], vert_off[b]) are the vertices that belong to a mesh.  The construction of
+    group_faces: no host read, cached per vert_mesh TENSOR OBJECT and in-place version."""
+    if vert_mesh.dim() != 1 or vert_mesh.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("vert_mesh must be a one-dimensional int32 or int64 tensor (got %s %s)" % (vert_mesh.dtype, tuple(vert_mesh.shape)))
+    hit = _vertex_group_cache.get(vert_mesh, extra=int(b))
+    if hit is None:
+        with torch.no_grad():
+            ids = vert_mesh.detach().to(torch.int64).clamp(-1, int(b))
+            hit = _vertex_group_cache.put(_group_by_mesh(ids, b), vert_mesh, extra=int(b))
     return hit
 
 
@@ -214,5 +237,5 @@ def regulariser_tables(face_mesh, vert_mesh, b, w_lap, w_move, w_edge):
     return hit
 
 
-__all__ = ["RaggedMeshBatch", "group_faces", "face_mesh", "csr_from_faces", "mesh_counts", "regulariser_coefficients",
+__all__ = ["RaggedMeshBatch", "group_faces", "group_vertices", "face_mesh", "csr_from_faces", "mesh_counts", "regulariser_coefficients",
            "regulariser_tables"]

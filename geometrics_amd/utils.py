@@ -420,6 +420,44 @@ def batched_pooling(blocks, verts_pos, img_info, headroom=0, fronts=None):
     return ops.PoolFeatures.apply(verts_pos, cam_mat.detach(), cam_pos.detach(), room, *blocks)
 
 
+def ragged_pooling(blocks, verts_union, vert_mesh, img_info):
+    """batched_pooling for a RAGGED batch: B meshes with their own vertex counts, as after an adaptive split, on ONE union mesh
+    (DESIGN.md section 4f).  blocks: the encoder maps, each [B,C,d,d] fp32; verts_union [Vt,3] fp32: the union's vertices in any
+    order (after split_info on a union the new vertices stand at the end: the meshes interleave); vert_mesh [Vt] int32 or int64:
+    the mesh of every vertex; img_info: [B,3] camera parameters or batch_camera_info's (cam_mat, cam_pos), as batched_pooling
+    takes it.  Returns [Vt, sum C]: row v is batched_pooling's row for that vertex as a vertex of mesh vert_mesh[v] alone (maps
+    blocks[l][m:m+1], camera m), bit for bit.  Differentiable in the maps and in the positions, ONE autograd node
+    (ops.RaggedPoolFeatures), one launch forward and two backward, no host read once the grouping of the vertices is cached
+    (per vert_mesh tensor OBJECT: ragged.group_vertices).  A vertex whose id is outside [0, B) belongs to no mesh: its row and
+    its position gradient are zeros and no map gradient hears of it; a mesh without vertices gets an all-zero map gradient."""
+    from . import ragged
+    blocks = list(blocks)
+    if not blocks:
+        raise RuntimeError("ragged_pooling needs at least one feature map")
+    for blk in blocks:
+        if not torch.is_tensor(blk) or blk.dtype != torch.float32 or blk.dim() != 4 or blk.shape[2] != blk.shape[3]:
+            raise RuntimeError("feature maps must be fp32 [B, C, dim, dim] tensors with square planes (got %s)"
+                               % ("%s %s" % (blk.dtype, tuple(blk.shape)) if torch.is_tensor(blk) else type(blk).__name__))
+    if not torch.is_tensor(verts_union) or verts_union.dtype != torch.float32 or verts_union.dim() != 2 or verts_union.shape[1] != 3:
+        raise RuntimeError("verts_union must be an fp32 [Vt,3] tensor, the union's vertices (got %s)"
+                           % ("%s %s" % (verts_union.dtype, tuple(verts_union.shape)) if torch.is_tensor(verts_union)
+                              else type(verts_union).__name__))
+    if not torch.is_tensor(vert_mesh) or vert_mesh.dtype not in (torch.int32, torch.int64) or vert_mesh.dim() != 1:
+        raise RuntimeError("vert_mesh must be a one-dimensional int32 or int64 tensor of mesh ids")
+    if vert_mesh.shape[0] != verts_union.shape[0]:
+        raise RuntimeError("vert_mesh holds %d ids, the union %d vertices" % (vert_mesh.shape[0], verts_union.shape[0]))
+    cam_mat, cam_pos = img_info if isinstance(img_info, (tuple, list)) else batch_camera_info(img_info)
+    b = int(cam_pos.shape[0])
+    if cam_mat.dtype != torch.float32 or cam_pos.dtype != torch.float32:
+        raise RuntimeError("the cameras must be fp32 (got %s, %s)" % (cam_mat.dtype, cam_pos.dtype))
+    for blk in blocks:
+        if blk.shape[0] != b:
+            raise RuntimeError("a feature map holds %d images, the cameras %d" % (blk.shape[0], b))
+    ids, _ = ragged.mesh_counts(vert_mesh, b)
+    vert_list, vert_off = ragged.group_vertices(vert_mesh, b)
+    return ops.RaggedPoolFeatures.apply(verts_union, ids, vert_list, vert_off, cam_mat.detach(), cam_pos.detach(), *blocks)
+
+
 def fan_out(x, n):
     """n handles on the same tensor, one per consumer (not a reference name): results are those of using `x` n times; the n
     gradients are summed by one launch in a fixed order instead of n - 1 accumulation launches."""

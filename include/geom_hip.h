@@ -810,6 +810,34 @@ int geom_pool_features_bwd_ld_f32(int b, int nv, const float *verts, const float
                                   const float *const *blocks, const int *channels, const int *dims, const float *grad_out,
                                   int64_t grad_ld, float *const *grad_blocks, float *grad_verts, void *workspace,
                                   size_t workspace_bytes, void *stream);
+/* RAGGED pooling: a batch of b meshes with their OWN vertex counts as one union (after an adaptive split).
+ * verts [vt,3]: the union's vertices in any order; vert_mesh [vt]: the mesh of every vertex -- an id outside [0, b) belongs to no
+ * mesh: its feature row and its position gradient are zeros and it contributes to no map gradient; vert_list [vt], vert_off
+ * [b+1] (device, int32): the vertices grouped by mesh -- a stable argsort of the ids clamped to [-1, b] -- and where each mesh's
+ * group starts in it (vert_off[m] = the first position whose id is >= m); cam_mat [b,3,3], cam_pos [b,3], blocks [b, C, dim, dim]
+ * as above.  Row v of out [vt, sum channels] (pitch out_ld) is what geom_pool_features_fwd_ld_f32 gives vertex v as a vertex of
+ * mesh vert_mesh[v] alone, bit for bit; grad_out (pitch grad_ld) and grad_verts [vt,3] are addressed by union vertex as well.
+ * grad_blocks [b, C, dim, dim] and grad_verts are fully overwritten (a mesh without vertices: zeros).  The same kernels' bodies
+ * instantiated for per-lane meshes: one launch forward, two backward, no float atomics, no host read.
+ * Codes, looked at before any pointer: dims[l] > 64 (forward as well): GEOM_EUNSUPPORTED; b * channels[l] * dims[l]^2 * 4 >=
+ * 2^32 for a map (all meshes' planes of a map are ONE buffer with 32-bit offsets): GEOM_ETOOBIG; otherwise as above.
+ * Values inside vert_list / vert_off outside their ranges are clamped into them (wrong rows, no access out of range).
+ * The workspace (geom_pool_features_ragged_bwd_workspace_bytes(b, vt, levels, dims) bytes, 16-byte aligned), in this order:
+ *   offsets: int32, per mesh one block of sum over l of (dims[l]*dims[l] + 1) ints, level-major, as in the batched layout; all
+ *            meshes' together padded to a multiple of 16 bytes;
+ *   vertex ids: int32, 4*vt per LEVEL, level after level: the lists of (mesh m, level l) are the 4 * (vert_off[m+1] - vert_off[m])
+ *            entries that start at entry 4 * vert_off[m] of level l's part, texel after texel; they hold UNION vertex ids;
+ *   weights:    float, 4*vt per level, entry for entry beside the vertex ids; the two together padded to 16 bytes;
+ *   per-chunk sums of d loss / d (xs, ys): float [32][vt][2], by union vertex (chunk slices beyond the launch's are unused). */
+int geom_pool_features_ragged_fwd_f32(int b, int vt, const float *verts, const int *vert_mesh, const int *vert_list,
+                                      const float *cam_mat, const float *cam_pos, int levels, const float *const *blocks,
+                                      const int *channels, const int *dims, float *out, int64_t out_ld, void *stream);
+size_t geom_pool_features_ragged_bwd_workspace_bytes(int b, int vt, int levels, const int *dims);
+int geom_pool_features_ragged_bwd_f32(int b, int vt, const float *verts, const int *vert_mesh, const int *vert_list,
+                                      const int *vert_off, const float *cam_mat, const float *cam_pos, int levels,
+                                      const float *const *blocks, const int *channels, const int *dims, const float *grad_out,
+                                      int64_t grad_ld, float *const *grad_blocks, float *grad_verts, void *workspace,
+                                      size_t workspace_bytes, void *stream);
 
 /* ---- culled Chamfer scan inside the surface step (optional; NULL everywhere = the brute-force tiles) ------------------
  * The culled scan (geom_chamfer_nn_culled_f32) needs both clouds listed in a spatially coherent order, as an INDEX
