@@ -14,6 +14,10 @@
 //                                 matrix in both orientations, and the non-zeros of the two dense matrices;
 //   geom_split_vertices_fwd_f32   old rows copied, new rows (x/3 + y/3) + z/3 with true divisions;
 //   geom_split_vertices_bwd_f32   the transpose as a gather over the vertex -> split-face incidence table: no atomics.
+// For the union of a ragged batch (one mesh to the launches above, except the two that are one workgroup by design):
+//   geom_face_select_ragged_f32   two launches of a workgroup per mesh: each mesh's own count, fallback and place in the list;
+//   geom_face_split_index_ragged  the same index tables and the new mesh ids from four launches over chunks of 256 items and
+//                                 one zero-fill, no workgroup waiting on another.
 //
 // Every index a kernel follows is checked against the size of what it points into before it is used: a table that names a row
 // outside leaves a NaN (floats) or the raw value (indices) instead of reading or writing out of bounds.
@@ -445,7 +449,315 @@ __global__ __launch_bounds__(SPLIT_THREADS) void split_vertices_bwd_kernel(Split
     }
 }
 
+// ============================================================================== a ragged batch: the union of B meshes ====
+// The union is ONE mesh to the curvature, the tables and the vertices (an edge is still shared by exactly two faces); what a
+// union needs of its own is a selection per mesh and index tables made by as many workgroups as it has chunks.  No workgroup
+// waits on another inside a launch: every dependence between chunks is a launch boundary.
+constexpr int SPLIT_CHUNK = SPLIT_THREADS; // items of a chunk of the running sums: one per thread
+
+// sum of `mine` over the threads of the workgroup (a fixed tree over 256 values)
+__device__ __forceinline__ int64_t block_sum(int64_t mine, int64_t *lds)
+{
+    __syncthreads(); // lds may still be read from a previous call
+    lds[threadIdx.x] = mine;
+    __syncthreads();
+    for (int w = SPLIT_THREADS / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) lds[threadIdx.x] += lds[threadIdx.x + w];
+        __syncthreads();
+    }
+    return lds[0];
+}
+
+// ------------------------------------------------------------------------------------------ selection per mesh ----
+struct RaggedSelectArgs {
+    int nfa, b;
+    const float *curv;
+    float angle;
+    const int *row_list, *row_off; // the active rows grouped by mesh, ascending inside a mesh; where each group starts
+    int64_t *stats;                // [b,4]: a mesh's count and the positions of its three largest curvatures
+    int64_t *selected, *counts, *totals;
+};
+
+// the part [lo, hi) of mesh m's group that this thread walks: contiguous and in thread order, so the compaction is ordered
+__device__ __forceinline__ void group_part(const RaggedSelectArgs &a, int m, int &lo, int &hi)
+{
+    int g0 = a.row_off[m], g1 = a.row_off[m + 1];
+    g0 = g0 < 0 ? 0 : (g0 > a.nfa ? a.nfa : g0);
+    g1 = g1 < g0 ? g0 : (g1 > a.nfa ? a.nfa : g1);
+    const int64_t n = g1 - g0, per = (n + SPLIT_THREADS - 1) / SPLIT_THREADS, at = (int64_t)threadIdx.x * per;
+    lo = g0 + (int)(at < n ? at : n);
+    hi = (int64_t)lo + per < g1 ? lo + (int)per : g1;
+}
+
+__device__ __forceinline__ bool above(float c, float angle) { return (c * 180.0f) / 3.14159265358979323846f > angle; }
+
+// what a mesh contributes to the list: its flagged rows, or below three of them as many of its three largest as exist
+__device__ __forceinline__ int64_t mesh_entries(const int64_t *stats)
+{
+    if (stats[0] >= 3) return stats[0];
+    return (stats[1] >= 0 ? 1 : 0) + (stats[2] >= 0 ? 1 : 0) + (stats[3] >= 0 ? 1 : 0);
+}
+
+// The list top3_insert keeps, in named registers (an array indexed by a loop variable lives in scratch memory): the same rule.
+struct Top3 {
+    float v0 = 0.f, v1 = 0.f, v2 = 0.f;
+    int i0 = -1, i1 = -1, i2 = -1;
+    __device__ __forceinline__ void insert(float v, int i)
+    {
+        if (v != v || i < 0) return; // a degenerate face is never selected
+        if (ahead(v, i, v0, i0)) v2 = v1, i2 = i1, v1 = v0, i1 = i0, v0 = v, i0 = i;
+        else if (ahead(v, i, v1, i1)) v2 = v1, i2 = i1, v1 = v, i1 = i;
+        else if (ahead(v, i, v2, i2)) v2 = v, i2 = i;
+    }
+};
+
+// Launch 1, a workgroup per mesh: stats[m] = {count, top3} of face_select_kernel taken over the mesh's rows alone.
+__global__ __launch_bounds__(SPLIT_THREADS) void face_select_ragged_stats_kernel(RaggedSelectArgs a)
+{
+    __shared__ int64_t lds64[SPLIT_THREADS];
+    __shared__ float cand_v[3 * SPLIT_THREADS];
+    __shared__ int cand_i[3 * SPLIT_THREADS];
+    const int t = threadIdx.x, m = blockIdx.x;
+    int lo, hi;
+    group_part(a, m, lo, hi);
+    Top3 mine;
+    int n = 0;
+    for (int g = lo; g < hi; ++g) {
+        const int i = a.row_list[g];
+        if (i < 0 || i >= a.nfa) continue;
+        const float c = a.curv[i];
+        n += above(c, a.angle) ? 1 : 0;
+        mine.insert(c, i);
+    }
+    const int64_t run = block_sum(n, lds64);
+    // the lists merge pairwise: ahead() is a strict order on (curvature, position) pairs, so the three of a union that are
+    // ahead of all others do not depend on the order of the merges
+    const auto keep = [&] {
+        cand_v[3 * t] = mine.v0, cand_v[3 * t + 1] = mine.v1, cand_v[3 * t + 2] = mine.v2;
+        cand_i[3 * t] = mine.i0, cand_i[3 * t + 1] = mine.i1, cand_i[3 * t + 2] = mine.i2;
+    };
+    keep();
+    __syncthreads();
+    for (int w = SPLIT_THREADS / 2; w > 0; w >>= 1) {
+        if (t < w) { // reads the list of thread t + w, which no thread writes in this step
+            for (int k = 0; k < 3; ++k) mine.insert(cand_v[3 * (t + w) + k], cand_i[3 * (t + w) + k]);
+            keep();
+        }
+        __syncthreads();
+    }
+    if (t != 0) return;
+    int64_t *out = a.stats + 4 * (int64_t)m;
+    out[0] = run, out[1] = mine.i0, out[2] = mine.i1, out[3] = mine.i2;
+}
+
+// Launch 2, a workgroup per mesh: it adds up what the meshes in front of it contribute and writes its own entries there.
+// counts[m] = its entries; the last workgroup writes totals = {S, the meshes with fewer than three faces that have a curvature}.
+__global__ __launch_bounds__(SPLIT_THREADS) void face_select_ragged_write_kernel(RaggedSelectArgs a)
+{
+    __shared__ int lds[SPLIT_THREADS];
+    __shared__ int64_t lds64[SPLIT_THREADS];
+    const int t = threadIdx.x, m = blockIdx.x;
+    const int64_t cap = (int64_t)a.nfa + 3 * (int64_t)a.b;
+    int64_t part = 0;
+    for (int q = t; q < m; q += SPLIT_THREADS) part += mesh_entries(a.stats + 4 * (int64_t)q);
+    const int64_t base = block_sum(part, lds64);
+    const int64_t *own = a.stats + 4 * (int64_t)m;
+    const int64_t mine = mesh_entries(own);
+    if (own[0] >= 3) {
+        int lo, hi;
+        group_part(a, m, lo, hi);
+        int n = 0;
+        for (int g = lo; g < hi; ++g) {
+            const int i = a.row_list[g];
+            if (i >= 0 && i < a.nfa) n += above(a.curv[i], a.angle) ? 1 : 0;
+        }
+        int64_t at = base + block_offset(n, lds);
+        for (int g = lo; g < hi; ++g) {
+            const int i = a.row_list[g];
+            if (i < 0 || i >= a.nfa || !above(a.curv[i], a.angle)) continue;
+            if (at >= 0 && at < cap) a.selected[at] = i;
+            ++at;
+        }
+    } else if (t == 0) {
+        int64_t at = base;
+        for (int k = 1; k <= 3; ++k)
+            if (own[k] >= 0 && at < cap) a.selected[at++] = own[k];
+    }
+    if (t == 0) a.counts[m] = mine;
+    if (m != a.b - 1) return;
+    int64_t bad = 0;
+    for (int q = t; q < a.b; q += SPLIT_THREADS) {
+        const int64_t *s = a.stats + 4 * (int64_t)q;
+        bad += (s[0] < 3 && s[3] < 0) ? 1 : 0;
+    }
+    bad = block_sum(bad, lds64);
+    if (t == 0) a.totals[0] = base + mine, a.totals[1] = bad;
+}
+
+// ------------------------------------------------------------------------------- index tables over many chunks ----
+struct RaggedIndexArgs {
+    int nv, nft, nfa, s;
+    const int64_t *faces, *face_list, *splitting, *vert_mesh, *face_mesh;
+    int64_t *corners, *split_pos, *unsplit_rank, *face_s, *inc_ptr, *inc_item, *vert_mesh_new, *face_mesh_new;
+    // the workspace (ragged_index_layout): zero at the first launch up to `slot`
+    int64_t *count;   // [nv]   how many split faces have the vertex as a corner
+    int64_t *vtot;    // [chunks of nv]   the same per chunk of vertices
+    int64_t *rtot;    // [chunks of nfa]  split rows per chunk of rows
+    int64_t *sp_tmp;  // [nfa]  k + 1 at splitting[k]
+    int64_t *fs_tmp;  // [nft]  k + 1 at the face of splitting[k]
+    int64_t *slot;    // [3s]   the order in which corner j of split face k arrived at its vertex
+};
+
+inline int64_t chunks_of(int64_t n) { return (n + SPLIT_CHUNK - 1) / SPLIT_CHUNK; }
+inline int64_t ragged_index_zeroed_words(int nv, int nft, int nfa) { return nv + chunks_of(nv) + chunks_of(nfa) + (int64_t)nfa + nft; }
+
+__device__ __forceinline__ int64_t count_up(int64_t *p) { return (int64_t)atomicAdd(reinterpret_cast<unsigned long long *>(p), 1ull); }
+
+// Launch 1, a thread per split face: the scatter, the corners, the new ids, and integer counts -- per vertex (the value the
+// atomic returns is kept: it is the corner's place in the vertex's row until the sort), per chunk of vertices, per chunk of rows.
+__global__ __launch_bounds__(SPLIT_THREADS) void face_split_scatter_ragged_kernel(RaggedIndexArgs a)
+{
+    const int64_t k = (int64_t)blockIdx.x * SPLIT_THREADS + threadIdx.x;
+    if (k >= a.s) return;
+    const int64_t p = a.splitting[k];
+    int64_t c[3] = {-1, -1, -1}, mesh = -1;
+    if (p >= 0 && p < a.nfa) {
+        a.sp_tmp[p] = k + 1;
+        count_up(a.rtot + p / SPLIT_CHUNK);
+        const int64_t own = a.face_list[9 * p + 2];
+        if (own >= 0 && own < a.nft) {
+            a.fs_tmp[own] = k + 1;
+            for (int j = 0; j < 3; ++j) c[j] = a.faces[3 * own + j];
+            mesh = a.face_mesh[own];
+        }
+    }
+    for (int j = 0; j < 3; ++j) {
+        int64_t place = -1;
+        if (c[j] >= 0 && c[j] < a.nv) {
+            place = count_up(a.count + c[j]);
+            count_up(a.vtot + c[j] / SPLIT_CHUNK);
+        }
+        a.corners[3 * k + j] = c[j];
+        a.slot[3 * k + j] = place;
+        a.face_mesh_new[(int64_t)a.nft + j * (int64_t)a.s + k] = mesh;
+    }
+    a.vert_mesh_new[(int64_t)a.nv + k] = mesh;
+}
+
+// Launch 2, a workgroup per chunk: the two running sums (the chunk's own, on top of the totals of the chunks in front of it),
+// the tables in their final form, the old ids copied.
+__global__ __launch_bounds__(SPLIT_THREADS) void face_split_scan_ragged_kernel(RaggedIndexArgs a)
+{
+    __shared__ int lds[SPLIT_THREADS];
+    __shared__ int64_t lds64[SPLIT_THREADS];
+    const int t = threadIdx.x;
+    const int64_t chunk = blockIdx.x, i = chunk * SPLIT_CHUNK + t;
+    if (chunk * SPLIT_CHUNK < a.nfa) { // unsplit_rank[i] = how many unsplit rows precede row i
+        int64_t part = 0;
+        for (int64_t q = t; q < chunk; q += SPLIT_THREADS) part += a.rtot[q];
+        const int64_t split_before = block_sum(part, lds64);
+        const int64_t k = i < a.nfa ? a.sp_tmp[i] - 1 : 0;
+        const int within = block_offset((i < a.nfa && k < 0) ? 1 : 0, lds);
+        if (i < a.nfa) a.split_pos[i] = k, a.unsplit_rank[i] = chunk * SPLIT_CHUNK - split_before + within;
+    }
+    if (chunk * SPLIT_CHUNK < a.nv) { // inc_ptr[u + 1] = the counts up to and with vertex u
+        int64_t part = 0;
+        for (int64_t q = t; q < chunk; q += SPLIT_THREADS) part += a.vtot[q];
+        const int64_t before = block_sum(part, lds64);
+        const int n = i < a.nv ? (int)a.count[i] : 0;
+        const int within = block_offset(n, lds);
+        if (i < a.nv) a.inc_ptr[i + 1] = before + within + n, a.vert_mesh_new[i] = a.vert_mesh[i];
+    }
+    if (i == 0) a.inc_ptr[0] = 0;
+    if (i < a.nft) a.face_s[i] = a.fs_tmp[i] - 1, a.face_mesh_new[i] = a.face_mesh[i];
+    if (i < 3 * (int64_t)a.s) a.inc_item[i] = -1;
+}
+
+// Launch 3, a thread per corner of a split face: the incidence rows, each corner at the place it arrived at.
+__global__ __launch_bounds__(SPLIT_THREADS) void face_split_fill_ragged_kernel(RaggedIndexArgs a)
+{
+    const int64_t e = (int64_t)blockIdx.x * SPLIT_THREADS + threadIdx.x;
+    if (e >= 3 * (int64_t)a.s) return;
+    const int64_t c = a.corners[e], place = a.slot[e];
+    if (c < 0 || c >= a.nv || place < 0) return;
+    const int64_t at = a.inc_ptr[c] + place;
+    if (at >= 0 && at < a.inc_ptr[c + 1] && at < 3 * (int64_t)a.s) a.inc_item[at] = e / 3;
+}
+
+// Launch 4, a thread per vertex: ascending split order within its row, which hides the order the atomics were served in.
+__global__ __launch_bounds__(SPLIT_THREADS) void face_split_sort_ragged_kernel(RaggedIndexArgs a)
+{
+    const int64_t u = (int64_t)blockIdx.x * SPLIT_THREADS + threadIdx.x;
+    if (u >= a.nv) return;
+    const int64_t lo = a.inc_ptr[u], hi = a.inc_ptr[u + 1];
+    if (lo < 0 || hi > 3 * (int64_t)a.s) return;
+    for (int64_t i = lo + 1; i < hi; ++i) {
+        const int64_t v = a.inc_item[i];
+        int64_t j = i;
+        for (; j > lo && a.inc_item[j - 1] > v; --j) a.inc_item[j] = a.inc_item[j - 1];
+        a.inc_item[j] = v;
+    }
+}
+
 } // namespace
+
+extern "C" int geom_face_select_ragged_f32(int nfa, const float *curvature, float angle, int b, const int *row_list,
+                                           const int *row_off, int64_t *stats, int64_t *selected, int64_t *counts,
+                                           int64_t *totals, void *stream)
+{
+    if (nfa < 0 || b < 0) return GEOM_EINVAL;
+    if (!totals || (nfa > 0 && (!curvature || !row_list))) return GEOM_EINVAL;
+    if (b > 0 && (!row_off || !stats || !selected || !counts)) return GEOM_EINVAL;
+    hipStream_t q = static_cast<hipStream_t>(stream);
+    if (b == 0) return hipMemsetAsync(totals, 0, 2 * sizeof(int64_t), q) == hipSuccess ? 0 : geom::launch_status();
+    RaggedSelectArgs a{nfa, b, curvature, angle, row_list, row_off, stats, selected, counts, totals};
+    hipLaunchKernelGGL(face_select_ragged_stats_kernel, dim3(b), dim3(SPLIT_THREADS), 0, q, a);
+    hipLaunchKernelGGL(face_select_ragged_write_kernel, dim3(b), dim3(SPLIT_THREADS), 0, q, a);
+    return geom::launch_status();
+}
+
+extern "C" int64_t geom_face_split_index_ragged_words(int nv, int nft, int nfa, int s)
+{
+    if (nv < 0 || nft < 0 || nfa < 0 || s < 0) return GEOM_EINVAL;
+    return ragged_index_zeroed_words(nv, nft, nfa) + 3 * (int64_t)s;
+}
+
+extern "C" int geom_face_split_index_ragged(int nv, int nft, const int64_t *faces, int nfa, const int64_t *face_list, int s,
+                                            const int64_t *splitting, const int64_t *vert_mesh, const int64_t *face_mesh,
+                                            int64_t *corners, int64_t *split_pos, int64_t *unsplit_rank, int64_t *face_s,
+                                            int64_t *inc_ptr, int64_t *inc_item, int64_t *vert_mesh_new, int64_t *face_mesh_new,
+                                            int64_t *workspace, void *stream)
+{
+    if (nv < 0 || nft < 0 || nfa < 0 || s < 0 || s > nfa) return GEOM_EINVAL;
+    if (!inc_ptr || !workspace) return GEOM_EINVAL;
+    if (nft > 0 && (!faces || !face_s || !face_mesh)) return GEOM_EINVAL;
+    if (nfa > 0 && (!face_list || !split_pos || !unsplit_rank)) return GEOM_EINVAL;
+    if (nv > 0 && !vert_mesh) return GEOM_EINVAL;
+    if (nv + s > 0 && !vert_mesh_new) return GEOM_EINVAL;
+    if (nft + s > 0 && !face_mesh_new) return GEOM_EINVAL;
+    if (s > 0 && (!splitting || !corners || !inc_item)) return GEOM_EINVAL;
+    if (3 * (int64_t)s > INT_MAX || (int64_t)nft + 3 * (int64_t)s > INT_MAX || (int64_t)nv + s > INT_MAX) return GEOM_ETOOBIG;
+    hipStream_t q = static_cast<hipStream_t>(stream);
+    const int64_t zeroed = ragged_index_zeroed_words(nv, nft, nfa);
+    RaggedIndexArgs a{nv, nft, nfa, s, faces, face_list, splitting, vert_mesh, face_mesh, corners, split_pos, unsplit_rank, face_s,
+                      inc_ptr, inc_item, vert_mesh_new, face_mesh_new};
+    a.count = workspace;
+    a.vtot = a.count + nv;
+    a.rtot = a.vtot + chunks_of(nv);
+    a.sp_tmp = a.rtot + chunks_of(nfa);
+    a.fs_tmp = a.sp_tmp + nfa;
+    a.slot = workspace + zeroed;
+    if (zeroed > 0 && hipMemsetAsync(workspace, 0, zeroed * sizeof(int64_t), q) != hipSuccess) return geom::launch_status();
+    const auto blocks = [](int64_t items) { return dim3((unsigned)((items + SPLIT_THREADS - 1) / SPLIT_THREADS)); };
+    int64_t widest = nfa > nv ? nfa : nv;
+    widest = nft > widest ? nft : widest;
+    widest = 3 * (int64_t)s > widest ? 3 * (int64_t)s : widest;
+    if (s > 0) hipLaunchKernelGGL(face_split_scatter_ragged_kernel, blocks(s), dim3(SPLIT_THREADS), 0, q, a);
+    hipLaunchKernelGGL(face_split_scan_ragged_kernel, blocks(widest > 0 ? widest : 1), dim3(SPLIT_THREADS), 0, q, a);
+    if (s > 0) hipLaunchKernelGGL(face_split_fill_ragged_kernel, blocks(3 * (int64_t)s), dim3(SPLIT_THREADS), 0, q, a);
+    if (s > 0 && nv > 0) hipLaunchKernelGGL(face_split_sort_ragged_kernel, blocks(nv), dim3(SPLIT_THREADS), 0, q, a);
+    return geom::launch_status();
+}
 
 extern "C" int geom_face_curvature_f32(int nv, const float *verts, int nft, const int64_t *faces, int nfa,
                                        const int64_t *face_list, float *curvature, void *stream)

@@ -104,11 +104,16 @@ def _finish_csr(c):
     return c
 
 
-def csr_from_parts(rowptr, col, val, rowptr_t, col_t, val_t):
+def csr_from_parts(rowptr, col, val, rowptr_t, col_t, val_t, derive=True):
     """An adjacency handed over already in CSR (+ CSR^T): int32 rowptr/col, fp32 val, on the device.  The result
-    can be passed wherever a layer takes `adj` (geometrics_amd.ragged builds block-diagonal batches this way)."""
+    can be passed wherever a layer takes `adj` (geometrics_amd.ragged builds block-diagonal batches this way).
+    derive=False: the six arrays alone, nothing read on the host (utils.ragged_split_info inside a captured step); the
+    derived tables (_finish_csr: the ELL width is a host decision) are made when adjacency_csr first sees the object, as
+    for a CSR handed over through register_csr."""
     c = _Csr()
     c.rowptr, c.col, c.val, c.rowptr_t, c.col_t, c.val_t = rowptr, col, val, rowptr_t, col_t, val_t
+    if not derive:
+        return c
     with torch.no_grad():
         return _finish_csr(c)
 
@@ -119,6 +124,9 @@ def adjacency_csr(adj):
     adjacency of the same size -- auto_encoder.py builds a fresh one per mesh).  Building reads the dense
     matrix once (one host sync, at first use only)."""
     if isinstance(adj, _Csr):
+        if not hasattr(adj, "ell_w"):              # csr_from_parts(derive=False): its derived tables are made at first use
+            with torch.no_grad():
+                _finish_csr(adj)
         return adj
     if hasattr(adj, "csr") and isinstance(adj.csr, _Csr):     # a RaggedMeshBatch
         return adj.csr

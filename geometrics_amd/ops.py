@@ -1243,3 +1243,40 @@ class SplitVertices(torch.autograd.Function):
         out_f = torch.empty(ix.nv, ctx.c, dtype=torch.float32, device=gv.device)
         _lib.call("geom_split_vertices_bwd_f32", ix.nv, ix.s, ctx.c, gv, gf, ix.inc_ptr, ix.inc_item, out_v, out_f)
         return out_v, out_f, None
+
+
+# ---------------------------------------------- the same for the union of a ragged batch ----
+def select_faces_ragged(curvature, angle, row_list, row_off):
+    """The selection of select_faces per mesh (geom_face_select_ragged_f32; row_list / row_off: ragged.group_rows): (selected
+    int64 [Fa + 3 b] -- its first totals[0] entries are mesh 0's positions, then mesh 1's, ... --, counts int64 [b], totals int64
+    [2] = {entries, meshes without three faces that have a curvature}), all on the device: two launches, no host read."""
+    c = _f32(curvature, "curvature", 1)
+    row_list = _lib.require(row_list, "row_list", torch.int32, 1)
+    row_off = _lib.require(row_off, "row_off", torch.int32, 1)
+    _lib.same_device(c, row_list, row_off)
+    b = row_off.numel() - 1
+    if row_list.numel() != c.shape[0] or b < 0:
+        raise RuntimeError("row_list must list the %d active rows and row_off hold b+1 offsets (ragged.group_rows)" % c.shape[0])
+    new = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=c.device)
+    stats, selected, counts, totals = new(b, 4), new(c.shape[0] + 3 * b), new(b), new(2)
+    _lib.call("geom_face_select_ragged_f32", c.shape[0], c, float(angle), b, row_list, row_off, stats, selected, counts, totals)
+    return selected, counts, totals
+
+
+def split_index_ragged(faces, face_list, splitting, nv, vert_mesh, face_mesh):
+    """(SplitIndex, vert_mesh_new int64 [V+S], face_mesh_new int64 [Ft+3S]) of splitting the active rows `splitting` of a union:
+    the tables of split_index made by geom_face_split_index_ragged -- a zero-fill and at most four launches over chunks of the
+    union, no host read -- and the mesh ids after the split."""
+    ix = SplitIndex()
+    dev = faces.device
+    s = ix.s = int(splitting.numel())
+    ix.nv = int(nv)
+    nft, nfa = faces.shape[0], face_list.shape[0]
+    new = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
+    ix.corners, ix.split_pos, ix.unsplit_rank, ix.face_s = new(s, 3), new(nfa), new(nfa), new(nft)
+    ix.inc_ptr, ix.inc_item = new(ix.nv + 1), new(3 * s)
+    vert_mesh_new, face_mesh_new = new(ix.nv + s), new(nft + 3 * s)
+    workspace = new(max(int(_lib.lib().geom_face_split_index_ragged_words(ix.nv, nft, nfa, s)), 1))
+    _lib.call("geom_face_split_index_ragged", ix.nv, nft, faces, nfa, face_list, s, splitting, vert_mesh, face_mesh, ix.corners,
+              ix.split_pos, ix.unsplit_rank, ix.face_s, ix.inc_ptr, ix.inc_item, vert_mesh_new, face_mesh_new, workspace)
+    return ix, vert_mesh_new, face_mesh_new

@@ -137,6 +137,26 @@ def group_vertices(vert_mesh, b):
     return hit
 
 
+_row_group_cache = ByTensor()    # (face_list, face_mesh), extra: the mesh count -> (row_list, row_off)
+
+
+def group_rows(face_list, face_mesh, b):
+    """(row_list int32 [Fa], row_off int32 [b+1]) for utils.ragged_calc_curve: the ACTIVE rows of a union's face_list [Fa,3,3]
+    grouped by the mesh of their face, face_mesh[face_list[i, 0, 2]], ascending inside a mesh; rows whose id is outside [0, b)
+    stand in front of row_off[0] or behind row_off[b].  The construction of group_faces on the rows' ids: no host read, cached
+    per face_list and face_mesh TENSOR OBJECTS and their in-place versions."""
+    if face_list.dim() != 3 or face_list.shape[1:] != (3, 3):
+        raise RuntimeError("face_list must be [Fa,3,3] (got shape %s)" % (tuple(face_list.shape),))
+    if face_mesh.dim() != 1 or face_mesh.dtype != torch.int64:
+        raise RuntimeError("face_mesh must be a one-dimensional int64 tensor (got %s %s)" % (face_mesh.dtype, tuple(face_mesh.shape)))
+    hit = _row_group_cache.get(face_list, face_mesh, extra=int(b))
+    if hit is None:
+        with torch.no_grad():
+            ids = face_mesh.detach().index_select(0, face_list[:, 0, 2]).clamp(-1, int(b))
+            hit = _row_group_cache.put(_group_by_mesh(ids, b), face_list, face_mesh, extra=int(b))
+    return hit
+
+
 def face_mesh(faces, vert_mesh):
     """vert_mesh[faces[:, 0]]: the mesh of every face from the mesh of every vertex -- for callers that track ids per vertex
     (through utils.split_info a new vertex inherits its face's mesh)."""
@@ -237,5 +257,5 @@ def regulariser_tables(face_mesh, vert_mesh, b, w_lap, w_move, w_edge):
     return hit
 
 
-__all__ = ["RaggedMeshBatch", "group_faces", "group_vertices", "face_mesh", "csr_from_faces", "mesh_counts", "regulariser_coefficients",
+__all__ = ["RaggedMeshBatch", "group_faces", "group_vertices", "group_rows", "face_mesh", "csr_from_faces", "mesh_counts", "regulariser_coefficients",
            "regulariser_tables"]

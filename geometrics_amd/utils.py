@@ -60,7 +60,9 @@ def calc_face_list(faces):
     """int64 [F,3,3] on the device: row i, slot j = [the face across edge j, the label that face gives the shared edge, i], edges
     0 / 1 / 2 = the vertex pairs (0,1), (1,2), (0,2) (reference old_GEOMetrics/utils.py:158-179, an O(F^2) python loop there;
     here one sort of the 3F edge keys).  Set-up code on torch ops, one host read (the check).  An edge that is not shared by
-    exactly two faces raises -- the reference silently returns a ragged list for such a mesh."""
+    exactly two faces raises -- the reference silently returns a ragged list for such a mesh.  The UNION of a ragged batch
+    (faces of several meshes indexing their concatenated vertices, in any order) is such a mesh as it stands: no edge joins two
+    meshes, so every edge is still shared by exactly two faces, both of its own mesh (ragged_adj_init)."""
     faces = torch.as_tensor(faces)
     if faces.dim() != 2 or faces.shape[1] != 3:
         raise RuntimeError("faces must be [F,3] (got shape %s)" % (tuple(faces.shape),))
@@ -152,6 +154,119 @@ def split_info(info, verts, features, splitting, number):
     layers.register_csr(t["adj"], (t["rowptr"], t["col"], t["val"], t["rowptr"], t["col"], t["val_t"]))
     layers.register_csr(t["adj_orig"], (t["rowptr"], t["col"], t["ones"], t["rowptr"], t["col"], t["ones"]))
     new_info = {"adj": t["adj"], "adj_orig": t["adj_orig"], "faces": t["new_faces"], "face_list": t["new_face_list"]}
+    return new_info, new_verts, new_features
+
+
+# ------------------------------------- the same for a ragged batch held as ONE union mesh ----
+def _ragged_info(info, nv=None):
+    """The checked tables of a union's info: (faces, face_list, face_mesh, vert_mesh, b).  Shapes and dtypes first (they need no
+    device), each complaint naming its argument."""
+    faces, face_list, face_mesh, vert_mesh = info["faces"], info["face_list"], info["face_mesh"], info["vert_mesh"]
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int64:
+        raise RuntimeError("info['faces'] must be [Ft,3] int64 (got %s %s)" % (faces.dtype, tuple(faces.shape)))
+    if face_list.dim() != 3 or face_list.shape[1:] != (3, 3) or face_list.dtype != torch.int64:
+        raise RuntimeError("info['face_list'] must be [Fa,3,3] int64 (got %s %s)" % (face_list.dtype, tuple(face_list.shape)))
+    if face_mesh.dtype != torch.int64 or face_mesh.shape != (faces.shape[0],):
+        raise RuntimeError("info['face_mesh'] must be int64 [%d], one id per face ever made (got %s %s)"
+                           % (faces.shape[0], face_mesh.dtype, tuple(face_mesh.shape)))
+    if vert_mesh.dtype != torch.int64 or vert_mesh.dim() != 1 or (nv is not None and vert_mesh.numel() != nv):
+        raise RuntimeError("info['vert_mesh'] must be int64 [%s], one id per vertex (got %s %s)"
+                           % ("Vt" if nv is None else nv, vert_mesh.dtype, tuple(vert_mesh.shape)))
+    return faces, face_list, face_mesh, vert_mesh, int(info["b"])
+
+
+def ragged_adj_init(faces_union, vert_mesh, b):
+    """The info of a ragged batch of b meshes held as one union mesh -- faces_union [Ft,3] int64 into the concatenated vertices,
+    vert_mesh int64 [Vt] the mesh of every vertex --, what adj_init + calc_face_list are to one mesh: {'faces', 'face_list'
+    (calc_face_list works on a union as it stands), 'face_mesh' int64 [Ft] (ragged.face_mesh: one id per face ever made, dead
+    ones included), 'vert_mesh', 'csr' (ragged.csr_from_faces: pass it wherever a layer takes `adj`), 'b'}.  There is no 'adj'
+    and no 'adj_orig': a union never forms a dense [Vt,Vt] matrix.  Set-up code: torch ops and their host reads."""
+    from . import ragged
+    if not torch.is_tensor(faces_union) or faces_union.dim() != 2 or faces_union.shape[1] != 3 or faces_union.dtype != torch.int64:
+        raise RuntimeError("faces must be an [Ft,3] int64 tensor (got %s)" % (
+            "%s %s" % (faces_union.dtype, tuple(faces_union.shape)) if torch.is_tensor(faces_union) else type(faces_union).__name__))
+    if not torch.is_tensor(vert_mesh) or vert_mesh.dim() != 1 or vert_mesh.dtype != torch.int64:
+        raise RuntimeError("vert_mesh must be a one-dimensional int64 tensor (got %s)" % (
+            "%s %s" % (vert_mesh.dtype, tuple(vert_mesh.shape)) if torch.is_tensor(vert_mesh) else type(vert_mesh).__name__))
+    faces = faces_union.contiguous()
+    return {"faces": faces, "face_list": calc_face_list(faces), "face_mesh": ragged.face_mesh(faces, vert_mesh).contiguous(),
+            "vert_mesh": vert_mesh.contiguous(), "csr": ragged.csr_from_faces(faces, vert_mesh.numel()), "b": int(b)}
+
+
+_ragged_active_cache = ByTensor()   # (face_list, faces, face_mesh) -> (the active faces, their mesh ids)
+
+
+def ragged_active_faces(info):
+    """(faces[face_list[:, 0, 2]], face_mesh[face_list[:, 0, 2]]): the active faces of a union and the mesh of each -- the pair
+    ragged_point_to_surface and ragged_stage_regularisers take.  Cached per TENSOR OBJECTS and in-place versions, as
+    active_faces: the tables those functions key on the pair are built once per topology."""
+    face_list, faces, face_mesh = info["face_list"], info["faces"], info["face_mesh"]
+    hit = _ragged_active_cache.get(face_list, faces, face_mesh)
+    if hit is None:
+        with torch.no_grad():
+            own = face_list[:, 0, 2]
+            hit = _ragged_active_cache.put((faces.index_select(0, own).contiguous(), face_mesh.index_select(0, own).contiguous()),
+                                           face_list, faces, face_mesh)
+    return hit
+
+
+def ragged_calc_curve(verts, info, angle=70):
+    """calc_curve for every mesh of a union at once: (splitting int64 [S], counts int64 [b]).  `splitting` lists mesh 0's
+    positions into info['face_list'], then mesh 1's, ...: per mesh what calc_curve selects on that mesh alone -- the rows above
+    `angle` ascending, or below three of them the mesh's OWN three most curved faces, largest first, the lower position first
+    on ties, NaN never -- because the curvature launch is the same (each face has the bits it has on its mesh alone) and the
+    selection walks each mesh's rows separately (a workgroup per mesh, two launches, no atomics: two runs give the same bits).
+    counts[m] = how many entries mesh m contributed, on the device.  A row whose mesh id is outside [0, b) is never selected.
+    Three launches and ONE host read of two words: S, and the number of meshes with fewer than three faces that have a
+    curvature, which raises as calc_curve does.  Not differentiable."""
+    from . import ragged
+    faces, face_list, face_mesh, _, b = _ragged_info(info)
+    curvature = ops.face_curvature(verts, faces, face_list)
+    row_list, row_off = ragged.group_rows(face_list, face_mesh, b)
+    selected, counts, totals = ops.select_faces_ragged(curvature, angle, row_list, row_off)
+    total, short = totals.tolist()                      # the one host read
+    if short:
+        raise RuntimeError("ragged_calc_curve: %d of the %d meshes have fewer than 3 faces with a curvature (degenerate or too "
+                           "small a mesh)" % (short, b))
+    return selected[:total], counts
+
+
+def ragged_split_info(info, verts, features, splitting):
+    """split_info on the union of a ragged batch (info: ragged_adj_init or an earlier call's), minus the dense matrices: returns
+    (new_info, new_verts [Vt+S,3], new_features [Vt+S,C]).  `splitting`: unique positions into info['face_list'] in [0, Fa), not
+    checked (ragged_calc_curve's list); S = splitting.numel().  new_info has the keys of ragged_adj_init: 'faces' [Ft+3S,3] and
+    'face_list' [Fa+2S,3,3] by the launch split_info uses (geom_face_split_tables, dense matrices off), 'vert_mesh' [Vt+S] and
+    'face_mesh' [Ft+3S] (old ids, then every new vertex and child the mesh of its split face), 'csr' the normalised adjacency
+    from the same launch (pass it wherever a layer takes `adj`; ragged_stage_regularisers reads its rowptr / col / inv_deg).
+    The vertices are ops.SplitVertices: the union's new rows and both gradients carry the existing kernels' bits.
+      * restricted to mesh m and relabelled by rank inside the mesh, the result IS split_info's on mesh m alone (DESIGN 4g);
+      * no [n,n] tensor is allocated; the index tables come from launches over chunks of the union;
+      * nothing is read on the host and the call can be captured in a graph: the csr is layers.csr_from_parts(rowptr, col, val,
+        rowptr, col, val_t, derive=False) -- the six arrays; its derived tables (the width of its neighbour table is a host
+        decision) are made when a layer or a regulariser first sees it (layers.adjacency_csr), as for the CSR split_info hands
+        over with its dense matrices; a later ragged_split_info takes it as it is."""
+    from . import layers
+    nv = verts.shape[0]
+    faces, face_list, face_mesh, vert_mesh, b = _ragged_info(info, nv)
+    if features.dim() != 2 or features.shape[0] != nv:
+        raise RuntimeError("features %s must have the %d rows of verts" % (tuple(features.shape), nv))
+    splitting = torch.as_tensor(splitting, device=verts.device).to(torch.int64).reshape(-1).contiguous()
+    if splitting.numel() > face_list.shape[0]:
+        raise RuntimeError("ragged_split_info: splitting holds %d positions for %d active faces" % (splitting.numel(), face_list.shape[0]))
+    old = info["csr"]
+    if not isinstance(old, layers._Csr) or old.rowptr.numel() != nv + 1:
+        raise RuntimeError("info['csr'] must be the union's adjacency over the %d rows of verts (ragged.csr_from_faces)" % nv)
+    faces = ops._lib.require(faces, "info['faces']", torch.int64, 2, 3)
+    face_list = ops._lib.require(face_list, "info['face_list']", torch.int64, 3, 3)
+    face_mesh = ops._lib.require(face_mesh, "info['face_mesh']", torch.int64, 1)
+    vert_mesh = ops._lib.require(vert_mesh, "info['vert_mesh']", torch.int64, 1)
+    ix, vert_mesh_new, face_mesh_new = ops.split_index_ragged(faces, face_list, splitting, nv, vert_mesh, face_mesh)
+    t = ops.split_tables(faces, face_list, ix, old.rowptr, old.col, dense=False)
+    new_verts, new_features = ops.SplitVertices.apply(verts, features, ix)
+    # the pattern is symmetric: it is its own transpose; the normalised matrix's transpose has the columns' 1 / row length
+    csr = layers.csr_from_parts(t["rowptr"], t["col"], t["val"], t["rowptr"], t["col"], t["val_t"], derive=False)
+    new_info = {"faces": t["new_faces"], "face_list": t["new_face_list"], "face_mesh": face_mesh_new, "vert_mesh": vert_mesh_new,
+                "csr": csr, "b": b}
     return new_info, new_verts, new_features
 
 

@@ -750,6 +750,32 @@ int geom_split_vertices_fwd_f32(int nv, int s, int c, const float *verts, const 
 int geom_split_vertices_bwd_f32(int nv, int s, int c, const float *grad_out_verts, const float *grad_out_features,
                                 const int64_t *inc_ptr, const int64_t *inc_item, float *grad_verts, float *grad_features,
                                 void *stream);
+/* ---- the same for the UNION of a ragged batch: verts / faces / face_list as above (the union is one mesh to the curvature, the
+ * tables and the vertices), plus the id of its mesh per face ever made (face_mesh int64 [nft]) and per vertex (vert_mesh int64
+ * [nv]).  An id outside [0, b) belongs to no mesh.
+ *
+ * The selection of geom_face_select_f32 taken per mesh.  row_list int32 [nfa]: the active rows grouped by the mesh of their face,
+ * ascending inside a mesh; row_off int32 [b+1]: where each group starts (rows in front of row_off[0] or behind row_off[b] belong
+ * to no mesh and are never selected).  selected int64 [nfa + 3 b]: mesh 0's entries, then mesh 1's, ...: a mesh's positions i with
+ * (curvature[i] * 180) / pi > angle, ascending, or below three of them the positions of its three largest curvatures, largest
+ * first, lower position first on ties, NaN never (as many as exist).  counts int64 [b]: the entries per mesh.  totals int64 [2] =
+ * {entries in all, meshes with fewer than three hits AND fewer than three faces that have a curvature}.  stats: int64 [b,4] of
+ * scratch.  Two launches of a workgroup per mesh, no atomics: the same bits on every run.  b == 0: totals = {0, 0}. */
+int geom_face_select_ragged_f32(int nfa, const float *curvature, float angle, int b, const int *row_list, const int *row_off,
+                                int64_t *stats, int64_t *selected, int64_t *counts, int64_t *totals, void *stream);
+/* The index tables of geom_face_split_index -- same fields, same meaning, written in full -- over as many workgroups as the
+ * union has chunks of 256 items, and the ids after the split: vert_mesh_new [nv+s] (old ids, then vertex nv + k the mesh of split
+ * face k), face_mesh_new [nft+3s] (old ids, then child nft + j s + k the same); -1 where splitting[k] names no face.  workspace:
+ * geom_face_split_index_ragged_words(nv, nft, nfa, s) int64 words, contents free.  One zero-fill of the workspace and at most
+ * four launches -- scatter and integer counts; the running sums (a chunk's own on top of the totals of the chunks in front of
+ * it); the incidence fill; the sort inside each vertex's row, after which no order in which an atomic was served shows -- with no
+ * workgroup waiting on another and no host read.  Codes as geom_face_split_index; 3 s, nft + 3 s or nv + s above INT_MAX:
+ * GEOM_ETOOBIG. */
+int64_t geom_face_split_index_ragged_words(int nv, int nft, int nfa, int s);
+int geom_face_split_index_ragged(int nv, int nft, const int64_t *faces, int nfa, const int64_t *face_list, int s,
+                                 const int64_t *splitting, const int64_t *vert_mesh, const int64_t *face_mesh, int64_t *corners,
+                                 int64_t *split_pos, int64_t *unsplit_rank, int64_t *face_s, int64_t *inc_ptr, int64_t *inc_item,
+                                 int64_t *vert_mesh_new, int64_t *face_mesh_new, int64_t *workspace, void *stream);
 
 /* ---- per-vertex BatchNorm + ReLU + residual average (SURVEY 8f "next" row 2; models.py:222-297) --------
  * nn.BatchNorm1d(verts) applied to x [b,nv,c]: one statistic per vertex over its b*c values, then
