@@ -81,12 +81,32 @@ __device__ __forceinline__ float block_sum_virtual(float (&v)[FIN_VIRTUAL / THRE
 struct FinalizeNoWait {
     __device__ __forceinline__ bool operator()() const { return true; }
 };
+// Faces: which faces a mesh's points are binned into.  FinalizeShared: every mesh has the batch's a.nf faces and a point's bin
+// is its face id.  FinalizeRagged: a RAGGED batch -- the meshes own their faces inside one union face list (ragged.group_faces);
+// mesh m has F_m = face_off[m + 1] - face_off[m] faces (read on the device), a point's bin is the POSITION of its union face id
+// inside the mesh (face_pos: the inverse of face_list, -1 for a face of no mesh; a union id that is no face of mesh m
+// contributes nowhere), and the offsets leave the workgroup as one (absolute start in seg, count) pair per UNION face, the ids
+// in seg as ids of the flat batch (surface_layout.h: RaggedSurfaceScratch).  The launch's kernel hands every workgroup its own
+// copy of the arguments with a.nf = F_m (surface_gather.hip: surface_finalize_ragged_kernel, which also turns away a mesh with
+// more faces than the launch's LDS holds).  The ordering itself is the same code.
+struct FinalizeShared {
+};
+struct FinalizeRagged {
+    const int *face_list, *face_off, *face_pos; // [nft], [b + 1], [nft]
+    int2 *pair;                                 // [nft]
+    int *fmesh;                                 // [nft]: the mesh that wrote the pair (-1: none)
+    int nft;
+    int face0; // where the workgroup's mesh starts in face_list (the launch's kernel sets it, with a.nf = the mesh's face count)
+};
 // ITEMS: points per thread the REGS variant keeps in registers (per <= ITEMS * THREADS; beyond: the scratch variant).
 // READY: the caller guarantees a.records_ready (the code that forms records is left out: it is what made the register
 // variant spill inside the fused scan launch).
-template <bool REGS, int THREADS, typename Wait = FinalizeNoWait, int ITEMS = FIN_REG_POINTS / THREADS, bool READY = false>
-__device__ __forceinline__ void surface_finalize_body(const FinalizeArgs &a, int *ord_lds, const int block, Wait wait = Wait())
+template <bool REGS, int THREADS, typename Wait = FinalizeNoWait, int ITEMS = FIN_REG_POINTS / THREADS, bool READY = false,
+          typename Faces = FinalizeShared>
+__device__ __forceinline__ void surface_finalize_body(const FinalizeArgs &a, int *ord_lds, const int block, Wait wait = Wait(),
+                                                      const Faces &fc = Faces())
 {
+    constexpr bool RAGGED = std::is_same<Faces, FinalizeRagged>::value;
     constexpr int WAVES = THREADS / GEOM_WAVE;
     constexpr int V = FIN_VIRTUAL / THREADS;
     int *off = ord_lds;                       // [nf+1]: counts, then offsets (ordering only)
@@ -99,6 +119,15 @@ __device__ __forceinline__ void surface_finalize_body(const FinalizeArgs &a, int
     // ---- the extra workgroup (block == b) reduces the loss while the others order their meshes: float4 loads, all
     //      of a thread's loads in flight together, then a fixed tree -- no cross-workgroup hand-off at all ----
     if (mesh == a.b) {
+        if constexpr (RAGGED) {
+            // the faces no mesh writes a pair for; the loss only where the caller wants this role's (per-mesh weights)
+            for (int f = tid; f < fc.nft; f += THREADS)
+                if (fc.face_pos[f] < 0) fc.pair[f] = make_int2(0, 0), fc.fmesh[f] = -1;
+            if (!a.loss) {
+                if (tid == 0 && a.status) a.status[a.b] = 0;
+                return;
+            }
+        }
         if (!wait()) {
             if (tid == 0) {
                 a.loss[0] = __builtin_nanf("");
@@ -218,6 +247,10 @@ __device__ __forceinline__ void surface_finalize_body(const FinalizeArgs &a, int
                 a.rec[2 * (p0 + id) + 0] = make_float4(g.x, g.y, g.z, skip_zero);
                 a.rec[2 * (p0 + id) + 1] = w;
             }
+            if constexpr (RAGGED) { // union face id -> position inside this mesh
+                const int pos = f >= 0 && f < fc.nft ? fc.face_pos[f] - fc.face0 : -1;
+                f = pos < a.nf ? pos : -1;
+            }
             const bool on_mesh = f >= 0 && f < a.nf; // else: contributes nowhere
             fi = on_mesh ? (int)f : -1;
             sl = on_mesh ? atomicAdd(&off[fi], 1) : 0; // LDS atomic: arrival slot inside the face
@@ -318,8 +351,15 @@ __device__ __forceinline__ void surface_finalize_body(const FinalizeArgs &a, int
         if (tid == THREADS - 1) off[a.nf] = base + run;
         __syncthreads();
         FIN_PHASE(5);
-        int *g_off = a.off + (int64_t)mesh * (a.nf + 1);
-        for (int f = tid; f <= a.nf; f += THREADS) g_off[f] = off[f];
+        if constexpr (RAGGED) {
+            for (int k = tid; k < a.nf; k += THREADS) {
+                const int face = fc.face_list[fc.face0 + k];
+                if ((unsigned)face < (unsigned)fc.nft) fc.pair[face] = make_int2((int)p0 + off[k], off[k + 1] - off[k]), fc.fmesh[face] = mesh;
+            }
+        } else {
+            int *g_off = a.off + (int64_t)mesh * (a.nf + 1);
+            for (int f = tid; f <= a.nf; f += THREADS) g_off[f] = off[f];
+        }
         // ---- ids at offset + slot, then ranked into ascending order ----
         int placed_below = 0; // ids below: their final place was found in front of the wait (grouped samples of a role)
         if (REGS) {
@@ -358,12 +398,13 @@ __device__ __forceinline__ void surface_finalize_body(const FinalizeArgs &a, int
         //      orders its segment serially, 10 faces per thread: 18-24 us instead of 5 -- a crowded face is quadratic for one
         //      thread; the same with crowded faces handed to a wave each: 13.7 us.) ----
         int *g_seg = a.seg + p0;
+        const int id0 = RAGGED ? (int)p0 : 0; // a ragged batch keeps ids of the flat batch: its gather enters seg by union face
         auto place = [&](int id, int f) {
             const int s0 = off[f], n = off[f + 1] - s0;
             int rank = 0;
             if (n > 1) // a face that holds one point (most do): nothing to rank
                 for (int j = 0; j < n; ++j) rank += seg[s0 + j] < id ? 1 : 0;
-            g_seg[s0 + rank] = id;
+            g_seg[s0 + rank] = id0 + id;
         };
         if (REGS) {
             // segment bounds of all of a thread's ids first (2 * ITEMS LDS reads in flight), then id by id.  (One entry of
@@ -383,7 +424,7 @@ __device__ __forceinline__ void surface_finalize_body(const FinalizeArgs &a, int
                 int rank = 0;
                 if (cnt[it] > 1) // a face that holds one point (most do): nothing to rank
                     for (int j = 0; j < cnt[it]; ++j) rank += seg[s0[it] + j] < id ? 1 : 0;
-                g_seg[s0[it] + rank] = id;
+                g_seg[s0[it] + rank] = id0 + id;
             }
         } else {
 #pragma unroll

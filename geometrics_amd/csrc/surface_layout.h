@@ -28,3 +28,35 @@ static inline SurfaceScratch geom_surface_scratch(int *order, int b, int nf, int
     return SurfaceScratch{order, seg, pface, pface + (int64_t)b * cap, reinterpret_cast<float4 *>(order + geom_surface_order_ints(b, nf, cap)),
                           order + geom_surface_status_offset(b, nf, cap)};
 }
+
+// The same scratch for a RAGGED batch (b meshes that own their faces inside one union of nft faces):
+//   pair[nft] (int2) | fmesh[nft] | seg[b,cap] | pface[b,cap] | slot[b,cap] | pad to 4 words | rec[b,cap,2] float4 | status[b+1, pad to 4]
+// pair[f] = (where face f's points start in seg -- an index into the WHOLE seg array --, how many they are), written by the
+// workgroup of the face's mesh; (0, 0) for a face of no mesh (written by the loss role's workgroup); count < 0: the mesh's
+// ordering was given up (more faces than the launch's LDS holds; status[m] != 0 says the same per mesh).  fmesh[f]: the mesh that
+// wrote the pair, -1 for none.  seg holds ids of the flat batch, m * cap + id, so rec is entered with them directly: the gather
+// goes from a UNION face id to its records by pair[f] -> seg -> rec, the chain off[f], off[f+1] -> seg -> rec of the batched
+// layout, and nothing has to be zeroed in front of the launch.
+static inline int64_t geom_surface_ragged_order_ints(int b, int nft, int64_t cap)
+{
+    return ((3 * (int64_t)nft + 3 * (int64_t)b * cap) + 3) & ~3ll;
+}
+static inline int64_t geom_surface_ragged_status_offset(int b, int nft, int64_t cap)
+{
+    return geom_surface_ragged_order_ints(b, nft, cap) + (int64_t)b * cap * 8;
+}
+struct RaggedSurfaceScratch {
+    int2 *pair;                // [nft]
+    int *fmesh;                // [nft]
+    int *seg, *pface, *slot;   // [b,cap] each
+    float4 *rec;               // [b,cap,2]
+    int *status;               // [b+1]
+};
+static inline RaggedSurfaceScratch geom_surface_ragged_scratch(int *order, int b, int nft, int64_t cap)
+{
+    if (!order) return RaggedSurfaceScratch{};
+    int *fmesh = order + 2 * (int64_t)nft, *seg = fmesh + nft, *pface = seg + (int64_t)b * cap;
+    return RaggedSurfaceScratch{reinterpret_cast<int2 *>(order), fmesh, seg, pface, pface + (int64_t)b * cap,
+                                reinterpret_cast<float4 *>(order + geom_surface_ragged_order_ints(b, nft, cap)),
+                                order + geom_surface_ragged_status_offset(b, nft, cap)};
+}

@@ -231,7 +231,8 @@ def finalize_roles_gave_up():
 # Inspection hook (tests, bench.py's parity spot check): a dict that receives the arg-min outputs of the next SurfaceLoss
 # forward passes as they sit on the device -- idx_gt (nearest sampled point of every gt point), idx_pred (nearest gt point of
 # every sampled point), the draws (choices, u, v) and sampled points it ran on and, one-sided loss, tri_index / tri_option /
-# tri_dist of the point-to-triangle scan.  None: off.
+# tri_dist of the point-to-triangle scan.  RaggedSurfaceLoss fills it likewise (per-mesh neighbour indices, UNION face ids; one-
+# sided loss: tri_index / tri_option and closest / weights / sq of the closest-point pass).  None: off.
 scan_capture = None
 
 # The one-sided loss with f1=False reads only the sampled points' nearest gt points: utils.batch_point_to_surface then leaves
@@ -1041,18 +1042,42 @@ def _offsets_by_row(rows, stride, dev):
     return _row_offsets[key]
 
 
+# The backward of the ragged surface loss: "ordered" (the default: finalize + gather, no float atomics, same bits on every run)
+# or "scatter" (GEOM_RAGGED_BACKWARD=scatter: the fp32-atomic kernels, always -- the A/B switch; they also serve a batch whose
+# points per mesh do not fit the finalize launch's LDS).
+ragged_backward = os.environ.get("GEOM_RAGGED_BACKWARD", "ordered")
+
+
+def _face_positions(face_list, face_off):
+    """ragged.face_positions from the grouping alone: the inverse of face_list, -1 outside [face_off[0], face_off[B])."""
+    pos = torch.empty_like(face_list)
+    pos[face_list.to(torch.int64)] = torch.arange(face_list.numel(), dtype=torch.int32, device=face_list.device)
+    return torch.where((pos >= face_off[0]) & (pos < face_off[-1]), pos, torch.full_like(pos, -1))
+
+
 class RaggedSurfaceLoss(torch.autograd.Function):
     """SurfaceLoss for a ragged batch: B meshes with their own faces on one union vertex array, one call instead of B.
 
     Value: the mean over the meshes of what SurfaceLoss gives for that mesh alone -- scale * (sum sq_pred / (B num) +
-    sum sq_other / (B N)).  Only the two steps that must know which faces belong to which mesh run on the ragged kernels (the
-    draw: ops.draw_samples_ragged, and the point-to-triangle scan); everything else sees either regular [B, ., 3] clouds
-    (the Chamfer scan at b = B) or the union as ONE mesh at b = 1 with the union's face ids (gather, closest point,
-    backward).  Backward: the fp32-atomic scatter kernels of SurfaceLoss's overflow fallback.  No host read."""
+    sum sq_other / (B N)); with mesh_weight [B] fp32, (1/B) sum_m w[m] * (mesh m's loss).  Only the steps that must know which
+    faces belong to which mesh run on the ragged kernels (the draw: ops.draw_samples_ragged, the point-to-triangle scan, and
+    the backward's preparation); everything else sees either regular [B, ., 3] clouds (the Chamfer scan at b = B) or the union
+    as ONE mesh at b = 1 with the union's face ids (gather of the points, closest point).
+    Backward: SurfaceLoss's -- when a gradient is wanted the forward ends with the ragged finalize launch (every mesh's points
+    counting-sorted by face in ascending id order, csrc/surface_gather.hip) and the backward is ONE gather launch over the
+    union's vertices: no zero-fill, no float atomics, the same bits on every run, per mesh the bits of the batched pair on that
+    mesh alone.  face_pos: ragged.face_positions (None: derived from the grouping).  Where the points of a mesh do not fit the
+    finalize launch's LDS (num + N beyond ~38 000), or with ragged_backward = "scatter": the fp32-atomic scatter kernels of
+    SurfaceLoss's overflow fallback, which know no per-mesh weights (a RuntimeError with them).  No host read."""
 
     @staticmethod
-    def forward(ctx, verts, faces, face_list, face_off, gt, choices, u, v, two_sided, scale, points=None, need_gt_nn=True):
+    def forward(ctx, verts, faces, face_list, face_off, gt, choices, u, v, two_sided, scale, points=None, need_gt_nn=True,
+                mesh_weight=None, face_pos=None):
         verts_c, faces, face_list, face_off, b = _ragged_mesh(verts, faces, face_list, face_off)
+        if mesh_weight is not None:
+            mesh_weight = _f32(mesh_weight.detach(), "mesh_weight", 1)
+            if mesh_weight.shape[0] != b or mesh_weight.device != verts_c.device:
+                raise RuntimeError("mesh_weight must be [B] on the meshes' device")
         gt_c = _f32(gt.detach(), "gt_points", 3, 3)
         if gt_c.shape[0] != b or gt_c.device != verts_c.device:
             raise RuntimeError("gt_points must be [B,N,3] on the meshes' device with B = %d meshes" % b)
@@ -1086,11 +1111,42 @@ class RaggedSurfaceLoss(torch.autograd.Function):
             _lib.call("geom_tri_distance_ragged_f32", b, n_gt, gt_c, nv, verts_c, nf, faces, face_list, face_off,
                       torch.empty(b, n_gt, **f32), option, index, 0)
             _lib.call("geom_p2tri_loss_fwd_f32", 1, b * n_gt, gt_c, nv, verts_c, nf, faces, option, index, other_sq, closest, weights)
-        parts, out = torch.empty(2, **f32), torch.empty((), **f32)
-        _lib.call("geom_sum_f32", sq_pred.numel(), sq_pred, scale / sq_pred.numel(), parts)
-        _lib.call("geom_sum_f32", other_sq.numel(), other_sq, scale / other_sq.numel(), parts[1:])
-        _lib.call("geom_sum_f32", 2, parts, 1.0, out)
-        if ctx.needs_input_grad[0]:     # the backward sees ONE mesh: per-mesh neighbour indices become indices of the flat batch
+        out = torch.empty((), **f32)
+        if mesh_weight is None:         # (the value keeps these three sums whichever backward follows)
+            parts = torch.empty(2, **f32)
+            _lib.call("geom_sum_f32", sq_pred.numel(), sq_pred, scale / sq_pred.numel(), parts)
+            _lib.call("geom_sum_f32", other_sq.numel(), other_sq, scale / other_sq.numel(), parts[1:])
+            _lib.call("geom_sum_f32", 2, parts, 1.0, out)
+        want = bool(ctx.needs_input_grad[0])
+        # the ordered backward's preparation; with per-mesh weights the same launch's loss role forms the weighted loss
+        ctx.order = None
+        if mesh_weight is not None and ragged_backward == "scatter":
+            raise RuntimeError("per-mesh weights need the ordered backward (GEOM_RAGGED_BACKWARD=scatter is set)")
+        if mesh_weight is not None or (want and ragged_backward != "scatter"):
+            if face_pos is None:
+                face_pos = _face_positions(face_list, face_off)
+            face_pos = _lib.require(face_pos, "face_pos", torch.int32, 1)
+            if face_pos.numel() != nf or face_pos.device != dev:
+                raise RuntimeError("face_pos must hold one position per face on the meshes' device (ragged.face_positions)")
+            order = torch.empty(_lib.lib().geom_surface_order_ragged_words(b, nf, num, n_gt), dtype=torch.int32, device=dev)
+            code = _lib.status("geom_surface_finalize_ragged_f32", b, nf, face_list, face_off, face_pos, num, choices, u, v, points,
+                               n_gt, gt_c, idx_g, idx_p if two_sided else None, None if two_sided else index,
+                               None if two_sided else closest, None if two_sided else weights, sq_pred, other_sq,
+                               scale / sq_pred.numel(), scale / other_sq.numel(), scale / (b * num), scale / (b * n_gt), order,
+                               None if mesh_weight is None else out, mesh_weight)
+            if code == _lib.EUNSUPPORTED and mesh_weight is not None:
+                raise RuntimeError("per-mesh weights need the ordered backward (the points of a mesh within ~38 000)")
+            if code != _lib.EUNSUPPORTED:       # (else: too many points per mesh for the in-LDS ordering -- scatter backward)
+                _lib.check(code, "geom_surface_finalize_ragged_f32")
+                if want:
+                    from . import ragged
+                    ctx.order, ctx.vf, ctx.mesh_weight = order, ragged.vertex_faces(faces, nv), mesh_weight
+                    ctx.shape = (b, num, n_gt, nf)
+        if scan_capture is not None:
+            scan_capture.update(idx_gt=idx_p, idx_pred=idx_g, sq_gt=sq_gt, sq_pred=sq_pred, choices=choices, u=u, v=v, points=points)
+            if not two_sided:
+                scan_capture.update(tri_index=index, tri_option=option, closest=closest, weights=weights, sq=other_sq)
+        if want and ctx.order is None:  # the scatter backward sees ONE mesh: per-mesh neighbour indices become indices of the flat batch
             idx_g_flat = idx_g + _offsets_by_row(b, n_gt, dev)
             if two_sided:
                 ctx.save_for_backward(faces, choices, u, v, points, gt_c, idx_g_flat, idx_p + _offsets_by_row(b, num, dev))
@@ -1103,11 +1159,17 @@ class RaggedSurfaceLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad, _g1, _g2):
+        grad = grad.contiguous()
+        if ctx.order is not None:           # prepared by the forward's finalize launch: one gather, no atomics
+            b, num, n_gt, nf = ctx.shape
+            grad_verts = torch.empty(ctx.nv, 3, dtype=torch.float32, device=ctx.order.device)
+            _lib.call("geom_surface_gather_ragged_f32", b, ctx.nv, nf, ctx.vf[0], ctx.vf[1], num, n_gt, ctx.order, grad,
+                      ctx.mesh_weight, grad_verts)
+            return (grad_verts,) + (None,) * 13
         saved = ctx.saved_tensors
         faces, choices, u, v, points, gt, idx_g = saved[:7]
         b, num, _ = points.shape
         n_gt, nf, nv = gt.shape[1], faces.shape[0], ctx.nv
-        grad = grad.contiguous()
         grad_verts = torch.zeros(nv, 3, dtype=torch.float32, device=points.device)
         coef_s, coef_o = ctx.scale / (b * num), ctx.scale / (b * n_gt)
         if ctx.two_sided:
@@ -1118,7 +1180,7 @@ class RaggedSurfaceLoss(torch.autograd.Function):
             index, closest, weights = saved[7:10]
             _lib.call("geom_surface_loss_bwd_f32", 1, nv, nf, faces, b * num, choices, u, v, points, b * n_gt, gt, idx_g, index,
                       closest, weights, grad, coef_s, coef_o, grad_verts)
-        return (grad_verts,) + (None,) * 11
+        return (grad_verts,) + (None,) * 13
 
 
 class VertexHead(torch.autograd.Function):

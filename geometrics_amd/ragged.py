@@ -121,6 +121,50 @@ def group_faces(face_mesh, b, faces=None):
     return hit
 
 
+_position_cache = ByTensor()    # the keys of group_faces, extra: the mesh count -> face_pos
+
+
+def face_positions(face_mesh, b, faces=None):
+    """face_pos int32 [Ft] on face_mesh's device: the inverse permutation of group_faces' face_list -- face f stands at
+    face_list[face_pos[f]], so its position inside its mesh m is face_pos[f] - face_off[m] -- with -1 for a face of no mesh (an
+    id outside [0, b)).  What the ordered backward of the ragged surface loss bins by (ops.RaggedSurfaceLoss).  Torch ops
+    only, no host read; cached per tensor objects like group_faces."""
+    keys = (face_mesh,) if faces is None else (faces, face_mesh)
+    hit = _position_cache.get(*keys, extra=int(b))
+    if hit is None:
+        face_list, _ = group_faces(face_mesh, b, faces)
+        with torch.no_grad():
+            ids = face_mesh.detach().to(torch.int64)
+            pos = torch.empty_like(face_list)
+            pos[face_list.to(torch.int64)] = torch.arange(face_list.numel(), dtype=torch.int32, device=face_list.device)
+            pos = torch.where((ids >= 0) & (ids < int(b)), pos, torch.full_like(pos, -1))
+        hit = _position_cache.put(pos.contiguous(), *keys, extra=int(b))
+    return hit
+
+
+_vertex_face_cache = ByTensor()    # (faces,), extra: the vertex count -> (vf_ptr, vf_item)
+
+
+def vertex_faces(faces, nv):
+    """(vf_ptr int32 [nv+1], vf_item int32 [3 Ft]) of ops.vertex_faces -- vertex -> incident (face << 2 | corner), ascending per
+    vertex: what the gather backward walks -- built WITHOUT its two host reads: a stable argsort of the flattened corners, and
+    the row starts by a binary search over arange(nv + 1) (the construction of group_faces).  A corner outside [0, nv) falls in
+    front of vf_ptr[0] or behind vf_ptr[nv] and is never walked.  A ragged stage gets new faces after every split, so this table
+    is rebuilt every step: a host read here would be the only one of the loss.  Cached per faces TENSOR OBJECT and version."""
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int64:
+        raise RuntimeError("faces must be [Ft,3] int64 (got %s %s)" % (faces.dtype, tuple(faces.shape)))
+    hit = _vertex_face_cache.get(faces, extra=int(nv))
+    if hit is None:
+        with torch.no_grad():
+            flat = faces.detach().reshape(-1)
+            order = torch.argsort(flat, stable=True)                      # position p = 3*face + corner
+            vf_item = (((order // 3) << 2) | (order % 3)).to(torch.int32).contiguous()
+            bounds = torch.arange(int(nv) + 1, dtype=torch.int64, device=faces.device)
+            vf_ptr = torch.searchsorted(flat[order].contiguous(), bounds).to(torch.int32).contiguous()
+        hit = _vertex_face_cache.put((vf_ptr, vf_item), faces, extra=int(nv))
+    return hit
+
+
 def group_vertices(vert_mesh, b):
     """(vert_list int32 [Vt], vert_off int32 [b+1]) on vert_mesh's device, for the ragged pooling: the
     union's vertices grouped by mesh -- a stable argsort of the ids clamped to [-1, b], so a vertex of no mesh stands in front of
@@ -257,5 +301,5 @@ def regulariser_tables(face_mesh, vert_mesh, b, w_lap, w_move, w_edge):
     return hit
 
 
-__all__ = ["RaggedMeshBatch", "group_faces", "group_vertices", "group_rows", "face_mesh", "csr_from_faces", "mesh_counts", "regulariser_coefficients",
+__all__ = ["RaggedMeshBatch", "group_faces", "face_positions", "vertex_faces", "group_vertices", "group_rows", "face_mesh", "csr_from_faces", "mesh_counts", "regulariser_coefficients",
            "regulariser_tables"]

@@ -338,14 +338,23 @@ def batch_point_to_surface(pred_vert, adj_info, gt_points, num=1000, f1=False, d
     return _surface_loss(pred_vert, adj_info, gt_points, num, f1, draws, False, loss_out, gt_index, weight)
 
 
-def _ragged_surface_loss(verts, faces, face_mesh, gt_points, num, f1, draws, two_sided):
+def _ragged_surface_loss(verts, faces, face_mesh, gt_points, num, f1, draws, two_sided, weight=1.0):
     from . import ragged
     if gt_points.dim() != 3:
         raise RuntimeError("gt_points must be [B,N,3] (got shape %s)" % (tuple(gt_points.shape),))
     if face_mesh.dim() != 1 or face_mesh.shape[0] != faces.shape[0]:
         raise RuntimeError("face_mesh must hold one mesh id per face: [%d] (got shape %s)" % (faces.shape[0], tuple(face_mesh.shape)))
     b = gt_points.shape[0]
+    mesh_weight = None
+    if isinstance(weight, torch.Tensor):      # per-mesh factors: the loss's own scale stays, the kernels apply the factors
+        if weight.shape != (b,) or weight.dtype != torch.float32 or weight.device != gt_points.device:
+            raise RuntimeError("a per-mesh weight must be a [%d] float32 tensor on %s (got %s %s on %s)"
+                               % (b, gt_points.device, weight.dtype, tuple(weight.shape), weight.device))
+        mesh_weight, weight = weight, 1.0
+    elif isinstance(weight, bool) or not isinstance(weight, (int, float)):
+        raise RuntimeError("weight must be a python float or a [B] float32 tensor (got %s)" % type(weight).__name__)
     face_list, face_off = ragged.group_faces(face_mesh, b, faces)
+    face_pos = ragged.face_positions(face_mesh, b, faces)
     points = None
     if draws is None:       # one launch draws AND gathers the points
         choices, u, v, points = ops.draw_samples_ragged(verts, faces, face_list, face_off, num, with_points=True)
@@ -353,13 +362,13 @@ def _ragged_surface_loss(verts, faces, face_mesh, gt_points, num, f1, draws, two
         choices, u, v = draws
     need_gt_nn = bool(f1) or two_sided
     loss, sq_gt, sq_pred = ops.RaggedSurfaceLoss.apply(verts, faces, face_list, face_off, gt_points, choices, u, v, two_sided,
-                                                       LOSS_SCALE, points, need_gt_nn)
+                                                       LOSS_SCALE * float(weight), points, need_gt_nn, mesh_weight, face_pos)
     if f1:
         return loss, _f_score(sq_gt, sq_pred, num)
     return loss
 
 
-def ragged_point_to_surface(verts, faces, face_mesh, gt_points, num=1000, f1=False, draws=None):
+def ragged_point_to_surface(verts, faces, face_mesh, gt_points, num=1000, f1=False, draws=None, weight=1.0):
     """batch_point_to_surface for a RAGGED batch: B meshes with their own faces, as after an adaptive split.  verts [Vt,3]
     fp32 (differentiable): the meshes' vertices concatenated, as in ragged.RaggedMeshBatch; faces [Ft,3] int64 into verts: the
     faces the loss runs on (active_faces for split meshes); face_mesh [Ft] in [0, B): the mesh of every face, in any order
@@ -367,14 +376,20 @@ def ragged_point_to_surface(verts, faces, face_mesh, gt_points, num=1000, f1=Fal
     batch_point_to_surface(verts[None], {'faces': the faces of mesh m}, gt_points[m:m+1], num) -- 3000 * (sum sq_pred / (B num)
     + sum sq_tri / (B N)) -- in ONE call: neither search crosses from one mesh into another and every mesh gets `num`
     samples.  draws=(choices [B,num] UNION face ids, u, v) replays draws.  No host read unless f1=True, no padding.  Each
-    mesh may hold 1 to 16384 faces; a mesh outside that makes the loss NaN (ops.draw_samples_ragged)."""
-    return _ragged_surface_loss(verts, faces, face_mesh, gt_points, num, f1, draws, False)
+    mesh may hold 1 to 16384 faces; a mesh outside that makes the loss NaN (ops.draw_samples_ragged).  weight, as
+    batch_point_to_surface's: a factor folded into the loss's own scale (`weight * loss` without the multiply launches), or a
+    [B] fp32 tensor of PER-MESH factors -- the result is (1/B) sum_m weight[m] * L_m with L_m the loss of mesh m alone: the three
+    stages of the cascade stacked into one call (their unions concatenated into one union of 3B meshes, whatever their
+    topologies, against `torch.cat((gt, gt, gt))`, weights 3 x (.2, .2, 2) per stage: the mean is over the stacked batch).
+    The gradient is bit-reproducible: the ordered backward of ops.RaggedSurfaceLoss (GEOM_RAGGED_BACKWARD=scatter: the fp32-atomic
+    scatter, float weights only)."""
+    return _ragged_surface_loss(verts, faces, face_mesh, gt_points, num, f1, draws, False, weight)
 
 
-def ragged_point_to_point(verts, faces, face_mesh, gt_points, num=1000, f1=False, draws=None):
+def ragged_point_to_point(verts, faces, face_mesh, gt_points, num=1000, f1=False, draws=None, weight=1.0):
     """batch_point_to_point for a ragged batch: arguments and contract as ragged_point_to_surface, the mean over m of
     batch_point_to_point on mesh m alone."""
-    return _ragged_surface_loss(verts, faces, face_mesh, gt_points, num, f1, draws, True)
+    return _ragged_surface_loss(verts, faces, face_mesh, gt_points, num, f1, draws, True, weight)
 
 
 def calc_point_to_line(p, triangles, point_options):

@@ -984,6 +984,31 @@ int geom_surface_finalize_w_f32(int b, int nf, int num, const int64_t *choices, 
 int geom_surface_gather_w_f32(int b, int nv, int nf, const int *vf_ptr, const int *vf_item, int num, int n_gt,
                               int has_other, const int *order, const float *grad, const float *mesh_weight,
                               float *grad_verts, void *stream);
+/* The same pair for a RAGGED batch: b meshes that own their faces inside one union of nft faces on nv union vertices
+ * (face_list [nft] / face_off [b+1]: the faces grouped by mesh, ascending inside a mesh; face_pos [nft]: the inverse of
+ * face_list, -1 for a face of no mesh).  choices / index hold UNION face ids; idx_g / idx_p are per mesh as the Chamfer scan
+ * at b meshes writes them (the partner of sample s of mesh m is gt[m * n_gt + idx_g[m, s]]); exactly one of idx_p / index.
+ * The finalize always orders: one workgroup per mesh, its face count read on the device; the launch's LDS is sized for
+ * geom_surface_ragged_face_cap(nft, num, n_gt) = min(nft, what fits beside num + n_gt points) faces per mesh
+ * (GEOM_EUNSUPPORTED, from both, when the points alone do not fit: use the scatter backward).  A mesh with more faces than
+ * that is not ordered: its status word is set and the gather writes NaN to the vertices of its faces; no other mesh is
+ * affected.  loss may be NULL (the caller sums the loss itself); with mesh_weight [b] it is required and receives sum_m w[m]
+ * * (scale_sample * sum(sq_sample[m]) + scale_other * sum(sq_other[m])).  `order`: geom_surface_order_ragged_words(b, nft,
+ * num, n_gt) int32 words, 16-byte aligned, uninitialised.  The gather writes every element of grad_verts [nv,3] once (vf_ptr
+ * / vf_item: the UNION's vertex -> (face << 2 | corner) table): mesh m's rows carry the bits of geom_surface_finalize_w_f32 +
+ * geom_surface_gather_w_f32 at b = 1 on the faces of mesh m in ascending union id with mesh_weight = w + m.  With weights, a
+ * vertex whose incident faces belong to different meshes gets NaN; a vertex without incident faces gets 0. */
+int64_t geom_surface_order_ragged_words(int b, int nft, int num, int n_gt);
+int geom_surface_ragged_face_cap(int nft, int num, int n_gt);
+int geom_surface_finalize_ragged_f32(int b, int nft, const int *face_list, const int *face_off, const int *face_pos, int num,
+                                     const int64_t *choices, const float *u, const float *v, const float *points, int n_gt,
+                                     const float *gt, const int *idx_g, const int *idx_p, const int *index,
+                                     const float *closest, const float *weights, const float *sq_sample,
+                                     const float *sq_other, float scale_sample, float scale_other, float coef_sample,
+                                     float coef_other, int *order, float *loss, const float *mesh_weight, void *stream);
+int geom_surface_gather_ragged_f32(int b, int nv, int nft, const int *vf_ptr, const int *vf_item, int num, int n_gt,
+                                   const int *order, const float *grad, const float *mesh_weight, float *grad_verts,
+                                   void *stream);
 
 /* ---- ragged mesh batches (SURVEY 8f "next" row 4; auto_encoder.py:71-76, layers.py:78) ---------------
  * Meshes of different sizes are concatenated along the vertex axis; segment s owns rows
