@@ -17,6 +17,9 @@
 // A batch of meshes with their OWN vertex counts (after an adaptive split) is one union of vertices with a mesh id each: the
 // same bodies instantiated a second time (RG below), a workgroup owning 64 positions of the vertices grouped by mesh and every
 // lane bringing its own mesh -- geom_pool_features_ragged_*, DESIGN.md section 4f.
+// The old driver's pooling(blocks, verts_pos, matrix) (old_GEOMetrics/utils.py:379-427) projects with one 4 x 4 matrix per image
+// where the camera pair stands: a third instantiation axis (MX below), which only project() and the finish step's chain read --
+// geom_pool_features_proj_* / geom_pool_features_ragged_proj_*, compiled through pooling_proj.hip, DESIGN.md section 4h.
 // The reference's interpolation quirk is kept: weights are (ceil - x, x - floor), so a coordinate that
 // is exactly integral (incl. clamped ones) gets all-zero weights (utils.py:346-350, 372-379).
 #include "buffer_access.h"
@@ -31,7 +34,15 @@ constexpr int PL_MAX_CHUNKS = 32;   // grid.z of the pooling launches (more 64-c
 constexpr float PL_SCALE = 0.57f, PL_FOCAL = 248.f, PL_HALF = 224.f / 2.0f, PL_NORM = 223.f;
 
 struct PoolArgs {
-    const float *verts, *cam_mat, *cam_pos;
+    const float *verts;
+    // the camera, one kind per launch: the pair cam_mat [b,9], cam_pos [b,3] of batch_camera_info, or -- the MATRIX launches (MX
+    // below) -- proj [b,16], one row-major 4 x 4 projection matrix per mesh (cam_pos is null then).  proj
+    // shares cam_mat's place: the struct, and with it the camera launches' code objects, are what they were without it.
+    union {
+        const float *cam_mat;
+        const float *proj;
+    };
+    const float *cam_pos;
     const float *blocks[GEOM_POOL_MAX_LEVELS];
     float *grad_blocks[GEOM_POOL_MAX_LEVELS];
     int channels[GEOM_POOL_MAX_LEVELS], dims[GEOM_POOL_MAX_LEVELS];
@@ -46,8 +57,10 @@ struct PoolArgs {
     const int *vert_off;  // [b + 1] where each mesh's group starts in vert_list
 };
 
-// Every body below is stated once and instantiated twice: RG = false, the batched launches ([b, nv] rows, a workgroup's mesh is
-// uniform), RG = true, the ragged ones (the mesh is the LANE's).  What differs is where a row lives and which mesh it belongs to:
+// Every body below is stated once and instantiated for {batched, ragged} x {camera, matrix}: RG = false, the batched launches
+// ([b, nv] rows, a workgroup's mesh is uniform), RG = true, the ragged ones (the mesh is the LANE's); MX = false, the camera pair
+// of batch_camera_info, MX = true, the old driver's projection matrix (project() and the chain of pool_bwd_verts_finish_body:
+// nothing else knows the camera's kind).  What RG changes is where a row lives and which mesh it belongs to:
 template <bool RG>
 __device__ __forceinline__ size_t vert_row(const PoolArgs &a, int mesh, int v)
 {
@@ -84,10 +97,23 @@ struct Projection {
     float X, Y, Z, xs, ys;
 };
 
-template <bool RG>
+// MX (the reference's pooling(blocks, verts_pos, matrix), old utils.py:379-385): q = M . (x, y, z, 1) with M = proj[mesh], each
+// row summed left to right, ys = (q0 / q3 + 1) / 2, xs = 1 - (q1 / q3 + 1) / 2.  Row 2 of M is never read (the reference computes q2
+// and drops it).  (X, Y, Z) of the result = (q0, q1, q3).  RG: the lane loads its own mesh's 12 floats -- as many as the camera pair.
+template <bool RG, bool MX>
 __device__ __forceinline__ Projection project(const PoolArgs &a, int mesh, int v)
 {
     const float *p = a.verts + vert_row<RG>(a, mesh, v) * 3;
+    if constexpr (MX) {
+        const float *M = a.proj + (size_t)mesh * 16;
+        Projection r;
+        r.X = ((p[0] * M[0] + p[1] * M[1]) + p[2] * M[2]) + M[3];
+        r.Y = ((p[0] * M[4] + p[1] * M[5]) + p[2] * M[6]) + M[7];
+        r.Z = ((p[0] * M[12] + p[1] * M[13]) + p[2] * M[14]) + M[15];
+        r.ys = (r.X / r.Z + 1.f) / 2.f;
+        r.xs = 1.f - (r.Y / r.Z + 1.f) / 2.f;
+        return r;
+    }
     const float *M = a.cam_mat + (size_t)mesh * 9, *cp = a.cam_pos + (size_t)mesh * 3;
     const float ax = p[0] * PL_SCALE - cp[0], ay = p[1] * PL_SCALE - cp[1], az = p[2] * PL_SCALE - cp[2];
     Projection r;
@@ -268,10 +294,10 @@ static inline unsigned pool_grid(const PoolArgs &a, bool ragged = false)
 // A live work item's walk over its chunks: the vertex is projected once; body(chunk, the vertex's texels in that chunk's map, the
 // chunk's channels) per chunk (one chunk per workgroup up to PL_MAX_CHUNKS chunks).  The body is the whole workgroup's: it may
 // hold barriers.
-template <bool RG, class Body>
+template <bool RG, bool MX, class Body>
 __device__ __forceinline__ void pool_chunks(const PoolArgs &a, const PoolWork &k, Body body)
 {
-    const Projection pr = project<RG>(a, k.mesh, k.v);
+    const Projection pr = project<RG, MX>(a, k.mesh, k.v);
     for (int z = k.z; z < a.chunks; z += a.zc) {
         const Chunk ck = chunk_of(a, z);
         body(ck, texel(pr.xs, pr.ys, a.dims[ck.level]), min(GEOM_WAVE, a.channels[ck.level] - ck.cc));
@@ -294,7 +320,7 @@ struct PoolFronts {
 };
 
 // (RG: nothing in front; a vertex of no mesh gets a row of zeros -- a select, whatever its position or mesh 0's planes hold)
-template <bool RG>
+template <bool RG, bool MX>
 __global__ __launch_bounds__(PL_THREADS) void pool_fwd_kernel(PoolArgs a, float *out, PoolFronts fr)
 {
     __shared__ PoolTile tile;
@@ -316,7 +342,7 @@ __global__ __launch_bounds__(PL_THREADS) void pool_fwd_kernel(PoolArgs a, float 
     if (!k.live) return;
     const int mesh = k.mesh, v0 = k.v0, lane = k.lane;
     const bool ok = k.ok;
-    pool_chunks<RG>(a, k, [&](const Chunk &ck, const Texel &t, int nch) {
+    pool_chunks<RG, MX>(a, k, [&](const Chunk &ck, const Texel &t, int nch) {
         chunk_quads<RG>(a, ck, mesh, t, nch, [&](int c, const Quad &q) {
             const float s1 = (t.A * q.c11) * t.G, s2 = (t.H * q.c12) * t.A;
             const float s3 = (t.G * q.c21) * t.B, s4 = (t.B * q.c22) * t.H;
@@ -374,7 +400,7 @@ struct VertsLds {
     float part[PL_WAVES][2][PL_VERTS];
 };
 
-template <bool RG>
+template <bool RG, bool MX>
 __device__ __forceinline__ void pool_bwd_verts_body(const PoolArgs &a, const BinSpace &ws, const float *grad_out, int bid, int nblocks,
                                                     VertsLds &L)
 {
@@ -382,7 +408,7 @@ __device__ __forceinline__ void pool_bwd_verts_body(const PoolArgs &a, const Bin
     if (!k.live) return;
     const int mesh = k.mesh, v0 = k.v0, lane = k.lane, wave = threadIdx.x >> 6;
     float ax = 0.f, ay = 0.f; // this wave's share of d loss / d (xs, ys) of the lane's vertex over the workgroup's chunks
-    pool_chunks<RG>(a, k, [&](const Chunk &ck, const Texel &t, int nch) {
+    pool_chunks<RG, MX>(a, k, [&](const Chunk &ck, const Texel &t, int nch) {
         const float *gi = grad_out + (RG ? 0 : ((size_t)mesh * a.nv + v0) * a.ld) + ck.off + ck.cc + (lane < nch ? lane : 0);
         for (int vv = wave; vv < PL_VERTS; vv += PL_WAVES) { // (a wave reads one vertex's 64 channels per round)
             float g = 0.f;
@@ -418,7 +444,7 @@ __device__ __forceinline__ void pool_bwd_verts_body(const PoolArgs &a, const Bin
 }
 
 // (RG: v is a vertex of the union and brings its own mesh; the vertex of no mesh gets a zero row without a look at the sums)
-template <bool RG>
+template <bool RG, bool MX>
 __device__ __forceinline__ void pool_bwd_verts_finish_body(const PoolArgs &a, const BinSpace &ws, float *grad_verts, int mesh, int v)
 {
     if (v >= a.nv) return;
@@ -431,11 +457,28 @@ __device__ __forceinline__ void pool_bwd_verts_finish_body(const PoolArgs &a, co
         }
         mesh = m.mesh;
     }
-    const Projection pr = project<RG>(a, mesh, v);
+    const Projection pr = project<RG, MX>(a, mesh, v);
     float sx = 0.f, sy = 0.f;
     for (int z = 0; z < a.zc; ++z) {
         const float *p = ws.sums(z, RG ? 0 : mesh, v);
         sx += p[0], sy += p[1];
+    }
+    if constexpr (MX) {
+        // ys = (q0 / q3 + 1) / 2, xs = 1 - (q1 / q3 + 1) / 2 with (q0, q1, q3) = (pr.X, pr.Y, pr.Z):
+        //   g0 = d/dq0 = (0.5 * sy) / q3,  g1 = d/dq1 = (-0.5 * sx) / q3,  g3 = d/dq3 = -(g0 * q0 + g1 * q1) / q3,
+        //   grad_v[j] = (g0 * M[0][j] + g1 * M[1][j]) + g3 * M[3][j]        -- in this order, uncontracted
+        const float *M = a.proj + (size_t)mesh * 16;
+        float *gv = grad_verts + vert_row<RG>(a, mesh, v) * 3;
+        if (sx == 0.f && sy == 0.f) { // the clamp is a SELECT on the sums: see below
+            gv[0] = gv[1] = gv[2] = 0.f;
+            return;
+        }
+        const float g0 = (0.5f * sy) / pr.Z, g1 = (-0.5f * sx) / pr.Z;
+        const float g3 = -(g0 * pr.X + g1 * pr.Y) / pr.Z;
+        gv[0] = (g0 * M[0] + g1 * M[4]) + g3 * M[12];
+        gv[1] = (g0 * M[1] + g1 * M[5]) + g3 * M[13];
+        gv[2] = (g0 * M[2] + g1 * M[6]) + g3 * M[14];
+        return;
     }
     // xs = h/223, ys = w/223; h = (-Y)/(-Z)*F + 112, w = X/(-Z)*F + 112
     const float gh = sx / PL_NORM, gw = sy / PL_NORM;
@@ -482,24 +525,24 @@ struct BinLds {
 
 // f(vertex, texel, weight) for every corner of a mesh's vertices in one map: a pass of the binning workgroup over its vertices
 // (RG: the positions of the mesh's group in the grouped list; v is then a vertex of the union)
-template <bool RG, class F>
+template <bool RG, bool MX, class F>
 __device__ __forceinline__ void mesh_corners(const PoolArgs &a, int mesh, int dim, F f)
 {
     const Group g = RG ? group_of(a.vert_off, a.nv, mesh) : Group{0, a.nv};
     for (int i = threadIdx.x; i < g.n; i += BIN_THREADS) {
         const int v = RG ? list_vertex(a, g.p0 + i) : i;
-        const Projection pr = project<RG>(a, mesh, v);
+        const Projection pr = project<RG, MX>(a, mesh, v);
         corners(texel(pr.xs, pr.ys, dim), [&](int i, float w) { f(v, i, w); });
     }
 }
 
-template <bool RG>
+template <bool RG, bool MX>
 __device__ __forceinline__ void pool_bin_body(const PoolArgs &a, const BinSpace &ws, int l, int mesh, BinLds &L)
 {
     const int dim = a.dims[l], texels = dim * dim;
     for (int i = threadIdx.x; i <= texels; i += BIN_THREADS) L.counts[i] = 0;
     __syncthreads();
-    mesh_corners<RG>(a, mesh, dim, [&](int, int i, float) { atomicAdd(&L.counts[i], 1); });
+    mesh_corners<RG, MX>(a, mesh, dim, [&](int, int i, float) { atomicAdd(&L.counts[i], 1); });
     __syncthreads();
     // exclusive scan of counts[0..texels): thread owns a contiguous run, wave shuffle scan, wave totals
     const int per = (texels + BIN_THREADS - 1) / BIN_THREADS;
@@ -532,7 +575,7 @@ __device__ __forceinline__ void pool_bin_body(const PoolArgs &a, const BinSpace 
     }
     int *ev = ws.list_v<RG>(mesh, l);
     float *ew = ws.list_w<RG>(mesh, l);
-    mesh_corners<RG>(a, mesh, dim, [&](int v, int i, float w) {
+    mesh_corners<RG, MX>(a, mesh, dim, [&](int v, int i, float w) {
         const int p = atomicAdd(&L.counts[i], 1);
         ev[p] = v, ew[p] = w;
     });
@@ -545,7 +588,7 @@ __device__ __forceinline__ void pool_bin_body(const PoolArgs &a, const BinSpace 
 //   2. pool_bwd_grads_kernel: the map gradient from the lists BESIDE the vertex gradient from the per-chunk sums.
 static_assert(BIN_THREADS == PL_THREADS, "the two roles of a launch share its workgroup size");
 
-template <bool RG>
+template <bool RG, bool MX>
 __global__ __launch_bounds__(PL_THREADS) void pool_bwd_lists_kernel(PoolArgs a, BinSpace ws, const float *grad_out, int bin_blocks,
                                                                     int verts_blocks)
 {
@@ -554,8 +597,8 @@ __global__ __launch_bounds__(PL_THREADS) void pool_bwd_lists_kernel(PoolArgs a, 
         VertsLds verts;
         __device__ Lds() {}
     } lds;
-    if ((int)blockIdx.x < bin_blocks) pool_bin_body<RG>(a, ws, (int)blockIdx.x % a.levels, (int)blockIdx.x / a.levels, lds.bin);
-    else pool_bwd_verts_body<RG>(a, ws, grad_out, (int)blockIdx.x - bin_blocks, verts_blocks, lds.verts);
+    if ((int)blockIdx.x < bin_blocks) pool_bin_body<RG, MX>(a, ws, (int)blockIdx.x % a.levels, (int)blockIdx.x / a.levels, lds.bin);
+    else pool_bwd_verts_body<RG, MX>(a, ws, grad_out, (int)blockIdx.x - bin_blocks, verts_blocks, lds.verts);
 }
 
 // What this kernel has to avoid is not traffic but INSTRUCTIONS and TAILS.  The lists are short and skewed: at the training
@@ -723,14 +766,14 @@ __device__ __forceinline__ void pg_run(const PoolArgs &a, const BinSpace &ws, co
 // finish_z >= 0: the workgroups of that grid.z slice chain the vertex tiles' sums to grad_verts (256 vertices each); gather_tasks
 // = the runs of all maps (0: no map wants a gradient)
 // (RG: the finish role's slice is one row of workgroups over the union, blockIdx.y = 0)
-template <bool RG>
+template <bool RG, bool MX>
 __global__ __launch_bounds__(PL_THREADS) void pool_bwd_grads_kernel(PoolArgs a, BinSpace ws, GatherPlan p, const float *grad_out,
                                                                     int gather_tasks, int finish_z, float *grad_verts)
 {
     __shared__ __attribute__((aligned(16))) float tile[PG_TILE + GEOM_WAVE];
     if ((int)blockIdx.z == finish_z) {
         if (RG && blockIdx.y) return;
-        pool_bwd_verts_finish_body<RG>(a, ws, grad_verts, blockIdx.y, (int)blockIdx.x * PL_THREADS + (int)threadIdx.x);
+        pool_bwd_verts_finish_body<RG, MX>(a, ws, grad_verts, blockIdx.y, (int)blockIdx.x * PL_THREADS + (int)threadIdx.x);
         return;
     }
     // an XCD gets CONSECUTIVE runs (gridDim.x is a multiple of 8) -- the 2 x 2 texels a vertex touches then meet in one L2 (its
@@ -755,15 +798,24 @@ __global__ __launch_bounds__(PL_THREADS) void pool_bwd_grads_kernel(PoolArgs a, 
 
 // The launch arguments of every entry point, checked.  ld: floats between two vertex rows of the pooled features / of their
 // gradient (0 = the pooled width).  todo = false: an empty batch, nothing to launch (the return value is then 0).
-int fill_args(PoolArgs &a, bool &todo, int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos, int levels,
+// The camera of a launch: the (cam_mat, cam_pos) pair, or -- mx -- the [b,16] projection matrices (the pair is then unused).
+struct CamIn {
+    const float *cam_mat, *cam_pos, *proj;
+    bool mx;
+};
+static inline CamIn camera(const float *cam_mat, const float *cam_pos) { return CamIn{cam_mat, cam_pos, nullptr, false}; }
+static inline CamIn matrices(const float *proj) { return CamIn{nullptr, nullptr, proj, true}; }
+
+int fill_args(PoolArgs &a, bool &todo, int b, int nv, const float *verts, const CamIn &cam, int levels,
               const float *const *blocks, const int *channels, const int *dims, int64_t ld)
 {
     todo = false;
+    const float *cam_mat = cam.cam_mat, *cam_pos = cam.cam_pos;
     if (b < 0 || nv < 0 || levels < 0 || levels > GEOM_POOL_MAX_LEVELS) return GEOM_EINVAL;
-    if (!verts || !cam_mat || !cam_pos || (levels > 0 && (!blocks || !channels || !dims))) return GEOM_EINVAL;
+    if (!verts || (cam.mx ? !cam.proj : (!cam_mat || !cam_pos)) || (levels > 0 && (!blocks || !channels || !dims))) return GEOM_EINVAL;
     if (b > 65535 || (size_t)((nv + PL_VERTS - 1) / PL_VERTS) * b * PL_MAX_CHUNKS > (size_t)INT_MAX - 8) return GEOM_ETOOBIG;
     a.vert_mesh = a.vert_list = a.vert_off = nullptr;
-    a.verts = verts, a.cam_mat = cam_mat, a.cam_pos = cam_pos, a.levels = levels, a.b = b, a.nv = nv, a.ctot = 0, a.chunks = 0;
+    a.verts = verts, a.cam_pos = cam_pos, a.levels = levels, a.b = b, a.nv = nv, a.ctot = 0, a.chunks = 0;
     for (int l = 0; l < levels; ++l) {
         if (!blocks[l] || channels[l] <= 0 || dims[l] <= 0) return GEOM_EINVAL;
         if ((size_t)channels[l] * dims[l] * dims[l] * 4 > (size_t)INT_MAX) return GEOM_ETOOBIG; // (a mesh's planes as one buffer)
@@ -775,10 +827,11 @@ int fill_args(PoolArgs &a, bool &todo, int b, int nv, const float *verts, const 
     if (ld && (ld < a.ctot || ld > INT_MAX)) return GEOM_EINVAL;
     a.ld = ld ? (int)ld : a.ctot;
     a.zc = a.chunks < PL_MAX_CHUNKS ? a.chunks : PL_MAX_CHUNKS;
+    if (cam.mx) a.proj = cam.proj;
+    else a.cam_mat = cam_mat;
     todo = true;
     return 0;
 }
-
 } // namespace
 
 // out_ld: floats between two vertex rows of `out` (0 = the pooled width: a contiguous [b,nv,sum channels] tensor; larger: the
@@ -786,14 +839,14 @@ int fill_args(PoolArgs &a, bool &todo, int b, int nv, const float *verts, const 
 // n_fronts: up to two tensors fronts[f] [b, nv, widths[f]] (contiguous) copied into columns [cols[f], cols[f] + widths[f]) of the
 // wide buffer `buf` (row pitch out_ld, `out` = buf + the pooled features' first column) by the same launch: what the caller
 // concatenates in front of the pooled features (GEOMetrics.py:123,128; models.py:241)
-extern "C" int geom_pool_features_fwd_fronts_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
-                                                 int levels, const float *const *blocks, const int *channels, const int *dims,
-                                                 float *out, int64_t out_ld, int n_fronts, const float *const *fronts,
-                                                 const int *widths, const int *cols, float *buf, void *stream)
+template <bool MX>
+static int launch_fwd_fronts(int b, int nv, const float *verts, const CamIn &cam, int levels, const float *const *blocks,
+                             const int *channels, const int *dims, float *out, int64_t out_ld, int n_fronts,
+                             const float *const *fronts, const int *widths, const int *cols, float *buf, void *stream)
 {
     PoolArgs a;
     bool todo;
-    if (int rc = fill_args(a, todo, b, nv, verts, cam_mat, cam_pos, levels, blocks, channels, dims, out_ld); rc || !todo) return rc;
+    if (int rc = fill_args(a, todo, b, nv, verts, cam, levels, blocks, channels, dims, out_ld); rc || !todo) return rc;
     if (!out) return GEOM_EINVAL;
     PoolFronts fr{};
     fr.work_blocks = (int)pool_grid(a);
@@ -807,17 +860,9 @@ extern "C" int geom_pool_features_fwd_fronts_f32(int b, int nv, const float *ver
         extra += (int)blocks;
     }
     fr.first_block[n_fronts] = extra, fr.count = n_fronts, fr.dst = buf;
-    hipLaunchKernelGGL(pool_fwd_kernel<false>, dim3(fr.work_blocks + extra), dim3(PL_THREADS), 0, static_cast<hipStream_t>(stream), a, out, fr);
+    const dim3 grid(fr.work_blocks + extra);
+    hipLaunchKernelGGL((pool_fwd_kernel<false, MX>), grid, dim3(PL_THREADS), 0, static_cast<hipStream_t>(stream), a, out, fr);
     return geom::launch_status();
-}
-
-// the same with nothing in front
-extern "C" int geom_pool_features_fwd_ld_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
-                                             int levels, const float *const *blocks, const int *channels, const int *dims,
-                                             float *out, int64_t out_ld, void *stream)
-{
-    return geom_pool_features_fwd_fronts_f32(b, nv, verts, cam_mat, cam_pos, levels, blocks, channels, dims, out, out_ld, 0, nullptr,
-                                             nullptr, nullptr, nullptr, stream);
 }
 
 // The workspace at `base` (only its addresses are formed here; a null base serves the size query) and its size in bytes: the
@@ -851,14 +896,8 @@ static BinLayout pool_ws_layout(int b, int nv, int levels, const int *dims, void
     return lay;
 }
 
-extern "C" size_t geom_pool_features_bwd_workspace_bytes(int b, int nv, int levels, const int *dims)
-{
-    if (b <= 0 || nv <= 0 || levels <= 0 || levels > GEOM_POOL_MAX_LEVELS || !dims) return 0;
-    return pool_ws_layout(b, nv, levels, dims, nullptr).bytes;
-}
-
 // the two launches of a backward pass from checked arguments (a.vert_* set: the ragged instantiations)
-template <bool RG>
+template <bool RG, bool MX>
 static int launch_bwd(PoolArgs &a, const int *dims, const float *grad_out, float *const *grad_blocks, float *grad_verts, void *workspace,
                       size_t workspace_bytes, void *stream)
 {
@@ -879,29 +918,15 @@ static int launch_bwd(PoolArgs &a, const int *dims, const float *grad_out, float
     if (plan.max_parts > 65534 || (size_t)nv * a.ld * 4 > (size_t)INT_MAX) return GEOM_ETOOBIG;
     const int bin_blocks = any_map ? levels * b : 0;
     const unsigned verts_blocks = grad_verts ? pool_grid(a, RG) : 0;
-    hipLaunchKernelGGL(pool_bwd_lists_kernel<RG>, dim3(bin_blocks + verts_blocks), dim3(PL_THREADS), 0, s, a, lay.ws, grad_out, bin_blocks,
+    hipLaunchKernelGGL((pool_bwd_lists_kernel<RG, MX>), dim3(bin_blocks + verts_blocks), dim3(PL_THREADS), 0, s, a, lay.ws, grad_out, bin_blocks,
                        (int)verts_blocks);
     const int gather_tasks = any_map ? plan.first_task[levels] : 0;
     const int parts = any_map ? plan.max_parts : 0;
     const int finish_blocks = grad_verts ? (nv + PL_THREADS - 1) / PL_THREADS : 0; // the finish role's slice needs this many in x
     const unsigned gx = geom::xcd_run_grid(gather_tasks > finish_blocks ? gather_tasks : finish_blocks);
-    hipLaunchKernelGGL(pool_bwd_grads_kernel<RG>, dim3(gx, b, parts + (grad_verts ? 1 : 0)), dim3(PL_THREADS), 0, s, a, lay.ws, plan,
+    hipLaunchKernelGGL((pool_bwd_grads_kernel<RG, MX>), dim3(gx, b, parts + (grad_verts ? 1 : 0)), dim3(PL_THREADS), 0, s, a, lay.ws, plan,
                        grad_out, gather_tasks, grad_verts ? parts : -1, grad_verts);
     return geom::launch_status();
-}
-
-// grad_ld: floats between two vertex rows of `grad_out` (0 = the pooled width; larger: the gradient is read in place out of a
-// column slice of a wider buffer -- the input gradient of the deformation block's first product)
-extern "C" int geom_pool_features_bwd_ld_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
-                                             int levels, const float *const *blocks, const int *channels, const int *dims,
-                                             const float *grad_out, int64_t grad_ld, float *const *grad_blocks, float *grad_verts,
-                                             void *workspace, size_t workspace_bytes, void *stream)
-{
-    PoolArgs a;
-    bool todo;
-    if (int rc = fill_args(a, todo, b, nv, verts, cam_mat, cam_pos, levels, blocks, channels, dims, grad_ld); rc || !todo) return rc;
-    if (!grad_out) return GEOM_EINVAL;
-    return launch_bwd<false>(a, dims, grad_out, grad_blocks, grad_verts, workspace, workspace_bytes, stream);
 }
 
 // ---- the ragged launches: a union of b meshes with their own vertex counts (geom_hip.h) -------------------
@@ -919,20 +944,72 @@ static int ragged_limits(int b, int vt, int levels, const int *channels, const i
     return 0;
 }
 
-extern "C" int geom_pool_features_ragged_fwd_f32(int b, int vt, const float *verts, const int *vert_mesh, const int *vert_list,
-                                                 const float *cam_mat, const float *cam_pos, int levels, const float *const *blocks,
-                                                 const int *channels, const int *dims, float *out, int64_t out_ld, void *stream)
+template <bool MX>
+static int launch_ragged_fwd(int b, int vt, const float *verts, const int *vert_mesh, const int *vert_list, const CamIn &cam, int levels,
+                             const float *const *blocks, const int *channels, const int *dims, float *out, int64_t out_ld, void *stream)
 {
     if (int rc = ragged_limits(b, vt, levels, channels, dims)) return rc;
     PoolArgs a;
     bool todo;
-    if (int rc = fill_args(a, todo, b, vt, verts, cam_mat, cam_pos, levels, blocks, channels, dims, out_ld); rc || !todo) return rc;
+    if (int rc = fill_args(a, todo, b, vt, verts, cam, levels, blocks, channels, dims, out_ld); rc || !todo) return rc;
     if (!out || !vert_mesh || !vert_list) return GEOM_EINVAL;
     a.vert_mesh = vert_mesh, a.vert_list = vert_list;
     PoolFronts fr{};
     fr.work_blocks = (int)pool_grid(a, true);
-    hipLaunchKernelGGL(pool_fwd_kernel<true>, dim3(fr.work_blocks), dim3(PL_THREADS), 0, static_cast<hipStream_t>(stream), a, out, fr);
+    const dim3 grid(fr.work_blocks);
+    hipLaunchKernelGGL((pool_fwd_kernel<true, MX>), grid, dim3(PL_THREADS), 0, static_cast<hipStream_t>(stream), a, out, fr);
     return geom::launch_status();
+}
+
+// ---- the entry points.  This file is compiled TWICE: as it stands -- the camera entry points and the MX = false instantiations --
+// and through pooling_proj.hip, which defines GEOM_POOL_MATRIX_UNIT and includes it -- the matrix entry points and the MX = true
+// instantiations.  One code-object module per camera kind, because what the optimiser makes of a kernel depends on what else its
+// module holds: with the matrix instantiations beside it the camera route's pool_bwd_grads_kernel came out at 54 VGPRs for 53 (its
+// source unchanged), and the camera launches are to stay what they were (profiles/matrix_pooling.txt).
+#ifndef GEOM_POOL_MATRIX_UNIT
+extern "C" int geom_pool_features_fwd_fronts_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
+                                                 int levels, const float *const *blocks, const int *channels, const int *dims,
+                                                 float *out, int64_t out_ld, int n_fronts, const float *const *fronts,
+                                                 const int *widths, const int *cols, float *buf, void *stream)
+{
+    return launch_fwd_fronts<false>(b, nv, verts, camera(cam_mat, cam_pos), levels, blocks, channels, dims, out, out_ld, n_fronts, fronts, widths,
+                             cols, buf, stream);
+}
+
+// the same with nothing in front
+extern "C" int geom_pool_features_fwd_ld_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
+                                             int levels, const float *const *blocks, const int *channels, const int *dims,
+                                             float *out, int64_t out_ld, void *stream)
+{
+    return geom_pool_features_fwd_fronts_f32(b, nv, verts, cam_mat, cam_pos, levels, blocks, channels, dims, out, out_ld, 0, nullptr,
+                                             nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" size_t geom_pool_features_bwd_workspace_bytes(int b, int nv, int levels, const int *dims)
+{
+    if (b <= 0 || nv <= 0 || levels <= 0 || levels > GEOM_POOL_MAX_LEVELS || !dims) return 0;
+    return pool_ws_layout(b, nv, levels, dims, nullptr).bytes;
+}
+
+// grad_ld: floats between two vertex rows of `grad_out` (0 = the pooled width; larger: the gradient is read in place out of a
+// column slice of a wider buffer -- the input gradient of the deformation block's first product)
+extern "C" int geom_pool_features_bwd_ld_f32(int b, int nv, const float *verts, const float *cam_mat, const float *cam_pos,
+                                             int levels, const float *const *blocks, const int *channels, const int *dims,
+                                             const float *grad_out, int64_t grad_ld, float *const *grad_blocks, float *grad_verts,
+                                             void *workspace, size_t workspace_bytes, void *stream)
+{
+    PoolArgs a;
+    bool todo;
+    if (int rc = fill_args(a, todo, b, nv, verts, camera(cam_mat, cam_pos), levels, blocks, channels, dims, grad_ld); rc || !todo) return rc;
+    if (!grad_out) return GEOM_EINVAL;
+    return launch_bwd<false, false>(a, dims, grad_out, grad_blocks, grad_verts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int geom_pool_features_ragged_fwd_f32(int b, int vt, const float *verts, const int *vert_mesh, const int *vert_list,
+                                                 const float *cam_mat, const float *cam_pos, int levels, const float *const *blocks,
+                                                 const int *channels, const int *dims, float *out, int64_t out_ld, void *stream)
+{
+    return launch_ragged_fwd<false>(b, vt, verts, vert_mesh, vert_list, camera(cam_mat, cam_pos), levels, blocks, channels, dims, out, out_ld, stream);
 }
 
 extern "C" size_t geom_pool_features_ragged_bwd_workspace_bytes(int b, int vt, int levels, const int *dims)
@@ -950,10 +1027,10 @@ extern "C" int geom_pool_features_ragged_bwd_f32(int b, int vt, const float *ver
     if (int rc = ragged_limits(b, vt, levels, channels, dims)) return rc;
     PoolArgs a;
     bool todo;
-    if (int rc = fill_args(a, todo, b, vt, verts, cam_mat, cam_pos, levels, blocks, channels, dims, grad_ld); rc || !todo) return rc;
+    if (int rc = fill_args(a, todo, b, vt, verts, camera(cam_mat, cam_pos), levels, blocks, channels, dims, grad_ld); rc || !todo) return rc;
     if (!grad_out || !vert_mesh || !vert_list || !vert_off) return GEOM_EINVAL;
     a.vert_mesh = vert_mesh, a.vert_list = vert_list, a.vert_off = vert_off;
-    return launch_bwd<true>(a, dims, grad_out, grad_blocks, grad_verts, workspace, workspace_bytes, stream);
+    return launch_bwd<true, false>(a, dims, grad_out, grad_blocks, grad_verts, workspace, workspace_bytes, stream);
 }
 
 // ---- camera from (azimuth deg, elevation deg, distance): reference utils.py:286-313 -----------------------------------------
@@ -1003,3 +1080,50 @@ extern "C" int geom_camera_info_f32(int b, const float *param, float *cam_mat, f
     hipLaunchKernelGGL(camera_info_kernel, dim3((b + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), b, param, cam_mat, cam_pos);
     return geom::launch_status();
 }
+
+#else // GEOM_POOL_MATRIX_UNIT
+// ---- the MATRIX launches (geom_hip.h): proj [b,16] in place of the camera pair, everything else as in the
+// four camera entry points above -- the same checks in the same order, the same workspace, the bodies' MX instantiations ---------
+extern "C" int geom_pool_features_proj_fwd_f32(int b, int nv, const float *verts, const float *proj, int levels,
+                                               const float *const *blocks, const int *channels, const int *dims, float *out,
+                                               int64_t out_ld, int n_fronts, const float *const *fronts, const int *widths,
+                                               const int *cols, float *buf, void *stream)
+{
+    return launch_fwd_fronts<true>(b, nv, verts, matrices(proj), levels, blocks, channels, dims, out, out_ld, n_fronts, fronts, widths, cols, buf,
+                             stream);
+}
+
+extern "C" int geom_pool_features_proj_bwd_f32(int b, int nv, const float *verts, const float *proj, int levels,
+                                               const float *const *blocks, const int *channels, const int *dims, const float *grad_out,
+                                               int64_t grad_ld, float *const *grad_blocks, float *grad_verts, void *workspace,
+                                               size_t workspace_bytes, void *stream)
+{
+    PoolArgs a;
+    bool todo;
+    if (int rc = fill_args(a, todo, b, nv, verts, matrices(proj), levels, blocks, channels, dims, grad_ld); rc || !todo) return rc;
+    if (!grad_out) return GEOM_EINVAL;
+    return launch_bwd<false, true>(a, dims, grad_out, grad_blocks, grad_verts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int geom_pool_features_ragged_proj_fwd_f32(int b, int vt, const float *verts, const int *vert_mesh, const int *vert_list,
+                                                      const float *proj, int levels, const float *const *blocks, const int *channels,
+                                                      const int *dims, float *out, int64_t out_ld, void *stream)
+{
+    return launch_ragged_fwd<true>(b, vt, verts, vert_mesh, vert_list, matrices(proj), levels, blocks, channels, dims, out, out_ld, stream);
+}
+
+extern "C" int geom_pool_features_ragged_proj_bwd_f32(int b, int vt, const float *verts, const int *vert_mesh, const int *vert_list,
+                                                      const int *vert_off, const float *proj, int levels, const float *const *blocks,
+                                                      const int *channels, const int *dims, const float *grad_out, int64_t grad_ld,
+                                                      float *const *grad_blocks, float *grad_verts, void *workspace,
+                                                      size_t workspace_bytes, void *stream)
+{
+    if (int rc = ragged_limits(b, vt, levels, channels, dims)) return rc;
+    PoolArgs a;
+    bool todo;
+    if (int rc = fill_args(a, todo, b, vt, verts, matrices(proj), levels, blocks, channels, dims, grad_ld); rc || !todo) return rc;
+    if (!grad_out || !vert_mesh || !vert_list || !vert_off) return GEOM_EINVAL;
+    a.vert_mesh = vert_mesh, a.vert_list = vert_list, a.vert_off = vert_off;
+    return launch_bwd<true, true>(a, dims, grad_out, grad_blocks, grad_verts, workspace, workspace_bytes, stream);
+}
+#endif

@@ -704,6 +704,59 @@ def concat_in_front(front, view):
     return torch.cat((front, view), dim=-1)
 
 
+def _pool_forward_operands(v, headroom, blocks):
+    """What the two batched pooling nodes (PoolFeatures, PoolFeaturesProj) hand their forward launch besides the camera, for checked
+    vertices v [B,V,3]: (maps, channels, dims, their number, out, out_ld, (n_fronts, fronts, widths, cols, buf)).  headroom: an int or
+    (headroom, fronts), see PoolFeatures.forward."""
+    fronts = ()
+    if isinstance(headroom, (tuple, list)):
+        headroom, fronts = headroom
+    headroom = int(headroom or 0)
+    blks = [_f32(b, "block", 4) for b in blocks]
+    b, nv, _ = v.shape
+    for blk in blks:
+        if blk.shape[0] != b or blk.shape[2] != blk.shape[3]:
+            raise RuntimeError("feature maps must be [B, C, dim, dim] with the vertex batch size")
+    n = len(blks)
+    chans = (ctypes.c_int * n)(*[t.shape[1] for t in blks])
+    dims = (ctypes.c_int * n)(*[t.shape[2] for t in blks])
+    ctot = sum(t.shape[1] for t in blks)
+    srcs, own = [], []       # (contiguous front, its first column); (column, front) of those that are the caller's own tensor
+    if fronts:
+        col = 0
+        for t in fronts:
+            if not (torch.is_tensor(t) and t.dim() == 3 and tuple(t.shape[:2]) == (b, nv) and t.is_cuda and t.device == v.device
+                    and t.dtype == torch.float32):
+                raise RuntimeError("fronts must be fp32 [B,V,*] tensors on the meshes' device")
+            c = t.detach().contiguous()
+            srcs.append((c, col))
+            if c.data_ptr() == t.data_ptr():       # (a copy made here is not what the caller will hand to the concatenation)
+                own.append((col, t))
+            col += t.shape[2]
+        if col != headroom or len(srcs) > 2:
+            raise RuntimeError("at most two fronts, whose widths add up to the headroom")
+    if headroom > 0:      # the features as the trailing columns of a wider buffer: see concat_in_front
+        buf = torch.empty(b, nv, headroom + ctot, dtype=torch.float32, device=v.device)
+        out = buf[..., headroom:]
+        rec = _register_headroom(buf, headroom)
+        for col, t in own:
+            rec.place(col, t)
+    else:
+        buf, out = None, torch.empty(b, nv, ctot, dtype=torch.float32, device=v.device)
+    m = len(srcs)
+    front_args = (m, [t for t, _ in srcs], (ctypes.c_int * m)(*[t.shape[2] for t, _ in srcs]), (ctypes.c_int * m)(*[c for _, c in srcs]), buf)
+    return blks, chans, dims, n, out, headroom + ctot if headroom > 0 else 0, front_args
+
+
+def _pitched_gradient(grad_out, rows_uniform):
+    """(g, pitch): grad_out [..., V, C] in place when it is a column slice of a wider row-major buffer (the block's input gradient;
+    rows_uniform: every vertex row, across the leading dimension too, lies one pitch after the last), else a contiguous copy."""
+    ctot = grad_out.shape[-1]
+    if grad_out.stride(-1) == 1 and grad_out.stride(-2) >= ctot and rows_uniform and grad_out.is_cuda and grad_out.dtype == torch.float32:
+        return grad_out, grad_out.stride(-2)
+    return grad_out.contiguous(), ctot
+
+
 class PoolFeatures(torch.autograd.Function):
     """Bilinear pooling of the image feature maps at the projected vertex positions (reference
     batched_pooling, utils.py:316-389): one kernel forward, one backward (texel scatters + closed-form
@@ -715,48 +768,12 @@ class PoolFeatures(torch.autograd.Function):
         (headroom, fronts): also up to two [B,V,*] tensors, left to right as they will stand in front of the features (their
         widths add up to the headroom), which the launch copies there -- concat_in_front / the deformation block then find them
         in place (the gradient still flows through those nodes: the tensors are not inputs of this one)."""
-        fronts = ()
-        if isinstance(headroom, (tuple, list)):
-            headroom, fronts = headroom
-        headroom = int(headroom or 0)
         v = _f32(verts, "verts_pos", 3, 3)
         cam_mat = _f32(cam_mat, "cam_mat", 3, 3)
         cam_pos = _f32(cam_pos, "cam_pos", 2, 3)
-        blks = [_f32(b, "block", 4) for b in blocks]
+        blks, chans, dims, n, out, out_ld, front_args = _pool_forward_operands(v, headroom, blocks)
         b, nv, _ = v.shape
-        for blk in blks:
-            if blk.shape[0] != b or blk.shape[2] != blk.shape[3]:
-                raise RuntimeError("feature maps must be [B, C, dim, dim] with the vertex batch size")
-        n = len(blks)
-        chans = (ctypes.c_int * n)(*[t.shape[1] for t in blks])
-        dims = (ctypes.c_int * n)(*[t.shape[2] for t in blks])
-        ctot = sum(t.shape[1] for t in blks)
-        srcs, own = [], []       # (contiguous front, its first column); (column, front) of those that are the caller's own tensor
-        if fronts:
-            col = 0
-            for t in fronts:
-                if not (torch.is_tensor(t) and t.dim() == 3 and tuple(t.shape[:2]) == (b, nv) and t.is_cuda and t.device == v.device
-                        and t.dtype == torch.float32):
-                    raise RuntimeError("fronts must be fp32 [B,V,*] tensors on the meshes' device")
-                c = t.detach().contiguous()
-                srcs.append((c, col))
-                if c.data_ptr() == t.data_ptr():       # (a copy made here is not what the caller will hand to the concatenation)
-                    own.append((col, t))
-                col += t.shape[2]
-            if col != headroom or len(srcs) > 2:
-                raise RuntimeError("at most two fronts, whose widths add up to the headroom")
-        if headroom > 0:      # the features as the trailing columns of a wider buffer: see concat_in_front
-            buf = torch.empty(b, nv, headroom + ctot, dtype=torch.float32, device=v.device)
-            out = buf[..., headroom:]
-            rec = _register_headroom(buf, headroom)
-            for col, t in own:
-                rec.place(col, t)
-        else:
-            buf, out = None, torch.empty(b, nv, ctot, dtype=torch.float32, device=v.device)
-        m = len(srcs)
-        _lib.call("geom_pool_features_fwd_fronts_f32", b, nv, v, cam_mat, cam_pos, n, blks, chans, dims, out,
-                  headroom + ctot if headroom > 0 else 0, m, [t for t, _ in srcs],
-                  (ctypes.c_int * m)(*[t.shape[2] for t, _ in srcs]), (ctypes.c_int * m)(*[c for _, c in srcs]), buf)
+        _lib.call("geom_pool_features_fwd_fronts_f32", b, nv, v, cam_mat, cam_pos, n, blks, chans, dims, out, out_ld, *front_args)
         ctx.save_for_backward(v, cam_mat, cam_pos, *blks)
         ctx.meta = (chans, dims, n)
         return out
@@ -845,6 +862,102 @@ class RaggedPoolFeatures(torch.autograd.Function):
         _lib.call("geom_pool_features_ragged_bwd_f32", b, vt, v, vert_mesh, vert_list, vert_off, cam_mat, cam_pos, n, blks, chans, dims,
                   g, g_ld if g_ld != ctot else 0, gblks, gverts, ws, ws_bytes)
         return (gverts, None, None, None, None, None) + tuple(gblks)
+
+
+class PoolFeaturesProj(torch.autograd.Function):
+    """PoolFeatures with the old driver's PROJECTION MATRICES in place of the camera pair (reference old_GEOMetrics/utils.py:379-427
+    pooling(blocks, verts_pos, matrix)): proj [B,4,4] fp32, row-major, detached -- data, no gradient.  The same
+    kernels' bodies instantiated for the matrix projection: one launch forward, two backward; headroom as PoolFeatures takes it."""
+
+    @staticmethod
+    def forward(ctx, verts, proj, headroom, *blocks):
+        v = _f32(verts, "verts_pos", 3, 3)
+        proj = _proj_matrices(proj, v.shape[0], v.device)
+        blks, chans, dims, n, out, out_ld, front_args = _pool_forward_operands(v, headroom, blocks)
+        b, nv, _ = v.shape
+        _lib.call("geom_pool_features_proj_fwd_f32", b, nv, v, proj, n, blks, chans, dims, out, out_ld, *front_args)
+        ctx.save_for_backward(v, proj, *blks)
+        ctx.meta = (chans, dims, n)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        v, proj = ctx.saved_tensors[:2]
+        blks = ctx.saved_tensors[2:]
+        chans, dims, n = ctx.meta
+        b, nv, _ = v.shape
+        ctot = grad_out.shape[2]
+        g, g_ld = _pitched_gradient(grad_out, grad_out.stride(0) == nv * grad_out.stride(1))
+        need_blocks = [ctx.needs_input_grad[3 + i] for i in range(n)]
+        gblks = [torch.empty_like(t) if need else None for t, need in zip(blks, need_blocks)]
+        gverts = torch.empty_like(v) if ctx.needs_input_grad[0] else None
+        ws, ws_bytes = None, 0
+        if any(need_blocks) or gverts is not None:       # (the camera route's workspace: the layout knows no camera)
+            ws_bytes = _lib.lib().geom_pool_features_bwd_workspace_bytes(b, nv, n, dims)
+            ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=v.device)
+        _lib.call("geom_pool_features_proj_bwd_f32", b, nv, v, proj, n, blks, chans, dims, g, g_ld if g_ld != ctot else 0, gblks, gverts,
+                  ws, ws_bytes)
+        return (gverts, None, None) + tuple(gblks)
+
+
+class RaggedPoolFeaturesProj(torch.autograd.Function):
+    """RaggedPoolFeatures with proj [B,4,4] in place of the camera pair: row v of the [Vt, sum C] result is
+    PoolFeaturesProj's row for vertex v as a vertex of mesh vert_mesh[v] alone, bit for bit."""
+
+    @staticmethod
+    def forward(ctx, verts, vert_mesh, vert_list, vert_off, proj, *blocks):
+        v = _f32(verts, "verts_union", 2, 3)
+        vert_mesh = _lib.require(vert_mesh, "vert_mesh", torch.int32, 1)
+        vert_list = _lib.require(vert_list, "vert_list", torch.int32, 1)
+        vert_off = _lib.require(vert_off, "vert_off", torch.int32, 1)
+        blks = [_f32(b, "block", 4) for b in blocks]
+        vt, b = v.shape[0], vert_off.shape[0] - 1
+        proj = _proj_matrices(proj, b, v.device)
+        if vt == 0 or b <= 0 or not blks:
+            raise RuntimeError("the union must hold a vertex, the batch a mesh and a feature map (got %d vertices, %d meshes, %d maps)"
+                               % (vt, b, len(blks)))
+        if vert_mesh.shape[0] != vt or vert_list.shape[0] != vt:
+            raise RuntimeError("vert_mesh and vert_list must hold one entry per vertex of the union (%d)" % vt)
+        for blk in blks:
+            if blk.shape[0] != b or blk.shape[2] != blk.shape[3]:
+                raise RuntimeError("feature maps must be [B, C, dim, dim] with the matrices' batch size")
+        n = len(blks)
+        chans = (ctypes.c_int * n)(*[t.shape[1] for t in blks])
+        dims = (ctypes.c_int * n)(*[t.shape[2] for t in blks])
+        out = torch.empty(vt, sum(t.shape[1] for t in blks), dtype=torch.float32, device=v.device)
+        _lib.call("geom_pool_features_ragged_proj_fwd_f32", b, vt, v, vert_mesh, vert_list, proj, n, blks, chans, dims, out, 0)
+        ctx.save_for_backward(v, vert_mesh, vert_list, vert_off, proj, *blks)
+        ctx.meta = (chans, dims, n)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        v, vert_mesh, vert_list, vert_off, proj = ctx.saved_tensors[:5]
+        blks = ctx.saved_tensors[5:]
+        chans, dims, n = ctx.meta
+        vt, b = v.shape[0], proj.shape[0]
+        ctot = grad_out.shape[1]
+        g, g_ld = _pitched_gradient(grad_out, True)
+        need_blocks = [ctx.needs_input_grad[5 + i] for i in range(n)]
+        gblks = [torch.empty_like(t) if need else None for t, need in zip(blks, need_blocks)]
+        gverts = torch.empty_like(v) if ctx.needs_input_grad[0] else None
+        ws, ws_bytes = None, 0
+        if any(need_blocks) or gverts is not None:
+            ws_bytes = _lib.lib().geom_pool_features_ragged_bwd_workspace_bytes(b, vt, n, dims)
+            ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=v.device)
+        _lib.call("geom_pool_features_ragged_proj_bwd_f32", b, vt, v, vert_mesh, vert_list, vert_off, proj, n, blks, chans, dims,
+                  g, g_ld if g_ld != ctot else 0, gblks, gverts, ws, ws_bytes)
+        return (gverts, None, None, None, None) + tuple(gblks)
+
+
+def _proj_matrices(proj, b, device):
+    """proj as the matrix launches take it: fp32 [b,4,4] on `device`, contiguous."""
+    proj = _f32(proj, "the projection matrices", 3, 4)
+    if tuple(proj.shape) != (b, 4, 4):
+        raise RuntimeError("the projection matrices must be [B,4,4] with one matrix per mesh (got %s for %d meshes)" % (tuple(proj.shape), b))
+    if proj.device != device:
+        raise RuntimeError("the projection matrices live on %s, the vertices on %s" % (proj.device, device))
+    return proj
 
 
 class SegmentMax(torch.autograd.Function):
@@ -1211,7 +1324,8 @@ class VertexHead(torch.autograd.Function):
 
 
 __all__ = ["face_areas", "device_sum", "SampleFaces", "GatherSqDistSum", "PointToTriangleSum", "SurfaceLoss",
-           "Laplacian", "EdgeSqLenSum", "PoolFeatures", "RaggedPoolFeatures", "VertexHead", "SegmentMax", "manual_seed", "set_rng_state",
+           "Laplacian", "EdgeSqLenSum", "PoolFeatures", "RaggedPoolFeatures", "PoolFeaturesProj", "RaggedPoolFeaturesProj",
+           "VertexHead", "SegmentMax", "manual_seed", "set_rng_state",
            "draw_samples", "GtIndex", "ScanPrep", "RaggedSurfaceLoss", "draw_samples_ragged", "tri_distance_ragged",
            "chamfer_nn", "tri_distance_indexed"]
 

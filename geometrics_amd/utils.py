@@ -533,6 +533,50 @@ def batch_camera_info(param):
     return torch.stack(rows, dim=1), cam_pos
 
 
+def _is_proj(img_info):
+    """Whether img_info is the old driver's projection matrices, a [B,4,4] tensor ([B,3] and longer rows are camera parameters)."""
+    return torch.is_tensor(img_info) and img_info.dim() == 3
+
+
+def _check_proj(proj, b, device, what):
+    """The matrix route's argument checks, before any launch: fp32 [b,4,4] on the vertices' device."""
+    if proj.dim() != 3 or tuple(proj.shape[1:]) != (4, 4):
+        raise RuntimeError("the projection matrices must be a [B,4,4] tensor, one row-major 4 x 4 matrix per %s (got %s)"
+                           % (what, str(tuple(proj.shape))))
+    if proj.dtype != torch.float32:
+        raise RuntimeError("the projection matrices must be fp32 (got %s)" % proj.dtype)
+    if proj.shape[0] != b:
+        raise RuntimeError("one projection matrix per %s: got %d for %d" % (what, proj.shape[0], b))
+    if proj.device != device:
+        raise RuntimeError("the projection matrices live on %s, the vertices on %s" % (proj.device, device))
+    return proj.detach()
+
+
+def pooling(blocks, verts_pos, matrix):
+    """The old driver's pooling(blocks, verts_pos, matrix) (reference old_GEOMetrics/utils.py:379-427), name and argument order:
+    blocks, the fp32 feature maps [C_l, d, d] of ONE image; verts_pos [V,3] fp32; matrix [4,4] fp32, the image's projection matrix
+    as the render script wrote it (batch['mats']: projection x model-view).  Returns [V, sum C], differentiable in the maps and
+    in the positions; the matrix is data and gets no gradient.  q = matrix . (x, y, z, 1), ys = (q0 / q3 + 1) / 2, xs = 1 -
+    (q1 / q3 + 1) / 2 (row 2 of the matrix is never read), then batched_pooling's clamp, weights and texels (DESIGN.md section
+    4h).  The batched matrix route at b = 1 on VIEWS of the arguments: no copy of a map, one launch forward, two backward."""
+    blocks = list(blocks)
+    for blk in blocks:
+        if not torch.is_tensor(blk) or blk.dtype != torch.float32 or blk.dim() != 3 or blk.shape[1] != blk.shape[2]:
+            raise RuntimeError("feature maps must be fp32 [C, dim, dim] tensors with square planes, the maps of one image (got %s)"
+                               % ("%s %s" % (blk.dtype, tuple(blk.shape)) if torch.is_tensor(blk) else type(blk).__name__))
+    if not torch.is_tensor(verts_pos) or verts_pos.dtype != torch.float32 or verts_pos.dim() != 2 or verts_pos.shape[1] != 3:
+        raise RuntimeError("verts_pos must be an fp32 [V,3] tensor (got %s)"
+                           % ("%s %s" % (verts_pos.dtype, tuple(verts_pos.shape)) if torch.is_tensor(verts_pos)
+                              else type(verts_pos).__name__))
+    if not torch.is_tensor(matrix) or matrix.dim() != 2:
+        raise RuntimeError("matrix must be a [4,4] tensor, the image's projection matrix (got %s)"
+                           % (str(tuple(matrix.shape)) if torch.is_tensor(matrix) else type(matrix).__name__))
+    proj = _check_proj(matrix[None], 1, verts_pos.device, "image")
+    if not blocks:
+        raise RuntimeError("pooling needs at least one feature map")
+    return ops.PoolFeaturesProj.apply(verts_pos[None], proj, 0, *[blk[None] for blk in blocks])[0]
+
+
 def batched_pooling(blocks, verts_pos, img_info, headroom=0, fronts=None):
     """[B,V,sum C] image features bilinearly pooled from the encoder maps `blocks` (each [B,C,d,d]) at the
     pixels the vertices project to (reference utils.py:316-389).  Differentiable in the maps and in the
@@ -544,9 +588,14 @@ def batched_pooling(blocks, verts_pos, img_info, headroom=0, fronts=None):
     features -- e.g. (positions, previous_features) -- which the pooling launch then copies into place itself (the later
     concatenations find them there and copy nothing; gradients flow as before)."""
     # img_info: the camera parameters [B,3], or -- a driver that pools three times per step with the same cameras
-    # (GEOMetrics.py:118-128) -- the (cam_mat, cam_pos) pair batch_camera_info(img_info) returned once
-    cam_mat, cam_pos = img_info if isinstance(img_info, (tuple, list)) else batch_camera_info(img_info)
+    # (GEOMetrics.py:118-128) -- the (cam_mat, cam_pos) pair batch_camera_info(img_info) returned once, or -- the old driver's
+    # data (batch['mats']) -- an fp32 [B,4,4] tensor of projection matrices: the matrix route, see pooling()
     room = int(headroom) if not fronts else (int(headroom), tuple(fronts))
+    if _is_proj(img_info):
+        if not torch.is_tensor(verts_pos) or verts_pos.dim() != 3:
+            raise RuntimeError("verts_pos must be a [B,V,3] tensor")
+        return ops.PoolFeaturesProj.apply(verts_pos, _check_proj(img_info, verts_pos.shape[0], verts_pos.device, "mesh"), room, *blocks)
+    cam_mat, cam_pos = img_info if isinstance(img_info, (tuple, list)) else batch_camera_info(img_info)
     return ops.PoolFeatures.apply(verts_pos, cam_mat.detach(), cam_pos.detach(), room, *blocks)
 
 
@@ -554,7 +603,8 @@ def ragged_pooling(blocks, verts_union, vert_mesh, img_info):
     """batched_pooling for a RAGGED batch: B meshes with their own vertex counts, as after an adaptive split, on ONE union mesh
     (DESIGN.md section 4f).  blocks: the encoder maps, each [B,C,d,d] fp32; verts_union [Vt,3] fp32: the union's vertices in any
     order (after split_info on a union the new vertices stand at the end: the meshes interleave); vert_mesh [Vt] int32 or int64:
-    the mesh of every vertex; img_info: [B,3] camera parameters or batch_camera_info's (cam_mat, cam_pos), as batched_pooling
+    the mesh of every vertex; img_info: [B,3] camera parameters, batch_camera_info's (cam_mat, cam_pos) or an fp32 [B,4,4] tensor
+    of projection matrices (the old driver's batch['mats']: the matrix route, ops.RaggedPoolFeaturesProj), as batched_pooling
     takes it.  Returns [Vt, sum C]: row v is batched_pooling's row for that vertex as a vertex of mesh vert_mesh[v] alone (maps
     blocks[l][m:m+1], camera m), bit for bit.  Differentiable in the maps and in the positions, ONE autograd node
     (ops.RaggedPoolFeatures), one launch forward and two backward, no host read once the grouping of the vertices is cached
@@ -576,6 +626,15 @@ def ragged_pooling(blocks, verts_union, vert_mesh, img_info):
         raise RuntimeError("vert_mesh must be a one-dimensional int32 or int64 tensor of mesh ids")
     if vert_mesh.shape[0] != verts_union.shape[0]:
         raise RuntimeError("vert_mesh holds %d ids, the union %d vertices" % (vert_mesh.shape[0], verts_union.shape[0]))
+    if _is_proj(img_info):
+        b = int(img_info.shape[0])
+        proj = _check_proj(img_info, b, verts_union.device, "mesh")
+        for blk in blocks:
+            if blk.shape[0] != b:
+                raise RuntimeError("a feature map holds %d images, the matrices are %d" % (blk.shape[0], b))
+        ids, _ = ragged.mesh_counts(vert_mesh, b)
+        vert_list, vert_off = ragged.group_vertices(vert_mesh, b)
+        return ops.RaggedPoolFeaturesProj.apply(verts_union, ids, vert_list, vert_off, proj, *blocks)
     cam_mat, cam_pos = img_info if isinstance(img_info, (tuple, list)) else batch_camera_info(img_info)
     b = int(cam_pos.shape[0])
     if cam_mat.dtype != torch.float32 or cam_pos.dtype != torch.float32:

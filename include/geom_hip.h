@@ -864,6 +864,35 @@ int geom_pool_features_ragged_bwd_f32(int b, int vt, const float *verts, const i
                                       const float *const *blocks, const int *channels, const int *dims, const float *grad_out,
                                       int64_t grad_ld, float *const *grad_blocks, float *grad_verts, void *workspace,
                                       size_t workspace_bytes, void *stream);
+/* PROJECTION-MATRIX pooling (the old driver's pooling(blocks, verts_pos, matrix), old utils.py:379-427): the
+ * four calls above with proj [b,16] -- one row-major 4 x 4 matrix per mesh, fp32, projection x model-view as the render script
+ * wrote it -- in place of (cam_mat, cam_pos).  For vertex p = (x, y, z) of mesh m and M = proj[m], in fp32, in this order,
+ * uncontracted:
+ *     q0 = ((x*M[0][0] + y*M[0][1]) + z*M[0][2]) + M[0][3]        (q1, q3 likewise from rows 1 and 3)
+ *     ys = (q0 / q3 + 1) / 2,    xs = 1 - (q1 / q3 + 1) / 2
+ * and (xs, ys) then go through the same clamp, weights and texel indexing as above (xs indexes the first plane axis).  ROW 2 OF
+ * THE MATRIX IS NEVER READ; there is no 0.57 and there are no focal constants.  Backward: the per-chunk sums sx, sy of d loss /
+ * d (xs, ys) as above, chained by g0 = (0.5*sy)/q3, g1 = (-0.5*sx)/q3, g3 = -(g0*q0 + g1*q1)/q3, grad_verts[j] = (g0*M[0][j] +
+ * g1*M[1][j]) + g3*M[3][j]; sx == 0 && sy == 0 gives an exactly zero row (the clamp is a select).  The matrix gets no gradient.
+ * The workspace is the one of the camera calls -- geom_pool_features_bwd_workspace_bytes / geom_pool_features_ragged_bwd_
+ * workspace_bytes serve these: the layout does not depend on the camera's kind.  Codes and limits are those of the camera calls,
+ * looked at in the same order; a null proj is GEOM_EINVAL.  geom_pool_features_proj_fwd_f32 is the fronts form (n_fronts = 0:
+ * nothing in front). */
+int geom_pool_features_proj_fwd_f32(int b, int nv, const float *verts, const float *proj, int levels, const float *const *blocks,
+                                    const int *channels, const int *dims, float *out, int64_t out_ld, int n_fronts,
+                                    const float *const *fronts, const int *widths, const int *cols, float *buf, void *stream);
+int geom_pool_features_proj_bwd_f32(int b, int nv, const float *verts, const float *proj, int levels, const float *const *blocks,
+                                    const int *channels, const int *dims, const float *grad_out, int64_t grad_ld,
+                                    float *const *grad_blocks, float *grad_verts, void *workspace, size_t workspace_bytes,
+                                    void *stream);
+int geom_pool_features_ragged_proj_fwd_f32(int b, int vt, const float *verts, const int *vert_mesh, const int *vert_list,
+                                           const float *proj, int levels, const float *const *blocks, const int *channels,
+                                           const int *dims, float *out, int64_t out_ld, void *stream);
+int geom_pool_features_ragged_proj_bwd_f32(int b, int vt, const float *verts, const int *vert_mesh, const int *vert_list,
+                                           const int *vert_off, const float *proj, int levels, const float *const *blocks,
+                                           const int *channels, const int *dims, const float *grad_out, int64_t grad_ld,
+                                           float *const *grad_blocks, float *grad_verts, void *workspace, size_t workspace_bytes,
+                                           void *stream);
 
 /* ---- culled Chamfer scan inside the surface step (optional; NULL everywhere = the brute-force tiles) ------------------
  * The culled scan (geom_chamfer_nn_culled_f32) needs both clouds listed in a spatially coherent order, as an INDEX
